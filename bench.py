@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X self-play hot path (contract: see DESIGN.md, "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: it sets up, runs W warm-up and K timed steps, writes the outputs if asked and
+prints the line.  --full adds everything else below (the nested legs, the CPU baselines, `value_spread`).
+--dump-outputs DIR: what the timed path computed in its LAST timed step -- rank 0's SelfPlayResult of its batch (see
+selfplay_outputs; bitboards as float64 pairs of 32-bit halves) -- as DIR/<name>.npy in float32 / float64, at most 64 MB in
+all (beyond that a fixed sample of the games, DIR/games.npy says which).  The inputs are seeded: the same arguments give
+the same games in every run.
 
 Headline workload (BASELINE.json configs[2], the configuration the north star's metric is quoted on): per
 GPU, 1024 PV-MCTS self-play games of 8x8 Othello, 100 playouts per move, both colours searching, SLPolicy +
@@ -22,15 +29,15 @@ per SLPolicy evaluation) x the evaluations a launch executed / the launch's dura
 on the launch stream around every timed launch; `executed_*` = the f16 MFMA FLOPs issued for them (3 MFMAs per
 product of the Value net, 6 of SLPolicy: float32-grade results on f16 units); `traffic`, `rocprof_kernel_avg_ms`
 and `executed_frac_pmc` come from the committed rocprofv3 profile of this command (tools/profile_mcts.sh ->
-profiles/), quoted only when it was taken on these kernel sources.  `cpu_baseline` times the oracle's restatement
+profiles/), quoted only when it was taken on these kernel sources.  `cpu_baseline` (--full) times the oracle's restatement
 of MCTS.py (oracle/mcts_py.py, torch-CPU B = 1 nets, C rollout) on the host: P single-threaded processes, and one
 core beside it.
 
-Nested, none of them `value`: `rollout` (BASELINE configs[1], the headline of rounds 1-4: 4096 boards per launch
-played to the end by the fused rollout kernel, with its own HBM / VALU roofline and CPU baselines;
---rollout-only prints it as the line's headline), `mcts.per_playout_launches` (the same games on the per-playout
-engine), `mcts400` / `mcts_nthr1` (one batch of whole games at 400 playouts per move -- one GPU's share of
-configs[3] -- / with n_thr = 1) and their `*_opening` samples, `reinforce` (configs[4] in miniature: a set's 64 games as one
+Nested, with --full only, none of them `value`: `rollout` (BASELINE configs[1], the headline of rounds 1-4: 4096 boards
+per launch played to the end by the fused rollout kernel, with its own HBM / VALU roofline and CPU baselines;
+--rollout-only prints it as the line's headline, its CPU baseline with --full), `mcts.per_playout_launches` (the same
+games on the per-playout engine), `mcts400` / `mcts_nthr1` (one batch of whole games at 400 playouts per move -- one
+GPU's share of configs[3] -- / with n_thr = 1) and their `*_opening` samples, `reinforce` (configs[4] in miniature: a set's 64 games as one
 launch, the update -- forward, loss, backward, Adam -- as this repository's split-f16 kernels; with the CPU side beside it), `configs0` (one SL-vs-SL game on the CPU restatement), `mcts_single_game`.
 """
 import argparse
@@ -108,7 +115,7 @@ def cpu_baseline(w, b, budget_s=10.0):
 
 
 def mcts_leg(n_games, n_sims, n_turns, full_games, world, rank, dist, value_f32=False, use_graph=True, n_thr=15,
-             persistent=None, steps=1, warmup_steps=0, fresh_table=True):
+             persistent=None, steps=1, warmup_steps=0, fresh_table=True, outputs=None):
     """BASELINE configs[2]: PV-MCTS self-play, `n_games` games per GPU, `n_sims` playouts per move, SLPolicy +
     Value with random-init weights (Chainer-default LeCunNormal, seed 0), reference constants lmbda=0.5,
     c_puct=1, n_thr=15, both colours search.  One leaf-eval = one playout (value net + rollout at the leaf; the
@@ -117,7 +124,8 @@ def mcts_leg(n_games, n_sims, n_turns, full_games, world, rank, dist, value_f32=
     steps, then exactly `steps` timed ones between barrier + synchronize on both sides.  Every step plays NEW
     games (the rollouts' Philox streams go on from the previous step's) and -- fresh_table -- starts from an
     EMPTY position table: nothing computed outside a step (warm-up, earlier steps) answers a request inside
-    it.  --mcts-turns N > 0 times a bounded sample of the first N turns instead of whole games."""
+    it.  --mcts-turns N > 0 times a bounded sample of the first N turns instead of whole games.  `outputs`: a dict
+    that receives the last timed step's SelfPlayResult as host arrays (selfplay_outputs)."""
     from iago_amd import engine, network, ops
     from iago_amd.dist import all_gather_into, gather_tuples
     w, b = shipped_rollout_weights()
@@ -180,6 +188,8 @@ def mcts_leg(n_games, n_sims, n_turns, full_games, world, rank, dist, value_f32=
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(selfplay_outputs(res))
     kernel_ms = [e0.elapsed_time(e1) for e0, e1 in m.launch_events] if is_p else []
     if is_p:
         m.launch_events = None
@@ -1013,8 +1023,9 @@ class RolloutRounds(object):
         return sum(int(self.views(buf, k)[3].to(torch.int64).sum().item()) for k in range(self.K))
 
 
-def rollout_leg(args, world, rank, dist):
-    """The headline leg; returns the dict of measurements rank 0 prints."""
+def rollout_leg(args, world, rank, dist, outputs=None):
+    """The headline leg; returns the dict of measurements rank 0 prints.  `outputs`: a dict that receives the last
+    timed launch's results as host arrays."""
     from iago_amd import _lib, ops
     from iago_amd.dist import all_gather_into   # (= dist.all_gather_into_tensor under nccl)
     B, K, W = args.boards, args.steps, args.warmup
@@ -1114,6 +1125,10 @@ def rollout_leg(args, world, rank, dist):
     x_last, slot_last = divmod(n_launches - 1, S)
     last, nlast = x_last & 1, slot_last + 1          # the buffer / steps of the last exchange
     steps_last = sum(int(rr.views(last, k)[3].to(torch.int64).sum().item()) for k in range(nlast))
+    if outputs is not None:   # the last timed launch: what ops.rollout hands its caller (the game axis is 0)
+        fo, fp, z, nt = rr.views(last, slot_last)
+        outputs.update(final_own=(bitboard_halves(fo), 0), final_opp=(bitboard_halves(fp), 0),
+                       z=(z.cpu().numpy().astype(np.float32), 0), n_turns=(nt.cpu().numpy().astype(np.float32), 0))
     steps_round = torch.tensor([steps_last], dtype=torch.float64, device="cuda")
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if use_gather:
@@ -1210,6 +1225,48 @@ def rollout_leg(args, world, rank, dist):
                                           "BASELINE configs[1] (4096 boards in flight); not `value`" % LB}
             del lown, lopp, lout
     return out, (w, b)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def bitboard_halves(t):
+    """int64 bitboards (any shape) -> float64 [..., 2]: bits 0-31 and bits 32-63, exact integers."""
+    u = t.cpu().numpy().view(np.uint64)
+    return np.stack([u & np.uint64(0xFFFFFFFF), u >> np.uint64(32)], axis=-1).astype(np.float64)
+
+
+def selfplay_outputs(res):
+    """A SelfPlayResult (what SelfPlayEngine.play hands its caller) as host arrays {name: (array, game axis)}: the
+    positions before every turn (bitboard halves, mover first), the root visit counts, the moves and the flags of the
+    turns searched, and per game the result from colour 1's view, the final boards and the turn the game ended at."""
+    out = {"own": (bitboard_halves(res.own), 1), "opp": (bitboard_halves(res.opp), 1),
+           "pi": (res.pi.cpu().numpy().astype(np.float32), 1),
+           "valid": (res.valid.cpu().numpy().astype(np.float32), 1),
+           "move": (res.move.cpu().numpy().astype(np.float32), 1),
+           "z": (res.z.cpu().numpy().astype(np.float32), 0),
+           "final_p1": (bitboard_halves(res.final_p1), 0), "final_p2": (bitboard_halves(res.final_p2), 0)}
+    if res.game_turns is not None:
+        out["game_turns"] = (res.game_turns.cpu().numpy().astype(np.float32), 0)
+    return out
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: writes {name: (array, game axis)} as path/<name>.npy, and path/games.npy = the indices of the
+    games written.  Every array holds one entry per game; when all of them exceed `limit` bytes, a fixed sample of
+    the games (seed 0: the same games in every run) is written instead of all."""
+    n = {a.shape[ax] for a, ax in outputs.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    total = sum(a.nbytes for a, _ in outputs.values())
+    keep = np.arange(n)
+    if total + 8 * n > limit - 4096:         # (4 kB: the .npy headers)
+        k = max(1, int((limit - 4096) // (total / n + 8)))
+        keep = np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "games.npy"), keep.astype(np.float64))
+    for name, (a, ax) in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a if len(keep) == n else np.take(a, keep, axis=ax))
 
 
 def spawn_ranks(n):
@@ -1367,6 +1424,13 @@ def main():
                          "whole games (default), N > 0 = only the opening sample of N turns, 0 = skip")
     ap.add_argument("--nthr1-turns", type=int, default=-1,
                     help="PV-MCTS with n_thr = 1 (SURVEY.md 8d: the policy net inside every playout): as --mcts400-turns")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the nested legs (rollout, per-playout launches, mcts400, "
+                         "mcts_nthr1, mcts_saturated, reinforce, mcts_single_game), the CPU baselines and value_spread "
+                         "(default: the headline leg only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-budget", type=float, default=4.0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-start", type=float, default=0.0, help=argparse.SUPPRESS)
@@ -1383,6 +1447,9 @@ def main():
         raise SystemExit("--steps >= 1 and --warmup >= 0 expected")
     if args.rollout_only:
         args.rollout_steps, args.rollout_warmup = args.steps, args.warmup
+    if args.dump_outputs and args.rollout_only and args.repeats <= 0:
+        raise SystemExit("--dump-outputs with --rollout-only needs --repeats N > 0 (the default sizes the timed region "
+                         "by the clock, so the last step's games would differ from run to run)")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher
@@ -1426,12 +1493,13 @@ def main():
 
     # ---- the nested configs[1] leg (the headline of rounds 1-4, and of --rollout-only)
     roll = None
-    if args.rollout_only or not (args.no_rollout_leg or args.mcts_only):
+    outputs = {} if (args.dump_outputs and rank == 0) else None
+    if args.rollout_only or (args.full and not (args.no_rollout_leg or args.mcts_only)):
         import copy
         ra = copy.copy(args)
         ra.steps, ra.warmup = args.rollout_steps, args.rollout_warmup
         log("configs[1]: %d-board rollout launches" % args.boards)
-        roll, _ = rollout_leg(ra, world, rank, dist)
+        roll, _ = rollout_leg(ra, world, rank, dist, outputs=outputs if args.rollout_only else None)
         roll["steps"], roll["warmup"] = ra.steps, ra.warmup
         roll["config"] = {"workload": "BASELINE configs[1]: %d parallel Othello boards per GPU in ONE launch "
                                       "per step, launches serialized on one stream, rollout-policy-only "
@@ -1453,8 +1521,10 @@ def main():
             for key in ("overlapped", "large_batch"):
                 if key in roll:
                     line[key] = roll[key]
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 line["cpu_baseline"] = cpu_baseline(w, b)
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
             sys.stdout.flush()
             os.write(json_fd, (json.dumps(line) + "\n").encode())
         if dist is not None:
@@ -1469,9 +1539,11 @@ def main():
     mcts = mcts_leg(args.mcts_games, args.mcts_sims, max(args.mcts_turns, 0), full, world, rank, dist,
                     value_f32=args.mcts_value_f32, use_graph=not args.mcts_eager, n_thr=args.mcts_nthr,
                     persistent=False if (args.mcts_per_playout or args.mcts_eager) else None,
-                    steps=K, warmup_steps=W, fresh_table=not args.keep_table)
+                    steps=K, warmup_steps=W, fresh_table=not args.keep_table, outputs=outputs)
     log("configs[2]: %.3f s per batch, %.2f M leaf-evals/s" % (mcts["seconds"] / K, mcts["leaf_evals_per_sec"] / 1e6))
-    extras = not args.mcts_only and not args.mcts_value_f32
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+    extras = args.full and not args.mcts_only and not args.mcts_value_f32
     if extras and full and not args.mcts_eager:
         # the same games on the per-playout launches (rounds 1-3's engine), one batch, for comparison
         log("configs[2] on the per-playout launches (one batch)")
@@ -1558,11 +1630,11 @@ def main():
                              "role (role_split_game_cus: two game workgroups per CU on that many CUs, one net workgroup on each "
                              "of the others)")
     train = None
-    if args.train_iters > 0 and not args.mcts_only:
+    if args.full and args.train_iters > 0 and not args.mcts_only:
         log("configs[4] in miniature: REINFORCE sets")
         train = reinforce_leg(args.train_iters, world, rank, dist)
     b1 = None
-    if rank == 0 and not args.mcts_only:
+    if rank == 0 and args.full and not args.mcts_only:
         log("one game (serving mode)")
         b1 = mcts_b1_leg()
 
@@ -1630,7 +1702,8 @@ def main():
             line["mcts_executed_frac_f16_peak"] = rl["frac"]
         if saturated is not None:
             line["mcts_saturated"] = saturated
-        line["value_spread"] = value_spread(args.mcts_games, args.mcts_sims, line["value"])
+        if args.full:
+            line["value_spread"] = value_spread(args.mcts_games, args.mcts_sims, line["value"])
         line["mcts"] = mcts
         for k, v in more.items():
             line[k] = v
@@ -1658,7 +1731,7 @@ def main():
                 line["reinforce_mcts_fed_rounds_per_sec"] = train["mcts_fed"]["rounds_per_sec"]
         if b1 is not None:
             line["mcts_single_game"] = b1
-        if not args.no_cpu_baseline and world == 1:  # the CPU baselines are N = 1 figures
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baselines are N = 1 figures
             log("CPU baselines")
             per_game = mcts["leaf_evals"] / (games_step * K) if full else None
             line["cpu_baseline"] = mcts_cpu_baseline(leaf_evals_per_game=per_game)

@@ -1,5 +1,6 @@
 """The driver's contract for bench.py (one JSON line on stdout, the named keys): the nested configs[1] leg as
---rollout-only prints it (a timed region that does not depend on --steps), and the default run's headline."""
+--rollout-only prints it (a timed region that does not depend on --steps), the headline with the legs of --full, and a
+plain run (the headline alone) with the outputs of its last step."""
 import json
 import os
 import subprocess
@@ -48,7 +49,7 @@ def test_headline_is_the_pv_mcts_leg_under_the_clock():
     persistent search -- with K >= 3 timed batches, a fresh position table per batch, the search kernel's MFMA roofline
     from live HIP events, and the hits of the position table split into same-game and cross-game."""
     a = run_bench("--steps", "3", "--warmup", "1", "--mcts-games", "256", "--no-rollout-leg", "--mcts400-turns", "0",
-                  "--nthr1-turns", "0", "--train-iters", "0", "--no-cpu-baseline")
+                  "--nthr1-turns", "0", "--train-iters", "0", "--no-cpu-baseline", "--full")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int),
                      ("warmup", int), ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str),
                      ("dtype", str), ("data", str), ("config", dict), ("roofline", dict), ("leaf_evals_per_sec", float)):
@@ -86,3 +87,40 @@ def test_headline_is_the_pv_mcts_leg_under_the_clock():
         assert sat[k]["role_split_game_cus"] in cus and sat[k]["batches_replayed_turn_by_turn"] == 0
     assert m["persistent"]["role_split_game_cus"] == 0          # (256 games: the single launch)
     assert a["value_spread"]["min"] <= a["value_spread"]["max"] and a["value_spread"]["boxes"] >= 1
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A run without --full times the headline leg and nothing else; --dump-outputs writes what its last timed step
+    computed (float32 / float64 arrays, <= 64 MB), and the same arguments give the same arrays in a second process."""
+    import numpy as np
+    args = ("--steps", "2", "--warmup", "1", "--mcts-games", "64")
+    a = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    b = run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    for line in (a, b):
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["mcts"]["steps"] == 2
+        assert len(line["mcts"]["step_seconds"]) == 2 and line["config"]["games_per_step"] == 64
+        assert abs(line["ms_per_step"] * 2 - line["mcts"]["seconds"] * 1e3) < 1e-6 * line["mcts"]["seconds"] * 1e3
+        for key in ("rollout", "cpu_baseline", "reinforce", "mcts_saturated", "mcts400", "mcts_nthr1", "mcts_single_game",
+                    "configs0", "value_spread"):
+            assert key not in line, key
+        assert "per_playout_launches" not in line["mcts"]
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(os.listdir(str(tmp_path / "b")))
+    assert {"games.npy", "own.npy", "opp.npy", "pi.npy", "move.npy", "valid.npy", "z.npy"} <= set(files)
+    got, total = {}, 0
+    for f in files:
+        x, y = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert x.dtype in (np.float32, np.float64), f
+        assert np.array_equal(x, y), f      # same arguments, same games
+        got[f[:-4]] = x
+        total += os.path.getsize(str(tmp_path / "a" / f))
+    assert total <= 64 << 20
+    assert np.array_equal(got["games"], np.arange(64)) and got["z"].shape == (64,)
+    assert set(np.unique(got["z"]).tolist()) <= {-1.0, 0.0, 1.0}
+    T = got["pi"].shape[0]
+    assert got["pi"].shape == (T, 64, 64) and got["own"].shape == got["opp"].shape == (T, 64, 2)
+    moved = got["valid"] == 1
+    mv = got["move"][moved].astype(np.int64)
+    assert moved.any() and ((mv >= 0) & (mv < 64)).all()
+    rows = got["pi"][moved]
+    assert (rows[np.arange(len(mv)), mv] == rows.max(axis=1)).all()   # the move is the most visited child

@@ -144,7 +144,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env.update(IAGO_BENCH_BACKEND="gloo", IAGO_BENCH_DEVICE="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--rollout-steps", "20", "--rollout-warmup", "5", "--large-boards", "0",
-                          "--mcts-games", "128", "--nthr1-turns", "0", "--mcts400-turns", "2", "--train-iters", "2"],
+                          "--mcts-games", "128", "--nthr1-turns", "0", "--mcts400-turns", "2", "--train-iters", "2", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -170,7 +170,8 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
 
 
 FIVE = ["--gpus", "5", "--steps", "2", "--warmup", "1", "--boards", "4096", "--rollout-steps", "20", "--rollout-warmup", "5",
-        "--mcts-games", "32", "--nthr1-turns", "0", "--mcts400-turns", "0", "--train-iters", "1", "--large-boards", "0"]
+        "--mcts-games", "32", "--nthr1-turns", "0", "--mcts400-turns", "0", "--train-iters", "1", "--large-boards", "0",
+        "--full"]
 
 
 def _rehearsal_env():

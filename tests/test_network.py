@@ -12,7 +12,7 @@ from oracle import nets_np
 from oracle import oracle as orc
 
 TOL = 1e-5
-REF_MODELS = "/root/reference/models"  # rollout_model.npz only; sl / value live in tests/golden
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")  # the reference's shipped checkpoints
 
 
 def sample_planes(n, seed):
@@ -97,16 +97,14 @@ def test_value_dropout_only_in_training_mode():
     assert not torch.equal(a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="shipped checkpoints live in /root/reference")
 def test_shipped_checkpoints_known_answers():
     """SURVEY.md section 8a KATs (measured there with an independent torch
     restatement) + the float64 oracle on the same weights."""
     s = orc.initial_state()
     x = np.concatenate([orc.make_state_var(s, 1), orc.make_state_var(s, 2)]).astype(np.float32)
-    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-    sl = network.SLPolicy().load_npz(os.path.join(gold, "sl_model.npz")).eval()
-    va = network.Value().load_npz(os.path.join(gold, "value_model.npz")).eval()
-    ro = network.RolloutPolicy().load_npz(os.path.join(REF_MODELS, "rollout_model.npz")).eval()
+    sl = network.SLPolicy().load_npz(os.path.join(GOLDEN, "sl_model.npz")).eval()
+    va = network.Value().load_npz(os.path.join(GOLDEN, "value_model.npz")).eval()
+    ro = network.RolloutPolicy().load_npz(os.path.join(GOLDEN, "rollout_model.npz")).eval()
     with torch.no_grad():
         p = sl(torch.from_numpy(x)).numpy()
         v = va(torch.from_numpy(x)).numpy()
@@ -122,7 +120,7 @@ def test_shipped_checkpoints_known_answers():
         assert np.max(np.abs(got - fn(x, m.npz_dict()))) < TOL
     # the 82 shipped rollout floats are also the golden data the benchmark uses
     import json
-    g = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "simulate.json")))
+    g = json.load(open(os.path.join(GOLDEN, "simulate.json")))
     w, b = ro.kernel_weights()
     assert np.array_equal(w, np.asarray(g["shipped_w"], np.float32))
     assert np.array_equal(b, np.asarray(g["shipped_b"], np.float32))

@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 for S in 6 8 12 16 24; do
-  rm -rf /tmp/pa; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pa -- python3 $REPO/bench.py --streams $S --no-cpu-baseline --mcts-turns 0 --large-boards 0 --train-iters 0 > /tmp/pa.log 2>&1
+  rm -rf /tmp/pa; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pa -- python3 $REPO/bench.py --full --streams $S --no-cpu-baseline --mcts-turns 0 --large-boards 0 --train-iters 0 > /tmp/pa.log 2>&1
   python3 - <<PY
 import json,csv,glob
 d=json.loads([l for l in open('/tmp/pa.log') if l.startswith('{"metric"')][-1]); r=d['roofline']
