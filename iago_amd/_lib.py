@@ -180,7 +180,7 @@ class MctsSearchArgs(C.Structure):
         ("rec_move", C.c_void_p), ("rec_pi", C.c_void_p),
         ("vtable", C.c_void_p), ("vtable_slots", C.c_int64),
         ("trace", C.c_void_p), ("trace_rows", C.c_int32), ("pace_margin", C.c_int32),
-        ("max_cus", C.c_int32), ("reserved", C.c_int32),
+        ("max_cus", C.c_int32), ("games_total", C.c_int32),
     ]
 
 

@@ -153,13 +153,14 @@ __device__ __forceinline__ uint64_t flips_hw(uint64_t o, uint64_t p, uint32_t po
 // INDEXED (the persistent search): the 16 boards of the call are boards idx[0..15] (-1 = no board in that row of
 // lanes) instead of boards 16 block_id ..; `table_ready`: the factor table is in LDS already (an earlier call of
 // this workgroup put it there).
-// (INDEXED, the persistent search again) `hand`: the boards' positions and Philox stream offsets come from, and their results
+// (INDEXED, the persistent search again) `hand`: the boards' positions, games and Philox stream offsets come from, and their results
 // go to, LDS arrays indexed by the board's number within the workgroup (idx[..] - base) -- written / read by this very
 // workgroup around the call: through global memory each was a store followed by a load of the same address, a round trip to
 // L2 at the head of every pass.
 struct RowHandoff {
     const uint64_t *own, *opp; // [board of the workgroup]
     const int32_t *stream;
+    const int32_t *game;       // the game the board belongs to (the Philox key's game word: id_base + game)
     int8_t *z;
     int32_t base;              // idx[..] of the workgroup's board 0
 };
@@ -237,9 +238,11 @@ __device__ __forceinline__ void rollout_row_body(const HwParams &P, const uint32
         b = live ? at : 0;
     }
     uint64_t own, opp; // side to move, in this lane's orientation below
+    uint32_t game_word = P.id_base + (uint32_t)b; // (INDEXED: Philox counter word 0, the board's game)
     if (INDEXED && hand) {
         const int slot = live ? (int)b - hand->base : 0;
         stream_id += live ? (uint32_t)hand->stream[slot] : 0u;
+        game_word = P.id_base + (live ? (uint32_t)hand->game[slot] : 0u);
         own = live ? hand->own[slot] : 0ull;
         opp = live ? hand->opp[slot] : 0ull;
     } else {
@@ -260,7 +263,7 @@ __device__ __forceinline__ void rollout_row_body(const HwParams &P, const uint32
 
     // lane l draws Philox counter block l: the 16 lanes of a row hold the uniforms of 64 turns
     // (kept as the float32 uniforms themselves: converted once per 64 turns, not once per fetch)
-    uint32_t rw[4] = {P.id_base + (uint32_t)b, L.l, stream_id, 0u};
+    uint32_t rw[4] = {INDEXED ? game_word : P.id_base + (uint32_t)b, L.l, stream_id, 0u};
     auto draw = [&]() __attribute__((always_inline)) {
         philox4x32_10(rw, P.key0, P.key1);
 #pragma unroll
@@ -291,7 +294,7 @@ __device__ __forceinline__ void rollout_row_body(const HwParams &P, const uint32
                 u4[i] = live ? P.uniforms[(int64_t)(t4 + i) * P.n + b] : 0.0f;
         } else {
             if (__builtin_expect((t4 & 63u) == 0u && t4 != 0u, 0)) { // the next 16 counter blocks = 64 turns
-                rw[0] = P.id_base + (uint32_t)b;
+                rw[0] = INDEXED ? game_word : P.id_base + (uint32_t)b;
                 rw[1] = (t4 >> 2) + L.l;
                 rw[2] = stream_id;
                 rw[3] = 0u;

@@ -71,6 +71,7 @@ constexpr int CTL_NO_CHILDREN = 4; // a searched root had no children (n_sims be
 constexpr int CTL_PROGRESS = 5, CTL_PLAYING = 6;
 constexpr int CTL_NET_WGS = 7;            // net workgroups of this launch (written by the launch: the grid follows the device)
 constexpr int CTL_IDLE = 14;              // net workgroups that found nothing to do at their last look (they poll)
+constexpr int CTL_NEXT_GAME = 12;         // a stream: game ids claimed beyond the first fill (the next one: n_games + this)
 constexpr uint32_t NOBODY = 0x7FFFFFFFu;  // "game" of a request nobody waits for (its value goes to the position table only)
 constexpr uint32_t KIND_VALUE = 0u, KIND_POLICY = 1u;
 // games of a GAME workgroup: 8 lanes per game in the descent and the backup (16 games = two waves, 32 = all four),
@@ -119,6 +120,12 @@ struct SearchParams {
     uint8_t *rec_valid;              // [max_turns][n_games]: the mover had a move and searched
     int8_t *rec_move;                // [max_turns][n_games]: the move played, -1 = pass / no turn
     int32_t *rec_pi;                 // [max_turns][n_games][64]: the root's visit counts by action
+    // a self-play STREAM (stream != 0): games_total games in the launch, at most n_games (the slots) of them in play; a game
+    // workgroup whose games are all over claims the next game ids (CTL_NEXT_GAME), one per slot, resets the slots' trees and
+    // plays those games from their first turn.
+    // game_own / game_opp / n_turns are then [games_total] and the records [max_turns][games_total], indexed by the GAME;
+    // the rollouts draw with the game's id.  Not a stream: games_total = n_games, game = slot
+    int32_t games_total, stream;
     // optional position table shared by all games and launches: value_func(state) is a pure function of the position, and
     // games that start from one position keep meeting each other's positions (9.5 % of the value requests of 1024 games
     // x 100 playouts repeat a position asked for before: LABNOTES.md).  Direct-mapped, 32-byte entries {seq, own, opp,
@@ -283,12 +290,16 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     // positions, Philox stream offsets and results between the descent / backup and the rollout passes: LDS (RowHandoff)
     __shared__ uint64_t h_own[GAMES_PER_WG], h_opp[GAMES_PER_WG];
     __shared__ int32_t h_stream[GAMES_PER_WG];
+    __shared__ int32_t h_game[GAMES_PER_WG]; // the game each slot plays (the slot itself unless a stream), read at its end
     __shared__ int8_t h_z[GAMES_PER_WG];
-    const iago_row::RowHandoff hand = {h_own, h_opp, h_stream, h_z, (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
+    const iago_row::RowHandoff hand = {h_own, h_opp, h_stream, h_game, h_z, (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
     const int gl = tid >> 3; // this game's number within the workgroup
+    const int n_here = (int)min((int64_t)S.games_per_wg, T.n_games - (int64_t)blockIdx.x * S.games_per_wg); // its slots
 
     const bool whole = S.max_turns > 0;
-    int state = (exists && S.active[g] != 0 && S.n_sims > 0) ? (whole ? ST_TURN : ST_READY) : ST_DONE;
+    // (a stream: slot g starts game g while there is one -- `active` is not read)
+    const bool first = exists && g < S.games_total && (S.stream || S.active[g] != 0);
+    int state = (first && S.n_sims > 0) ? (whole ? ST_TURN : ST_READY) : ST_DONE;
     uint32_t epoch = 0u; // reply tag of the game's last request (never 0 once used)
     int n_done = 0;
     if (exists && r == 0u) {
@@ -300,7 +311,9 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     int turn = 0, stones = 4;
     bool pass_flg = false, g_over = false;
     const int search_end = whole ? ST_MOVE : ST_DONE; // where a game goes when its search's last playout is backed up
-    if (whole && exists) {
+    if (mine)
+        h_game[gl] = (int32_t)g; // (the 8 lanes write the same word; each reads back its own store)
+    if (whole && exists && g < S.games_total) {
         g_own = S.game_own[g];
         g_opp = S.game_opp[g];
         if (state == ST_DONE && r == 0u)
@@ -413,7 +426,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                                 __hip_atomic_store(&S.ctl[CTL_NO_CHILDREN], 1u, RLX_AGENT);
                         }
                         if (S.rec_move) {
-                            const int64_t row = (int64_t)turn * T.n_games + g;
+                            const int64_t row = (int64_t)turn * S.games_total + h_game[gl];
                             if (r == 0u) {
                                 S.rec_own[row] = g_own;
                                 S.rec_opp[row] = g_opp;
@@ -466,9 +479,10 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                         turn++;
                         if (turn >= S.max_turns || (turn % 2 == 0 && g_over)) {
                             if (r == 0u) {
-                                S.n_turns[g] = turn;
-                                S.game_own[g] = g_own;         // (colour 1's stones after an even number of turns)
-                                S.game_opp[g] = g_opp;
+                                const int64_t G = h_game[gl];
+                                S.n_turns[G] = turn;
+                                S.game_own[G] = g_own;         // (colour 1's stones after an even number of turns)
+                                S.game_opp[G] = g_opp;
                             }
                             state = ST_DONE;
                             if (S.trace && r == 0u && g < S.trace_rows) { // (diagnostic: the game's end, its requests)
@@ -733,8 +747,10 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
         // the other by thread 0 between the iteration's last two barriers they were up to six dependent round trips to L2
         // (2 - 4 us of a 34 us iteration, with the whole workgroup waiting).  All of it is timing-only state, one
         // iteration old at most when it is used.
-        uint32_t c_abort = 0u, c_idle = 0u, c_t0 = 0u, c_h0 = 0u, c_t1 = 0u, c_h1 = 0u, c_play = 0u, c_prog = 0u;
+        uint32_t c_abort = 0u, c_idle = 0u, c_t0 = 0u, c_h0 = 0u, c_t1 = 0u, c_h1 = 0u, c_play = 0u, c_prog = 0u, c_next = 0u;
         if (tid == 0) {
+            if (S.stream)
+                c_next = __hip_atomic_load(&S.ctl[CTL_NEXT_GAME], RLX_AGENT);
             c_abort = __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT);
             c_idle = __hip_atomic_load(&S.ctl[CTL_IDLE], RLX_AGENT);
             c_t0 = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT);
@@ -840,14 +856,51 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                 // each) and TWO iterations' worth of these (the workgroups look at the rings at different moments: a second
                 // burst can be on its way before the first shows in anybody's snapshot) fit the ring together
                 pace[3] = (int32_t)((QCAP - (uint32_t)T.n_games) / 2u) / S.n_game_wgs;
-            if (S.pace_margin >= 0) {
+            // (a stream: no hold while game ids are left to claim -- the mean then mixes old and new games; the rule
+            // holds again for the final drain, when every id is taken)
+            if (S.pace_margin >= 0 && (!S.stream || (int64_t)c_next + T.n_games >= (int64_t)S.games_total)) {
                 if (wait0 + wait1 > S.pace_backlog && c_play != 0u && c_play <= (uint32_t)T.n_games)
                     limit = (int)(c_prog / c_play) + S.pace_margin;
             }
             pace[2] = limit;
         }
-        const int all_done = __syncthreads_and(!mine || state == ST_DONE);
+        int all_done = __syncthreads_and(!mine || state == ST_DONE);
         pace_limit = pace[2];
+        if (all_done && !stop && S.stream) {
+            // A stream: the workgroup's games are all over -- its slots take the next block of game ids, one each, and
+            // start those games together.  (Claimed slot by slot, games of every phase shared a workgroup: a rollout pass
+            // lasts as long as its longest board and a wave's descent as its deepest game, so every iteration paid for
+            // the opening's rollouts AND the end's pass chains -- 0.84x / 0.75x the batch loop's games/s at 100 / 400
+            // playouts; LABNOTES.md.)  Which slot plays which game changes nothing: a game draws with its own id
+            __shared__ uint32_t claimed;
+            if (tid == 0)
+                claimed = __hip_atomic_fetch_add(&S.ctl[CTL_NEXT_GAME], (uint32_t)n_here, RLX_AGENT);
+            __syncthreads();
+            const int64_t next = T.n_games + (int64_t)claimed + gl;
+            if (exists && next < S.games_total) {
+                // its start position and books (game.py:32), a fresh tree: reset_kernel's Node(None, 1.0) -- except the
+                // pool's overflow flag, which voids the launch whichever game set it.  The reply tag `epoch` goes on
+                // counting: a reply to the slot's last game is never taken for one to this game
+                g_own = S.game_own[next];
+                g_opp = S.game_opp[next];
+                turn = 0;
+                stones = 4;
+                pass_flg = false;
+                g_over = false;
+                n_done = 0;
+                if (r == 0u) {
+                    S.done[g] = 0;
+                    init_node(T, base, -1, -2, 1.0f + 0.1f);
+                    T.n_nodes[g] = 1;
+                    T.root[g] = 0;
+                    atomicAdd(&pace[1], 1); // (in play again: CTL_PLAYING at the next iteration's end)
+                }
+                h_game[gl] = (int32_t)next;
+                state = ST_TURN;
+                in_play = true;
+            }
+            all_done = __syncthreads_and(!mine || state == ST_DONE);
+        }
         if (all_done || stop)
             break;
         if (!__syncthreads_or(busy)) {
@@ -1214,6 +1267,10 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
         (a->max_turns > 0 && a->rec_move && (!a->rec_own || !a->rec_opp || !a->rec_valid || !a->rec_pi)))
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: whole games (max_turns > 0) need game_own, game_opp, "
                                            "n_turns, and all of rec_own / rec_opp / rec_valid / rec_move / rec_pi or none");
+    if (a->games_total < 0 || (a->games_total > 0 && (a->max_turns == 0 || a->n_sims < 1 || a->z_log || a->z_log_rows > 0 ||
+                                                      a->trace || a->trace_rows > 0)))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: games_total >= 0; a stream (games_total > 0) plays "
+                                           "whole games (max_turns > 0, n_sims >= 1), without z_log or trace");
     if (a->max_turns == 0 && (!a->root_own || !a->root_opp))
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: root_own / root_opp expected");
     if (a->z_log_rows > 0 && (!a->z_log || !a->z_log_n))
@@ -1375,6 +1432,8 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.rec_valid = a->rec_valid;
     S.rec_move = a->rec_move;
     S.rec_pi = a->rec_pi;
+    S.stream = a->games_total > 0 ? 1 : 0;
+    S.games_total = a->games_total > 0 ? a->games_total : (int32_t)tree->n_games;
     S.vtable = nullptr;
     S.vtable_mask = 0u;
     if (a->vtable_slots > 0) {

@@ -26,6 +26,7 @@ from ._lib import MctsTree, check
 START_OWN = 0x0000000810000000  # colour 1 "X", moves first: (3,4), (4,3)  (game.py:26-30)
 START_OPP = 0x0000001008000000  # colour 2 "O": (3,3), (4,4)
 HANDICAP_CELLS = (2 * 8 + 4, 3 * 8 + 5, 4 * 8 + 2, 5 * 8 + 3)  # src/train_rl.py:45
+STREAM_REC_BYTES = 4 << 30      # SelfPlayEngine.play_stream: largest rec_pi (n_games x max_turns x 64 int32) it allocates
 
 
 def _p(t):
@@ -1116,6 +1117,9 @@ class BatchedMCTS(object):
             a.max_turns = int(game["max_turns"])
             # (a whole game of 400-playout searches takes seconds; IAGO_PERSISTENT_GAME_LIMIT_MS: the lab's shorter limit)
             a.time_limit_ms = max(self.time_limit_ms, int(os.environ.get("IAGO_PERSISTENT_GAME_LIMIT_MS", "60000")))
+            a.games_total = int(game.get("games_total", 0))
+            if a.games_total:   # (a stream: the limit of a batch of whole games per batch's worth of games)
+                a.time_limit_ms = min(a.time_limit_ms * -(-a.games_total // self.n_games), 0x7FFFFFFF)
             a.game_own, a.game_opp, a.n_turns = game["own"].data_ptr(), game["opp"].data_ptr(), game["n_turns"].data_ptr()
             a.rec_own, a.rec_opp = game["rec_own"].data_ptr(), game["rec_opp"].data_ptr()
             a.rec_valid, a.rec_move, a.rec_pi = (game["rec_valid"].data_ptr(), game["rec_move"].data_ptr(),
@@ -1313,6 +1317,28 @@ class SelfPlayResult(object):
                     turn=turn.expand(T, B).reshape(-1)[m])
 
 
+def _end_turns(valid):
+    """(B,) each game's end turn from its records valid (T, B): the books of game.py:117-142,253-255 as the one-launch
+    path keeps them -- a stone per move, a pass after a pass ends the game, `while stone_num < 64` once per pair of
+    turns."""
+    T, B = valid.shape
+    dev = valid.device
+    stones = torch.full((B,), 4, dtype=torch.int32, device=dev)
+    pass_flg = torch.zeros(B, dtype=torch.bool, device=dev)
+    over = torch.zeros(B, dtype=torch.bool, device=dev)
+    end = torch.full((B,), T, dtype=torch.int32, device=dev)
+    for t in range(T):
+        moved = valid[t] != 0
+        passing = ~moved & ~over
+        stones = torch.where(passing & pass_flg, torch.full_like(stones, 64), stones + moved.to(torch.int32))
+        pass_flg = torch.where(over, pass_flg, passing)
+        if t % 2 == 1:
+            new = ~over & (stones >= 64)
+            end = torch.where(new, torch.full_like(end, t + 1), end)
+            over = over | new
+    return end
+
+
 class SelfPlayEngine(object):
     """Lockstep PV-MCTS self-play: both colours search the shared tree, moves
     are the most visited children, passes advance the tree with -1
@@ -1323,20 +1349,22 @@ class SelfPlayEngine(object):
         self.B = mcts.n_games
         self.max_turns = max_turns
 
-    def _play_persistent(self, n_sims, own, opp, record):
+    def _play_persistent(self, n_sims, own, opp, record, games_total=0):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
-        loop below (tests/test_search_persistent_gpu.py)."""
-        m, B, T = self.mcts, self.B, self.max_turns
+        loop below (tests/test_search_persistent_gpu.py).  games_total > 0: the games_total games of own / opp
+        as a stream through the B slots (play_stream)."""
+        m, T = self.mcts, self.max_turns
+        B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
-        g = dict(max_turns=T, own=own, opp=opp, n_turns=torch.zeros(B, dtype=torch.int32, device=dev),
+        g = dict(max_turns=T, games_total=games_total, own=own, opp=opp, n_turns=torch.zeros(B, dtype=torch.int32, device=dev),
                  rec_own=torch.zeros((T, B), dtype=torch.int64, device=dev),
                  rec_opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
                  rec_valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
                  rec_move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
                  rec_pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev))
-        active = torch.ones(B, dtype=torch.uint8, device=dev)
+        active = torch.ones(self.B, dtype=torch.uint8, device=dev)
         if m.value_cache:
             key = tuple((q.data_ptr(), q._version) for q in m.value_fn.parameters())
             if key != m._value_key:
@@ -1385,6 +1413,12 @@ class SelfPlayEngine(object):
             res.valid, res.move, res.pi = g["rec_valid"][:t], g["rec_move"][:t], g["rec_pi"][:t]
         return res
 
+    def _whole_games_in_one_launch(self, n_sims):
+        m = self.mcts
+        return (getattr(m, "persistent", False) and m.rollout_hook is None
+                and os.environ.get("IAGO_PERSISTENT_GAMES", "1") != "0"
+                and 2 * m.tree.capacity >= suggest_capacity(n_sims, m.n_thr, moves=min(self.max_turns, 64)))
+
     def play(self, n_sims, handicap=None, record=True):
         m, B = self.mcts, self.B
         dev = m.cur_own.device
@@ -1396,9 +1430,7 @@ class SelfPlayEngine(object):
         # The one-launch whole-game path wherever the persistent search applies and the pools can hold a whole game
         # without compaction; else -- and when a pool fills up all the same -- the turn-by-turn loop below, whose
         # searches (one persistent launch per turn) compact a pool that is half full.  Same games either way.
-        if (getattr(m, "persistent", False) and m.rollout_hook is None
-                and os.environ.get("IAGO_PERSISTENT_GAMES", "1") != "0"
-                and 2 * m.tree.capacity >= suggest_capacity(n_sims, m.n_thr, moves=min(self.max_turns, 64))):
+        if self._whole_games_in_one_launch(n_sims):
             res = self._play_persistent(n_sims, own.clone(), opp.clone(), record)
             if res is not None:
                 return res
@@ -1459,4 +1491,88 @@ class SelfPlayEngine(object):
         if record:
             for name in ("own", "opp", "pi", "valid", "move"):
                 setattr(res, name, getattr(res, name)[:t])
+        return res
+
+    def play_stream(self, n_sims, n_games, handicap=None, record=True):
+        """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
+        where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
+        first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
+        games.  Game G is bit for bit game G of the BATCH LOOP -- play() ceil(n_games / B) times, batch k with
+        game_id_base + k B, each from the same sim_counter -- which is also the path taken where the one launch does not
+        apply (another engine, pools that cannot hold a whole game, z_log or trace; and, as a replay, a pool that filled
+        up in the launch).  handicap: (n_games,) int64 bit masks of extra colour-2 stones.  The result has n_games
+        columns (tuples() give the game ids game_id_base ..); n_turns is the longest game's, `launches` the launches it
+        took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch."""
+        m, B, T = self.mcts, self.B, self.max_turns
+        n_games = int(n_games)
+        if n_games < 1:
+            raise ValueError("play_stream: n_games >= 1 expected")
+        if n_games * T * 64 * 4 > STREAM_REC_BYTES:
+            raise ValueError("play_stream: %d games x %d turns of visit counts exceed %d bytes: fewer games per call"
+                             % (n_games, T, STREAM_REC_BYTES))
+        if handicap is not None and tuple(handicap.shape) != (n_games,):
+            raise ValueError("play_stream: handicap is an (n_games,) int64 tensor")
+        if (self._whole_games_in_one_launch(n_sims) and getattr(m, "z_log", None) is None
+                and getattr(m, "trace", None) is None):
+            dev = m.cur_own.device
+            own = torch.full((n_games,), START_OWN, dtype=torch.int64, device=dev)
+            opp = torch.full((n_games,), START_OPP, dtype=torch.int64, device=dev)
+            if handicap is not None:
+                opp = opp | handicap
+            m.tree.reset()
+            res = self._play_persistent(n_sims, own, opp, record, games_total=n_games)
+            if res is not None:
+                res.launches = 1
+                return res
+            self.n_replayed = getattr(self, "n_replayed", 0) + 1
+        return self._play_batches(n_sims, n_games, handicap, record)
+
+    def _play_batches(self, n_sims, n_games, handicap, record):
+        """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same
+        sim_counter, the first n_games columns kept."""
+        m, B = self.mcts, self.B
+        base, s0 = m.game_id_base, m.sim_counter
+        parts = []
+        try:
+            for k in range(-(-n_games // B)):
+                w = min(B, n_games - k * B)
+                hc = None
+                if handicap is not None:
+                    hc = torch.zeros(B, dtype=torch.int64, device=handicap.device)
+                    hc[:w] = handicap[k * B:k * B + w]
+                m.game_id_base, m.sim_counter = base + k * B, s0
+                parts.append((self.play(n_sims, handicap=hc, record=record), w))
+        finally:
+            m.game_id_base = base
+        res = SelfPlayResult()
+        # (a batch played through the turn loop has no per-game end turns: its records give them)
+        turns = [r.game_turns if r.game_turns is not None or not record else _end_turns(r.valid) for r, _ in parts]
+        if any(x is None for x in turns):
+            res.game_turns = None
+            t = max(r.n_turns for r, _ in parts)
+        else:                                  # (the longest of the games kept, as in the one launch)
+            res.game_turns = torch.cat([x[:w] for x, (_, w) in zip(turns, parts)])
+            t = int(res.game_turns.max().item())
+        m.sim_counter = (s0 + t * n_sims) & 0xFFFFFFFF
+        res.game_id_base, res.n_turns, res.launches = base, t, len(parts)
+        res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
+        res.z = torch.cat([r.z[:w] for r, w in parts])
+        res.final_p1 = torch.cat([r.final_p1[:w] for r, w in parts])
+        res.final_p2 = torch.cat([r.final_p2[:w] for r, w in parts])
+        if record:
+            cols = {k: [] for k in ("own", "opp", "valid", "move", "pi")}
+            for r, w in parts:
+                dev, rows = r.z.device, min(r.n_turns, t)
+                pad = t - rows
+                # (rows past a batch's last turn: what the one launch records after a game's end -- the final
+                # boards still swapping sides, no move)
+                tw = (torch.arange(rows, t, device=dev) % 2 == 0).reshape(pad, 1)
+                p1, p2 = r.final_p1[:w].reshape(1, w), r.final_p2[:w].reshape(1, w)
+                cols["own"].append(torch.cat([r.own[:rows, :w], torch.where(tw, p1, p2)]))
+                cols["opp"].append(torch.cat([r.opp[:rows, :w], torch.where(tw, p2, p1)]))
+                cols["valid"].append(torch.cat([r.valid[:rows, :w], r.valid.new_zeros((pad, w))]))
+                cols["move"].append(torch.cat([r.move[:rows, :w], r.move.new_full((pad, w), -1)]))
+                cols["pi"].append(torch.cat([r.pi[:rows, :w], r.pi.new_zeros((pad, w, 64))]))
+            for k, v in cols.items():
+                setattr(res, k, torch.cat(v, dim=1))
         return res

@@ -556,7 +556,12 @@ typedef struct iago_mcts_search_args {
                              sequence of playouts, hence every tree and move, is unchanged.  0 = default (16), < 0 = off */
     int32_t max_cus;      /* CUs the launch may count on when fewer than the device's are free for it (a CU-masked stream, a
                              device shared with another job); 0 = all CUs of the device */
-    int32_t reserved;
+    int32_t games_total;  /* 0: as above.  > 0: a self-play STREAM of that many whole games (max_turns > 0, n_sims >= 1, no
+                             z_log / trace; `active` is not read), the tree's n_games of them in play: slot g starts game g;
+                             a game workgroup whose games are all over claims the next ids (ctl[12]), one per slot, resets
+                             the slots' trees (not their overflow flags) and plays those games.  game_own / game_opp / n_turns are [games_total], rec_* [max_turns]
+                             [games_total], indexed by the game; its rollouts draw with id_base + G: game G is game G % n_games
+                             of a launch with games_total 0 and id_base + G - G % n_games, bit for bit */
 } iago_mcts_search_args;
 IAGO_API int iago_mcts_search_persistent(const iago_mcts_search_args *args, void *stream);
 /*
