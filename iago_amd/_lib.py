@@ -161,6 +161,13 @@ class MctsValueAhead(C.Structure):
 
 SEARCH_QUEUE_ENTRIES = 4096   # IAGO_SEARCH_QUEUE_ENTRIES
 SEARCH_GAMES_PER_WORKGROUP = 32   # IAGO_SEARCH_GAMES_PER_WORKGROUP
+# whole-game launches (max_turns > 0, games_total = 0): iago_mcts_search_args.active[g] selects the game's kind
+MATCH_MCTS_COLOUR_1 = 2   # a match: PV-MCTS plays colour 1 (moves first), the SL policy colour 2
+MATCH_MCTS_COLOUR_2 = 3   # a match: PV-MCTS plays colour 2, the SL policy colour 1 (the reference's game.py --auto)
+MATCH_KEY = 0x4D415443    # a match's policy draws: Philox key = the rollout seed with its high word XOR this
+MATCH_SEED_XOR = MATCH_KEY << 32
+CTL_BAD_DRAW = 13         # ctl word a match raises when a policy draw found no mass on the legal moves
+REC_DRAWN = 2             # rec_valid of a move played without a search (a policy draw or a forced final move)
 
 
 class MctsSearchArgs(C.Structure):

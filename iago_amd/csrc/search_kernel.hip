@@ -49,6 +49,7 @@
 #include "mcts_dev.hpp"
 #include "conv_trunk_body.hpp" // (brings rollout_row_body.hpp)
 #include "conv_policy_body.hpp"
+#include "sample_dev.hpp"
 
 #include <cstdlib>
 
@@ -65,8 +66,11 @@ constexpr int CTL_FINISHED = 2, CTL_ABORT = 3;
 // two request rings, one per kind of net work: head (tickets handed out) / tail (entries reserved) of ring q
 __host__ __device__ constexpr int ctl_head(uint32_t q) { return 8 + 2 * (int)q; }
 __host__ __device__ constexpr int ctl_tail(uint32_t q) { return 9 + 2 * (int)q; }
-enum { ST_READY = 0, ST_WAIT_PRIOR, ST_PRIOR_READY, ST_ROLL, ST_ROLL_FRESH, ST_WAIT_VALUE, ST_HAVE_VALUE, ST_DONE, ST_TURN, ST_MOVE };
+enum { ST_READY = 0, ST_WAIT_PRIOR, ST_PRIOR_READY, ST_ROLL, ST_ROLL_FRESH, ST_WAIT_VALUE, ST_HAVE_VALUE, ST_DONE, ST_TURN, ST_MOVE,
+       ST_WAIT_DRAW, ST_DRAW }; // (a match: the policy side waits for its move's distribution, then draws)
 constexpr int CTL_NO_CHILDREN = 4; // a searched root had no children (n_sims below n_thr)
+constexpr uint32_t MATCH_KEY = 0x4D415443u; // ("MATC") a match's policy draws: the rollout key's high word XOR this
+constexpr int CTL_BAD_DRAW = 13;   // a match: a policy draw found no probability mass on the legal moves (NaN / zero)
 // pacing (below): sum over the games in play of their progress (turn x n_sims + playouts of the turn), games in play
 constexpr int CTL_PROGRESS = 5, CTL_PLAYING = 6;
 constexpr int CTL_NET_WGS = 7;            // net workgroups of this launch (written by the launch: the grid follows the device)
@@ -234,6 +238,31 @@ __device__ __forceinline__ bool group8_all(bool x)
     return group8_add(x ? 0u : 1u) == 0u;
 }
 
+// A match's policy move (game.py:100-104): sample_wave's draw from the 64 replies of the game's mailbox -- p = prob x valid /
+// sum, float64 sums in cell order, the first cell whose cdf / cdf[-1] exceeds u -- run whole by every lane of the game (8
+// lanes, no LDS row to share): bit-identical to sample_moves.  64: no mass on the legal moves (NaN / inf / zero)
+__device__ __forceinline__ int policy_draw(const u64 *rep, uint64_t lg, double u)
+{
+    double s = 0.0; // np.sum(prob * valid)
+#pragma unroll 1
+    for (int j = 0; j < 64; j++)
+        s += ((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0;
+    double last = 0.0; // cumsum(p / s)[-1]
+#pragma unroll 1
+    for (int j = 0; j < 64; j++)
+        last += (((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0) / s;
+    if (!(s > 0.0) || !(s <= 1.7976931348623157e308) || !(last > 0.0))
+        return 64;
+    double acc = 0.0;
+    int n = 0; // searchsorted(cdf, u, side='right')
+#pragma unroll 1
+    for (int j = 0; j < 64; j++) {
+        acc += (((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0) / s;
+        n += acc / last <= u ? 1 : 0;
+    }
+    return n;
+}
+
 // Node.update_recursive (MCTS.py:51-72) over the recorded path + the leaf mix (MCTS.py:123-125): the
 // arithmetic of mix_backup_path_kernel, 8 lanes per game.
 __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, uint32_t r, int leaf, bool fresh, float vg,
@@ -351,13 +380,28 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
         bool busy = false; // this game did something in this iteration
         if (mine) {
             // ---- replies
-            if (state == ST_WAIT_PRIOR) {
+            if (state == ST_WAIT_PRIOR || state == ST_WAIT_DRAW) {
                 bool ok = true;
 #pragma unroll
                 for (int i = 0; i < 8; i++)
                     ok = ok && (uint32_t)(ld(&S.rep_p[g * 64 + (int)r * 8 + i]) >> 32) == epoch;
-                if (group8_all(ok))
-                    state = ST_PRIOR_READY;
+                if (group8_all(ok)) {
+                    if (state == ST_WAIT_DRAW) {
+                        // np.random.choice(64, p=prob*valid/np.sum(prob*valid)) (game.py:102-104) with the uniform of
+                        // (seed ^ MATCH_KEY << 32, game id, turn, stream 0): ops.sample_moves' draw.  (The move waits in
+                        // `leaf`, which no search of this game reads before the move is played)
+                        const uint64_t lg = group8_legal(to_lane(g_own, L), to_lane(g_opp, L), L);
+                        const double u = sample_uniform(R.key0, R.key1 ^ MATCH_KEY, R.id_base + (uint32_t)h_game[gl],
+                                                        (uint32_t)turn, 0u);
+                        leaf = policy_draw(S.rep_p + g * 64, lg, u);
+                        if (leaf == 64) { // (numpy raises: the engine does, from this flag; the game goes on meanwhile)
+                            if (r == 0u)
+                                __hip_atomic_store(&S.ctl[CTL_BAD_DRAW], 1u, RLX_AGENT);
+                            leaf = (int)__builtin_ctzll(lg);
+                        }
+                    }
+                    state = state == ST_WAIT_PRIOR ? ST_PRIOR_READY : ST_DRAW;
+                }
             } else if (state == ST_WAIT_VALUE) {
                 const u64 x = ld(&S.rep_v[g]);
                 if ((uint32_t)(x >> 32) == epoch) {
@@ -382,20 +426,34 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             // or is over (a pass leads straight on to the next turn: at most a few rounds)
             if (whole) {
                 for (int rep = 0; rep < 6; rep++) {
-                    const bool at_move = state == ST_MOVE, at_turn = state == ST_TURN;
-                    if (__builtin_amdgcn_ballot_w64(at_move || at_turn) == 0ull)
+                    const bool at_move = state == ST_MOVE, at_turn = state == ST_TURN, at_draw = state == ST_DRAW;
+                    if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
                         break;
-                    busy = busy || at_move || at_turn;
+                    busy = busy || at_move || at_turn || at_draw;
                     const uint64_t lg = group8_legal(to_lane(g_own, L), to_lane(g_opp, L), L);
                     const bool can_move = lg != 0ull && !g_over;
-                    if (at_turn && can_move) {
+                    // a match (active 2: PV-MCTS plays colour 1, 3: colour 2; game.py:96-118): the final move when it is
+                    // the only one is played as it is, by either side (no search, no update_with_move), and the SL
+                    // policy's turn asks its net for the position and waits to draw
+                    const int code = (at_turn && can_move && !S.stream) ? (int)S.active[g] : 0;
+                    const bool match = code == 2 || code == 3;
+                    const bool forced = match && stones > 62 && __popcll(lg) == 1;
+                    const bool policy_turn = match && !forced && (turn & 1) == (code == 2 ? 1 : 0);
+                    if (policy_turn) {
+                        epoch++;
+                        if (r == 0u)
+                            send_request(S, KIND_POLICY, g, epoch, g_own, g_opp); // make_state_var(state, color)
+                        state = ST_WAIT_DRAW;
+                    }
+                    if (at_turn && can_move && !forced && !policy_turn) {
                         // the mover searches: MCTS.get_move(state, color) (game.py:112)
                         n_done = 0;
                         if (r == 0u)
                             S.done[g] = turn * S.n_sims; // (the rollouts' Philox stream: stream base + turn x n_sims + playout)
                         state = ST_READY;
                     }
-                    const bool moving = at_move || (at_turn && !can_move);
+                    const bool drawn = at_draw || forced; // a stone placed without a search
+                    const bool moving = at_move || drawn || (at_turn && !can_move);
                     // the root's children are the mover's legal moves in ascending order (Node.expand)
                     const int root = moving ? T.root[g] : 0;
                     const int rfc = moving ? T.nodes[base + root].first_child : -1;
@@ -425,21 +483,25 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             if (mv == -2 && r == 0u) // max() of an empty children dict (MCTS.py:147): n_sims < n_thr
                                 __hip_atomic_store(&S.ctl[CTL_NO_CHILDREN], 1u, RLX_AGENT);
                         }
+                        if (at_draw)
+                            mv = leaf; // the policy's draw
+                        if (forced)
+                            mv = (int)__builtin_ctzll(lg); // game.py:97-98
                         if (S.rec_move) {
                             const int64_t row = (int64_t)turn * S.games_total + h_game[gl];
                             if (r == 0u) {
                                 S.rec_own[row] = g_own;
                                 S.rec_opp[row] = g_opp;
-                                S.rec_valid[row] = at_move ? 1 : 0;
-                                S.rec_move[row] = (int8_t)(at_move ? mv : -1);
+                                S.rec_valid[row] = at_move ? 1 : (drawn ? 2 : 0);
+                                S.rec_move[row] = (int8_t)(at_move || drawn ? mv : -1);
                             }
 #pragma unroll
                             for (int i = 0; i < 8; i++)
                                 S.rec_pi[row * 64 + (int)(8u * r) + i] = row_n[i];
                         }
                         // MCTS.update_with_move (MCTS.py:149-154) for the games not over: the child becomes the root,
-                        // or (no such child) a fresh Node(None, 1.0)
-                        if (!g_over && r == 0u) {
+                        // or (no such child) a fresh Node(None, 1.0) -- not after a forced final move (game.py:97-98)
+                        if (!g_over && !forced && r == 0u) {
                             int child = -1;
                             if (rfc >= 0) {
                                 if (mv >= 0 && ((lg >> mv) & 1ull))
@@ -457,7 +519,8 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             }
                         }
                         // the stone, the books, the swap of sides (iago_play_turn; game.py:117-142,253-255)
-                        const bool placed = at_move && mv >= 0;
+                        const bool played = at_move || drawn;
+                        const bool placed = played && mv >= 0;
                         const uint64_t f = group8_flips(to_lane(g_own, L), to_lane(g_opp, L), (uint32_t)mv & 63u, L);
                         uint64_t o = g_own, p = g_opp;
                         if (placed) {
@@ -466,8 +529,8 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             p = g_opp & ~f & ~bit;
                         }
                         const bool was_over = g_over;
-                        stones += at_move ? 1 : 0;
-                        const bool passing = !at_move && !was_over;
+                        stones += played ? 1 : 0;
+                        const bool passing = !played && !was_over;
                         if (passing && pass_flg)
                             stones = 64;                       // a pass after a pass ends the game
                         if (!was_over)

@@ -16,6 +16,7 @@ n_thr simulations, no sign flip in backup, pass = action -1, subtree reuse.
 The wall-clock budget (10 s per move, MCTS.py:142) becomes a simulation count.
 """
 import ctypes as C
+import numbers
 import os
 
 import torch
@@ -1317,6 +1318,33 @@ class SelfPlayResult(object):
                     turn=turn.expand(T, B).reshape(-1)[m])
 
 
+_BAD_DRAW = ("a match's policy draw met NaN / inf / zero probability mass on the legal moves (numpy.random.choice "
+             "raises there, game.py:102-104)")
+
+
+class MatchResult(SelfPlayResult):
+    """The games of SelfPlayEngine.play_match: PV-MCTS against the SL policy (game.py:96-145,246-262).  As a
+    SelfPlayResult, with valid 1 where PV-MCTS searched, 2 where a move was played without a search (the policy's
+    draw, or a final move that was the only one: pi is 0 there), 0 for a pass or no turn; mcts_colour: (B,) int8, the
+    colour PV-MCTS played in each game."""
+
+    def tuples(self):
+        """SelfPlayResult.tuples() of the positions PV-MCTS searched (valid == 1) only."""
+        full = self.valid
+        try:
+            self.valid = (full == 1).to(full.dtype)
+            return SelfPlayResult.tuples(self)
+        finally:
+            self.valid = full
+
+    def score(self):
+        """PV-MCTS's results: dict(wins, draws, losses, n, win_rate), a draw counting 1/2."""
+        z = self.z.to(torch.int32) * torch.where(self.mcts_colour == 1, 1, -1).to(torch.int32)
+        wins, draws, losses = (int(v) for v in torch.stack([(z > 0).sum(), (z == 0).sum(), (z < 0).sum()]).tolist())
+        n = wins + draws + losses
+        return dict(wins=wins, draws=draws, losses=losses, n=n, win_rate=(wins + 0.5 * draws) / n if n else float("nan"))
+
+
 def _end_turns(valid):
     """(B,) each game's end turn from its records valid (T, B): the books of game.py:117-142,253-255 as the one-launch
     path keeps them -- a stone per move, a pass after a pass ends the game, `while stone_num < 64` once per pair of
@@ -1349,12 +1377,13 @@ class SelfPlayEngine(object):
         self.B = mcts.n_games
         self.max_turns = max_turns
 
-    def _play_persistent(self, n_sims, own, opp, record, games_total=0):
+    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
         loop below (tests/test_search_persistent_gpu.py).  games_total > 0: the games_total games of own / opp
-        as a stream through the B slots (play_stream)."""
+        as a stream through the B slots (play_stream).  active: (B,) uint8 kinds of game (play_match's codes), default
+        all self-play; res: the result object to fill (default a SelfPlayResult)."""
         m, T = self.mcts, self.max_turns
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
@@ -1364,7 +1393,8 @@ class SelfPlayEngine(object):
                  rec_valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
                  rec_move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
                  rec_pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev))
-        active = torch.ones(self.B, dtype=torch.uint8, device=dev)
+        if active is None:
+            active = torch.ones(self.B, dtype=torch.uint8, device=dev)
         if m.value_cache:
             key = tuple((q.data_ptr(), q._version) for q in m.value_fn.parameters())
             if key != m._value_key:
@@ -1378,8 +1408,9 @@ class SelfPlayEngine(object):
         m._launch_persistent(None, None, active, n_sims, game=g)
         back = torch.cat([m.error_flags(), m._ps["ctl"][4].to(torch.int64).reshape(1),
                           g["n_turns"].max().to(torch.int64).reshape(1),
-                          g["rec_valid"].sum().to(torch.int64).reshape(1),
-                          m._ps["ctl"][7].to(torch.int64).reshape(1)]).tolist()
+                          (g["rec_valid"] == 1).sum().to(torch.int64).reshape(1),
+                          m._ps["ctl"][7].to(torch.int64).reshape(1),
+                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)]).tolist()
         m.net_workgroups_launched = int(back[8])
         if back[0] and not back[4]:
             # a pool filled up (the launch cannot compact): nothing of this attempt counts
@@ -1389,10 +1420,12 @@ class SelfPlayEngine(object):
         m.raise_errors(back[:5])
         if back[5]:
             raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
+        if back[9]:
+            raise _lib.IagoError(_BAD_DRAW)
         t = int(back[6])
         m.sim_counter = (m.sim_counter + t * n_sims) & 0xFFFFFFFF
         m.n_leaf_evals += int(back[7]) * n_sims
-        res = SelfPlayResult()
+        res = SelfPlayResult() if res is None else res
         res.game_id_base = m.game_id_base
         res.n_turns = t
         res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
@@ -1526,6 +1559,114 @@ class SelfPlayEngine(object):
                 return res
             self.n_replayed = getattr(self, "n_replayed", 0) + 1
         return self._play_batches(n_sims, n_games, handicap, record)
+
+    def _match_colours(self, mcts_colour):
+        """play_match's mcts_colour as a (B,) int8 device tensor of 1 / 2."""
+        dev = self.mcts.cur_own.device
+        if isinstance(mcts_colour, torch.Tensor):
+            if tuple(mcts_colour.shape) != (self.B,) or mcts_colour.is_floating_point() or mcts_colour.is_complex():
+                raise ValueError("play_match: mcts_colour is 1, 2 or a (%d,) integer tensor of 1 / 2" % self.B)
+            col = mcts_colour.to(device=dev, dtype=torch.int8)
+            if not bool(((col == 1) | (col == 2)).all()) or not torch.equal(col.to(mcts_colour.dtype).cpu(),
+                                                                            mcts_colour.cpu()):
+                raise ValueError("play_match: mcts_colour holds values other than 1 and 2")
+            return col
+        if isinstance(mcts_colour, bool) or not isinstance(mcts_colour, numbers.Integral) or mcts_colour not in (1, 2):
+            raise ValueError("play_match: mcts_colour is 1, 2 or a (%d,) integer tensor of 1 / 2" % self.B)
+        return torch.full((self.B,), int(mcts_colour), dtype=torch.int8, device=dev)
+
+    def play_match(self, n_sims, mcts_colour=2, record=True):
+        """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
+        `game.py --auto` (game.py:96-145,246-262) -- with the engine's nets: in game g PV-MCTS plays colour
+        mcts_colour[g] (1 moves first; an int: every game; 2, the default, is the reference's setting) and the policy
+        net (the engine's policy_fn) the other colour.  PV-MCTS searches from its tree as in play(); the policy's move is
+        the masked draw of ops.sample_moves from the net's distribution of the position, with the uniform of
+        (seed ^ MATCH_SEED_XOR, game_id_base + g, turn, stream 0), and advances the tree like any move (game.py:107); a
+        final move that is the only one (stone_num > 62) is played by either side without a search and without
+        update_with_move (game.py:97-98).  ONE launch of the persistent search where play() takes it, else (and when a
+        pool fills up in the launch) the turn loop below: the same games record for record.  sim_counter advances by
+        n_sims per turn, searched or not.  Returns a MatchResult."""
+        m, B, T = self.mcts, self.B, self.max_turns
+        col = self._match_colours(mcts_colour)
+        dev = m.cur_own.device
+        own = torch.full((B,), START_OWN, dtype=torch.int64, device=dev)
+        opp = torch.full((B,), START_OPP, dtype=torch.int64, device=dev)
+        m.tree.reset()
+        if self._whole_games_in_one_launch(n_sims):
+            codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
+            res = self._play_persistent(n_sims, own.clone(), opp.clone(), record, active=codes, res=MatchResult())
+            if res is not None:
+                res.mcts_colour, res.launches = col, 1
+                return res
+            self.n_replayed = getattr(self, "n_replayed", 0) + 1
+            m.tree.reset()
+        stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
+        pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        res = MatchResult()
+        res.game_id_base, res.mcts_colour = m.game_id_base, col
+        if record:
+            res.own = torch.zeros((T, B), dtype=torch.int64, device=dev)
+            res.opp = torch.zeros((T, B), dtype=torch.int64, device=dev)
+            res.pi = torch.zeros((T, B, 64), dtype=torch.int32, device=dev)
+            res.valid = torch.zeros((T, B), dtype=torch.uint8, device=dev)
+            res.move = torch.full((T, B), -1, dtype=torch.int8, device=dev)
+        res.mover = []
+        legal = ops.legal_moves(own, opp)
+        active = (legal != 0).to(torch.uint8)
+        legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
+        cells = torch.arange(64, device=dev)
+        key = m.seed ^ _lib.MATCH_SEED_XOR
+        pf = m.policy_fn
+        t = 0
+        while t < T:
+            on = active.bool()
+            mcts_moves = col == (1 if t % 2 == 0 else 2)
+            # game.py:97-98: the only move of the last empty square, either side, no search
+            forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
+            searched = on & mcts_moves & ~forced
+            drawn = on & ~mcts_moves & ~forced
+            s_act = searched.to(torch.uint8)
+            m.search(own, opp, s_act, n_sims, check=False)   # (sim_counter: + n_sims whoever searched)
+            move, visits = m.best_move(s_act)
+            with torch.no_grad():
+                if hasattr(pf, "forward_boards_split3"):
+                    probs = pf.forward_boards_split3(own, opp)
+                else:
+                    probs = pf(ops.encode_planes(own, opp))
+            draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)), seed=key,
+                                    id_base=m.game_id_base, step=t, stream_id=0)
+            only = ((legal.reshape(B, 1) >> cells) & 1).argmax(dim=1).to(torch.int8)
+            mv = torch.where(searched, move, torch.where(drawn, draw, torch.where(forced, only, torch.full_like(move, -1))))
+            if record:
+                res.own[t], res.opp[t], res.move[t] = own, opp, mv
+                res.valid[t] = s_act + 2 * (drawn | forced).to(torch.uint8)
+                res.pi[t] = visits * s_act.reshape(B, 1).to(torch.int32)
+            res.mover.append(1 if t % 2 == 0 else 2)
+            m.update_with_move(mv, ((done == 0) & ~forced).to(torch.uint8))  # game.py:107,113,140
+            bad_draw = (drawn & (draw == 64)).any()
+            ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
+            legal, legal_next = legal_next, legal
+            active, active_next = active_next, active
+            t += 1
+            back = torch.cat([m.error_flags(), (searched & (mv == -2)).any().to(torch.int64).reshape(1),
+                              bad_draw.to(torch.int64).reshape(1), done.all().to(torch.int64).reshape(1)]).tolist()
+            m.raise_errors(back[:5])
+            if back[5]:
+                raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
+            if back[6]:
+                raise _lib.IagoError(_BAD_DRAW)
+            if t % 2 == 0 and back[7]:
+                break
+        p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
+        res.z = ops.judge(p1, p2)
+        res.final_p1, res.final_p2 = p1, p2
+        res.n_turns, res.launches = t, t
+        res.game_turns = None
+        if record:
+            for name in ("own", "opp", "pi", "valid", "move"):
+                setattr(res, name, getattr(res, name)[:t])
+        return res
 
     def _play_batches(self, n_sims, n_games, handicap, record):
         """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same

@@ -515,19 +515,22 @@ typedef struct iago_mcts_search_args {
     uint64_t *wg_own, *wg_opp;
     /* Whole self-play games in the launch: max_turns > 0 (0: one search from root_own / root_opp).  Every game then
        also walks through its TURNS on its own clock -- the mover's legal moves (game.py:210-235); a search of n_sims
-       playouts and the most visited move (MCTS.get_move, MCTS.py:139-147), or a pass; MCTS.update_with_move
-       (MCTS.py:149-154); the stone and the books of game.py:117-142,253-255 (stone_num, pass_flg, `while
-       stone_num < 64` once per pair of turns: iago_play_turn's arithmetic) -- until it is over or max_turns turns
-       are played: what engine.SelfPlayEngine.play drives turn by turn for all games in lockstep.  Playout p of a
-       game's turn t draws from Philox stream rollout->stream_id + t * n_sims + p.  The trees must be reset and hold
-       a whole game (no compaction in the launch).
+       playouts and the most visited move (MCTS.py:139-147), or a pass; MCTS.update_with_move (MCTS.py:149-154); the
+       stone and the books of game.py:117-142,253-255 (iago_play_turn's arithmetic) -- until it is over or max_turns
+       turns are played: engine.SelfPlayEngine.play's turn loop.  Playout p of turn t draws from Philox stream
+       rollout->stream_id + t * n_sims + p.  The trees must be reset and hold a whole game (no compaction in the launch).
+       With games_total 0, active[g] picks the game: 0 none, 2 / 3 a MATCH (game.py:96-145,246-262) in which PV-MCTS
+       plays colour 1 / 2 and the SL policy (the `policy` net) the other colour, other values self-play.  A policy turn
+       plays iago_sample_moves' draw from the net's distribution of the position with the uniform of (rollout->seed ^
+       0x4D415443 << 32, rollout->id_base + g, step t, stream 0), then update_with_move; a final move that is the only
+       one (stone_num > 62, game.py:97-98) is played by either side without a search and without update_with_move.
          game_own / game_opp [n_games]: in: the start positions (own = the first mover); out: the final positions
            as they stand after n_turns swaps of sides;  n_turns [n_games]: out;
          rec_* (optional, all or none) [max_turns][n_games] (rec_pi: [max_turns][n_games][64] int32): per turn the
-           position before it (own = mover), whether the mover searched, the move (-1: pass / no turn), the root's
-           visit counts by action; rows of turns a game did not play are not written.
-       ctl [16]: ctl[3] != 0: gave up after time_limit_ms; ctl[4] != 0: a searched root had no children
-       (n_sims < n_thr: the reference's max() of an empty dict, MCTS.py:147). */
+           position before it (own = mover), rec_valid 1 (searched) / 2 (played without a search: rec_pi 0) / 0, the
+           move (-1: pass / no turn), the root's visit counts by action; rows of turns a game did not play are not written.
+       ctl [16]: ctl[3] != 0: gave up after time_limit_ms; ctl[4] != 0: a searched root had no children (n_sims < n_thr:
+       MCTS.py:147); ctl[13] != 0: a match's draw met NaN / zero mass (numpy raises; the game went on at the lowest move). */
     int32_t max_turns;
     int32_t games_per_workgroup; /* games a game workgroup owns: 0 (= IAGO_SEARCH_GAMES_PER_WORKGROUP), 8, 16 or 32; the first
                                     ceil(n_games / that) workgroups of the grid are the game workgroups */
