@@ -9,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace iago_trunk {
 
@@ -99,13 +100,51 @@ __device__ __forceinline__ int cell_of_lane(int r)
 
 extern __shared__ __align__(16) char trunk_lds[];
 
+// The K loop's B tiles for TB boards per workgroup, in the order they run within a chunk pair: tap-major, tile n of
+// a tap = tap * 4 TB + n.  TB >= 2 (row tiles, trunk_item): the tiles wholly off the board are left out -- row 0 of
+// a board pair under ky = 0 (taps 0-2), row 7 under ky = 2 (taps 6-8).
+constexpr bool tile_off_board(int tb, int tap, int n)
+{
+    return tb >= 2 && ((tap < 3 && (n & 7) == 0) || (tap >= 6 && (n & 7) == 7));
+}
+// kept tiles of a chunk pair that run before tile n of tap `tap` (tap 9: all of them)
+constexpr int kept_before(int tb, int tap, int n)
+{
+    int k = 0;
+    for (int t = 0; t < 9; t++)
+        for (int m = 0; m < 4 * tb; m++) {
+            if (t == tap && m == n)
+                return k;
+            k += !tile_off_board(tb, t, m);
+        }
+    return k;
+}
+// tap * 4 TB + n of the k-th kept tile of a chunk pair
+constexpr int kept_tile(int tb, int k)
+{
+    for (int t = 0; t < 9; t++)
+        for (int m = 0; m < 4 * tb; m++)
+            if (!tile_off_board(tb, t, m) && k-- == 0)
+                return t * 4 * tb + m;
+    return -1;
+}
+// f(std::integral_constant<int, I>) for I = I0 .. I1 - 1, in order (the body sees I as a constant expression)
+template <int I0, int I1, class F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (I0 < I1) {
+        f(std::integral_constant<int, I0>{});
+        static_for<I0 + 1, I1>(f);
+    }
+}
+
 // The work of one workgroup on the TB boards (rows) b0 .. b0 + TB - 1 of n_rows.
 // SRCH: the persistent search's form -- W.pos, W.res, W.w1s and W.head_w are all given (decided at compile time: as
 // run-time choices both forms' registers were live in the head and the kernel spilled 103 of them)
 template <bool FUSED, int TB, bool SRCH = false>
 __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W, const int64_t b0, const int64_t n_rows)
 {
-    constexpr int NN = 4 * TB;      // 16-cell B tiles of a k-step: TB boards x 4 quarters
+    constexpr int NN = 4 * TB;      // 16-cell B tiles of a k-step: TB boards x 4 quarters (TB >= 2: x 8 rows / 2)
     char *const T = trunk_lds;
     // (SRCH: the walk is called from the net workgroups' loop.  Everything below that depends on the thread alone -- the
     // 36 B-operand addresses, the rows of the epilogue, the A operands' lane offset -- would be hoisted out of that loop,
@@ -262,29 +301,64 @@ __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W
 
     // ---- per-lane addresses of the B operand.  The K loop runs on v_mfma_f32_16x16x32_f16: lane = (column c16 =
     // lane & 15, k quarter kq = lane >> 4); a k-step covers 32 input channels = two 16-channel chunks at one tap,
-    // a B tile is 16 cells (quarter q of a board) x 32 channels: this lane reads cell 16 q + c16, channels 8 kq ..
-    // 8 kq + 7 of the chunk pair (16 bytes at + 16 kq), tap (ky, kx).  Boards 0 / 1 through addr (+ an immediate BS
-    // for the odd board), boards 2 / 3 by adding 2 BS; the hi / lo halves of a row are 256 B apart (immediate)
+    // a B tile is 16 cells x 32 channels: this lane reads its cell of the tile, channels 8 kq .. 8 kq + 7 of the chunk
+    // pair (16 bytes at + 16 kq), tap (ky, kx); the hi / lo halves of a row are 256 B apart (immediate).
+    // TB = 1: tile n = quarter n of the board (cells 16 n + c16), one address per (quarter, tap).
+    // TB >= 2: tile n = row n & 7 of the board pair n >> 3 -- lanes c16 < 8 take cell 8 row + c16 of the even board,
+    // lanes c16 >= 8 cell 8 row + c16 - 8 of the odd one.  Then row 0 is wholly off the board under the three taps of
+    // ky = 0 and row 7 under those of ky = 2: those tiles' MFMAs would only add zeros and are left out (6 of the 72
+    // tiles of a pair's chunk pair).  Every kept (row, tap) has its row in the board, so only kx decides whether a
+    // lane's cell is in the board: one address per tap (its first kept row), moved on by 8 RS per row -- by 0 for
+    // the lanes of the zero slot (kx != 1: the stride registers sx) and as an immediate for kx = 1.  The board
+    // stride BS = 0 mod 256 B keeps the 16 lanes of a ds_read_b128 cycle on 16 different 4-bank groups: the even
+    // board's cells 0-3 (kq) and 4-7 (kq + 1) meet the odd board's cells 4-7 (kq) and 0-3 (kq + 1)
+    constexpr bool ROWS = TB >= 2;
+    static_assert(TB == 1 || TB == 2 || TB == 4, "boards per workgroup");
     const int c16 = lane & 15, kq = lane >> 4;
-    uint32_t addr[4][9]; // [quarter][tap]
-#pragma unroll
-    for (int q = 0; q < 4; q++)
+    constexpr int NADDR = ROWS ? 9 : 36;
+    uint32_t addr[NADDR]; // ROWS: [tap]; TB = 1: [9 quarter + tap]
+    uint32_t sx[2] = {0u, 0u}; // ROWS: the row stride under kx = 0 and kx = 2
+    uint32_t wrow[ROWS ? 1 : 4]; // rows this lane writes in the epilogue (ROWS: its cell of row 0 of pair 0)
+    if constexpr (ROWS) {
+        const int x = c16 & 7, odd = c16 >> 3;
 #pragma unroll
         for (int tap = 0; tap < 9; tap++) {
-            const int cell = 16 * q + c16;
-            const int yy = (cell >> 3) + tap / 3 - 1, xx = (cell & 7) + tap % 3 - 1;
-            const bool ok = yy >= 0 && yy < 8 && xx >= 0 && xx < 8;
-            // an out-of-board tap reads zeros from the slot with the bank offset its row would have had (rows are
-            // 2 x 16 B apart mod 256 B: 32 B per row index mod 8): the 16 lanes of an LDS cycle keep 16 different
-            // 4-bank groups whether or not some of them are redirected
-            const int lin = (cell + (tap / 3 - 1) * 8 + (tap % 3 - 1)) & 7;
-            addr[q][tap] = (uint32_t)((ok ? (yy * 8 + xx) * RS : 64 * RS + 32 * lin) + kq * 16);
+            const int row = tap < 3 ? 1 : 0; // the first row this tap reads: row 0 is skipped under ky = 0
+            const int yy = row + tap / 3 - 1, xx = x + tap % 3 - 1;
+            const bool ok = xx >= 0 && xx < 8;
+            // an out-of-board tap reads zeros from its board's slot with the bank offset its cell would have had
+            addr[tap] = (uint32_t)(odd * BS + (ok ? (yy * 8 + xx) * RS : 64 * RS + 32 * (xx & 7)) + kq * 16);
         }
-    // rows this lane writes in the epilogue (its cell of every quarter)
-    uint32_t wrow[4];
+        sx[0] = x > 0 ? 8u * RS : 0u;
+        sx[1] = x < 7 ? 8u * RS : 0u;
+        wrow[0] = (uint32_t)(odd * BS + x * RS);
+    } else {
 #pragma unroll
-    for (int q = 0; q < 4; q++)
-        wrow[q] = (uint32_t)((16 * q + c16) * RS);
+        for (int q = 0; q < 4; q++)
+#pragma unroll
+            for (int tap = 0; tap < 9; tap++) {
+                const int cell = 16 * q + c16;
+                const int yy = (cell >> 3) + tap / 3 - 1, xx = (cell & 7) + tap % 3 - 1;
+                const bool ok = yy >= 0 && yy < 8 && xx >= 0 && xx < 8;
+                // an out-of-board tap reads zeros from the slot with the bank offset its row would have had (rows are
+                // 2 x 16 B apart mod 256 B: 32 B per row index mod 8): the 16 lanes of an LDS cycle keep 16 different
+                // 4-bank groups whether or not some of them are redirected
+                const int lin = (cell + (tap / 3 - 1) * 8 + (tap % 3 - 1)) & 7;
+                addr[9 * q + tap] = (uint32_t)((ok ? (yy * 8 + xx) * RS : 64 * RS + 32 * lin) + kq * 16);
+            }
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            wrow[q] = (uint32_t)((16 * q + c16) * RS);
+    }
+    // byte offset in T of this lane's B operand for tile n of tap `tap` (constants after unrolling)
+    auto b_off = [&](int tap, int n) -> uint32_t {
+        if constexpr (ROWS) {
+            const int dx = tap % 3 - 1, r = (n & 7) - (tap < 3 ? 1 : 0);
+            return addr[tap] + (uint32_t)r * (dx == 0 ? 8u * RS : sx[dx > 0]) + (uint32_t)(n >> 3) * (2u * BS);
+        } else {
+            return addr[9 * n + tap];
+        }
+    };
 
     const int L_lo = PIECES ? W.layer_lo : 0, L_hi = PIECES ? W.layer_hi : P.n_layers;
     for (int L = L_lo; L < L_hi; L++) {
@@ -317,27 +391,31 @@ __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W
                 a_hi[i][m] = a_load(wh, (uint32_t)i * 4096u, m);
                 a_lo[i][m] = a_load(wl, (uint32_t)i * 4096u, m);
             }
-        // B operands THREE tiles ahead of the MFMAs that use them (four register sets): an LDS read issued now has
+        // B operands THREE kept tiles ahead of the MFMAs that use them (a ring of NR register sets: NR divides the
+        // kept tiles of a chunk pair, so the ring lines up again at every chunk pair): an LDS read issued now has
         // eighteen MFMAs (288 cycles) to arrive.  A v_mfma_f32_16x16x32_f16 leaves 8 of its 16 cycles to the wave's
         // other instructions: the two reads of a tile go out one per MFMA gap, and the two MFMAs that add into the
         // same accumulator stand four apart (measured with tools/exp_walk_stamps.py on the stamped build: with the
         // reads bunched between two tiles and one MFMA between the dependent pair the K loops of a pair took 99.6 us
         // against 75.9 us of MFMA issue; LABNOTES.md, round 5)
-        half8 bh[4], bl[4];
-        auto b_addr = [&](int tile) -> const char * {
-            // tile = tap * NN + n of the running chunk pair; 9 NN .. 9 NN + 2 = the first three tiles of the next pair
-            const int over = tile >= 9 * NN ? 64 : 0, tt = tile % (9 * NN), tp = tt / NN, n = tt % NN;
-            return T + addr[n & 3][tp] + (n >> 2) * BS + over;
-        };
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const char *p0 = b_addr(i);
-            bh[i] = *(const half8 *)p0;
-            bl[i] = *(const half8 *)(p0 + 256);
-        }
+        constexpr int KEPT = kept_before(TB, 9, 0), NR = KEPT % 4 == 0 ? 4 : 6;
+        static_assert(KEPT % NR == 0, "the B ring must line up at every chunk pair");
+        half8 bh[NR], bl[NR];
+        static_for<0, 3>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int tile = kept_tile(TB, decltype(kc)::value);
+            const char *p0 = T + b_off(tile / NN, tile % NN);
+            bh[decltype(kc)::value] = *(const half8 *)p0;
+            bl[decltype(kc)::value] = *(const half8 *)(p0 + 256);
+        });
         for (int cp = 0; cp < n_pairs; cp++) {
-#pragma unroll
-            for (int tap = 0; tap < 9; tap++) {
+            static_for<0, KEPT>([&](auto kc) __attribute__((always_inline)) {
+                constexpr int k = decltype(kc)::value, tile = kept_tile(TB, k), tap = tile / NN, n = tile % NN;
+                constexpr int j = k - kept_before(TB, tap, 0); // this tile's place among the kept tiles of its tap
+                static_assert(kept_before(TB, tap + 1, 0) - kept_before(TB, tap, 0) >= 4, "four A loads per k-step");
+                // the tile whose operands are fetched now: three kept tiles on, in the next chunk pair past the end of
+                // this one (64 B further in every row; past the last chunk pair: harmless reads of the same rows)
+                constexpr int kn = k + 3, tile_n = kept_tile(TB, kn % KEPT), cur = k % NR, nxt = kn % NR;
+                constexpr uint32_t over = kn >= KEPT ? 64u : 0u;
                 // k-step s + 2 (the last two prefetches repeat the last k-step): weights at (18 cp + tap) x 256
                 int cp2 = cp, tp2 = tap + 2;
                 if (tp2 >= 9) {
@@ -351,48 +429,39 @@ __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W
                 const uint32_t w2 = (uint32_t)(18 * cp2 + tp2) * 4096u; // (its four loads go out one per tile below)
                 const half8 ah0 = __builtin_bit_cast(half8, a_hi[tap % 3][0]), ah1 = __builtin_bit_cast(half8, a_hi[tap % 3][1]);
                 const half8 al0 = __builtin_bit_cast(half8, a_lo[tap % 3][0]), al1 = __builtin_bit_cast(half8, a_lo[tap % 3][1]);
-#pragma unroll
-                for (int n = 0; n < NN; n++) {
-                    const int tile = tap * NN + n, cur = tile % 4, nxt = (tile + 3) % 4;
-                    // (past the last chunk pair: harmless reads 64 B further in the same rows)
-                    const char *p = b_addr(tile + 3);
-                    __builtin_amdgcn_sched_barrier(0);
-                    IAGO_MFMA16(acc_cross[0][n], ah0, bl[cur]);
-                    bh[nxt] = *(const half8 *)p;
-                    __builtin_amdgcn_sched_barrier(0);
-                    IAGO_MFMA16(acc_cross[1][n], ah1, bl[cur]);
-                    bl[nxt] = *(const half8 *)(p + 256);
-                    __builtin_amdgcn_sched_barrier(0);
-                    IAGO_MFMA16(acc_main[0][n], ah0, bh[cur]);
-                    // the A operands of k-step s + 2: one 16-byte load in this gap of each of the step's first four tiles
-                    if (n == 0)
-                        a_hi[(tap + 2) % 3][0] = a_load(wh, w2, 0);
-                    else if (n == 1)
-                        a_hi[(tap + 2) % 3][1] = a_load(wh, w2, 1);
-                    else if (n == 2)
-                        a_lo[(tap + 2) % 3][0] = a_load(wl, w2, 0);
-                    else if (n == 3)
-                        a_lo[(tap + 2) % 3][1] = a_load(wl, w2, 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                    IAGO_MFMA16(acc_main[1][n], ah1, bh[cur]);
-                    IAGO_MFMA16(acc_cross[0][n], al0, bh[cur]);
-                    IAGO_MFMA16(acc_cross[1][n], al1, bh[cur]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+                const char *p = T + b_off(tile_n / NN, tile_n % NN) + over;
+                __builtin_amdgcn_sched_barrier(0);
+                IAGO_MFMA16(acc_cross[0][n], ah0, bl[cur]);
+                bh[nxt] = *(const half8 *)p;
+                __builtin_amdgcn_sched_barrier(0);
+                IAGO_MFMA16(acc_cross[1][n], ah1, bl[cur]);
+                bl[nxt] = *(const half8 *)(p + 256);
+                __builtin_amdgcn_sched_barrier(0);
+                IAGO_MFMA16(acc_main[0][n], ah0, bh[cur]);
+                // the A operands of k-step s + 2: one 16-byte load in this gap of each of the tap's first four kept tiles
+                if constexpr (j == 0)
+                    a_hi[(tap + 2) % 3][0] = a_load(wh, w2, 0);
+                else if constexpr (j == 1)
+                    a_hi[(tap + 2) % 3][1] = a_load(wh, w2, 1);
+                else if constexpr (j == 2)
+                    a_lo[(tap + 2) % 3][0] = a_load(wl, w2, 0);
+                else if constexpr (j == 3)
+                    a_lo[(tap + 2) % 3][1] = a_load(wl, w2, 1);
+                __builtin_amdgcn_sched_barrier(0);
+                IAGO_MFMA16(acc_main[1][n], ah1, bh[cur]);
+                IAGO_MFMA16(acc_cross[0][n], al0, bh[cur]);
+                IAGO_MFMA16(acc_cross[1][n], al1, bh[cur]);
+                __builtin_amdgcn_sched_barrier(0);
+            });
             // next chunk pair of 32 input channels: 64 B further in every row (the zero rows are RS bytes of
             // zeros and more: their addresses move along)
 #pragma unroll
-            for (int q = 0; q < 4; q++)
-#pragma unroll
-                for (int tap = 0; tap < 9; tap++)
-                    addr[q][tap] += 64u;
+            for (int i = 0; i < NADDR; i++)
+                addr[i] += 64u;
         }
 #pragma unroll
-        for (int q = 0; q < 4; q++)
-#pragma unroll
-            for (int tap = 0; tap < 9; tap++)
-                addr[q][tap] -= 64u * (uint32_t)n_pairs;
+        for (int i = 0; i < NADDR; i++)
+            addr[i] -= 64u * (uint32_t)n_pairs;
 
         // ---- epilogue: every wave has read T for the last time; bias, ReLU, split, back into T
         // bias of the 8 channels this lane finishes: 32 wv + 16 m + 4 kq + v
@@ -414,8 +483,8 @@ __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W
         f2 vsum = (f2){0.0f, 0.0f};
 #pragma unroll
         for (int n = 0; n < NN; n++) {
-            // D row 4 kq + v of M tile m, column c16: channel 32 wv + 16 m + 4 kq + v of cell 16 (n & 3) + c16, board n >> 2
-            char *row = T + wrow[n & 3] + (n >> 2) * BS + (32 * wv + 4 * kq) * 2;
+            // D row 4 kq + v of M tile m, column c16: channel 32 wv + 16 m + 4 kq + v of column c16's cell of tile n
+            char *row = T + (ROWS ? wrow[0] + (n & 7) * (8 * RS) + (n >> 3) * (2 * BS) : wrow[ROWS ? 0 : n]) + (32 * wv + 4 * kq) * 2;
 #pragma unroll
             for (int m = 0; m < 2; m++) {
                 h2 hi[2], lo[2];

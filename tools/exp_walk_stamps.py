@@ -36,7 +36,8 @@ def main():
         res = {"error": str(e)[:200]}
     assert L.iago_debug_walk_stamps(buf, 1) == 0
     st = list(buf)
-    for name, base, mfma_cycles in (("value_pair", 0, 234 * 48 * 16), ("value_single", 32, 234 * 24 * 16), ("policy", 64, 234 * 48 * 16)):
+    # (MFMAs per k-step: a pair runs 66 of its 72 tiles -- the tiles wholly off the board are left out -- x 6)
+    for name, base, mfma_cycles in (("value_pair", 0, 234 * 44 * 16), ("value_single", 32, 234 * 24 * 16), ("policy", 64, 234 * 48 * 16)):
         n = st[base + 31]
         if not n:
             continue
