@@ -50,6 +50,25 @@ def _search_streams(game_cus):
     return _SEARCH_STREAMS[key]
 
 
+def _split_arg(want):
+    """split= / IAGO_SEARCH_SPLIT: "auto", or the game CUs of the role split -- 0 (the single launch) or a positive
+    multiple of 8.  Anything else is refused: the widening loop of BatchedMCTS would turn it into a count that is no
+    multiple of 8, and the search would quietly take the single launch."""
+    if isinstance(want, str):
+        if want == "auto":
+            return want
+        try:
+            n = int(want.strip())
+        except ValueError:
+            n = None
+    else:
+        n = int(want) if isinstance(want, numbers.Integral) and not isinstance(want, bool) else None
+    if n is None or n < 0 or n % 8:
+        raise ValueError("split / IAGO_SEARCH_SPLIT: \"auto\", 0 or a positive multiple of 8 (game CUs) expected, not %r"
+                         % (want,))
+    return n
+
+
 def suggest_capacity(n_sims, n_thr=15, moves=64, branching=12):
     """Nodes per game that a whole self-play game needs without ever compacting the pools:
     every expansion adds ~`branching` children, a search adds at most
@@ -175,6 +194,8 @@ class BatchedMCTS(object):
                  net_workgroups=None, max_cus=None, split=None):
         if n_thr < 1:
             raise ValueError("n_thr must be >= 1")
+        # (checked before anything is allocated)
+        want = _split_arg(split if split is not None else os.environ.get("IAGO_SEARCH_SPLIT", "auto"))
         # (what the caller asked for explicitly, before the defaults below fill the options in: any of these selects
         # the per-playout launches unless `persistent` says otherwise)
         per_playout_asked = bool(use_graph or async_steps or value_ahead or lookahead is not None
@@ -265,9 +286,8 @@ class BatchedMCTS(object):
         # game workgroup holds a CU alone, so beyond 32 of them each one is a net workgroup less; two per CU give the CUs
         # back (1536 / 2048 / 4096 games: 17.4 -> 17.9, 17.1 -> 18.3, 10.8 -> 15.1 M leaf-evals/s; 1024 games: no
         # difference, the single launch stays; LABNOTES.md, round 6).  split / IAGO_SEARCH_SPLIT: game CUs, 0 = always the single
-        # launch.  Not with max_cus (the split owns the device); a runtime without CU-masked streams falls back to
-        # the single launch.
-        want = split if split is not None else os.environ.get("IAGO_SEARCH_SPLIT", "auto")
+        # launch (_split_arg refuses anything but "auto", 0 and positive multiples of 8).  Not with max_cus (the split
+        # owns the device); a runtime without CU-masked streams falls back to the single launch.
         if want == "auto":
             # (32-game workgroups only: the smaller workgroups of batches up to 960 games measure slower two per CU --
             # 640 / 768 / 896 games at 16 per workgroup: 14.9 / 16.3 / 16.6 M single, 13.5 / 15.1 / 16.3 M split)

@@ -29,20 +29,22 @@ def main():
         policy, value = make_nets()
         games = [int(g) for g in d["games"]]
         T = max(int(d["pi_%d" % g].shape[0]) for g in games)
-        G = max(games) + 1
+        col = {g: k for k, g in enumerate(sorted(set(games)))}     # (one column per game given, whatever its id)
+        G = len(col)
         B = dict(ops=ops, policy=policy, value=value, n_sims=int(d["n_sims"]),
                  pi=np.zeros((T, G, 64), np.int64), move=np.zeros((T, G), np.int64),
                  zlog=np.zeros((max(int(d["zlog_%d" % g].shape[0]) for g in games), G), np.int8),
                  zn=np.zeros(G, np.int64), game_turns=np.zeros(G, np.int64))
-        for g in games:
+        for g, c in col.items():
             pi, mv, zl = d["pi_%d" % g], d["move_%d" % g], d["zlog_%d" % g]
-            B["pi"][:pi.shape[0], g], B["move"][:mv.shape[0], g] = pi, mv
-            B["zlog"][:zl.shape[0], g], B["zn"][g] = zl, zl.shape[0]
-            B["game_turns"][g] = int(d["game_turns_%d" % g])
+            B["pi"][:pi.shape[0], c], B["move"][:mv.shape[0], c] = pi, mv
+            B["zlog"][:zl.shape[0], c], B["zn"][c] = zl, zl.shape[0]
+            B["game_turns"][c] = int(d["game_turns_%d" % g])
         probe = Probe(B)
         out["compared"], out["max_path"] = {}, {}
         for g, n_turns, start in zip(games, d["n_turns"], d["compare_from"]):
-            out["compared"][str(g)] = rebuild(B, probe, g, int(n_turns), n_thr=int(d["n_thr"]), compare_from=int(start))
+            out["compared"][str(g)] = rebuild(B, probe, g, int(n_turns), n_thr=int(d["n_thr"]), compare_from=int(start),
+                                              col=col[g])
             out["max_path"][str(g)] = int(B["max_path"][g])
     except BaseException:   # (an assertion of rebuild(): reported to the test, which fails with it)
         out["error"] = traceback.format_exc()

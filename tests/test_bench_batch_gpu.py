@@ -26,10 +26,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import mcts_py
-from oracle import oracle as orc
 from tests.conftest import GOLDEN
 from tests.bench_batch_util import Probe as _Probe, rebuild as _rebuild
+from tests.bench_batch_util import audit_table, rebuild_in_workers, replay_records
 
 pytestmark = pytest.mark.gpu
 
@@ -94,115 +93,9 @@ def whole_nthr1():
     return _play(100, 128, 128 * 100, n_thr=1)
 
 
-def _rebuild_in_workers(B, jobs, tmp_path, n_workers=4):
-    """jobs: [(game, turns to rebuild, compare from turn)] spread over worker processes (tests/rebuild_worker.py: the
-    Python restatement of MCTS.py with the nets' outputs from the production kernels on one board, each worker its
-    own HIP context).  Returns (searches compared, {game: deepest path})."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    procs = []
-    for w in range(n_workers):
-        mine = jobs[w::n_workers]
-        if not mine:
-            continue
-        arrays = dict(n_sims=B["n_sims"], n_thr=B["n_thr"], games=np.array([j[0] for j in mine]),
-                      n_turns=np.array([j[1] for j in mine]), compare_from=np.array([j[2] for j in mine]))
-        for g, _, _ in mine:
-            arrays["pi_%d" % g], arrays["move_%d" % g] = B["pi"][:, g], B["move"][:, g]
-            arrays["zlog_%d" % g] = B["zlog"][:B["zn"][g], g]
-            arrays["game_turns_%d" % g] = B["game_turns"][g]
-        src, dst = os.path.join(str(tmp_path), "job%d.npz" % w), os.path.join(str(tmp_path), "job%d.json" % w)
-        np.savez(src, **arrays)
-        procs.append((subprocess.Popen([sys.executable, os.path.join(root, "tests", "rebuild_worker.py"), src, dst], cwd=root), dst))
-    n, depth = 0, {}
-    for p, dst in procs:
-        rc = p.wait(timeout=600)
-        out = json.load(open(dst))
-        assert rc == 0 and "error" not in out, out.get("error")
-        n += sum(out["compared"].values())
-        depth.update({int(g): d for g, d in out["max_path"].items()})
-    return n, depth
-
-
-def _replay_records(B, whole):
-    """(i): every record of every game through the C oracle.  Returns the number of records checked."""
-    own, opp, valid, move, pi, T, n_sims = B["own"], B["opp"], B["valid"], B["move"], B["pi"], B["T"], B["n_sims"]
-    n_rec = 0
-    for g in range(1024):
-        state = orc.initial_state()
-        stone_num, pass_flg, t = 4, False, 0
-        over = False
-        while not over and t < T:
-            for color in (1, 2):
-                p1, p2 = orc.state_to_bits(state)
-                mover = (p1, p2) if color == 1 else (p2, p1)
-                assert (int(own[t, g]), int(opp[t, g])) == mover, (g, t)
-                acts = orc.legal_actions(state, color)
-                if len(acts) > 0:
-                    assert valid[t, g] == 1, (g, t)
-                    a = int(move[t, g])
-                    assert a in acts, (g, t, a)
-                    row = pi[t, g]
-                    assert np.all(row[[x for x in range(64) if x not in acts]] == 0), (g, t)
-                    assert a == int(np.argmax(row)) and row[a] > 0, (g, t)      # first most-visited child (MCTS.py:147)
-                    # the root was a leaf for its first visits, then every playout went to a child (MCTS.py:109)
-                    assert int(row.sum()) >= n_sims - B["n_thr"], (g, t)   # (+ the visits the reused subtree brought)
-                    orc.place_stone(state, a, color)
-                    stone_num += 1
-                    pass_flg = False
-                else:
-                    assert valid[t, g] == 0 and move[t, g] == -1 and not pi[t, g].any(), (g, t)
-                    if pass_flg:
-                        stone_num = 64
-                    pass_flg = True
-                n_rec += 1
-                t += 1
-                if t >= T:
-                    break
-            if stone_num >= 64:
-                over = True
-        if whole:
-            assert over and B["game_turns"][g] == t, (g, t, B["game_turns"][g])
-            assert B["z"][g] == orc.judge(state, 1), g
-            assert orc.state_to_bits(state) == (int(B["f1"][g]), int(B["f2"][g])), g
-        else:
-            assert B["game_turns"][g] == T, g
-    return n_rec
-
-
-def _audit_table(B, n_walk):
-    """(iii): the position table after the batch."""
-    tab = B["table"]
-    seq, own, opp, val = tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3]
-    used = np.nonzero(seq)[0]
-    assert len(used) > 1000
-    assert not np.any(seq[used] & np.uint64(1)), "an entry was left with an odd sequence word"
-    assert np.array_equal(val[used] >> np.uint64(32), seq[used] & np.uint64(0xFFFFFFFF)), "value word / sequence word mismatch"
-    writer = (seq[used] >> np.uint64(32)).astype(np.int64)
-    assert writer.min() >= 0 and writer.max() < 1024           # the game that asked (or walked ahead)
-    assert not np.any(own[used] & opp[used])                     # positions: disjoint stones, the centre occupied
-    rs = np.random.RandomState(5)
-    pick = used if len(used) <= n_walk else rs.choice(used, n_walk, replace=False)
-    ops, value = B["ops"], B["value"]
-    o, p = ops.bits_to_tensor(own[pick]), ops.bits_to_tensor(opp[pick])
-    idx = torch.arange(len(pick), dtype=torch.int64, device="cuda")
-    one = torch.ones(1, dtype=torch.int32, device="cuda")
-    out = torch.full((len(pick),), float("nan"), dtype=torch.float32, device="cuda")
-    with torch.no_grad():
-        for i in range(len(pick)):      # ONE board per launch: the one-board walk (value to out[index[0]])
-            value.forward_boards_counted(o, p, idx[i:i + 1], one, out)
-    got = out.cpu().numpy().view(np.uint32)
-    want = (val[pick] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    bad = np.nonzero(got != want)[0]
-    assert len(bad) == 0, "%d of %d table values differ from the one-board walk (first: slot %d)" % (
-        len(bad), len(pick), int(pick[bad[0]]))
-    return len(used), len(pick)
-
-
 def test_bench_batch_records_through_the_oracle(batch100):
     B = batch100
-    n = _replay_records(B, whole=True)
+    n = replay_records(B, whole=True, games=range(1024))
     assert n > 1024 * 58 and B["leaf_evals"] == int(B["valid"].sum()) * 100
     t = B["totals"]
     # the regime of the bench: the nets behind the rings, pairs, the table, the values ahead -- all in use
@@ -221,18 +114,18 @@ def test_bench_batch_searches_rebuilt_by_the_oracle(batch100):
 
 
 def test_bench_batch_position_table_audit(batch100):
-    used, walked = _audit_table(batch100, 4096)
+    used, walked = audit_table(batch100, 4096, n_games=1024)
     assert used > 200_000 and walked == 4096
 
 
 def test_config3_share_on_the_persistent_search(batch400):
     """(iv) 1024 games x 400 playouts per move, first 8 turns, on the engine the bench's mcts400 leg times."""
     B = batch400
-    assert _replay_records(B, whole=False) == 1024 * 8
+    assert replay_records(B, whole=False, games=range(1024)) == 1024 * 8
     probe = _Probe(B)
     n = sum(_rebuild(B, probe, g, 8) for g in range(3, 1024, 128))     # 8 games x 8 searches of 400 playouts
     assert n == 8 * 8
-    used, walked = _audit_table(B, 4096)
+    used, walked = audit_table(B, 4096, n_games=1024)
     assert used > 10_000 and walked == 4096
     assert B["leaf_evals"] == 1024 * 8 * 400
 
@@ -244,15 +137,15 @@ def test_whole_games_at_400_playouts_through_the_oracle(whole400, tmp_path):
     child under a pass child, one level every n_thr visits; the last turns descend through ~65 levels per playout) and
     where the recorded path is longest: the oracle's own deepest path must fit the path buffer; the table audited."""
     B = whole400
-    n = _replay_records(B, whole=True)
+    n = replay_records(B, whole=True, games=range(1024))
     assert n > 1024 * 58 and B["leaf_evals"] == int(B["valid"].sum()) * 400
     jobs = [(g, 128, 0) for g in (1, 640)]                                           # whole games, every search
     jobs += [(g, 128, max(int(B["game_turns"][g]) - 8, 0)) for g in range(77, 1024, 128)]   # the last 6+ searches of 8 games
-    n_cmp, depth = _rebuild_in_workers(B, jobs, tmp_path)
+    n_cmp, depth = rebuild_in_workers(B, jobs, tmp_path)
     assert n_cmp >= 2 * 55 + 8 * 6
     assert len(depth) == 10 and 30 < max(depth.values()) < B["path_stride"], depth
     print("deepest oracle path per rebuilt game:", depth)
-    used, walked = _audit_table(B, 2048)
+    used, walked = audit_table(B, 2048, n_games=1024)
     assert used > 200_000 and walked == 2048
 
 
@@ -261,8 +154,8 @@ def test_whole_games_at_n_thr_1_through_the_oracle(whole_nthr1, tmp_path):
     second visit, the policy net inside every playout; MCTS.py:80,109): records through the oracle, the first 4
     searches of 8 games rebuilt."""
     B = whole_nthr1
-    n = _replay_records(B, whole=True)
+    n = replay_records(B, whole=True, games=range(1024))
     assert n > 1024 * 58 and B["leaf_evals"] == int(B["valid"].sum()) * 100
     assert B["totals"][1] > 500_000                         # the policy net at (nearly) every playout
-    n_cmp, depth = _rebuild_in_workers(B, [(g, 4, 0) for g in range(9, 1024, 128)], tmp_path, n_workers=2)
+    n_cmp, depth = rebuild_in_workers(B, [(g, 4, 0) for g in range(9, 1024, 128)], tmp_path, n_workers=2)
     assert n_cmp == 8 * 4

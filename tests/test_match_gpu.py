@@ -13,6 +13,7 @@ import torch
 
 from oracle import mcts_py
 from oracle import oracle as orc
+from tests.bench_batch_util import replay_match
 
 pytestmark = pytest.mark.gpu
 
@@ -113,47 +114,8 @@ def _bits(x):
 
 
 def _replay(s, g, on_turn=None):
-    """Game g of result s through the C oracle (game.py:96-145,246-262), every record checked; on_turn(t, state,
-    color, kind, acts) is called before each move ('search' / 'draw' / 'forced' / 'pass')."""
-    own, opp = _bits(s["own"]), _bits(s["opp"])
-    mc = int(s["mcts_colour"][g])
-    state = orc.initial_state()
-    stone_num, pass_flg, t, over = 4, False, 0, False
-    while not over and t < 128:
-        for color in (1, 2):
-            p1, p2 = orc.state_to_bits(state)
-            assert (int(own[t, g]), int(opp[t, g])) == ((p1, p2) if color == 1 else (p2, p1)), (g, t)
-            acts = orc.legal_actions(state, color)
-            row = s["pi"][t, g]
-            a = int(s["move"][t, g])
-            if len(acts) > 0:
-                kind = "forced" if stone_num > 62 and len(acts) == 1 else ("search" if color == mc else "draw")
-                assert a in acts, (g, t, a)
-                if kind == "search":
-                    assert s["valid"][t, g] == 1, (g, t)
-                    assert np.all(row[[x for x in range(64) if x not in acts]] == 0), (g, t)
-                    assert a == int(np.argmax(row)) and int(row.sum()) >= N_SIMS - 15, (g, t)
-                else:
-                    assert s["valid"][t, g] == 2 and not row.any(), (g, t, kind)
-                if on_turn:
-                    on_turn(t, state, color, kind, acts)
-                orc.place_stone(state, a, color)
-                stone_num += 1
-                pass_flg = False
-            else:
-                assert s["valid"][t, g] == 0 and a == -1 and not row.any(), (g, t)
-                if on_turn:
-                    on_turn(t, state, color, "pass", acts)
-                if pass_flg:
-                    stone_num = 64
-                pass_flg = True
-            t += 1
-        if stone_num >= 64:
-            over = True
-    assert over and t % 2 == 0 and int(s["game_turns"][g]) == t, (g, t)
-    assert s["z"][g] == orc.judge(state, 1), g
-    assert orc.state_to_bits(state) == (int(_bits(s["final_p1"])[g]), int(_bits(s["final_p2"])[g])), g
-    return t
+    """Game g of result s through the C oracle, every record checked (tests/bench_batch_util.replay_match)."""
+    return replay_match(s, g, N_SIMS, on_turn=on_turn)
 
 
 @pytest.mark.parametrize("which", ["mixed", "all2"])
