@@ -5,6 +5,10 @@ of the batched HIP engine (engine.BatchedMCTS).
 Differences, both forced: the budget is `n_sims` playouts per move when given
 (the reference's 10 s wall clock, MCTS.py:142, is kept as the fallback), and
 the nets are passed in instead of being read from './models' (MCTS.py:82-85).
+
+wave = W > 1 (8, 16 or 32): the wave search -- W playouts of the tree in flight at once, steered by virtual visits
+(virtual_loss per in-flight visit), deterministic (engine.BatchedMCTS, include/iago_hip_serving.h).  W = 1 is the
+reference's one-playout-at-a-time order.
 """
 import time
 
@@ -17,7 +21,7 @@ class MCTS(object):
 
     def __init__(self, lmbda=0.5, c_puct=1, n_thr=15, time_limit=10, policy_net=None,
                  value_net=None, rollout_weights=None, n_sims=None, capacity=65536, seed=0,
-                 use_graph=False):
+                 use_graph=False, wave=1, virtual_loss=1.0):
         if policy_net is None or (value_net is None and lmbda < 1):
             raise ValueError("policy_net / value_net are required (the reference loads "
                              "./models/sl_model.npz and ./models/value_model.npz here)")
@@ -26,7 +30,9 @@ class MCTS(object):
         self.policy_net, self.value_net = policy_net, value_net
         self._m = engine.BatchedMCTS(1, policy_net, value_net, rollout_weights, lmbda=lmbda,
                                      c_puct=c_puct, n_thr=n_thr, capacity=capacity, seed=seed,
-                                     use_graph=use_graph)
+                                     use_graph=use_graph, wave=wave, virtual_loss=virtual_loss)
+        self.wave = wave
+        self.chunk = max(8, 4 * wave)   # playouts per search of the time-limited loop
         self._one = torch.ones(1, dtype=torch.uint8, device="cuda")
 
     def get_move(self, state, color):
@@ -37,7 +43,7 @@ class MCTS(object):
         else:
             start = time.time()
             while time.time() - start < self.time_limit:
-                self._m.search(own, opp, self._one, 8)
+                self._m.search(own, opp, self._one, self.chunk)
         move = int(self._m.best_move(self._one)[0].item())
         if move == -2:
             raise ValueError("max() arg is an empty sequence: the root has no children "

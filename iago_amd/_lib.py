@@ -46,6 +46,10 @@ EXPERIMENTAL_SYMBOLS = [
     "iago_mcts_select", "iago_mcts_expand", "iago_mcts_pending", "iago_mcts_backup", "iago_mcts_mix_backup",
     "iago_mcts_expand_cached", "iago_mcts_fresh_leaves",
 ]
+# include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W))
+SERVING_SYMBOLS = [
+    "iago_mcts_search_wave",
+]
 
 
 class IagoError(RuntimeError):
@@ -191,6 +195,13 @@ class MctsSearchArgs(C.Structure):
     ]
 
 
+class SearchWaveArgs(C.Structure):
+    """Mirror of iago_search_wave_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("width", C.c_int32), ("vloss", C.c_float), ("timing", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
 class ValueSplitArgs(C.Structure):
     """Mirror of iago_value_split_args (include/iago_hip.h)."""
     _fields_ = [
@@ -308,8 +319,9 @@ def lib():
     L.iago_mcts_search_streams_create.argtypes = [i32, C.POINTER(vp)]
     L.iago_mcts_search_streams_destroy.argtypes = [vp]
     L.iago_mcts_search_split.argtypes = [C.POINTER(MctsSearchArgs), vp, vp]
+    L.iago_mcts_search_wave.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchWaveArgs), vp]
     L.iago_selfplay_policy.argtypes = [C.POINTER(SelfplayPolicyArgs), vp]
-    for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS:
+    for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)
     _lib = L

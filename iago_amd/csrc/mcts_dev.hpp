@@ -23,6 +23,7 @@ __device__ __forceinline__ void init_node(const Tree &T, int64_t i, int parent, 
     T.nodes[i].n_visits = 0;
     T.nodes[i].q = 0.0f;
     T.nodes[i].p = p;
+    T.nodes[i].reserved1 = 0; // in-flight visits of the wave search (search_kernel.hip): none
     if (T.has_v)
         T.nodes[i].v = __builtin_nanf(""); // value_func(node) not evaluated yet
 }

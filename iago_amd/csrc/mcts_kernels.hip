@@ -887,6 +887,7 @@ __global__ __launch_bounds__(BLOCK) void compact_commit_kernel(Tree T, Tree S)
         T.nodes[base + i].n_visits = S.nodes[base + i].n_visits;
         T.nodes[base + i].q = S.nodes[base + i].q;
         T.nodes[base + i].p = S.nodes[base + i].p;
+        T.nodes[base + i].reserved1 = 0;
         if (T.has_v && S.has_v)
             T.nodes[base + i].v = S.nodes[base + i].v;
     }

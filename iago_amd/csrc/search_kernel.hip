@@ -50,6 +50,7 @@
 #include "conv_trunk_body.hpp" // (brings rollout_row_body.hpp)
 #include "conv_policy_body.hpp"
 #include "sample_dev.hpp"
+#include "../../include/iago_hip_serving.h"
 
 #include <cstdlib>
 
@@ -67,7 +68,8 @@ constexpr int CTL_FINISHED = 2, CTL_ABORT = 3;
 __host__ __device__ constexpr int ctl_head(uint32_t q) { return 8 + 2 * (int)q; }
 __host__ __device__ constexpr int ctl_tail(uint32_t q) { return 9 + 2 * (int)q; }
 enum { ST_READY = 0, ST_WAIT_PRIOR, ST_PRIOR_READY, ST_ROLL, ST_ROLL_FRESH, ST_WAIT_VALUE, ST_HAVE_VALUE, ST_DONE, ST_TURN, ST_MOVE,
-       ST_WAIT_DRAW, ST_DRAW }; // (a match: the policy side waits for its move's distribution, then draws)
+       ST_WAIT_DRAW, ST_DRAW,   // (a match: the policy side waits for its move's distribution, then draws)
+       ST_IDLE };               // (a wave search: a slot without a playout in its tree's current wave)
 constexpr int CTL_NO_CHILDREN = 4; // a searched root had no children (n_sims below n_thr)
 constexpr uint32_t MATCH_KEY = 0x4D415443u; // ("MATC") a match's policy draws: the rollout key's high word XOR this
 constexpr int CTL_BAD_DRAW = 13;   // a match: a policy draw found no probability mass on the legal moves (NaN / zero)
@@ -153,6 +155,11 @@ struct SearchParams {
     int32_t ahead_idle;
     int32_t roll_defer; // rollouts: games a full pass of 16 may leave over for the next iteration (0: every game at once)
     int32_t path_lds_cap; // bytes of the launch's dynamic LDS a game workgroup may keep its games' recorded paths in
+    // the wave search (iago_mcts_search_wave, search_wave_kernel): `wave` slots per tree, n_slots = trees x wave
+    int32_t wave;
+    float vloss;
+    int64_t n_slots;
+    int64_t *wave_timing;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -264,11 +271,13 @@ __device__ __forceinline__ int policy_draw(const u64 *rep, uint64_t lg, double u
 }
 
 // Node.update_recursive (MCTS.py:51-72) over the recorded path + the leaf mix (MCTS.py:123-125): the
-// arithmetic of mix_backup_path_kernel, 8 lanes per game.
+// arithmetic of mix_backup_path_kernel, 8 lanes per game.  g: the slot (its path, its leaf value), gt: its tree (the same
+// unless a wave search, which also takes the playout's in-flight visit off every node of the path)
+template <bool WAVE>
 __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, uint32_t r, int leaf, bool fresh, float vg,
-                                            int path_n, const int8_t zl, const int path_at)
+                                            int path_n, const int8_t zl, const int path_at, const int64_t gt)
 {
-    const int64_t base = g * (int64_t)S.T.capacity;
+    const int64_t base = gt * (int64_t)S.T.capacity;
     const float lmbda = S.lmbda;
     if (fresh && lmbda < 1.0f && r == 0u)
         S.T.nodes[base + leaf].v = vg; // value_func(leaf), now stored (the value cache)
@@ -279,10 +288,10 @@ __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, ui
     if (r == 0u) {
         S.leaf_value[g] = lv;
         if (S.z_log && lmbda > 0.0f) {
-            const int k = S.z_log_n[g];
-            S.z_log_n[g] = k + 1;
+            const int k = S.z_log_n[gt];
+            S.z_log_n[gt] = k + 1;
             if (k < S.z_log_rows)
-                S.z_log[(int64_t)k * S.T.n_games + g] = zg;
+                S.z_log[(int64_t)k * S.T.n_games + gt] = zg;
         }
     }
     const int len = path_n < S.path_stride ? path_n : S.path_stride;
@@ -295,20 +304,55 @@ __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, ui
         const int n = (int)old.x + 1;                // MCTS.py:61
         const float q = __uint_as_float(old.y);
         *nq = make_uint2((uint32_t)n, __float_as_uint(q + (lv - q) / (float)n)); // MCTS.py:63
+        if constexpr (WAVE)
+            S.T.nodes[base + node].reserved1 -= 1; // vv: this playout is no longer in flight
     }
 }
 
+// in-flight visits (vv) of a wave search: the score of a child (Node.select, MCTS.py:39-49) when a playout of the wave
+// is on its way through it -- n + vv visits, the in-flight ones counted as a loss of `vloss` each.  vv == 0: the
+// reference's score exactly (the same float32 c_puct * P, float64 sqrt, divide and add).  (No contraction: the
+// restatement in tests/wave_mcts.py rounds every product and difference on its own)
+__device__ __forceinline__ double wave_score(float c_puct, float p, float q, int n, int vv, double sq, double vloss)
+{
+#pragma clang fp contract(off)
+    const float cp = c_puct * p;
+    const int nc = n + vv;
+    const double u = (double)cp * sq / (0.01 + (double)nc);
+    const double qe = vv == 0 ? (double)q : ((double)q * (double)n - vloss * (double)vv) / (double)nc;
+    return qe + u;
+}
+
+// a barrier that also orders the workgroup's global stores before it against its loads after it (workgroup-scope
+// release / acquire): how the slots of a wave search hand a tree to each other (cdna_hip_programming.md, guideline 16)
+__device__ __forceinline__ bool wg_handoff_or(bool x)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    const bool any = __syncthreads_or(x) != 0;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return any;
+}
+
 // The games of a GAME workgroup (8 lanes per game: 32 games = the four waves).
+// WAVE (iago_mcts_search_wave): the 8-lane groups are SLOTS, S.wave consecutive ones per tree (32 per workgroup: a tree
+// never straddles two), and a slot plays one playout of its tree's current wave.  Its descent waits for the slot before
+// it (the tree's `wv_next`, handed over with wg_handoff_or), its leaf is evaluated as in the plain search, and the
+// wave's backups run in slot order once every leaf of the wave has its value.
+template <bool WAVE>
 __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0)
 {
     const Tree &T = S.T;
     const int tid = threadIdx.x;
-    const bool mine = tid < 8 * S.games_per_wg;
+    const bool mine = tid < 8 * S.games_per_wg; // (WAVE: 32 slots, every thread)
     const int64_t g = (int64_t)blockIdx.x * S.games_per_wg + (tid >> 3);
     const Lane8 L = make_lane8(threadIdx.x);
     const uint32_t r = L.l8;
-    const bool exists = mine && g < T.n_games;
-    const int64_t base = exists ? g * (int64_t)T.capacity : 0;
+    const int W = WAVE ? S.wave : 1;
+    const int64_t n_slots = WAVE ? S.n_slots : T.n_games;
+    const bool exists = mine && g < n_slots;
+    const int64_t gt = WAVE ? g / W : g; // the tree
+    const int s_in = WAVE ? (int)(g % W) : 0, tl = WAVE ? (tid >> 3) / W : 0; // slot within the tree, tree within the workgroup
+    const int64_t base = exists ? gt * (int64_t)T.capacity : 0;
     const bool need_v = S.lmbda < 1.0f, need_z = S.lmbda > 0.0f;
     // the descent's recorded path (Node.update_recursive's ancestors): in the workgroup's dynamic LDS -- a game workgroup
     // walks no net while it has games -- when 32 paths fit there, else in the caller's array.  (From global memory the
@@ -323,12 +367,28 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     __shared__ int8_t h_z[GAMES_PER_WG];
     const iago_row::RowHandoff hand = {h_own, h_opp, h_stream, h_game, h_z, (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
     const int gl = tid >> 3; // this game's number within the workgroup
-    const int n_here = (int)min((int64_t)S.games_per_wg, T.n_games - (int64_t)blockIdx.x * S.games_per_wg); // its slots
+    const int n_here = (int)min((int64_t)S.games_per_wg, n_slots - (int64_t)blockIdx.x * S.games_per_wg); // its slots
 
     const bool whole = S.max_turns > 0;
     // (a stream: slot g starts game g while there is one -- `active` is not read)
-    const bool first = exists && g < S.games_total && (S.stream || S.active[g] != 0);
+    const bool first = exists && gt < S.games_total && (S.stream || S.active[gt] != 0);
     int state = (first && S.n_sims > 0) ? (whole ? ST_TURN : ST_READY) : ST_DONE;
+    // a wave search: per tree of the workgroup, the slots of its current wave that have descended (the next one to go),
+    // the wave's playouts, whether a slot of the wave still waits for its leaf's evaluation
+    __shared__ int32_t wv_next[GAMES_PER_WG], wv_size[GAMES_PER_WG], wv_block[GAMES_PER_WG];
+    __shared__ long long wv_time[4]; // (diagnostic, thread 0: descents, rollouts, backups, waits; S.wave_timing)
+    if (WAVE) {
+        const int m = S.n_sims < W ? S.n_sims : W;
+        if (state == ST_READY && s_in >= m)
+            state = ST_IDLE;
+        if (tid < GAMES_PER_WG) {
+            wv_next[tid] = 0;
+            wv_size[tid] = m;
+            wv_block[tid] = 0;
+        }
+        if (tid < 4)
+            wv_time[tid] = 0;
+    }
     uint32_t epoch = 0u; // reply tag of the game's last request (never 0 once used)
     int n_done = 0;
     if (exists && r == 0u) {
@@ -341,7 +401,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     bool pass_flg = false, g_over = false;
     const int search_end = whole ? ST_MOVE : ST_DONE; // where a game goes when its search's last playout is backed up
     if (mine)
-        h_game[gl] = (int32_t)g; // (the 8 lanes write the same word; each reads back its own store)
+        h_game[gl] = (int32_t)gt; // (the 8 lanes write the same word; each reads back its own store; a wave: the tree's id)
     if (whole && exists && g < S.games_total) {
         g_own = S.game_own[g];
         g_opp = S.game_opp[g];
@@ -350,6 +410,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     }
     // cursor of the descent (kept across iterations while the game waits for priors)
     int node = 0, fc = -1, k = 0, nv = 0, path_n = 0, leaf = 0;
+    int nvv = 0; // (a wave search: the cursor node's in-flight visits)
     uint32_t vbits = 0;
     uint64_t own = 0, opp = 0;
     bool may_expand = false, leaf_fresh = false;
@@ -377,6 +438,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     int pace_limit = 0x7fffffff;
 
     for (;;) {
+        const long long c_it = WAVE ? wall_clock64() : 0;
         bool busy = false; // this game did something in this iteration
         if (mine) {
             // ---- replies
@@ -411,9 +473,10 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             }
             // (the 8 lanes of a game load the same word in the same instruction, or agree through group8_all:
             // one state per game)
-            // ---- backup of the games whose value has arrived (their rollout ran when they descended)
-            if (state == ST_HAVE_VALUE) {
-                backup_game(S, g, r, leaf, true, v_reply, path_n, h_z[gl], path_at);
+            // ---- backup of the games whose value has arrived (their rollout ran when they descended; a wave search
+            // backs its slots up together, below)
+            if (!WAVE && state == ST_HAVE_VALUE) {
+                backup_game<false>(S, g, r, leaf, true, v_reply, path_n, h_z[gl], path_at, g);
                 n_done++;
                 if (S.trace && r == 0u)
                     atomicAdd((unsigned long long *)&S.totals[9], 1ull); // (diagnostic: playouts over time)
@@ -424,7 +487,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             }
             // ---- whole games: the turn's end (the move) and the next turn's start, until the game searches again
             // or is over (a pass leads straight on to the next turn: at most a few rounds)
-            if (whole) {
+            if (!WAVE && whole) {
                 for (int rep = 0; rep < 6; rep++) {
                     const bool at_move = state == ST_MOVE, at_turn = state == ST_TURN, at_draw = state == ST_DRAW;
                     if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
@@ -560,25 +623,36 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                     }
                 }
             }
-            // ---- descent (MCTS.py:105-133): from the root, or on from the leaf whose priors arrived
-            const bool fresh_start = state == ST_READY && turn * S.n_sims + n_done <= pace_limit;
-            bool descending = fresh_start || state == ST_PRIOR_READY;
+        }
+        // ---- descent (MCTS.py:105-133): from the root, or on from the leaf whose priors arrived.  A wave search: the
+        // slots of a tree one after the other (a step per slot, every tree of the workgroup at once), each seeing the
+        // in-flight visits and the expansions of the slots before it
+        const long long c_desc = WAVE ? wall_clock64() : 0;
+        for (int sub = 0; sub < (WAVE ? W : 1); sub++) {
+        const bool my_turn = !WAVE || s_in == wv_next[tl];
+        bool went_any = false;
+        if (mine) {
+            const bool fresh_start = state == ST_READY && (WAVE ? my_turn : turn * S.n_sims + n_done <= pace_limit);
+            bool descending = fresh_start || (state == ST_PRIOR_READY && my_turn);
             bool have_priors = state == ST_PRIOR_READY;
             bool skip_record = state == ST_PRIOR_READY; // the cursor node is on the path already
             bool need_prior = false;
             if (fresh_start) {
-                node = T.root[g];
-                own = whole ? g_own : S.root_own[g];
-                opp = whole ? g_opp : S.root_opp[g];
+                node = T.root[gt];
+                own = whole ? g_own : S.root_own[gt];
+                opp = whole ? g_opp : S.root_opp[gt];
                 const uint4 s0 = ((const uint4 *)&T.nodes[base + node])[0], l0 = ((const uint4 *)&T.nodes[base + node])[1];
                 fc = (int)l0.x;
                 k = (int)((l0.z >> 8) & 0xFFu);
                 nv = (int)s0.x;
+                if (WAVE)
+                    nvv = (int)l0.w;
                 vbits = s0.w;
                 path_n = 0;
                 may_expand = true;
             }
             const bool went = descending;
+            went_any = went;
             busy = busy || went;
             for (int depth = 0; depth < MAX_DEPTH; depth++) {
                 if (descending && !skip_record) {
@@ -590,7 +664,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                                 gpath[path_n] = node;
                         }
                         else
-                            T.overflow[g] = 1; // deeper than the path buffer: reported like a full pool
+                            T.overflow[gt] = 1; // deeper than the path buffer: reported like a full pool
                     }
                     path_n++;
                 }
@@ -608,12 +682,12 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             may_expand = false;
                             uint32_t fc1 = 0; // first child + 1, 0 = no room
                             if (r == 0u) {
-                                const int at = T.n_nodes[g];
+                                const int at = T.n_nodes[gt];
                                 if (at + kn <= T.capacity) {
-                                    T.n_nodes[g] = at + kn;
+                                    T.n_nodes[gt] = at + kn;
                                     fc1 = (uint32_t)at + 1u;
                                 } else {
-                                    T.overflow[g] = 1;
+                                    T.overflow[gt] = 1;
                                 }
                             }
                             fc1 = group8_add(fc1);
@@ -671,15 +745,17 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             fc = (int)l0.x;
                             nv = (int)s0.x;
                             k = (int)((l0.z >> 8) & 0xFFu);
+                            if (WAVE)
+                                nvv = (int)l0.w;
                             vbits = s0.w;
                         }
                         continue;
                     }
                 }
-                const double sq = sqrt((double)nv); // np.sqrt(parent.n_visits), MCTS.py:49
+                const double sq = sqrt((double)(WAVE ? nv + nvv : nv)); // np.sqrt(parent.n_visits), MCTS.py:49
                 double best_v = -INFINITY;
                 int best_i = 0x7fffffff;
-                uint32_t pl[4] = {0u, 0u, 0u, 0u}; // of the best child: first_child, n_visits, action | n_children << 8, v
+                uint32_t pl[4] = {0u, 0u, 0u, 0u}; // of the best child: first_child, n_visits, action | n_children << 8 (| vv << 16), v
                 for (int j0 = (int)r; j0 < kk; j0 += 16) {
                     const int j1 = j0 + 8;
                     const bool two = j1 < kk;
@@ -689,6 +765,23 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                     const float p0 = __uint_as_float(s0.z), q0 = __uint_as_float(s0.y);
                     const float p1 = __uint_as_float(s1.z), q1 = __uint_as_float(s1.y);
                     const int n0 = (int)s0.x, n1 = (int)s1.x;
+                    if constexpr (WAVE) {
+                        // (vv < 2^16: at most 32 playouts in flight)
+                        const double v = wave_score(S.c_puct, p0, q0, n0, (int)l0.w, sq, (double)S.vloss);
+                        if (v > best_v) {
+                            best_v = v;
+                            best_i = j0;
+                            pl[0] = l0.x, pl[1] = (uint32_t)n0, pl[2] = (l0.z & 0xFFFFu) | (l0.w << 16), pl[3] = s0.w;
+                        }
+                        if (two) {
+                            const double v1 = wave_score(S.c_puct, p1, q1, n1, (int)l1.w, sq, (double)S.vloss);
+                            if (v1 > best_v) {
+                                best_v = v1;
+                                best_i = j1;
+                                pl[0] = l1.x, pl[1] = (uint32_t)n1, pl[2] = (l1.z & 0xFFFFu) | (l1.w << 16), pl[3] = s1.w;
+                            }
+                        }
+                    } else {
                     {
                         const float cp = S.c_puct * p0;                          // float32, MCTS.py:49
                         const double u = (double)cp * sq / (0.01 + (double)n0);
@@ -708,6 +801,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                             best_i = j1;
                             pl[0] = l1.x, pl[1] = (uint32_t)n1, pl[2] = l1.z & 0xFFFFu, pl[3] = s1.w;
                         }
+                    }
                     }
                 }
                 argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
@@ -729,7 +823,9 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                     node = child;
                     fc = (int)pl[0];
                     nv = (int)pl[1];
-                    k = (int)(pl[2] >> 8);
+                    k = (int)((pl[2] >> 8) & 0xFFu);
+                    if (WAVE)
+                        nvv = (int)(pl[2] >> 16);
                     vbits = pl[3];
                 }
             }
@@ -760,7 +856,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                     }
                 } else {
                     if (descending && fc >= 0 && r == 0u)
-                        T.overflow[g] = 1; // path longer than MAX_DEPTH: reported like a full pool
+                        T.overflow[gt] = 1; // path longer than MAX_DEPTH: reported like a full pool
                     // the leaf of this playout (MCTS.py:123-127): its rollout runs now, its value is the
                     // stored one or is asked for
                     leaf = node;
@@ -791,16 +887,34 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                         S.cur_opp[g] = opp;
                         h_own[gl] = own; // (what the rollout pass reads)
                         h_opp[gl] = opp;
-                        h_stream[gl] = turn * S.n_sims + n_done;
+                        h_stream[gl] = turn * S.n_sims + n_done + s_in; // (a wave: playout p = the wave's first + the slot)
                         if (ask)
                             send_request(S, KIND_VALUE, g, epoch, own, opp);
                     }
                     state = ask ? ST_ROLL_FRESH : ST_ROLL;
+                    if constexpr (WAVE) {
+                        // the playout is in flight: vv + 1 along its path, and the tree's next slot may descend
+                        __threadfence_block(); // (lane 0's path entries, read by the group's other lanes)
+                        const int len = path_n < S.path_stride ? path_n : S.path_stride;
+                        for (int d = (int)r; d < len; d += 8) {
+                            const int pn = path_at >= 0 ? ((const int32_t *)iago_trunk::trunk_lds)[path_at + d] : gpath[d];
+                            T.nodes[base + pn].reserved1 += 1;
+                        }
+                        if (r == 0u)
+                            wv_next[tl] = s_in + 1;
+                    }
                 }
             }
             if (exists && r == 0u)
                 S.roll[g] = (need_z && (state == ST_ROLL || state == ST_ROLL_FRESH)) ? 1 : 0;
         }
+        if constexpr (WAVE) {
+            if (!wg_handoff_or(went_any))
+                break;
+        }
+        }
+        if (WAVE && tid == 0)
+            wv_time[0] += wall_clock64() - c_desc;
         // ---- rollouts of the leaves reached in this iteration (Simulate, mcts_self_play.py:9-134): the games that
         // have one are packed into rows of 16 boards (about half of a workgroup's games reach a leaf in an iteration,
         // the others wait for a net: one pass of the 16-lanes-per-board body instead of two, most of the time).  A
@@ -824,6 +938,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             c_prog = __hip_atomic_load(&S.ctl[CTL_PROGRESS], RLX_AGENT);
         }
         const bool rolls = mine && need_z && (state == ST_ROLL || state == ST_ROLL_FRESH);
+        const long long c_roll = WAVE ? wall_clock64() : 0;
         bool rolled = true; // this game's rollout ran in this iteration (or it needs none)
         {
             // Passes of 16 boards.  A pass costs the same whether it plays 16 boards or one, and all games of the workgroup
@@ -866,9 +981,19 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                 __syncthreads();
             }
         }
-        if (mine && rolled) {
+        if (WAVE && mine && rolled) {
+            // a wave search: the leaf's value is at hand (stored, from the table, or -- ROLL_FRESH -- on its way); the
+            // backup waits for the wave's other leaves
             if (state == ST_ROLL) {
-                backup_game(S, g, r, leaf, leaf_fresh, __uint_as_float(vbits), path_n, h_z[gl], path_at);
+                v_reply = __uint_as_float(vbits);
+                state = ST_HAVE_VALUE;
+            } else if (state == ST_ROLL_FRESH) {
+                state = ST_WAIT_VALUE;
+            }
+        }
+        if (!WAVE && mine && rolled) {
+            if (state == ST_ROLL) {
+                backup_game<false>(S, g, r, leaf, leaf_fresh, __uint_as_float(vbits), path_n, h_z[gl], path_at, g);
                 n_done++;
                 if (S.trace && r == 0u)
                     atomicAdd((unsigned long long *)&S.totals[9], 1ull);
@@ -878,6 +1003,47 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             } else if (state == ST_ROLL_FRESH) {
                 state = ST_WAIT_VALUE;
             }
+        }
+        if constexpr (WAVE) {
+            // ---- the backups of every tree whose wave has all its leaf values: in slot order (a step per slot, each
+            // handing the tree to the next), then the tree's next wave -- or the end of its search
+            const long long c_back = wall_clock64();
+            if (tid == 0)
+                wv_time[1] += c_back - c_roll;
+            if (mine && r == 0u && state != ST_HAVE_VALUE && state != ST_DONE && s_in < wv_size[tl])
+                wv_block[tl] = 1;
+            __syncthreads();
+            // (a tree in search whose wave blocks nothing: every slot of the wave holds its value, the others are idle)
+            const bool ready = mine && state != ST_DONE && wv_block[tl] == 0;
+            if (wg_handoff_or(ready)) {
+                for (int j = 0; j < W; j++) {
+                    if (ready && s_in == j && state == ST_HAVE_VALUE) {
+                        backup_game<true>(S, g, r, leaf, leaf_fresh, v_reply, path_n, h_z[gl], path_at, gt);
+                        if (S.trace && r == 0u)
+                            atomicAdd((unsigned long long *)&S.totals[9], 1ull);
+                    }
+                    wg_handoff_or(false);
+                }
+                if (ready) {
+                    n_done += wv_size[tl];
+                    const int m = S.n_sims - n_done < W ? S.n_sims - n_done : W;
+                    state = n_done >= S.n_sims ? ST_DONE : (s_in < m ? ST_READY : ST_IDLE);
+                    if (r == 0u)
+                        S.done[g] = n_done;
+                    busy = true;
+                }
+                __syncthreads(); // (every slot has read its tree's wave size)
+                if (ready && s_in == 0 && r == 0u) {
+                    const int m = S.n_sims - n_done < W ? S.n_sims - n_done : W;
+                    wv_size[tl] = m;
+                    wv_next[tl] = 0;
+                }
+            }
+            // (read above, before the barrier: cleared for the next iteration's look)
+            if (mine && r == 0u && s_in == 0)
+                wv_block[tl] = 0;
+            if (tid == 0)
+                wv_time[2] += wall_clock64() - c_back;
         }
         if (S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] < S.trace_rows - T.n_games) {
             const int64_t iters = (int64_t)wg_count[0];
@@ -913,12 +1079,12 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             int limit = 0x7fffffff;
             pace[3] = 0;
             const int32_t wait0 = (int32_t)(c_t0 - c_h0), wait1 = (int32_t)(c_t1 - c_h1);
-            if (S.ahead_idle >= 0 && S.vtable_mask && T.n_games <= (int64_t)(QCAP / 2u) && c_idle >= (uint32_t)S.ahead_idle &&
+            if (S.ahead_idle >= 0 && S.vtable_mask && n_slots <= (int64_t)(QCAP / 2u) && c_idle >= (uint32_t)S.ahead_idle &&
                 wait0 <= 0 && wait1 <= 0)
                 // this iteration's share of the ring for requests nobody waits for: the games' own requests (at most one
                 // each) and TWO iterations' worth of these (the workgroups look at the rings at different moments: a second
                 // burst can be on its way before the first shows in anybody's snapshot) fit the ring together
-                pace[3] = (int32_t)((QCAP - (uint32_t)T.n_games) / 2u) / S.n_game_wgs;
+                pace[3] = (int32_t)((QCAP - (uint32_t)n_slots) / 2u) / S.n_game_wgs;
             // (a stream: no hold while game ids are left to claim -- the mean then mixes old and new games; the rule
             // holds again for the final drain, when every id is taken)
             if (S.pace_margin >= 0 && (!S.stream || (int64_t)c_next + T.n_games >= (int64_t)S.games_total)) {
@@ -970,12 +1136,21 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
             if (tid == 0)
                 wg_count[1]++;
             __builtin_amdgcn_s_sleep(32); // every game waits for a reply: poll again in ~1 us
+            if (WAVE && tid == 0)
+                wv_time[3] += wall_clock64() - c_it;
         }
     }
     if (exists && r == 0u && S.stats) {
-        S.stats[2 * g] += st_levels;
-        S.stats[2 * g + 1] += st_children;
+        if (WAVE) {
+            atomicAdd(&S.stats[2 * gt], st_levels);
+            atomicAdd(&S.stats[2 * gt + 1], st_children);
+        } else {
+            S.stats[2 * g] += st_levels;
+            S.stats[2 * g + 1] += st_children;
+        }
     }
+    if (WAVE && tid < 4 && S.wave_timing)
+        atomicAdd((unsigned long long *)&S.wave_timing[tid], (unsigned long long)wv_time[tid]);
     // (a launch that gave up: what every unfinished game was waiting for, for the post-mortem -- the trees are void anyway:
     // cur_node = the reply tag it waits for, leaf_value = its state; tools/debug_split_abort.py)
     if (exists && r == 0u && state != ST_DONE && __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u) {
@@ -1220,7 +1395,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (blockIdx.x == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
     if ((int)blockIdx.x < S.n_game_wgs)
-        game_workgroup(S, R, t0);
+        game_workgroup<false>(S, R, t0);
+    net_workgroup(S, VP, PP, t0);
+}
+
+// The wave search (iago_mcts_search_wave): the same grid, game workgroups of 32 SLOTS, S.wave of them per tree.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_wave_kernel(
+    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+{
+    const long long t0 = wall_clock64();
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
+    if ((int)blockIdx.x < S.n_game_wgs)
+        game_workgroup<true>(S, R, t0);
     net_workgroup(S, VP, PP, t0);
 }
 
@@ -1236,7 +1423,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_kernel(SearchParams S,
                                                                                                    iago_row::HwParams R)
 {
-    game_workgroup(S, R, wall_clock64());
+    game_workgroup<false>(S, R, wall_clock64());
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_net_kernel(
@@ -1308,7 +1495,8 @@ struct iago_search_streams {
 };
 
 namespace {
-int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp)
+int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
+                  const iago_search_wave_args *wv = nullptr)
 {
     if (!a || !a->tree || !a->value || !a->policy || !a->rollout)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: null args");
@@ -1339,14 +1527,18 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (a->z_log_rows > 0 && (!a->z_log || !a->z_log_n))
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: z_log needs z_log_n");
     const iago_rollout_args *ro = a->rollout;
-    if (ro->n != tree->n_games || !ro->z || !ro->table || ((uintptr_t)ro->table & 15u) || ro->log_form || ro->trace ||
+    const int wave = wv ? wv->width : 1;
+    const int64_t n_slots = tree->n_games * wave; // (a wave search: the slots' arrays)
+    if (wv && n_slots > (int64_t)QCAP)
+        return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_wave: more slots (n_games x width) than a request ring holds");
+    if (ro->n != n_slots || !ro->z || !ro->table || ((uintptr_t)ro->table & 15u) || ro->log_form || ro->trace ||
         ro->uniforms || ro->throughput_hint != 0)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: product-form rollout of the n games without "
                                            "trace / uniforms expected");
-    const int gpw = a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
+    const int gpw = wv ? GAMES_PER_WG : a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
     if (gpw != 8 && gpw != 16 && gpw != 24 && gpw != 32)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: games_per_workgroup is 0 (= 32), 8, 16 or 32");
-    const int64_t n_game_wgs = (tree->n_games + gpw - 1) / gpw;
+    const int64_t n_game_wgs = (n_slots + gpw - 1) / gpw;
     // The grid follows the device: every game workgroup must be resident together with at least one net workgroup (a
     // game waits for replies only net workgroups give), and a net workgroup beyond what fits would only start when
     // another one ends -- at the end of the launch.  Resident workgroups = CUs the launch may count on (max_cus, else
@@ -1486,6 +1678,12 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (S.roll_defer < 0 || S.roll_defer > 15)
         S.roll_defer = S.roll_defer < 0 ? 0 : 15;
     S.path_lds_cap = path_lds_cap;
+    S.wave = wave;
+    S.vloss = wv ? wv->vloss : 0.0f;
+    S.n_slots = n_slots;
+    S.wave_timing = wv ? wv->timing : nullptr;
+    if (wv)
+        S.pace_margin = -1; // (pacing evens out the games of a batch: the slots of a wave keep their tree's step)
     S.max_turns = a->max_turns;
     S.game_own = a->game_own;
     S.game_opp = a->game_opp;
@@ -1517,9 +1715,17 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     // every polled word starts from zero: the control block, the request ring and the reply mailboxes
     if (hipMemsetAsync(a->ctl, 0, 64, (hipStream_t)stream) != hipSuccess ||
         hipMemsetAsync(a->q_slots, 0, (size_t)2 * QCAP * 64, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_v, 0, (size_t)tree->n_games * 8, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_p, 0, (size_t)tree->n_games * 512, (hipStream_t)stream) != hipSuccess)
+        hipMemsetAsync(a->rep_v, 0, (size_t)n_slots * 8, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(a->rep_p, 0, (size_t)n_slots * 512, (hipStream_t)stream) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_persistent: hipMemsetAsync failed");
+    if (wv) {
+        static std::atomic<uint64_t> configured_wave{0};
+        if (iago_reserve_lds((const void *)search_wave_kernel, lds, configured_wave,
+                             "iago_mcts_search_wave: cannot reserve the nets' LDS image"))
+            return IAGO_ERR_HIP;
+        hipLaunchKernelGGL(search_wave_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
+        return iago_check_launch("iago_mcts_search_wave");
+    }
     if (!sp) {
         hipLaunchKernelGGL(search_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
         return iago_check_launch("iago_mcts_search_persistent");
@@ -1551,6 +1757,20 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
 extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)
 {
     return search_launch(a, stream, nullptr);
+}
+
+extern "C" int iago_mcts_search_wave(const iago_mcts_search_args *a, const iago_search_wave_args *w, void *stream)
+{
+    if (!a || !w)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: null args");
+    if (w->width != 1 && w->width != 8 && w->width != 16 && w->width != 32)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: width is 1, 8, 16 or 32");
+    if (!(w->vloss >= 0.0f && w->vloss <= 3.4028235e38f))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: vloss >= 0 (finite) expected");
+    if (a->max_turns != 0 || a->games_total != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: one search per launch (max_turns 0, games_total 0): "
+                                           "whole games take iago_mcts_search_persistent");
+    return search_launch(a, stream, nullptr, w);
 }
 
 extern "C" int iago_mcts_search_split(const iago_mcts_search_args *a, iago_search_streams *streams, void *stream)

@@ -191,9 +191,21 @@ class BatchedMCTS(object):
                  n_thr=15, capacity=4096, seed=0, game_id_base=0, device="cuda", use_graph=False,
                  sync_free=None, lookahead=None, lookahead_slots=None, value_cache=None, lookahead_overlap=None,
                  z_log_rows=0, async_steps=None, async_parts=None, value_ahead=None, persistent=None,
-                 net_workgroups=None, max_cus=None, split=None):
+                 net_workgroups=None, max_cus=None, split=None, wave=1, virtual_loss=1.0):
         if n_thr < 1:
             raise ValueError("n_thr must be >= 1")
+        # Wave search (iago_mcts_search_wave in include/iago_hip_serving.h): `wave` playouts of every tree in flight at
+        # once, steered by virtual visits (an in-flight visit counts as a loss of `virtual_loss`), descents and backups
+        # in slot order -- deterministic, and with wave = 1 today's search bit for bit.  For ONE game (MCTS.get_move)
+        # the chip otherwise waits on one playout at a time.  wave > 1 needs the persistent search (its single launch).
+        if isinstance(wave, bool) or wave not in (1, 8, 16, 32):
+            raise ValueError("wave must be 1, 8, 16 or 32, not %r" % (wave,))
+        virtual_loss = float(virtual_loss)
+        if not (0.0 <= virtual_loss < float("inf")):
+            raise ValueError("virtual_loss must be a finite number >= 0, not %r" % (virtual_loss,))
+        self.wave, self.virtual_loss = int(wave), virtual_loss
+        self.wave_entry = self.wave > 1   # (True at wave 1 too: the wave entry point at width 1 -- what the tests set)
+        ns = n_games * self.wave          # the slots: per-playout state of the search, W per tree
         # (checked before anything is allocated)
         want = _split_arg(split if split is not None else os.environ.get("IAGO_SEARCH_SPLIT", "auto"))
         # (what the caller asked for explicitly, before the defaults below fill the options in: any of these selects
@@ -223,9 +235,9 @@ class BatchedMCTS(object):
         self._value_total = torch.zeros(1, dtype=torch.int64, **kw)  # value-net evaluations, on the device
         self._value_key = None
         self.fused_leaf_eval = os.environ.get("IAGO_FUSED_LEAF_EVAL", "1") != "0"
-        self.cur_node = torch.zeros(n_games, dtype=torch.int32, **kw)
-        self.cur_own = torch.zeros(n_games, dtype=torch.int64, **kw)
-        self.cur_opp = torch.zeros(n_games, dtype=torch.int64, **kw)
+        self.cur_node = torch.zeros(ns, dtype=torch.int32, **kw)
+        self.cur_own = torch.zeros(ns, dtype=torch.int64, **kw)
+        self.cur_opp = torch.zeros(ns, dtype=torch.int64, **kw)
         self.needs_expand = torch.zeros(n_games, dtype=torch.uint8, **kw)
         self._pending = torch.zeros(n_games, dtype=torch.uint8, **kw)
         self._pend_idx = torch.zeros(n_games, dtype=torch.int64, **kw)
@@ -233,9 +245,9 @@ class BatchedMCTS(object):
         self._pend_count = torch.zeros(1, dtype=torch.int32, **kw)
         self._pend_total = torch.zeros(1, dtype=torch.int64, **kw)  # policy evaluations, on the device
         self.legal = torch.zeros(n_games, dtype=torch.int64, **kw)
-        self.leaf_value = torch.zeros(n_games, dtype=torch.float32, **kw)
+        self.leaf_value = torch.zeros(ns, dtype=torch.float32, **kw)
         self.planes = torch.zeros((n_games, 2, 8, 8), dtype=torch.float32, **kw)
-        self.z = torch.zeros(n_games, dtype=torch.int8, **kw)
+        self.z = torch.zeros(ns, dtype=torch.int8, **kw)
         self.v = torch.zeros(n_games, dtype=torch.float32, **kw)
         self.move = torch.zeros(n_games, dtype=torch.int8, **kw)
         self.visits = torch.zeros((n_games, 64), dtype=torch.int32, **kw)
@@ -273,13 +285,15 @@ class BatchedMCTS(object):
         # rollout passes of 16 boards, and every game workgroup is a net workgroup less)
         self.games_per_workgroup = int(os.environ.get("IAGO_PERSISTENT_GPW", "0")) or (
             8 if n_games <= 256 else 16 if n_games <= 960 else _lib.SEARCH_GAMES_PER_WORKGROUP)
+        if self.wave > 1:   # (the wave search: 32 slots per game workgroup, whole trees of them)
+            self.games_per_workgroup = _lib.SEARCH_GAMES_PER_WORKGROUP
         # The launch's grid follows the device (iago_mcts_search_capacity: CUs x workgroups of the search kernel per CU,
         # all of them resident from the start); max_cus / IAGO_PERSISTENT_CUS: the CUs the launch may count on when fewer
         # are free for it -- a CU-masked stream, a device shared with another job.  The games take at most half of them
         # (4096 games per launch on a whole MI355X); larger batches take the per-playout launches.
         self.max_cus = int(max_cus if max_cus is not None else os.environ.get("IAGO_PERSISTENT_CUS", "0"))
         self.resident_workgroups = self._search_capacity()
-        n_gw = -(-n_games // self.games_per_workgroup)
+        n_gw = -(-ns // self.games_per_workgroup)
         # Role split (iago_mcts_search_split): the game workgroups as a launch of their own, two per CU on `split` CUs
         # (a multiple of 8), the net workgroups on all the others -- two CU-masked streams, co-resident by construction.
         # Same trees.  Default ("auto"): wherever the games need more than 32 workgroups -- in the single launch every
@@ -288,7 +302,9 @@ class BatchedMCTS(object):
         # difference, the single launch stays; LABNOTES.md, round 6).  split / IAGO_SEARCH_SPLIT: game CUs, 0 = always the single
         # launch (_split_arg refuses anything but "auto", 0 and positive multiples of 8).  Not with max_cus (the split
         # owns the device); a runtime without CU-masked streams falls back to the single launch.
-        if want == "auto":
+        if self.wave > 1:
+            want_split = 0     # (the wave search runs as the single launch)
+        elif want == "auto":
             # (32-game workgroups only: the smaller workgroups of batches up to 960 games measure slower two per CU --
             # 640 / 768 / 896 games at 16 per workgroup: 14.9 / 16.3 / 16.6 M single, 13.5 / 15.1 / 16.3 M split)
             want_split = (8 * (-(-n_gw // 16)) if (n_gw > 32 and self.games_per_workgroup == _lib.SEARCH_GAMES_PER_WORKGROUP)
@@ -301,7 +317,8 @@ class BatchedMCTS(object):
         can_p = (self.resident_workgroups > 0 and 2 * n_gw <= self.resident_workgroups
                  and can_cache and getattr(value_fn, "search_args", None) is not None
                  and getattr(policy_fn, "search_args", None) is not None and getattr(policy_fn, "split3", False)
-                 and rollout_weights is not None and not rollout_weights.log_form and 0.0 <= self.lmbda < 1.0)
+                 and rollout_weights is not None and not rollout_weights.log_form and 0.0 <= self.lmbda < 1.0
+                 and ns <= _lib.SEARCH_QUEUE_ENTRIES)
         # Default: ON wherever it applies, unless the caller asks for the per-playout launches (use_graph,
         # look-ahead / asynchronous-step / value-look-ahead options, a rollout hook comes later); the environment
         # variable IAGO_PERSISTENT=0 / 1 overrides both (measurements: tools/time_value_ahead.py).
@@ -316,6 +333,9 @@ class BatchedMCTS(object):
                              "workgroups may take half of the %d workgroups this device keeps resident)"
                              % (self.resident_workgroups // 2 * self.games_per_workgroup, self.resident_workgroups))
         self.persistent = bool(persistent)
+        if self.wave > 1 and not self.persistent:
+            raise ValueError("wave > 1 needs the persistent search (the split-f16 value net, the three-piece policy net, "
+                             "product-form rollout weights, lmbda < 1, at most %d slots)" % _lib.SEARCH_QUEUE_ENTRIES)
         if self.persistent:
             if not self.value_cache:
                 raise ValueError("persistent needs the value cache")
@@ -463,10 +483,10 @@ class BatchedMCTS(object):
             self.PATH_STRIDE = 520
             i64 = torch.int64
             self._ps = dict(
-                path=torch.zeros((n_games, self.PATH_STRIDE), dtype=torch.int32, **kw),
-                done=torch.zeros(n_games, dtype=torch.int32, **kw), roll=torch.zeros(n_games, dtype=torch.uint8, **kw),
+                path=torch.zeros((ns, self.PATH_STRIDE), dtype=torch.int32, **kw),
+                done=torch.zeros(ns, dtype=torch.int32, **kw), roll=torch.zeros(ns, dtype=torch.uint8, **kw),
                 q_slots=torch.zeros(2 * _lib.SEARCH_QUEUE_ENTRIES * 8, dtype=i64, **kw), ctl=torch.zeros(16, dtype=torch.int32, **kw),
-                rep_v=torch.zeros(n_games, dtype=i64, **kw), rep_p=torch.zeros(n_games * 64, dtype=i64, **kw),
+                rep_v=torch.zeros(ns, dtype=i64, **kw), rep_p=torch.zeros(ns * 64, dtype=i64, **kw),
                 totals=torch.zeros(16, dtype=i64, **kw), wg_own=torch.zeros(4 * grid, dtype=i64, **kw),
                 wg_opp=torch.zeros(4 * grid, dtype=i64, **kw), wg_v=torch.zeros(4 * grid, dtype=torch.float32, **kw),
                 wg_probs=torch.zeros((4 * grid, 64), dtype=torch.float32, **kw))
@@ -477,6 +497,9 @@ class BatchedMCTS(object):
             self.z_log = torch.zeros((z_log_rows, n_games), dtype=torch.int8, **kw) if z_log_rows else None
             self.z_log_n = torch.zeros(n_games, dtype=torch.int32, **kw) if z_log_rows else None
             self.time_limit_ms = int(os.environ.get("IAGO_PERSISTENT_LIMIT_MS", "4000"))
+            # (the wave search's game-workgroup time, 100 MHz ticks: descents, rollouts, backups, waits; tools/time_wave.py)
+            self.wave_timing = torch.zeros(4, dtype=i64, **kw)
+            self._wave_active = None
         self.tree.reset_hooks = list(getattr(self.tree, "reset_hooks", ())) + [
             lambda mask: setattr(self, "_live_after_compaction", 0)]
         # Game-asynchronous steps (iago_mcts_async in include/iago_hip.h): a game whose leaf has a
@@ -1153,7 +1176,14 @@ class BatchedMCTS(object):
         if ev is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        if self._split is not None:
+        if self.wave_entry:
+            if game is not None:
+                raise ValueError("whole games in one launch are not available to the wave search (the turn loop is)")
+            w = _lib.SearchWaveArgs()
+            w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
+            self._wave_active = active
+            check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
+        elif self._split is not None:
             check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
         else:
             check(_lib.lib().iago_mcts_search_persistent(C.byref(a), _stream()), "iago_mcts_search_persistent")
@@ -1237,6 +1267,9 @@ class BatchedMCTS(object):
     def raise_errors(self, flags):
         """The errors of a search from the host copy of error_flags()."""
         overflow, err, sat_v, sat_p, gave_up = (int(x) for x in flags)
+        if gave_up and self.wave_entry and self._wave_active is not None:
+            # the trees of a wave search that gave up still count playouts in flight (vv): fresh roots for them
+            self.tree.reset(self._wave_active)
         if gave_up:
             raise _lib.IagoError("the persistent search gave up at its clock limit (%d ms for a search, 60 s for whole games: a "
                                  "reply never came -- is another job on the device, or fewer CUs free than workgroups?%s); the "
@@ -1468,7 +1501,7 @@ class SelfPlayEngine(object):
 
     def _whole_games_in_one_launch(self, n_sims):
         m = self.mcts
-        return (getattr(m, "persistent", False) and m.rollout_hook is None
+        return (getattr(m, "persistent", False) and m.rollout_hook is None and not getattr(m, "wave_entry", False)
                 and os.environ.get("IAGO_PERSISTENT_GAMES", "1") != "0"
                 and 2 * m.tree.capacity >= suggest_capacity(n_sims, m.n_thr, moves=min(self.max_turns, 64)))
 

@@ -1,0 +1,50 @@
+/*
+ * iago_hip_serving.h -- searching ONE position fast: the entry points that serve a single game (MCTS.get_move behind
+ * the front end) rather than batches of games.  Same conventions as iago_hip.h; part of the library's ABI
+ * (iago_abi_version).
+ */
+#ifndef IAGO_HIP_SERVING_H
+#define IAGO_HIP_SERVING_H
+
+#include "iago_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct iago_search_wave_args {
+    int32_t width;   /* W: playouts of one tree in flight together, 1, 8, 16 or 32 */
+    float vloss;     /* virtual loss of an in-flight visit, >= 0 (1.0: counted as a loss; 0: only the counts steer) */
+    int64_t *timing; /* optional [4] int64, added to (100 MHz ticks summed over the game workgroups): descents, rollout
+                        passes, backups, iterations in which every slot waited for a net */
+    int64_t reserved[4];
+} iago_search_wave_args;
+
+/*
+ * The persistent search of iago_mcts_search_persistent with W playouts of every tree in flight at once.
+ * Tree g owns the W consecutive SLOTS g*W .. g*W+W-1; every array of `args` that is per game there is per slot here
+ * ([n_games*W]: cur_node, cur_own, cur_opp, done, roll, leaf_value, rep_v; rep_p [n_games*W*64]; path
+ * [n_games*W][path_stride]; the rollout's n = n_games*W), the rest stays per tree (root_own, root_opp, active, the
+ * tree, z_log_n, z_log [rows][n_games], stats).  A search of n_sims playouts runs as ceil(n_sims / W) WAVES (the last
+ * one n_sims mod W playouts, or W); playout p is slot p mod W of wave p div W.  Every tree node counts its in-flight
+ * visits in `reserved1` (vv, 0 outside a wave; every node-creating path leaves it 0):
+ *   - the descents of a wave run one after the other in slot order, each exactly MCTS.playout's (expansion when the
+ *     real n_visits >= n_thr, the priors at the expansion, first maximum wins) except that child c of parent X scores
+ *     Q_eff + float32(c_puct * P) * sqrt(X.n + X.vv) / (0.01 + c.n + c.vv) in float64, Q_eff = c.Q when c.vv == 0,
+ *     else (c.Q * c.n - vloss * c.vv) / (c.n + c.vv); a descent that reaches its leaf adds 1 to vv along its path;
+ *   - a leaf is evaluated as before (value cache, position table, value net; the rollout draws from Philox stream
+ *     rollout->stream_id + p with id_base + g), as soon as its descent ends;
+ *   - when all leaves of the wave are evaluated the backups run in slot order: vv -= 1 along the path, then the
+ *     reference's update.  z_log is written in playout order.
+ * With W = 1 every vv stays 0: the trees, moves, z_log and draws of iago_mcts_search_persistent, bit for bit.
+ * The game workgroups hold 32 slots each (games_per_workgroup is not read).  Whole games are not available here:
+ * max_turns > 0 or games_total > 0 is refused, as is a width outside {1, 8, 16, 32} or a negative / NaN vloss
+ * (IAGO_ERR_INVALID).  ctl[3] != 0 after the launch: it gave up, and the trees' vv are NOT 0 (reset them).
+ */
+IAGO_API int iago_mcts_search_wave(const iago_mcts_search_args *args, const iago_search_wave_args *wave, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* IAGO_HIP_SERVING_H */
