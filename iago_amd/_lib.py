@@ -50,6 +50,11 @@ EXPERIMENTAL_SYMBOLS = [
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave",
 ]
+# include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
+# (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True))
+TRAINING_SYMBOLS = [
+    "iago_value_grad_workspace_bytes", "iago_value_mse_grad",
+]
 
 
 class IagoError(RuntimeError):
@@ -94,6 +99,25 @@ class PolicyGradArgs(C.Structure):
         ("g_w", C.c_void_p * 7), ("g_b", C.c_void_p * 7),
         ("g_w9", C.c_void_p), ("g_b10", C.c_void_p),
         ("loss", C.c_void_p), ("probs", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("overflow", C.c_void_p),
+    ]
+
+
+class ValueGradArgs(C.Structure):
+    """Mirror of iago_value_grad_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("result", C.c_void_p), ("keep", C.c_void_p),
+        ("dropout_scale", C.c_float),
+        ("n", C.c_int64), ("n_mean", C.c_int64),
+        ("w1", C.c_void_p), ("b1", C.c_void_p),
+        ("w_hi", C.c_void_p * 7), ("w_lo", C.c_void_p * 7), ("wt_hi", C.c_void_p * 7), ("wt_lo", C.c_void_p * 7),
+        ("bias", C.c_void_p * 7),
+        ("w9", C.c_void_p), ("b9", C.c_void_p), ("w10", C.c_void_p), ("w11", C.c_void_p),
+        ("g_w1", C.c_void_p), ("g_b1", C.c_void_p),
+        ("g_w", C.c_void_p * 7), ("g_b", C.c_void_p * 7),
+        ("g_w9", C.c_void_p), ("g_b9", C.c_void_p), ("g_w10", C.c_void_p), ("g_w11", C.c_void_p),
+        ("loss", C.c_void_p), ("pred", C.c_void_p), ("h9", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
         ("overflow", C.c_void_p),
     ]
@@ -281,6 +305,8 @@ def lib():
     L.iago_policy_grad_workspace_bytes.restype = i64
     L.iago_policy_reinforce_grad.argtypes = [C.POINTER(PolicyGradArgs), vp]
     L.iago_adam_chainer.argtypes = [C.POINTER(AdamArgs), vp]
+    L.iago_value_grad_workspace_bytes.argtypes = [i64]
+    L.iago_value_mse_grad.argtypes = [C.POINTER(ValueGradArgs), vp]
     L.iago_split_nchw.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.iago_merge_nchw.argtypes = [vp, vp, vp, i64, i32, vp]
     L.iago_value_stem.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
@@ -321,9 +347,10 @@ def lib():
     L.iago_mcts_search_split.argtypes = [C.POINTER(MctsSearchArgs), vp, vp]
     L.iago_mcts_search_wave.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchWaveArgs), vp]
     L.iago_selfplay_policy.argtypes = [C.POINTER(SelfplayPolicyArgs), vp]
-    for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS:
+    for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)
+    L.iago_value_grad_workspace_bytes.restype = i64
     _lib = L
     return L
 

@@ -3,7 +3,8 @@
 // units in "split f16" arithmetic: every float32 operand as two f16 numbers (22 significant bits), three MFMAs per
 // product sum into float32 accumulators (csrc/conv_kernels.hip).  Together with iago_conv3x3_split (forward and,
 // with transposed weights, backward-data) this replaces the MIOpen float32 convolutions of the update
-// (9 ms of an 18 ms set at 1,900 rows: DESIGN.md section 5).
+// (9 ms of an 18 ms set at 1,900 rows: DESIGN.md section 5).  The Value net's supervised update (train_value.py:53-57,
+// iago_value_mse_grad) runs the same trunk (pg_trunk_grad) with its own head kernels.
 //
 // Data: split channel blocks [n][C/16][64][16] f16 hi / lo as everywhere in conv_kernels.hip.  A gradient tensor
 // carries a power-of-two scale 2^e (an int32 device word per tensor) so that its largest element sits near 2^14: the
@@ -18,8 +19,11 @@
 //   boards; a board is one stage (K = 64 = two k-steps), double-buffered in LDS.
 //   Partial sums per group of boards go to memory and are added up in a fixed order (deterministic).
 #include "abi_common.hpp"
+#include "../../include/iago_hip_training.h"
 
 #include <hip/hip_fp16.h>
+#include <math.h>
+#include <string>
 
 namespace {
 
@@ -456,6 +460,279 @@ __global__ __launch_bounds__(256) void head_reduce_kernel(const float *part, int
         *loss = s * inv_n;
 }
 
+// ---- The head of the Value net and its loss, forward and backward (network.py:66-96, train_value.py:53-57):
+//   h9 = relu(conv3x3(x8; w9) + b9), h10 = w10 . h9, d = h10 * mask (keep ? scale : 0), pred = w11 . d,
+//   loss = sum (pred - y)^2 / n_mean, dpred = (2 / n_mean) (pred - y)
+// and back: dw11 = sum dpred d, dh10 = dpred w11 mask, dh9 = w10^T dh10, dpre9 = [h9 > 0] dh9, db9 = sum dpre9,
+// dY8[c][i] = [x8 > 0] sum_t w9[c][t] dpre9[i - t] (float32 channel blocks + the largest magnitude, as
+// head_grad_kernel writes them).  One wave per board at a time, lane = cell; plain float32 arithmetic (the head is
+// 0.13 % of the forward's products).  dw10 and dw9 need a product per board of all cells or all channels: they come
+// from the per-board values this kernel keeps (h9, dh10, dpre9) in value_head_wgrad_kernel.
+struct ValueHeadGradParams {
+    const uint4 *x_hi, *x_lo;    // [n][8][64][16] f16: the output of block 8
+    const float *w9, *b9, *w10, *w11;
+    const float *result;         // [n]
+    const uint8_t *keep;         // optional [n][128]
+    float scale, two_over_n;
+    int64_t n;
+    float4v *dy;                 // [n][8][64][16] float32
+    uint32_t *max_bits;
+    float *h9, *dh10, *dpre9;    // [n][64], [n][128], [n][64]
+    float *part;                 // [gridDim.x][VHEAD_PART]: dw11 (128), db9 (1), sum of squares (1) per workgroup
+    float *pred, *h9_out;        // optional [n], [n][64]
+};
+constexpr int VHEAD_PART = 130;
+constexpr int VW10_STRIDE = 129; // w10 in LDS as [cell][unit], rows padded: both walks conflict-free
+
+__device__ __forceinline__ float lane_value(float v, int l)
+{
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+__global__ __launch_bounds__(256) void value_head_grad_kernel(ValueHeadGradParams P)
+{
+    __shared__ float w9s[9 * 128];            // [tap][channel]
+    __shared__ float w10s[64 * VW10_STRIDE];  // [cell][unit]
+    __shared__ float red[4][VHEAD_PART];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int i = tid; i < 9 * 128; i += 256)
+        w9s[i] = P.w9[(i & 127) * 9 + (i >> 7)];
+    for (int i = tid; i < 128 * 64; i += 256)
+        w10s[(i & 63) * VW10_STRIDE + (i >> 6)] = P.w10[i];
+    __syncthreads();
+    const float b9 = P.b9[0], w11a = P.w11[lane], w11b = P.w11[lane + 64];
+    const int y = lane >> 3, xc = lane & 7;
+    float acc11a = 0.0f, acc11b = 0.0f, acc_b9 = 0.0f, acc_sq = 0.0f, big = 0.0f;
+    for (int64_t b = (int64_t)blockIdx.x * 4 + wv; b < P.n; b += (int64_t)gridDim.x * 4) {
+        // (the weights' LDS reads through an offset the compiler cannot see: hoisted out of the loop, all 9,344 of
+        // them would live in registers and spill)
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        const float *w9l = w9s + z, *w10l = w10s + z;
+        float x[128];
+#pragma unroll
+        for (int cb = 0; cb < 8; cb++) {
+            const int64_t at = ((b * 8 + cb) * 64 + lane) * 2;
+            const uint4 h0 = P.x_hi[at], h1 = P.x_hi[at + 1], l0 = P.x_lo[at], l1 = P.x_lo[at + 1];
+            const __half2 *hh0 = (const __half2 *)&h0, *hh1 = (const __half2 *)&h1;
+            const __half2 *ll0 = (const __half2 *)&l0, *ll1 = (const __half2 *)&l1;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float2 a = __half22float2(hh0[k]), c2 = __half22float2(ll0[k]);
+                const float2 d = __half22float2(hh1[k]), e2 = __half22float2(ll1[k]);
+                x[16 * cb + 2 * k] = a.x + c2.x * (1.0f / 2048.0f);
+                x[16 * cb + 2 * k + 1] = a.y + c2.y * (1.0f / 2048.0f);
+                x[16 * cb + 8 + 2 * k] = d.x + e2.x * (1.0f / 2048.0f);
+                x[16 * cb + 8 + 2 * k + 1] = d.y + e2.y * (1.0f / 2048.0f);
+            }
+        }
+        // block 9: this cell's term of every tap, gathered at the output cells; taps in order
+        float pre = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 9; t++) {
+            float v = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 128; c++)
+                v = fmaf(w9l[t * 128 + c], x[c], v);
+            const int yy = y + t / 3 - 1, xx = xc + t % 3 - 1;
+            const bool in = yy >= 0 && yy < 8 && xx >= 0 && xx < 8;
+            const float g = __shfl(v, in ? yy * 8 + xx : 0);
+            pre += in ? g : 0.0f;
+        }
+        const float h9 = fmaxf(pre + b9, 0.0f);
+        P.h9[b * 64 + lane] = h9;
+        if (P.h9_out)
+            P.h9_out[b * 64 + lane] = h9;
+        // fc10 (units lane and lane + 64), the dropout mask, fc11
+        float h10a = 0.0f, h10b = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 64; c++) {
+            const float hc = lane_value(h9, c);
+            h10a = fmaf(w10l[c * VW10_STRIDE + lane], hc, h10a);
+            h10b = fmaf(w10l[c * VW10_STRIDE + 64 + lane], hc, h10b);
+        }
+        float ma = 1.0f, mb = 1.0f;
+        if (P.keep) {
+            ma = P.keep[b * 128 + lane] ? P.scale : 0.0f;
+            mb = P.keep[b * 128 + 64 + lane] ? P.scale : 0.0f;
+        }
+        const float da = h10a * ma, db = h10b * mb;
+        const float pred = wave_sum(fmaf(w11b, db, w11a * da));
+        if (P.pred && lane == 0)
+            P.pred[b] = pred;
+        const float diff = pred - P.result[b];
+        acc_sq = fmaf(diff, diff, acc_sq); // (the same in every lane)
+        const float dp = P.two_over_n * diff;
+        acc11a = fmaf(dp, da, acc11a);
+        acc11b = fmaf(dp, db, acc11b);
+        const float dha = dp * w11a * ma, dhb = dp * w11b * mb;
+        P.dh10[b * 128 + lane] = dha;
+        P.dh10[b * 128 + 64 + lane] = dhb;
+        // back through fc10 to this cell, then block 9's ReLU
+        float dh9 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < 64; j++)
+            dh9 = fmaf(w10l[lane * VW10_STRIDE + j], lane_value(dha, j), dh9);
+#pragma unroll
+        for (int j = 0; j < 64; j++)
+            dh9 = fmaf(w10l[lane * VW10_STRIDE + 64 + j], lane_value(dhb, j), dh9);
+        const float dpre = h9 > 0.0f ? dh9 : 0.0f;
+        acc_b9 += dpre;
+        P.dpre9[b * 64 + lane] = dpre;
+        // block 9 transposed: input cell i takes dpre9 of output cell i - tap
+        float g[9];
+#pragma unroll
+        for (int t = 0; t < 9; t++) {
+            const int yy = y - t / 3 + 1, xx = xc - t % 3 + 1;
+            const bool in = yy >= 0 && yy < 8 && xx >= 0 && xx < 8;
+            const float s = __shfl(dpre, in ? yy * 8 + xx : 0);
+            g[t] = in ? s : 0.0f;
+        }
+#pragma unroll
+        for (int cb = 0; cb < 8; cb++) {
+#pragma unroll
+            for (int qt = 0; qt < 4; qt++) {
+                float4v v;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int c = 16 * cb + 4 * qt + k;
+                    float s = 0.0f;
+#pragma unroll
+                    for (int t = 0; t < 9; t++)
+                        s = fmaf(w9l[t * 128 + c], g[t], s);
+                    v[k] = x[c] > 0.0f ? s : 0.0f;
+                    big = fmaxf(big, fabsf(v[k]));
+                }
+                P.dy[((b * 8 + cb) * 64 + lane) * 4 + qt] = v;
+            }
+        }
+    }
+    big = wave_max(big);
+    if (lane == 0 && big > 0.0f)
+        atomicMax(P.max_bits, __float_as_uint(big));
+    acc_b9 = wave_sum(acc_b9);
+    red[wv][lane] = acc11a;
+    red[wv][64 + lane] = acc11b;
+    if (lane == 0) {
+        red[wv][128] = acc_b9;
+        red[wv][129] = acc_sq;
+    }
+    __syncthreads();
+    if (tid < VHEAD_PART)
+        P.part[(int64_t)blockIdx.x * VHEAD_PART + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+// dw10[j][c] = sum dh10[j] h9[c] and dw9[c][tap] = sum over output cells o of dpre9[o] x8[c][o + tap], per workgroup
+// over a contiguous range of boards (in board order); one board at a time in LDS
+constexpr int VW_PART = 128 * 64 + 128 * 9;
+constexpr int VX_STRIDE = 65;
+struct ValueWgradParams {
+    const uint4 *x_hi, *x_lo;
+    const float *h9, *dh10, *dpre9;
+    int64_t n;
+    float *part;                 // [gridDim.x][VW_PART]: dw10 [128][64], dw9 [128][9]
+};
+
+template <int T0, int NT>
+__device__ __forceinline__ void value_w9_taps(float (&acc)[5], const float *xs, const float *dps)
+{
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+        const int ky = (T0 + i) / 3, kx = (T0 + i) % 3;
+        float s = acc[i];
+#pragma unroll
+        for (int o = 0; o < 64; o++) {
+            const int yy = (o >> 3) + ky - 1, xx = (o & 7) + kx - 1;
+            if (yy >= 0 && yy < 8 && xx >= 0 && xx < 8)
+                s = fmaf(dps[o], xs[yy * 8 + xx], s);
+        }
+        acc[i] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void value_head_wgrad_kernel(ValueWgradParams P)
+{
+    __shared__ float xs[128 * VX_STRIDE]; // [channel][cell]
+    __shared__ float hs[64], dps[64], ds[128];
+    const int tid = threadIdx.x;
+    const int64_t per = (P.n + gridDim.x - 1) / gridDim.x;
+    const int64_t b_lo = (int64_t)blockIdx.x * per, b_hi = b_lo + per < P.n ? b_lo + per : P.n;
+    const int j = tid >> 1, c0 = (tid & 1) * 32, c = tid & 127;
+    float a10[32], a9[5];
+#pragma unroll
+    for (int k = 0; k < 32; k++)
+        a10[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+        a9[k] = 0.0f;
+    for (int64_t b = b_lo; b < b_hi; b++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) { // 1,024 pieces of 8 channels: (block, cell, half)
+            const int e = tid + 256 * q, cb = e >> 7, cell = (e >> 1) & 63, hp = e & 1;
+            const uint4 h = P.x_hi[b * 1024 + e], l = P.x_lo[b * 1024 + e];
+            const __half2 *hh = (const __half2 *)&h, *ll = (const __half2 *)&l;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float2 a = __half22float2(hh[k]), d = __half22float2(ll[k]);
+                const int ch = cb * 16 + hp * 8 + 2 * k;
+                xs[ch * VX_STRIDE + cell] = a.x + d.x * (1.0f / 2048.0f);
+                xs[(ch + 1) * VX_STRIDE + cell] = a.y + d.y * (1.0f / 2048.0f);
+            }
+        }
+        if (tid < 64) {
+            hs[tid] = P.h9[b * 64 + tid];
+            dps[tid] = P.dpre9[b * 64 + tid];
+        } else if (tid < 192) {
+            ds[tid - 64] = P.dh10[b * 128 + tid - 64];
+        }
+        __syncthreads();
+        const float g = ds[j];
+#pragma unroll
+        for (int k = 0; k < 32; k++)
+            a10[k] = fmaf(g, hs[c0 + k], a10[k]);
+        if (tid < 128) // (wave-uniform)
+            value_w9_taps<0, 5>(a9, xs + c * VX_STRIDE, dps);
+        else
+            value_w9_taps<5, 4>(a9, xs + c * VX_STRIDE, dps);
+        __syncthreads();
+    }
+    float *out = P.part + (int64_t)blockIdx.x * VW_PART;
+#pragma unroll
+    for (int k = 0; k < 32; k++)
+        out[j * 64 + c0 + k] = a10[k];
+    const int t0 = tid < 128 ? 0 : 5, nt = tid < 128 ? 5 : 4;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+        if (k < nt)
+            out[128 * 64 + c * 9 + t0 + k] = a9[k];
+}
+
+// every head gradient = the sum of its workgroups' partial sums in workgroup order; loss = sum of squares / n_mean
+__global__ __launch_bounds__(256) void value_head_reduce_kernel(const float *wpart, const float *hpart, int n_parts,
+                                                                float n_mean, float *dw10, float *dw9, float *dw11,
+                                                                float *db9, float *loss)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= VW_PART + VHEAD_PART)
+        return;
+    const bool w = t < VW_PART;
+    const float *src = w ? wpart + t : hpart + (t - VW_PART);
+    const int stride = w ? VW_PART : VHEAD_PART;
+    float s = 0.0f;
+    for (int g = 0; g < n_parts; g++)
+        s += src[(int64_t)g * stride];
+    if (t < 128 * 64)
+        dw10[t] = s;
+    else if (t < VW_PART)
+        dw9[t - 128 * 64] = s;
+    else if (t < VW_PART + 128)
+        dw11[t - VW_PART] = s;
+    else if (t == VW_PART + 128)
+        *db9 = s;
+    else
+        *loss = s / n_mean;
+}
+
 // ---- The weight and bias gradients of block 1 (3x3, 2 -> 64 on the planes of the board: plane 0 = the opponent's
 // stones, plane 1 = the mover's, game.py:168-174): dW1[co][plane][ky][kx] = sum over boards and cells of dY1[co][y][x]
 // [plane has a stone at (y + ky - 1, x + kx - 1)], db1[co] = sum dY1.  One wave per board at a time, lane = channel.
@@ -640,6 +917,115 @@ int64_t iago_policy_grad_workspace_bytes(int64_t n)
     return b;
 }
 
+extern "C++" { // (a template: C++ linkage inside the C entry points' block)
+
+// What the trunk of both nets' updates reads and writes (blocks 1..8: SLPolicy and Value share their shape)
+struct PgTrunk {
+    const uint64_t *own, *opp;
+    int64_t n;
+    const float *w1, *b1;
+    const void *const *w_hi, *const *w_lo, *const *wt_hi, *const *wt_lo;
+    const float *const *bias;
+    float *g_w1, *g_b1;
+    float *const *g_w, *const *g_b;
+    uint32_t *overflow;
+};
+// the trunk's scratch, carved from the front of the workspace (iago_policy_grad_workspace_bytes)
+struct PgScratch {
+    void *x_hi[8], *x_lo[8];
+    float *dyf;
+    void *dys_hi, *dys_lo;
+    float *wpart[7], *bpart[7], *hpart, *spart;
+    uint32_t *max_bits; // [0..7]: of the gradient at block k + 1's pre-activations; [16..23]: scales
+    int32_t *scale_exp;
+    char *end;          // the first byte after the trunk's scratch
+};
+
+// Forward with every block's output kept, head(S) -- which leaves the float32 gradient at block 8's pre-activations
+// in S.dyf and raises S.max_bits[7] --, then blocks 8 .. 2, the one reduction launch, block 1
+template <class Head>
+static int pg_trunk_grad(const PgTrunk &T, void *workspace, void *stream, const char *who, Head head)
+{
+    const int64_t n = T.n;
+    hipStream_t st = (hipStream_t)stream;
+    PgScratch S;
+    char *at = (char *)workspace;
+    auto take = [&](int64_t bytes) {
+        char *p = at;
+        at += pg_round(bytes);
+        return (void *)p;
+    };
+    for (int k = 0; k < 8; k++) {
+        S.x_hi[k] = take(n * (k ? 16384 : 8192));
+        S.x_lo[k] = take(n * (k ? 16384 : 8192));
+    }
+    S.dyf = (float *)take(n * 32768);
+    S.dys_hi = take(n * 16384);
+    S.dys_lo = take(n * 16384);
+    // (partial sums of the weight and bias gradients: a buffer per block, reduced by ONE launch at the end)
+    for (int k = 0; k < 7; k++) {
+        S.wpart[k] = (float *)take((int64_t)PG_MAX_GROUPS * 9 * 128 * (k ? 128 : 64) * 4);
+        S.bpart[k] = (float *)take(((n * 8 + 1) / 2) * 32 * 4);
+    }
+    S.hpart = (float *)take((int64_t)PG_GRID * HEAD_PART * 4);
+    S.spart = (float *)take((int64_t)PG_GRID * STEM_PART * 4);
+    S.max_bits = (uint32_t *)take(256);
+    S.scale_exp = (int32_t *)(S.max_bits + 16);
+    S.end = at;
+    if (hipMemsetAsync(S.max_bits, 0, 256, st) != hipSuccess)
+        return iago_fail(IAGO_ERR_HIP, (std::string(who) + ": hipMemsetAsync failed").c_str());
+
+    // forward, every block's output kept
+    int rc = iago_value_stem_boards(T.own, T.opp, T.w1, T.b1, S.x_hi[0], S.x_lo[0], n, T.overflow, stream);
+    for (int k = 0; k < 7 && rc == IAGO_OK; k++)
+        rc = iago_conv3x3_split(S.x_hi[k], S.x_lo[k], T.w_hi[k], T.w_lo[k], T.bias[k], S.x_hi[k + 1], S.x_lo[k + 1], n,
+                                k ? 128 : 64, 128, T.overflow, stream);
+    if (rc != IAGO_OK)
+        return rc;
+    rc = head(S);
+    // blocks 8 .. 2: the gradient at the block's pre-activations (float32 in dyf) -> its scaled pieces + the bias
+    // gradient; the weight gradient; the gradient at the pre-activations of the block below
+    for (int k = 6; k >= 0 && rc == IAGO_OK; k--) {
+        const int cin = k ? 128 : 64;
+        rc = iago_split_scaled(S.dyf, S.max_bits + k + 1, S.dys_hi, S.dys_lo, S.scale_exp + k + 1, n, 128, S.bpart[k],
+                               nullptr, stream);
+        if (rc == IAGO_OK)
+            rc = iago_conv3x3_wgrad_split(S.dys_hi, S.dys_lo, S.x_hi[k], S.x_lo[k], n, cin, S.wpart[k], pg_groups(cin),
+                                          S.scale_exp + k + 1, nullptr, stream);
+        if (rc == IAGO_OK)
+            rc = iago_conv3x3_bwd_data_split(S.dys_hi, S.dys_lo, S.scale_exp + k + 1, T.wt_hi[k], T.wt_lo[k], S.x_hi[k],
+                                             S.x_lo[k], cin, S.dyf, S.max_bits + k, n, stream);
+    }
+    if (rc != IAGO_OK)
+        return rc;
+    {
+        ReduceAllParams Rp;
+        int at_block = 0;
+        for (int k = 0; k < 7; k++) {
+            const int cin = k ? 128 : 64;
+            Rp.wpart[k] = S.wpart[k];
+            Rp.bpart[k] = S.bpart[k];
+            Rp.dw[k] = T.g_w[k];
+            Rp.db[k] = T.g_b[k];
+            Rp.scale_exp[k] = S.scale_exp + k + 1;
+            Rp.groups[k] = pg_groups(cin);
+            Rp.cin[k] = cin;
+            Rp.w_block0[k] = at_block;
+            at_block += (9 * 128 * cin + 255) / 256;
+        }
+        Rp.w_block0[7] = at_block;
+        Rp.n = n;
+        hipLaunchKernelGGL(grad_reduce_all_kernel, dim3((unsigned)(at_block + 7 * 128 / 4)), dim3(256), 0, st, Rp);
+    }
+    // block 1 from the float32 gradient at its pre-activations
+    hipLaunchKernelGGL(stem_wgrad_kernel, dim3(PG_GRID), dim3(256), 0, st, (const float *)S.dyf, T.own, T.opp, n, S.spart);
+    hipLaunchKernelGGL(stem_reduce_kernel, dim3((STEM_PART + 3) / 4), dim3(256), 0, st, (const float *)S.spart, PG_GRID,
+                       T.g_w1, T.g_b1);
+    return iago_check_launch(who);
+}
+
+} // extern "C++"
+
 int iago_policy_reinforce_grad(const iago_policy_grad_args *A, void *stream)
 {
     if (!A || A->n < 0 || A->n_mean <= 0)
@@ -656,99 +1042,116 @@ int iago_policy_reinforce_grad(const iago_policy_grad_args *A, void *stream)
                                            "(iago_policy_grad_workspace_bytes)");
     if (n == 0)
         return iago_fail(IAGO_ERR_INVALID, "iago_policy_reinforce_grad: no rows");
-    hipStream_t st = (hipStream_t)stream;
-    char *at = (char *)A->workspace;
-    auto take = [&](int64_t bytes) {
-        char *p = at;
-        at += pg_round(bytes);
-        return (void *)p;
-    };
-    void *x_hi[8], *x_lo[8];
-    for (int k = 0; k < 8; k++) {
-        x_hi[k] = take(n * (k ? 16384 : 8192));
-        x_lo[k] = take(n * (k ? 16384 : 8192));
-    }
-    float *dyf = (float *)take(n * 32768);
-    void *dys_hi = take(n * 16384), *dys_lo = take(n * 16384);
-    // (partial sums of the weight and bias gradients: a buffer per block, reduced by ONE launch at the end)
-    float *wpart[7], *bpart[7];
-    for (int k = 0; k < 7; k++) {
-        wpart[k] = (float *)take((int64_t)PG_MAX_GROUPS * 9 * 128 * (k ? 128 : 64) * 4);
-        bpart[k] = (float *)take(((n * 8 + 1) / 2) * 32 * 4);
-    }
-    float *hpart = (float *)take((int64_t)PG_GRID * HEAD_PART * 4);
-    float *spart = (float *)take((int64_t)PG_GRID * STEM_PART * 4);
-    uint32_t *max_bits = (uint32_t *)take(256); // [0..7]: of the gradient at block k + 1's pre-activations; [16..23]: scales
-    int32_t *scale_exp = (int32_t *)(max_bits + 16);
-    if (hipMemsetAsync(max_bits, 0, 256, st) != hipSuccess)
-        return iago_fail(IAGO_ERR_HIP, "iago_policy_reinforce_grad: hipMemsetAsync failed");
-
-    // forward, every block's output kept (src/train_rl.py:61)
-    int rc = iago_value_stem_boards(A->own, A->opp, A->w1, A->b1, x_hi[0], x_lo[0], n, A->overflow, stream);
-    for (int k = 0; k < 7 && rc == IAGO_OK; k++)
-        rc = iago_conv3x3_split(x_hi[k], x_lo[k], A->w_hi[k], A->w_lo[k], A->bias[k], x_hi[k + 1], x_lo[k + 1], n,
-                                k ? 128 : 64, 128, A->overflow, stream);
-    if (rc != IAGO_OK)
-        return rc;
+    const PgTrunk T = {A->own, A->opp, n, A->w1, A->b1, A->w_hi, A->w_lo, A->wt_hi, A->wt_lo, A->bias,
+                       A->g_w1, A->g_b1, A->g_w, A->g_b, A->overflow};
     // head + loss, forward and backward (src/train_rl.py:61-65)
-    const float inv_n = 1.0f / (float)A->n_mean;
-    HeadGradParams H;
-    H.x_hi = (const uint4 *)x_hi[7];
-    H.x_lo = (const uint4 *)x_lo[7];
-    H.w9 = A->w9;
-    H.b10 = A->b10;
-    H.action = A->action;
-    H.reward = A->reward;
-    H.inv_n = inv_n;
-    H.n = n;
-    H.dy = (float4v *)dyf;
-    H.max_bits = max_bits + 7;
-    H.part = hpart;
-    H.probs = A->probs;
-    H.bad = A->overflow;
-    hipLaunchKernelGGL(head_grad_kernel, dim3(PG_GRID), dim3(256), 0, st, H);
-    hipLaunchKernelGGL(head_reduce_kernel, dim3((HEAD_PART + 3) / 4), dim3(256), 0, st, (const float *)hpart, PG_GRID, inv_n, A->g_w9,
-                       A->g_b10, A->loss);
-    // blocks 8 .. 2: the gradient at the block's pre-activations (float32 in dyf) -> its scaled pieces + the bias
-    // gradient; the weight gradient; the gradient at the pre-activations of the block below
-    for (int k = 6; k >= 0 && rc == IAGO_OK; k--) {
-        const int cin = k ? 128 : 64;
-        rc = iago_split_scaled(dyf, max_bits + k + 1, dys_hi, dys_lo, scale_exp + k + 1, n, 128, bpart[k], nullptr, stream);
-        if (rc == IAGO_OK)
-            rc = iago_conv3x3_wgrad_split(dys_hi, dys_lo, x_hi[k], x_lo[k], n, cin, wpart[k], pg_groups(cin),
-                                          scale_exp + k + 1, nullptr, stream);
-        if (rc == IAGO_OK)
-            rc = iago_conv3x3_bwd_data_split(dys_hi, dys_lo, scale_exp + k + 1, A->wt_hi[k], A->wt_lo[k], x_hi[k], x_lo[k],
-                                             cin, dyf, max_bits + k, n, stream);
-    }
-    if (rc != IAGO_OK)
-        return rc;
-    {
-        ReduceAllParams Rp;
-        int at_block = 0;
-        for (int k = 0; k < 7; k++) {
-            const int cin = k ? 128 : 64;
-            Rp.wpart[k] = wpart[k];
-            Rp.bpart[k] = bpart[k];
-            Rp.dw[k] = A->g_w[k];
-            Rp.db[k] = A->g_b[k];
-            Rp.scale_exp[k] = scale_exp + k + 1;
-            Rp.groups[k] = pg_groups(cin);
-            Rp.cin[k] = cin;
-            Rp.w_block0[k] = at_block;
-            at_block += (9 * 128 * cin + 255) / 256;
-        }
-        Rp.w_block0[7] = at_block;
-        Rp.n = n;
-        hipLaunchKernelGGL(grad_reduce_all_kernel, dim3((unsigned)(at_block + 7 * 128 / 4)), dim3(256), 0, st, Rp);
-    }
-    // block 1 from the float32 gradient at its pre-activations
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3(PG_GRID), dim3(256), 0, st, (const float *)dyf, A->own, A->opp, n, spart);
-    hipLaunchKernelGGL(stem_reduce_kernel, dim3((STEM_PART + 3) / 4), dim3(256), 0, st, (const float *)spart, PG_GRID,
-                       A->g_w1, A->g_b1);
-    return iago_check_launch("iago_policy_reinforce_grad");
+    auto head = [&](const PgScratch &S) {
+        hipStream_t st = (hipStream_t)stream;
+        const float inv_n = 1.0f / (float)A->n_mean;
+        HeadGradParams H;
+        H.x_hi = (const uint4 *)S.x_hi[7];
+        H.x_lo = (const uint4 *)S.x_lo[7];
+        H.w9 = A->w9;
+        H.b10 = A->b10;
+        H.action = A->action;
+        H.reward = A->reward;
+        H.inv_n = inv_n;
+        H.n = n;
+        H.dy = (float4v *)S.dyf;
+        H.max_bits = S.max_bits + 7;
+        H.part = S.hpart;
+        H.probs = A->probs;
+        H.bad = A->overflow;
+        hipLaunchKernelGGL(head_grad_kernel, dim3(PG_GRID), dim3(256), 0, st, H);
+        hipLaunchKernelGGL(head_reduce_kernel, dim3((HEAD_PART + 3) / 4), dim3(256), 0, st, (const float *)S.hpart,
+                           PG_GRID, inv_n, A->g_w9, A->g_b10, A->loss);
+        return IAGO_OK;
+    };
+    return pg_trunk_grad(T, A->workspace, stream, "iago_policy_reinforce_grad", head);
 }
 
+// the head's scratch behind the trunk's: h9, dh10, dpre9 per board, the two head kernels' partial sums
+static int64_t value_head_bytes(int64_t n)
+{
+    return 2 * pg_round(n * 64 * 4) + pg_round(n * 128 * 4) + pg_round((int64_t)PG_GRID * VHEAD_PART * 4) +
+           pg_round((int64_t)PG_GRID * VW_PART * 4);
+}
+
+int64_t iago_value_grad_workspace_bytes(int64_t n)
+{
+    if (n < 0)
+        return -1;
+    return iago_policy_grad_workspace_bytes(n) + value_head_bytes(n);
+}
+
+int iago_value_mse_grad(const iago_value_grad_args *A, void *stream)
+{
+    if (!A)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: null arguments");
+    const int64_t n = A->n;
+    if (n <= 0 || A->n_mean <= 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: n and n_mean must be positive");
+    if (!A->own || !A->opp || !A->result || !A->w1 || !A->b1 || !A->w9 || !A->b9 || !A->w10 || !A->w11 ||
+        !A->g_w1 || !A->g_b1 || !A->g_w9 || !A->g_b9 || !A->g_w10 || !A->g_w11 || !A->loss || !A->workspace)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: null pointer");
+    for (int k = 0; k < 7; k++)
+        if (!A->w_hi[k] || !A->w_lo[k] || !A->wt_hi[k] || !A->wt_lo[k] || !A->bias[k] || !A->g_w[k] || !A->g_b[k])
+            return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: null pointer (blocks 2..8)");
+    if (A->workspace_bytes < iago_value_grad_workspace_bytes(n) || ((uintptr_t)A->workspace & 255))
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: workspace too small or not 256-byte aligned "
+                                           "(iago_value_grad_workspace_bytes)");
+    if (!isfinite(A->dropout_scale))
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_mse_grad: dropout_scale must be finite");
+    const PgTrunk T = {A->own, A->opp, n, A->w1, A->b1, A->w_hi, A->w_lo, A->wt_hi, A->wt_lo, A->bias,
+                       A->g_w1, A->g_b1, A->g_w, A->g_b, A->overflow};
+    // head + loss, forward and backward (train_value.py:53-57)
+    auto head = [&](const PgScratch &S) {
+        hipStream_t st = (hipStream_t)stream;
+        char *at = S.end;
+        auto take = [&](int64_t bytes) {
+            char *p = at;
+            at += pg_round(bytes);
+            return (float *)p;
+        };
+        float *h9 = take(n * 64 * 4), *dh10 = take(n * 128 * 4), *dpre9 = take(n * 64 * 4);
+        float *hpart = take((int64_t)PG_GRID * VHEAD_PART * 4), *wpart = take((int64_t)PG_GRID * VW_PART * 4);
+        ValueHeadGradParams H;
+        H.x_hi = (const uint4 *)S.x_hi[7];
+        H.x_lo = (const uint4 *)S.x_lo[7];
+        H.w9 = A->w9;
+        H.b9 = A->b9;
+        H.w10 = A->w10;
+        H.w11 = A->w11;
+        H.result = A->result;
+        H.keep = A->keep;
+        H.scale = A->dropout_scale;
+        H.two_over_n = (float)(2.0 / (double)A->n_mean); // (Chainer: gy * float32(2 / size))
+        H.n = n;
+        H.dy = (float4v *)S.dyf;
+        H.max_bits = S.max_bits + 7;
+        H.h9 = h9;
+        H.dh10 = dh10;
+        H.dpre9 = dpre9;
+        H.part = hpart;
+        H.pred = A->pred;
+        H.h9_out = A->h9;
+        hipLaunchKernelGGL(value_head_grad_kernel, dim3(PG_GRID), dim3(256), 0, st, H);
+        ValueWgradParams W;
+        W.x_hi = (const uint4 *)S.x_hi[7];
+        W.x_lo = (const uint4 *)S.x_lo[7];
+        W.h9 = h9;
+        W.dh10 = dh10;
+        W.dpre9 = dpre9;
+        W.n = n;
+        W.part = wpart;
+        hipLaunchKernelGGL(value_head_wgrad_kernel, dim3(PG_GRID), dim3(256), 0, st, W);
+        hipLaunchKernelGGL(value_head_reduce_kernel, dim3((VW_PART + VHEAD_PART + 255) / 256), dim3(256), 0, st,
+                           (const float *)wpart, (const float *)hpart, PG_GRID, (float)A->n_mean, A->g_w10, A->g_w9,
+                           A->g_w11, A->g_b9, A->loss);
+        return IAGO_OK;
+    };
+    return pg_trunk_grad(T, A->workspace, stream, "iago_value_mse_grad", head);
+}
 
 int iago_adam_chainer(const iago_adam_args *a, void *stream)
 {

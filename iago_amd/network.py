@@ -174,14 +174,7 @@ class SLPolicy(nn.Module, _NpzMixin):
     def _bwd_layers(self):
         """Blocks 2..8 in the backward-data form of iago_policy_reinforce_grad (transposed, flipped, two f16 pieces),
         rebuilt when the weights change."""
-        from . import ops
-        ws = [getattr(self, "block%d" % k).conv.weight for k in range(2, 9)]
-        key = tuple((w._version, w.data_ptr()) for w in ws)
-        hit = self.__dict__.get("_bwd_cache")
-        if hit is None or hit[0] != key:
-            hit = (key, ops.split_weights_transposed_many(ws))
-            self.__dict__["_bwd_cache"] = hit
-        return hit[1]
+        return _bwd_layers(self)
 
     GRAD_CHUNK_ROWS = int(os.environ.get("IAGO_GRAD_CHUNK_ROWS", "4096"))   # 1.25 GB of scratch per chunk
 
@@ -340,6 +333,19 @@ class SLPolicy(nn.Module, _NpzMixin):
             return ops.policy_head(h, self.conv9.weight.reshape(128), self.bias10.b, n_dev)
 
 
+def _bwd_layers(module):
+    """Blocks 2..8 of SLPolicy / Value in the backward-data form of the gradient kernels (transposed, flipped, two f16
+    pieces: ops.split_weights_transposed_many), cached by the weights' _version: rebuilt after every optimiser step."""
+    from . import ops
+    ws = [getattr(module, "block%d" % k).conv.weight for k in range(2, 9)]
+    key = tuple((w._version, w.data_ptr()) for w in ws)
+    hit = module.__dict__.get("_bwd_cache")
+    if hit is None or hit[0] != key:
+        hit = (key, ops.split_weights_transposed_many(ws))
+        module.__dict__["_bwd_cache"] = hit
+    return hit[1]
+
+
 def _f32_weights(module, k):
     """Cached [4][9][cin][32] layout of block k's weight (ops.f32_weights)."""
     from . import ops
@@ -468,6 +474,68 @@ class Value(nn.Module, _NpzMixin):
         return hit[1]
 
     fused = True   # one launch for the whole net (iago_value_forward_split); False: stem, trunk, head
+
+    GRAD_CHUNK_ROWS = int(os.environ.get("IAGO_GRAD_CHUNK_ROWS", "4096"))   # 1.25 GB of scratch per chunk
+
+    def value_grads(self, own, opp, result, keep=None, n_mean=None, pred=None):
+        """train_value.py:53-57 on the matrix units in split-f16 arithmetic (iago_value_mse_grad): cleargrads +
+        loss.backward() for loss = mean_squared_error(self(x), result); every parameter's .grad is overwritten.
+        own / opp: the positions (own = the side to move); keep: optional (n, 128) dropout mask of fc10's units
+        (nonzero = kept, scaled by float32(1 / (1 - 0.4)) as F.dropout does; None = no dropout, the eval-mode
+        gradient); n_mean: the row count the mean divides by (default n); pred: optional (n,) float32, the model's
+        output.  An activation of the forward that leaves the f16 range raises bit 0 of the module's overflow word
+        (see check_saturation): those gradients must not be applied.  Returns the loss (0-dim device tensor).  The
+        kernels' scratch is shared with SLPolicy.reinforce_grads and freed by ops.release_grad_workspace()."""
+        if not self.split_f16:
+            raise ValueError("value_grads: the split-f16 kernels compute the gradients; this module is set to "
+                             "split_f16 = False (float32 autograd is SupervisedTrainer(native=False))")
+        from . import ops
+        convs = [getattr(self, "block%d" % k).conv for k in range(2, 9)]
+        params = [self.block1.conv.weight, self.block1.conv.bias, self.block9.conv.weight, self.block9.conv.bias,
+                  self.fc10.weight, self.fc11.weight]
+        for c in convs:
+            params += [c.weight, c.bias]
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise ValueError("value_grads: float32 CUDA parameters expected")
+            if p.grad is None:
+                p.grad = torch.empty_like(p)
+        layers = [self._split_weights(k) + (getattr(self, "block%d" % k).conv.bias.detach(),) for k in range(2, 9)]
+        grads = dict(w1=self.block1.conv.weight.grad, b1=self.block1.conv.bias.grad,
+                     w=[c.weight.grad for c in convs], b=[c.bias.grad for c in convs],
+                     w9=self.block9.conv.weight.grad, b9=self.block9.conv.bias.grad,
+                     w10=self.fc10.weight.grad, w11=self.fc11.weight.grad)
+        n = own.numel()
+        n_mean = n if n_mean is None else n_mean
+        own, opp = own.contiguous(), opp.contiguous()
+        result = result.to(torch.float32).contiguous()
+        if keep is not None:
+            keep = keep.to(torch.uint8).contiguous()
+        layers_t = _bwd_layers(self)
+
+        def rows(lo, hi):
+            return ops.value_mse_grad(own[lo:hi], opp[lo:hi], result[lo:hi], n_mean,
+                                      self.block1.conv.weight.detach(), self.block1.conv.bias.detach(), layers,
+                                      layers_t, self.block9.conv.weight.detach(), self.block9.conv.bias.detach(),
+                                      self.fc10.weight.detach(), self.fc11.weight.detach(), grads,
+                                      keep=None if keep is None else keep[lo:hi],
+                                      pred=None if pred is None else pred[lo:hi],
+                                      overflow=self._overflow_flag(own.device))
+        # as SLPolicy.reinforce_grads: beyond GRAD_CHUNK_ROWS rows in chunks, every chunk dividing by the same n_mean,
+        # the chunks' gradients added in chunk order (deterministic)
+        chunk = self.GRAD_CHUNK_ROWS
+        if n <= chunk:
+            return rows(0, n)
+        total = [torch.zeros_like(p) for p in params]
+        loss = None
+        for lo in range(0, n, chunk):
+            part = rows(lo, min(n, lo + chunk))
+            loss = part if loss is None else loss + part
+            for t, p in zip(total, params):
+                t += p.grad
+        for t, p in zip(total, params):
+            p.grad.copy_(t)
+        return loss
 
     def _forward_split(self, x, device):
         """x: planes (n,2,8,8) or (own, opp).  The whole net in one launch."""

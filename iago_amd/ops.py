@@ -580,9 +580,9 @@ def adam_chainer(params, grads, ms, vs, alpha_t, beta1, beta2, eps, weight_decay
 _grad_workspace = {}
 
 
-def policy_grad_workspace(device, n):
-    """The scratch of iago_policy_reinforce_grad for n rows on `device`: kept, grown in steps of 256 rows."""
-    need = int(_lib.lib().iago_policy_grad_workspace_bytes((n + 255) // 256 * 256))
+def _grad_workspace_at_least(device, need):
+    """The one scratch buffer of the gradient entry points on `device` (iago_policy_reinforce_grad,
+    iago_value_mse_grad): kept between calls, grown to the largest need seen."""
     ws = _grad_workspace.get(str(device))
     if ws is None or ws.numel() < need:
         _grad_workspace[str(device)] = ws = None      # (release before the larger allocation)
@@ -591,8 +591,19 @@ def policy_grad_workspace(device, n):
     return ws
 
 
+def policy_grad_workspace(device, n):
+    """The scratch of iago_policy_reinforce_grad for n rows on `device`: kept, grown in steps of 256 rows."""
+    return _grad_workspace_at_least(device, int(_lib.lib().iago_policy_grad_workspace_bytes((n + 255) // 256 * 256)))
+
+
+def value_grad_workspace(device, n):
+    """The scratch of iago_value_mse_grad for n rows on `device`: the same buffer as policy_grad_workspace's."""
+    return _grad_workspace_at_least(device, int(_lib.lib().iago_value_grad_workspace_bytes((n + 255) // 256 * 256)))
+
+
 def release_grad_workspace():
-    """Free the scratch policy_grad_workspace keeps (308 KB per row of the largest batch seen + 247 MB)."""
+    """Free the scratch policy_grad_workspace / value_grad_workspace keep (308 KB per row of the largest batch seen
+    + 247 MB)."""
     _grad_workspace.clear()
 
 
@@ -625,6 +636,51 @@ def policy_reinforce_grad(own, opp, action, reward, n_mean, w1, b1, layers, laye
     A.workspace, A.workspace_bytes = ws.data_ptr(), ws.numel()
     A.overflow = _flag(overflow)
     check(_lib.lib().iago_policy_reinforce_grad(C.byref(A), _stream()), "iago_policy_reinforce_grad")
+    return loss
+
+
+DROPOUT_SCALE = float(np.float32(1.0 / (1.0 - 0.4)))   # F.dropout(h, 0.4)'s factor of the kept units, float32
+
+
+def value_mse_grad(own, opp, result, n_mean, w1, b1, layers, layers_t, w9, b9, w10, w11, grads, keep=None,
+                   dropout_scale=DROPOUT_SCALE, pred=None, h9=None, overflow=None):
+    """iago_value_mse_grad (include/iago_hip_training.h): the gradients of sum((Value(x) - result)^2) / n_mean
+    (train_value.py:53-57) written to `grads` = dict(w1, b1, w=[7], b=[7], w9, b9, w10, w11) of float32 tensors in
+    the parameters' shapes.  layers: 7 x (w_hi, w_lo, bias) as for conv3x3_split; layers_t: 7 x (wt_hi, wt_lo) from
+    split_weights_transposed.  keep: optional (n, 128) mask of fc10's units (nonzero = kept, scaled by
+    dropout_scale); None = no dropout.  pred (n,) / h9 (n, 64): optional float32 outputs.  Returns the loss (0-dim
+    float32 device tensor)."""
+    n = own.numel()
+    dev = own.device
+    ws = value_grad_workspace(dev, n)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    A = _lib.ValueGradArgs()
+    A.own, A.opp = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp")
+    A.result = _dev(result, torch.float32, "result")
+    if keep is not None:
+        if tuple(keep.shape) != (n, 128):
+            raise ValueError("value_mse_grad: keep must be (n, 128)")
+        A.keep = _dev(keep, torch.uint8, "keep")
+    A.dropout_scale = dropout_scale
+    A.n, A.n_mean = n, int(n_mean)
+    A.w1, A.b1 = _dev(w1, torch.float32, "w1"), _dev(b1, torch.float32, "b1")
+    for k in range(7):
+        A.w_hi[k], A.w_lo[k] = _dev(layers[k][0], torch.float16, "w_hi").value, _dev(layers[k][1], torch.float16, "w_lo").value
+        A.bias[k] = _dev(layers[k][2], torch.float32, "bias").value
+        A.wt_hi[k], A.wt_lo[k] = (_dev(layers_t[k][0], torch.float16, "wt_hi").value,
+                                  _dev(layers_t[k][1], torch.float16, "wt_lo").value)
+        A.g_w[k], A.g_b[k] = _dev(grads["w"][k], torch.float32, "g_w").value, _dev(grads["b"][k], torch.float32, "g_b").value
+    A.w9, A.b9 = _dev(w9, torch.float32, "w9"), _dev(b9, torch.float32, "b9")
+    A.w10, A.w11 = _dev(w10, torch.float32, "w10"), _dev(w11, torch.float32, "w11")
+    A.g_w1, A.g_b1 = _dev(grads["w1"], torch.float32, "g_w1"), _dev(grads["b1"], torch.float32, "g_b1")
+    A.g_w9, A.g_b9 = _dev(grads["w9"], torch.float32, "g_w9"), _dev(grads["b9"], torch.float32, "g_b9")
+    A.g_w10, A.g_w11 = _dev(grads["w10"], torch.float32, "g_w10"), _dev(grads["w11"], torch.float32, "g_w11")
+    A.loss = _dev(loss, torch.float32, "loss")
+    A.pred = _dev(pred, torch.float32, "pred") if pred is not None else None
+    A.h9 = _dev(h9, torch.float32, "h9") if h9 is not None else None
+    A.workspace, A.workspace_bytes = ws.data_ptr(), ws.numel()
+    A.overflow = _flag(overflow)
+    check(_lib.lib().iago_value_mse_grad(C.byref(A), _stream()), "iago_value_mse_grad")
     return loss
 
 

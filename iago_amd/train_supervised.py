@@ -9,14 +9,20 @@ same double softmax as in REINFORCE; it is reproduced here.  Data sets are
 [x==1, x==2] planes of "white(2) to play" boards (load.py:41-47) are
 encode_planes(own = the 2-stones, opp = the 1-stones).  Data preparation
 (load.py) and the 8-fold augmentation are ops.augment8.
+
+native=True computes every minibatch's loss and gradients with the split-f16
+gradient kernels of the library (network.Value.value_grads,
+network.SLPolicy.reinforce_grads) instead of autograd over the tensor
+library's float32 convolutions; the optimiser step is the same.
 """
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, network, ops
 from .train_rl import ChainerAdam
 
 MINIBATCH = 4096  # train_policy.py:43, train_value.py:33
+DROPOUT_RATIO = 0.4  # network.py:95, F.dropout(h, 0.4) in training mode
 
 
 def policy_loss(model, own, opp, actions):
@@ -31,16 +37,60 @@ def value_loss(model, own, opp, results):
 
 class SupervisedTrainer(object):
     """kind = 'policy' (SLPolicy / RolloutPolicy, labels = actions) or 'value'
-    (Value, labels = results)."""
+    (Value, labels = results).
 
-    def __init__(self, model, kind, seed=0, device="cuda"):
+    native=True: the minibatches' gradients come from the split-f16 kernels --
+    Value + 'value' through Value.value_grads (iago_value_mse_grad), SLPolicy +
+    'policy' through SLPolicy.reinforce_grads with every reward 1 (the
+    supervised loss mean(softmax_cross_entropy(softmax(logits), y)) is the
+    REINFORCE loss with r = 1).  Any other model, or a model set to
+    `split_f16 = False` / `split3 = False`, raises ValueError.  The dropout of
+    a native Value step draws its mask from the trainer's generator: per
+    minibatch, right after that minibatch's slice of the epoch's permutation
+    (torch.randperm(n, generator=self.gen) once per epoch),
+    keep = torch.rand((m, 128), generator=self.gen) >= DROPOUT_RATIO.  A step
+    whose forward left the f16 range raises IagoError and applies nothing."""
+
+    def __init__(self, model, kind, seed=0, device="cuda", native=False):
         if kind not in ("policy", "value"):
             raise ValueError("kind must be 'policy' or 'value'")
-        self.model, self.kind = model.to(device), kind
+        if native:
+            if kind == "value" and isinstance(model, network.Value):
+                if not model.split_f16:
+                    raise ValueError("native=True: the Value net is set to split_f16 = False")
+            elif kind == "policy" and isinstance(model, network.SLPolicy):
+                if not model.split3:
+                    raise ValueError("native=True: the SLPolicy net is set to split3 = False")
+            else:
+                raise ValueError("native=True trains Value ('value') or SLPolicy ('policy'), not %s ('%s')"
+                                 % (type(model).__name__, kind))
+        self.model, self.kind, self.native = model.to(device), kind, native
         self.opt = ChainerAdam(self.model)                     # optimizers.Adam() + WeightDecay(5e-4)
         self.gen = torch.Generator(device=device)
         self.gen.manual_seed(seed)
         self.loss_fn = policy_loss if kind == "policy" else value_loss
+
+    def _native_step(self, own, opp, labels):
+        """One minibatch through the gradient kernels, then Adam -- unless the forward saturated."""
+        m = own.numel()
+        if self.kind == "value":
+            keep = torch.rand((m, 128), device=own.device, generator=self.gen) >= DROPOUT_RATIO
+            loss = self.model.value_grads(own, opp, labels, keep=keep)
+        else:
+            ones = torch.ones(m, dtype=torch.float32, device=own.device)
+            loss = self.model.reinforce_grads(own, opp, labels, ones)
+        # the loss and the saturation word in ONE read-back, BEFORE Adam: the gradients of a clamped forward (or of a
+        # label outside 0 .. 63) must not reach the parameters
+        flag = self.model._overflow_flag(own.device)
+        loss_v, bad = torch.stack([loss.to(torch.float64), flag[0].to(torch.float64)]).tolist()
+        if bad:
+            flag.zero_()
+            raise _lib.IagoError(
+                "supervised native step: %s; no update was applied.  Train with native=False (float32 autograd)"
+                % ("a label lies outside 0 .. 63" if int(bad) & 2 else
+                   "an activation of the forward left the f16 range of the split kernels (|a| > 65000) or is NaN"))
+        self.opt.update()
+        return loss_v
 
     def epoch(self, own, opp, labels):
         """One shuffled sweep (train_policy.py:46-62); returns the mean minibatch loss."""
@@ -50,6 +100,10 @@ class SupervisedTrainer(object):
         total, count = 0.0, 0
         for lo in range(0, n, MINIBATCH):
             idx = perm[lo:lo + MINIBATCH]
+            if self.native:
+                total += self._native_step(own[idx], opp[idx], labels[idx])
+                count += 1
+                continue
             for p in self.model.parameters():
                 p.grad = None
             loss, _ = self.loss_fn(self.model, own[idx], opp[idx], labels[idx])

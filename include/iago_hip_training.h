@@ -1,0 +1,61 @@
+/*
+ * iago_hip_training.h -- training the nets on the library's own kernels: the supervised update of the Value net
+ * (train_value.py).  Same conventions as iago_hip.h; part of the library's ABI (iago_abi_version).
+ */
+#ifndef IAGO_HIP_TRAINING_H
+#define IAGO_HIP_TRAINING_H
+
+#include "iago_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/*
+ * iago_value_mse_grad: the whole of train_value.py:53-57 -- pred = model(x), loss = mean_squared_error(pred, y),
+ *   model.cleargrads(), loss.backward() -- for n rows of the Value net (network.py:66-96), in the split-f16 arithmetic
+ *   of iago_policy_reinforce_grad (csrc/policy_grad_kernels.hip; the trunk, blocks 1..8, runs the same kernels):
+ *   forward with every block's output kept, then the head and the loss forward and backward in float32:
+ *     h9 = relu(conv3x3(x8; w9) + b9) [n][64],  h10 = w10 . h9,  d = h10 * (keep ? dropout_scale : 0),
+ *     pred = w11 . d,  loss = sum (pred - y)^2 / n_mean,  dpred = float32(2 / n_mean) (pred - y),
+ *   dw11, dh10 through the mask, dw10, dh9 masked by h9 > 0, dw9 / db9, and the gradient at block 8's
+ *   pre-activations (masked by x8 > 0); from there blocks 8..2 and block 1 as iago_policy_reinforce_grad.
+ *   Every sum has a fixed order (partial sums per workgroup, then a reduction launch): the same bits run after run.
+ *   own / opp [n]: the positions, own = the side to move; result [n] float32 (y); keep: optional uint8 [n][128], the
+ *   dropout mask of fc10's output (0 = dropped; NULL = no dropout, the eval-mode gradient); dropout_scale: the kept
+ *   units' factor, float32(1 / (1 - 0.4)) as F.dropout scales (finite); n_mean: the row count the mean divides by.
+ *   w1 [64][2][3][3], b1 [64]; blocks 2..8 as in iago_policy_grad_args; w9 [1][128][3][3], b9 [1], w10 [128][64],
+ *   w11 [1][128].  g_*: the gradients in the parameters' own layouts; loss: device float; pred: optional [n], the
+ *   model's output; h9: optional [n][64], block 9's output.  workspace: iago_value_grad_workspace_bytes(n) bytes,
+ *   256-byte aligned.  overflow: bit 0 as for iago_conv3x3_split (the forward left the f16 range): that call's loss
+ *   and gradients must not be used.  Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or
+ *   pointer, n <= 0, n_mean <= 0, a workspace too small or misaligned, or a non-finite dropout_scale.
+ */
+typedef struct iago_value_grad_args {
+    const uint64_t *own, *opp;
+    const float *result;
+    const uint8_t *keep;
+    float dropout_scale;
+    int64_t n, n_mean;
+    const float *w1, *b1;
+    const void *w_hi[7], *w_lo[7], *wt_hi[7], *wt_lo[7];
+    const float *bias[7];
+    const float *w9, *b9, *w10, *w11;
+    float *g_w1, *g_b1;
+    float *g_w[7], *g_b[7];
+    float *g_w9, *g_b9, *g_w10, *g_w11;
+    float *loss;
+    float *pred, *h9;
+    void *workspace;
+    int64_t workspace_bytes;
+    uint32_t *overflow;
+} iago_value_grad_args;
+/* bytes of the workspace of iago_value_mse_grad for n rows (-1 for n < 0) */
+IAGO_API int64_t iago_value_grad_workspace_bytes(int64_t n);
+IAGO_API int iago_value_mse_grad(const iago_value_grad_args *args, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* IAGO_HIP_TRAINING_H */
