@@ -234,6 +234,7 @@ class BatchedMCTS(object):
         self._fresh_count = torch.zeros(1, dtype=torch.int32, **kw)
         self._value_total = torch.zeros(1, dtype=torch.int64, **kw)  # value-net evaluations, on the device
         self._value_key = None
+        self._policy_key = None
         self.fused_leaf_eval = os.environ.get("IAGO_FUSED_LEAF_EVAL", "1") != "0"
         self.cur_node = torch.zeros(ns, dtype=torch.int32, **kw)
         self.cur_own = torch.zeros(ns, dtype=torch.int64, **kw)
@@ -460,14 +461,21 @@ class BatchedMCTS(object):
                 self._ev_priors = torch.cuda.Event()
                 self._ev_rows = torch.cuda.Event()
 
+            # games whose cached priors were computed by policy weights that have changed since (search() refreshes
+            # them when the game next searches: its roots are known then)
+            self._la_stale = torch.zeros(n_games, dtype=torch.bool, **kw)
+            self._la_stale_any = False
+
             def reset_lookahead(mask):
                 if mask is None:
                     self._la_next_seq.zero_()
                     self._la_cache_seq.fill_(-1)
+                    self._la_stale.zero_()
                 else:
                     m = mask.bool()
                     self._la_next_seq[m] = 0
                     self._la_cache_seq[m] = -1
+                    self._la_stale[m] = False
             self.tree.reset_hooks = [reset_lookahead]
         self.value_ahead = bool(getattr(self, "value_ahead", False))
         if self.persistent:
@@ -804,6 +812,48 @@ class BatchedMCTS(object):
         check(_lib.lib().iago_mcts_store_priors(C.byref(self._la[which]), _p(probs), _p(self._pend_total),
                                                 _stream()), "iago_mcts_store_priors")
         q["count"].zero_()
+
+    def _refresh_priors(self, own, opp, active):
+        """The policy net's weights changed since the look-ahead cached the priors of leaves that have not expanded
+        yet: those priors again, from the current weights (the reference evaluates the net when the leaf expands,
+        MCTS.py:109-121), for the games of `active` whose priors are stale.  Each leaf's position is rebuilt from its
+        game's root by the moves of its path -- own / opp of an active game ARE its root's position; a game outside
+        `active` stays marked until it searches -- and a leaf no longer under its game's root (left behind by
+        update_with_move) is skipped: it never expands."""
+        games = self._la_stale & (active != 0)
+        self._la_stale &= ~games
+        self._la_stale_any = bool(self._la_stale.any().item())
+        t, S = self.tree, self._la[0].slots
+        dev, cap = t.nodes.device, t.capacity
+        fc = t.first_child.reshape(t.n_games, cap)
+        seq = (-2 - fc).clamp(min=0)
+        cached = self._la_cache_seq.gather(1, (seq % S).to(torch.int64)) == seq
+        live = torch.arange(cap, device=dev).reshape(1, cap) < t.n_nodes.reshape(-1, 1)
+        g, node = torch.nonzero(live & (fc <= -2) & cached & games.reshape(-1, 1), as_tuple=True)
+        if g.numel() == 0:
+            return
+        base, root = g * cap, t.root[g].to(torch.int64)
+        cur, on = node.clone(), node != root
+        acts, steps = [], []
+        while bool(on.any().item()):   # (leaf to root, one level per pass)
+            acts.append(torch.where(on, t.action[base + cur].to(torch.int8), torch.full_like(node, -1, dtype=torch.int8)))
+            steps.append(on.clone())
+            up = t.parent[base + cur].to(torch.int64)
+            cur = torch.where(on & (up >= 0), up, cur)
+            on = on & (up >= 0) & (cur != root)
+        keep = cur == root
+        o, p = own[g].clone(), opp[g].clone()
+        for a, s in zip(reversed(acts), reversed(steps)):   # (root to leaf: the mover's stone, then the other side moves)
+            ops.apply_moves(o, p, a)
+            o, p = torch.where(s, p, o), torch.where(s, o, p)
+        g, slot, o, p = g[keep], (seq[g, node] % S)[keep], o[keep], p[keep]
+        n = int(g.numel())
+        if n == 0:
+            return
+        with torch.no_grad():
+            probs = self.policy_fn.forward_counted_boards(o.contiguous(), p.contiguous(), None, n,
+                                                          torch.full((1,), n, dtype=torch.int32, device=dev))
+        self._la_cache[g, slot] = probs[:n]
 
     def _flush_value_ahead(self, which, rows_event=None):
         """The value look-ahead's batch for the nodes queue `which` holds: one row per child without a
@@ -1221,6 +1271,17 @@ class BatchedMCTS(object):
             # (the descent appends to the fresh-leaf list through this count and the backup clears
             # it: a playout aborted between the two must not leave a stale count behind)
             self._fresh_count.zero_()
+        if self.lookahead:
+            # the cached priors of queued leaves belong to the policy weights that computed them
+            params = getattr(self.policy_fn, "parameters", None)
+            key = tuple((q.data_ptr(), q._version) for q in params()) if params is not None else id(self.policy_fn)
+            if key != self._policy_key:
+                if self._policy_key is not None:
+                    self._la_stale.fill_(True)
+                    self._la_stale_any = True
+                self._policy_key = key
+            if self._la_stale_any:
+                self._refresh_priors(own, opp, active)
         if used > self.tree.capacity // 2 and used > self._live_after_compaction * 5 // 4:
             # a pool is half full: free the nodes that subtree reuse left behind (what the
             # reference's garbage collector does after MCTS.py:149-152) before this search adds

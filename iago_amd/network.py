@@ -162,7 +162,9 @@ class SLPolicy(nn.Module, _NpzMixin):
     def _split3_layers(self):
         from . import ops
         ws = [getattr(self, "block%d" % k).conv for k in range(2, 9)]
-        key = tuple((c.weight._version, c.weight.data_ptr(), c.bias._version) for c in ws)
+        # (the layers hold the bias tensors themselves: a bias whose storage was replaced -- `p.data = ...` keeps
+        # its version -- is told apart by its pointer)
+        key = tuple((c.weight._version, c.weight.data_ptr(), c.bias._version, c.bias.data_ptr()) for c in ws)
         hit = self.__dict__.get("_split3_cache")
         if hit is None or hit[0] != key:
             pieces = ops.split_weights3_many([c.weight for c in ws])

@@ -40,3 +40,17 @@ def random_positions(n, seed):
 def state_of(own, opp):
     """(own, opp) bits -> reference-style board with own = colour 1."""
     return orc.bits_to_state(int(own), int(opp))
+
+
+def fresh(m):
+    """A module of m's class built fresh on m's weights (its own caches, none of m's)."""
+    return type(m)().cuda().eval().load_npz(m.npz_dict())
+
+
+def delta(p, seed):
+    """A deterministic change of the parameter p that moves the shipped nets' outputs well beyond their 1e-5
+    tolerance to float64: noise of half the tensor's mean magnitude plus a floor (the deep layers' weights are ~1e-4)."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    amp = 0.5 * float(p.detach().abs().mean()) + 0.004
+    return (torch.randn(tuple(p.shape), generator=g) * amp).to(device=p.device, dtype=p.dtype)
