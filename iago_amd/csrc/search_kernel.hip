@@ -1,39 +1,21 @@
 // search_kernel.hip -- a whole PV-MCTS search (n_sims playouts of every game: MCTS.get_move's loop,
 // MCTS.py:139-147), or whole self-play games (the turn loop of game.py:117-142,253-255 around it), as
-// ONE persistent launch in which every game runs on its own clock.
-//
-// Why.  MCTS.playout (MCTS.py:105-133) is sequential inside a game, but the games of a batch are
-// independent.  The per-playout engine (mcts_kernels.hip + conv_trunk_kernel.hip: descent, leaf
-// evaluation, backup as three launches per playout for all games) makes every game wait for the
-// slowest kind of playout -- the 16 % that end on a leaf without a stored value, whose one-board walk
-// through the Value net takes 70 us of a 128 us playout --, runs the policy net as batches that hold
-// most of the chip while the playouts' kernels want it, and ends every move with a barrier.  Here the
-// chip is a pool of workgroups (one per CU) of two kinds:
+// ONE persistent launch in which every game runs on its own clock ("The persistent search":
+// why, and the measurements behind its scheduling rules).  The chip is a pool of workgroups of two kinds:
 //   * GAME workgroups (the first ceil(n_games / 32) of the grid: dispatched first, so always resident):
-//     each owns 32 games and loops over descent (8 lanes per game: select, expansion, continued
-//     descent, exactly descend_kernel's arithmetic) -> rollout of the leaves reached (the
-//     16-lanes-per-board body in passes of 16 boards, Philox stream = stream base + turn x n_sims + the
-//     game's own playout count) -> backup (mix_backup_path_kernel's arithmetic) and, with whole games,
-//     the game's move between two of its searches (most visited child, update_with_move, the stone,
-//     the books, the recorded tuple).  A game whose leaf has no stored value -- and whose position the
-//     shared position table does not hold -- writes the leaf's position into a request ring and waits
-//     for the value (its rollout runs meanwhile); a game whose leaf expands (n_visits >= n_thr,
-//     MCTS.py:109) does the same and waits for the priors -- the policy net runs exactly where the
-//     reference runs it (no look-ahead: no evaluation is wasted); the workgroup's other games go on.
+//     each owns 32 games, 8 lanes per game (a wave search: 32 slots, S.wave per tree).  game_workgroup is
+//     a driver loop over phase functions: replies -> a playout's end -> the turn boundary of whole games
+//     (the most visited move, the record, update_with_move, the stone and the books) -> descent (select,
+//     expansion, pass chains; exactly descend_kernel's arithmetic) -> the control words -> rollout passes
+//     of 16 boards (Philox stream = stream base + turn x n_sims + the game's own playout count) -> the
+//     wave's backups -> the iteration's end (pacing, abort) -> a stream's claim of the next games.  A leaf
+//     without a stored value (that the shared position table does not hold) or a node that expands
+//     (n_visits >= n_thr, MCTS.py:109) sends a request to a ring and the game waits for the reply while
+//     its rollout runs and the workgroup's other games go on.
 //   * NET workgroups (the rest of the grid): each takes a ticket of a ring that has an entry waiting
-//     (its home ring first: one ring per net, the policy ring at home on 2 of the 8 XCDs), reads the
-//     entry, walks the board through the Value net (trunk_item<true, 1>, or <true, 2> for two entries
-//     together) or the SLPolicy net (policy_item) -- the kernels' own device functions: bit-identical
-//     numbers -- and publishes the result in the game's mailbox (and the position table).
-// Scheduling inside a game workgroup (timing only): the games that reach a leaf in an iteration are packed
-// into rows of 16 boards for the rollout body (about half of the 32 do: one pass instead of two); a game
-// more than `pace_margin` playouts ahead of the batch's mean progress holds while requests queue up (a
-// batch ends with its slowest game, and a game is slow when it asks the nets a lot: what the leaders do
-// not ask for, the laggards get); a level at which every descending game of the wave has ONE child, a
-// pass (the chains the reference grows under a finished game), is followed without scoring.  And idle net
-// workgroups are put to use: when a game asks for the priors of a node that is about to expand while net
-// workgroups poll and nothing waits in the rings, the node's children are walked through the value net for
-// the position table -- requests nobody waits for; the children's first visits find their values there.
+//     (its home ring first: one ring per net), walks the board through the Value net (trunk_item<true, 1>,
+//     or <true, 2> for two entries together) or the SLPolicy net (policy_item) -- the kernels' own device
+//     functions: bit-identical numbers -- and publishes the result in the game's mailbox (and the table).
 // A game's sequence of playouts -- leaves, values, priors, rollouts, backups, expansions, moves -- is
 // exactly the reference's; only the interleaving between games changes: trees, moves and results are
 // bit-identical to the per-playout engine's (tests/test_search_persistent_gpu.py; the comparisons with
@@ -270,6 +252,13 @@ __device__ __forceinline__ int policy_draw(const u64 *rep, uint64_t lg, double u
     return n;
 }
 
+// entry d of a game's recorded path: in the workgroup's LDS from word path_at (>= 0; an LDS access, not a flat one), else in
+// the caller's array
+__device__ __forceinline__ int path_entry(int path_at, const int32_t *gpath, int d)
+{
+    return path_at >= 0 ? ((const int32_t *)iago_trunk::trunk_lds)[path_at + d] : gpath[d];
+}
+
 // Node.update_recursive (MCTS.py:51-72) over the recorded path + the leaf mix (MCTS.py:123-125): the
 // arithmetic of mix_backup_path_kernel, 8 lanes per game.  g: the slot (its path, its leaf value), gt: its tree (the same
 // unless a wave search, which also takes the playout's in-flight visit off every node of the path)
@@ -297,8 +286,7 @@ __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, ui
     const int len = path_n < S.path_stride ? path_n : S.path_stride;
     const int32_t *const gpath = S.path + g * (int64_t)S.path_stride;
     for (int d = (int)r; d < len; d += 8) {
-        // (path_at >= 0: the path is in the workgroup's LDS at that word; an LDS access, not a flat one)
-        const int node = path_at >= 0 ? ((const int32_t *)iago_trunk::trunk_lds)[path_at + d] : gpath[d];
+        const int node = path_entry(path_at, gpath, d);
         uint2 *nq = (uint2 *)&S.T.nodes[base + node];
         const uint2 old = *nq;
         const int n = (int)old.x + 1;                // MCTS.py:61
@@ -338,835 +326,988 @@ __device__ __forceinline__ bool wg_handoff_or(bool x)
 // never straddles two), and a slot plays one playout of its tree's current wave.  Its descent waits for the slot before
 // it (the tree's `wv_next`, handed over with wg_handoff_or), its leaf is evaluated as in the plain search, and the
 // wave's backups run in slot order once every leaf of the wave has its value.
+// game_workgroup is a driver loop over the phases below; every phase function is called by all threads of the workgroup
+// or, where it says so, by the lanes of the games (`mine`: whole waves).
+
+// a thread of a game workgroup: its game (a wave search: its slot and tree), its place in the group of 8, its path
+struct Slot {
+    int tid, gl;          // the thread, its game's number within the workgroup
+    uint32_t r;           // lane within the game's 8
+    Lane8 L;
+    bool mine, exists;    // a lane of one of the workgroup's games (a wave search: every thread); that game exists
+    int64_t g, gt, base;  // the slot, its tree (the same unless a wave search), the tree's first node
+    int64_t n_slots;
+    int W, s_in, tl;      // a wave search: slots per tree, slot within the tree, tree within the workgroup
+    int path_at;          // word of the dynamic LDS where this game's path starts (-1: in the caller's array)
+    int32_t *gpath;
+    bool whole, need_v, need_z;
+    int search_end;       // where a game goes when its search's last playout is backed up
+};
+
+// a game and its books: its state, the reply tag of its last request (never 0 once used), the playouts of its current
+// search; with whole games its turn, its books (game.py:32,117-142) and its own position (own = side to move)
+struct Game {
+    int state;
+    uint32_t epoch;
+    int n_done, turn, stones;
+    bool pass_flg, g_over;
+    uint64_t g_own, g_opp;
+};
+
+// the descent's cursor (kept across iterations while the game waits for priors): the node, its first child, children,
+// visits, in-flight visits (a wave search) and stored value bits, the position there, the path's length; the leaf reached,
+// whether the node may still expand, whether the leaf had no stored value, and the value that came back for it
+struct Cursor {
+    int node, fc, k, nv, nvv;
+    uint32_t vbits;
+    uint64_t own, opp;
+    int path_n, leaf;
+    bool may_expand, leaf_fresh;
+    float v_reply;
+};
+
+// the static LDS of a game workgroup, declared once
+struct GameLds {
+    // positions, Philox stream offsets and results between the descent / backup and the rollout passes (RowHandoff)
+    uint64_t h_own[GAMES_PER_WG], h_opp[GAMES_PER_WG];
+    int32_t h_stream[GAMES_PER_WG];
+    int32_t h_game[GAMES_PER_WG]; // the game each slot plays (the slot itself unless a stream), read at its end
+    // (diagnostic counters of the workgroup, kept by thread 0 in LDS: as per-thread 64-bit registers they were 12 VGPRs
+    // live across the whole loop -- what the game launch of the role split spilled to scratch memory)
+    uint32_t wg_count[6]; // [0] iterations, [1] idle iterations, [2..5] iterations with 0 / 1..16 / 17..20 / more games rolled out
+    int32_t roll_list[GAMES_PER_WG]; // games whose leaf is rolled out in this iteration, packed
+    uint32_t roll_wave[BLOCK / 64], roll_wave_old[BLOCK / 64];
+    // pacing: the workgroup's changes of CTL_PROGRESS / CTL_PLAYING in an iteration, which go out as one atomic each;
+    // pace[2]: the progress above which a game holds; pace[3]: the iteration's budget of requests nobody waits for
+    int32_t pace[4];
+    uint32_t claimed; // a stream: the first game id of the block the workgroup claimed
+    int8_t h_z[GAMES_PER_WG];
+};
+// a wave search adds, per tree of the workgroup, the slots of its current wave that have descended (the next one to go),
+// the wave's playouts, whether a slot of the wave still waits for its leaf's evaluation
+template <bool WAVE> struct GameShared : GameLds {};
+template <> struct GameShared<true> : GameLds {
+    int32_t wv_next[GAMES_PER_WG], wv_size[GAMES_PER_WG], wv_block[GAMES_PER_WG];
+    long long wv_time[4]; // (diagnostic, thread 0: descents, rollouts, backups, waits; S.wave_timing)
+};
+
 template <bool WAVE>
-__device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0)
+__device__ __forceinline__ Slot make_slot(const SearchParams &S)
 {
-    const Tree &T = S.T;
-    const int tid = threadIdx.x;
-    const bool mine = tid < 8 * S.games_per_wg; // (WAVE: 32 slots, every thread)
-    const int64_t g = (int64_t)blockIdx.x * S.games_per_wg + (tid >> 3);
-    const Lane8 L = make_lane8(threadIdx.x);
-    const uint32_t r = L.l8;
-    const int W = WAVE ? S.wave : 1;
-    const int64_t n_slots = WAVE ? S.n_slots : T.n_games;
-    const bool exists = mine && g < n_slots;
-    const int64_t gt = WAVE ? g / W : g; // the tree
-    const int s_in = WAVE ? (int)(g % W) : 0, tl = WAVE ? (tid >> 3) / W : 0; // slot within the tree, tree within the workgroup
-    const int64_t base = exists ? gt * (int64_t)T.capacity : 0;
-    const bool need_v = S.lmbda < 1.0f, need_z = S.lmbda > 0.0f;
+    Slot I;
+    I.tid = threadIdx.x;
+    I.gl = I.tid >> 3;
+    I.L = make_lane8(threadIdx.x);
+    I.r = I.L.l8;
+    I.mine = I.tid < 8 * S.games_per_wg; // (WAVE: 32 slots, every thread)
+    I.g = (int64_t)blockIdx.x * S.games_per_wg + I.gl;
+    I.W = WAVE ? S.wave : 1;
+    I.n_slots = WAVE ? S.n_slots : S.T.n_games;
+    I.exists = I.mine && I.g < I.n_slots;
+    I.gt = WAVE ? I.g / I.W : I.g;
+    I.s_in = WAVE ? (int)(I.g % I.W) : 0;
+    I.tl = WAVE ? I.gl / I.W : 0;
+    I.base = I.exists ? I.gt * (int64_t)S.T.capacity : 0;
+    I.need_v = S.lmbda < 1.0f;
+    I.need_z = S.lmbda > 0.0f;
     // the descent's recorded path (Node.update_recursive's ancestors): in the workgroup's dynamic LDS -- a game workgroup
     // walks no net while it has games -- when 32 paths fit there, else in the caller's array.  (From global memory the
     // backup was two dependent round trips to L2: the path entry, then the node.)
     const bool path_lds = (size_t)S.games_per_wg * (size_t)S.path_stride * 4u <= (size_t)S.path_lds_cap;
-    const int path_at = path_lds ? (tid >> 3) * S.path_stride : -1; // word of the dynamic LDS where this game's path starts
-    int32_t *const gpath = S.path + (exists ? g : 0) * (int64_t)S.path_stride;
-    // positions, Philox stream offsets and results between the descent / backup and the rollout passes: LDS (RowHandoff)
-    __shared__ uint64_t h_own[GAMES_PER_WG], h_opp[GAMES_PER_WG];
-    __shared__ int32_t h_stream[GAMES_PER_WG];
-    __shared__ int32_t h_game[GAMES_PER_WG]; // the game each slot plays (the slot itself unless a stream), read at its end
-    __shared__ int8_t h_z[GAMES_PER_WG];
-    const iago_row::RowHandoff hand = {h_own, h_opp, h_stream, h_game, h_z, (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
-    const int gl = tid >> 3; // this game's number within the workgroup
-    const int n_here = (int)min((int64_t)S.games_per_wg, n_slots - (int64_t)blockIdx.x * S.games_per_wg); // its slots
+    I.path_at = path_lds ? I.gl * S.path_stride : -1;
+    I.gpath = S.path + (I.exists ? I.g : 0) * (int64_t)S.path_stride;
+    I.whole = S.max_turns > 0;
+    I.search_end = I.whole ? ST_MOVE : ST_DONE;
+    return I;
+}
 
-    const bool whole = S.max_turns > 0;
-    // (a stream: slot g starts game g while there is one -- `active` is not read)
-    const bool first = exists && gt < S.games_total && (S.stream || S.active[gt] != 0);
-    int state = (first && S.n_sims > 0) ? (whole ? ST_TURN : ST_READY) : ST_DONE;
-    // a wave search: per tree of the workgroup, the slots of its current wave that have descended (the next one to go),
-    // the wave's playouts, whether a slot of the wave still waits for its leaf's evaluation
-    __shared__ int32_t wv_next[GAMES_PER_WG], wv_size[GAMES_PER_WG], wv_block[GAMES_PER_WG];
-    __shared__ long long wv_time[4]; // (diagnostic, thread 0: descents, rollouts, backups, waits; S.wave_timing)
-    if (WAVE) {
-        const int m = S.n_sims < W ? S.n_sims : W;
-        if (state == ST_READY && s_in >= m)
-            state = ST_IDLE;
-        if (tid < GAMES_PER_WG) {
-            wv_next[tid] = 0;
-            wv_size[tid] = m;
-            wv_block[tid] = 0;
+// a game's start (game.py:32): its position (own = colour 1, the first mover), its books, no playouts yet
+__device__ __forceinline__ void start_game(Game &G, uint64_t own, uint64_t opp)
+{
+    G.g_own = own;
+    G.g_opp = opp;
+    G.turn = 0;
+    G.stones = 4;
+    G.pass_flg = false;
+    G.g_over = false;
+    G.n_done = 0;
+}
+
+// reset_kernel's Node(None, 1.0) as the tree's only node, its root (one lane)
+__device__ __forceinline__ void fresh_root(const Tree &T, int64_t gt, int64_t base)
+{
+    init_node(T, base, -1, -2, 1.0f + 0.1f);
+    T.n_nodes[gt] = 1;
+    T.root[gt] = 0;
+}
+
+// the two halves of a node record: s = {n_visits, q, p, v}, l = {first_child, parent, action | n_children << 8, vv}
+__device__ __forceinline__ void node_record(const Tree &T, int64_t at, uint4 &s, uint4 &l)
+{
+    s = ((const uint4 *)&T.nodes[at])[0];
+    l = ((const uint4 *)&T.nodes[at])[1];
+}
+
+// the cursor at `node`: an = action | n_children << 8, vv its in-flight visits (a wave search)
+template <bool WAVE>
+__device__ __forceinline__ void cursor_to(Cursor &C, int node, uint32_t fc, uint32_t nv, uint32_t an, uint32_t vv, uint32_t vbits)
+{
+    C.node = node;
+    C.fc = (int)fc;
+    C.k = (int)((an >> 8) & 0xFFu);
+    C.nv = (int)nv;
+    if (WAVE)
+        C.nvv = (int)vv;
+    C.vbits = vbits;
+}
+
+// GameFunctions.place_stone(state, a, c); c = 3 - c (MCTS.py:131-132): move a (< 0: a pass, nothing placed) and the swap
+// of sides.  Every lane of the group takes part (group8_flips)
+__device__ __forceinline__ void place_stone(uint64_t &own, uint64_t &opp, int a, const Lane8 &L)
+{
+    const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
+    uint64_t o = own, p = opp;
+    if (a >= 0) {
+        const uint64_t bit = 1ull << (a & 63);
+        o = own | f | bit;
+        p = opp & ~f & ~bit;
+    }
+    own = p;
+    opp = o;
+}
+
+// Node.select's score of a child (MCTS.py:39-49) against the best so far; strict `>`: the first maximum wins (python max,
+// MCTS.py:46).  pl: the best child's first_child, n_visits, action | n_children << 8 (| vv << 16), v
+template <bool WAVE>
+__device__ __forceinline__ void score_child(const SearchParams &S, uint4 s, uint4 l, int j, double sq, double &best_v,
+                                            int &best_i, uint32_t (&pl)[4])
+{
+    const float p = __uint_as_float(s.z), q = __uint_as_float(s.y);
+    const int n = (int)s.x;
+    double v;
+    if constexpr (WAVE) {
+        v = wave_score(S.c_puct, p, q, n, (int)l.w, sq, (double)S.vloss); // (vv < 2^16: at most 32 playouts in flight)
+    } else {
+        const float cp = S.c_puct * p;                          // float32, MCTS.py:49
+        const double u = (double)cp * sq / (0.01 + (double)n);
+        v = (double)q + u;                                      // get_value, MCTS.py:75-76
+    }
+    if (v > best_v) {
+        best_v = v;
+        best_i = j;
+        pl[0] = l.x, pl[1] = (uint32_t)n, pl[2] = WAVE ? (l.z & 0xFFFFu) | (l.w << 16) : l.z & 0xFFFFu, pl[3] = s.w;
+    }
+}
+
+// the end of a playout of the plain search: the backup, the count, the rollouts' Philox stream of the next one
+__device__ __forceinline__ void finish_playout(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G,
+                                               const Cursor &C, bool fresh, float v)
+{
+    backup_game<false>(S, I.g, I.r, C.leaf, fresh, v, C.path_n, sh.h_z[I.gl], I.path_at, I.g);
+    G.n_done++;
+    if (S.trace && I.r == 0u)
+        atomicAdd((unsigned long long *)&S.totals[9], 1ull); // (diagnostic: playouts over time)
+    if (I.r == 0u)
+        S.done[I.g] = G.turn * S.n_sims + G.n_done;
+    G.state = G.n_done >= S.n_sims ? I.search_end : ST_READY;
+}
+
+// ---- 1. replies (the games' lanes): the priors, a match's policy distribution, or the value the game waits for.  (The 8
+// lanes of a game load the same word in the same instruction, or agree through group8_all: one state per game)
+__device__ __forceinline__ void take_replies(const SearchParams &S, const iago_row::HwParams &R, const Slot &I,
+                                             const GameLds &sh, Game &G, Cursor &C)
+{
+    if (G.state == ST_WAIT_PRIOR || G.state == ST_WAIT_DRAW) {
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            ok = ok && (uint32_t)(ld(&S.rep_p[I.g * 64 + (int)I.r * 8 + i]) >> 32) == G.epoch;
+        if (group8_all(ok)) {
+            if (G.state == ST_WAIT_DRAW) {
+                // np.random.choice(64, p=prob*valid/np.sum(prob*valid)) (game.py:102-104) with the uniform of
+                // (seed ^ MATCH_KEY << 32, game id, turn, stream 0): ops.sample_moves' draw.  (The move waits in
+                // `leaf`, which no search of this game reads before the move is played)
+                const uint64_t lg = group8_legal(to_lane(G.g_own, I.L), to_lane(G.g_opp, I.L), I.L);
+                const double u = sample_uniform(R.key0, R.key1 ^ MATCH_KEY, R.id_base + (uint32_t)sh.h_game[I.gl],
+                                                (uint32_t)G.turn, 0u);
+                C.leaf = policy_draw(S.rep_p + I.g * 64, lg, u);
+                if (C.leaf == 64) { // (numpy raises: the engine does, from this flag; the game goes on meanwhile)
+                    if (I.r == 0u)
+                        __hip_atomic_store(&S.ctl[CTL_BAD_DRAW], 1u, RLX_AGENT);
+                    C.leaf = (int)__builtin_ctzll(lg);
+                }
+            }
+            G.state = G.state == ST_WAIT_PRIOR ? ST_PRIOR_READY : ST_DRAW;
         }
-        if (tid < 4)
-            wv_time[tid] = 0;
+    } else if (G.state == ST_WAIT_VALUE) {
+        const u64 x = ld(&S.rep_v[I.g]);
+        if ((uint32_t)(x >> 32) == G.epoch) {
+            C.v_reply = __uint_as_float((uint32_t)x);
+            G.state = ST_HAVE_VALUE;
+        }
     }
-    uint32_t epoch = 0u; // reply tag of the game's last request (never 0 once used)
-    int n_done = 0;
-    if (exists && r == 0u) {
-        S.done[g] = 0;
-        S.roll[g] = 0;
+}
+
+// MCTS.get_move's most visited child of the root (MCTS.py:147) -- the root's children are the mover's legal moves in
+// ascending order (Node.expand) --: -2 if it has none.  row_n: the visit counts of this lane's 8 actions
+__device__ __forceinline__ int most_visited(const Tree &T, const Slot &I, uint64_t lg, int rfc, bool at_move, int (&row_n)[8])
+{
+    int best_n = -1, best_a = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int a = (int)(8u * I.r) + i;
+        int n = 0;
+        if (at_move && rfc >= 0 && ((lg >> a) & 1ull)) {
+            n = T.nodes[I.base + rfc + __popcll(lg & ((1ull << a) - 1ull))].n_visits;
+            if (n > best_n) { // the first maximum wins (MCTS.py:147)
+                best_n = n;
+                best_a = a;
+            }
+        }
+        row_n[i] = n;
     }
-    // whole games: the game's own position (own = side to move), its books (game.py:32,117-142) and its turn
-    uint64_t g_own = 0, g_opp = 0;
-    int turn = 0, stones = 4;
-    bool pass_flg = false, g_over = false;
-    const int search_end = whole ? ST_MOVE : ST_DONE; // where a game goes when its search's last playout is backed up
-    if (mine)
-        h_game[gl] = (int32_t)gt; // (the 8 lanes write the same word; each reads back its own store; a wave: the tree's id)
-    if (whole && exists && g < S.games_total) {
-        g_own = S.game_own[g];
-        g_opp = S.game_opp[g];
-        if (state == ST_DONE && r == 0u)
-            S.n_turns[g] = 0;
+    // argmax over the 8 lanes: more visits, then the lower action
+    most_visited_step<DPP_XOR1>(best_n, best_a);
+    most_visited_step<DPP_XOR2>(best_n, best_a);
+    most_visited_step<DPP_HALF_MIRROR>(best_n, best_a);
+    return best_n >= 0 ? best_a : -2;
+}
+
+// the turn's record: the position before it, valid (1: searched, 2: played without a search, 0: no turn), the move
+__device__ __forceinline__ void record_turn(const SearchParams &S, const Slot &I, const GameLds &sh, const Game &G, int valid,
+                                            int mv, const int (&row_n)[8])
+{
+    const int64_t row = (int64_t)G.turn * S.games_total + sh.h_game[I.gl];
+    if (I.r == 0u) {
+        S.rec_own[row] = G.g_own;
+        S.rec_opp[row] = G.g_opp;
+        S.rec_valid[row] = (uint8_t)valid;
+        S.rec_move[row] = (int8_t)(valid ? mv : -1);
     }
-    // cursor of the descent (kept across iterations while the game waits for priors)
-    int node = 0, fc = -1, k = 0, nv = 0, path_n = 0, leaf = 0;
-    int nvv = 0; // (a wave search: the cursor node's in-flight visits)
-    uint32_t vbits = 0;
-    uint64_t own = 0, opp = 0;
-    bool may_expand = false, leaf_fresh = false;
-    float v_reply = 0.0f;
-    int st_levels = 0, st_children = 0;
-    // (diagnostic counters of the workgroup, kept by thread 0 in LDS: as per-thread 64-bit registers they were 12 VGPRs
-    // live across the whole loop -- what the game launch of the role split spilled to scratch memory)
-    __shared__ uint32_t wg_count[6]; // [0] iterations, [1] idle iterations, [2..5] iterations with 0 / 1..16 / 17..20 / more games rolled out
-    if (tid < 6)
-        wg_count[tid] = 0u;
-    __shared__ int32_t roll_list[GAMES_PER_WG]; // games whose leaf is rolled out in this iteration, packed
-    __shared__ uint32_t roll_wave[BLOCK / 64], roll_wave_old[BLOCK / 64];
-    bool deferred = false; // this game's rollout was put off to the next iteration's first pass
-    bool table_ready = false;                   // the rollout's factor table is in LDS (from the first pass on)
-    // pacing: what this game has added to CTL_PROGRESS / whether CTL_PLAYING counts it; the workgroup's changes of an
-    // iteration are collected in LDS and go out as one atomic each; pace[2]: the progress above which a game holds
-    __shared__ int32_t pace[4];
-    int contrib = 0;
-    bool in_play = state != ST_DONE;
-    if (tid < 4)
-        pace[tid] = tid == 2 ? 0x7fffffff : 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        S.rec_pi[row * 64 + (int)(8u * I.r) + i] = row_n[i];
+}
+
+// MCTS.update_with_move (MCTS.py:149-154): the child of move mv becomes the root, or (no such child) a fresh Node(None, 1.0)
+// (one lane)
+__device__ __forceinline__ void advance_root(const Tree &T, const Slot &I, uint64_t lg, int rfc, int mv)
+{
+    int child = -1;
+    if (rfc >= 0) {
+        if (mv >= 0 && ((lg >> mv) & 1ull))
+            child = rfc + __popcll(lg & ((1ull << mv) - 1ull));
+        else if (mv == -1 && (int)T.nodes[I.base + rfc].action == -1)
+            child = rfc;
+    }
+    if (child >= 0) {
+        T.root[I.g] = child;
+        T.nodes[I.base + child].parent = -1;
+    } else {
+        fresh_root(T, I.g, I.base);
+    }
+}
+
+// the move mv (< 0: none) on the board, the books, the swap of sides (iago_play_turn; game.py:117-142,253-255); then the
+// next turn or the game's end
+__device__ __forceinline__ void play_move(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G, bool played, int mv,
+                                          const long long t0)
+{
+    place_stone(G.g_own, G.g_opp, mv, I.L);
+    const bool was_over = G.g_over;
+    G.stones += played ? 1 : 0;
+    const bool passing = !played && !was_over;
+    if (passing && G.pass_flg)
+        G.stones = 64;                       // a pass after a pass ends the game
+    if (!was_over)
+        G.pass_flg = passing;
+    if (G.turn % 2 == 1)                     // `while stone_num < 64` once per pair of turns
+        G.g_over = was_over || G.stones >= 64;
+    G.turn++;
+    if (G.turn >= S.max_turns || (G.turn % 2 == 0 && G.g_over)) {
+        if (I.r == 0u) {
+            const int64_t id = sh.h_game[I.gl];
+            S.n_turns[id] = G.turn;
+            S.game_own[id] = G.g_own;        // (colour 1's stones after an even number of turns)
+            S.game_opp[id] = G.g_opp;
+        }
+        G.state = ST_DONE;
+        if (S.trace && I.r == 0u && I.g < S.trace_rows) { // (diagnostic: the game's end, its requests)
+            int64_t *row = S.trace + 4 * ((int64_t)S.trace_rows - 1 - I.g);
+            row[0] = wall_clock64() - t0;
+            row[1] = G.epoch;
+            row[2] = G.turn;
+        }
+    } else {
+        G.state = ST_TURN;
+    }
+}
+
+// ---- 3. whole games (the games' lanes): the turn's end (the move) and the next turn's start, until the game searches
+// again or is over (a pass leads straight on to the next turn: at most a few rounds)
+__device__ __forceinline__ void turn_boundary(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G, const Cursor &C,
+                                              bool &busy, const long long t0)
+{
+    const Tree &T = S.T;
+    for (int rep = 0; rep < 6; rep++) {
+        const bool at_move = G.state == ST_MOVE, at_turn = G.state == ST_TURN, at_draw = G.state == ST_DRAW;
+        if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
+            break;
+        busy = busy || at_move || at_turn || at_draw;
+        const uint64_t lg = group8_legal(to_lane(G.g_own, I.L), to_lane(G.g_opp, I.L), I.L);
+        const bool can_move = lg != 0ull && !G.g_over;
+        // a match (active 2: PV-MCTS plays colour 1, 3: colour 2; game.py:96-118): the final move when it is the only one
+        // is played as it is, by either side (no search, no update_with_move), and the SL policy's turn asks its net for
+        // the position and waits to draw
+        const int code = (at_turn && can_move && !S.stream) ? (int)S.active[I.g] : 0;
+        const bool match = code == 2 || code == 3;
+        const bool forced = match && G.stones > 62 && __popcll(lg) == 1;
+        const bool policy_turn = match && !forced && (G.turn & 1) == (code == 2 ? 1 : 0);
+        if (policy_turn) {
+            G.epoch++;
+            if (I.r == 0u)
+                send_request(S, KIND_POLICY, I.g, G.epoch, G.g_own, G.g_opp); // make_state_var(state, color)
+            G.state = ST_WAIT_DRAW;
+        }
+        if (at_turn && can_move && !forced && !policy_turn) {
+            // the mover searches: MCTS.get_move(state, color) (game.py:112)
+            G.n_done = 0;
+            if (I.r == 0u)
+                S.done[I.g] = G.turn * S.n_sims; // (the rollouts' Philox stream: stream base + turn x n_sims + playout)
+            G.state = ST_READY;
+        }
+        const bool drawn = at_draw || forced; // a stone placed without a search
+        const bool moving = at_move || drawn || (at_turn && !can_move);
+        const int root = moving ? T.root[I.g] : 0;
+        const int rfc = moving ? T.nodes[I.base + root].first_child : -1;
+        int row_n[8];
+        const int best = most_visited(T, I, lg, rfc, at_move, row_n);
+        if (moving) {
+            int mv = -1;
+            if (at_move) {
+                mv = best;
+                if (mv == -2 && I.r == 0u) // max() of an empty children dict (MCTS.py:147): n_sims < n_thr
+                    __hip_atomic_store(&S.ctl[CTL_NO_CHILDREN], 1u, RLX_AGENT);
+            }
+            if (at_draw)
+                mv = C.leaf; // the policy's draw
+            if (forced)
+                mv = (int)__builtin_ctzll(lg); // game.py:97-98
+            if (S.rec_move)
+                record_turn(S, I, sh, G, at_move ? 1 : (drawn ? 2 : 0), mv, row_n);
+            // for the games not over, and not after a forced final move (game.py:97-98)
+            if (!G.g_over && !forced && I.r == 0u)
+                advance_root(T, I, lg, rfc, mv);
+            play_move(S, I, sh, G, at_move || drawn, mv, t0);
+        }
+    }
+}
+
+// on the way out of a descent that stopped at a node to expand (the games' lanes): ask for its priors and wait.  The node
+// WILL expand when they are back, and its children are leaves without a value at their first visits -- the first of them
+// in this very playout.  While net workgroups have nothing to do they walk the children's positions beside the policy
+// walk, for the position table (nobody waits for these)
+__device__ __forceinline__ void ask_priors(const SearchParams &S, const Slot &I, GameLds &sh, Game &G, const Cursor &C)
+{
+    G.epoch++;
+    if (I.r == 0u)
+        send_request(S, KIND_POLICY, I.g, G.epoch, C.own, C.opp);
+    G.state = ST_WAIT_PRIOR;
+    if (sh.pace[3] > 0 && I.need_v) {
+        uint64_t rest = group8_legal(to_lane(C.own, I.L), to_lane(C.opp, I.L), I.L);
+        while (rest) {
+            const int a2 = (int)__builtin_ctzll(rest);
+            rest &= rest - 1ull;
+            uint64_t c_own = C.own, c_opp = C.opp;
+            place_stone(c_own, c_opp, a2, I.L); // the child: the other side moves
+            uint32_t known = 0u, by = 0u;
+            // (the ring holds QCAP entries: at most one per game that waits -- <= QCAP / 2 games when this is on -- and
+            // these, handed out as a budget per workgroup and iteration while the ring was empty, two iterations' worth of
+            // which fit beside the games' own: pace[3])
+            if (I.r == 0u && !vtable_get(S, c_own, c_opp, known, by) && atomicSub(&sh.pace[3], 1) > 0)
+                send_request(S, KIND_VALUE, (int64_t)NOBODY, (uint32_t)I.g, c_own, c_opp); // (reply tag: the sender)
+        }
+    }
+}
+
+// on the way out of a descent that reached the leaf of its playout (MCTS.py:123-127; the games' lanes): its rollout runs
+// now, its value is the stored one, the position table's, or is asked for
+template <bool WAVE>
+__device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I, GameShared<WAVE> &sh, Game &G, Cursor &C,
+                                           bool descending)
+{
+    if (descending && C.fc >= 0 && I.r == 0u)
+        S.T.overflow[I.gt] = 1; // path longer than MAX_DEPTH: reported like a full pool
+    C.leaf = C.node;
+    const float c = __uint_as_float(C.vbits);
+    C.leaf_fresh = I.need_v && c != c;
+    bool ask = C.leaf_fresh;
+    if (S.vtable_mask) {
+        // has any game of any launch asked for this position before?
+        uint32_t hit = 0u, bits = 0u, by = 0u;
+        if (C.leaf_fresh && I.r == 0u && vtable_get(S, C.own, C.opp, bits, by)) {
+            hit = 1u;
+            atomicAdd((unsigned long long *)&S.totals[8], 1ull);
+            if (by == (uint32_t)I.g) // (asked for -- or walked ahead -- by this very game)
+                atomicAdd((unsigned long long *)&S.totals[12], 1ull);
+        }
+        hit = group8_add(hit);
+        bits = group8_add(I.r == 0u ? bits : 0u);
+        if (hit) {
+            C.vbits = bits; // (leaf_fresh stays: the backup stores the value in the node)
+            ask = false;
+        }
+    }
+    if (ask)
+        G.epoch++;
+    if (I.r == 0u) {
+        S.cur_node[I.g] = C.node;
+        S.cur_own[I.g] = C.own;
+        S.cur_opp[I.g] = C.opp;
+        sh.h_own[I.gl] = C.own; // (what the rollout pass reads)
+        sh.h_opp[I.gl] = C.opp;
+        sh.h_stream[I.gl] = G.turn * S.n_sims + G.n_done + I.s_in; // (a wave: playout p = the wave's first + the slot)
+        if (ask)
+            send_request(S, KIND_VALUE, I.g, G.epoch, C.own, C.opp);
+    }
+    G.state = ask ? ST_ROLL_FRESH : ST_ROLL;
+    if constexpr (WAVE) {
+        // the playout is in flight: vv + 1 along its path, and the tree's next slot may descend
+        __threadfence_block(); // (lane 0's path entries, read by the group's other lanes)
+        const int len = C.path_n < S.path_stride ? C.path_n : S.path_stride;
+        for (int d = (int)I.r; d < len; d += 8)
+            S.T.nodes[I.base + path_entry(I.path_at, I.gpath, d)].reserved1 += 1;
+        if (I.r == 0u)
+            sh.wv_next[I.tl] = I.s_in + 1;
+    }
+}
+
+// Node.expand (MCTS.py:109-120) of the cursor node once it has n_thr visits: a pass child or a single legal move without
+// a net (MCTS.py:112-117), else with the priors -- which, when they have not arrived, the descent stops to ask for
+__device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cursor &C, bool &descending, bool have_priors,
+                                       bool &need_prior)
+{
+    const Tree &T = S.T;
+    const bool grow = descending && C.may_expand && C.fc < 0 && C.nv >= S.n_thr;
+    if (__builtin_amdgcn_ballot_w64(grow) == 0ull)
+        return;
+    const uint64_t lg = group8_legal(to_lane(C.own, I.L), to_lane(C.opp, I.L), I.L);
+    if (grow) {
+        const int kn = lg ? __popcll(lg) : 1;
+        if (lg != 0ull && kn > 1 && !have_priors) {
+            need_prior = true; // Node.expand needs policy_func(state) (MCTS.py:118-120)
+            descending = false;
+        } else {
+            C.may_expand = false;
+            uint32_t fc1 = 0; // first child + 1, 0 = no room
+            if (I.r == 0u) {
+                const int at = T.n_nodes[I.gt];
+                if (at + kn <= T.capacity) {
+                    T.n_nodes[I.gt] = at + kn;
+                    fc1 = (uint32_t)at + 1u;
+                } else {
+                    T.overflow[I.gt] = 1;
+                }
+            }
+            fc1 = group8_add(fc1);
+            if (fc1 != 0u) {
+                const int nf = (int)fc1 - 1;
+                if (lg == 0ull || kn == 1) {
+                    if (I.r == 0u) // pass child / single legal move: Node(node, 1)
+                        init_node(T, I.base + nf, C.node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
+                } else {
+                    uint32_t row = (uint32_t)(lg >> (8u * I.r)) & 0xFFu;
+                    int at = nf + __popcll(lg & ((1ull << (8u * I.r)) - 1ull));
+                    while (row) {
+                        const int a = (int)(8u * I.r) + __builtin_ctz(row);
+                        row &= row - 1u;
+                        const float p = __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a]));
+                        init_node(T, I.base + at, C.node, a, p + 0.1f); // MCTS.py:19
+                        at++;
+                    }
+                }
+                if (I.r == 0u) {
+                    T.nodes[I.base + C.node].first_child = nf;
+                    T.nodes[I.base + C.node].n_children = (uint8_t)kn;
+                }
+                C.fc = nf;
+                C.k = kn;
+            }
+        }
+    }
+    __threadfence_block(); // the new children are read by the other lanes of the group below
+}
+
+// Node.select (MCTS.py:39-49): two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
+template <bool WAVE>
+__device__ __forceinline__ void select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
+{
+    const int kk = descending ? C.k : 0;
+    const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv)); // np.sqrt(parent.n_visits), MCTS.py:49
+    double best_v = -INFINITY;
+    int best_i = 0x7fffffff;
+    uint32_t pl[4] = {0u, 0u, 0u, 0u};
+    for (int j0 = (int)I.r; j0 < kk; j0 += 16) {
+        const int j1 = j0 + 8;
+        const bool two = j1 < kk;
+        const int64_t c0 = I.base + C.fc + j0, c1 = two ? I.base + C.fc + j1 : c0;
+        uint4 s0, l0, s1, l1;
+        node_record(S.T, c0, s0, l0);
+        node_record(S.T, c1, s1, l1);
+        score_child<WAVE>(S, s0, l0, j0, sq, best_v, best_i, pl);
+        if (two)
+            score_child<WAVE>(S, s1, l1, j1, sq, best_v, best_i, pl);
+    }
+    argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
+    argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
+    argmax_step_payload<DPP_HALF_MIRROR>(best_v, best_i, pl);
+    uint64_t own = C.own, opp = C.opp;
+    place_stone(own, opp, descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1, I.L);
+    if (descending) {
+        C.own = own;
+        C.opp = opp;
+        cursor_to<WAVE>(C, C.fc + best_i, pl[0], pl[1], pl[2], pl[2] >> 16, pl[3]);
+    }
+}
+
+// ---- 4. descent (MCTS.py:105-133; the games' lanes): from the root, or on from the leaf whose priors arrived, to a node
+// that waits for its priors or to the playout's leaf.  A wave search: one step of its trees' slot order (the slot whose
+// turn it is), seeing the in-flight visits and the expansions of the slots before it.  Returns whether the game descended
+template <bool WAVE>
+__device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, GameShared<WAVE> &sh, Game &G, Cursor &C,
+                                        int pace_limit, int &st_levels, int &st_children)
+{
+    bool my_turn = true;
+    if constexpr (WAVE)
+        my_turn = I.s_in == sh.wv_next[I.tl];
+    const bool fresh_start = G.state == ST_READY && (WAVE ? my_turn : G.turn * S.n_sims + G.n_done <= pace_limit);
+    bool descending = fresh_start || (G.state == ST_PRIOR_READY && my_turn);
+    bool have_priors = G.state == ST_PRIOR_READY;
+    bool skip_record = G.state == ST_PRIOR_READY; // the cursor node is on the path already
+    bool need_prior = false;
+    if (fresh_start) {
+        const int root = S.T.root[I.gt];
+        C.own = I.whole ? G.g_own : S.root_own[I.gt];
+        C.opp = I.whole ? G.g_opp : S.root_opp[I.gt];
+        uint4 s0, l0;
+        node_record(S.T, I.base + root, s0, l0);
+        cursor_to<WAVE>(C, root, l0.x, s0.x, l0.z, l0.w, s0.w);
+        C.path_n = 0;
+        C.may_expand = true;
+    }
+    const bool went = descending;
+    for (int depth = 0; depth < MAX_DEPTH; depth++) {
+        if (descending && !skip_record) {
+            if (I.r == 0u) {
+                if (C.path_n < S.path_stride) {
+                    if (I.path_at >= 0)
+                        ((int32_t *)iago_trunk::trunk_lds)[I.path_at + C.path_n] = C.node;
+                    else
+                        I.gpath[C.path_n] = C.node;
+                }
+                else
+                    S.T.overflow[I.gt] = 1; // deeper than the path buffer: reported like a full pool
+            }
+            C.path_n++;
+        }
+        skip_record = false;
+        expand(S, I, C, descending, have_priors, need_prior);
+        have_priors = false;
+        descending = descending && C.fc >= 0; // leaf reached (MCTS.py:107)
+        if (__builtin_amdgcn_ballot_w64(descending) == 0ull)
+            break;
+        st_levels += descending ? 1 : 0;
+        st_children += descending ? C.k : 0;
+        // Chains of pass nodes.  At the end of a game neither side has a move, and the reference goes on expanding: a pass
+        // child under the pass child, one level deeper every n_thr visits (MCTS.py:109-117) -- the last turns of a game
+        // descend through 65 such levels per playout on average (400 playouts per move; LABNOTES.md).  A node with ONE
+        // child leaves nothing to choose (max over one element, MCTS.py:46): when that is so for every game of the wave
+        // that still descends and all those children are passes, the level is the child's record and the swap of sides
+        if (__builtin_amdgcn_ballot_w64(descending && C.k != 1) == 0ull) {
+            uint4 s0, l0;
+            node_record(S.T, descending ? I.base + C.fc : I.base, s0, l0);
+            const bool pass_child = (int)(int8_t)(l0.z & 0xFFu) < 0;
+            if (__builtin_amdgcn_ballot_w64(descending && !pass_child) == 0ull) {
+                if (descending) {
+                    const uint64_t t = C.own; // GameFunctions.place_stone(state, -1, c) places nothing; c = 3 - c
+                    C.own = C.opp;
+                    C.opp = t;
+                    cursor_to<WAVE>(C, C.fc, l0.x, s0.x, l0.z, l0.w, s0.w);
+                }
+                continue;
+            }
+        }
+        select_child<WAVE>(S, I, C, descending);
+    }
+    if (went) {
+        if (need_prior)
+            ask_priors(S, I, sh, G, C);
+        else
+            reach_leaf<WAVE>(S, I, sh, G, C, descending);
+    }
+    if (I.exists && I.r == 0u)
+        S.roll[I.g] = (I.need_z && (G.state == ST_ROLL || G.state == ST_ROLL_FRESH)) ? 1 : 0;
+    return went;
+}
+
+// ---- 5. the control words this iteration's end looks at (abort, the rings' depths for the pacing and the values-ahead
+// gate, the games in play and their progress): eight loads in flight together HERE, under the rollouts -- read one after
+// the other by thread 0 between the iteration's last two barriers they were up to six dependent round trips to L2
+// (2 - 4 us of a 34 us iteration, with the whole workgroup waiting).  All of it is timing-only state, one iteration old at
+// most when it is used.
+struct CtlWords {
+    uint32_t abort, idle, t0, h0, t1, h1, play, prog, next;
+};
+__device__ __forceinline__ CtlWords read_ctl(const SearchParams &S, int tid)
+{
+    CtlWords c = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (tid == 0) {
+        if (S.stream)
+            c.next = __hip_atomic_load(&S.ctl[CTL_NEXT_GAME], RLX_AGENT);
+        c.abort = __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT);
+        c.idle = __hip_atomic_load(&S.ctl[CTL_IDLE], RLX_AGENT);
+        c.t0 = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT);
+        c.h0 = __hip_atomic_load(&S.ctl[ctl_head(0)], RLX_AGENT);
+        c.t1 = __hip_atomic_load(&S.ctl[ctl_tail(1)], RLX_AGENT);
+        c.h1 = __hip_atomic_load(&S.ctl[ctl_head(1)], RLX_AGENT);
+        c.play = __hip_atomic_load(&S.ctl[CTL_PLAYING], RLX_AGENT);
+        c.prog = __hip_atomic_load(&S.ctl[CTL_PROGRESS], RLX_AGENT);
+    }
+    return c;
+}
+
+// ---- 6. rollouts of the leaves reached in this iteration (Simulate, mcts_self_play.py:9-134): the games that have one are
+// packed into rows of 16 boards (about half of a workgroup's games reach a leaf in an iteration, the others wait for a net:
+// one pass of the 16-lanes-per-board body instead of two, most of the time).  A board's game does not depend on its row:
+// Philox counters are keyed by the game and its playout count.
+// Passes of 16 boards.  A pass costs the same whether it plays 16 boards or one, and all games of the workgroup wait for
+// it: when a full pass leaves only a few games over (at most S.roll_defer), they are played in the NEXT iteration's first
+// pass, ahead of that iteration's own (17 .. 20 games rolled out in 16 % of the iterations, more than 20 in 32 %:
+// LABNOTES.md, round 5).  Timing only: a game's rollout is keyed by its own playout count, whenever it runs.
+// Returns whether this game's rollout ran in this iteration (or it needs none)
+__device__ __forceinline__ bool rollout_passes(const SearchParams &S, const iago_row::HwParams &R, const Slot &I, GameLds &sh,
+                                               bool rolls, bool &deferred, bool &table_ready)
+{
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(rolls && I.r == 0u); // bit 8 j: game j of this wave
+    const uint64_t balo = __builtin_amdgcn_ballot_w64(rolls && deferred && I.r == 0u);
+    if ((I.tid & 63) == 0) {
+        sh.roll_wave[I.tid >> 6] = (uint32_t)(((bal & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
+        sh.roll_wave_old[I.tid >> 6] = (uint32_t)(((balo & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
+    }
+    if (I.tid < GAMES_PER_WG)
+        sh.roll_list[I.tid] = -1;
     __syncthreads();
-    if (mine && in_play && r == 0u)
-        atomicAdd(&pace[1], 1);
+    uint32_t gm = 0u, go = 0u; // bit j: game j of the workgroup has a rollout / one put off in the last iteration
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; w++) {
+        gm |= sh.roll_wave[w] << (8 * w);
+        go |= sh.roll_wave_old[w] << (8 * w);
+    }
+    const int n_roll = __popc(gm), rem = n_roll & 15;
+    const int n_now = (n_roll < 16 || rem > S.roll_defer) ? n_roll : n_roll - rem;
+    const uint32_t below = (1u << I.gl) - 1u;
+    // the games put off last time first, then this iteration's own, each in game order
+    const int rank = deferred ? __popc(go & below) : __popc(go) + __popc(gm & ~go & below);
+    const bool now = rolls && rank < n_now;
+    if (now && I.r == 0u)
+        sh.roll_list[rank] = (int32_t)I.g;
+    deferred = rolls && !now;
+    __syncthreads();
+    if (I.tid == 0)
+        sh.wg_count[2 + (n_roll == 0 ? 0 : n_roll <= 16 ? 1 : n_roll <= 20 ? 2 : 3)]++; // (diagnostic: totals[10], [13..15])
+    const iago_row::RowHandoff hand = {sh.h_own, sh.h_opp, sh.h_stream, sh.h_game, sh.h_z,
+                                       (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
+#pragma unroll 1
+    for (int at = 0; at < n_now; at += 16) {
+        iago_row::rollout_row_body<false, true, true>(R, 0u, sh.roll_list + at, table_ready, &hand);
+        table_ready = true;
+        __syncthreads();
+    }
+    return !rolls || now;
+}
+
+// ---- 7. a wave search: the backups of every tree whose wave has all its leaf values, in slot order (a step per slot, each
+// handing the tree to the next), then the tree's next wave -- or the end of its search
+__device__ __forceinline__ void wave_backups(const SearchParams &S, const Slot &I, GameShared<true> &sh, Game &G,
+                                             const Cursor &C, const long long c_roll, bool &busy)
+{
+    const long long c_back = wall_clock64();
+    if (I.tid == 0)
+        sh.wv_time[1] += c_back - c_roll;
+    if (I.mine && I.r == 0u && G.state != ST_HAVE_VALUE && G.state != ST_DONE && I.s_in < sh.wv_size[I.tl])
+        sh.wv_block[I.tl] = 1;
+    __syncthreads();
+    // (a tree in search whose wave blocks nothing: every slot of the wave holds its value, the others are idle)
+    const bool ready = I.mine && G.state != ST_DONE && sh.wv_block[I.tl] == 0;
+    if (wg_handoff_or(ready)) {
+        for (int j = 0; j < I.W; j++) {
+            if (ready && I.s_in == j && G.state == ST_HAVE_VALUE) {
+                backup_game<true>(S, I.g, I.r, C.leaf, C.leaf_fresh, C.v_reply, C.path_n, sh.h_z[I.gl], I.path_at, I.gt);
+                if (S.trace && I.r == 0u)
+                    atomicAdd((unsigned long long *)&S.totals[9], 1ull);
+            }
+            wg_handoff_or(false);
+        }
+        if (ready) {
+            G.n_done += sh.wv_size[I.tl];
+            const int m = S.n_sims - G.n_done < I.W ? S.n_sims - G.n_done : I.W;
+            G.state = G.n_done >= S.n_sims ? ST_DONE : (I.s_in < m ? ST_READY : ST_IDLE);
+            if (I.r == 0u)
+                S.done[I.g] = G.n_done;
+            busy = true;
+        }
+        __syncthreads(); // (every slot has read its tree's wave size)
+        if (ready && I.s_in == 0 && I.r == 0u) {
+            const int m = S.n_sims - G.n_done < I.W ? S.n_sims - G.n_done : I.W;
+            sh.wv_size[I.tl] = m;
+            sh.wv_next[I.tl] = 0;
+        }
+    }
+    // (read above, before the barrier: cleared for the next iteration's look)
+    if (I.mine && I.r == 0u && I.s_in == 0)
+        sh.wv_block[I.tl] = 0;
+    if (I.tid == 0)
+        sh.wv_time[2] += wall_clock64() - c_back;
+}
+
+// ---- 8. the iteration's end: the timeline sample (diagnostic), the pacing books, the clock limit; thread 0 then sets the
+// next iteration's pacing limit and values-ahead budget.  Returns whether the launch stops
+__device__ __forceinline__ bool iteration_end(const SearchParams &S, const Slot &I, GameLds &sh, const Game &G,
+                                              const CtlWords &c, const long long t0, int &contrib, bool &in_play)
+{
+    const Tree &T = S.T;
+    if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] < S.trace_rows - T.n_games) {
+        const int64_t iters = (int64_t)sh.wg_count[0];
+        S.trace[4 * iters + 0] = wall_clock64() - t0;
+        S.trace[4 * iters + 1] = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT) + __hip_atomic_load(&S.ctl[ctl_tail(1)], RLX_AGENT);
+        S.trace[4 * iters + 2] = __hip_atomic_load(&S.ctl[ctl_head(0)], RLX_AGENT) + __hip_atomic_load(&S.ctl[ctl_head(1)], RLX_AGENT);
+        S.trace[4 * iters + 3] = (int64_t)__hip_atomic_load(&S.ctl[CTL_FINISHED], RLX_AGENT) |
+                                 (__hip_atomic_load(&S.totals[9], RLX_AGENT) << 8);
+    }
+    if (I.tid == 0)
+        sh.wg_count[0]++;
+    const int prog = G.state == ST_DONE ? 0 : G.turn * S.n_sims + G.n_done;
+    if (I.mine && I.r == 0u) {
+        if (prog != contrib)
+            atomicAdd(&sh.pace[0], prog - contrib);
+        if (in_play && G.state == ST_DONE)
+            atomicAdd(&sh.pace[1], -1);
+    }
+    contrib = prog;
+    in_play = in_play && G.state != ST_DONE;
+    // (the workgroup's own stores to done / the tree are read by its next iteration: same CU)
+    const bool over = wall_clock64() - t0 > S.clock_limit;
+    if (over && I.tid == 0)
+        __hip_atomic_store(&S.ctl[CTL_ABORT], 1u, RLX_AGENT);
+    const int stop = __syncthreads_or(over || (I.tid == 0 && c.abort != 0u));
+    if (I.tid == 0) {
+        if (sh.pace[0])
+            __hip_atomic_fetch_add(&S.ctl[CTL_PROGRESS], (uint32_t)sh.pace[0], RLX_AGENT);
+        if (sh.pace[1])
+            __hip_atomic_fetch_add(&S.ctl[CTL_PLAYING], (uint32_t)sh.pace[1], RLX_AGENT);
+        sh.pace[0] = 0;
+        sh.pace[1] = 0;
+        int limit = 0x7fffffff;
+        sh.pace[3] = 0;
+        const int32_t wait0 = (int32_t)(c.t0 - c.h0), wait1 = (int32_t)(c.t1 - c.h1);
+        if (S.ahead_idle >= 0 && S.vtable_mask && I.n_slots <= (int64_t)(QCAP / 2u) && c.idle >= (uint32_t)S.ahead_idle &&
+            wait0 <= 0 && wait1 <= 0)
+            // this iteration's share of the ring for requests nobody waits for: the games' own requests (at most one
+            // each) and TWO iterations' worth of these (the workgroups look at the rings at different moments: a second
+            // burst can be on its way before the first shows in anybody's snapshot) fit the ring together
+            sh.pace[3] = (int32_t)((QCAP - (uint32_t)I.n_slots) / 2u) / S.n_game_wgs;
+        // (a stream: no hold while game ids are left to claim -- the mean then mixes old and new games; the rule
+        // holds again for the final drain, when every id is taken)
+        if (S.pace_margin >= 0 && (!S.stream || (int64_t)c.next + T.n_games >= (int64_t)S.games_total)) {
+            if (wait0 + wait1 > S.pace_backlog && c.play != 0u && c.play <= (uint32_t)T.n_games)
+                limit = (int)(c.prog / c.play) + S.pace_margin;
+        }
+        sh.pace[2] = limit;
+    }
+    return stop != 0;
+}
+
+// ---- 9. a stream whose workgroup has all its games over: its slots take the next block of game ids, one each, and start
+// those games together.  (Claimed slot by slot, games of every phase shared a workgroup: a rollout pass lasts as long as
+// its longest board and a wave's descent as its deepest game, so every iteration paid for the opening's rollouts AND the
+// end's pass chains -- 0.84x / 0.75x the batch loop's games/s at 100 / 400 playouts; LABNOTES.md.)  Which slot plays which
+// game changes nothing: a game draws with its own id.  Returns whether the workgroup's games are all over still
+__device__ __forceinline__ bool stream_claim(const SearchParams &S, const Slot &I, GameLds &sh, Game &G, bool &in_play)
+{
+    const Tree &T = S.T;
+    const int n_here = (int)min((int64_t)S.games_per_wg, I.n_slots - (int64_t)blockIdx.x * S.games_per_wg); // its slots
+    if (I.tid == 0)
+        sh.claimed = __hip_atomic_fetch_add(&S.ctl[CTL_NEXT_GAME], (uint32_t)n_here, RLX_AGENT);
+    __syncthreads();
+    const int64_t next = T.n_games + (int64_t)sh.claimed + I.gl;
+    if (I.exists && next < S.games_total) {
+        // a fresh tree, except the pool's overflow flag, which voids the launch whichever game set it.  The reply tag
+        // `epoch` goes on counting: a reply to the slot's last game is never taken for one to this game
+        start_game(G, S.game_own[next], S.game_opp[next]);
+        if (I.r == 0u) {
+            S.done[I.g] = 0;
+            fresh_root(T, I.g, I.base);
+            atomicAdd(&sh.pace[1], 1); // (in play again: CTL_PLAYING at the next iteration's end)
+        }
+        sh.h_game[I.gl] = (int32_t)next;
+        G.state = ST_TURN;
+        in_play = true;
+    }
+    return __syncthreads_and(!I.mine || G.state == ST_DONE) != 0;
+}
+
+// ---- 10. after the loop: the descent statistics, the wave timing, the post-mortem of a launch that gave up, the totals
+template <bool WAVE>
+__device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, GameShared<WAVE> &sh, const Game &G,
+                                         int st_levels, int st_children, const long long t0)
+{
+    if (I.exists && I.r == 0u && S.stats) {
+        if (WAVE) {
+            atomicAdd(&S.stats[2 * I.gt], st_levels);
+            atomicAdd(&S.stats[2 * I.gt + 1], st_children);
+        } else {
+            S.stats[2 * I.g] += st_levels;
+            S.stats[2 * I.g + 1] += st_children;
+        }
+    }
+    if constexpr (WAVE) {
+        if (I.tid < 4 && S.wave_timing)
+            atomicAdd((unsigned long long *)&S.wave_timing[I.tid], (unsigned long long)sh.wv_time[I.tid]);
+    }
+    // (a launch that gave up: what every unfinished game was waiting for, for the post-mortem -- the trees are void anyway:
+    // cur_node = the reply tag it waits for, leaf_value = its state; tools/debug_split_abort.py)
+    if (I.exists && I.r == 0u && G.state != ST_DONE && __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u) {
+        S.cur_node[I.g] = (int32_t)G.epoch;
+        S.leaf_value[I.g] = (float)G.state;
+    }
+    if (I.tid == 0) {
+        atomicAdd((unsigned long long *)&S.totals[2], (unsigned long long)sh.wg_count[0]);
+        atomicAdd((unsigned long long *)&S.totals[6], (unsigned long long)sh.wg_count[1]);
+        atomicAdd((unsigned long long *)&S.totals[10], (unsigned long long)sh.wg_count[2]);
+        atomicAdd((unsigned long long *)&S.totals[13], (unsigned long long)sh.wg_count[3]);
+        atomicAdd((unsigned long long *)&S.totals[14], (unsigned long long)sh.wg_count[4]);
+        atomicAdd((unsigned long long *)&S.totals[15], (unsigned long long)sh.wg_count[5]);
+        atomicAdd((unsigned long long *)&S.totals[7], (unsigned long long)(wall_clock64() - t0));
+        __hip_atomic_fetch_add(&S.ctl[CTL_FINISHED], 1u, RLX_AGENT);
+    }
+}
+
+template <bool WAVE>
+__device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0)
+{
+    __shared__ GameShared<WAVE> sh;
+    const Slot I = make_slot<WAVE>(S);
+    // (a stream: slot g starts game g while there is one -- `active` is not read)
+    const bool first = I.exists && I.gt < S.games_total && (S.stream || S.active[I.gt] != 0);
+    Game G;
+    G.state = (first && S.n_sims > 0) ? (I.whole ? ST_TURN : ST_READY) : ST_DONE;
+    G.epoch = 0u;
+    if constexpr (WAVE) {
+        const int m = S.n_sims < I.W ? S.n_sims : I.W;
+        if (G.state == ST_READY && I.s_in >= m)
+            G.state = ST_IDLE;
+        if (I.tid < GAMES_PER_WG) {
+            sh.wv_next[I.tid] = 0;
+            sh.wv_size[I.tid] = m;
+            sh.wv_block[I.tid] = 0;
+        }
+        if (I.tid < 4)
+            sh.wv_time[I.tid] = 0;
+    }
+    if (I.exists && I.r == 0u) {
+        S.done[I.g] = 0;
+        S.roll[I.g] = 0;
+    }
+    if (I.mine)
+        sh.h_game[I.gl] = (int32_t)I.gt; // (the 8 lanes write the same word; each reads back its own store; a wave: the tree's id)
+    const bool whole_game = I.whole && I.exists && I.g < S.games_total;
+    start_game(G, whole_game ? S.game_own[I.g] : 0ull, whole_game ? S.game_opp[I.g] : 0ull);
+    if (whole_game && G.state == ST_DONE && I.r == 0u)
+        S.n_turns[I.g] = 0;
+    Cursor C = {};
+    C.fc = -1;
+    int st_levels = 0, st_children = 0;
+    if (I.tid < 6)
+        sh.wg_count[I.tid] = 0u;
+    bool deferred = false;    // this game's rollout was put off to the next iteration's first pass
+    bool table_ready = false; // the rollout's factor table is in LDS (from the first pass on)
+    int contrib = 0;          // pacing: what this game has added to CTL_PROGRESS / whether CTL_PLAYING counts it
+    bool in_play = G.state != ST_DONE;
+    if (I.tid < 4)
+        sh.pace[I.tid] = I.tid == 2 ? 0x7fffffff : 0;
+    __syncthreads();
+    if (I.mine && in_play && I.r == 0u)
+        atomicAdd(&sh.pace[1], 1);
     int pace_limit = 0x7fffffff;
 
     for (;;) {
         const long long c_it = WAVE ? wall_clock64() : 0;
         bool busy = false; // this game did something in this iteration
-        if (mine) {
-            // ---- replies
-            if (state == ST_WAIT_PRIOR || state == ST_WAIT_DRAW) {
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    ok = ok && (uint32_t)(ld(&S.rep_p[g * 64 + (int)r * 8 + i]) >> 32) == epoch;
-                if (group8_all(ok)) {
-                    if (state == ST_WAIT_DRAW) {
-                        // np.random.choice(64, p=prob*valid/np.sum(prob*valid)) (game.py:102-104) with the uniform of
-                        // (seed ^ MATCH_KEY << 32, game id, turn, stream 0): ops.sample_moves' draw.  (The move waits in
-                        // `leaf`, which no search of this game reads before the move is played)
-                        const uint64_t lg = group8_legal(to_lane(g_own, L), to_lane(g_opp, L), L);
-                        const double u = sample_uniform(R.key0, R.key1 ^ MATCH_KEY, R.id_base + (uint32_t)h_game[gl],
-                                                        (uint32_t)turn, 0u);
-                        leaf = policy_draw(S.rep_p + g * 64, lg, u);
-                        if (leaf == 64) { // (numpy raises: the engine does, from this flag; the game goes on meanwhile)
-                            if (r == 0u)
-                                __hip_atomic_store(&S.ctl[CTL_BAD_DRAW], 1u, RLX_AGENT);
-                            leaf = (int)__builtin_ctzll(lg);
-                        }
-                    }
-                    state = state == ST_WAIT_PRIOR ? ST_PRIOR_READY : ST_DRAW;
-                }
-            } else if (state == ST_WAIT_VALUE) {
-                const u64 x = ld(&S.rep_v[g]);
-                if ((uint32_t)(x >> 32) == epoch) {
-                    v_reply = __uint_as_float((uint32_t)x);
-                    state = ST_HAVE_VALUE;
-                }
-            }
-            // (the 8 lanes of a game load the same word in the same instruction, or agree through group8_all:
-            // one state per game)
-            // ---- backup of the games whose value has arrived (their rollout ran when they descended; a wave search
+        if (I.mine) {
+            take_replies(S, R, I, sh, G, C);
+            // ---- 2. the backup of a game whose value has arrived (its rollout ran when it descended; a wave search
             // backs its slots up together, below)
-            if (!WAVE && state == ST_HAVE_VALUE) {
-                backup_game<false>(S, g, r, leaf, true, v_reply, path_n, h_z[gl], path_at, g);
-                n_done++;
-                if (S.trace && r == 0u)
-                    atomicAdd((unsigned long long *)&S.totals[9], 1ull); // (diagnostic: playouts over time)
-                if (r == 0u)
-                    S.done[g] = turn * S.n_sims + n_done;
-                state = n_done >= S.n_sims ? search_end : ST_READY;
+            if (!WAVE && G.state == ST_HAVE_VALUE) {
+                finish_playout(S, I, sh, G, C, true, C.v_reply);
                 busy = true;
             }
-            // ---- whole games: the turn's end (the move) and the next turn's start, until the game searches again
-            // or is over (a pass leads straight on to the next turn: at most a few rounds)
-            if (!WAVE && whole) {
-                for (int rep = 0; rep < 6; rep++) {
-                    const bool at_move = state == ST_MOVE, at_turn = state == ST_TURN, at_draw = state == ST_DRAW;
-                    if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
-                        break;
-                    busy = busy || at_move || at_turn || at_draw;
-                    const uint64_t lg = group8_legal(to_lane(g_own, L), to_lane(g_opp, L), L);
-                    const bool can_move = lg != 0ull && !g_over;
-                    // a match (active 2: PV-MCTS plays colour 1, 3: colour 2; game.py:96-118): the final move when it is
-                    // the only one is played as it is, by either side (no search, no update_with_move), and the SL
-                    // policy's turn asks its net for the position and waits to draw
-                    const int code = (at_turn && can_move && !S.stream) ? (int)S.active[g] : 0;
-                    const bool match = code == 2 || code == 3;
-                    const bool forced = match && stones > 62 && __popcll(lg) == 1;
-                    const bool policy_turn = match && !forced && (turn & 1) == (code == 2 ? 1 : 0);
-                    if (policy_turn) {
-                        epoch++;
-                        if (r == 0u)
-                            send_request(S, KIND_POLICY, g, epoch, g_own, g_opp); // make_state_var(state, color)
-                        state = ST_WAIT_DRAW;
-                    }
-                    if (at_turn && can_move && !forced && !policy_turn) {
-                        // the mover searches: MCTS.get_move(state, color) (game.py:112)
-                        n_done = 0;
-                        if (r == 0u)
-                            S.done[g] = turn * S.n_sims; // (the rollouts' Philox stream: stream base + turn x n_sims + playout)
-                        state = ST_READY;
-                    }
-                    const bool drawn = at_draw || forced; // a stone placed without a search
-                    const bool moving = at_move || drawn || (at_turn && !can_move);
-                    // the root's children are the mover's legal moves in ascending order (Node.expand)
-                    const int root = moving ? T.root[g] : 0;
-                    const int rfc = moving ? T.nodes[base + root].first_child : -1;
-                    int best_n = -1, best_a = 0x7fffffff;
-                    int row_n[8];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const int a = (int)(8u * r) + i;
-                        int n = 0;
-                        if (at_move && rfc >= 0 && ((lg >> a) & 1ull)) {
-                            n = T.nodes[base + rfc + __popcll(lg & ((1ull << a) - 1ull))].n_visits;
-                            if (n > best_n) { // the first maximum wins (MCTS.py:147)
-                                best_n = n;
-                                best_a = a;
-                            }
-                        }
-                        row_n[i] = n;
-                    }
-                    // argmax over the 8 lanes: more visits, then the lower action
-                    most_visited_step<DPP_XOR1>(best_n, best_a);
-                    most_visited_step<DPP_XOR2>(best_n, best_a);
-                    most_visited_step<DPP_HALF_MIRROR>(best_n, best_a);
-                    if (moving) {
-                        int mv = -1;
-                        if (at_move) {
-                            mv = best_n >= 0 ? best_a : -2;
-                            if (mv == -2 && r == 0u) // max() of an empty children dict (MCTS.py:147): n_sims < n_thr
-                                __hip_atomic_store(&S.ctl[CTL_NO_CHILDREN], 1u, RLX_AGENT);
-                        }
-                        if (at_draw)
-                            mv = leaf; // the policy's draw
-                        if (forced)
-                            mv = (int)__builtin_ctzll(lg); // game.py:97-98
-                        if (S.rec_move) {
-                            const int64_t row = (int64_t)turn * S.games_total + h_game[gl];
-                            if (r == 0u) {
-                                S.rec_own[row] = g_own;
-                                S.rec_opp[row] = g_opp;
-                                S.rec_valid[row] = at_move ? 1 : (drawn ? 2 : 0);
-                                S.rec_move[row] = (int8_t)(at_move || drawn ? mv : -1);
-                            }
-#pragma unroll
-                            for (int i = 0; i < 8; i++)
-                                S.rec_pi[row * 64 + (int)(8u * r) + i] = row_n[i];
-                        }
-                        // MCTS.update_with_move (MCTS.py:149-154) for the games not over: the child becomes the root,
-                        // or (no such child) a fresh Node(None, 1.0) -- not after a forced final move (game.py:97-98)
-                        if (!g_over && !forced && r == 0u) {
-                            int child = -1;
-                            if (rfc >= 0) {
-                                if (mv >= 0 && ((lg >> mv) & 1ull))
-                                    child = rfc + __popcll(lg & ((1ull << mv) - 1ull));
-                                else if (mv == -1 && (int)T.nodes[base + rfc].action == -1)
-                                    child = rfc;
-                            }
-                            if (child >= 0) {
-                                T.root[g] = child;
-                                T.nodes[base + child].parent = -1;
-                            } else {
-                                init_node(T, base, -1, -2, 1.0f + 0.1f);
-                                T.n_nodes[g] = 1;
-                                T.root[g] = 0;
-                            }
-                        }
-                        // the stone, the books, the swap of sides (iago_play_turn; game.py:117-142,253-255)
-                        const bool played = at_move || drawn;
-                        const bool placed = played && mv >= 0;
-                        const uint64_t f = group8_flips(to_lane(g_own, L), to_lane(g_opp, L), (uint32_t)mv & 63u, L);
-                        uint64_t o = g_own, p = g_opp;
-                        if (placed) {
-                            const uint64_t bit = 1ull << (mv & 63);
-                            o = g_own | f | bit;
-                            p = g_opp & ~f & ~bit;
-                        }
-                        const bool was_over = g_over;
-                        stones += played ? 1 : 0;
-                        const bool passing = !played && !was_over;
-                        if (passing && pass_flg)
-                            stones = 64;                       // a pass after a pass ends the game
-                        if (!was_over)
-                            pass_flg = passing;
-                        if (turn % 2 == 1)                     // `while stone_num < 64` once per pair of turns
-                            g_over = was_over || stones >= 64;
-                        g_own = p;
-                        g_opp = o;
-                        turn++;
-                        if (turn >= S.max_turns || (turn % 2 == 0 && g_over)) {
-                            if (r == 0u) {
-                                const int64_t G = h_game[gl];
-                                S.n_turns[G] = turn;
-                                S.game_own[G] = g_own;         // (colour 1's stones after an even number of turns)
-                                S.game_opp[G] = g_opp;
-                            }
-                            state = ST_DONE;
-                            if (S.trace && r == 0u && g < S.trace_rows) { // (diagnostic: the game's end, its requests)
-                                int64_t *row = S.trace + 4 * ((int64_t)S.trace_rows - 1 - g);
-                                row[0] = wall_clock64() - t0;
-                                row[1] = epoch;
-                                row[2] = turn;
-                            }
-                        } else {
-                            state = ST_TURN;
-                        }
-                    }
-                }
-            }
+            if (!WAVE && I.whole)
+                turn_boundary(S, I, sh, G, C, busy, t0);
         }
-        // ---- descent (MCTS.py:105-133): from the root, or on from the leaf whose priors arrived.  A wave search: the
-        // slots of a tree one after the other (a step per slot, every tree of the workgroup at once), each seeing the
-        // in-flight visits and the expansions of the slots before it
         const long long c_desc = WAVE ? wall_clock64() : 0;
-        for (int sub = 0; sub < (WAVE ? W : 1); sub++) {
-        const bool my_turn = !WAVE || s_in == wv_next[tl];
-        bool went_any = false;
-        if (mine) {
-            const bool fresh_start = state == ST_READY && (WAVE ? my_turn : turn * S.n_sims + n_done <= pace_limit);
-            bool descending = fresh_start || (state == ST_PRIOR_READY && my_turn);
-            bool have_priors = state == ST_PRIOR_READY;
-            bool skip_record = state == ST_PRIOR_READY; // the cursor node is on the path already
-            bool need_prior = false;
-            if (fresh_start) {
-                node = T.root[gt];
-                own = whole ? g_own : S.root_own[gt];
-                opp = whole ? g_opp : S.root_opp[gt];
-                const uint4 s0 = ((const uint4 *)&T.nodes[base + node])[0], l0 = ((const uint4 *)&T.nodes[base + node])[1];
-                fc = (int)l0.x;
-                k = (int)((l0.z >> 8) & 0xFFu);
-                nv = (int)s0.x;
-                if (WAVE)
-                    nvv = (int)l0.w;
-                vbits = s0.w;
-                path_n = 0;
-                may_expand = true;
+        for (int sub = 0; sub < (WAVE ? I.W : 1); sub++) {
+            bool went = false;
+            if (I.mine) {
+                went = descend<WAVE>(S, I, sh, G, C, pace_limit, st_levels, st_children);
+                busy = busy || went;
             }
-            const bool went = descending;
-            went_any = went;
-            busy = busy || went;
-            for (int depth = 0; depth < MAX_DEPTH; depth++) {
-                if (descending && !skip_record) {
-                    if (r == 0u) {
-                        if (path_n < S.path_stride) {
-                            if (path_at >= 0)
-                                ((int32_t *)iago_trunk::trunk_lds)[path_at + path_n] = node;
-                            else
-                                gpath[path_n] = node;
-                        }
-                        else
-                            T.overflow[gt] = 1; // deeper than the path buffer: reported like a full pool
-                    }
-                    path_n++;
-                }
-                skip_record = false;
-                const bool expand = descending && may_expand && fc < 0 && nv >= S.n_thr;
-                if (__builtin_amdgcn_ballot_w64(expand) != 0ull) {
-                    const uint64_t lg = group8_legal(to_lane(own, L), to_lane(opp, L), L);
-                    if (expand) {
-                        const int kn = lg ? __popcll(lg) : 1;
-                        if (lg != 0ull && kn > 1 && !have_priors) {
-                            // Node.expand needs policy_func(state) (MCTS.py:118-120): ask for it and wait here
-                            need_prior = true;
-                            descending = false;
-                        } else {
-                            may_expand = false;
-                            uint32_t fc1 = 0; // first child + 1, 0 = no room
-                            if (r == 0u) {
-                                const int at = T.n_nodes[gt];
-                                if (at + kn <= T.capacity) {
-                                    T.n_nodes[gt] = at + kn;
-                                    fc1 = (uint32_t)at + 1u;
-                                } else {
-                                    T.overflow[gt] = 1;
-                                }
-                            }
-                            fc1 = group8_add(fc1);
-                            if (fc1 != 0u) {
-                                const int nf = (int)fc1 - 1;
-                                if (lg == 0ull || kn == 1) {
-                                    // pass child / single legal move: Node(node, 1), no net (MCTS.py:112-117)
-                                    if (r == 0u)
-                                        init_node(T, base + nf, node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
-                                } else {
-                                    uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
-                                    int at = nf + __popcll(lg & ((1ull << (8u * r)) - 1ull));
-                                    while (row) {
-                                        const int a = (int)(8u * r) + __builtin_ctz(row);
-                                        row &= row - 1u;
-                                        const float p = __uint_as_float((uint32_t)ld(&S.rep_p[g * 64 + a]));
-                                        init_node(T, base + at, node, a, p + 0.1f); // MCTS.py:19
-                                        at++;
-                                    }
-                                }
-                                if (r == 0u) {
-                                    T.nodes[base + node].first_child = nf;
-                                    T.nodes[base + node].n_children = (uint8_t)kn;
-                                }
-                                fc = nf;
-                                k = kn;
-                            }
-                        }
-                    }
-                    __threadfence_block(); // the new children are read by the other lanes of the group below
-                }
-                have_priors = false;
-                descending = descending && fc >= 0; // leaf reached (MCTS.py:107)
-                if (__builtin_amdgcn_ballot_w64(descending) == 0ull)
+            if constexpr (WAVE) {
+                if (!wg_handoff_or(went))
                     break;
-                const int kk = descending ? k : 0;
-                st_levels += descending ? 1 : 0;
-                st_children += kk;
-                // Chains of pass nodes.  At the end of a game neither side has a move, and the reference goes on
-                // expanding: a pass child under the pass child, one level deeper every n_thr visits (MCTS.py:109-117) --
-                // the last turns of a game descend through 65 such levels per playout on average (400 playouts per
-                // move; LABNOTES.md).  A node with ONE child leaves nothing to choose (max over one element, MCTS.py:46):
-                // when that is so for every game of the wave that still descends and all those children are passes,
-                // the level is the child's record and the swap of sides
-                if (__builtin_amdgcn_ballot_w64(descending && k != 1) == 0ull) {
-                    const int64_t c = descending ? base + fc : base;
-                    const uint4 s0 = ((const uint4 *)&T.nodes[c])[0], l0 = ((const uint4 *)&T.nodes[c])[1];
-                    const bool pass_child = (int)(int8_t)(l0.z & 0xFFu) < 0;
-                    if (__builtin_amdgcn_ballot_w64(descending && !pass_child) == 0ull) {
-                        if (descending) {
-                            const uint64_t t = own; // GameFunctions.place_stone(state, -1, c) places nothing; c = 3 - c
-                            own = opp;
-                            opp = t;
-                            node = fc;
-                            fc = (int)l0.x;
-                            nv = (int)s0.x;
-                            k = (int)((l0.z >> 8) & 0xFFu);
-                            if (WAVE)
-                                nvv = (int)l0.w;
-                            vbits = s0.w;
-                        }
-                        continue;
-                    }
-                }
-                const double sq = sqrt((double)(WAVE ? nv + nvv : nv)); // np.sqrt(parent.n_visits), MCTS.py:49
-                double best_v = -INFINITY;
-                int best_i = 0x7fffffff;
-                uint32_t pl[4] = {0u, 0u, 0u, 0u}; // of the best child: first_child, n_visits, action | n_children << 8 (| vv << 16), v
-                for (int j0 = (int)r; j0 < kk; j0 += 16) {
-                    const int j1 = j0 + 8;
-                    const bool two = j1 < kk;
-                    const int64_t c0 = base + fc + j0, c1 = two ? base + fc + j1 : c0;
-                    const uint4 s0 = ((const uint4 *)&T.nodes[c0])[0], l0 = ((const uint4 *)&T.nodes[c0])[1];
-                    const uint4 s1 = ((const uint4 *)&T.nodes[c1])[0], l1 = ((const uint4 *)&T.nodes[c1])[1];
-                    const float p0 = __uint_as_float(s0.z), q0 = __uint_as_float(s0.y);
-                    const float p1 = __uint_as_float(s1.z), q1 = __uint_as_float(s1.y);
-                    const int n0 = (int)s0.x, n1 = (int)s1.x;
-                    if constexpr (WAVE) {
-                        // (vv < 2^16: at most 32 playouts in flight)
-                        const double v = wave_score(S.c_puct, p0, q0, n0, (int)l0.w, sq, (double)S.vloss);
-                        if (v > best_v) {
-                            best_v = v;
-                            best_i = j0;
-                            pl[0] = l0.x, pl[1] = (uint32_t)n0, pl[2] = (l0.z & 0xFFFFu) | (l0.w << 16), pl[3] = s0.w;
-                        }
-                        if (two) {
-                            const double v1 = wave_score(S.c_puct, p1, q1, n1, (int)l1.w, sq, (double)S.vloss);
-                            if (v1 > best_v) {
-                                best_v = v1;
-                                best_i = j1;
-                                pl[0] = l1.x, pl[1] = (uint32_t)n1, pl[2] = (l1.z & 0xFFFFu) | (l1.w << 16), pl[3] = s1.w;
-                            }
-                        }
-                    } else {
-                    {
-                        const float cp = S.c_puct * p0;                          // float32, MCTS.py:49
-                        const double u = (double)cp * sq / (0.01 + (double)n0);
-                        const double v = (double)q0 + u;                         // get_value, MCTS.py:75-76
-                        if (v > best_v) { // strict: the first maximum wins (python max, MCTS.py:46)
-                            best_v = v;
-                            best_i = j0;
-                            pl[0] = l0.x, pl[1] = (uint32_t)n0, pl[2] = l0.z & 0xFFFFu, pl[3] = s0.w;
-                        }
-                    }
-                    if (two) {
-                        const float cp = S.c_puct * p1;
-                        const double u = (double)cp * sq / (0.01 + (double)n1);
-                        const double v = (double)q1 + u;
-                        if (v > best_v) {
-                            best_v = v;
-                            best_i = j1;
-                            pl[0] = l1.x, pl[1] = (uint32_t)n1, pl[2] = l1.z & 0xFFFFu, pl[3] = s1.w;
-                        }
-                    }
-                    }
-                }
-                argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
-                argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
-                argmax_step_payload<DPP_HALF_MIRROR>(best_v, best_i, pl);
-                const int child = fc + best_i;
-                const int a = descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1;
-                // GameFunctions.place_stone(state, action, c); c = 3 - c  (MCTS.py:131-132)
-                const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
-                if (descending) {
-                    uint64_t no = own, np_ = opp;
-                    if (a >= 0) {
-                        const uint64_t bit = 1ull << (a & 63);
-                        no = own | f | bit;
-                        np_ = opp & ~f & ~bit;
-                    }
-                    own = np_;
-                    opp = no;
-                    node = child;
-                    fc = (int)pl[0];
-                    nv = (int)pl[1];
-                    k = (int)((pl[2] >> 8) & 0xFFu);
-                    if (WAVE)
-                        nvv = (int)(pl[2] >> 16);
-                    vbits = pl[3];
-                }
             }
-            if (went) {
-                if (need_prior) {
-                    epoch++;
-                    if (r == 0u)
-                        send_request(S, KIND_POLICY, g, epoch, own, opp);
-                    state = ST_WAIT_PRIOR;
-                    // The node WILL expand when its priors are back, and its children are leaves without a value at their
-                    // first visits -- the first of them in this very playout.  While net workgroups have nothing to do they
-                    // walk the children's positions beside the policy walk, for the position table (nobody waits for these)
-                    if (pace[3] > 0 && need_v) {
-                        uint64_t rest = group8_legal(to_lane(own, L), to_lane(opp, L), L);
-                        while (rest) {
-                            const uint32_t a2 = (uint32_t)__builtin_ctzll(rest);
-                            rest &= rest - 1ull;
-                            const uint64_t f2 = group8_flips(to_lane(own, L), to_lane(opp, L), a2, L);
-                            const uint64_t bit2 = 1ull << a2;
-                            const uint64_t c_own = opp & ~f2 & ~bit2, c_opp = own | f2 | bit2; // the child: the other side moves
-                            uint32_t known = 0u, by = 0u;
-                            // (the ring holds QCAP entries: at most one per game that waits -- <= QCAP / 2 games when this
-                            // is on -- and these, handed out as a budget per workgroup and iteration while the ring was
-                            // empty, two iterations' worth of which fit beside the games' own: pace[3])
-                            if (r == 0u && !vtable_get(S, c_own, c_opp, known, by) && atomicSub(&pace[3], 1) > 0)
-                                send_request(S, KIND_VALUE, (int64_t)NOBODY, (uint32_t)g, c_own, c_opp); // (reply tag: the sender)
-                        }
-                    }
-                } else {
-                    if (descending && fc >= 0 && r == 0u)
-                        T.overflow[gt] = 1; // path longer than MAX_DEPTH: reported like a full pool
-                    // the leaf of this playout (MCTS.py:123-127): its rollout runs now, its value is the
-                    // stored one or is asked for
-                    leaf = node;
-                    const float c = __uint_as_float(vbits);
-                    leaf_fresh = need_v && c != c;
-                    bool ask = leaf_fresh;
-                    if (S.vtable_mask) {
-                        // has any game of any launch asked for this position before?
-                        uint32_t hit = 0u, bits = 0u, by = 0u;
-                        if (leaf_fresh && r == 0u && vtable_get(S, own, opp, bits, by)) {
-                            hit = 1u;
-                            atomicAdd((unsigned long long *)&S.totals[8], 1ull);
-                            if (by == (uint32_t)g) // (asked for -- or walked ahead -- by this very game)
-                                atomicAdd((unsigned long long *)&S.totals[12], 1ull);
-                        }
-                        hit = group8_add(hit);
-                        bits = group8_add(r == 0u ? bits : 0u);
-                        if (hit) {
-                            vbits = bits; // (leaf_fresh stays: the backup stores the value in the node)
-                            ask = false;
-                        }
-                    }
-                    if (ask)
-                        epoch++;
-                    if (r == 0u) {
-                        S.cur_node[g] = node;
-                        S.cur_own[g] = own;
-                        S.cur_opp[g] = opp;
-                        h_own[gl] = own; // (what the rollout pass reads)
-                        h_opp[gl] = opp;
-                        h_stream[gl] = turn * S.n_sims + n_done + s_in; // (a wave: playout p = the wave's first + the slot)
-                        if (ask)
-                            send_request(S, KIND_VALUE, g, epoch, own, opp);
-                    }
-                    state = ask ? ST_ROLL_FRESH : ST_ROLL;
-                    if constexpr (WAVE) {
-                        // the playout is in flight: vv + 1 along its path, and the tree's next slot may descend
-                        __threadfence_block(); // (lane 0's path entries, read by the group's other lanes)
-                        const int len = path_n < S.path_stride ? path_n : S.path_stride;
-                        for (int d = (int)r; d < len; d += 8) {
-                            const int pn = path_at >= 0 ? ((const int32_t *)iago_trunk::trunk_lds)[path_at + d] : gpath[d];
-                            T.nodes[base + pn].reserved1 += 1;
-                        }
-                        if (r == 0u)
-                            wv_next[tl] = s_in + 1;
-                    }
-                }
-            }
-            if (exists && r == 0u)
-                S.roll[g] = (need_z && (state == ST_ROLL || state == ST_ROLL_FRESH)) ? 1 : 0;
         }
         if constexpr (WAVE) {
-            if (!wg_handoff_or(went_any))
-                break;
+            if (I.tid == 0)
+                sh.wv_time[0] += wall_clock64() - c_desc;
         }
-        }
-        if (WAVE && tid == 0)
-            wv_time[0] += wall_clock64() - c_desc;
-        // ---- rollouts of the leaves reached in this iteration (Simulate, mcts_self_play.py:9-134): the games that
-        // have one are packed into rows of 16 boards (about half of a workgroup's games reach a leaf in an iteration,
-        // the others wait for a net: one pass of the 16-lanes-per-board body instead of two, most of the time).  A
-        // board's game does not depend on its row: Philox counters are keyed by the game and its playout count
-        // the control words this iteration's end looks at (abort, the rings' depths for the pacing and the values-ahead gate,
-        // the games in play and their progress): eight loads in flight together HERE, under the rollouts -- read one after
-        // the other by thread 0 between the iteration's last two barriers they were up to six dependent round trips to L2
-        // (2 - 4 us of a 34 us iteration, with the whole workgroup waiting).  All of it is timing-only state, one
-        // iteration old at most when it is used.
-        uint32_t c_abort = 0u, c_idle = 0u, c_t0 = 0u, c_h0 = 0u, c_t1 = 0u, c_h1 = 0u, c_play = 0u, c_prog = 0u, c_next = 0u;
-        if (tid == 0) {
-            if (S.stream)
-                c_next = __hip_atomic_load(&S.ctl[CTL_NEXT_GAME], RLX_AGENT);
-            c_abort = __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT);
-            c_idle = __hip_atomic_load(&S.ctl[CTL_IDLE], RLX_AGENT);
-            c_t0 = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT);
-            c_h0 = __hip_atomic_load(&S.ctl[ctl_head(0)], RLX_AGENT);
-            c_t1 = __hip_atomic_load(&S.ctl[ctl_tail(1)], RLX_AGENT);
-            c_h1 = __hip_atomic_load(&S.ctl[ctl_head(1)], RLX_AGENT);
-            c_play = __hip_atomic_load(&S.ctl[CTL_PLAYING], RLX_AGENT);
-            c_prog = __hip_atomic_load(&S.ctl[CTL_PROGRESS], RLX_AGENT);
-        }
-        const bool rolls = mine && need_z && (state == ST_ROLL || state == ST_ROLL_FRESH);
+        const CtlWords c = read_ctl(S, I.tid);
+        const bool rolls = I.mine && I.need_z && (G.state == ST_ROLL || G.state == ST_ROLL_FRESH);
         const long long c_roll = WAVE ? wall_clock64() : 0;
-        bool rolled = true; // this game's rollout ran in this iteration (or it needs none)
-        {
-            // Passes of 16 boards.  A pass costs the same whether it plays 16 boards or one, and all games of the workgroup
-            // wait for it: when a full pass leaves only a few games over (at most S.roll_defer), they are played in the
-            // NEXT iteration's first pass, ahead of that iteration's own (17 .. 20 games rolled out in 16 % of the
-            // iterations, more than 20 in 32 %: LABNOTES.md, round 5).  Timing only: a game's rollout is keyed by its
-            // own playout count, whenever it runs.
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(rolls && r == 0u); // bit 8 j: game j of this wave
-            const uint64_t balo = __builtin_amdgcn_ballot_w64(rolls && deferred && r == 0u);
-            if ((tid & 63) == 0) {
-                roll_wave[tid >> 6] = (uint32_t)(((bal & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
-                roll_wave_old[tid >> 6] = (uint32_t)(((balo & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56);
-            }
-            if (tid < GAMES_PER_WG)
-                roll_list[tid] = -1;
-            __syncthreads();
-            uint32_t gm = 0u, go = 0u; // bit j: game j of the workgroup has a rollout / one put off in the last iteration
-#pragma unroll
-            for (int w = 0; w < BLOCK / 64; w++) {
-                gm |= roll_wave[w] << (8 * w);
-                go |= roll_wave_old[w] << (8 * w);
-            }
-            const int n_roll = __popc(gm), rem = n_roll & 15;
-            const int n_now = (n_roll < 16 || rem > S.roll_defer) ? n_roll : n_roll - rem;
-            const uint32_t below = (1u << (tid >> 3)) - 1u;
-            // the games put off last time first, then this iteration's own, each in game order
-            const int rank = deferred ? __popc(go & below) : __popc(go) + __popc(gm & ~go & below);
-            const bool now = rolls && rank < n_now;
-            if (now && r == 0u)
-                roll_list[rank] = (int32_t)g;
-            deferred = rolls && !now;
-            rolled = !rolls || now;
-            __syncthreads();
-            if (tid == 0)
-                wg_count[2 + (n_roll == 0 ? 0 : n_roll <= 16 ? 1 : n_roll <= 20 ? 2 : 3)]++; // (diagnostic: totals[10], [13..15])
-#pragma unroll 1
-            for (int at = 0; at < n_now; at += 16) {
-                iago_row::rollout_row_body<false, true, true>(R, 0u, roll_list + at, table_ready, &hand);
-                table_ready = true;
-                __syncthreads();
-            }
-        }
-        if (WAVE && mine && rolled) {
-            // a wave search: the leaf's value is at hand (stored, from the table, or -- ROLL_FRESH -- on its way); the
-            // backup waits for the wave's other leaves
-            if (state == ST_ROLL) {
-                v_reply = __uint_as_float(vbits);
-                state = ST_HAVE_VALUE;
-            } else if (state == ST_ROLL_FRESH) {
-                state = ST_WAIT_VALUE;
-            }
-        }
-        if (!WAVE && mine && rolled) {
-            if (state == ST_ROLL) {
-                backup_game<false>(S, g, r, leaf, leaf_fresh, __uint_as_float(vbits), path_n, h_z[gl], path_at, g);
-                n_done++;
-                if (S.trace && r == 0u)
-                    atomicAdd((unsigned long long *)&S.totals[9], 1ull);
-                if (r == 0u)
-                    S.done[g] = turn * S.n_sims + n_done;
-                state = n_done >= S.n_sims ? search_end : ST_READY;
-            } else if (state == ST_ROLL_FRESH) {
-                state = ST_WAIT_VALUE;
-            }
-        }
-        if constexpr (WAVE) {
-            // ---- the backups of every tree whose wave has all its leaf values: in slot order (a step per slot, each
-            // handing the tree to the next), then the tree's next wave -- or the end of its search
-            const long long c_back = wall_clock64();
-            if (tid == 0)
-                wv_time[1] += c_back - c_roll;
-            if (mine && r == 0u && state != ST_HAVE_VALUE && state != ST_DONE && s_in < wv_size[tl])
-                wv_block[tl] = 1;
-            __syncthreads();
-            // (a tree in search whose wave blocks nothing: every slot of the wave holds its value, the others are idle)
-            const bool ready = mine && state != ST_DONE && wv_block[tl] == 0;
-            if (wg_handoff_or(ready)) {
-                for (int j = 0; j < W; j++) {
-                    if (ready && s_in == j && state == ST_HAVE_VALUE) {
-                        backup_game<true>(S, g, r, leaf, leaf_fresh, v_reply, path_n, h_z[gl], path_at, gt);
-                        if (S.trace && r == 0u)
-                            atomicAdd((unsigned long long *)&S.totals[9], 1ull);
-                    }
-                    wg_handoff_or(false);
+        const bool rolled = rollout_passes(S, R, I, sh, rolls, deferred, table_ready);
+        // the leaf's value is at hand (stored or from the table) or -- ROLL_FRESH -- on its way; a wave search's backup
+        // waits for the wave's other leaves
+        if (I.mine && rolled) {
+            if (G.state == ST_ROLL) {
+                if constexpr (WAVE) {
+                    C.v_reply = __uint_as_float(C.vbits);
+                    G.state = ST_HAVE_VALUE;
+                } else {
+                    finish_playout(S, I, sh, G, C, C.leaf_fresh, __uint_as_float(C.vbits));
                 }
-                if (ready) {
-                    n_done += wv_size[tl];
-                    const int m = S.n_sims - n_done < W ? S.n_sims - n_done : W;
-                    state = n_done >= S.n_sims ? ST_DONE : (s_in < m ? ST_READY : ST_IDLE);
-                    if (r == 0u)
-                        S.done[g] = n_done;
-                    busy = true;
-                }
-                __syncthreads(); // (every slot has read its tree's wave size)
-                if (ready && s_in == 0 && r == 0u) {
-                    const int m = S.n_sims - n_done < W ? S.n_sims - n_done : W;
-                    wv_size[tl] = m;
-                    wv_next[tl] = 0;
-                }
+            } else if (G.state == ST_ROLL_FRESH) {
+                G.state = ST_WAIT_VALUE;
             }
-            // (read above, before the barrier: cleared for the next iteration's look)
-            if (mine && r == 0u && s_in == 0)
-                wv_block[tl] = 0;
-            if (tid == 0)
-                wv_time[2] += wall_clock64() - c_back;
         }
-        if (S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] < S.trace_rows - T.n_games) {
-            const int64_t iters = (int64_t)wg_count[0];
-            S.trace[4 * iters + 0] = wall_clock64() - t0;
-            S.trace[4 * iters + 1] = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT) + __hip_atomic_load(&S.ctl[ctl_tail(1)], RLX_AGENT);
-            S.trace[4 * iters + 2] = __hip_atomic_load(&S.ctl[ctl_head(0)], RLX_AGENT) + __hip_atomic_load(&S.ctl[ctl_head(1)], RLX_AGENT);
-            S.trace[4 * iters + 3] = (int64_t)__hip_atomic_load(&S.ctl[CTL_FINISHED], RLX_AGENT) |
-                                     (__hip_atomic_load(&S.totals[9], RLX_AGENT) << 8);
-        }
-        if (tid == 0)
-            wg_count[0]++;
-        if (mine && r == 0u) {
-            const int prog = state == ST_DONE ? 0 : turn * S.n_sims + n_done;
-            if (prog != contrib)
-                atomicAdd(&pace[0], prog - contrib);
-            if (in_play && state == ST_DONE)
-                atomicAdd(&pace[1], -1);
-        }
-        contrib = state == ST_DONE ? 0 : turn * S.n_sims + n_done;
-        in_play = in_play && state != ST_DONE;
-        // (the workgroup's own stores to done / the tree are read by its next iteration: same CU)
-        const bool over = wall_clock64() - t0 > S.clock_limit;
-        if (over && tid == 0)
-            __hip_atomic_store(&S.ctl[CTL_ABORT], 1u, RLX_AGENT);
-        const int stop = __syncthreads_or(over || (tid == 0 && c_abort != 0u));
-        if (tid == 0) {
-            if (pace[0])
-                __hip_atomic_fetch_add(&S.ctl[CTL_PROGRESS], (uint32_t)pace[0], RLX_AGENT);
-            if (pace[1])
-                __hip_atomic_fetch_add(&S.ctl[CTL_PLAYING], (uint32_t)pace[1], RLX_AGENT);
-            pace[0] = 0;
-            pace[1] = 0;
-            int limit = 0x7fffffff;
-            pace[3] = 0;
-            const int32_t wait0 = (int32_t)(c_t0 - c_h0), wait1 = (int32_t)(c_t1 - c_h1);
-            if (S.ahead_idle >= 0 && S.vtable_mask && n_slots <= (int64_t)(QCAP / 2u) && c_idle >= (uint32_t)S.ahead_idle &&
-                wait0 <= 0 && wait1 <= 0)
-                // this iteration's share of the ring for requests nobody waits for: the games' own requests (at most one
-                // each) and TWO iterations' worth of these (the workgroups look at the rings at different moments: a second
-                // burst can be on its way before the first shows in anybody's snapshot) fit the ring together
-                pace[3] = (int32_t)((QCAP - (uint32_t)n_slots) / 2u) / S.n_game_wgs;
-            // (a stream: no hold while game ids are left to claim -- the mean then mixes old and new games; the rule
-            // holds again for the final drain, when every id is taken)
-            if (S.pace_margin >= 0 && (!S.stream || (int64_t)c_next + T.n_games >= (int64_t)S.games_total)) {
-                if (wait0 + wait1 > S.pace_backlog && c_play != 0u && c_play <= (uint32_t)T.n_games)
-                    limit = (int)(c_prog / c_play) + S.pace_margin;
-            }
-            pace[2] = limit;
-        }
-        int all_done = __syncthreads_and(!mine || state == ST_DONE);
-        pace_limit = pace[2];
-        if (all_done && !stop && S.stream) {
-            // A stream: the workgroup's games are all over -- its slots take the next block of game ids, one each, and
-            // start those games together.  (Claimed slot by slot, games of every phase shared a workgroup: a rollout pass
-            // lasts as long as its longest board and a wave's descent as its deepest game, so every iteration paid for
-            // the opening's rollouts AND the end's pass chains -- 0.84x / 0.75x the batch loop's games/s at 100 / 400
-            // playouts; LABNOTES.md.)  Which slot plays which game changes nothing: a game draws with its own id
-            __shared__ uint32_t claimed;
-            if (tid == 0)
-                claimed = __hip_atomic_fetch_add(&S.ctl[CTL_NEXT_GAME], (uint32_t)n_here, RLX_AGENT);
-            __syncthreads();
-            const int64_t next = T.n_games + (int64_t)claimed + gl;
-            if (exists && next < S.games_total) {
-                // its start position and books (game.py:32), a fresh tree: reset_kernel's Node(None, 1.0) -- except the
-                // pool's overflow flag, which voids the launch whichever game set it.  The reply tag `epoch` goes on
-                // counting: a reply to the slot's last game is never taken for one to this game
-                g_own = S.game_own[next];
-                g_opp = S.game_opp[next];
-                turn = 0;
-                stones = 4;
-                pass_flg = false;
-                g_over = false;
-                n_done = 0;
-                if (r == 0u) {
-                    S.done[g] = 0;
-                    init_node(T, base, -1, -2, 1.0f + 0.1f);
-                    T.n_nodes[g] = 1;
-                    T.root[g] = 0;
-                    atomicAdd(&pace[1], 1); // (in play again: CTL_PLAYING at the next iteration's end)
-                }
-                h_game[gl] = (int32_t)next;
-                state = ST_TURN;
-                in_play = true;
-            }
-            all_done = __syncthreads_and(!mine || state == ST_DONE);
-        }
+        if constexpr (WAVE)
+            wave_backups(S, I, sh, G, C, c_roll, busy);
+        const bool stop = iteration_end(S, I, sh, G, c, t0, contrib, in_play);
+        bool all_done = __syncthreads_and(!I.mine || G.state == ST_DONE) != 0;
+        pace_limit = sh.pace[2];
+        if (all_done && !stop && S.stream)
+            all_done = stream_claim(S, I, sh, G, in_play);
         if (all_done || stop)
             break;
         if (!__syncthreads_or(busy)) {
-            if (tid == 0)
-                wg_count[1]++;
+            if (I.tid == 0)
+                sh.wg_count[1]++;
             __builtin_amdgcn_s_sleep(32); // every game waits for a reply: poll again in ~1 us
-            if (WAVE && tid == 0)
-                wv_time[3] += wall_clock64() - c_it;
+            if constexpr (WAVE) {
+                if (I.tid == 0)
+                    sh.wv_time[3] += wall_clock64() - c_it;
+            }
         }
     }
-    if (exists && r == 0u && S.stats) {
-        if (WAVE) {
-            atomicAdd(&S.stats[2 * gt], st_levels);
-            atomicAdd(&S.stats[2 * gt + 1], st_children);
-        } else {
-            S.stats[2 * g] += st_levels;
-            S.stats[2 * g + 1] += st_children;
-        }
-    }
-    if (WAVE && tid < 4 && S.wave_timing)
-        atomicAdd((unsigned long long *)&S.wave_timing[tid], (unsigned long long)wv_time[tid]);
-    // (a launch that gave up: what every unfinished game was waiting for, for the post-mortem -- the trees are void anyway:
-    // cur_node = the reply tag it waits for, leaf_value = its state; tools/debug_split_abort.py)
-    if (exists && r == 0u && state != ST_DONE && __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u) {
-        S.cur_node[g] = (int32_t)epoch;
-        S.leaf_value[g] = (float)state;
-    }
-    if (tid == 0) {
-        atomicAdd((unsigned long long *)&S.totals[2], (unsigned long long)wg_count[0]);
-        atomicAdd((unsigned long long *)&S.totals[6], (unsigned long long)wg_count[1]);
-        atomicAdd((unsigned long long *)&S.totals[10], (unsigned long long)wg_count[2]);
-        atomicAdd((unsigned long long *)&S.totals[13], (unsigned long long)wg_count[3]);
-        atomicAdd((unsigned long long *)&S.totals[14], (unsigned long long)wg_count[4]);
-        atomicAdd((unsigned long long *)&S.totals[15], (unsigned long long)wg_count[5]);
-        atomicAdd((unsigned long long *)&S.totals[7], (unsigned long long)(wall_clock64() - t0));
-        __hip_atomic_fetch_add(&S.ctl[CTL_FINISHED], 1u, RLX_AGENT);
-    }
+    epilogue<WAVE>(S, I, sh, G, st_levels, st_children, t0);
 }
 
 // A NET workgroup: ticket -> entry -> walk -> reply, until every game workgroup has finished.
@@ -1388,27 +1529,29 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
 // ONE grid: the game workgroups first (they are dispatched first, so all of them are resident whatever else
 // holds CUs; a net workgroup never waits for another net workgroup, so one that finds no CU free simply starts
 // late), then the net workgroups.  A game workgroup whose games are done serves the queue like the others.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_kernel(
-    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+template <bool WAVE>
+__device__ __forceinline__ void search_body(const SearchParams &S, const iago_row::HwParams &R, const iago_trunk::TrunkRParams &VP,
+                                            const iago_policy::PolicyParams &PP)
 {
     const long long t0 = wall_clock64();
     if (blockIdx.x == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
     if ((int)blockIdx.x < S.n_game_wgs)
-        game_workgroup<false>(S, R, t0);
+        game_workgroup<WAVE>(S, R, t0);
     net_workgroup(S, VP, PP, t0);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_kernel(
+    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+{
+    search_body<false>(S, R, VP, PP);
 }
 
 // The wave search (iago_mcts_search_wave): the same grid, game workgroups of 32 SLOTS, S.wave of them per tree.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_wave_kernel(
     SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
 {
-    const long long t0 = wall_clock64();
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
-    if ((int)blockIdx.x < S.n_game_wgs)
-        game_workgroup<true>(S, R, t0);
-    net_workgroup(S, VP, PP, t0);
+    search_body<true>(S, R, VP, PP);
 }
 
 // The same search as TWO launches that run together, one per role (iago_mcts_search_split: each on a stream of its own
@@ -1495,8 +1638,8 @@ struct iago_search_streams {
 };
 
 namespace {
-int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
-                  const iago_search_wave_args *wv = nullptr)
+// the arguments of a launch (what does not depend on the device)
+int check_args(const iago_mcts_search_args *a, const iago_search_wave_args *wv)
 {
     if (!a || !a->tree || !a->value || !a->policy || !a->rollout)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: null args");
@@ -1527,30 +1670,46 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (a->z_log_rows > 0 && (!a->z_log || !a->z_log_n))
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: z_log needs z_log_n");
     const iago_rollout_args *ro = a->rollout;
-    const int wave = wv ? wv->width : 1;
-    const int64_t n_slots = tree->n_games * wave; // (a wave search: the slots' arrays)
+    const int64_t n_slots = tree->n_games * (wv ? wv->width : 1); // (a wave search: the slots' arrays)
     if (wv && n_slots > (int64_t)QCAP)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_wave: more slots (n_games x width) than a request ring holds");
     if (ro->n != n_slots || !ro->z || !ro->table || ((uintptr_t)ro->table & 15u) || ro->log_form || ro->trace ||
         ro->uniforms || ro->throughput_hint != 0)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: product-form rollout of the n games without "
                                            "trace / uniforms expected");
-    const int gpw = wv ? GAMES_PER_WG : a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
-    if (gpw != 8 && gpw != 16 && gpw != 24 && gpw != 32)
+    const int gpw = a->games_per_workgroup;
+    if (!wv && gpw > 0 && gpw != 8 && gpw != 16 && gpw != 24 && gpw != 32)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: games_per_workgroup is 0 (= 32), 8, 16 or 32");
-    const int64_t n_game_wgs = (n_slots + gpw - 1) / gpw;
-    // The grid follows the device: every game workgroup must be resident together with at least one net workgroup (a
-    // game waits for replies only net workgroups give), and a net workgroup beyond what fits would only start when
-    // another one ends -- at the end of the launch.  Resident workgroups = CUs the launch may count on (max_cus, else
-    // the device's) x workgroups of this kernel per CU (its registers and LDS allow one).
+    if (a->max_cus < 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: max_cus < 0");
+    if (a->vtable_slots > 0 && (!a->vtable || ((uintptr_t)a->vtable & 31u) || (a->vtable_slots & (a->vtable_slots - 1)) != 0))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: vtable must be 32-byte aligned, vtable_slots a "
+                                           "power of two");
+    return IAGO_OK;
+}
+
+struct SearchGrid {
+    int gpw;                                 // games (a wave search: slots) per game workgroup
+    int64_t n_slots, n_game_wgs, net_wgs, grid;
+    int path_lds_cap, game_lds;              // the games' paths in dynamic LDS: bytes a workgroup may use; the game launch's
+};
+
+// The grid follows the device: every game workgroup must be resident together with at least one net workgroup (a game
+// waits for replies only net workgroups give), and a net workgroup beyond what fits would only start when another one
+// ends -- at the end of the launch.  Resident workgroups = CUs the launch may count on (max_cus, else the device's) x
+// workgroups of this kernel per CU (its registers and LDS allow one).
+int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iago_search_wave_args *wv, SearchGrid &G)
+{
+    G.gpw = wv ? GAMES_PER_WG : a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
+    G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
+    G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
     int32_t cus = 0, per_cu = 0;
     if (const int rc = iago_mcts_search_capacity(&cus, &per_cu))
         return rc;
-    if (a->max_cus < 0)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: max_cus < 0");
     int64_t resident = (int64_t)(a->max_cus > 0 && a->max_cus < cus ? a->max_cus : cus) * per_cu;
     // the games' recorded paths in the launch's dynamic LDS when they fit there (else in the caller's array)
-    int path_lds_cap = SEARCH_IMG_TOP, game_lds = 0;
+    G.path_lds_cap = SEARCH_IMG_TOP;
+    G.game_lds = 0;
     if (sp) {
         // Role split: the game launch has sp->game_cus CUs of its own and the net launch all the others.  A game
         // workgroup keeps its paths in LDS when TWO workgroups with them fit a CU (else in the caller's array)
@@ -1559,7 +1718,7 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: the streams belong to another device");
         if (a->max_cus != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
-        const size_t want = (size_t)gpw * (size_t)a->path_stride * 4u;
+        const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
         // (asked of the runtime once per device and LDS size: every launch comes through here)
         static std::atomic<int32_t> static_lds{-1};
         int32_t fixed = static_lds.load(std::memory_order_acquire);
@@ -1570,23 +1729,23 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
             fixed = (int32_t)fa.sharedSizeBytes;
             static_lds.store(fixed, std::memory_order_release);
         }
-        game_lds = (want + (size_t)fixed + 256u) * 2u <= (size_t)160 * 1024u ? (int)want : 0;
-        path_lds_cap = game_lds;
+        G.game_lds = (want + (size_t)fixed + 256u) * 2u <= (size_t)160 * 1024u ? (int)want : 0;
+        G.path_lds_cap = G.game_lds;
         static std::atomic<uint64_t> configured_game{0};
-        if (game_lds && iago_reserve_lds((const void *)search_game_kernel, 96 * 1024, configured_game,
-                                         "iago_mcts_search_split: cannot reserve the game workgroups' LDS"))
+        if (G.game_lds && iago_reserve_lds((const void *)search_game_kernel, 96 * 1024, configured_game,
+                                           "iago_mcts_search_split: cannot reserve the game workgroups' LDS"))
             return IAGO_ERR_HIP;
         static std::atomic<uint64_t> occ_known[64]; // per device: LDS bytes << 8 | workgroups per CU (+ 1 << 63: valid)
         int per_game = 0;
         const uint64_t seen = occ_known[dev & 63].load(std::memory_order_acquire);
-        if ((seen >> 63) && ((seen >> 8) & 0xFFFFFFull) == (uint64_t)game_lds) {
+        if ((seen >> 63) && ((seen >> 8) & 0xFFFFFFull) == (uint64_t)G.game_lds) {
             per_game = (int)(seen & 0xFF);
         } else {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_game, (const void *)search_game_kernel, 256, (size_t)game_lds) != hipSuccess)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_game, (const void *)search_game_kernel, 256, (size_t)G.game_lds) != hipSuccess)
                 return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: the device does not answer");
-            occ_known[dev & 63].store((1ull << 63) | ((uint64_t)game_lds << 8) | (uint64_t)(per_game & 0xFF), std::memory_order_release);
+            occ_known[dev & 63].store((1ull << 63) | ((uint64_t)G.game_lds << 8) | (uint64_t)(per_game & 0xFF), std::memory_order_release);
         }
-        if (n_game_wgs > (int64_t)sp->game_cus * per_game)
+        if (G.n_game_wgs > (int64_t)sp->game_cus * per_game)
             return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_split: the game workgroups do not fit the game launch's CUs "
                                                 "(more game CUs, fewer games per launch, or the single launch)");
         // The net launch takes at most 7/8 of the device's CUs (224 of 256), whatever the game launch leaves.  Measured, not
@@ -1595,29 +1754,27 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
         // ticket, stopped executing in the same 100 us, and went on the moment the game launch had ended (at its clock
         // limit); with at most 224, 960 batches in a row on the same settings: none (LABNOTES.md, round 6)
         const int64_t net_cus = cus - (sp->game_cus > cus / 8 ? sp->game_cus : cus / 8);
-        resident = n_game_wgs + net_cus * per_cu;
+        resident = G.n_game_wgs + net_cus * per_cu;
     }
-    if (n_game_wgs + 1 > resident)
+    if (G.n_game_wgs + 1 > resident)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_persistent: the game workgroups and one net workgroup do not "
                                             "fit the device together (fewer games per launch, or the per-playout launches)");
-    const int64_t net_wgs = a->net_workgroups < resident - n_game_wgs ? a->net_workgroups : resident - n_game_wgs;
-    const int64_t grid = n_game_wgs + net_wgs;
-    if (a->value->n < 4 * grid || a->policy->n < 4 * grid || a->value->planes || a->value->index || a->value->n_dev ||
+    G.net_wgs = a->net_workgroups < resident - G.n_game_wgs ? a->net_workgroups : resident - G.n_game_wgs;
+    G.grid = G.n_game_wgs + G.net_wgs;
+    if (a->value->n < 4 * G.grid || a->policy->n < 4 * G.grid || a->value->planes || a->value->index || a->value->n_dev ||
         a->policy->index || a->policy->n_dev || !a->value->own || a->value->own != a->wg_own ||
         a->value->opp != a->wg_opp || a->policy->own != a->wg_own || a->policy->opp != a->wg_opp)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: the nets read their rows from wg_own / wg_opp "
                                            "(four rows per workgroup of the grid: n >= 4 x (game + net workgroups)), no gather list, no "
                                            "device count");
-    iago_trunk::TrunkRParams VP;
-    if (const int rc = iago_trunk::value_params_of(a->value, VP))
-        return rc;
-    VP.count_lo = 0;
-    VP.count_hi = 0x7fffffff;
-    iago_policy::PolicyParams PP;
-    if (const int rc = iago_policy::policy_params_of(a->policy, PP))
-        return rc;
+    return IAGO_OK;
+}
+
+// the kernels' parameters: the arguments, the grid, the tuning knobs of the environment
+SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, const iago_search_wave_args *wv)
+{
     SearchParams S;
-    S.T = *tree;
+    S.T = *a->tree;
     S.root_own = a->root_own;
     S.root_opp = a->root_opp;
     S.active = a->active;
@@ -1625,8 +1782,8 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.lmbda = a->lmbda;
     S.n_thr = a->n_thr;
     S.n_sims = a->n_sims;
-    S.n_game_wgs = (int32_t)n_game_wgs;
-    S.games_per_wg = gpw;
+    S.n_game_wgs = (int32_t)G.n_game_wgs;
+    S.games_per_wg = G.gpw;
     S.cur_node = a->cur_node;
     S.cur_own = a->cur_own;
     S.cur_opp = a->cur_opp;
@@ -1634,7 +1791,7 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.path_stride = a->path_stride;
     S.done = a->done;
     S.roll = a->roll;
-    S.z = ro->z;
+    S.z = a->rollout->z;
     S.leaf_value = a->leaf_value;
     S.z_log = a->z_log_rows > 0 ? a->z_log : nullptr;
     S.z_log_n = a->z_log_n;
@@ -1665,10 +1822,9 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.policy_xcds = policy_xcds;
     // (tuning knob of the pacing: requests that must be waiting for a leader to hold)
     const char *pace_env = getenv("IAGO_PERSISTENT_PACE_BACKLOG"); // (read per launch: the tests vary it)
-    const int pace_backlog = pace_env ? atoi(pace_env) : 128;
-    const int pace_margin = a->pace_margin == 0 ? 16 : (a->pace_margin < 0 ? -1 : a->pace_margin);
-    S.pace_margin = pace_margin;
-    S.pace_backlog = pace_backlog;
+    S.pace_backlog = pace_env ? atoi(pace_env) : 128;
+    // (pacing evens out the games of a batch: the slots of a wave keep their tree's step)
+    S.pace_margin = wv ? -1 : a->pace_margin == 0 ? 16 : (a->pace_margin < 0 ? -1 : a->pace_margin);
     // (tuning knob: net workgroups that must poll for values to be walked ahead of their visit; -1 = never)
     const char *ahead_env = getenv("IAGO_PERSISTENT_AHEAD"); // (read per launch: the tests vary it)
     S.ahead_idle = ahead_env ? atoi(ahead_env) : 4;
@@ -1677,13 +1833,11 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.roll_defer = defer_env ? atoi(defer_env) : 10;
     if (S.roll_defer < 0 || S.roll_defer > 15)
         S.roll_defer = S.roll_defer < 0 ? 0 : 15;
-    S.path_lds_cap = path_lds_cap;
-    S.wave = wave;
+    S.path_lds_cap = G.path_lds_cap;
+    S.wave = wv ? wv->width : 1;
     S.vloss = wv ? wv->vloss : 0.0f;
-    S.n_slots = n_slots;
+    S.n_slots = G.n_slots;
     S.wave_timing = wv ? wv->timing : nullptr;
-    if (wv)
-        S.pace_margin = -1; // (pacing evens out the games of a batch: the slots of a wave keep their tree's step)
     S.max_turns = a->max_turns;
     S.game_own = a->game_own;
     S.game_opp = a->game_opp;
@@ -1694,40 +1848,48 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     S.rec_move = a->rec_move;
     S.rec_pi = a->rec_pi;
     S.stream = a->games_total > 0 ? 1 : 0;
-    S.games_total = a->games_total > 0 ? a->games_total : (int32_t)tree->n_games;
-    S.vtable = nullptr;
-    S.vtable_mask = 0u;
-    if (a->vtable_slots > 0) {
-        if (!a->vtable || ((uintptr_t)a->vtable & 31u) || (a->vtable_slots & (a->vtable_slots - 1)) != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: vtable must be 32-byte aligned, vtable_slots a "
-                                               "power of two");
-        S.vtable = (u64 *)a->vtable;
-        S.vtable_mask = (uint32_t)(a->vtable_slots - 1);
-    }
+    S.games_total = a->games_total > 0 ? a->games_total : (int32_t)a->tree->n_games;
+    S.vtable = a->vtable_slots > 0 ? (u64 *)a->vtable : nullptr;
+    S.vtable_mask = a->vtable_slots > 0 ? (uint32_t)(a->vtable_slots - 1) : 0u;
     S.trace = a->trace_rows > 0 ? a->trace : nullptr;
     S.trace_rows = a->trace_rows;
-    iago_row::HwParams R = iago_row::hw_params_of(ro);
+    return S;
+}
+
+// the zeroing of the polled words and the launch: one kernel, or the role split's two on their masked streams
+int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp, const iago_search_wave_args *wv,
+                  const SearchGrid &G, const SearchParams &S)
+{
+    iago_trunk::TrunkRParams VP;
+    if (const int rc = iago_trunk::value_params_of(a->value, VP))
+        return rc;
+    VP.count_lo = 0;
+    VP.count_hi = 0x7fffffff;
+    iago_policy::PolicyParams PP;
+    if (const int rc = iago_policy::policy_params_of(a->policy, PP))
+        return rc;
+    iago_row::HwParams R = iago_row::hw_params_of(a->rollout);
     R.own = a->cur_own;
     R.opp = a->cur_opp;
     R.mask = a->roll;
     R.stream_ids = a->done;
-    constexpr int lds = search_lds(); // (reserved for the kernel by iago_mcts_search_capacity above)
+    constexpr int lds = search_lds(); // (reserved for the kernel by iago_mcts_search_capacity)
     // every polled word starts from zero: the control block, the request ring and the reply mailboxes
     if (hipMemsetAsync(a->ctl, 0, 64, (hipStream_t)stream) != hipSuccess ||
         hipMemsetAsync(a->q_slots, 0, (size_t)2 * QCAP * 64, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_v, 0, (size_t)n_slots * 8, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_p, 0, (size_t)n_slots * 512, (hipStream_t)stream) != hipSuccess)
+        hipMemsetAsync(a->rep_v, 0, (size_t)G.n_slots * 8, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(a->rep_p, 0, (size_t)G.n_slots * 512, (hipStream_t)stream) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_persistent: hipMemsetAsync failed");
     if (wv) {
         static std::atomic<uint64_t> configured_wave{0};
         if (iago_reserve_lds((const void *)search_wave_kernel, lds, configured_wave,
                              "iago_mcts_search_wave: cannot reserve the nets' LDS image"))
             return IAGO_ERR_HIP;
-        hipLaunchKernelGGL(search_wave_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
+        hipLaunchKernelGGL(search_wave_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
         return iago_check_launch("iago_mcts_search_wave");
     }
     if (!sp) {
-        hipLaunchKernelGGL(search_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
+        hipLaunchKernelGGL(search_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
         return iago_check_launch("iago_mcts_search_persistent");
     }
     // both launches after everything queued on the caller's stream so far (the zeroing above included), the caller's
@@ -1739,10 +1901,10 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)n_game_wgs), dim3(256), game_lds, sp->game, S, R);
+    hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
     int rc = iago_check_launch("iago_mcts_search_split (game launch)");
     if (rc == IAGO_OK) {
-        hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)net_wgs), dim3(256), lds, sp->net, S, VP, PP);
+        hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)G.net_wgs), dim3(256), lds, sp->net, S, VP, PP);
         rc = iago_check_launch("iago_mcts_search_split (net launch)");
     }
     // (also after a failed launch: whatever did start is waited for by the caller's stream)
@@ -1751,6 +1913,17 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
         hipStreamWaitEvent((hipStream_t)stream, sp->net_done, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the stream after the launches");
     return rc;
+}
+
+int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
+                  const iago_search_wave_args *wv = nullptr)
+{
+    SearchGrid G;
+    if (const int rc = check_args(a, wv))
+        return rc;
+    if (const int rc = size_grid(a, sp, wv, G))
+        return rc;
+    return launch_search(a, stream, sp, wv, G, search_params(a, G, wv));
 }
 } // namespace
 

@@ -42,57 +42,40 @@ def request_log(s):
     }
 }''')
     # (the timeline rows and the per-game end rows would overwrite the log)
-    s = patch(s, "if (S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] <", "if (false && S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] <")
-    s = patch(s, "if (S.trace && r == 0u && g < S.trace_rows) {", "if (false && S.trace && r == 0u && g < S.trace_rows) {")
+    s = patch(s, "if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
+              "if (false && S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
+    s = patch(s, "if (S.trace && I.r == 0u && I.g < S.trace_rows) {", "if (false && S.trace && I.r == 0u && I.g < S.trace_rows) {")
     return s
 
 
 def phase_stamps(s):
-    """Game workgroup 0's iteration by phase (100 MHz stamps of thread 0): replies + moves, descent, the control
-    words' loads + the packing of the rollouts, the rollout passes, the backup of the rolled games, the end of the
-    iteration (two barriers, pacing); summed in iago_game_phases[0..5], the iterations in [7]."""
+    """Game workgroup 0's iteration by phase (100 MHz stamps of thread 0), at the driver loop's phase calls: replies +
+    moves, descent, the control words' loads, the rollouts (packing + passes), the backups, the end of the iteration (two
+    barriers, pacing); summed in iago_game_phases[0..5], the iterations in [7]."""
     s = patch(s, "namespace {\nusing namespace iago;", "__device__ unsigned long long iago_game_phases[8];\nnamespace {\nusing namespace iago;")
     s = patch(s, """    for (;;) {
-        bool busy = false; // this game did something in this iteration""", """    long long ph[6] = {0, 0, 0, 0, 0, 0};
+        const long long c_it = WAVE ? wall_clock64() : 0;""", """    long long ph[6] = {0, 0, 0, 0, 0, 0};
     for (;;) {
-        long long c_a = wall_clock64();
-        bool busy = false; // this game did something in this iteration""")
-    s = patch(s, """            // ---- descent (MCTS.py:105-133): from the root, or on from the leaf whose priors arrived
-""", """            { const long long c = wall_clock64(); ph[0] += c - c_a; c_a = c; }
-            // ---- descent (MCTS.py:105-133): from the root, or on from the leaf whose priors arrived
-""")
-    s = patch(s, """        uint32_t c_abort = 0u, c_idle = 0u,""", """        { const long long c = wall_clock64(); ph[1] += c - c_a; c_a = c; }
-        uint32_t c_abort = 0u, c_idle = 0u,""")
-    s = patch(s, """#pragma unroll 1
-            for (int at = 0; at < n_now; at += 16) {""", """            { const long long c = wall_clock64(); ph[2] += c - c_a; c_a = c; }
-#pragma unroll 1
-            for (int at = 0; at < n_now; at += 16) {""")
-    s = patch(s, """        if (mine && rolled) {
-            if (state == ST_ROLL) {""", """        { const long long c = wall_clock64(); ph[3] += c - c_a; c_a = c; }
-        if (mine && rolled) {
-            if (state == ST_ROLL) {""")
-    s = patch(s, """        if (tid == 0)
-            wg_count[0]++;
-        if (mine && r == 0u) {
-            const int prog""", """        { const long long c = wall_clock64(); ph[4] += c - c_a; c_a = c; }
-        if (tid == 0)
-            wg_count[0]++;
-        if (mine && r == 0u) {
-            const int prog""")
+        const long long c_it = WAVE ? wall_clock64() : 0;
+        long long c_a = wall_clock64();""")
+    for i, anchor in enumerate(("        const long long c_desc = WAVE ? wall_clock64() : 0;\n",
+                                "        const CtlWords c = read_ctl(S, I.tid);\n",
+                                "        const bool rolled = rollout_passes(",
+                                "        // the leaf's value is at hand (stored or from the table)",
+                                "        const bool stop = iteration_end(")):
+        s = patch(s, anchor, "        { const long long c = wall_clock64(); ph[%d] += c - c_a; c_a = c; }\n" % i + anchor)
     s = patch(s, """        if (!__syncthreads_or(busy)) {
-            if (tid == 0)
-                wg_count[1]++;""", """        { const long long c = wall_clock64(); ph[5] += c - c_a; c_a = c; }
+            if (I.tid == 0)
+                sh.wg_count[1]++;""", """        { const long long c = wall_clock64(); ph[5] += c - c_a; c_a = c; }
         if (!__syncthreads_or(busy)) {
-            if (tid == 0)
-                wg_count[1]++;""")
-    s = patch(s, """    if (tid == 0) {
-        atomicAdd((unsigned long long *)&S.totals[2], (unsigned long long)wg_count[0]);""", """    if (tid == 0 && blockIdx.x == 0) {
+            if (I.tid == 0)
+                sh.wg_count[1]++;""")
+    s = patch(s, """    epilogue<WAVE>(S, I, sh, G, st_levels, st_children, t0);""", """    if (I.tid == 0 && blockIdx.x == 0) {
         for (int i = 0; i < 6; i++)
             atomicAdd(&iago_game_phases[i], (unsigned long long)ph[i]);
-        atomicAdd(&iago_game_phases[7], (unsigned long long)wg_count[0]);
+        atomicAdd(&iago_game_phases[7], (unsigned long long)sh.wg_count[0]);
     }
-    if (tid == 0) {
-        atomicAdd((unsigned long long *)&S.totals[2], (unsigned long long)wg_count[0]);""")
+    epilogue<WAVE>(S, I, sh, G, st_levels, st_children, t0);""")
     s += """
 extern "C" __attribute__((visibility("default"))) int iago_debug_game_phases(unsigned long long *host, int clear)
 {
@@ -262,8 +245,9 @@ def reply_times(s):
     """Post-mortem of a launch that gave up (round 6): per game, in the `trace` buffer, [0] the clock at its last request,
     [1] the clock at which a net workgroup wrote the reply to that request's mailbox (value or priors), [2] the clock at
     which its workgroup left the loop, [3] state | reply tag << 8 (tools/debug_split_abort.py)."""
-    s = patch(s, "if (S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] <", "if (false && S.trace && blockIdx.x == 0 && tid == 0 && (int64_t)wg_count[0] <")
-    s = patch(s, "if (S.trace && r == 0u && g < S.trace_rows) {", "if (false && S.trace && r == 0u && g < S.trace_rows) {")
+    s = patch(s, "if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
+              "if (false && S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
+    s = patch(s, "if (S.trace && I.r == 0u && I.g < S.trace_rows) {", "if (false && S.trace && I.r == 0u && I.g < S.trace_rows) {")
     s = patch(s, """    atomicAdd((unsigned long long *)&S.totals[(uint32_t)g == NOBODY ? 11 : kind], 1ull);
 }""", """    atomicAdd((unsigned long long *)&S.totals[(uint32_t)g == NOBODY ? 11 : kind], 1ull);
     if (S.trace && (uint32_t)g != NOBODY && g < S.trace_rows)
@@ -277,12 +261,12 @@ def reply_times(s):
               """                st(&S.rep_p[(int64_t)(job[0] & 0x7FFFFFFFu) * 64 + tid], ((u64)job[1] << 32) | __float_as_uint(res_p[tid]));
             if (S.trace && tid == 0 && (int)(job[0] & 0x7FFFFFFFu) < S.trace_rows)
                 S.trace[4 * (int64_t)(job[0] & 0x7FFFFFFFu) + 1] = wall_clock64();""")
-    s = patch(s, """        S.cur_node[g] = (int32_t)epoch;
-        S.leaf_value[g] = (float)state;""", """        S.cur_node[g] = (int32_t)epoch;
-        S.leaf_value[g] = (float)state;
-        if (S.trace && g < S.trace_rows) {
-            S.trace[4 * g + 2] = wall_clock64();
-            S.trace[4 * g + 3] = (int64_t)state | ((int64_t)epoch << 8);
+    s = patch(s, """        S.cur_node[I.g] = (int32_t)G.epoch;
+        S.leaf_value[I.g] = (float)G.state;""", """        S.cur_node[I.g] = (int32_t)G.epoch;
+        S.leaf_value[I.g] = (float)G.state;
+        if (S.trace && I.g < S.trace_rows) {
+            S.trace[4 * I.g + 2] = wall_clock64();
+            S.trace[4 * I.g + 3] = (int64_t)G.state | ((int64_t)G.epoch << 8);
         }""")
     # ... and per net workgroup (rows 4096 + blockIdx.x): [0] the clock at its last loop top, [1] the clock when it last began
     # to wait for a ticket, [2] ring << 32 | ticket it last waited for, [3] stage (1 loop top, 2 waiting in fetch, 3 fetched,

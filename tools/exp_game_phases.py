@@ -13,7 +13,7 @@ L = _lib.lib()
 L.iago_debug_game_phases.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
 buf = (C.c_ulonglong * 8)()
 w, b = bench.shipped_rollout_weights()
-NAMES = ("replies + moves", "descent", "control words + packing", "rollout passes", "backup", "end of iteration")
+NAMES = ("replies + moves", "descent", "control words", "packing + rollout passes", "backup", "end of iteration")
 # python tools/exp_game_phases.py [playouts per move = 100] [n_thr = 15]   (round 6: 400 / 15 = configs[3]'s share, 100 / 1)
 SIMS = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 N_THR = int(sys.argv[2]) if len(sys.argv) > 2 else 15
