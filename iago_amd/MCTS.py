@@ -9,19 +9,32 @@ the nets are passed in instead of being read from './models' (MCTS.py:82-85).
 wave = W > 1 (8, 16 or 32): the wave search -- W playouts of the tree in flight at once, steered by virtual visits
 (virtual_loss per in-flight visit), deterministic (engine.BatchedMCTS, include/iago_hip_serving.h).  W = 1 is the
 reference's one-playout-at-a-time order.
+
+solve_empties = k: at a root with at most k empties get_move plays the exact endgame solver's move (the lowest-indexed
+move of the best final disc difference, engine.solve_endgame) and runs no search; n_solved counts these moves.  None,
+the default, always searches.
 """
 import time
 
+import numpy as np
 import torch
 
 from . import boards, engine, ops
+
+SOLVE_EMPTIES_MAX = 20   # what the solver takes (include/iago_hip_serving.h)
+
+
+def solve_split_depth(empties):
+    """The root split of a single-position solve at `empties` empties: the fastest measured on MI355X (LABNOTES
+    "Exact endgame")."""
+    return 0 if empties <= 8 else (4 if empties <= 10 else 3)
 
 
 class MCTS(object):
 
     def __init__(self, lmbda=0.5, c_puct=1, n_thr=15, time_limit=10, policy_net=None,
                  value_net=None, rollout_weights=None, n_sims=None, capacity=65536, seed=0,
-                 use_graph=False, wave=1, virtual_loss=1.0):
+                 use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None):
         if policy_net is None or (value_net is None and lmbda < 1):
             raise ValueError("policy_net / value_net are required (the reference loads "
                              "./models/sl_model.npz and ./models/value_model.npz here)")
@@ -34,10 +47,23 @@ class MCTS(object):
         self.wave = wave
         self.chunk = max(8, 4 * wave)   # playouts per search of the time-limited loop
         self._one = torch.ones(1, dtype=torch.uint8, device="cuda")
+        if solve_empties is not None and (isinstance(solve_empties, bool) or not isinstance(solve_empties, int) or
+                                          not 0 <= solve_empties <= SOLVE_EMPTIES_MAX):
+            raise ValueError("solve_empties must be None or an int in [0, %d], got %r" % (SOLVE_EMPTIES_MAX,
+                                                                                        solve_empties))
+        self.solve_empties = solve_empties
+        self.n_solved = 0
 
     def get_move(self, state, color):
         """MCTS.py:139-147: playouts from the root, then the most visited child."""
         own, opp = boards.own_opp(state, color)
+        if self.solve_empties is not None:
+            empties = int(np.count_nonzero(np.asarray(state) == 0))
+            if empties <= self.solve_empties:
+                move = int(engine.solve_endgame(own, opp, split_depth=solve_split_depth(empties))["move"][0].item())
+                if move >= 0:   # (a pass or a finished game: the search answers as it always has)
+                    self.n_solved += 1
+                    return move
         if self.n_sims is not None:
             self._m.search(own, opp, self._one, self.n_sims)
         else:

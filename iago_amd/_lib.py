@@ -46,9 +46,10 @@ EXPERIMENTAL_SYMBOLS = [
     "iago_mcts_select", "iago_mcts_expand", "iago_mcts_pending", "iago_mcts_backup", "iago_mcts_mix_backup",
     "iago_mcts_expand_cached", "iago_mcts_fresh_leaves",
 ]
-# include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W))
+# include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
+# the exact endgame solver (ops.solve_endgame, engine.solve_endgame)
 SERVING_SYMBOLS = [
-    "iago_mcts_search_wave",
+    "iago_mcts_search_wave", "iago_solve_endgame",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True))
@@ -226,6 +227,23 @@ class SearchWaveArgs(C.Structure):
     ]
 
 
+ENDGAME_EXACT = 0          # IAGO_ENDGAME_EXACT
+ENDGAME_WLD = 1            # IAGO_ENDGAME_WLD
+ENDGAME_MAX_EMPTIES = 20   # IAGO_ENDGAME_MAX_EMPTIES
+ENDGAME_MAX_TIME_MS = 600000
+ENDGAME_CTL_WORDS = 4
+
+
+class EndgameArgs(C.Structure):
+    """Mirror of iago_endgame_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("n", C.c_int64),
+        ("mode", C.c_int32), ("max_empties", C.c_int32), ("time_limit_ms", C.c_int32), ("reserved0", C.c_int32),
+        ("score", C.c_void_p), ("move", C.c_void_p), ("nodes", C.c_void_p), ("solved", C.c_void_p),
+        ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
 class ValueSplitArgs(C.Structure):
     """Mirror of iago_value_split_args (include/iago_hip.h)."""
     _fields_ = [
@@ -347,6 +365,7 @@ def lib():
     L.iago_mcts_search_split.argtypes = [C.POINTER(MctsSearchArgs), vp, vp]
     L.iago_mcts_search_wave.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchWaveArgs), vp]
     L.iago_selfplay_policy.argtypes = [C.POINTER(SelfplayPolicyArgs), vp]
+    L.iago_solve_endgame.argtypes = [C.POINTER(EndgameArgs), vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)

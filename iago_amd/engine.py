@@ -19,6 +19,7 @@ import ctypes as C
 import numbers
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -1831,3 +1832,88 @@ class SelfPlayEngine(object):
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))
         return res
+
+
+def _most_empties(own, opp):
+    """The stack the solver needs: the most empties of the positions, capped at what it takes (beyond: refused)."""
+    bits = ops.tensor_to_bits(own | opp)
+    return min(max((64 - bin(int(b)).count("1") for b in bits), default=0), _lib.ENDGAME_MAX_EMPTIES)
+
+
+def solve_endgame(own, opp, mode="exact", split_depth=0, time_limit_ms=ops.ENDGAME_TIME_LIMIT_MS):
+    """ops.solve_endgame for one position or a few, with a root split: every position is expanded `split_depth` plies
+    (a pass is a ply; a finished game is not expanded) with ops.legal_moves / ops.apply_moves, all the leaves are
+    solved in ONE launch with the full window, and the values are minimaxed back, the lowest-indexed move winning ties.
+    The result equals split_depth = 0's (score and move); what it buys is lanes: a single position at 14+ empties
+    spreads over the chip instead of running on one lane.  Returns the dict of ops.solve_endgame for the roots (nodes:
+    the leaves' nodes plus the split's own; ctl: the launch's)."""
+    if not isinstance(split_depth, int) or isinstance(split_depth, bool) or split_depth < 0:
+        raise ValueError("split_depth must be an int >= 0, got %r" % (split_depth,))
+    dev = own.device
+    if split_depth == 0:
+        return ops.solve_endgame(own, opp, mode=mode, max_empties=_most_empties(own, opp), time_limit_ms=time_limit_ms)
+    n = own.numel()
+    # levels[k]: (own, opp) device tensors of the nodes at ply k, their parent at ply k - 1 and the move from it
+    nodes = [(own.reshape(n).contiguous(), opp.reshape(n).contiguous(), None, None)]
+    leaf = []   # per level: bool numpy array, the node is solved by the kernel
+    for depth in range(split_depth + 1):
+        o, p, _, _ = nodes[depth]
+        m = o.numel()
+        legal = ops.tensor_to_bits(ops.legal_moves(o, p))
+        other = ops.tensor_to_bits(ops.legal_moves(p, o))
+        over = (legal == 0) & (other == 0)
+        if depth == split_depth:
+            leaf.append(np.ones(m, bool))
+            break
+        leaf.append(over.copy())
+        parent, move = [], []
+        for i in range(m):
+            if over[i]:
+                continue
+            lm = int(legal[i])
+            if lm == 0:
+                parent.append(i)
+                move.append(-1)   # the pass child
+            while lm:
+                b = lm & -lm
+                parent.append(i)
+                move.append(b.bit_length() - 1)
+                lm ^= b
+        idx = torch.tensor(parent, dtype=torch.int64, device=dev)
+        mv = torch.tensor(move, dtype=torch.int8, device=dev)
+        co, cp = o[idx].contiguous(), p[idx].contiguous()
+        ops.apply_moves(co, cp, mv)
+        nodes.append((cp, co, np.array(parent, np.int64), np.array(move, np.int64)))   # the other side moves next
+    # every leaf in one launch
+    lo = torch.cat([nodes[k][0][torch.from_numpy(np.nonzero(leaf[k])[0]).to(dev)] for k in range(len(leaf))])
+    lp = torch.cat([nodes[k][1][torch.from_numpy(np.nonzero(leaf[k])[0]).to(dev)] for k in range(len(leaf))])
+    lo, lp = lo.contiguous(), lp.contiguous()
+    res = ops.solve_endgame(lo, lp, mode=mode, max_empties=_most_empties(lo, lp), time_limit_ms=time_limit_ms)
+    score_l, move_l = res["score"].cpu().numpy().astype(np.int64), res["move"].cpu().numpy().astype(np.int64)
+    nodes_l = res["nodes"].cpu().numpy()
+    # minimax back, deepest level first: value = max over children of -child, the first (lowest-index) maximum wins
+    val, mov, cnt, at = [], [], [], 0
+    for k in range(len(leaf)):
+        m = len(leaf[k])
+        val.append(np.zeros(m, np.int64))
+        mov.append(np.full(m, -3, np.int64))
+        cnt.append(np.ones(m, np.int64))
+        sel = np.nonzero(leaf[k])[0]
+        val[k][sel] = score_l[at:at + len(sel)]
+        mov[k][sel] = move_l[at:at + len(sel)]
+        cnt[k][sel] = nodes_l[at:at + len(sel)]
+        at += len(sel)
+    for k in range(len(leaf) - 1, 0, -1):
+        parent, move = nodes[k][2], nodes[k][3]
+        best = np.full(len(leaf[k - 1]), -1000, np.int64)
+        for j in range(len(parent)):   # children in ascending move order per parent (-1, the pass, is alone)
+            i = parent[j]
+            cnt[k - 1][i] += cnt[k][j]
+            if -val[k][j] > best[i]:
+                best[i] = -val[k][j]
+                mov[k - 1][i] = move[j]
+        inner = ~leaf[k - 1]
+        val[k - 1][inner] = best[inner]
+    return dict(score=torch.from_numpy(val[0].astype(np.int8)).to(dev), move=torch.from_numpy(mov[0].astype(np.int8)).to(dev),
+                nodes=torch.from_numpy(cnt[0]).to(dev), solved=torch.ones(n, dtype=torch.uint8, device=dev),
+                ctl=res["ctl"])

@@ -925,3 +925,46 @@ def rollout(own, opp, weights=None, seed=0, id_base=0, stream_id=0, uniforms=Non
                         want_turns, want_trace, out, throughput_hint, stream_id_dev)
     check(p.launch(), "iago_rollout")
     return p.result
+
+
+ENDGAME_MODES = {"exact": _lib.ENDGAME_EXACT, "wld": _lib.ENDGAME_WLD}
+ENDGAME_TIME_LIMIT_MS = 60000
+
+
+def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS,
+                  check_result=True):
+    """The exact value of every position under perfect play (iago_solve_endgame, include/iago_hip_serving.h).
+
+    own / opp: (n,) int64 CUDA tensors, own = side to move.  mode "exact": score = the final disc difference
+    #own - #opp (empty squares count for nobody); "wld": its sign only (much cheaper).  Returns a dict of device
+    tensors: score (n,) int8, move (n,) int8 = the lowest-indexed move reaching the score (-1: the side to move must
+    pass, -2: the game is over), nodes (n,) int64, solved (n,) uint8, ctl (4,) int32.
+    check_result (one host sync): raise IagoError when the launch gave up at time_limit_ms or refused a position
+    (own & opp != 0, more than max_empties empties); the result is the error's `result` attribute."""
+    if mode not in ENDGAME_MODES:
+        raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
+    n = own.numel()
+    if opp.numel() != n:
+        raise ValueError("own/opp sizes differ")
+    dev = own.device
+    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
+               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev))
+    a = _lib.EndgameArgs()
+    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
+    a.mode, a.max_empties, a.time_limit_ms = ENDGAME_MODES[mode], int(max_empties), int(time_limit_ms)
+    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
+    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
+    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
+    check(_lib.lib().iago_solve_endgame(C.byref(a), _stream()), "iago_solve_endgame")
+    if check_result:
+        gave_up, _, refused, _ = (int(v) for v in out["ctl"].tolist())
+        if gave_up or refused:
+            err = _lib.IagoError(
+                "iago_solve_endgame: %s" % ("gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
+                    time_limit_ms, n - int(out["solved"].sum().item()), n) if gave_up else
+                    "%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % (
+                        refused, max_empties)))
+            err.result = out
+            raise err
+    return out

@@ -34,7 +34,7 @@ def _softmax_like_reference(out):
 
 
 def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0, draws=None,
-             device="cuda"):
+             device="cuda", exact_empties=None):
     """n_games lockstep games.  stop_num: (n_games,) ints in [4, 64] (None: drawn uniformly
     from {4..63} like gen_value_data.py:14, from a generator seeded with `seed`).
     draws: replay mode for ONE game (parity tests): an iterator of the uniforms consumed, in
@@ -43,7 +43,14 @@ def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0,
 
     Returns dict: own/opp (B,) int64 recorded positions (own = the side to move there),
     z (B,) int8 result from that side's view (-1 also for dropped games), dropped (B,) bool,
-    color (B,) int8 colour to move at the recorded position, final_p1/final_p2, n_turns."""
+    color (B,) int8 colour to move at the recorded position, final_p1/final_p2, n_turns.
+    exact_empties = k (an int <= 20) adds exact labels: every kept recorded position with at most k empties is solved
+    (ops.solve_endgame, win / draw / loss) after the games; z_exact (B,) int8 = its result under perfect play from the
+    recorded side's view, exact (B,) bool = where z_exact applies (dropped games: False).  The other keys stay what a
+    call without it returns."""
+    if exact_empties is not None and (isinstance(exact_empties, bool) or not isinstance(exact_empties, int) or
+                                      not 0 <= exact_empties <= ops._lib.ENDGAME_MAX_EMPTIES):
+        raise ValueError("exact_empties must be None or an int in [0, 20], got %r" % (exact_empties,))
     B = n_games
     if draws is not None and B != 1:
         raise ValueError("replay mode (draws) plays one game")
@@ -146,8 +153,20 @@ def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0,
         raise ValueError("replay: the game consumed fewer draws than recorded")
     p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
     color = torch.where(t_rec % 2 == 0, torch.ones_like(z), torch.full_like(z, 2))
-    return dict(own=rec_own, opp=rec_opp, z=z, dropped=dropped, color=color, final_p1=p1,
-                final_p2=p2, n_turns=t, stop_num=stop)
+    out = dict(own=rec_own, opp=rec_opp, z=z, dropped=dropped, color=color, final_p1=p1,
+               final_p2=p2, n_turns=t, stop_num=stop)
+    if exact_empties is not None:
+        empties = torch.tensor([64 - bin(int(b)).count("1") for b in ops.tensor_to_bits(rec_own | rec_opp)],
+                               dtype=torch.int64, device=device)
+        exact = ~dropped & (empties <= exact_empties)
+        z_exact = torch.zeros(B, dtype=torch.int8, device=device)
+        rows = torch.nonzero(exact).reshape(-1)
+        if rows.numel():
+            r = ops.solve_endgame(rec_own[rows].contiguous(), rec_opp[rows].contiguous(), mode="wld",
+                                  max_empties=exact_empties)
+            z_exact[rows] = r["score"]
+        out.update(z_exact=z_exact, exact=exact)
+    return out
 
 
 class SelfPlay(object):

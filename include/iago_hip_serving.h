@@ -43,6 +43,49 @@ typedef struct iago_search_wave_args {
  */
 IAGO_API int iago_mcts_search_wave(const iago_mcts_search_args *args, const iago_search_wave_args *wave, void *stream);
 
+/* ------------------------------------------------------------------ exact endgame */
+
+#define IAGO_ENDGAME_EXACT 0          /* mode: the exact final disc difference */
+#define IAGO_ENDGAME_WLD 1            /* mode: its sign only (win / draw / loss) */
+#define IAGO_ENDGAME_MAX_EMPTIES 20   /* the largest max_empties */
+#define IAGO_ENDGAME_MAX_TIME_MS 600000
+#define IAGO_ENDGAME_CTL_WORDS 4
+
+typedef struct iago_endgame_args {
+    const uint64_t *own; /* [n] side to move (bit a = row*8+col) */
+    const uint64_t *opp; /* [n] its opponent */
+    int64_t n;
+    int32_t mode;          /* IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD */
+    int32_t max_empties;   /* 0 .. IAGO_ENDGAME_MAX_EMPTIES: sizes the search stack */
+    int32_t time_limit_ms; /* 1 .. IAGO_ENDGAME_MAX_TIME_MS: the launch gives up after this long on the device clock */
+    int32_t reserved0;     /* 0 */
+    int8_t *score;         /* [n] out */
+    int8_t *move;          /* [n] out */
+    int64_t *nodes;        /* [n] out: nodes visited */
+    uint8_t *solved;       /* [n] out: 1 = score and move are exact */
+    uint32_t *ctl;         /* [IAGO_ENDGAME_CTL_WORDS] cleared by the call; [0] != 0: gave up, [2]: positions refused */
+    int64_t reserved[4];   /* 0 */
+} iago_endgame_args;
+
+/*
+ * The exact value of n Othello positions under perfect play, one lane per position (negamax alpha-beta, no tables).
+ * Rules are the library's: a side with no legal move passes, the game ends when neither side can move (a full board
+ * included), and the score is #own - #opp at the end, empty squares counted for nobody (judge's count, so
+ * sign(score) is the reference's result z for the side to move).
+ *   - EXACT: score[i] = the negamax value in [-64, 64]; move[i] = the LOWEST-indexed move that reaches it (the
+ *     reference's first-maximum order).
+ *   - WLD: score[i] = its sign, found with a window (-1, 1) around 0 (much cheaper); move[i] = the lowest-indexed move
+ *     that reaches that outcome.
+ *   - move[i] is -1 when the side to move must pass, -2 when the game is over; nodes[i] counts the nodes visited.
+ * A position with own & opp != 0 or with more than max_empties empties is refused: solved[i] = 0, ctl[2] counts it.
+ * solved[] and ctl are cleared on `stream` before the launch, and score / move / nodes are meaningful where
+ * solved[i] = 1.  The launch stops on its own clock after time_limit_ms: then ctl[0] != 0 and every position it had
+ * not finished keeps solved[i] = 0, so a launch never hangs the device whatever it is given.  Host-side refusals
+ * (IAGO_ERR_INVALID, nothing launched): a null args / ctl, a null array with n > 0, n < 0, a mode outside the two, a
+ * max_empties or time_limit_ms out of range, reserved fields not 0.
+ */
+IAGO_API int iago_solve_endgame(const iago_endgame_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

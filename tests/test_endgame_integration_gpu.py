@@ -1,0 +1,117 @@
+"""The exact endgame solver behind the library's users: MCTS(solve_empties=k) (get_move plays the solver's move at <= k
+empties and searches as before above), a front-end game with it, and value_self_play.generate(exact_empties=k)
+(exact win / draw / loss labels next to the unchanged self-play results)."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as orc
+
+from . import endgame_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def nets():
+    from iago_amd import network, ops
+    policy = network.SLPolicy().load_npz(os.path.join(GOLDEN, "sl_model.npz")).cuda().eval()
+    value = network.Value().load_npz(os.path.join(GOLDEN, "value_model.npz")).cuda().eval()
+    rollout = network.RolloutPolicy().load_npz(os.path.join(GOLDEN, "rollout_model.npz")).eval()
+    return policy, value, ops.RolloutWeights(*rollout.kernel_weights())
+
+
+def _mcts(nets, **kw):
+    from iago_amd.MCTS import MCTS
+    policy, value, rw = nets
+    return MCTS(policy_net=policy, value_net=value, rollout_weights=rw, n_sims=32, seed=9, capacity=8192, **kw)
+
+
+def _states(n, seed, lo, hi):
+    own, opp = ref.late_positions(n, seed, lo, hi)
+    out = []
+    for a, b in zip(own, opp):
+        if ref.bit_legal(int(a), int(b)):   # get_move is asked only where there is a move
+            out.append((orc.bits_to_state(int(a), int(b)), 1, int(a), int(b)))
+    return out
+
+
+def test_mcts_plays_the_solver_move_at_few_empties(nets):
+    m = _mcts(nets, solve_empties=10)
+    for state, color, a, b in _states(24, 71, 1, 10):
+        before = m.n_leaf_evals
+        move = m.get_move(state, color)
+        assert move == ref.solve_bits(a, b)[1]
+        assert m.n_leaf_evals == before
+    assert m.n_solved > 0
+
+
+def test_mcts_searches_as_before_above_k(nets):
+    with_k, plain = _mcts(nets, solve_empties=8), _mcts(nets)
+    for state, color, _, _ in _states(6, 72, 12, 20):
+        assert with_k.get_move(state, color) == plain.get_move(state, color)
+        assert with_k.n_leaf_evals == plain.n_leaf_evals
+    assert with_k.n_solved == 0
+
+
+def test_mcts_refuses_bad_solve_empties(nets):
+    for bad in (-1, 21, 2.5, True):
+        with pytest.raises(ValueError):
+            _mcts(nets, solve_empties=bad)
+
+
+def test_front_end_game_with_the_solver(nets):
+    from iago_amd import game as game_mod
+    from iago_amd.game import Game
+    policy = nets[0]
+    m = _mcts(nets, solve_empties=10)
+    lines = []
+    g = Game(True, model=policy, mcts=m, date="2000-01-02-00-00", out=lines.append,
+             choice=np.random.RandomState(3).choice)
+    jd = game_mod.play(g, True)
+    assert g.stone_num >= 64 and jd in lines
+    assert m.n_solved > 0
+    # the gamelog replays through the oracle: every move legal, the game over at the end
+    s, color = orc.initial_state(), 1
+    for line in g.gamelog.splitlines():
+        hit = re.match(r"\[\d+\].*: (?:\[(\d+), (\d+)\]|Pass)$", line)
+        if not hit:
+            continue
+        if hit.group(1) is None:
+            assert orc.legal_actions(s, color) == []
+        else:
+            a = (int(hit.group(1)) - 1) * 8 + int(hit.group(2)) - 1
+            assert a in orc.legal_actions(s, color)
+            orc.place_stone(s, a, color)
+        color = 3 - color
+    assert orc.legal_actions(s, 1) == [] and orc.legal_actions(s, 2) == []
+
+
+def test_value_labels_exact(nets):
+    from iago_amd import ops, value_self_play
+    policy = nets[0]
+    stop = torch.from_numpy(np.random.RandomState(4).randint(50, 64, 256))
+    plain = value_self_play.generate(policy, policy, 256, stop_num=stop, seed=11)
+    lab = value_self_play.generate(policy, policy, 256, stop_num=stop, seed=11, exact_empties=10)
+    for k, v in plain.items():
+        if isinstance(v, torch.Tensor):
+            assert torch.equal(v, lab[k]), k
+        else:
+            assert v == lab[k], k
+    exact, z_exact = lab["exact"].cpu().numpy(), lab["z_exact"].cpu().numpy()
+    own, opp = ops.tensor_to_bits(lab["own"]), ops.tensor_to_bits(lab["opp"])
+    dropped = lab["dropped"].cpu().numpy()
+    assert exact.sum() > 50 and not (exact & dropped).any()
+    for i in range(256):
+        if exact[i]:
+            assert ref.empties(own[i], opp[i]) <= 10
+            assert int(z_exact[i]) == ref.solve_bits(own[i], opp[i], wld=True)[0], i
+        elif not dropped[i]:
+            assert ref.empties(own[i], opp[i]) > 10
+    with pytest.raises(ValueError):
+        value_self_play.generate(policy, policy, 4, exact_empties=21)

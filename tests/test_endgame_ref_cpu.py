@@ -1,0 +1,135 @@
+"""The endgame references of tests/endgame_ref.py against each other and on hand-built positions, and the host side
+of iago_solve_endgame (its header entry, its refusals before any device work).  No GPU."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+
+from . import endgame_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def sq(r, c):
+    return 1 << (8 * r + c)
+
+
+def test_bitboard_twin_agrees_with_oracle_rules():
+    own, opp = ref.late_positions(240, 3, 0, 8)
+    kinds = set()
+    for a, b in zip(own, opp):
+        state = orc.bits_to_state(int(a), int(b))   # own = colour 1
+        for wld in (False, True):
+            want = ref.solve_state(state, 1, wld)
+            assert ref.solve_bits(a, b, wld) == want, (hex(int(a)), hex(int(b)), wld)
+        kinds.add(min(want[1], 0))
+        assert ref.bit_legal(int(a), int(b)) == orc.actions_to_mask(orc.legal_actions(state, 1))
+    assert 0 in kinds and -2 in kinds
+
+
+def test_full_board():
+    own = 0xFFFFFFFF00000000 | 0xFF
+    opp = 0xFFFFFFFFFFFFFFFF & ~own
+    assert ref.solve_bits(own, opp) == (40 - 24, -2)
+    assert ref.solve_state(orc.bits_to_state(own, opp), 1) == (16, -2)
+    assert ref.solve_bits(opp, own, wld=True) == (-1, -2)
+
+
+def test_one_empty_only_one_side_can_take():
+    # a0 empty; only colour 1 (own) brackets it (a1 opponent, a2 own); the opponent cannot take a0
+    full = 0xFFFFFFFFFFFFFFFF
+    opp = sq(1, 0)
+    own = full & ~sq(0, 0) & ~opp
+    assert ref.solve_bits(own, opp) == (64, 0)          # takes a0 and flips a1: 64 - 0
+    # the side that cannot take it passes, the other one takes it
+    score, move = ref.solve_bits(opp, own)
+    assert (score, move) == (-64, -1)
+    assert ref.solve_state(orc.bits_to_state(opp, own), 1) == (-64, -1)
+
+
+def test_forced_pass_then_opponent_moves():
+    # own: b1 alone; the opponent: c1..h1.  Own has no move (nothing to bracket), the opponent takes a1 over b1,
+    # then nobody can move: 0 - 8 from own's view, after a pass
+    own = sq(0, 1)
+    opp = sum(sq(0, c) for c in range(2, 8))
+    assert ref.bit_legal(own, opp) == 0 and ref.bit_legal(opp, own) == sq(0, 0)
+    assert ref.solve_bits(own, opp) == (-8, -1)
+    assert ref.solve_bits(opp, own) == (8, 0)
+    assert ref.solve_state(orc.bits_to_state(own, opp), 1) == (-8, -1)
+    assert ref.solve_bits(own, opp, wld=True) == (-1, -1)
+
+
+def test_game_already_over():
+    own, opp = sq(3, 3), sq(5, 5)       # nobody can move: 1 - 1 = 0, many empties
+    assert ref.solve_bits(own, opp) == (0, -2)
+    assert ref.solve_bits(own | sq(0, 0), opp) == (1, -2)
+    assert ref.solve_bits(own | sq(0, 0), opp, wld=True) == (1, -2)
+
+
+def test_tie_goes_to_the_lowest_index():
+    # own at d1, e1 symmetric around the opponent run: two moves of equal value
+    own = sq(0, 3)
+    opp = sq(0, 2) | sq(0, 4)
+    moves = ref.BitRules.moves((own, opp))
+    assert moves == [1, 5]
+    vals = [-ref.negamax(ref.BitRules, ref.BitRules.play((own, opp), m), -ref.INF, ref.INF, False) for m in moves]
+    assert vals[0] == vals[1]
+    assert ref.solve_bits(own, opp) == (vals[0], 1)
+    assert ref.solve_state(orc.bits_to_state(own, opp), 1) == (vals[0], 1)
+
+
+def test_serving_header_lists_the_solver():
+    from iago_amd import _lib
+    text = open(os.path.join(ROOT, "include", "iago_hip_serving.h")).read()
+    assert sorted(set(re.findall(r"IAGO_API[^;(]*?\b(iago_\w+)\s*\(", text))) == sorted(_lib.SERVING_SYMBOLS)
+    assert "iago_solve_endgame" in _lib.SERVING_SYMBOLS
+    assert C.sizeof(_lib.EndgameArgs) == 8 * 3 + 4 * 4 + 8 * 5 + 8 * 4
+    for name in ("IAGO_ENDGAME_EXACT 0", "IAGO_ENDGAME_WLD 1", "IAGO_ENDGAME_MAX_EMPTIES 20",
+                 "IAGO_ENDGAME_MAX_TIME_MS 600000", "IAGO_ENDGAME_CTL_WORDS 4"):
+        assert re.search(r"#define\s+" + name.replace(" ", r"\s+") + r"\b", text), name
+
+
+def test_host_side_refusals():
+    from iago_amd import _lib, build
+    build.build()
+    L = _lib.lib()
+    buf = (C.c_uint64 * 8)()
+    ctl = (C.c_uint32 * 4)()
+
+    def args(**kw):
+        a = _lib.EndgameArgs()
+        for f in ("own", "opp", "score", "move", "nodes", "solved"):
+            setattr(a, f, C.addressof(buf))
+        a.ctl = C.addressof(ctl)
+        a.n, a.mode, a.max_empties, a.time_limit_ms = 1, 0, 20, 1000
+        for k, v in kw.items():
+            if k == "reserved":
+                a.reserved[1] = v
+            else:
+                setattr(a, k, v)
+        return a
+
+    assert L.iago_solve_endgame(None, None) == -1
+    for kw in (dict(own=None), dict(opp=None), dict(score=None), dict(move=None), dict(nodes=None),
+               dict(solved=None), dict(ctl=None), dict(n=-1), dict(mode=2), dict(mode=-1), dict(max_empties=21),
+               dict(max_empties=-1), dict(time_limit_ms=0), dict(time_limit_ms=600001), dict(reserved0=1),
+               dict(reserved=7)):
+        assert L.iago_solve_endgame(C.byref(args(**kw)), None) == -1, kw   # IAGO_ERR_INVALID
+        assert b"iago_solve_endgame" in L.iago_last_error()
+
+
+def test_python_entry_points_refuse_bad_options():
+    import torch
+    from iago_amd import _lib, engine, ops
+    t = torch.zeros(2, dtype=torch.int64)
+    with pytest.raises(ValueError):
+        ops.solve_endgame(t, t, mode="best")
+    with pytest.raises(_lib.IagoError):
+        ops.solve_endgame(t, t)                              # CPU tensors: no CPU fallback
+    for bad in (-1, 1.5, True):
+        with pytest.raises(ValueError):
+            engine.solve_endgame(t, t, split_depth=bad)

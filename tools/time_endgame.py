@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Speed of the exact endgame solver (ops.solve_endgame / engine.solve_endgame, include/iago_hip_serving.h).
+
+    python tools/time_endgame.py [--batch 4096] [--batch-empties 8,10,12,14,16] [--single-empties 12,14,16,18]
+                                 [--splits 0,1,2,3,4] [--reps 5] [--limit-ms 20000]
+
+Positions: seeded SLPolicy-vs-SLPolicy games (rl_self_play.play_batch, the shipped sl_model.npz), the recorded
+positions of colour 1 at exactly E empties.  Prints one JSON line per measurement:
+  * batch: `--batch` positions at E empties in one launch, both modes -- positions/s and nodes/s over HIP events;
+  * single: one position at E empties through engine.solve_endgame(split_depth=k) -- the median wall time of `--reps`
+    positions (host split and minimax included), its nodes.
+A launch that gives up at --limit-ms is reported as such."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def positions_at(policy, empties, n, seed):
+    """n positions with exactly `empties` empties from seeded policy-vs-policy games (own = colour 1 to move)."""
+    from iago_amd import ops, rl_self_play
+    own, opp, k = [], [], 0
+    while len(own) < n:
+        r = rl_self_play.play_batch(policy, policy, 1024, seed=seed + k, game_id_base=1024 * k)
+        k += 1
+        o, p = ops.tensor_to_bits(r["own"]), ops.tensor_to_bits(r["opp"])
+        for g in range(o.shape[1]):
+            for t in range(o.shape[0]):
+                if o[t, g] | p[t, g] and 64 - bin(int(o[t, g] | p[t, g])).count("1") == empties:
+                    own.append(o[t, g])
+                    opp.append(p[t, g])
+                    break
+    return np.array(own[:n], np.uint64), np.array(opp[:n], np.uint64)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--batch-empties", default="8,10,12,14,16")
+    ap.add_argument("--single-empties", default="12,14,16,18")
+    ap.add_argument("--splits", default="0,1,2,3,4")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--limit-ms", type=int, default=20000)
+    ap.add_argument("--seed", type=int, default=7)
+    args = ap.parse_args()
+    from iago_amd import _lib, engine, network, ops
+    policy = network.SLPolicy().load_npz(os.path.join(GOLDEN, "sl_model.npz")).cuda().eval()
+    ints = lambda s: [int(x) for x in s.split(",") if x]   # noqa: E731
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    w = positions_at(policy, 6, 64, args.seed)
+    ops.solve_endgame(ops.bits_to_tensor(w[0]), ops.bits_to_tensor(w[1]))   # warm-up: code object, allocator
+    for E in ints(args.batch_empties):
+        o, p = positions_at(policy, E, args.batch, args.seed + 100 * E)
+        to, tp = ops.bits_to_tensor(o), ops.bits_to_tensor(p)
+        for mode in ("exact", "wld"):
+            torch.cuda.synchronize()
+            e0.record()
+            r = ops.solve_endgame(to, tp, mode=mode, max_empties=E, time_limit_ms=args.limit_ms, check_result=False)
+            e1.record()
+            torch.cuda.synchronize()
+            s = e0.elapsed_time(e1) / 1e3
+            nodes = int(r["nodes"].sum().item())
+            solved = int(r["solved"].sum().item())
+            print(json.dumps(dict(tool="time_endgame", kind="batch", empties=E, mode=mode, n=len(o), solved=solved,
+                                  gave_up=bool(r["ctl"][0].item()), s=round(s, 4),
+                                  positions_per_s=round(solved / s, 1), nodes=nodes, mnodes_per_s=round(nodes / s / 1e6, 2),
+                                  max_nodes=int(r["nodes"].max().item()))), flush=True)
+    for E in ints(args.single_empties):
+        o, p = positions_at(policy, E, args.reps, args.seed + 1000 + E)
+        for k in ints(args.splits):
+            times, nodes, gave_up = [], [], False
+            for i in range(len(o)):
+                to, tp = ops.bits_to_tensor(o[i:i + 1]), ops.bits_to_tensor(p[i:i + 1])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                try:
+                    r = engine.solve_endgame(to, tp, split_depth=k, time_limit_ms=args.limit_ms)
+                    torch.cuda.synchronize()
+                except _lib.IagoError:
+                    gave_up = True
+                    break
+                times.append(time.perf_counter() - t0)
+                nodes.append(int(r["nodes"][0].item()))
+            print(json.dumps(dict(tool="time_endgame", kind="single", empties=E, split_depth=k, reps=len(times),
+                                  gave_up=gave_up, median_ms=round(1e3 * float(np.median(times)), 2) if times else None,
+                                  max_ms=round(1e3 * max(times), 2) if times else None,
+                                  median_nodes=int(np.median(nodes)) if nodes else None)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
