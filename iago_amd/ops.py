@@ -931,6 +931,24 @@ ENDGAME_MODES = {"exact": _lib.ENDGAME_EXACT, "wld": _lib.ENDGAME_WLD}
 ENDGAME_TIME_LIMIT_MS = 60000
 
 
+def _check_endgame_ctl(out, n, max_empties, time_limit_ms):
+    """Raise IagoError (with the result as its `result` attribute) unless the launch finished every position."""
+    gave_up, _, refused, overflow = (int(v) for v in out["ctl"].tolist())
+    if not (gave_up or refused or overflow):
+        return
+    if overflow:
+        what = ("a position needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped "
+                "with solved = 0 and its outputs unwritten" % max_empties)
+    elif gave_up:
+        what = "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
+            time_limit_ms, n - int(out["solved"].sum().item()), n)
+    else:
+        what = "%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % (refused, max_empties)
+    err = _lib.IagoError("iago_solve_endgame: " + what)
+    err.result = out
+    raise err
+
+
 def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS,
                   check_result=True):
     """The exact value of every position under perfect play (iago_solve_endgame, include/iago_hip_serving.h).
@@ -939,8 +957,9 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     #own - #opp (empty squares count for nobody); "wld": its sign only (much cheaper).  Returns a dict of device
     tensors: score (n,) int8, move (n,) int8 = the lowest-indexed move reaching the score (-1: the side to move must
     pass, -2: the game is over), nodes (n,) int64, solved (n,) uint8, ctl (4,) int32.
-    check_result (one host sync): raise IagoError when the launch gave up at time_limit_ms or refused a position
-    (own & opp != 0, more than max_empties empties); the result is the error's `result` attribute."""
+    check_result (one host sync): raise IagoError when the launch gave up at time_limit_ms, refused a position
+    (own & opp != 0, more than max_empties empties) or dropped one for want of stack (ctl[3]); the result is the
+    error's `result` attribute."""
     if mode not in ENDGAME_MODES:
         raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
     n = own.numel()
@@ -958,13 +977,5 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     a.ctl = _dev(out["ctl"], torch.int32, "ctl")
     check(_lib.lib().iago_solve_endgame(C.byref(a), _stream()), "iago_solve_endgame")
     if check_result:
-        gave_up, _, refused, _ = (int(v) for v in out["ctl"].tolist())
-        if gave_up or refused:
-            err = _lib.IagoError(
-                "iago_solve_endgame: %s" % ("gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
-                    time_limit_ms, n - int(out["solved"].sum().item()), n) if gave_up else
-                    "%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % (
-                        refused, max_empties)))
-            err.result = out
-            raise err
+        _check_endgame_ctl(out, n, max_empties, time_limit_ms)
     return out

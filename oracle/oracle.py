@@ -16,8 +16,8 @@ _SO = os.path.join(_HERE, "_build", "liboracle.so")
 
 def build(force=False):
     """Compile the oracle with gcc (idempotent)."""
-    src = os.path.join(_HERE, "othello_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, name) for name in ("othello_oracle.c", "endgame_oracle.c")]
+    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(src) for src in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
     return _SO
 
@@ -71,6 +71,11 @@ def lib():
         L.orc_node_update_Q.restype = C.c_float
         L.orc_leaf_value.argtypes = [C.c_float, C.c_float, C.c_int]
         L.orc_leaf_value.restype = C.c_float
+        i64p = C.POINTER(C.c_int64)
+        L.orc_endgame_solve.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int64, C.c_int, ip, i64p]
+        L.orc_endgame_solve.restype = C.c_int
+        L.orc_endgame_root_values.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int64, ip, ip, i64p]
+        L.orc_endgame_root_values.restype = C.c_int
         _lib = L
     return _lib
 
@@ -221,6 +226,36 @@ def node_update_Q(Q, leaf_value, n_after):
 
 def leaf_value(lmbda, v, z):
     return np.float32(lib().orc_leaf_value(float(lmbda), float(np.float32(v)), int(z)))
+
+
+# ------------------------------------------------------- exact endgame
+ENDGAME_ABORTED = -1000
+
+
+def solve_endgame(own, opp, wld=False, limit=0, fastest_root=False):
+    """(score, move, nodes) of the position (own = the side to move, bit a = row*8+col) under perfect play, by the C
+    reference solver (oracle/endgame_oracle.c), with the contract of iago_solve_endgame: a side without a move
+    passes, the game ends when neither can move, score = #own - #opp with the empties for nobody (wld: its sign),
+    move = the lowest-indexed move reaching the score, -1 = must pass, -2 = game over.  limit > 0: give up after
+    that many nodes and return None.  fastest_root: the root tries its moves fewest-replies-first like the inner
+    nodes (and keeps ties of a lower index exact): the same (score, move), the node count of a solver with such a
+    root."""
+    move, nodes = C.c_int(0), C.c_int64(0)
+    s = lib().orc_endgame_solve(int(own), int(opp), int(bool(wld)), int(limit), int(bool(fastest_root)),
+                                C.byref(move), C.byref(nodes))
+    if s == ENDGAME_ABORTED:
+        return None
+    return s, move.value, nodes.value
+
+
+def root_values(own, opp, wld=False, limit=0):
+    """{move: exact value} of every legal move of the side to move, each searched with the full window ({} when it
+    has none); None when `limit` > 0 nodes did not suffice."""
+    moves, values, nodes = (C.c_int * 64)(), (C.c_int * 64)(), C.c_int64(0)
+    n = lib().orc_endgame_root_values(int(own), int(opp), int(bool(wld)), int(limit), moves, values, C.byref(nodes))
+    if n == ENDGAME_ABORTED:
+        return None
+    return {moves[i]: values[i] for i in range(n)}
 
 
 # ----------------------------------------------------- bitboard bridging

@@ -1,6 +1,11 @@
 """The exact endgame solver (iago_solve_endgame, ops.solve_endgame, engine.solve_endgame) on the device: exact against
 the Python references of tests/endgame_ref.py where they are fast enough, self-consistent (negamax over the children,
-WLD = sign of exact, independent of the batch and of the root split) where they are not, and its refusals and give-up."""
+WLD = sign of exact, independent of the batch and of the root split) where they are not, and its refusals and give-up.
+
+What is pinned to what: the oracle-rules negamax (endgame_ref.solve_state) holds the bitboard twin (solve_bits) on the
+CPU up to 8 empties; the twin holds the kernel here up to 10; the C reference (oracle/endgame_oracle.c, pinned to both
+on the CPU) holds it from 11 to 20 empties through tests/golden/endgame_deep.json, rows of at most 2 M reference nodes,
+in tests/test_endgame_deep_gpu.py.  The 12 - 16 consistency test below stays a self-check."""
 import numpy as np
 import pytest
 import torch

@@ -115,3 +115,41 @@ def test_value_labels_exact(nets):
             assert ref.empties(own[i], opp[i]) > 10
     with pytest.raises(ValueError):
         value_self_play.generate(policy, policy, 4, exact_empties=21)
+
+
+def test_mcts_plays_the_reference_move_up_to_14_empties(nets):
+    m = _mcts(nets, solve_empties=14)
+    states = _states(16, 73, 11, 14)
+    assert len(states) >= 12 and {ref.empties(a, b) for _, _, a, b in states} == {11, 12, 13, 14}
+    for state, color, a, b in states:
+        before = m.n_leaf_evals
+        move = m.get_move(state, color)
+        assert move == orc.solve_endgame(a, b)[1], (hex(a), hex(b))
+        assert m.n_leaf_evals == before
+    assert m.n_solved == len(states)
+
+
+def test_value_labels_exact_up_to_14_empties(nets):
+    from iago_amd import ops, value_self_play
+    policy = nets[0]
+    stop = torch.from_numpy(np.random.RandomState(5).randint(46, 64, 256))
+    plain = value_self_play.generate(policy, policy, 256, stop_num=stop, seed=12)
+    lab = value_self_play.generate(policy, policy, 256, stop_num=stop, seed=12, exact_empties=14)
+    for k, v in plain.items():
+        if isinstance(v, torch.Tensor):
+            assert torch.equal(v, lab[k]), k
+        else:
+            assert v == lab[k], k
+    exact, z_exact = lab["exact"].cpu().numpy(), lab["z_exact"].cpu().numpy()
+    own, opp = ops.tensor_to_bits(lab["own"]), ops.tensor_to_bits(lab["opp"])
+    dropped = lab["dropped"].cpu().numpy()
+    assert exact.sum() > 50 and not (exact & dropped).any()
+    deep = 0
+    for i in range(256):
+        if exact[i]:
+            assert ref.empties(own[i], opp[i]) <= 14
+            assert int(z_exact[i]) == orc.solve_endgame(own[i], opp[i], wld=True)[0], i
+            deep += ref.empties(own[i], opp[i]) > 10
+        elif not dropped[i]:
+            assert ref.empties(own[i], opp[i]) > 14
+    assert deep > 20   # the labels above the earlier test's 10 empties are really there

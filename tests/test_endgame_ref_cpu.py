@@ -133,3 +133,118 @@ def test_python_entry_points_refuse_bad_options():
     for bad in (-1, 1.5, True):
         with pytest.raises(ValueError):
             engine.solve_endgame(t, t, split_depth=bad)
+
+
+# ------------------------------------------------------------------ the C reference (oracle/endgame_oracle.c)
+def test_c_reference_equals_both_python_references():
+    own, opp = ref.late_positions(520, 7, 0, 9)
+    kinds, counts = set(), set()
+    for a, b in zip(own, opp):
+        state = orc.bits_to_state(int(a), int(b))
+        for wld in (False, True):
+            got = orc.solve_endgame(a, b, wld)[:2]
+            assert got == ref.solve_bits(a, b, wld), (hex(int(a)), hex(int(b)), wld)
+            assert got == ref.solve_state(state, 1, wld), (hex(int(a)), hex(int(b)), wld)
+        kinds.add(min(got[1], 0))
+        counts.add(ref.empties(a, b))
+    assert kinds == {0, -1, -2} and counts == set(range(10))
+
+
+def test_c_reference_on_the_hand_built_positions():
+    full = 0xFFFFFFFFFFFFFFFF
+    own = 0xFFFFFFFF00000000 | 0xFF
+    assert orc.solve_endgame(own, full & ~own)[:2] == (16, -2)
+    assert orc.solve_endgame(full & ~own, own, wld=True)[:2] == (-1, -2)
+    opp = sq(1, 0)
+    own = full & ~sq(0, 0) & ~opp
+    assert orc.solve_endgame(own, opp)[:2] == (64, 0)
+    assert orc.solve_endgame(opp, own)[:2] == (-64, -1)
+    own, opp = sq(0, 1), sum(sq(0, c) for c in range(2, 8))
+    assert orc.solve_endgame(own, opp)[:2] == (-8, -1)
+    assert orc.solve_endgame(opp, own)[:2] == (8, 0)
+    assert orc.solve_endgame(own, opp, wld=True)[:2] == (-1, -1)
+    own, opp = sq(3, 3), sq(5, 5)
+    assert orc.solve_endgame(own, opp)[:2] == (0, -2)
+    assert orc.solve_endgame(own | sq(0, 0), opp)[:2] == (1, -2)
+    assert orc.solve_endgame(own | sq(0, 0), opp, wld=True)[:2] == (1, -2)
+    own, opp = sq(0, 3), sq(0, 2) | sq(0, 4)
+    assert orc.root_values(own, opp) == {1: ref.solve_bits(own, opp)[0], 5: ref.solve_bits(own, opp)[0]}
+    assert orc.solve_endgame(own, opp)[:2] == ref.solve_bits(own, opp) and orc.solve_endgame(own, opp)[1] == 1
+    # a node budget that does not suffice is reported, not answered
+    o, p = ref.late_positions(1, 9, 12, 12)
+    assert orc.solve_endgame(o[0], p[0], limit=10) is None and orc.root_values(o[0], p[0], limit=10) is None
+
+
+def test_c_root_values_equal_full_window_negamax():
+    own, opp = ref.late_positions(120, 8, 1, 8)
+    seen_tie = 0
+    for a, b in zip(own, opp):
+        a, b = int(a), int(b)
+        for wld in (False, True):
+            want = {m: -ref.negamax(ref.BitRules, ref.BitRules.play((a, b), m), -ref.INF, ref.INF, wld)
+                    for m in ref.BitRules.moves((a, b))}
+            got = orc.root_values(a, b, wld)
+            assert got == want, (hex(a), hex(b), wld)
+            if want:
+                s, m, _ = orc.solve_endgame(a, b, wld)
+                assert s == max(want.values()) and m == min(k for k, v in want.items() if v == s)
+                seen_tie += sum(1 for v in want.values() if v == s) > 1
+    assert seen_tie > 10
+
+
+# ------------------------------------------------------------------ the committed fixture of deep positions
+@pytest.fixture(scope="module")
+def deep_fixture():
+    from .conftest import load_json
+    return load_json("endgame_deep.json")
+
+
+def test_deep_fixture_families_and_row_counts(deep_fixture):
+    from . import endgame_families as fam
+    fam.check_fixture(deep_fixture)
+    # "filled" says where the sparse boards make up for random games that are too heavy under the cap
+    for e, f in deep_fixture["filled"].items():
+        n = sum(1 for r in deep_fixture["rows"] if r["family"] == "sparse" and r["empties"] == int(e))
+        assert n == f["sparse"] and n + min(f["random_exact"], f["random_wld"]) >= deep_fixture["rows_min"]
+
+
+def test_deep_fixture_is_what_the_reference_computes(deep_fixture):
+    """A seeded sample of the rows the reference solves fast (<= 300 k nodes), re-solved: identical, nodes included."""
+    rows = [r for r in deep_fixture["rows"] if all(r[m] is None or max(r[m][2:]) <= 300000 for m in ("exact", "wld"))]
+    assert len(rows) >= 100
+    rs = np.random.RandomState(17)
+    for i in rs.choice(len(rows), 120, replace=False):
+        r = rows[i]
+        for mode in ("exact", "wld"):
+            if r[mode]:
+                again = orc.solve_endgame(r["own"], r["opp"], mode == "wld")
+                ordered = orc.solve_endgame(r["own"], r["opp"], mode == "wld", fastest_root=True)
+                assert again[:2] == ordered[:2] and list(again) + [ordered[2]] == r[mode], (i, mode)
+        if r["values"]:
+            assert {str(m): v for m, v in orc.root_values(r["own"], r["opp"]).items()} == r["values"], i
+
+
+def test_symmetry_helpers_are_the_boards_symmetries():
+    from . import endgame_families as fam
+    o, p = ref.late_positions(6, 19, 4, 7)
+    for a, b in zip(o, p):
+        vals = orc.root_values(a, b)
+        for k in range(8):
+            ta, tb = fam.sym_bits(k, a), fam.sym_bits(k, b)
+            assert bin(ta).count("1") == bin(int(a)).count("1")
+            assert orc.root_values(ta, tb) == {fam.sym_move(k, m): v for m, v in vals.items()}
+    assert len({tuple(fam.sym_move(k, a) for a in range(64)) for k in range(8)}) == 8
+
+
+def test_solve_endgame_raises_when_the_stack_word_is_set():
+    """ops.solve_endgame's check of ctl (host side only: a faked ctl, no launch)."""
+    import torch
+    from iago_amd import _lib, ops
+    out = dict(solved=torch.tensor([1, 0, 1], dtype=torch.uint8), ctl=torch.tensor([0, 3, 0, 0], dtype=torch.int32))
+    ops._check_endgame_ctl(out, 3, 12, 1000)                      # a clean launch: nothing raised
+    for ctl, what in (([0, 3, 0, 1], "stack"), ([1, 3, 0, 0], "gave up"), ([0, 3, 2, 0], "refused"),
+                      ([1, 3, 1, 1], "stack")):
+        out["ctl"] = torch.tensor(ctl, dtype=torch.int32)
+        with pytest.raises(_lib.IagoError, match=what) as e:
+            ops._check_endgame_ctl(out, 3, 12, 1000)
+        assert e.value.result is out
