@@ -235,6 +235,7 @@ class BatchedMCTS(object):
         self._fresh_count = torch.zeros(1, dtype=torch.int32, **kw)
         self._value_total = torch.zeros(1, dtype=torch.int64, **kw)  # value-net evaluations, on the device
         self._value_key = None
+        self._vtable = None   # (the persistent search's position table, where it keeps one)
         self._policy_key = None
         self.fused_leaf_eval = os.environ.get("IAGO_FUSED_LEAF_EVAL", "1") != "0"
         self.cur_node = torch.zeros(ns, dtype=torch.int32, **kw)
@@ -1243,6 +1244,19 @@ class BatchedMCTS(object):
             ev.append((e0, e1))
         self._ps_keep = (keep_v, keep_p, ro, va, pa, own, opp, active, game)   # alive until the next launch
 
+    def _forget_stale_values(self):
+        """The stored values belong to the weights that computed them: once the value net's parameters have changed,
+        the values in the nodes and the position table are forgotten.  Before every launch that reads them."""
+        if not self.value_cache:
+            return
+        key = tuple((q.data_ptr(), q._version) for q in self.value_fn.parameters())
+        if key != self._value_key:
+            if self._value_key is not None:
+                self.tree.v.fill_(float("nan"))
+                if self._vtable is not None:
+                    self._vtable.zero_()
+            self._value_key = key
+
     def search_counts(self, active):
         """Device tensor int64[2]: games in `active`, nodes of the fullest pool -- what search()
         reads back before it starts (a caller that batches its readbacks passes them in)."""
@@ -1260,15 +1274,8 @@ class BatchedMCTS(object):
             # playout, whatever the other games of the batch do at that turn)
             self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
             return
+        self._forget_stale_values()
         if self.value_cache:
-            # the stored values belong to the weights that computed them
-            key = tuple((q.data_ptr(), q._version) for q in self.value_fn.parameters())
-            if key != self._value_key:
-                if self._value_key is not None:
-                    self.tree.v.fill_(float("nan"))
-                    if getattr(self, "_vtable", None) is not None:
-                        self._vtable.zero_()
-                self._value_key = key
             # (the descent appends to the fresh-leaf list through this count and the backup clears
             # it: a playout aborted between the two must not leave a stale count behind)
             self._fresh_count.zero_()
@@ -1483,14 +1490,46 @@ def _end_turns(valid):
 
 
 class SelfPlayEngine(object):
-    """Lockstep PV-MCTS self-play: both colours search the shared tree, moves
-    are the most visited children, passes advance the tree with -1
-    (game.py:117-142 turn structure, both sides driven by MCTS.get_move)."""
+    """Whole games on the B boards of a BatchedMCTS, three ways.  play(): lockstep PV-MCTS self-play -- both colours
+    search the shared tree, moves are the most visited children, passes advance the tree with -1 (game.py:117-142 turn
+    structure, both sides driven by MCTS.get_move).  play_stream(): n_games such games through the B slots.
+    play_match(): PV-MCTS against the SL policy (game.py --auto).  Two paths behind them, the same games record for
+    record: ONE launch of the persistent search that walks every game through its own turns (_play_persistent, wherever
+    _whole_games_in_one_launch allows it), and the turn loop (_play_turns: a search and a host readback per turn, self-play
+    being the match in which every game is searched and no move is drawn or forced), which is also the replay of a batch
+    whose launch filled a pool up (n_replayed counts those)."""
 
     def __init__(self, mcts, max_turns=_lib.IAGO_MAX_TURNS):
         self.mcts = mcts
         self.B = mcts.n_games
         self.max_turns = max_turns
+        self.n_replayed = 0   # batches replayed through the turn loop
+
+    def _start_boards(self, n, handicap=None):
+        """(own, opp) of n games at the opening; handicap: (n,) int64 bit masks of extra colour-2 stones."""
+        dev = self.mcts.cur_own.device
+        own = torch.full((n,), START_OWN, dtype=torch.int64, device=dev)
+        opp = torch.full((n,), START_OPP, dtype=torch.int64, device=dev)
+        return own, opp if handicap is None else opp | handicap
+
+    def _new_records(self, B):
+        """The record tensors of B games, max_turns rows each, by their SelfPlayResult names."""
+        T, dev = self.max_turns, self.mcts.cur_own.device
+        return dict(own=torch.zeros((T, B), dtype=torch.int64, device=dev),
+                    opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
+                    pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev),
+                    valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
+                    move=torch.full((T, B), -1, dtype=torch.int8, device=dev))
+
+    def _finish(self, res, p1, p2, t, launches, game_turns=None):
+        """What every result ends with: the header of a batch of t turns and its final boards (colour 1's stones,
+        colour 2's), judged.  game_turns: (B,) the turn at which each game ended -- the one-launch path records them."""
+        res.game_id_base = self.mcts.game_id_base
+        res.n_turns, res.launches, res.game_turns = t, launches, game_turns
+        res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
+        res.z = ops.judge(p1, p2)
+        res.final_p1, res.final_p2 = p1, p2
+        return res
 
     def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
@@ -1498,32 +1537,22 @@ class SelfPlayEngine(object):
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
         loop below (tests/test_search_persistent_gpu.py).  games_total > 0: the games_total games of own / opp
         as a stream through the B slots (play_stream).  active: (B,) uint8 kinds of game (play_match's codes), default
-        all self-play; res: the result object to fill (default a SelfPlayResult)."""
+        all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up."""
         m, T = self.mcts, self.max_turns
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
+        rec = self._new_records(B)
         g = dict(max_turns=T, games_total=games_total, own=own, opp=opp, n_turns=torch.zeros(B, dtype=torch.int32, device=dev),
-                 rec_own=torch.zeros((T, B), dtype=torch.int64, device=dev),
-                 rec_opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
-                 rec_valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
-                 rec_move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
-                 rec_pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev))
+                 **{"rec_" + k: v for k, v in rec.items()})
         if active is None:
             active = torch.ones(self.B, dtype=torch.uint8, device=dev)
-        if m.value_cache:
-            key = tuple((q.data_ptr(), q._version) for q in m.value_fn.parameters())
-            if key != m._value_key:
-                if m._value_key is not None:
-                    m.tree.v.fill_(float("nan"))
-                    if m._vtable is not None:
-                        m._vtable.zero_()
-                m._value_key = key
+        m._forget_stale_values()
         # (what the launch accumulates into, in case a pool fills up and the batch is replayed turn by turn)
         keep = [(t, t.clone()) for t in (m._ps["totals"], m.z_log_n, m.stats) if t is not None]
         m._launch_persistent(None, None, active, n_sims, game=g)
         back = torch.cat([m.error_flags(), m._ps["ctl"][4].to(torch.int64).reshape(1),
                           g["n_turns"].max().to(torch.int64).reshape(1),
-                          (g["rec_valid"] == 1).sum().to(torch.int64).reshape(1),
+                          (rec["valid"] == 1).sum().to(torch.int64).reshape(1),
                           m._ps["ctl"][7].to(torch.int64).reshape(1),
                           m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)]).tolist()
         m.net_workgroups_launched = int(back[8])
@@ -1540,25 +1569,19 @@ class SelfPlayEngine(object):
         t = int(back[6])
         m.sim_counter = (m.sim_counter + t * n_sims) & 0xFFFFFFFF
         m.n_leaf_evals += int(back[7]) * n_sims
-        res = SelfPlayResult() if res is None else res
-        res.game_id_base = m.game_id_base
-        res.n_turns = t
-        res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
         # a game's boards after n_turns[g] swaps of sides; colour 1's stones are `own` after an even number
         even = (g["n_turns"] % 2 == 0)
         p1, p2 = torch.where(even, own, opp), torch.where(even, opp, own)
-        res.z = ops.judge(p1, p2)
-        res.final_p1, res.final_p2 = p1, p2
-        res.game_turns = g["n_turns"]    # (B,) the turn at which each game ended (the batch's last: n_turns)
+        res = self._finish(SelfPlayResult() if res is None else res, p1, p2, t, 1, game_turns=g["n_turns"])
         if record:
             turn = torch.arange(t, device=dev).reshape(t, 1)
             played = turn < g["n_turns"].reshape(1, B)
             # (the turn-by-turn loop records a finished game's boards, still swapping sides, until the last game
             # of the batch is over: the same rows here)
             tw = (turn % 2 == 0)
-            res.own = torch.where(played, g["rec_own"][:t], torch.where(tw, p1.reshape(1, B), p2.reshape(1, B)))
-            res.opp = torch.where(played, g["rec_opp"][:t], torch.where(tw, p2.reshape(1, B), p1.reshape(1, B)))
-            res.valid, res.move, res.pi = g["rec_valid"][:t], g["rec_move"][:t], g["rec_pi"][:t]
+            res.own = torch.where(played, rec["own"][:t], torch.where(tw, p1.reshape(1, B), p2.reshape(1, B)))
+            res.opp = torch.where(played, rec["opp"][:t], torch.where(tw, p2.reshape(1, B), p1.reshape(1, B)))
+            res.valid, res.move, res.pi = rec["valid"][:t], rec["move"][:t], rec["pi"][:t]
         return res
 
     def _whole_games_in_one_launch(self, n_sims):
@@ -1567,78 +1590,113 @@ class SelfPlayEngine(object):
                 and os.environ.get("IAGO_PERSISTENT_GAMES", "1") != "0"
                 and 2 * m.tree.capacity >= suggest_capacity(n_sims, m.n_thr, moves=min(self.max_turns, 64)))
 
-    def play(self, n_sims, handicap=None, record=True):
-        m, B = self.mcts, self.B
-        dev = m.cur_own.device
-        own = torch.full((B,), START_OWN, dtype=torch.int64, device=dev)
-        opp = torch.full((B,), START_OPP, dtype=torch.int64, device=dev)
-        if handicap is not None:  # (B,) int64 bit masks of extra colour-2 stones
-            opp = opp | handicap
+    def _one_launch(self, n_sims, n, handicap, record, applies=True, **kw):
+        """Fresh trees, then the n games in one launch (_play_persistent(**kw)) wherever the persistent search applies
+        (and the caller's own condition does) and the pools can hold a whole game without compaction.  None where it
+        does not -- and where a pool filled up all the same (n_replayed) -- with the trees fresh for the caller's
+        fallback, whose searches (one launch per turn) compact a pool that is half full.  Same games either way."""
+        m = self.mcts
         m.tree.reset()
-        # The one-launch whole-game path wherever the persistent search applies and the pools can hold a whole game
-        # without compaction; else -- and when a pool fills up all the same -- the turn-by-turn loop below, whose
-        # searches (one persistent launch per turn) compact a pool that is half full.  Same games either way.
-        if self._whole_games_in_one_launch(n_sims):
-            res = self._play_persistent(n_sims, own.clone(), opp.clone(), record)
-            if res is not None:
-                return res
-            self.n_replayed = getattr(self, "n_replayed", 0) + 1   # batches replayed through the turn loop
+        if not (applies and self._whole_games_in_one_launch(n_sims)):
+            return None
+        res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, **kw)
+        if res is None:
+            self.n_replayed += 1
             m.tree.reset()
+        return res
+
+    def _movers(self, colours, t, active, legal, stone_num):
+        """Who moves at turn t in the games `active`: (the games searched as a uint8 mask and as a bool one, the games
+        whose move the policy draws, the games whose move is forced).  Self-play (colours None) searches them all."""
+        on = active.bool()
+        if colours is None:
+            return active, on, None, None
+        mcts_moves = colours == (1 if t % 2 == 0 else 2)
+        # game.py:97-98: the only move of the last empty square, either side, no search
+        forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
+        searched = on & mcts_moves & ~forced
+        return searched.to(torch.uint8), searched, on & ~mcts_moves & ~forced, forced
+
+    def _play_turns(self, n_sims, own, opp, record, res, colours=None):
+        """The games from (own, opp) turn by turn into res: a search from every root that is searched, the move, the
+        books, in lockstep.  colours None: self-play, every active game searched; else play_match's (B,) int8 colours
+        of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced."""
+        m, B, T = self.mcts, self.B, self.max_turns
+        dev = own.device
         stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        res = SelfPlayResult()
-        res.game_id_base = m.game_id_base
-        T = self.max_turns
-        if record:
-            res.own = torch.zeros((T, B), dtype=torch.int64, device=dev)
-            res.opp = torch.zeros((T, B), dtype=torch.int64, device=dev)
-            res.pi = torch.zeros((T, B, 64), dtype=torch.int32, device=dev)
-            res.valid = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-            res.move = torch.full((T, B), -1, dtype=torch.int8, device=dev)
-        res.mover = []
+        rec = self._new_records(B) if record else None
         legal = ops.legal_moves(own, opp)
         active = (legal != 0).to(torch.uint8)
         legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
+        bad_draw = torch.zeros(1, dtype=torch.int64, device=dev)   # (self-play draws nothing)
+        if colours is not None:
+            cells = torch.arange(64, device=dev)
+            key = m.seed ^ _lib.MATCH_SEED_XOR
+            pf = m.policy_fn
         t = 0
-        counts = m.search_counts(active).tolist()
+        s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
+        counts = m.search_counts(s_act).tolist()
         while t < T:
-            # ONE readback per move (below): the flags of this move's search, the check of its
+            # ONE readback per turn (below): the flags of this turn's search, the check of its
             # moves, the end-of-game test and the counts the next search starts from
-            m.search(own, opp, active, n_sims, counts=counts, check=False)
-            move, visits = m.best_move(active)
-            mv = torch.where(active.bool(), move, torch.full_like(move, -1))
+            m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
+            move, visits = m.best_move(s_act)
+            if colours is None:
+                mv = torch.where(searched, move, torch.full_like(move, -1))
+                valid, live = s_act, done ^ 1   # game.py:84,108,140 (the games not yet done)
+            else:
+                with torch.no_grad():
+                    if hasattr(pf, "forward_boards_split3"):
+                        probs = pf.forward_boards_split3(own, opp)
+                    else:
+                        probs = pf(ops.encode_planes(own, opp))
+                draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)), seed=key,
+                                        id_base=m.game_id_base, step=t, stream_id=0)
+                only = ((legal.reshape(B, 1) >> cells) & 1).argmax(dim=1).to(torch.int8)
+                mv = torch.where(searched, move, torch.where(drawn, draw, torch.where(forced, only, torch.full_like(move, -1))))
+                if record:
+                    valid = s_act + 2 * (drawn | forced).to(torch.uint8)
+                live = ((done == 0) & ~forced).to(torch.uint8)   # game.py:107,113,140
+                bad_draw = (drawn & (draw == 64)).any().to(torch.int64).reshape(1)
             if record:
-                res.own[t], res.opp[t], res.valid[t], res.move[t] = own, opp, active, mv
-                res.pi[t] = visits * active.reshape(B, 1).to(torch.int32)
-            res.mover.append(1 if t % 2 == 0 else 2)
-            m.update_with_move(mv, done ^ 1)  # game.py:84,108,140 (the games not yet done)
+                rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t] = own, opp, valid, mv
+                rec["pi"][t] = visits * s_act.reshape(B, 1).to(torch.int32)
+            m.update_with_move(mv, live)
             # the move, stone_num / pass_flg, `while game.stone_num < 64` once per pair of turns
             # (game.py:117-142,253-255), the swap of sides, the next mover's legal moves
             ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
             legal, legal_next = legal_next, legal
             active, active_next = active_next, active
             t += 1
+            s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
+            # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64)
             back = torch.cat([m.error_flags(), (mv == -2).any().to(torch.int64).reshape(1),
-                              done.all().to(torch.int64).reshape(1), m.search_counts(active)]).tolist()
+                              bad_draw, done.all().to(torch.int64).reshape(1),
+                              m.search_counts(s_act)]).tolist()
             m.raise_errors(back[:5])
-            back = back[1:]
-            if back[4]:
+            if back[5]:
                 # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
-                raise ValueError("a searched root has no children: n_sims is below the "
-                                 "expansion threshold n_thr")
-            if t % 2 == 0 and back[5]:
+                raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
+            if back[6]:
+                raise _lib.IagoError(_BAD_DRAW)
+            if t % 2 == 0 and back[7]:
                 break
-            counts = back[6:8]
+            counts = back[8:10]
         # colour 1's stones are `own` after an even number of turns
         p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
-        res.z = ops.judge(p1, p2)
-        res.final_p1, res.final_p2 = p1, p2
-        res.n_turns = t
-        res.game_turns = None   # (per-game end turns: the one-launch path records them)
+        self._finish(res, p1, p2, t, t)
         if record:
-            for name in ("own", "opp", "pi", "valid", "move"):
-                setattr(res, name, getattr(res, name)[:t])
+            for k, v in rec.items():
+                setattr(res, k, v[:t])
+        return res
+
+    def play(self, n_sims, handicap=None, record=True):
+        """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult."""
+        res = self._one_launch(n_sims, self.B, handicap, record)
+        if res is None:
+            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult())
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True):
@@ -1651,7 +1709,7 @@ class SelfPlayEngine(object):
         up in the launch).  handicap: (n_games,) int64 bit masks of extra colour-2 stones.  The result has n_games
         columns (tuples() give the game ids game_id_base ..); n_turns is the longest game's, `launches` the launches it
         took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch."""
-        m, B, T = self.mcts, self.B, self.max_turns
+        m, T = self.mcts, self.max_turns
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError("play_stream: n_games >= 1 expected")
@@ -1660,20 +1718,11 @@ class SelfPlayEngine(object):
                              % (n_games, T, STREAM_REC_BYTES))
         if handicap is not None and tuple(handicap.shape) != (n_games,):
             raise ValueError("play_stream: handicap is an (n_games,) int64 tensor")
-        if (self._whole_games_in_one_launch(n_sims) and getattr(m, "z_log", None) is None
-                and getattr(m, "trace", None) is None):
-            dev = m.cur_own.device
-            own = torch.full((n_games,), START_OWN, dtype=torch.int64, device=dev)
-            opp = torch.full((n_games,), START_OPP, dtype=torch.int64, device=dev)
-            if handicap is not None:
-                opp = opp | handicap
-            m.tree.reset()
-            res = self._play_persistent(n_sims, own, opp, record, games_total=n_games)
-            if res is not None:
-                res.launches = 1
-                return res
-            self.n_replayed = getattr(self, "n_replayed", 0) + 1
-        return self._play_batches(n_sims, n_games, handicap, record)
+        plain = getattr(m, "z_log", None) is None and getattr(m, "trace", None) is None
+        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games)
+        if res is None:
+            res = self._play_batches(n_sims, n_games, handicap, record)
+        return res
 
     def _match_colours(self, mcts_colour):
         """play_match's mcts_colour as a (B,) int8 device tensor of 1 / 2."""
@@ -1699,88 +1748,14 @@ class SelfPlayEngine(object):
         (seed ^ MATCH_SEED_XOR, game_id_base + g, turn, stream 0), and advances the tree like any move (game.py:107); a
         final move that is the only one (stone_num > 62) is played by either side without a search and without
         update_with_move (game.py:97-98).  ONE launch of the persistent search where play() takes it, else (and when a
-        pool fills up in the launch) the turn loop below: the same games record for record.  sim_counter advances by
+        pool fills up in the launch) the turn loop: the same games record for record.  sim_counter advances by
         n_sims per turn, searched or not.  Returns a MatchResult."""
-        m, B, T = self.mcts, self.B, self.max_turns
         col = self._match_colours(mcts_colour)
-        dev = m.cur_own.device
-        own = torch.full((B,), START_OWN, dtype=torch.int64, device=dev)
-        opp = torch.full((B,), START_OPP, dtype=torch.int64, device=dev)
-        m.tree.reset()
-        if self._whole_games_in_one_launch(n_sims):
-            codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
-            res = self._play_persistent(n_sims, own.clone(), opp.clone(), record, active=codes, res=MatchResult())
-            if res is not None:
-                res.mcts_colour, res.launches = col, 1
-                return res
-            self.n_replayed = getattr(self, "n_replayed", 0) + 1
-            m.tree.reset()
-        stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
-        pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        res = MatchResult()
-        res.game_id_base, res.mcts_colour = m.game_id_base, col
-        if record:
-            res.own = torch.zeros((T, B), dtype=torch.int64, device=dev)
-            res.opp = torch.zeros((T, B), dtype=torch.int64, device=dev)
-            res.pi = torch.zeros((T, B, 64), dtype=torch.int32, device=dev)
-            res.valid = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-            res.move = torch.full((T, B), -1, dtype=torch.int8, device=dev)
-        res.mover = []
-        legal = ops.legal_moves(own, opp)
-        active = (legal != 0).to(torch.uint8)
-        legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
-        cells = torch.arange(64, device=dev)
-        key = m.seed ^ _lib.MATCH_SEED_XOR
-        pf = m.policy_fn
-        t = 0
-        while t < T:
-            on = active.bool()
-            mcts_moves = col == (1 if t % 2 == 0 else 2)
-            # game.py:97-98: the only move of the last empty square, either side, no search
-            forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
-            searched = on & mcts_moves & ~forced
-            drawn = on & ~mcts_moves & ~forced
-            s_act = searched.to(torch.uint8)
-            m.search(own, opp, s_act, n_sims, check=False)   # (sim_counter: + n_sims whoever searched)
-            move, visits = m.best_move(s_act)
-            with torch.no_grad():
-                if hasattr(pf, "forward_boards_split3"):
-                    probs = pf.forward_boards_split3(own, opp)
-                else:
-                    probs = pf(ops.encode_planes(own, opp))
-            draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)), seed=key,
-                                    id_base=m.game_id_base, step=t, stream_id=0)
-            only = ((legal.reshape(B, 1) >> cells) & 1).argmax(dim=1).to(torch.int8)
-            mv = torch.where(searched, move, torch.where(drawn, draw, torch.where(forced, only, torch.full_like(move, -1))))
-            if record:
-                res.own[t], res.opp[t], res.move[t] = own, opp, mv
-                res.valid[t] = s_act + 2 * (drawn | forced).to(torch.uint8)
-                res.pi[t] = visits * s_act.reshape(B, 1).to(torch.int32)
-            res.mover.append(1 if t % 2 == 0 else 2)
-            m.update_with_move(mv, ((done == 0) & ~forced).to(torch.uint8))  # game.py:107,113,140
-            bad_draw = (drawn & (draw == 64)).any()
-            ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
-            legal, legal_next = legal_next, legal
-            active, active_next = active_next, active
-            t += 1
-            back = torch.cat([m.error_flags(), (searched & (mv == -2)).any().to(torch.int64).reshape(1),
-                              bad_draw.to(torch.int64).reshape(1), done.all().to(torch.int64).reshape(1)]).tolist()
-            m.raise_errors(back[:5])
-            if back[5]:
-                raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
-            if back[6]:
-                raise _lib.IagoError(_BAD_DRAW)
-            if t % 2 == 0 and back[7]:
-                break
-        p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
-        res.z = ops.judge(p1, p2)
-        res.final_p1, res.final_p2 = p1, p2
-        res.n_turns, res.launches = t, t
-        res.game_turns = None
-        if record:
-            for name in ("own", "opp", "pi", "valid", "move"):
-                setattr(res, name, getattr(res, name)[:t])
+        codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
+        res = self._one_launch(n_sims, self.B, None, record, active=codes, res=MatchResult())
+        if res is None:
+            res = self._play_turns(n_sims, *self._start_boards(self.B), record, MatchResult(), colours=col)
+        res.mcts_colour = col
         return res
 
     def _play_batches(self, n_sims, n_games, handicap, record):

@@ -403,3 +403,32 @@ def test_role_split_builds_the_same_trees(nets):
     assert res[0][3] == res[1][3]
     for x, y in zip(res[0][:3], res[1][:3]):
         assert np.array_equal(x, y)
+
+
+def test_turn_loops_read_back_once_per_turn(nets, monkeypatch):
+    """The host syncs of SelfPlayEngine's turn loop (IAGO_PERSISTENT_GAMES=0), as calls of Tensor.tolist / Tensor.item
+    while play() and play_match() run T = 6 turns on pools that need no compaction.  Before play() and play_match()
+    shared one loop: play() 7 = the first search's counts + one readback per turn (flags, move check, end-of-batch
+    test and the next search's counts in one tolist); play_match() 12 = per turn, the search's own read of its counts
+    and the loop's readback.  Neither may read back more often, and play()'s loop stays at one readback per turn."""
+    engine, ops, policy, value, rw = nets
+    G, n_sims, T = 16, 30, 6
+    monkeypatch.setenv("IAGO_PERSISTENT_GAMES", "0")
+    calls = []
+    for name in ("tolist", "item"):
+        def counted(self, *a, _f=getattr(torch.Tensor, name), **k):
+            calls.append(1)
+            return _f(self, *a, **k)
+        monkeypatch.setattr(torch.Tensor, name, counted)
+    m = engine.BatchedMCTS(G, policy, value, rw, n_thr=15, capacity=4096, seed=9, persistent=True)
+    eng = engine.SelfPlayEngine(m, max_turns=T)
+    got = {}
+    for name, fn in (("play", lambda: eng.play(n_sims)), ("play_match", lambda: eng.play_match(n_sims, mcts_colour=2))):
+        del calls[:]
+        r = fn()
+        got[name] = len(calls)
+        assert r.n_turns == T and r.game_turns is None and m.n_compactions == 0     # the turn loop, all T turns
+    print("host readbacks in %d turns: %r" % (T, got))
+    m.close()
+    assert got["play"] == 1 + T
+    assert got["play_match"] <= 2 * T
