@@ -49,7 +49,7 @@ EXPERIMENTAL_SYMBOLS = [
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
 # the exact endgame solver (ops.solve_endgame, engine.solve_endgame)
 SERVING_SYMBOLS = [
-    "iago_mcts_search_wave", "iago_solve_endgame",
+    "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True))
@@ -244,6 +244,25 @@ class EndgameArgs(C.Structure):
     ]
 
 
+class PlayEndgameArgs(C.Structure):
+    """Mirror of iago_play_endgame_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("turn", C.c_void_p), ("stones", C.c_void_p),
+        ("pass_flg", C.c_void_p), ("parked", C.c_void_p), ("n", C.c_int64), ("stride", C.c_int64),
+        ("max_turns", C.c_int32), ("max_empties", C.c_int32), ("time_limit_ms", C.c_int32), ("reserved0", C.c_int32),
+        ("rec_own", C.c_void_p), ("rec_opp", C.c_void_p), ("rec_valid", C.c_void_p), ("rec_move", C.c_void_p),
+        ("rec_score", C.c_void_p), ("finished", C.c_void_p), ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
+class SearchParkArgs(C.Structure):
+    """Mirror of iago_search_park_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("park_empties", C.c_int32), ("reserved0", C.c_int32), ("parked", C.c_void_p), ("stones", C.c_void_p),
+        ("pass_flg", C.c_void_p), ("streams", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
 class ValueSplitArgs(C.Structure):
     """Mirror of iago_value_split_args (include/iago_hip.h)."""
     _fields_ = [
@@ -366,6 +385,8 @@ def lib():
     L.iago_mcts_search_wave.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchWaveArgs), vp]
     L.iago_selfplay_policy.argtypes = [C.POINTER(SelfplayPolicyArgs), vp]
     L.iago_solve_endgame.argtypes = [C.POINTER(EndgameArgs), vp]
+    L.iago_play_endgame.argtypes = [C.POINTER(PlayEndgameArgs), vp]
+    L.iago_mcts_search_park.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchParkArgs), vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)

@@ -35,6 +35,7 @@
 #include "../../include/iago_hip_serving.h"
 
 #include <cstdlib>
+#include <vector>
 
 namespace {
 using namespace iago;
@@ -142,6 +143,12 @@ struct SearchParams {
     float vloss;
     int64_t n_slots;
     int64_t *wave_timing;
+    // the hand-over of iago_mcts_search_park (the PARK instantiations alone read these): a self-play game whose turn would
+    // be searched at a position of at most park_empties empties writes its books here, by game id, and is done
+    int32_t park_empties;
+    uint8_t *parked;
+    int32_t *park_stones;
+    uint8_t *park_pass;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -645,6 +652,9 @@ __device__ __forceinline__ void play_move(const SearchParams &S, const Slot &I, 
 
 // ---- 3. whole games (the games' lanes): the turn's end (the move) and the next turn's start, until the game searches
 // again or is over (a pass leads straight on to the next turn: at most a few rounds)
+// PARK (iago_mcts_search_park): a turn that would be searched at a position of at most S.park_empties empties hands the game
+// over instead -- the turn it stands at, its position (own = the mover) and its books, by game id -- and the game is done
+template <bool PARK>
 __device__ __forceinline__ void turn_boundary(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G, const Cursor &C,
                                               bool &busy, const long long t0)
 {
@@ -669,7 +679,22 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const Slot 
                 send_request(S, KIND_POLICY, I.g, G.epoch, G.g_own, G.g_opp); // make_state_var(state, color)
             G.state = ST_WAIT_DRAW;
         }
-        if (at_turn && can_move && !forced && !policy_turn) {
+        bool park = false;
+        if constexpr (PARK)
+            park = at_turn && can_move && 64 - __popcll(G.g_own | G.g_opp) <= S.park_empties;
+        if (park) {
+            if (I.r == 0u) {
+                const int64_t id = sh.h_game[I.gl];
+                S.n_turns[id] = G.turn;
+                S.game_own[id] = G.g_own;
+                S.game_opp[id] = G.g_opp;
+                S.park_stones[id] = G.stones;
+                S.park_pass[id] = G.pass_flg ? 1 : 0;
+                S.parked[id] = 1;
+            }
+            G.state = ST_DONE;
+        }
+        if (at_turn && can_move && !forced && !policy_turn && !park) {
             // the mover searches: MCTS.get_move(state, color) (game.py:112)
             G.n_done = 0;
             if (I.r == 0u)
@@ -1192,7 +1217,7 @@ __device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, G
     }
 }
 
-template <bool WAVE>
+template <bool WAVE, bool PARK = false>
 __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0)
 {
     __shared__ GameShared<WAVE> sh;
@@ -1252,7 +1277,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                 busy = true;
             }
             if (!WAVE && I.whole)
-                turn_boundary(S, I, sh, G, C, busy, t0);
+                turn_boundary<PARK>(S, I, sh, G, C, busy, t0);
         }
         const long long c_desc = WAVE ? wall_clock64() : 0;
         for (int sub = 0; sub < (WAVE ? I.W : 1); sub++) {
@@ -1529,7 +1554,7 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
 // ONE grid: the game workgroups first (they are dispatched first, so all of them are resident whatever else
 // holds CUs; a net workgroup never waits for another net workgroup, so one that finds no CU free simply starts
 // late), then the net workgroups.  A game workgroup whose games are done serves the queue like the others.
-template <bool WAVE>
+template <bool WAVE, bool PARK = false>
 __device__ __forceinline__ void search_body(const SearchParams &S, const iago_row::HwParams &R, const iago_trunk::TrunkRParams &VP,
                                             const iago_policy::PolicyParams &PP)
 {
@@ -1537,7 +1562,7 @@ __device__ __forceinline__ void search_body(const SearchParams &S, const iago_ro
     if (blockIdx.x == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
     if ((int)blockIdx.x < S.n_game_wgs)
-        game_workgroup<WAVE>(S, R, t0);
+        game_workgroup<WAVE, PARK>(S, R, t0);
     net_workgroup(S, VP, PP, t0);
 }
 
@@ -1567,6 +1592,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                                                                    iago_row::HwParams R)
 {
     game_workgroup<false>(S, R, wall_clock64());
+}
+
+// The whole-game search that hands its games over at park_empties (iago_mcts_search_park): the single launch and the game
+// launch of the role split, instantiations of their own -- the kernels above compile the code they always did.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_park_kernel(
+    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+{
+    search_body<false, true>(S, R, VP, PP);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_park_kernel(SearchParams S,
+                                                                                                        iago_row::HwParams R)
+{
+    game_workgroup<false, true>(S, R, wall_clock64());
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_net_kernel(
@@ -1698,7 +1737,7 @@ struct SearchGrid {
 // waits for replies only net workgroups give), and a net workgroup beyond what fits would only start when another one
 // ends -- at the end of the launch.  Resident workgroups = CUs the launch may count on (max_cus, else the device's) x
 // workgroups of this kernel per CU (its registers and LDS allow one).
-int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iago_search_wave_args *wv, SearchGrid &G)
+int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iago_search_wave_args *wv, bool park, SearchGrid &G)
 {
     G.gpw = wv ? GAMES_PER_WG : a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
     G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
@@ -1720,28 +1759,32 @@ int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iag
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
         const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
         // (asked of the runtime once per device and LDS size: every launch comes through here)
-        static std::atomic<int32_t> static_lds{-1};
+        // (park: the game launch's other instantiation, with books of its own)
+        const void *game_kernel = park ? (const void *)search_game_park_kernel : (const void *)search_game_kernel;
+        static std::atomic<int32_t> static_lds_of[2] = {{-1}, {-1}};
+        std::atomic<int32_t> &static_lds = static_lds_of[park ? 1 : 0];
         int32_t fixed = static_lds.load(std::memory_order_acquire);
         if (fixed < 0) {
             hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, (const void *)search_game_kernel) != hipSuccess)
+            if (hipFuncGetAttributes(&fa, game_kernel) != hipSuccess)
                 return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: hipFuncGetAttributes failed");
             fixed = (int32_t)fa.sharedSizeBytes;
             static_lds.store(fixed, std::memory_order_release);
         }
         G.game_lds = (want + (size_t)fixed + 256u) * 2u <= (size_t)160 * 1024u ? (int)want : 0;
         G.path_lds_cap = G.game_lds;
-        static std::atomic<uint64_t> configured_game{0};
-        if (G.game_lds && iago_reserve_lds((const void *)search_game_kernel, 96 * 1024, configured_game,
+        static std::atomic<uint64_t> configured_game_of[2] = {{0}, {0}};
+        if (G.game_lds && iago_reserve_lds(game_kernel, 96 * 1024, configured_game_of[park ? 1 : 0],
                                            "iago_mcts_search_split: cannot reserve the game workgroups' LDS"))
             return IAGO_ERR_HIP;
-        static std::atomic<uint64_t> occ_known[64]; // per device: LDS bytes << 8 | workgroups per CU (+ 1 << 63: valid)
+        static std::atomic<uint64_t> occ_known_of[2][64]; // per device: LDS bytes << 8 | workgroups per CU (+ 1 << 63: valid)
+        std::atomic<uint64_t> *occ_known = occ_known_of[park ? 1 : 0];
         int per_game = 0;
         const uint64_t seen = occ_known[dev & 63].load(std::memory_order_acquire);
         if ((seen >> 63) && ((seen >> 8) & 0xFFFFFFull) == (uint64_t)G.game_lds) {
             per_game = (int)(seen & 0xFF);
         } else {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_game, (const void *)search_game_kernel, 256, (size_t)G.game_lds) != hipSuccess)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_game, game_kernel, 256, (size_t)G.game_lds) != hipSuccess)
                 return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: the device does not answer");
             occ_known[dev & 63].store((1ull << 63) | ((uint64_t)G.game_lds << 8) | (uint64_t)(per_game & 0xFF), std::memory_order_release);
         }
@@ -1853,12 +1896,16 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.vtable_mask = a->vtable_slots > 0 ? (uint32_t)(a->vtable_slots - 1) : 0u;
     S.trace = a->trace_rows > 0 ? a->trace : nullptr;
     S.trace_rows = a->trace_rows;
+    S.park_empties = -1;
+    S.parked = nullptr;
+    S.park_stones = nullptr;
+    S.park_pass = nullptr;
     return S;
 }
 
 // the zeroing of the polled words and the launch: one kernel, or the role split's two on their masked streams
 int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp, const iago_search_wave_args *wv,
-                  const SearchGrid &G, const SearchParams &S)
+                  bool park, const SearchGrid &G, const SearchParams &S)
 {
     iago_trunk::TrunkRParams VP;
     if (const int rc = iago_trunk::value_params_of(a->value, VP))
@@ -1888,6 +1935,14 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
         hipLaunchKernelGGL(search_wave_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
         return iago_check_launch("iago_mcts_search_wave");
     }
+    if (!sp && park) {
+        static std::atomic<uint64_t> configured_park{0};
+        if (iago_reserve_lds((const void *)search_park_kernel, lds, configured_park,
+                             "iago_mcts_search_park: cannot reserve the nets' LDS image"))
+            return IAGO_ERR_HIP;
+        hipLaunchKernelGGL(search_park_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
+        return iago_check_launch("iago_mcts_search_park");
+    }
     if (!sp) {
         hipLaunchKernelGGL(search_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
         return iago_check_launch("iago_mcts_search_persistent");
@@ -1901,7 +1956,10 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
+    if (park)
+        hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
+    else
+        hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
     int rc = iago_check_launch("iago_mcts_search_split (game launch)");
     if (rc == IAGO_OK) {
         hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)G.net_wgs), dim3(256), lds, sp->net, S, VP, PP);
@@ -1916,16 +1974,76 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
 }
 
 int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
-                  const iago_search_wave_args *wv = nullptr)
+                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr)
 {
     SearchGrid G;
     if (const int rc = check_args(a, wv))
         return rc;
-    if (const int rc = size_grid(a, sp, wv, G))
+    if (const int rc = size_grid(a, sp, wv, pk != nullptr, G))
         return rc;
-    return launch_search(a, stream, sp, wv, G, search_params(a, G, wv));
+    SearchParams S = search_params(a, G, wv);
+    if (pk) {
+        S.park_empties = pk->park_empties;
+        S.parked = pk->parked;
+        S.park_stones = pk->stones;
+        S.park_pass = pk->pass_flg;
+        if (hipMemsetAsync(pk->parked, 0, (size_t)S.games_total, (hipStream_t)stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_park: clearing parked");
+        }
+    }
+    return launch_search(a, stream, sp, wv, pk != nullptr, G, S);
+}
+
+// (iago_mcts_search_park) whether `active` [n] holds a match's codes: read where it lies -- host memory as it is, device
+// memory through a copy on the stream.  < 0: the copy failed
+int has_match_codes(const uint8_t *active, int64_t n, hipStream_t stream)
+{
+    hipPointerAttribute_t at;
+    const bool on_device = hipPointerGetAttributes(&at, active) == hipSuccess &&
+                           (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged);
+    (void)hipGetLastError();
+    std::vector<uint8_t> copy;
+    if (on_device) {
+        copy.resize((size_t)n);
+        if (hipMemcpyAsync(copy.data(), active, (size_t)n, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return -1;
+        }
+        active = copy.data();
+    }
+    for (int64_t i = 0; i < n; i++)
+        if (active[i] > 1)
+            return 1;
+    return 0;
 }
 } // namespace
+
+extern "C" int iago_mcts_search_park(const iago_mcts_search_args *a, const iago_search_park_args *pk, void *stream)
+{
+    if (!a || !pk)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: null args");
+    if (!pk->parked || !pk->stones || !pk->pass_flg)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: parked, stones and pass_flg expected");
+    for (int i = 0; i < 4; i++)
+        if (pk->reserved[i] != 0 || pk->reserved0 != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: reserved fields must be 0");
+    if (pk->park_empties < 0 || pk->park_empties > IAGO_ENDGAME_MAX_EMPTIES)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: park_empties must be in [0, 20]");
+    if (a->max_turns == 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: whole games only (max_turns > 0)");
+    // (before the other arguments are looked at: a stream does not read `active`, every game of it is self-play)
+    if (a->games_total == 0 && a->active && a->tree && a->tree->n_games >= 1) {
+        const int m = has_match_codes(a->active, a->tree->n_games, (hipStream_t)stream);
+        if (m < 0)
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_park: cannot read `active`");
+        if (m)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: match codes in `active` (self-play games only: a "
+                                               "match's policy side needs the net workgroups to its last move)");
+    }
+    return search_launch(a, stream, pk->streams, nullptr, pk);
+}
 
 extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)
 {

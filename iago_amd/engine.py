@@ -1177,9 +1177,10 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _launch_persistent(self, own, opp, active, n_sims, game=None):
+    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None):
         """iago_mcts_search_persistent: one search from the roots (own, opp), or -- game = dict(max_turns, own,
-        opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games."""
+        opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games; park = dict(empties,
+        parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park)."""
         if self.rollout_hook is not None:
             raise ValueError("rollout_hook is not available in the persistent search (z_log_rows records the z)")
         ps = self._ps
@@ -1235,6 +1236,12 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
+        elif park is not None:
+            k = _lib.SearchParkArgs()
+            k.park_empties = int(park["empties"])
+            k.parked, k.stones, k.pass_flg = park["parked"].data_ptr(), park["stones"].data_ptr(), park["pass_flg"].data_ptr()
+            k.streams = self._split   # (the role split where today's launch takes it, else the single launch)
+            check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
         elif self._split is not None:
             check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
         else:
@@ -1242,7 +1249,7 @@ class BatchedMCTS(object):
         if ev is not None:
             e1.record()
             ev.append((e0, e1))
-        self._ps_keep = (keep_v, keep_p, ro, va, pa, own, opp, active, game)   # alive until the next launch
+        self._ps_keep = (keep_v, keep_p, ro, va, pa, own, opp, active, game, park)   # alive until the next launch
 
     def _forget_stale_values(self):
         """The stored values belong to the weights that computed them: once the value net's parameters have changed,
@@ -1417,13 +1424,25 @@ class SelfPlayResult(object):
     """Training tuples of one self-play round, device resident.
 
     own/opp: (T, B) int64 positions before each searched move (own = mover),
-    pi: (T, B, 64) int32 root visit counts, valid: (T, B) uint8 (the game moved
-    at that turn), move: (T, B) int8, z: (B,) int8 result from colour 1's view,
+    pi: (T, B, 64) int32 root visit counts, valid: (T, B) uint8 (1: the game searched and moved
+    at that turn; 3: the move is the exact endgame solver's, solve_empties; 0: a pass or no turn),
+    move: (T, B) int8, score: (T, B) int8 the exact final disc difference from the mover's view on
+    the solved rows (0 elsewhere), z: (B,) int8 result from colour 1's view,
     mover: (T,) colour to move at that turn (1 or 2)."""
 
+    SCORE_RECORD = "score"   # the attribute that holds the `score` record
+
     def tuples(self):
-        """Flat (s, pi, z) rows of all searched moves; z from the mover's view."""
-        m = self.valid.reshape(-1).bool()
+        """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view."""
+        return self._rows(1, True)
+
+    def solved_tuples(self):
+        """Flat rows of the moves the endgame solver played (valid == 3): own, opp, move, score (the exact final disc
+        difference from the mover's view), z (from the mover's view), colour, game, turn."""
+        return self._rows(3, False)
+
+    def _rows(self, kind, searched):
+        m = self.valid.reshape(-1) == kind
         T, B = self.valid.shape
         sign = torch.tensor([1 if c == 1 else -1 for c in self.mover], dtype=torch.int8,
                             device=self.z.device).reshape(T, 1)
@@ -1434,10 +1453,14 @@ class SelfPlayResult(object):
         # ranks into ONE canonical order (train_rl.ReinforceTrainer.step_from_tuples)
         game = (torch.arange(B, dtype=torch.int32, device=dev) + int(getattr(self, "game_id_base", 0))).reshape(1, B)
         turn = torch.arange(T, dtype=torch.int32, device=dev).reshape(T, 1)
-        return dict(own=self.own.reshape(-1)[m], opp=self.opp.reshape(-1)[m],
-                    pi=self.pi.reshape(-1, 64)[m], z=zz[m], move=self.move.reshape(-1)[m],
+        rows = dict(own=self.own.reshape(-1)[m], opp=self.opp.reshape(-1)[m], z=zz[m], move=self.move.reshape(-1)[m],
                     colour=colour.reshape(-1)[m], game=game.expand(T, B).reshape(-1)[m],
                     turn=turn.expand(T, B).reshape(-1)[m])
+        if searched:
+            rows["pi"] = self.pi.reshape(-1, 64)[m]
+        else:
+            rows["score"] = getattr(self, self.SCORE_RECORD).reshape(-1)[m]
+        return rows
 
 
 _BAD_DRAW = ("a match's policy draw met NaN / inf / zero probability mass on the legal moves (numpy.random.choice "
@@ -1447,8 +1470,11 @@ _BAD_DRAW = ("a match's policy draw met NaN / inf / zero probability mass on the
 class MatchResult(SelfPlayResult):
     """The games of SelfPlayEngine.play_match: PV-MCTS against the SL policy (game.py:96-145,246-262).  As a
     SelfPlayResult, with valid 1 where PV-MCTS searched, 2 where a move was played without a search (the policy's
-    draw, or a final move that was the only one: pi is 0 there), 0 for a pass or no turn; mcts_colour: (B,) int8, the
-    colour PV-MCTS played in each game."""
+    draw, or a final move that was the only one: pi is 0 there), 3 where PV-MCTS played the endgame solver's move
+    (solve_empties), 0 for a pass or no turn; mcts_colour: (B,) int8, the colour PV-MCTS played in each game.  score()
+    being the match's result, the (T, B) record of the solved rows' exact scores is `solved_score` here."""
+
+    SCORE_RECORD = "solved_score"
 
     def tuples(self):
         """SelfPlayResult.tuples() of the positions PV-MCTS searched (valid == 1) only."""
@@ -1489,6 +1515,21 @@ def _end_turns(valid):
     return end
 
 
+def _solve_empties_arg(k):
+    """solve_empties of play / play_stream / play_match: None, or an int in [0, 20] (as MCTS(solve_empties=) takes it)."""
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k <= _lib.ENDGAME_MAX_EMPTIES:
+        raise ValueError("solve_empties must be None or an int in [0, %d], not %r" % (_lib.ENDGAME_MAX_EMPTIES, k))
+    return int(k)
+
+
+def _empties(own, opp):
+    """(n,) int32: 64 - popcount(own | opp), the true count of empty squares (stone_num ignores handicap stones)."""
+    cells = torch.arange(64, device=own.device)
+    return 64 - (((own | opp).reshape(-1, 1) >> cells) & 1).sum(dim=1).to(torch.int32)
+
+
 class SelfPlayEngine(object):
     """Whole games on the B boards of a BatchedMCTS, three ways.  play(): lockstep PV-MCTS self-play -- both colours
     search the shared tree, moves are the most visited children, passes advance the tree with -1 (game.py:117-142 turn
@@ -1519,7 +1560,8 @@ class SelfPlayEngine(object):
                     opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
                     pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev),
                     valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
-                    move=torch.full((T, B), -1, dtype=torch.int8, device=dev))
+                    move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
+                    score=torch.zeros((T, B), dtype=torch.int8, device=dev))
 
     def _finish(self, res, p1, p2, t, launches, game_turns=None):
         """What every result ends with: the header of a batch of t turns and its final boards (colour 1's stones,
@@ -1531,13 +1573,16 @@ class SelfPlayEngine(object):
         res.final_p1, res.final_p2 = p1, p2
         return res
 
-    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None):
+    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None, solve_empties=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
         loop below (tests/test_search_persistent_gpu.py).  games_total > 0: the games_total games of own / opp
         as a stream through the B slots (play_stream).  active: (B,) uint8 kinds of game (play_match's codes), default
-        all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up."""
+        all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up.
+        solve_empties = k: TWO launches -- the games hand over at their first turn of at most k empties
+        (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the same
+        records (valid 3, score), and the one readback follows both."""
         m, T = self.mcts, self.max_turns
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
@@ -1549,12 +1594,23 @@ class SelfPlayEngine(object):
         m._forget_stale_values()
         # (what the launch accumulates into, in case a pool fills up and the batch is replayed turn by turn)
         keep = [(t, t.clone()) for t in (m._ps["totals"], m.z_log_n, m.stats) if t is not None]
-        m._launch_persistent(None, None, active, n_sims, game=g)
+        park, played_out = None, []
+        if solve_empties is not None:
+            park = dict(empties=solve_empties, parked=torch.zeros(B, dtype=torch.uint8, device=dev),
+                        stones=torch.zeros(B, dtype=torch.int32, device=dev),
+                        pass_flg=torch.zeros(B, dtype=torch.uint8, device=dev))
+        m._launch_persistent(None, None, active, n_sims, game=g, park=park)
+        if park is not None:
+            # (own / opp / n_turns: a parked game's position and turn in, its final position and turn count out)
+            out = ops.play_endgame(own, opp, g["n_turns"], park["stones"], park["pass_flg"], park["parked"], max_turns=T,
+                                   max_empties=solve_empties, records={k: rec[k] for k in ("own", "opp", "valid", "move", "score")},
+                                   check_result=False)
+            played_out = [out["ctl"].to(torch.int64), (out["finished"] != park["parked"]).sum().reshape(1)]
         back = torch.cat([m.error_flags(), m._ps["ctl"][4].to(torch.int64).reshape(1),
                           g["n_turns"].max().to(torch.int64).reshape(1),
                           (rec["valid"] == 1).sum().to(torch.int64).reshape(1),
                           m._ps["ctl"][7].to(torch.int64).reshape(1),
-                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)]).tolist()
+                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)] + played_out).tolist()
         m.net_workgroups_launched = int(back[8])
         if back[0] and not back[4]:
             # a pool filled up (the launch cannot compact): nothing of this attempt counts
@@ -1566,13 +1622,16 @@ class SelfPlayEngine(object):
             raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
         if back[9]:
             raise _lib.IagoError(_BAD_DRAW)
+        if park is not None:
+            ops.check_play_endgame(back[10:15], out, solve_empties, ops.ENDGAME_TIME_LIMIT_MS)
         t = int(back[6])
         m.sim_counter = (m.sim_counter + t * n_sims) & 0xFFFFFFFF
         m.n_leaf_evals += int(back[7]) * n_sims
         # a game's boards after n_turns[g] swaps of sides; colour 1's stones are `own` after an even number
         even = (g["n_turns"] % 2 == 0)
         p1, p2 = torch.where(even, own, opp), torch.where(even, opp, own)
-        res = self._finish(SelfPlayResult() if res is None else res, p1, p2, t, 1, game_turns=g["n_turns"])
+        res = self._finish(SelfPlayResult() if res is None else res, p1, p2, t, 1 if park is None else 2,
+                           game_turns=g["n_turns"])
         if record:
             turn = torch.arange(t, device=dev).reshape(t, 1)
             played = turn < g["n_turns"].reshape(1, B)
@@ -1582,6 +1641,7 @@ class SelfPlayEngine(object):
             res.own = torch.where(played, rec["own"][:t], torch.where(tw, p1.reshape(1, B), p2.reshape(1, B)))
             res.opp = torch.where(played, rec["opp"][:t], torch.where(tw, p2.reshape(1, B), p1.reshape(1, B)))
             res.valid, res.move, res.pi = rec["valid"][:t], rec["move"][:t], rec["pi"][:t]
+            setattr(res, res.SCORE_RECORD, rec["score"][:t])
         return res
 
     def _whole_games_in_one_launch(self, n_sims):
@@ -1617,11 +1677,24 @@ class SelfPlayEngine(object):
         searched = on & mcts_moves & ~forced
         return searched.to(torch.uint8), searched, on & ~mcts_moves & ~forced, forced
 
-    def _play_turns(self, n_sims, own, opp, record, res, colours=None):
+    def _solved_turn(self, k, least, t, searched, own, opp):
+        """solve_empties = k at turn t: (the games of `searched` that still search, the games whose move the solver
+        plays) -- those of `searched` at a position of at most k empties.  least: the fewest empties any game started
+        with; a turn takes at most one, so before turn least - k no game can be there and nothing is launched."""
+        if k is None or least - t > k:
+            return searched, None
+        sol = searched & (_empties(own, opp) <= k)
+        return searched & ~sol, sol
+
+    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None):
         """The games from (own, opp) turn by turn into res: a search from every root that is searched, the move, the
         books, in lockstep.  colours None: self-play, every active game searched; else play_match's (B,) int8 colours
-        of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced."""
+        of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced.  solve_empties = k:
+        a game that would search at a position of at most k empties leaves the search mask; the solver (ops.solve_endgame,
+        EXACT: one launch per turn for all such games) gives its move, recorded with valid 3 and the exact score, and
+        its flags join the turn's readback."""
         m, B, T = self.mcts, self.B, self.max_turns
+        k = solve_empties
         dev = own.device
         stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -1637,12 +1710,26 @@ class SelfPlayEngine(object):
             pf = m.policy_fn
         t = 0
         s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
+        least = 0 if k is None else int(_empties(own, opp).min().item())
+        searched, sol = self._solved_turn(k, least, t, searched, own, opp)
+        if sol is not None:
+            s_act = searched.to(torch.uint8)
+        if k is not None:
+            full, none = torch.full_like(own, -1), torch.zeros_like(own)
+            unsolved = torch.zeros(1, dtype=torch.int64, device=dev)
         counts = m.search_counts(s_act).tolist()
         while t < T:
             # ONE readback per turn (below): the flags of this turn's search, the check of its
             # moves, the end-of-game test and the counts the next search starts from
             m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
             move, visits = m.best_move(s_act)
+            if sol is not None:
+                # (a game that is not solved here sends a full board: no search, no refusal)
+                ex = ops.solve_endgame(torch.where(sol, own, full), torch.where(sol, opp, none), mode="exact",
+                                       max_empties=k, check_result=False)
+                unsolved = (ex["solved"] == 0).any().to(torch.int64).reshape(1)
+                move = torch.where(sol, ex["move"], move)
+                searched = searched | sol   # (from here on: the games PV-MCTS moves in)
             if colours is None:
                 mv = torch.where(searched, move, torch.full_like(move, -1))
                 valid, live = s_act, done ^ 1   # game.py:84,108,140 (the games not yet done)
@@ -1661,6 +1748,9 @@ class SelfPlayEngine(object):
                 live = ((done == 0) & ~forced).to(torch.uint8)   # game.py:107,113,140
                 bad_draw = (drawn & (draw == 64)).any().to(torch.int64).reshape(1)
             if record:
+                if sol is not None:
+                    valid = valid + 3 * sol.to(torch.uint8)
+                    rec["score"][t] = torch.where(sol, ex["score"], torch.zeros_like(ex["score"]))
                 rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t] = own, opp, valid, mv
                 rec["pi"][t] = visits * s_act.reshape(B, 1).to(torch.int32)
             m.update_with_move(mv, live)
@@ -1671,16 +1761,23 @@ class SelfPlayEngine(object):
             active, active_next = active_next, active
             t += 1
             s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
-            # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64)
+            searched, sol = self._solved_turn(k, least, t, searched, own, opp)
+            if sol is not None:
+                s_act = searched.to(torch.uint8)
+            # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64, a solved
+            # one a legal move)
             back = torch.cat([m.error_flags(), (mv == -2).any().to(torch.int64).reshape(1),
                               bad_draw, done.all().to(torch.int64).reshape(1),
-                              m.search_counts(s_act)]).tolist()
+                              m.search_counts(s_act)] + ([unsolved] if k is not None else [])).tolist()
             m.raise_errors(back[:5])
             if back[5]:
                 # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
                 raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
             if back[6]:
                 raise _lib.IagoError(_BAD_DRAW)
+            if k is not None and back[10]:
+                raise _lib.IagoError("solve_empties = %d: the endgame solver refused or did not finish a position at "
+                                     "turn %d" % (k, t - 1))
             if t % 2 == 0 and back[7]:
                 break
             counts = back[8:10]
@@ -1688,18 +1785,27 @@ class SelfPlayEngine(object):
         p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
         self._finish(res, p1, p2, t, t)
         if record:
-            for k, v in rec.items():
-                setattr(res, k, v[:t])
+            for name, v in rec.items():
+                setattr(res, res.SCORE_RECORD if name == "score" else name, v[:t])
         return res
 
-    def play(self, n_sims, handicap=None, record=True):
-        """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult."""
-        res = self._one_launch(n_sims, self.B, handicap, record)
+    def play(self, n_sims, handicap=None, record=True, solve_empties=None):
+        """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
+        solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
+        at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
+        (iago_solve_endgame, EXACT: the lowest-indexed move reaching the best final disc difference), recorded with
+        valid 3, pi 0 and the exact score from the mover's view in `score`, and played through update_with_move and the
+        books like a searched move.  The games then end under perfect play: z is the game-theoretic value of every
+        position from the first solved turn on.  sim_counter advances by n_sims per turn all the same; n_leaf_evals
+        counts the valid == 1 rows.  Where whole games run in one launch they hand over at k empties and ONE more launch
+        (iago_play_endgame) plays them all out (launches = 2); the turn loop solves per turn: the same records."""
+        k = _solve_empties_arg(solve_empties)
+        res = self._one_launch(n_sims, self.B, handicap, record, solve_empties=k)
         if res is None:
-            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult())
+            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult(), solve_empties=k)
         return res
 
-    def play_stream(self, n_sims, n_games, handicap=None, record=True):
+    def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -1708,7 +1814,9 @@ class SelfPlayEngine(object):
         apply (another engine, pools that cannot hold a whole game, z_log or trace; and, as a replay, a pool that filled
         up in the launch).  handicap: (n_games,) int64 bit masks of extra colour-2 stones.  The result has n_games
         columns (tuples() give the game ids game_id_base ..); n_turns is the longest game's, `launches` the launches it
-        took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch."""
+        took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch.  solve_empties: as in play() --
+        the stream's games hand over at k empties and one launch plays all n_games out (launches = 2)."""
+        k = _solve_empties_arg(solve_empties)
         m, T = self.mcts, self.max_turns
         n_games = int(n_games)
         if n_games < 1:
@@ -1719,9 +1827,9 @@ class SelfPlayEngine(object):
         if handicap is not None and tuple(handicap.shape) != (n_games,):
             raise ValueError("play_stream: handicap is an (n_games,) int64 tensor")
         plain = getattr(m, "z_log", None) is None and getattr(m, "trace", None) is None
-        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games)
+        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games, solve_empties=k)
         if res is None:
-            res = self._play_batches(n_sims, n_games, handicap, record)
+            res = self._play_batches(n_sims, n_games, handicap, record, k)
         return res
 
     def _match_colours(self, mcts_colour):
@@ -1739,7 +1847,7 @@ class SelfPlayEngine(object):
             raise ValueError("play_match: mcts_colour is 1, 2 or a (%d,) integer tensor of 1 / 2" % self.B)
         return torch.full((self.B,), int(mcts_colour), dtype=torch.int8, device=dev)
 
-    def play_match(self, n_sims, mcts_colour=2, record=True):
+    def play_match(self, n_sims, mcts_colour=2, record=True, solve_empties=None):
         """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
         `game.py --auto` (game.py:96-145,246-262) -- with the engine's nets: in game g PV-MCTS plays colour
         mcts_colour[g] (1 moves first; an int: every game; 2, the default, is the reference's setting) and the policy
@@ -1749,16 +1857,22 @@ class SelfPlayEngine(object):
         final move that is the only one (stone_num > 62) is played by either side without a search and without
         update_with_move (game.py:97-98).  ONE launch of the persistent search where play() takes it, else (and when a
         pool fills up in the launch) the turn loop: the same games record for record.  sim_counter advances by
-        n_sims per turn, searched or not.  Returns a MatchResult."""
+        n_sims per turn, searched or not.  Returns a MatchResult.  solve_empties = k (as in play()): PV-MCTS plays the
+        exact solver's move at its turns of at most k empties (valid 3) -- not the forced final move, which keeps
+        precedence (valid 2), and not the policy's turns.  Such a match ALWAYS runs through the turn loop (launches =
+        its turns): a one-launch match cannot hand its games over, the policy side needs the net workgroups to the last
+        move."""
+        k = _solve_empties_arg(solve_empties)
         col = self._match_colours(mcts_colour)
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
-        res = self._one_launch(n_sims, self.B, None, record, active=codes, res=MatchResult())
+        res = self._one_launch(n_sims, self.B, None, record, applies=k is None, active=codes, res=MatchResult())
         if res is None:
-            res = self._play_turns(n_sims, *self._start_boards(self.B), record, MatchResult(), colours=col)
+            res = self._play_turns(n_sims, *self._start_boards(self.B), record, MatchResult(), colours=col,
+                                   solve_empties=k)
         res.mcts_colour = col
         return res
 
-    def _play_batches(self, n_sims, n_games, handicap, record):
+    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None):
         """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same
         sim_counter, the first n_games columns kept."""
         m, B = self.mcts, self.B
@@ -1772,7 +1886,7 @@ class SelfPlayEngine(object):
                     hc = torch.zeros(B, dtype=torch.int64, device=handicap.device)
                     hc[:w] = handicap[k * B:k * B + w]
                 m.game_id_base, m.sim_counter = base + k * B, s0
-                parts.append((self.play(n_sims, handicap=hc, record=record), w))
+                parts.append((self.play(n_sims, handicap=hc, record=record, solve_empties=solve_empties), w))
         finally:
             m.game_id_base = base
         res = SelfPlayResult()
@@ -1791,7 +1905,7 @@ class SelfPlayEngine(object):
         res.final_p1 = torch.cat([r.final_p1[:w] for r, w in parts])
         res.final_p2 = torch.cat([r.final_p2[:w] for r, w in parts])
         if record:
-            cols = {k: [] for k in ("own", "opp", "valid", "move", "pi")}
+            cols = {k: [] for k in ("own", "opp", "valid", "move", "pi", "score")}
             for r, w in parts:
                 dev, rows = r.z.device, min(r.n_turns, t)
                 pad = t - rows
@@ -1804,6 +1918,7 @@ class SelfPlayEngine(object):
                 cols["valid"].append(torch.cat([r.valid[:rows, :w], r.valid.new_zeros((pad, w))]))
                 cols["move"].append(torch.cat([r.move[:rows, :w], r.move.new_full((pad, w), -1)]))
                 cols["pi"].append(torch.cat([r.pi[:rows, :w], r.pi.new_zeros((pad, w, 64))]))
+                cols["score"].append(torch.cat([r.score[:rows, :w], r.score.new_zeros((pad, w))]))
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))
         return res

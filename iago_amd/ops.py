@@ -979,3 +979,73 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     if check_result:
         _check_endgame_ctl(out, n, max_empties, time_limit_ms)
     return out
+
+
+def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_MAX_TURNS,
+                 max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS, records=None,
+                 check_result=True):
+    """The parked games of a batch to their end under perfect play (iago_play_endgame, include/iago_hip_serving.h):
+    both sides play iago_solve_endgame's EXACT move at every turn, with the books of the whole-game search.
+
+    own / opp (n,) int64, own = the side to move; turn / stones (n,) int32; pass_flg (n,) uint8; parked (n,) uint8,
+    None = every game.  own, opp and turn are UPDATED IN PLACE for the games played: the final position (own = the side
+    that would move next) and the turns the game took.  records: None (fresh zeroed tensors, move -1), or a dict of
+    (max_turns, stride) tensors own, opp (int64), valid (uint8), move, score (int8) whose rows from each game's turn on
+    are written.  Returns the dict of the records + finished (n,) uint8 and ctl (4,) int32.  check_result (one host
+    sync): raise IagoError unless every parked game was played to its end (the clock limit, a game refused for
+    own & opp != 0, more than max_empties empties or a turn outside the records; the result is the error's `result`)."""
+    n = own.numel()
+    dev = own.device
+    for name, t in (("opp", opp), ("turn", turn), ("stones", stones), ("pass_flg", pass_flg)):
+        if t.numel() != n:
+            raise ValueError("own / %s sizes differ" % name)
+    if parked is None:
+        parked = torch.ones(n, dtype=torch.uint8, device=dev)
+    elif parked.numel() != n:
+        raise ValueError("own / parked sizes differ")
+    T = int(max_turns)
+    if records is None:
+        records = dict(own=torch.zeros((T, n), dtype=torch.int64, device=dev),
+                       opp=torch.zeros((T, n), dtype=torch.int64, device=dev),
+                       valid=torch.zeros((T, n), dtype=torch.uint8, device=dev),
+                       move=torch.full((T, n), -1, dtype=torch.int8, device=dev),
+                       score=torch.zeros((T, n), dtype=torch.int8, device=dev))
+    stride = records["own"].shape[1] if records["own"].dim() == 2 else n
+    for k in ("own", "opp", "valid", "move", "score"):
+        if tuple(records[k].shape) != (T, stride):
+            raise ValueError("records[%r] must be (max_turns, stride) = (%d, %d)" % (k, T, stride))
+    out = dict(records)
+    out["finished"] = torch.empty(n, dtype=torch.uint8, device=dev)
+    out["ctl"] = torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev)
+    a = _lib.PlayEndgameArgs()
+    a.own, a.opp, a.turn = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), _dev(turn, torch.int32, "turn")
+    a.stones, a.pass_flg = _dev(stones, torch.int32, "stones"), _dev(pass_flg, torch.uint8, "pass_flg")
+    a.parked, a.n, a.stride = _dev(parked, torch.uint8, "parked"), n, stride
+    a.max_turns, a.max_empties, a.time_limit_ms = T, int(max_empties), int(time_limit_ms)
+    a.rec_own, a.rec_opp = _dev(out["own"], torch.int64, "records own"), _dev(out["opp"], torch.int64, "records opp")
+    a.rec_valid, a.rec_move = _dev(out["valid"], torch.uint8, "records valid"), _dev(out["move"], torch.int8, "records move")
+    a.rec_score = _dev(out["score"], torch.int8, "records score")
+    a.finished, a.ctl = _dev(out["finished"], torch.uint8, "finished"), _dev(out["ctl"], torch.int32, "ctl")
+    check(_lib.lib().iago_play_endgame(C.byref(a), _stream()), "iago_play_endgame")
+    if check_result:
+        back = torch.cat([out["ctl"].to(torch.int64), (out["finished"] != parked).sum().reshape(1)]).tolist()
+        check_play_endgame(back, out, max_empties, time_limit_ms)
+    return out
+
+
+def check_play_endgame(back, out, max_empties, time_limit_ms):
+    """Raise IagoError unless iago_play_endgame played every parked game to its end; back: its four ctl words and the
+    number of games with finished != parked, read back by the caller."""
+    gave_up, _, refused, overflow, unfinished = (int(v) for v in back)
+    if not (gave_up or refused or overflow or unfinished):
+        return
+    if gave_up:
+        what = "gave up at its clock limit (%d ms)" % time_limit_ms
+    elif refused:
+        what = ("%d games refused (own & opp != 0, more than max_empties = %d empties, or a turn outside the records)"
+                % (refused, max_empties))
+    else:
+        what = "a game needed more stack frames than max_empties = %d sizes (ctl[3] set)" % max_empties
+    err = _lib.IagoError("iago_play_endgame: %s: %d games not played to their end" % (what, unfinished))
+    err.result = out
+    raise err

@@ -86,6 +86,70 @@ typedef struct iago_endgame_args {
  */
 IAGO_API int iago_solve_endgame(const iago_endgame_args *args, void *stream);
 
+typedef struct iago_play_endgame_args {
+    uint64_t *own;           /* [n] in: the position at the game's turn, own = the side to move; out: the final position,
+                                own = the side that would move next (colour 1 after an even number of turns) */
+    uint64_t *opp;           /* [n] in / out */
+    int32_t *turn;           /* [n] in: the turn the game stands at, 0 .. max_turns - 1; out: the turns it took */
+    const int32_t *stones;   /* [n] the game's stone count (game.py:32: 4 at the start, + 1 per move) */
+    const uint8_t *pass_flg; /* [n] the turn before this one was a pass */
+    const uint8_t *parked;   /* [n] 1: play this game; 0: not touched (finished stays 0) */
+    int64_t n;
+    int64_t stride;          /* >= n: the records' row of turn t and game g is t * stride + g */
+    int32_t max_turns;       /* 1 .. IAGO_MAX_TURNS: the records' rows; a game ends there at the latest */
+    int32_t max_empties;     /* 0 .. IAGO_ENDGAME_MAX_EMPTIES: sizes the search stack; a game with more empties is refused */
+    int32_t time_limit_ms;   /* 1 .. IAGO_ENDGAME_MAX_TIME_MS */
+    int32_t reserved0;       /* 0 */
+    uint64_t *rec_own;       /* [max_turns][stride] out: the position before the turn (own = mover) */
+    uint64_t *rec_opp;
+    uint8_t *rec_valid;      /* 3: a solved move; 0: a pass or no turn */
+    int8_t *rec_move;        /* the move played, -1 = pass / no turn */
+    int8_t *rec_score;       /* the exact final disc difference from the mover's view (0 where valid is 0) */
+    uint8_t *finished;       /* [n] out: 1 = the game was played to its end */
+    uint32_t *ctl;           /* [IAGO_ENDGAME_CTL_WORDS] cleared by the call; [0] != 0: gave up, [2]: games refused */
+    int64_t reserved[4];     /* 0 */
+} iago_play_endgame_args;
+
+/*
+ * The parked games of a batch (parked[g] = 1) to their end under perfect play, one lane per game, each on its own clock:
+ * at every turn the mover's position is solved as iago_solve_endgame does in mode EXACT (same search, same move: the
+ * lowest-indexed one that reaches the best final disc difference) and the move is played with the books of the whole-game
+ * search (iago_mcts_search_persistent with max_turns > 0; game.py:117-142,253-255): a stone per move, a pass when the
+ * mover has no move, a pass after a pass sets stones = 64, `stones >= 64` is tested after odd turns only, and the game
+ * ends at an even turn or at max_turns.  Every turn from the game's `turn` on writes its row of the records; rows before
+ * it and rows of other games are not touched.  At the end turn / own / opp hold the game's turn count and final position
+ * and finished[g] = 1.  A game with own & opp != 0, more than max_empties empties or a turn outside 0 .. max_turns - 1 is
+ * refused (finished[g] = 0, ctl[2] counts it, nothing else written).  finished[] and ctl are cleared on `stream` before
+ * the launch; it stops on its own clock after time_limit_ms (ctl[0] != 0, the unfinished games keep finished = 0 and
+ * their turn / own / opp).  Host-side refusals (IAGO_ERR_INVALID, nothing launched): a null args / ctl, a null array
+ * with n > 0, n < 0, stride < n, max_turns, max_empties or time_limit_ms out of range, reserved fields not 0.
+ */
+IAGO_API int iago_play_endgame(const iago_play_endgame_args *args, void *stream);
+
+typedef struct iago_search_park_args {
+    int32_t park_empties;         /* 0 .. IAGO_ENDGAME_MAX_EMPTIES */
+    int32_t reserved0;            /* 0 */
+    uint8_t *parked;              /* [games] out: 1 = the game was handed over (cleared by the call) */
+    int32_t *stones;              /* [games] out, where parked: the game's stone count */
+    uint8_t *pass_flg;            /* [games] out, where parked: the turn before was a pass */
+    iago_search_streams *streams; /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    int64_t reserved[4];          /* 0 */
+} iago_search_park_args;
+
+/*
+ * Whole self-play games (iago_mcts_search_persistent with max_turns > 0, a stream included) that HAND OVER at
+ * park_empties: a game whose turn would be searched -- the mover can move and the game is not over -- at a position with
+ * 64 - popcount(own | opp) <= park_empties runs no search there.  It writes n_turns (the turn it stands at), game_own /
+ * game_opp (own = the mover), stones, pass_flg and parked = 1, all indexed by the game's id ([games] = games_total, or
+ * n_games), and is done: its workgroup goes on as after a finished game (net work, or the stream's next game).  Its
+ * records hold the turns before that one.  Everything before the hand-over is iago_mcts_search_persistent's, bit for
+ * bit; iago_play_endgame plays the parked games to their end.  Refused (IAGO_ERR_INVALID): null args or outputs,
+ * max_turns == 0, a park_empties outside 0 .. 20, reserved fields not 0, and match codes (2 / 3) in `active` -- the
+ * policy side of a match needs the net workgroups to its last move; `active` is read back on `stream` for this check
+ * when it is device memory (not in a stream, which does not read it).
+ */
+IAGO_API int iago_mcts_search_park(const iago_mcts_search_args *args, const iago_search_park_args *park, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
