@@ -1,5 +1,9 @@
-// mcts_dev.hpp -- device helpers of the tree kernels (mcts_kernels.hip) that the persistent search kernel
-// (search_kernel.hip) shares: node initialisation and the argmax butterfly of Node.select (MCTS.py:39-49).
+// mcts_dev.hpp -- the tree arithmetic of MCTS.py, stated once for every search kernel: the per-playout kernels
+// (mcts_kernels.hip) and the persistent, wave and park searches (search_kernel.hip) build bit-identical trees because they
+// call these functions.  Node.select's score and its argmax butterfly, the stone of a selection, Node.expand, the leaf
+// mix, the value cache, Node.update, a fresh root and the z-log record; what a schedule adds (where a prior is read,
+// which lane writes, queues, paths) stays with its kernel.  puct_score and leaf_mix are compiled with floating-point
+// contraction off: every product and sum is rounded on its own, as numpy rounds them.
 #pragma once
 #include "abi_common.hpp"
 #include "othello_dev.hpp"
@@ -28,6 +32,65 @@ __device__ __forceinline__ void init_node(const Tree &T, int64_t i, int parent, 
         T.nodes[i].v = __builtin_nanf(""); // value_func(node) not evaluated yet
 }
 
+// Node(None, 1.0) as game g's only node, its root (MCTS.py:81,154; one lane)
+__device__ __forceinline__ void fresh_root(const Tree &T, int64_t g, int64_t base)
+{
+    init_node(T, base, -1, -2, 1.0f + 0.1f);
+    T.n_nodes[g] = 1;
+    T.root[g] = 0;
+}
+
+// the two halves of a node record: s = {n_visits, q, p, v}, l = {first_child, parent, action | n_children << 8, vv}
+__device__ __forceinline__ void node_record(const Tree &T, int64_t at, uint4 &s, uint4 &l)
+{
+    s = ((const uint4 *)&T.nodes[at])[0];
+    l = ((const uint4 *)&T.nodes[at])[1];
+}
+
+// ---- Node.select (MCTS.py:39-49)
+
+// Node.get_value (MCTS.py:75-76) of a child with prior p, value q and n visits under a parent with sq =
+// np.sqrt(parent.n_visits): float32 c_puct * P, float64 sqrt, divide and add, as numpy >= 2 promotes them (MCTS.py:49)
+__device__ __forceinline__ double puct_score(float c_puct, float p, float q, int n, double sq)
+{
+#pragma clang fp contract(off)
+    const float cp = c_puct * p;
+    const double u = (double)cp * sq / (0.01 + (double)n);
+    return (double)q + u;
+}
+
+// in-flight visits (vv) of a wave search: the score of a child when a playout of the wave is on its way through it --
+// n + vv visits, the in-flight ones counted as a loss of `vloss` each.  vv == 0: puct_score exactly.  (No contraction:
+// the restatement in tests/wave_mcts.py rounds every product and difference on its own)
+__device__ __forceinline__ double wave_score(float c_puct, float p, float q, int n, int vv, double sq, double vloss)
+{
+#pragma clang fp contract(off)
+    const float cp = c_puct * p;
+    const int nc = n + vv;
+    const double u = (double)cp * sq / (0.01 + (double)nc);
+    const double qe = vv == 0 ? (double)q : ((double)q * (double)n - vloss * (double)vv) / (double)nc;
+    return qe + u;
+}
+
+// the score of child j, whose record is (s, l), against the best of its lane so far; strict `>`: the first maximum wins
+// (python max, MCTS.py:46).  pl: the best child's first_child, n_visits, action | n_children << 8 (| vv << 16), v
+template <bool WAVE>
+__device__ __forceinline__ void score_child(float c_puct, double vloss, uint4 s, uint4 l, int j, double sq, double &best_v,
+                                            int &best_i, uint32_t (&pl)[4])
+{
+    const float p = __uint_as_float(s.z), q = __uint_as_float(s.y);
+    const int n = (int)s.x;
+    // (vv < 2^16: at most 32 playouts in flight)
+    const double v = WAVE ? wave_score(c_puct, p, q, n, (int)l.w, sq, vloss) : puct_score(c_puct, p, q, n, sq);
+    if (v > best_v) {
+        best_v = v;
+        best_i = j;
+        pl[0] = l.x, pl[1] = (uint32_t)n, pl[2] = WAVE ? (l.z & 0xFFFFu) | (l.w << 16) : l.z & 0xFFFFu, pl[3] = s.w;
+    }
+}
+
+// python's max over the children (MCTS.py:46) across the 8 lanes of a game: the larger score, of equal scores the
+// smaller index -- every lane offers its first maximum, so the first maximum wins
 template <int CTRL>
 __device__ __forceinline__ void argmax_step(double &v, int &idx)
 {
@@ -56,6 +119,124 @@ __device__ __forceinline__ void argmax_step_payload(double &v, int &idx, uint32_
         const uint32_t o = dpp_u32<CTRL>(pl[i]);
         pl[i] = take ? o : pl[i];
     }
+}
+
+// GameFunctions.place_stone(state, a, c); c = 3 - c (MCTS.py:131-132): move a (< 0: a pass, nothing placed) and the swap
+// of sides.  Every lane of the group takes part (group8_flips)
+__device__ __forceinline__ void place_stone(uint64_t &own, uint64_t &opp, int a, const Lane8 &L)
+{
+    const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
+    uint64_t o = own, p = opp;
+    if (a >= 0) {
+        const uint64_t bit = 1ull << (a & 63);
+        o = own | f | bit;
+        p = opp & ~f & ~bit;
+    }
+    own = p;
+    opp = o;
+}
+
+// ---- Node.expand (MCTS.py:27-37, 109-121), the 8 lanes of a game together
+
+// k nodes of game g's pool, taken by the group's lane 0 (`lane0`; false on every lane: nothing is taken): first child + 1
+// on every lane of the group, 0 = no room (reported in T.overflow) or nothing taken
+__device__ __forceinline__ uint32_t alloc_children(const Tree &T, int64_t g, int k, bool lane0)
+{
+    uint32_t fc1 = 0;
+    if (lane0) {
+        const int at = T.n_nodes[g];
+        if (at + k <= T.capacity) {
+            T.n_nodes[g] = at + k;
+            fc1 = (uint32_t)at + 1u;
+        } else {
+            T.overflow[g] = 1;
+        }
+    }
+    return group8_add(fc1);
+}
+
+// the children of `node` for its legal moves lg, from pool index fc on.  No move (a pass child, action -1) or a single
+// one: Node(node, 1.0) without a net (MCTS.py:112-117), by lane 0.  Else Node.expand (MCTS.py:27-37): lane r creates the
+// children of board row r in ascending order of the move, child a with prior(a) + 0.1 (MCTS.py:19)
+template <class Prior>
+__device__ __forceinline__ void make_children(const Tree &T, int64_t base, int fc, int node, uint64_t lg, uint32_t r,
+                                              Prior prior)
+{
+    if ((lg & (lg - 1ull)) == 0ull) {
+        if (r == 0u)
+            init_node(T, base + fc, node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
+    } else {
+        uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
+        int at = fc + __popcll(lg & ((1ull << (8u * r)) - 1ull));
+        while (row) {
+            const int a = (int)(8u * r) + __builtin_ctz(row);
+            row &= row - 1u;
+            init_node(T, base + at, node, a, prior(a) + 0.1f);
+            at++;
+        }
+    }
+}
+
+// the parent's side of an expansion (one lane)
+__device__ __forceinline__ void link_children(const Tree &T, int64_t parent, int fc, int k)
+{
+    T.nodes[parent].first_child = fc;
+    T.nodes[parent].n_children = (uint8_t)k;
+}
+
+// ---- the leaf's value (MCTS.py:123-125) and Node.update_recursive (MCTS.py:51-72)
+
+// (1 - lmbda) * v + lmbda * z with numpy >= 2 scalar promotion (MCTS.py:123-125): the python-float factors are rounded to
+// float32, products and sum in float32.  (v is not read at lmbda = 1, z not at lmbda = 0: MCTS.py:124-125 are skipped)
+__device__ __forceinline__ float leaf_mix(float lmbda, float v, int8_t z)
+{
+#pragma clang fp contract(off)
+    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * v : 0.0f;
+    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)z) : 0.0f;
+    return a + b;
+}
+
+// value_func(leaf) (MCTS.py:97-103,124) is a pure function of the leaf's position: with a value cache (T.v) the net runs
+// only for the leaves it has not seen, whose fresh values vg are stored now (by the lanes with `writer`); the others
+// take the stored value.  (Every lane of a game may read the slot while one writes it: the loads of a wave come before
+// its stores)
+__device__ __forceinline__ float cached_value(float *slot, float vg, bool writer)
+{
+    const float cached = *slot;
+    if (cached == cached)
+        return cached;
+    if (writer)
+        *slot = vg;
+    return vg;
+}
+
+// Node.update (MCTS.py:58-63) with leaf value lv: (n_visits, Q) as one 8-byte load and one 8-byte store
+__device__ __forceinline__ void visit(const Tree &T, int64_t at, float lv)
+{
+    uint2 *nq = (uint2 *)&T.nodes[at];
+    const uint2 old = *nq;
+    const int n = (int)old.x + 1;                // MCTS.py:61
+    const float q = __uint_as_float(old.y);
+    *nq = make_uint2((uint32_t)n, __float_as_uint(q + (lv - q) / (float)n)); // MCTS.py:63
+}
+
+// Node.update_recursive (MCTS.py:65-72) from `node` up to the root: the same value at every level, no sign flip
+__device__ __forceinline__ void backup_climb(const Tree &T, int64_t base, int node, float lv)
+{
+    for (int depth = 0; node >= 0 && depth <= MAX_DEPTH; depth++) {
+        visit(T, base + node, lv);
+        node = T.nodes[base + node].parent;
+    }
+}
+
+// Diagnostic record of the parity tests (tests/test_mcts_production_gpu.py): the z every playout of game g backed up, in
+// playout order -- what the oracle's rollout_fn replays (z_log [rows][n_games], z_log_n [n_games] rows written so far)
+__device__ __forceinline__ void log_z(int8_t *z_log, int32_t *z_log_n, int rows, int64_t g, int64_t n_games, int8_t zg)
+{
+    const int k = z_log_n[g];
+    z_log_n[g] = k + 1;
+    if (k < rows)
+        z_log[(int64_t)k * n_games + g] = zg;
 }
 
 } // namespace iago_mcts

@@ -8,13 +8,13 @@
 // once per simulation for all games at once.
 //
 // Mapping: 8 lanes per game (othello_dev.hpp).  In select, the children of a
-// node are scored 8 at a time (lane j takes children j, j+8, ...; their
-// (n, Q, P) are contiguous, so a group reads 3 coalesced 32-byte runs), the
-// argmax is a 3-step DPP butterfly on (float64 score, child index), and the
-// chosen move is applied with the direction-per-lane flip primitive.
-// Scores are float64 exactly as the reference computes them under numpy >= 2
-// (float32 P and Q, float64 sqrt / divide / add); no FMA contraction can occur
-// in these expressions (no multiply feeds an add).
+// node are scored 8 at a time (lane j takes children j, j+8, ...; a child's
+// record is one 32-byte sector), the argmax is a 3-step DPP butterfly on
+// (float64 score, child index), and the chosen move is applied with the
+// direction-per-lane flip primitive.  The arithmetic itself -- the score, the
+// stone, the expansion, the leaf mix, the visit update -- is mcts_dev.hpp's,
+// shared with search_kernel.hip: the kernels here are schedules of it (which
+// thread does what, where a prior or a value is read, what is queued).
 #include "mcts_dev.hpp"
 
 using namespace iago;
@@ -27,9 +27,7 @@ __global__ __launch_bounds__(BLOCK) void reset_kernel(Tree T, const uint8_t *__r
     const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= T.n_games || (mask && !mask[g]))
         return;
-    init_node(T, g * T.capacity, -1, -2, 1.0f + 0.1f); // Node(None, 1.0), MCTS.py:81
-    T.n_nodes[g] = 1;
-    T.root[g] = 0;
+    fresh_root(T, g, g * T.capacity);
     T.overflow[g] = 0;
 }
 
@@ -65,15 +63,13 @@ __global__ __launch_bounds__(BLOCK) void select_kernel(
         const int pn = descending ? T.nodes[base + node].n_visits : 0;
         st_levels += descending ? 1 : 0;
         st_children += k;
-        const double sq = sqrt((double)pn); // np.sqrt(parent.n_visits), MCTS.py:49
+        const double sq = sqrt((double)pn);
         double best_v = -INFINITY;
         int best_i = 0x7fffffff;
         for (int j = (int)L.l8; j < k; j += 8) {
             const int64_t c = base + fc + j;
-            const float cp = c_puct * T.nodes[c].p;                        // float32, MCTS.py:49
-            const double u = (double)cp * sq / (0.01 + (double)T.nodes[c].n_visits);
-            const double v = (double)T.nodes[c].q + u;                     // get_value, MCTS.py:75-76
-            if (v > best_v) { // strict: the first maximum wins (python max, MCTS.py:46)
+            const double v = puct_score(c_puct, T.nodes[c].p, T.nodes[c].q, T.nodes[c].n_visits, sq);
+            if (v > best_v) { // strict: the lane's first maximum
                 best_v = v;
                 best_i = j;
             }
@@ -82,19 +78,11 @@ __global__ __launch_bounds__(BLOCK) void select_kernel(
         argmax_step<DPP_XOR2>(best_v, best_i);
         argmax_step<DPP_HALF_MIRROR>(best_v, best_i);
         const int child = fc + best_i;
-        const int a = descending ? (int)T.nodes[base + child].action : -1;
-        // GameFunctions.place_stone(state, action, c); c = 3 - c  (MCTS.py:131-132)
-        const uint64_t f =
-            group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
+        uint64_t c_own = own, c_opp = opp;
+        place_stone(c_own, c_opp, descending ? (int)T.nodes[base + child].action : -1, L);
         if (descending) {
-            uint64_t no = own, np_ = opp;
-            if (a >= 0) {
-                const uint64_t bit = 1ull << (a & 63);
-                no = own | f | bit;
-                np_ = opp & ~f & ~bit;
-            }
-            own = np_;
-            opp = no;
+            own = c_own;
+            opp = c_opp;
             node = child;
         }
     }
@@ -132,42 +120,14 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(Tree T, const int32_t *__
     const int node = live ? cur_node[g] : 0;
     const uint64_t lg = live ? legal[g] : 0ull;
     const int k = lg ? __popcll(lg) : 1;
-    // lane 0 allocates k nodes; every lane of the group learns the start
-    uint32_t fc1 = 0; // first child + 1, 0 = no room / already expanded
-    if (live && r == 0u && T.nodes[base + node].first_child < 0) {
-        const int at = T.n_nodes[g];
-        if (at + k <= T.capacity) {
-            T.n_nodes[g] = at + k;
-            fc1 = (uint32_t)at + 1u;
-        } else {
-            T.overflow[g] = 1;
-        }
-    }
-    fc1 = group8_add(fc1);
+    // (0: no room, or already expanded)
+    const uint32_t fc1 = alloc_children(T, g, k, live && r == 0u && T.nodes[base + node].first_child < 0);
     if (!live || fc1 == 0u)
         return;
     const int fc = (int)fc1 - 1;
-    if (lg == 0ull || k == 1) {
-        // pass child / single legal move: Node(node, 1), no net (MCTS.py:112-117)
-        if (r == 0u) {
-            const int a = lg ? (int)__builtin_ctzll(lg) : -1;
-            init_node(T, base + fc, node, a, 1.0f + 0.1f);
-        }
-    } else {
-        // Node.expand (MCTS.py:27-37): lane r creates the children of board row r
-        uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
-        int at = fc + __popcll(lg & ((1ull << (8u * r)) - 1ull));
-        while (row) {
-            const int a = (int)(8u * r) + __builtin_ctz(row);
-            row &= row - 1u;
-            init_node(T, base + at, node, a, probs[i * 64 + a] + 0.1f); // MCTS.py:19
-            at++;
-        }
-    }
-    if (r == 0u) {
-        T.nodes[base + node].first_child = fc;
-        T.nodes[base + node].n_children = (uint8_t)k;
-    }
+    make_children(T, base, fc, node, lg, r, [&](int a) { return probs[i * 64 + a]; });
+    if (r == 0u)
+        link_children(T, base + node, fc, k);
 }
 
 __global__ __launch_bounds__(BLOCK) void leaf_values_kernel(const float *__restrict__ v,
@@ -178,11 +138,7 @@ __global__ __launch_bounds__(BLOCK) void leaf_values_kernel(const float *__restr
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n)
         return;
-    // (1-lmbda)*v + lmbda*z with numpy>=2 scalar promotion (MCTS.py:123-125):
-    // the python-float factors are rounded to float32, products and sum in float32
-    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * v[i] : 0.0f;
-    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)z[i]) : 0.0f;
-    out[i] = a + b;
+    out[i] = leaf_mix(lmbda, lmbda < 1.0f ? v[i] : 0.0f, lmbda > 0.0f ? z[i] : (int8_t)0);
 }
 
 __global__ __launch_bounds__(BLOCK) void backup_kernel(Tree T, const uint8_t *__restrict__ active,
@@ -192,16 +148,19 @@ __global__ __launch_bounds__(BLOCK) void backup_kernel(Tree T, const uint8_t *__
     const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= T.n_games || !active[g])
         return;
-    const int64_t base = g * (int64_t)T.capacity;
-    const float lv = leaf_value[g];
-    int node = cur_node[g];
-    for (int depth = 0; node >= 0 && depth <= MAX_DEPTH; depth++) {
-        const int n = T.nodes[base + node].n_visits + 1; // MCTS.py:61
-        const float q = T.nodes[base + node].q;
-        T.nodes[base + node].n_visits = n;
-        T.nodes[base + node].q = q + (lv - q) / (float)n; // MCTS.py:63
-        node = T.nodes[base + node].parent;               // MCTS.py:71-72, same value, no sign flip
-    }
+    backup_climb(T, g * (int64_t)T.capacity, cur_node[g], leaf_value[g]);
+}
+
+// The mixed value of game g's playout: the value net's v[g], or with a value cache (T.v) the one stored in an active
+// game's leaf -- the net then ran only for the leaves without one (iago_mcts_fresh_leaves), whose v[g] is stored now
+// by the lanes with `writer` -- mixed with the rollout's z[g]
+__device__ __forceinline__ float playout_value(const Tree &T, int64_t leaf_at, bool act, const float *__restrict__ v,
+                                               const int8_t *__restrict__ z, float lmbda, int64_t g, bool writer)
+{
+    float vg = (lmbda < 1.0f) ? v[g] : 0.0f;
+    if (T.has_v && lmbda < 1.0f && act)
+        vg = cached_value(&T.nodes[leaf_at].v, vg, writer);
+    return leaf_mix(lmbda, vg, lmbda > 0.0f ? z[g] : (int8_t)0);
 }
 
 // leaf mix (leaf_values_kernel) + backup (backup_kernel) in one launch; every game's mixed
@@ -218,34 +177,13 @@ __global__ __launch_bounds__(BLOCK) void mix_backup_kernel(Tree T, const uint8_t
         *counter += 1u;
     if (g >= T.n_games)
         return;
-    // value_func(leaf) (MCTS.py:97-103,124) is a pure function of the leaf's position: with a
-    // value cache (T.v) the net ran only for the leaves it has not seen (iago_mcts_fresh_leaves),
-    // whose values are in v[g] and are stored now; the others take the stored value
     const int64_t base = g * (int64_t)T.capacity;
-    float vg = (lmbda < 1.0f) ? v[g] : 0.0f;
-    if (T.has_v && lmbda < 1.0f && active[g]) {
-        float *slot = &T.nodes[base + cur_node[g]].v;
-        const float cached = *slot;
-        if (cached != cached)
-            *slot = vg;
-        else
-            vg = cached;
-    }
-    // (1-lmbda)*v + lmbda*z exactly as leaf_values_kernel (MCTS.py:123-125)
-    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * vg : 0.0f;
-    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)z[g]) : 0.0f;
-    const float lv = a + b;
+    const int leaf = cur_node[g];
+    const float lv = playout_value(T, base + leaf, active[g] != 0, v, z, lmbda, g, true);
     leaf_value[g] = lv;
     if (!active[g])
         return;
-    int node = cur_node[g];
-    for (int depth = 0; node >= 0 && depth <= MAX_DEPTH; depth++) {
-        const int n = T.nodes[base + node].n_visits + 1; // MCTS.py:61
-        const float q = T.nodes[base + node].q;
-        T.nodes[base + node].n_visits = n;
-        T.nodes[base + node].q = q + (lv - q) / (float)n; // MCTS.py:63
-        node = T.nodes[base + node].parent;
-    }
+    backup_climb(T, base, leaf, lv);
 }
 
 __global__ __launch_bounds__(BLOCK) void best_move_kernel(Tree T, const uint8_t *__restrict__ active,
@@ -294,9 +232,7 @@ __global__ __launch_bounds__(BLOCK) void advance_root_kernel(Tree T, const uint8
             return;
         }
     }
-    init_node(T, base, -1, -2, 1.0f + 0.1f); // self.root = Node(None, 1.0) (MCTS.py:154)
-    T.n_nodes[g] = 1;
-    T.root[g] = 0;
+    fresh_root(T, g, base);
 }
 
 // ---- policy look-ahead (iago_mcts_mix_backup_lookahead / _store_priors / _expand_cached).
@@ -341,14 +277,34 @@ struct Lookahead {
     uint64_t *va_x_own, *va_x_opp;
 };
 
-// Diagnostic record of the parity tests (tests/test_mcts_production_gpu.py): the z every playout of
-// game g backed up, in playout order -- what the oracle's rollout_fn replays.
-__device__ __forceinline__ void log_z(const Lookahead &A, int64_t g, int64_t n_games, int8_t zg)
+// The leaf of a playout crosses the trigger exactly once (it gains one visit per playout that ends on it): its
+// position (own = the side to move) is queued for the next flush and the leaf tagged with its sequence number (one lane)
+__device__ __forceinline__ void queue_leaf(const Lookahead &A, const Tree &T, int64_t g, int64_t leaf_at, uint64_t own,
+                                           uint64_t opp)
 {
-    const int k = A.z_log_n[g];
-    A.z_log_n[g] = k + 1;
-    if (k < A.z_log_rows)
-        A.z_log[(int64_t)k * n_games + g] = zg;
+    const int pos = atomicAdd(A.q_count, 1);
+    if (pos < A.q_capacity) {
+        const int seq = A.next_seq[g];
+        A.next_seq[g] = seq + 1;
+        T.nodes[leaf_at].first_child = -2 - seq;
+        A.q_own[pos] = own;
+        A.q_opp[pos] = opp;
+        A.q_game[pos] = (int32_t)g;
+        A.q_seq[pos] = seq;
+    } else {
+        *A.error = 1;
+    }
+}
+
+// The priors of the leaf tagged `tag` in game g's cache; A.error = 2 (by the lanes with `report`) when there are none:
+// the leaf was never queued, or its slot has been recycled
+__device__ __forceinline__ const float *cached_priors(const Lookahead &A, int64_t g, int tag, bool report)
+{
+    const int seq = -2 - tag;
+    const int slot = tag <= -2 ? seq % A.slots : 0;
+    if ((tag > -2 || A.cache_seq[g * A.slots + slot] != seq) && report)
+        *A.error = 2;
+    return A.cache + (g * A.slots + slot) * 64;
 }
 
 __global__ __launch_bounds__(BLOCK) void mix_backup_lookahead_kernel(
@@ -364,53 +320,17 @@ __global__ __launch_bounds__(BLOCK) void mix_backup_lookahead_kernel(
         *A.clear_word = 0;
     if (g >= T.n_games)
         return;
-    // value_func(leaf) (MCTS.py:97-103,124) is a pure function of the leaf's position: with a
-    // value cache (T.v) the net ran only for the leaves it has not seen (iago_mcts_fresh_leaves),
-    // whose values are in v[g] and are stored now; the others take the stored value
     const int64_t base = g * (int64_t)T.capacity;
-    float vg = (lmbda < 1.0f) ? v[g] : 0.0f;
-    if (T.has_v && lmbda < 1.0f && active[g]) {
-        float *slot = &T.nodes[base + cur_node[g]].v;
-        const float cached = *slot;
-        if (cached != cached)
-            *slot = vg;
-        else
-            vg = cached;
-    }
-    // (1-lmbda)*v + lmbda*z exactly as leaf_values_kernel (MCTS.py:123-125)
-    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * vg : 0.0f;
-    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)z[g]) : 0.0f;
-    const float lv = a + b;
+    const int leaf = cur_node[g];
+    const float lv = playout_value(T, base + leaf, active[g] != 0, v, z, lmbda, g, true);
     leaf_value[g] = lv;
     if (!active[g])
         return;
     if (A.z_log && lmbda > 0.0f)
-        log_z(A, g, T.n_games, z[g]);
-    const int leaf = cur_node[g];
-    int node = leaf;
-    for (int depth = 0; node >= 0 && depth <= MAX_DEPTH; depth++) {
-        const int n = T.nodes[base + node].n_visits + 1; // MCTS.py:61
-        const float q = T.nodes[base + node].q;
-        T.nodes[base + node].n_visits = n;
-        T.nodes[base + node].q = q + (lv - q) / (float)n; // MCTS.py:63
-        node = T.nodes[base + node].parent;
-    }
-    // the leaf of this playout crosses the trigger exactly once (it gains one visit per playout
-    // that ends on it): queue its position for the next flush
-    if (T.nodes[base + leaf].n_visits == A.trigger && T.nodes[base + leaf].first_child == -1) {
-        const int pos = atomicAdd(A.q_count, 1);
-        if (pos < A.q_capacity) {
-            const int seq = A.next_seq[g];
-            A.next_seq[g] = seq + 1;
-            T.nodes[base + leaf].first_child = -2 - seq;
-            A.q_own[pos] = cur_own[g];
-            A.q_opp[pos] = cur_opp[g];
-            A.q_game[pos] = (int32_t)g;
-            A.q_seq[pos] = seq;
-        } else {
-            *A.error = 1;
-        }
-    }
+        log_z(A.z_log, A.z_log_n, A.z_log_rows, g, T.n_games, z[g]);
+    backup_climb(T, base, leaf, lv);
+    if (T.nodes[base + leaf].n_visits == A.trigger && T.nodes[base + leaf].first_child == -1)
+        queue_leaf(A, T, g, base + leaf, cur_own[g], cur_opp[g]);
 }
 
 // The same backup with the path the descent recorded (iago_mcts_descend with A.path): the 8 lanes
@@ -458,28 +378,13 @@ __global__ __launch_bounds__(BLOCK) void mix_backup_path_kernel(
             A.y_done[g] += 1;
     }
     const int leaf = cur_node[g];
-    float vg = (lmbda < 1.0f) ? v[g] : 0.0f;
-    if (T.has_v && lmbda < 1.0f && act) {
-        // (every lane reads the slot, lane 0 fills it: the loads of a wave come before its stores)
-        float *slot = &T.nodes[base + leaf].v;
-        const float cached = *slot;
-        if (cached != cached) {
-            if (r == 0u)
-                *slot = vg;
-        } else {
-            vg = cached;
-        }
-    }
-    // (1-lmbda)*v + lmbda*z exactly as leaf_values_kernel (MCTS.py:123-125)
-    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * vg : 0.0f;
-    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)z[g]) : 0.0f;
-    const float lv = a + b;
+    const float lv = playout_value(T, base + leaf, act, v, z, lmbda, g, r == 0u);
     if (r == 0u && (act || !A.y_wait))
         leaf_value[g] = lv;
     if (!act)
         return;
     if (A.z_log && lmbda > 0.0f && r == 0u)
-        log_z(A, g, T.n_games, z[g]);
+        log_z(A.z_log, A.z_log_n, A.z_log_rows, g, T.n_games, z[g]);
     // lane 0 decides the queueing from the leaf's count BEFORE this playout (+ 1 = after it)
     int leaf_n = 0, leaf_tag = 0;
     if (r == 0u) {
@@ -488,28 +393,10 @@ __global__ __launch_bounds__(BLOCK) void mix_backup_path_kernel(
     }
     const int len = A.path_len[g];
     const int32_t *path = A.path + g * (int64_t)A.path_stride;
-    for (int d = (int)r; d < len; d += 8) {
-        const int node = path[d];
-        uint2 *nq = (uint2 *)&T.nodes[base + node]; // (n_visits, Q): one 8-byte load, one 8-byte store
-        const uint2 old = *nq;
-        const int n = (int)old.x + 1;                // MCTS.py:61
-        const float q = __uint_as_float(old.y);
-        *nq = make_uint2((uint32_t)n, __float_as_uint(q + (lv - q) / (float)n)); // MCTS.py:63
-    }
-    if (r == 0u && leaf_n + 1 == A.trigger && leaf_tag == -1) {
-        const int pos = atomicAdd(A.q_count, 1);
-        if (pos < A.q_capacity) {
-            const int seq = A.next_seq[g];
-            A.next_seq[g] = seq + 1;
-            T.nodes[base + leaf].first_child = -2 - seq;
-            A.q_own[pos] = cur_own[g];
-            A.q_opp[pos] = cur_opp[g];
-            A.q_game[pos] = (int32_t)g;
-            A.q_seq[pos] = seq;
-        } else {
-            *A.error = 1;
-        }
-    }
+    for (int d = (int)r; d < len; d += 8)
+        visit(T, base + path[d], lv);
+    if (r == 0u && leaf_n + 1 == A.trigger && leaf_tag == -1)
+        queue_leaf(A, T, g, base + leaf, cur_own[g], cur_opp[g]);
 }
 
 // probs [>= *q_count][64]: the net's outputs for the queued positions, row i for queue entry i
@@ -550,47 +437,15 @@ __global__ __launch_bounds__(BLOCK) void expand_cached_kernel(Tree T, const uint
     const uint64_t lg = live ? legal[g] : 0ull;
     const int k = lg ? __popcll(lg) : 1;
     const int tag = live ? T.nodes[base + node].first_child : 0;
-    uint32_t fc1 = 0; // first child + 1, 0 = no room / already expanded
-    if (live && r == 0u && tag < 0) {
-        const int at = T.n_nodes[g];
-        if (at + k <= T.capacity) {
-            T.n_nodes[g] = at + k;
-            fc1 = (uint32_t)at + 1u;
-        } else {
-            T.overflow[g] = 1;
-        }
-    }
-    fc1 = group8_add(fc1);
+    // (0: no room, or already expanded)
+    const uint32_t fc1 = alloc_children(T, g, k, live && r == 0u && tag < 0);
     if (!live || fc1 == 0u)
         return;
     const int fc = (int)fc1 - 1;
-    if (lg == 0ull || k == 1) {
-        // pass child / single legal move: Node(node, 1), no net (MCTS.py:112-117)
-        if (r == 0u) {
-            const int a = lg ? (int)__builtin_ctzll(lg) : -1;
-            init_node(T, base + fc, node, a, 1.0f + 0.1f);
-        }
-    } else {
-        const int seq = -2 - tag;
-        const int slot = tag <= -2 ? seq % A.slots : 0;
-        const float *probs = A.cache + (g * A.slots + slot) * 64;
-        if (tag > -2 || A.cache_seq[g * A.slots + slot] != seq) {
-            if (r == 0u)
-                *A.error = 2; // no priors for this leaf (not queued, or its slot was recycled)
-        }
-        uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
-        int at = fc + __popcll(lg & ((1ull << (8u * r)) - 1ull));
-        while (row) {
-            const int a = (int)(8u * r) + __builtin_ctz(row);
-            row &= row - 1u;
-            init_node(T, base + at, node, a, probs[a] + 0.1f); // MCTS.py:19
-            at++;
-        }
-    }
-    if (r == 0u) {
-        T.nodes[base + node].first_child = fc;
-        T.nodes[base + node].n_children = (uint8_t)k;
-    }
+    const float *probs = k > 1 ? cached_priors(A, g, tag, r == 0u) : nullptr; // (one child: a node without a net)
+    make_children(T, base, fc, node, lg, r, [&](int a) { return probs[a]; });
+    if (r == 0u)
+        link_children(T, base + node, fc, k);
 }
 
 // ---- the whole descent of a playout in ONE launch (iago_mcts_descend): select from the root
@@ -637,7 +492,8 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
         node = T.root[g];
         own = root_own[g];
         opp = root_opp[g];
-        const uint4 s0 = ((const uint4 *)&T.nodes[base + node])[0], l0 = ((const uint4 *)&T.nodes[base + node])[1];
+        uint4 s0, l0;
+        node_record(T, base + node, s0, l0);
         fc = (int)l0.x;
         k = (int)((l0.z >> 8) & 0xFFu);
         nv = (int)s0.x;
@@ -663,41 +519,14 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
                 may_expand = false;
                 const int kn = lg ? __popcll(lg) : 1;
                 const int tag = fc;
-                uint32_t fc1 = 0; // first child + 1, 0 = no room
-                if (r == 0u) {
-                    const int at = T.n_nodes[g];
-                    if (at + kn <= T.capacity) {
-                        T.n_nodes[g] = at + kn;
-                        fc1 = (uint32_t)at + 1u;
-                    } else {
-                        T.overflow[g] = 1;
-                    }
-                }
-                fc1 = group8_add(fc1);
+                const uint32_t fc1 = alloc_children(T, g, kn, r == 0u);
                 if (fc1 != 0u) {
                     const int nf = (int)fc1 - 1;
-                    if (lg == 0ull || kn == 1) {
-                        // pass child / single legal move: Node(node, 1), no net (MCTS.py:112-117)
-                        if (r == 0u)
-                            init_node(T, base + nf, node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
-                    } else {
-                        const int seq = -2 - tag;
-                        const int slot = tag <= -2 ? seq % A.slots : 0;
-                        const float *probs = A.cache + (g * A.slots + slot) * 64;
-                        if ((tag > -2 || A.cache_seq[g * A.slots + slot] != seq) && r == 0u)
-                            *A.error = 2; // no priors for this leaf (not queued, or its slot was recycled)
-                        uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
-                        int at = nf + __popcll(lg & ((1ull << (8u * r)) - 1ull));
-                        while (row) {
-                            const int a = (int)(8u * r) + __builtin_ctz(row);
-                            row &= row - 1u;
-                            init_node(T, base + at, node, a, probs[a] + 0.1f); // MCTS.py:19
-                            at++;
-                        }
-                    }
+                    // (one child: a node without a net)
+                    const float *probs = kn > 1 ? cached_priors(A, g, tag, r == 0u) : nullptr;
+                    make_children(T, base, nf, node, lg, r, [&](int a) { return probs[a]; });
                     if (r == 0u) {
-                        T.nodes[base + node].first_child = nf;
-                        T.nodes[base + node].n_children = (uint8_t)kn;
+                        link_children(T, base + node, nf, kn);
                         if (A.va_x_count) {
                             // value look-ahead: the new children will be first-visited during this
                             // node's next visits (a full queue drops the hint)
@@ -722,7 +551,7 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
         const int kk = descending ? k : 0;
         st_levels += descending ? 1 : 0;
         st_children += kk;
-        const double sq = sqrt((double)nv); // np.sqrt(parent.n_visits), MCTS.py:49
+        const double sq = sqrt((double)nv);
         double best_v = -INFINITY;
         int best_i = 0x7fffffff;
         uint32_t pl[4] = {0u, 0u, 0u, 0u}; // of the best child: first_child, n_visits, action | n_children << 8, v
@@ -731,54 +560,23 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
             const int j1 = j0 + 8;
             const bool two = j1 < kk;
             const int64_t c0 = base + fc + j0, c1 = two ? base + fc + j1 : c0;
-            // a child's record as two 16-byte loads: (n_visits, Q, P, v) | (first_child, parent, action |
-            // n_children << 8, -) -- one 32-byte sector per child
-            const uint4 s0 = ((const uint4 *)&T.nodes[c0])[0], l0 = ((const uint4 *)&T.nodes[c0])[1];
-            const uint4 s1 = ((const uint4 *)&T.nodes[c1])[0], l1 = ((const uint4 *)&T.nodes[c1])[1];
-            const float p0 = __uint_as_float(s0.z), q0 = __uint_as_float(s0.y);
-            const float p1 = __uint_as_float(s1.z), q1 = __uint_as_float(s1.y);
-            const int n0 = (int)s0.x, n1 = (int)s1.x;
-            const int f0 = (int)l0.x, f1 = (int)l1.x;
-            const uint32_t a0 = l0.z & 0xFFFFu, a1 = l1.z & 0xFFFFu;
-            const uint32_t w0 = s0.w, w1 = s1.w;
-            {
-                const float cp = c_puct * p0;                          // float32, MCTS.py:49
-                const double u = (double)cp * sq / (0.01 + (double)n0);
-                const double v = (double)q0 + u;                       // get_value, MCTS.py:75-76
-                if (v > best_v) { // strict: the first maximum wins (python max, MCTS.py:46)
-                    best_v = v;
-                    best_i = j0;
-                    pl[0] = (uint32_t)f0, pl[1] = (uint32_t)n0, pl[2] = a0, pl[3] = w0;
-                }
-            }
-            if (two) {
-                const float cp = c_puct * p1;
-                const double u = (double)cp * sq / (0.01 + (double)n1);
-                const double v = (double)q1 + u;
-                if (v > best_v) {
-                    best_v = v;
-                    best_i = j1;
-                    pl[0] = (uint32_t)f1, pl[1] = (uint32_t)n1, pl[2] = a1, pl[3] = w1;
-                }
-            }
+            // (a child's record is one 32-byte sector, read as two 16-byte loads)
+            uint4 s0, l0, s1, l1;
+            node_record(T, c0, s0, l0);
+            node_record(T, c1, s1, l1);
+            score_child<false>(c_puct, 0.0, s0, l0, j0, sq, best_v, best_i, pl);
+            if (two)
+                score_child<false>(c_puct, 0.0, s1, l1, j1, sq, best_v, best_i, pl);
         }
         argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
         argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
         argmax_step_payload<DPP_HALF_MIRROR>(best_v, best_i, pl);
-        const int child = fc + best_i;
-        const int a = descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1;
-        // GameFunctions.place_stone(state, action, c); c = 3 - c  (MCTS.py:131-132)
-        const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
+        uint64_t c_own = own, c_opp = opp;
+        place_stone(c_own, c_opp, descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1, L);
         if (descending) {
-            uint64_t no = own, np_ = opp;
-            if (a >= 0) {
-                const uint64_t bit = 1ull << (a & 63);
-                no = own | f | bit;
-                np_ = opp & ~f & ~bit;
-            }
-            own = np_;
-            opp = no;
-            node = child;
+            own = c_own;
+            opp = c_opp;
+            node = fc + best_i;
             fc = (int)pl[0];
             nv = (int)pl[1];
             k = (int)(pl[2] >> 8);
@@ -935,21 +733,16 @@ __global__ __launch_bounds__(BLOCK) void value_ahead_rows_kernel(Tree T, ValueAh
         while (__builtin_amdgcn_ballot_w64(live && j < k) != 0ull) {
             const bool on = live && j < k;
             const int a = pass ? -1 : (lg ? (int)__builtin_ctzll(lg) : 0);
-            const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
+            uint64_t c_own = own, c_opp = opp;
+            place_stone(c_own, c_opp, a, L); // the child: the other side moves
             if (on && L.l8 == 0u) {
                 const int64_t c = base + fc + j;
                 const float cv = T.nodes[c].v;
                 if (cv != cv) {
-                    uint64_t no = own, np_ = opp;
-                    if (a >= 0) {
-                        const uint64_t bit = 1ull << (a & 63);
-                        no = own | f | bit;
-                        np_ = opp & ~f & ~bit;
-                    }
                     const int pos = atomicAdd(V.row_count, 1);
                     if (pos < V.row_capacity) {
-                        V.row_own[pos] = np_; // the child's mover is the other side (MCTS.py:131-132)
-                        V.row_opp[pos] = no;
+                        V.row_own[pos] = c_own;
+                        V.row_opp[pos] = c_opp;
                         V.row_node[pos] = c;
                     }
                 }
@@ -992,14 +785,11 @@ int check_tree(const Tree *t, const char *who)
     return IAGO_OK;
 }
 
-// The games whose cursor sits on a leaf due for expansion, in ascending order: one block
-// scans the flags in chunks of 1024 (ballot + prefix over the 16 waves).
-__global__ __launch_bounds__(1024) void pending_kernel(const uint8_t *__restrict__ needs_expand,
-                                                       const uint8_t *__restrict__ active, int n,
-                                                       uint8_t *__restrict__ pending,
-                                                       int64_t *__restrict__ index,
-                                                       int32_t *__restrict__ games, int32_t *__restrict__ count,
-                                                       int64_t *__restrict__ total)
+// Ordered compaction of a flag over n items by one block of 1024 threads, in chunks of 1024 (ballot + prefix over the
+// 16 waves): index[k] = g for the k-th g in ascending order with pred(g), *count = their number, added to *total
+template <class Pred>
+__device__ __forceinline__ void block_compact(int n, Pred pred, int64_t *__restrict__ index, int32_t *__restrict__ games,
+                                              int32_t *__restrict__ count, int64_t *__restrict__ total)
 {
     __shared__ int wave_sum[16];
     __shared__ int base;
@@ -1009,9 +799,7 @@ __global__ __launch_bounds__(1024) void pending_kernel(const uint8_t *__restrict
     __syncthreads();
     for (int g0 = 0; g0 < n; g0 += 1024) {
         const int g = g0 + tid;
-        const bool p = g < n && needs_expand[g] != 0 && active[g] != 0;
-        if (g < n)
-            pending[g] = p ? 1 : 0;
+        const bool p = g < n && pred(g);
         const unsigned long long m = __ballot(p);
         if (lane == 0)
             wave_sum[wave] = __popcll(m);
@@ -1022,7 +810,8 @@ __global__ __launch_bounds__(1024) void pending_kernel(const uint8_t *__restrict
         if (p) {
             const int k = off + __popcll(m & ((1ull << lane) - 1ull));
             index[k] = g;
-            games[k] = g;
+            if (games)
+                games[k] = g;
         }
         __syncthreads();
         if (tid == 0) {
@@ -1040,6 +829,25 @@ __global__ __launch_bounds__(1024) void pending_kernel(const uint8_t *__restrict
     }
 }
 
+// The games whose cursor sits on a leaf due for expansion, in ascending order (as int64 and as int32), and the flag
+// itself in `pending`.
+__global__ __launch_bounds__(1024) void pending_kernel(const uint8_t *__restrict__ needs_expand,
+                                                       const uint8_t *__restrict__ active, int n,
+                                                       uint8_t *__restrict__ pending,
+                                                       int64_t *__restrict__ index,
+                                                       int32_t *__restrict__ games, int32_t *__restrict__ count,
+                                                       int64_t *__restrict__ total)
+{
+    block_compact(
+        n,
+        [&](int g) {
+            const bool p = needs_expand[g] != 0 && active[g] != 0;
+            pending[g] = p ? 1 : 0;
+            return p;
+        },
+        index, games, count, total);
+}
+
 // The active games whose leaf has no cached value yet (T.v is NaN), in ascending order, and
 // their number: the rows of the value net's next launch.
 __global__ __launch_bounds__(1024) void fresh_leaves_kernel(Tree T, const uint8_t *__restrict__ active,
@@ -1047,43 +855,15 @@ __global__ __launch_bounds__(1024) void fresh_leaves_kernel(Tree T, const uint8_
                                                             int64_t *__restrict__ index, int32_t *__restrict__ count,
                                                             int64_t *__restrict__ total)
 {
-    __shared__ int wave_sum[16];
-    __shared__ int base;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int n = (int)T.n_games;
-    if (tid == 0)
-        base = 0;
-    __syncthreads();
-    for (int g0 = 0; g0 < n; g0 += 1024) {
-        const int g = g0 + tid;
-        bool p = false;
-        if (g < n && active[g] != 0) {
+    block_compact(
+        (int)T.n_games,
+        [&](int g) {
+            if (active[g] == 0)
+                return false;
             const float c = T.nodes[(int64_t)g * T.capacity + cur_node[g]].v;
-            p = c != c;
-        }
-        const unsigned long long m = __ballot(p);
-        if (lane == 0)
-            wave_sum[wave] = __popcll(m);
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < wave; w++)
-            off += wave_sum[w];
-        if (p)
-            index[off + __popcll(m & ((1ull << lane) - 1ull))] = g;
-        __syncthreads();
-        if (tid == 0) {
-            int t = base;
-            for (int w = 0; w < 16; w++)
-                t += wave_sum[w];
-            base = t;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        *count = base;
-        if (total)
-            *total += base;
-    }
+            return c != c;
+        },
+        index, nullptr, count, total);
 }
 
 } // namespace

@@ -266,8 +266,8 @@ __device__ __forceinline__ int path_entry(int path_at, const int32_t *gpath, int
     return path_at >= 0 ? ((const int32_t *)iago_trunk::trunk_lds)[path_at + d] : gpath[d];
 }
 
-// Node.update_recursive (MCTS.py:51-72) over the recorded path + the leaf mix (MCTS.py:123-125): the
-// arithmetic of mix_backup_path_kernel, 8 lanes per game.  g: the slot (its path, its leaf value), gt: its tree (the same
+// Node.update_recursive over the recorded path + the leaf mix, as mix_backup_path_kernel does them: 8 lanes per game.
+// g: the slot (its path, its leaf value), gt: its tree (the same
 // unless a wave search, which also takes the playout's in-flight visit off every node of the path)
 template <bool WAVE>
 __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, uint32_t r, int leaf, bool fresh, float vg,
@@ -278,44 +278,20 @@ __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, ui
     if (fresh && lmbda < 1.0f && r == 0u)
         S.T.nodes[base + leaf].v = vg; // value_func(leaf), now stored (the value cache)
     const int8_t zg = lmbda > 0.0f ? zl : (int8_t)0; // (the rollout's result, from the workgroup's LDS)
-    const float a = (lmbda < 1.0f) ? (float)(1.0 - (double)lmbda) * vg : 0.0f;
-    const float b = (lmbda > 0.0f) ? (float)((double)lmbda * (double)zg) : 0.0f;
-    const float lv = a + b;
+    const float lv = leaf_mix(lmbda, vg, zg);
     if (r == 0u) {
         S.leaf_value[g] = lv;
-        if (S.z_log && lmbda > 0.0f) {
-            const int k = S.z_log_n[gt];
-            S.z_log_n[gt] = k + 1;
-            if (k < S.z_log_rows)
-                S.z_log[(int64_t)k * S.T.n_games + gt] = zg;
-        }
+        if (S.z_log && lmbda > 0.0f)
+            log_z(S.z_log, S.z_log_n, S.z_log_rows, gt, S.T.n_games, zg);
     }
     const int len = path_n < S.path_stride ? path_n : S.path_stride;
     const int32_t *const gpath = S.path + g * (int64_t)S.path_stride;
     for (int d = (int)r; d < len; d += 8) {
         const int node = path_entry(path_at, gpath, d);
-        uint2 *nq = (uint2 *)&S.T.nodes[base + node];
-        const uint2 old = *nq;
-        const int n = (int)old.x + 1;                // MCTS.py:61
-        const float q = __uint_as_float(old.y);
-        *nq = make_uint2((uint32_t)n, __float_as_uint(q + (lv - q) / (float)n)); // MCTS.py:63
+        visit(S.T, base + node, lv);
         if constexpr (WAVE)
             S.T.nodes[base + node].reserved1 -= 1; // vv: this playout is no longer in flight
     }
-}
-
-// in-flight visits (vv) of a wave search: the score of a child (Node.select, MCTS.py:39-49) when a playout of the wave
-// is on its way through it -- n + vv visits, the in-flight ones counted as a loss of `vloss` each.  vv == 0: the
-// reference's score exactly (the same float32 c_puct * P, float64 sqrt, divide and add).  (No contraction: the
-// restatement in tests/wave_mcts.py rounds every product and difference on its own)
-__device__ __forceinline__ double wave_score(float c_puct, float p, float q, int n, int vv, double sq, double vloss)
-{
-#pragma clang fp contract(off)
-    const float cp = c_puct * p;
-    const int nc = n + vv;
-    const double u = (double)cp * sq / (0.01 + (double)nc);
-    const double qe = vv == 0 ? (double)q : ((double)q * (double)n - vloss * (double)vv) / (double)nc;
-    return qe + u;
 }
 
 // a barrier that also orders the workgroup's global stores before it against its loads after it (workgroup-scope
@@ -440,21 +416,6 @@ __device__ __forceinline__ void start_game(Game &G, uint64_t own, uint64_t opp)
     G.n_done = 0;
 }
 
-// reset_kernel's Node(None, 1.0) as the tree's only node, its root (one lane)
-__device__ __forceinline__ void fresh_root(const Tree &T, int64_t gt, int64_t base)
-{
-    init_node(T, base, -1, -2, 1.0f + 0.1f);
-    T.n_nodes[gt] = 1;
-    T.root[gt] = 0;
-}
-
-// the two halves of a node record: s = {n_visits, q, p, v}, l = {first_child, parent, action | n_children << 8, vv}
-__device__ __forceinline__ void node_record(const Tree &T, int64_t at, uint4 &s, uint4 &l)
-{
-    s = ((const uint4 *)&T.nodes[at])[0];
-    l = ((const uint4 *)&T.nodes[at])[1];
-}
-
 // the cursor at `node`: an = action | n_children << 8, vv its in-flight visits (a wave search)
 template <bool WAVE>
 __device__ __forceinline__ void cursor_to(Cursor &C, int node, uint32_t fc, uint32_t nv, uint32_t an, uint32_t vv, uint32_t vbits)
@@ -466,44 +427,6 @@ __device__ __forceinline__ void cursor_to(Cursor &C, int node, uint32_t fc, uint
     if (WAVE)
         C.nvv = (int)vv;
     C.vbits = vbits;
-}
-
-// GameFunctions.place_stone(state, a, c); c = 3 - c (MCTS.py:131-132): move a (< 0: a pass, nothing placed) and the swap
-// of sides.  Every lane of the group takes part (group8_flips)
-__device__ __forceinline__ void place_stone(uint64_t &own, uint64_t &opp, int a, const Lane8 &L)
-{
-    const uint64_t f = group8_flips(to_lane(own, L), to_lane(opp, L), (uint32_t)a & 63u, L);
-    uint64_t o = own, p = opp;
-    if (a >= 0) {
-        const uint64_t bit = 1ull << (a & 63);
-        o = own | f | bit;
-        p = opp & ~f & ~bit;
-    }
-    own = p;
-    opp = o;
-}
-
-// Node.select's score of a child (MCTS.py:39-49) against the best so far; strict `>`: the first maximum wins (python max,
-// MCTS.py:46).  pl: the best child's first_child, n_visits, action | n_children << 8 (| vv << 16), v
-template <bool WAVE>
-__device__ __forceinline__ void score_child(const SearchParams &S, uint4 s, uint4 l, int j, double sq, double &best_v,
-                                            int &best_i, uint32_t (&pl)[4])
-{
-    const float p = __uint_as_float(s.z), q = __uint_as_float(s.y);
-    const int n = (int)s.x;
-    double v;
-    if constexpr (WAVE) {
-        v = wave_score(S.c_puct, p, q, n, (int)l.w, sq, (double)S.vloss); // (vv < 2^16: at most 32 playouts in flight)
-    } else {
-        const float cp = S.c_puct * p;                          // float32, MCTS.py:49
-        const double u = (double)cp * sq / (0.01 + (double)n);
-        v = (double)q + u;                                      // get_value, MCTS.py:75-76
-    }
-    if (v > best_v) {
-        best_v = v;
-        best_i = j;
-        pl[0] = l.x, pl[1] = (uint32_t)n, pl[2] = WAVE ? (l.z & 0xFFFFu) | (l.w << 16) : l.z & 0xFFFFu, pl[3] = s.w;
-    }
 }
 
 // the end of a playout of the plain search: the backup, the count, the rollouts' Philox stream of the next one
@@ -807,8 +730,8 @@ __device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I,
     }
 }
 
-// Node.expand (MCTS.py:109-120) of the cursor node once it has n_thr visits: a pass child or a single legal move without
-// a net (MCTS.py:112-117), else with the priors -- which, when they have not arrived, the descent stops to ask for
+// Node.expand of the cursor node once it has n_thr visits (MCTS.py:109): a pass child or a single legal move without
+// a net, else with the priors -- which, when they have not arrived, the descent stops to ask for
 __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cursor &C, bool &descending, bool have_priors,
                                        bool &need_prior)
 {
@@ -824,37 +747,13 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
             descending = false;
         } else {
             C.may_expand = false;
-            uint32_t fc1 = 0; // first child + 1, 0 = no room
-            if (I.r == 0u) {
-                const int at = T.n_nodes[I.gt];
-                if (at + kn <= T.capacity) {
-                    T.n_nodes[I.gt] = at + kn;
-                    fc1 = (uint32_t)at + 1u;
-                } else {
-                    T.overflow[I.gt] = 1;
-                }
-            }
-            fc1 = group8_add(fc1);
+            const uint32_t fc1 = alloc_children(T, I.gt, kn, I.r == 0u);
             if (fc1 != 0u) {
                 const int nf = (int)fc1 - 1;
-                if (lg == 0ull || kn == 1) {
-                    if (I.r == 0u) // pass child / single legal move: Node(node, 1)
-                        init_node(T, I.base + nf, C.node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
-                } else {
-                    uint32_t row = (uint32_t)(lg >> (8u * I.r)) & 0xFFu;
-                    int at = nf + __popcll(lg & ((1ull << (8u * I.r)) - 1ull));
-                    while (row) {
-                        const int a = (int)(8u * I.r) + __builtin_ctz(row);
-                        row &= row - 1u;
-                        const float p = __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a]));
-                        init_node(T, I.base + at, C.node, a, p + 0.1f); // MCTS.py:19
-                        at++;
-                    }
-                }
-                if (I.r == 0u) {
-                    T.nodes[I.base + C.node].first_child = nf;
-                    T.nodes[I.base + C.node].n_children = (uint8_t)kn;
-                }
+                make_children(T, I.base, nf, C.node, lg, I.r,
+                              [&](int a) { return __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a])); });
+                if (I.r == 0u)
+                    link_children(T, I.base + C.node, nf, kn);
                 C.fc = nf;
                 C.k = kn;
             }
@@ -863,12 +762,12 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
     __threadfence_block(); // the new children are read by the other lanes of the group below
 }
 
-// Node.select (MCTS.py:39-49): two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
+// Node.select: two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
 template <bool WAVE>
 __device__ __forceinline__ void select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
 {
     const int kk = descending ? C.k : 0;
-    const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv)); // np.sqrt(parent.n_visits), MCTS.py:49
+    const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv));
     double best_v = -INFINITY;
     int best_i = 0x7fffffff;
     uint32_t pl[4] = {0u, 0u, 0u, 0u};
@@ -879,9 +778,9 @@ __device__ __forceinline__ void select_child(const SearchParams &S, const Slot &
         uint4 s0, l0, s1, l1;
         node_record(S.T, c0, s0, l0);
         node_record(S.T, c1, s1, l1);
-        score_child<WAVE>(S, s0, l0, j0, sq, best_v, best_i, pl);
+        score_child<WAVE>(S.c_puct, (double)S.vloss, s0, l0, j0, sq, best_v, best_i, pl);
         if (two)
-            score_child<WAVE>(S, s1, l1, j1, sq, best_v, best_i, pl);
+            score_child<WAVE>(S.c_puct, (double)S.vloss, s1, l1, j1, sq, best_v, best_i, pl);
     }
     argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
     argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);

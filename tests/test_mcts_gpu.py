@@ -581,6 +581,57 @@ def test_graph_mode_equals_eager(eng):
     assert np.array_equal(a[5], b[5])
 
 
+def test_per_phase_descent_and_climbing_backup_build_the_same_trees(eng, monkeypatch):
+    """The two forms of a look-ahead playout that only an environment knob selects -- the per-phase descent
+    (IAGO_FUSED_DESCENT=0: select / expand_cached / select / fresh_leaves) and the backup that climbs through
+    `parent` (IAGO_BACKUP_PATH=0) -- against the default (one-launch descent, backup over the recorded path),
+    which the oracle pins: bit-identical pools, roots and leaf values over two searches with subtree reuse."""
+    engine, ops = eng
+    from iago_amd import network
+    g = __import__("tests.conftest", fromlist=["load_json"]).load_json("simulate.json")
+    torch.manual_seed(4)
+    policy, value = network.SLPolicy().cuda().eval(), network.Value().cuda().eval()
+    w = ops.RolloutWeights(g["shipped_w"], g["shipped_b"])
+    G, cap = 16, 512
+    own, opp = random_positions(G, seed=8)
+    own[:4], opp[:4] = 0x0000000810000000, 0x0000001008000000
+
+    def make(knob):
+        if knob:
+            monkeypatch.setenv(knob, "0")
+        m = engine.BatchedMCTS(G, policy, value, w, n_thr=15, capacity=cap, seed=13, lookahead=4)
+        if knob:
+            monkeypatch.delenv(knob)
+        return m
+
+    ms = [make(None), make("IAGO_FUSED_DESCENT"), make("IAGO_BACKUP_PATH")]
+    assert ms[0].fused_descent is True and ms[0]._la_path is not None
+    assert ms[1].fused_descent is False
+    assert ms[2].fused_descent is True and ms[2]._la_path is None
+    assert all(m.lookahead == 4 for m in ms)
+    boards = [(ops.bits_to_tensor(own), ops.bits_to_tensor(opp)) for _ in ms]
+    used = torch.arange(cap, device="cuda").reshape(1, cap)
+    for t in range(2):
+        active = (ops.legal_moves(*boards[0]) != 0).to(torch.uint8)
+        for m, (o, p) in zip(ms, boards):
+            m.search(o, p, active, 45)
+            assert m.error_flags().tolist() == [0, 0, 0, 0, 0], t
+        ref = ms[0]
+        live = (used < ref.tree.n_nodes.reshape(G, 1)).reshape(-1)
+        assert int((ref.tree.n_nodes > 1).sum().item()) >= G // 2   # (the expansions did run)
+        for m in ms[1:]:
+            assert torch.equal(m.tree.n_nodes, ref.tree.n_nodes), t
+            assert torch.equal(m.tree.root, ref.tree.root), t
+            assert torch.equal(m.tree.nodes[live], ref.tree.nodes[live]), t
+            assert torch.equal(m.leaf_value.view(torch.int32), ref.leaf_value.view(torch.int32)), t
+        mv = ref.best_move(active)[0]
+        mv = torch.where(active.bool(), mv, torch.full_like(mv, -1))
+        for i, (m, (o, p)) in enumerate(zip(ms, boards)):
+            ops.apply_moves(o, p, mv)
+            m.update_with_move(mv)
+            boards[i] = (p, o)
+
+
 def test_pending_compaction():
     """iago_mcts_pending: mask, ascending ids (int64 and int32) and count in one launch."""
     import ctypes as C
