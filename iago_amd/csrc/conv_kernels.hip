@@ -1069,7 +1069,9 @@ int iago_conv3x3_split_trunk(const iago_conv_split_layer *layers, int32_t n_laye
         P.n_chunks = a.cin / 16;
         P.overflow = overflow;
     }
-    if (!getenv("IAGO_TRUNK_STAGED"))
+    // tuning knob IAGO_TRUNK_STAGED=1 (read per call): the round-1 LDS-staged trunk below; unset or 0: the resident one
+    const char *staged = getenv("IAGO_TRUNK_STAGED");
+    if (!staged || staged[0] == '0' || staged[0] == '\0')
         return iago_launch_trunk_resident(layers, n_layers, n, overflow, stream);
     static std::atomic<uint64_t> configured{0};
     if (iago_reserve_lds((const void *)conv3x3_split_trunk_kernel, LDS_BYTES, configured,

@@ -159,12 +159,16 @@ int iago_launch_trunk_resident(const iago_conv_split_layer *layers, int32_t n_la
 }
 
 namespace {
-// rows up to which a workgroup takes ONE board (tuning knob: IAGO_VALUE_TINY, default 256)
+// rows up to which a workgroup takes ONE board (tuning knob: IAGO_VALUE_TINY, default 256), clamped to [0, SMALL]:
+// above SMALL = 512 the one-board window (0, TINY] would overlap the four-board window (SMALL, ...) and both launches
+// would compute and write the same rows (the same values, twice the work)
+constexpr int64_t VALUE_SMALL_ROWS = 512;
 int64_t iago_value_tiny_rows()
 {
     static const int64_t v = [] {
         const char *e = getenv("IAGO_VALUE_TINY");
-        return e ? (int64_t)atoll(e) : (int64_t)256;
+        const int64_t t = e ? (int64_t)atoll(e) : (int64_t)256;
+        return t < 0 ? (int64_t)0 : (t > VALUE_SMALL_ROWS ? VALUE_SMALL_ROWS : t);
     }();
     return v;
 }
@@ -201,7 +205,7 @@ int iago_value_forward_split(const iago_value_split_args *a, void *stream)
     // small batches: one up to TINY rows, two up to SMALL, four above.  Same products in the same
     // order per board: bit-identical values.  With a device-side count every variant whose
     // window the bound n reaches is enqueued and the one that holds the count runs.
-    const int64_t TINY = iago_value_tiny_rows(), SMALL = 512;
+    const int64_t TINY = iago_value_tiny_rows(), SMALL = VALUE_SMALL_ROWS;
     const bool host_known = a->n_dev == nullptr;
     const int64_t rows = a->n;
     if (!host_known && iago_value_persistent()) {
