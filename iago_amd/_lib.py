@@ -47,9 +47,10 @@ EXPERIMENTAL_SYMBOLS = [
     "iago_mcts_expand_cached", "iago_mcts_fresh_leaves",
 ]
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
-# the exact endgame solver (ops.solve_endgame, engine.solve_endgame)
+# the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
+    "iago_mcts_search_explore", "iago_mcts_draw_move",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True))
@@ -195,6 +196,8 @@ MATCH_MCTS_COLOUR_1 = 2   # a match: PV-MCTS plays colour 1 (moves first), the S
 MATCH_MCTS_COLOUR_2 = 3   # a match: PV-MCTS plays colour 2, the SL policy colour 1 (the reference's game.py --auto)
 MATCH_KEY = 0x4D415443    # a match's policy draws: Philox key = the rollout seed with its high word XOR this
 MATCH_SEED_XOR = MATCH_KEY << 32
+EXPLORE_KEY = 0x4558504C  # exploring self-play's draws from the visit counts: the same, with this word (IAGO_EXPLORE_KEY)
+EXPLORE_SEED_XOR = EXPLORE_KEY << 32
 CTL_BAD_DRAW = 13         # ctl word a match raises when a policy draw found no mass on the legal moves
 REC_DRAWN = 2             # rec_valid of a move played without a search (a policy draw or a forced final move)
 
@@ -260,6 +263,14 @@ class SearchParkArgs(C.Structure):
     _fields_ = [
         ("park_empties", C.c_int32), ("reserved0", C.c_int32), ("parked", C.c_void_p), ("stones", C.c_void_p),
         ("pass_flg", C.c_void_p), ("streams", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
+class SearchExploreArgs(C.Structure):
+    """Mirror of iago_search_explore_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("explore_turns", C.c_int32), ("reserved0", C.c_int32), ("streams", C.c_void_p), ("park", C.c_void_p),
+        ("reserved", C.c_int64 * 4),
     ]
 
 
@@ -387,6 +398,8 @@ def lib():
     L.iago_solve_endgame.argtypes = [C.POINTER(EndgameArgs), vp]
     L.iago_play_endgame.argtypes = [C.POINTER(PlayEndgameArgs), vp]
     L.iago_mcts_search_park.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchParkArgs), vp]
+    L.iago_mcts_search_explore.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchExploreArgs), vp]
+    L.iago_mcts_draw_move.argtypes = [tp, vp, C.c_uint64, vp, vp, vp, vp, vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)

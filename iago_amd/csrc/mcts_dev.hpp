@@ -229,6 +229,60 @@ __device__ __forceinline__ void backup_climb(const Tree &T, int64_t base, int no
     }
 }
 
+// ---- exploring self-play ("Exploring self-play"): in the first explore_turns turns of a game the
+// move is drawn in proportion to the root's visit counts n[a] (the children in ascending cell order), in integers:
+// N = sum n, w = word turn & 3 of Philox4x32-10 on counter (game id, turn >> 2, 0, 0) under the rollouts' key with its
+// high word XOR EXPLORE_KEY, r = (uint64(w) * N) >> 32, the move is the lowest cell a with sum_{b <= a} n[b] > r
+// (N == 0: the most visited child's first-maximum rule stays)
+constexpr uint32_t EXPLORE_KEY = 0x4558504Cu; // ("EXPL")
+
+__device__ __forceinline__ uint32_t explore_word(uint32_t key0, uint32_t key1, uint32_t id, uint32_t turn)
+{
+    uint32_t c[4] = {id, turn >> 2, 0u, 0u};
+    philox4x32_10(c, key0, key1 ^ EXPLORE_KEY);
+    const uint32_t lo = (turn & 1u) ? c[1] : c[0], hi = (turn & 1u) ? c[3] : c[2]; // (selects: no indexed array)
+    return (turn & 2u) ? hi : lo;
+}
+
+// the draw's threshold r in [0, total)
+__device__ __forceinline__ uint32_t explore_threshold(uint32_t w, uint32_t total)
+{
+    return __umulhi(w, total);
+}
+
+// the draw across the 8 lanes of a game: row_n = the visit counts of this lane's 8 cells (8 l8 ..), 0 where no child.
+// Every lane of the group takes part and receives the move; 64 when no child was visited
+__device__ __forceinline__ int explore_draw8(const int (&row_n)[8], uint32_t l8, uint32_t w)
+{
+    uint32_t blk = 0u;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        blk += (uint32_t)row_n[i];
+    // the sum over the group and the sum of the lower lanes (group8_scan's butterfly, in integers)
+    uint32_t pre = 0u;
+    uint32_t o = dpp_u32<DPP_XOR1>(blk);
+    pre = (l8 & 1u) ? pre + o : pre;
+    blk += o;
+    o = dpp_u32<DPP_XOR2>(blk);
+    pre = (l8 & 2u) ? pre + o : pre;
+    blk += o;
+    o = dpp_u32<DPP_HALF_MIRROR>(blk);
+    pre = (l8 & 4u) ? pre + o : pre;
+    blk += o;
+    const uint32_t r = explore_threshold(w, blk);
+    uint32_t a = 64u;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        pre += (uint32_t)row_n[i];
+        a = (a == 64u && pre > r) ? 8u * l8 + (uint32_t)i : a;
+    }
+    // the lowest cell of the group (a lane whose lower lanes crossed r offers its first cell: a lower lane offers less)
+    a = min(a, dpp_u32<DPP_XOR1>(a));
+    a = min(a, dpp_u32<DPP_XOR2>(a));
+    a = min(a, dpp_u32<DPP_HALF_MIRROR>(a));
+    return blk == 0u ? 64 : (int)a;
+}
+
 // Diagnostic record of the parity tests (tests/test_mcts_production_gpu.py): the z every playout of game g backed up, in
 // playout order -- what the oracle's rollout_fn replays (z_log [rows][n_games], z_log_n [n_games] rows written so far)
 __device__ __forceinline__ void log_z(int8_t *z_log, int32_t *z_log_n, int rows, int64_t g, int64_t n_games, int8_t zg)

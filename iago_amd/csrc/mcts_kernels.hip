@@ -16,6 +16,7 @@
 // shared with search_kernel.hip: the kernels here are schedules of it (which
 // thread does what, where a prior or a value is read, what is queued).
 #include "mcts_dev.hpp"
+#include "../../include/iago_hip_serving.h" // (iago_mcts_draw_move)
 
 using namespace iago;
 using namespace iago_mcts;
@@ -210,6 +211,51 @@ __global__ __launch_bounds__(BLOCK) void best_move_kernel(Tree T, const uint8_t 
         }
         if (visits && a >= 0)
             visits[g * 64 + a] = n;
+    }
+    move[g] = (int8_t)best;
+}
+
+// best_move_kernel's sibling for exploring self-play (iago_mcts_draw_move): the move of game g is drawn in proportion
+// to the visit counts of its root's children -- mcts_dev.hpp's rule, the children in ascending cell order -- with the
+// Philox word of (game_id[g], turn[g]); no child visited: the first maximum, as above; no children: -2
+__global__ __launch_bounds__(BLOCK) void draw_move_kernel(Tree T, const uint8_t *__restrict__ active, uint32_t key0,
+                                                          uint32_t key1, const int32_t *__restrict__ game_id,
+                                                          const int32_t *__restrict__ turn, int8_t *__restrict__ move,
+                                                          int32_t *__restrict__ visits)
+{
+    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= T.n_games || (active && !active[g]))
+        return;
+    const int64_t base = g * (int64_t)T.capacity;
+    const int root = T.root[g];
+    const int fc = T.nodes[base + root].first_child;
+    const int k = fc >= 0 ? (int)T.nodes[base + root].n_children : 0;
+    int best = -2, best_n = -1;
+    uint32_t total = 0u;
+    if (visits)
+        for (int a = 0; a < 64; a++)
+            visits[g * 64 + a] = 0;
+    for (int j = 0; j < k; j++) {
+        const int n = T.nodes[base + fc + j].n_visits;
+        const int a = (int)T.nodes[base + fc + j].action;
+        if (n > best_n) {
+            best_n = n;
+            best = a;
+        }
+        total += (uint32_t)n;
+        if (visits && a >= 0)
+            visits[g * 64 + a] = n;
+    }
+    if (total != 0u) {
+        const uint32_t r = explore_threshold(explore_word(key0, key1, (uint32_t)game_id[g], (uint32_t)turn[g]), total);
+        uint32_t run = 0u;
+        for (int j = 0; j < k; j++) {
+            run += (uint32_t)T.nodes[base + fc + j].n_visits;
+            if (run > r) {
+                best = (int)T.nodes[base + fc + j].action;
+                break;
+            }
+        }
     }
     move[g] = (int8_t)best;
 }
@@ -982,6 +1028,20 @@ int iago_mcts_best_move(const iago_mcts_tree *tree, const uint8_t *active, int8_
     hipLaunchKernelGGL(best_move_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0,
                        (hipStream_t)stream, *tree, active, move, visits);
     return iago_check_launch("iago_mcts_best_move");
+}
+
+int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
+                        const int32_t *turn, int8_t *move, int32_t *visits, void *stream)
+{
+    if (check_tree(tree, "iago_mcts_draw_move: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (!game_id || !turn || !move)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_draw_move: null pointer (game_id, turn and move expected)");
+    if (tree->n_games == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(draw_move_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0, (hipStream_t)stream, *tree,
+                       active, (uint32_t)seed, (uint32_t)(seed >> 32), game_id, turn, move, visits);
+    return iago_check_launch("iago_mcts_draw_move");
 }
 
 int iago_mcts_advance_root(const iago_mcts_tree *tree, const uint8_t *mask, const int8_t *move,

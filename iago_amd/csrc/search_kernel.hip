@@ -35,6 +35,7 @@
 #include "../../include/iago_hip_serving.h"
 
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace {
@@ -149,6 +150,9 @@ struct SearchParams {
     uint8_t *parked;
     int32_t *park_stones;
     uint8_t *park_pass;
+    // exploring self-play (iago_mcts_search_explore; 0: off): the move of a searched turn below explore_turns is drawn in
+    // proportion to the root's visit counts (mcts_dev.hpp, explore_draw8) instead of taken as the most visited one
+    int32_t explore_turns;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -577,9 +581,11 @@ __device__ __forceinline__ void play_move(const SearchParams &S, const Slot &I, 
 // again or is over (a pass leads straight on to the next turn: at most a few rounds)
 // PARK (iago_mcts_search_park): a turn that would be searched at a position of at most S.park_empties empties hands the game
 // over instead -- the turn it stands at, its position (own = the mover) and its books, by game id -- and the game is done
+// S.explore_turns > 0 (iago_mcts_search_explore): the move of a searched turn below it is the draw from the visit counts
+// -- the row the turn records -- keyed by the game's id and its turn
 template <bool PARK>
-__device__ __forceinline__ void turn_boundary(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G, const Cursor &C,
-                                              bool &busy, const long long t0)
+__device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_row::HwParams &R, const Slot &I, const GameLds &sh,
+                                              Game &G, const Cursor &C, bool &busy, const long long t0)
 {
     const Tree &T = S.T;
     for (int rep = 0; rep < 6; rep++) {
@@ -629,7 +635,16 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const Slot 
         const int root = moving ? T.root[I.g] : 0;
         const int rfc = moving ? T.nodes[I.base + root].first_child : -1;
         int row_n[8];
-        const int best = most_visited(T, I, lg, rfc, at_move, row_n);
+        int best = most_visited(T, I, lg, rfc, at_move, row_n);
+        if (S.explore_turns > 0) {
+            // (once per turn; every lane takes part in the group's sums.  No child visited, or none at all: `best` stays)
+            const bool explores = at_move && G.turn < S.explore_turns;
+            if (__builtin_amdgcn_ballot_w64(explores) != 0ull) {
+                const uint32_t w = explore_word(R.key0, R.key1, R.id_base + (uint32_t)sh.h_game[I.gl], (uint32_t)G.turn);
+                const int drawn_a = explore_draw8(row_n, I.r, w);
+                best = (explores && drawn_a < 64) ? drawn_a : best;
+            }
+        }
         if (moving) {
             int mv = -1;
             if (at_move) {
@@ -1176,7 +1191,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
                 busy = true;
             }
             if (!WAVE && I.whole)
-                turn_boundary<PARK>(S, I, sh, G, C, busy, t0);
+                turn_boundary<PARK>(S, R, I, sh, G, C, busy, t0);
         }
         const long long c_desc = WAVE ? wall_clock64() : 0;
         for (int sub = 0; sub < (WAVE ? I.W : 1); sub++) {
@@ -1799,6 +1814,7 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.parked = nullptr;
     S.park_stones = nullptr;
     S.park_pass = nullptr;
+    S.explore_turns = 0;
     return S;
 }
 
@@ -1873,7 +1889,7 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
 }
 
 int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
-                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr)
+                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr, int explore_turns = 0)
 {
     SearchGrid G;
     if (const int rc = check_args(a, wv))
@@ -1881,6 +1897,7 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
     if (const int rc = size_grid(a, sp, wv, pk != nullptr, G))
         return rc;
     SearchParams S = search_params(a, G, wv);
+    S.explore_turns = explore_turns;
     if (pk) {
         S.park_empties = pk->park_empties;
         S.parked = pk->parked;
@@ -1917,31 +1934,71 @@ int has_match_codes(const uint8_t *active, int64_t n, hipStream_t stream)
             return 1;
     return 0;
 }
+
+// what iago_mcts_search_park and iago_mcts_search_explore ask of a launch that only self-play games may take: whole
+// games, and no match codes in `active` (a stream does not read it: every game of it is self-play)
+int self_play_only(const iago_mcts_search_args *a, void *stream, const char *who, const char *why)
+{
+    if (a->max_turns == 0)
+        return iago_fail(IAGO_ERR_INVALID, (std::string(who) + ": whole games only (max_turns > 0)").c_str());
+    // (before the other arguments are looked at)
+    if (a->games_total == 0 && a->active && a->tree && a->tree->n_games >= 1) {
+        const int m = has_match_codes(a->active, a->tree->n_games, (hipStream_t)stream);
+        if (m < 0)
+            return iago_fail(IAGO_ERR_HIP, (std::string(who) + ": cannot read `active`").c_str());
+        if (m)
+            return iago_fail(IAGO_ERR_INVALID,
+                             (std::string(who) + ": match codes in `active` (self-play games only: " + why + ")").c_str());
+    }
+    return IAGO_OK;
+}
+
+// the hand-over's own arguments
+int check_park(const iago_search_park_args *pk, const char *who)
+{
+    const std::string w(who);
+    if (!pk->parked || !pk->stones || !pk->pass_flg)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": parked, stones and pass_flg expected").c_str());
+    for (int i = 0; i < 4; i++)
+        if (pk->reserved[i] != 0 || pk->reserved0 != 0)
+            return iago_fail(IAGO_ERR_INVALID, (w + ": reserved fields must be 0").c_str());
+    if (pk->park_empties < 0 || pk->park_empties > IAGO_ENDGAME_MAX_EMPTIES)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": park_empties must be in [0, 20]").c_str());
+    return IAGO_OK;
+}
 } // namespace
 
 extern "C" int iago_mcts_search_park(const iago_mcts_search_args *a, const iago_search_park_args *pk, void *stream)
 {
     if (!a || !pk)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: null args");
-    if (!pk->parked || !pk->stones || !pk->pass_flg)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: parked, stones and pass_flg expected");
-    for (int i = 0; i < 4; i++)
-        if (pk->reserved[i] != 0 || pk->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: reserved fields must be 0");
-    if (pk->park_empties < 0 || pk->park_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: park_empties must be in [0, 20]");
-    if (a->max_turns == 0)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: whole games only (max_turns > 0)");
-    // (before the other arguments are looked at: a stream does not read `active`, every game of it is self-play)
-    if (a->games_total == 0 && a->active && a->tree && a->tree->n_games >= 1) {
-        const int m = has_match_codes(a->active, a->tree->n_games, (hipStream_t)stream);
-        if (m < 0)
-            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_park: cannot read `active`");
-        if (m)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: match codes in `active` (self-play games only: a "
-                                               "match's policy side needs the net workgroups to its last move)");
-    }
+    if (const int rc = check_park(pk, "iago_mcts_search_park"))
+        return rc;
+    if (const int rc = self_play_only(a, stream, "iago_mcts_search_park",
+                                      "a match's policy side needs the net workgroups to its last move"))
+        return rc;
     return search_launch(a, stream, pk->streams, nullptr, pk);
+}
+
+extern "C" int iago_mcts_search_explore(const iago_mcts_search_args *a, const iago_search_explore_args *ex, void *stream)
+{
+    if (!a || !ex)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: null args");
+    for (int i = 0; i < 4; i++)
+        if (ex->reserved[i] != 0 || ex->reserved0 != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: reserved fields must be 0");
+    if (ex->explore_turns < 0 || ex->explore_turns > IAGO_MAX_TURNS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: explore_turns must be in [0, 128]");
+    if (ex->park) {
+        if (const int rc = check_park(ex->park, "iago_mcts_search_explore (park)"))
+            return rc;
+        if (ex->park->streams && ex->park->streams != ex->streams)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore (park): park->streams must be NULL or `streams`");
+    }
+    if (const int rc = self_play_only(a, stream, "iago_mcts_search_explore",
+                                      "a match's moves are not drawn from the visit counts"))
+        return rc;
+    return search_launch(a, stream, ex->streams, nullptr, ex->park, ex->explore_turns);
 }
 
 extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)

@@ -1177,10 +1177,11 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None):
+    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None, explore_turns=None):
         """iago_mcts_search_persistent: one search from the roots (own, opp), or -- game = dict(max_turns, own,
         opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games; park = dict(empties,
-        parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park)."""
+        parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park); explore_turns
+        (an int > 0): those games' moves of the turns below it drawn from the visit counts (iago_mcts_search_explore)."""
         if self.rollout_hook is not None:
             raise ValueError("rollout_hook is not available in the persistent search (z_log_rows records the z)")
         ps = self._ps
@@ -1236,12 +1237,19 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
-        elif park is not None:
-            k = _lib.SearchParkArgs()
-            k.park_empties = int(park["empties"])
-            k.parked, k.stones, k.pass_flg = park["parked"].data_ptr(), park["stones"].data_ptr(), park["pass_flg"].data_ptr()
-            k.streams = self._split   # (the role split where today's launch takes it, else the single launch)
-            check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
+        elif park is not None or explore_turns:
+            k = None
+            if park is not None:
+                k = _lib.SearchParkArgs()
+                k.park_empties = int(park["empties"])
+                k.parked, k.stones, k.pass_flg = (park["parked"].data_ptr(), park["stones"].data_ptr(),
+                                                  park["pass_flg"].data_ptr())
+            # (the role split where today's launch takes it, else the single launch)
+            if explore_turns:
+                ops.search_explore(a, explore_turns, streams=self._split, park=k)
+            else:
+                k.streams = self._split
+                check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
         elif self._split is not None:
             check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
         else:
@@ -1413,6 +1421,18 @@ class BatchedMCTS(object):
                                              _stream()), "iago_mcts_best_move")
         return self.move, self.visits
 
+    def draw_move(self, turn, active=None, want_visits=True):
+        """best_move for exploring self-play: the move drawn in proportion to the visit counts of the root's children
+        (ops.draw_move), game g under the id game_id_base + g at turn `turn` (an int: every game's)."""
+        ids = getattr(self, "_draw_ids", None)
+        if ids is None or ids[0] != self.game_id_base:
+            g = (torch.arange(self.n_games, dtype=torch.int64, device=self.move.device) + self.game_id_base) & 0xFFFFFFFF
+            ids = self._draw_ids = (self.game_id_base, torch.where(g >= (1 << 31), g - (1 << 32), g).to(torch.int32),
+                                    torch.zeros(self.n_games, dtype=torch.int32, device=self.move.device))
+        ids[2].fill_(int(turn))
+        ops.draw_move(self.tree.ref(), active, self.seed, ids[1], ids[2], self.move, self.visits if want_visits else None)
+        return self.move, self.visits
+
     def update_with_move(self, move, mask=None):
         """MCTS.update_with_move (MCTS.py:149-154); move int8 tensor, -1 = pass."""
         check(_lib.lib().iago_mcts_advance_root(self.tree.ref(),
@@ -1573,7 +1593,8 @@ class SelfPlayEngine(object):
         res.final_p1, res.final_p2 = p1, p2
         return res
 
-    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None, solve_empties=None):
+    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None, solve_empties=None,
+                         explore_turns=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
@@ -1582,7 +1603,8 @@ class SelfPlayEngine(object):
         all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up.
         solve_empties = k: TWO launches -- the games hand over at their first turn of at most k empties
         (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the same
-        records (valid 3, score), and the one readback follows both."""
+        records (valid 3, score), and the one readback follows both.  explore_turns (an int > 0): the searched moves of
+        the turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore)."""
         m, T = self.mcts, self.max_turns
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
@@ -1599,7 +1621,7 @@ class SelfPlayEngine(object):
             park = dict(empties=solve_empties, parked=torch.zeros(B, dtype=torch.uint8, device=dev),
                         stones=torch.zeros(B, dtype=torch.int32, device=dev),
                         pass_flg=torch.zeros(B, dtype=torch.uint8, device=dev))
-        m._launch_persistent(None, None, active, n_sims, game=g, park=park)
+        m._launch_persistent(None, None, active, n_sims, game=g, park=park, explore_turns=explore_turns)
         if park is not None:
             # (own / opp / n_turns: a parked game's position and turn in, its final position and turn count out)
             out = ops.play_endgame(own, opp, g["n_turns"], park["stones"], park["pass_flg"], park["parked"], max_turns=T,
@@ -1686,15 +1708,17 @@ class SelfPlayEngine(object):
         sol = searched & (_empties(own, opp) <= k)
         return searched & ~sol, sol
 
-    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None):
+    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None, explore_turns=None):
         """The games from (own, opp) turn by turn into res: a search from every root that is searched, the move, the
         books, in lockstep.  colours None: self-play, every active game searched; else play_match's (B,) int8 colours
         of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced.  solve_empties = k:
         a game that would search at a position of at most k empties leaves the search mask; the solver (ops.solve_endgame,
         EXACT: one launch per turn for all such games) gives its move, recorded with valid 3 and the exact score, and
-        its flags join the turn's readback."""
+        its flags join the turn's readback.  explore_turns (self-play): the searched moves of the turns below it are
+        drawn from the visit counts (BatchedMCTS.draw_move) instead of best_move's."""
         m, B, T = self.mcts, self.B, self.max_turns
         k = solve_empties
+        explore_turns = explore_turns or 0
         dev = own.device
         stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -1722,7 +1746,7 @@ class SelfPlayEngine(object):
             # ONE readback per turn (below): the flags of this turn's search, the check of its
             # moves, the end-of-game test and the counts the next search starts from
             m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
-            move, visits = m.best_move(s_act)
+            move, visits = m.draw_move(t, s_act) if t < explore_turns else m.best_move(s_act)
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
                 ex = ops.solve_endgame(torch.where(sol, own, full), torch.where(sol, opp, none), mode="exact",
@@ -1789,7 +1813,7 @@ class SelfPlayEngine(object):
                 setattr(res, res.SCORE_RECORD if name == "score" else name, v[:t])
         return res
 
-    def play(self, n_sims, handicap=None, record=True, solve_empties=None):
+    def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -1798,14 +1822,24 @@ class SelfPlayEngine(object):
         books like a searched move.  The games then end under perfect play: z is the game-theoretic value of every
         position from the first solved turn on.  sim_counter advances by n_sims per turn all the same; n_leaf_evals
         counts the valid == 1 rows.  Where whole games run in one launch they hand over at k empties and ONE more launch
-        (iago_play_endgame) plays them all out (launches = 2); the turn loop solves per turn: the same records."""
+        (iago_play_endgame) plays them all out (launches = 2); the turn loop solves per turn: the same records.
+        explore_turns = e (an int >= 0; None or 0, the default: off): at a searched turn t < e (the game's turn counter,
+        passes included) the move is not the most visited child but drawn in proportion to the root's visit counts
+        (temperature 1), so that the games of a batch leave the opening on different lines.  The draw is in integers
+        (include/iago_hip_serving.h, iago_mcts_search_explore): with n the turn's visit row `pi`, N its sum and w the
+        Philox word of (seed ^ EXPLORE_SEED_XOR; game_id_base + g, t), the lowest cell a with sum_{b <= a} n[b] >
+        (w * N) >> 32.  The record keeps its shape (valid 1, pi the visit row, move the drawn move); the one launch and
+        the turn loop play the same games; solve_empties composes (a parked turn is not searched, so not drawn)."""
         k = _solve_empties_arg(solve_empties)
-        res = self._one_launch(n_sims, self.B, handicap, record, solve_empties=k)
+        e = ops.explore_turns_arg(explore_turns)
+        kw = {} if e is None else dict(explore_turns=e)   # (off: today's calls, argument for argument)
+        res = self._one_launch(n_sims, self.B, handicap, record, solve_empties=k, **kw)
         if res is None:
-            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult(), solve_empties=k)
+            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult(), solve_empties=k,
+                                   **kw)
         return res
 
-    def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None):
+    def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -1815,8 +1849,11 @@ class SelfPlayEngine(object):
         up in the launch).  handicap: (n_games,) int64 bit masks of extra colour-2 stones.  The result has n_games
         columns (tuples() give the game ids game_id_base ..); n_turns is the longest game's, `launches` the launches it
         took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch.  solve_empties: as in play() --
-        the stream's games hand over at k empties and one launch plays all n_games out (launches = 2)."""
+        the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
+        as in play() -- game G draws with its own id, whichever slot plays it."""
         k = _solve_empties_arg(solve_empties)
+        e = ops.explore_turns_arg(explore_turns)
+        kw = {} if e is None else dict(explore_turns=e)
         m, T = self.mcts, self.max_turns
         n_games = int(n_games)
         if n_games < 1:
@@ -1827,9 +1864,9 @@ class SelfPlayEngine(object):
         if handicap is not None and tuple(handicap.shape) != (n_games,):
             raise ValueError("play_stream: handicap is an (n_games,) int64 tensor")
         plain = getattr(m, "z_log", None) is None and getattr(m, "trace", None) is None
-        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games, solve_empties=k)
+        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games, solve_empties=k, **kw)
         if res is None:
-            res = self._play_batches(n_sims, n_games, handicap, record, k)
+            res = self._play_batches(n_sims, n_games, handicap, record, k, **kw)
         return res
 
     def _match_colours(self, mcts_colour):
@@ -1872,7 +1909,7 @@ class SelfPlayEngine(object):
         res.mcts_colour = col
         return res
 
-    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None):
+    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None, explore_turns=None):
         """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same
         sim_counter, the first n_games columns kept."""
         m, B = self.mcts, self.B
@@ -1886,7 +1923,8 @@ class SelfPlayEngine(object):
                     hc = torch.zeros(B, dtype=torch.int64, device=handicap.device)
                     hc[:w] = handicap[k * B:k * B + w]
                 m.game_id_base, m.sim_counter = base + k * B, s0
-                parts.append((self.play(n_sims, handicap=hc, record=record, solve_empties=solve_empties), w))
+                parts.append((self.play(n_sims, handicap=hc, record=record, solve_empties=solve_empties,
+                                        explore_turns=explore_turns), w))
         finally:
             m.game_id_base = base
         res = SelfPlayResult()

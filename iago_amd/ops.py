@@ -5,6 +5,7 @@ Boards are int64 CUDA tensors holding the 64-bit bitboards (bit a = row*8+col;
 requires CUDA tensors: there is no CPU path.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -1049,3 +1050,40 @@ def check_play_endgame(back, out, max_empties, time_limit_ms):
     err = _lib.IagoError("iago_play_endgame: %s: %d games not played to their end" % (what, unfinished))
     err.result = out
     raise err
+
+
+def explore_turns_arg(k):
+    """explore_turns of SelfPlayEngine.play / play_stream: None or 0 (off: None is returned), or a positive int (at most
+    IAGO_MAX_TURNS turns are drawn, a larger value means every turn)."""
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 0:
+        raise ValueError("explore_turns must be None or an int >= 0, not %r" % (k,))
+    return min(int(k), IAGO_MAX_TURNS) or None
+
+
+def draw_move(tree, active, seed, game_id, turn, move, visits=None):
+    """iago_mcts_draw_move (include/iago_hip_serving.h): iago_mcts_best_move's sibling for exploring self-play.  move[g]
+    (int8) of every game with active[g] != 0 (active None: every game) is drawn in proportion to the visit counts of the
+    children of its tree's root: N = their sum, w = word turn[g] & 3 of Philox4x32-10 on (game_id[g], turn[g] >> 2, 0, 0)
+    under seed ^ EXPLORE_SEED_XOR, r = (w * N) >> 32, the lowest cell a with sum_{b <= a} n[b] > r (N == 0: the first
+    maximum; no children: -2).  tree: a pointer to the iago_mcts_tree (TreePool.ref()); game_id / turn (n_games,) int32,
+    game_id the GLOBAL ids (id_base + g) as their 32 bits; visits: optional (n_games, 64) int32, the visit row."""
+    check(_lib.lib().iago_mcts_draw_move(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                         C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(game_id, torch.int32, "game_id"),
+                                         _dev(turn, torch.int32, "turn"), _dev(move, torch.int8, "move"),
+                                         _dev(visits, torch.int32, "visits") if visits is not None else None, _stream()),
+          "iago_mcts_draw_move")
+    return move, visits
+
+
+def search_explore(args, explore_turns, streams=None, park=None):
+    """iago_mcts_search_explore (include/iago_hip_serving.h): the whole-game launch of `args` (a _lib.MctsSearchArgs)
+    whose searched moves of the turns below explore_turns are drawn from the visit counts; streams: the role split's
+    handle or None; park: a _lib.SearchParkArgs (the hand-over of iago_mcts_search_park in the same launch) or None.
+    The caller keeps `args`, `park` and everything they point to alive until the launch has run."""
+    e = _lib.SearchExploreArgs()
+    e.explore_turns = int(explore_turns)
+    e.streams = streams
+    e.park = C.addressof(park) if park is not None else None
+    check(_lib.lib().iago_mcts_search_explore(C.byref(args), C.byref(e), _stream()), "iago_mcts_search_explore")

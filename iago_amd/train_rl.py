@@ -330,6 +330,16 @@ class ReinforceTrainer(object):
         self.log.append(out)
         return out
 
+    def step_from_self_play(self, self_play, n_sims, colour=None, explore_turns=None, **play_kw):
+        """One MCTS-fed round: self_play (an engine.SelfPlayEngine of THIS rank's games, its BatchedMCTS built with
+        game_id_base = idist.shard_range(n_games)[0]) plays its batch with n_sims playouts per move and the tuples go
+        through step_from_tuples.  explore_turns (and any other keyword of SelfPlayEngine.play) is passed on: the
+        first turns' moves drawn from the visit counts, keyed by the GLOBAL game id, so the ranks' shards explore as
+        one batch would.  Returns step_from_tuples' dict and the round's SelfPlayResult."""
+        self.model1.eval()
+        res = self_play.play(n_sims, explore_turns=explore_turns, **play_kw)
+        return self.step_from_tuples(res.tuples(), colour=colour), res
+
     def step(self):
         """One set + one update; returns dict(rate, loss, saved)."""
         model2 = self.pick_opponent()

@@ -150,6 +150,48 @@ typedef struct iago_search_park_args {
  */
 IAGO_API int iago_mcts_search_park(const iago_mcts_search_args *args, const iago_search_park_args *park, void *stream);
 
+/* ------------------------------------------------------------------ exploring self-play */
+
+#define IAGO_EXPLORE_KEY 0x4558504Cu /* ("EXPL") the draws' Philox key: the rollout seed with its high word XOR this */
+
+typedef struct iago_search_explore_args {
+    int32_t explore_turns;             /* 0 .. IAGO_MAX_TURNS: the turns (the game's turn counter, passes included) whose
+                                          searched move is drawn; 0 = none */
+    int32_t reserved0;                 /* 0 */
+    iago_search_streams *streams;      /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    const iago_search_park_args *park; /* optional: the hand-over of iago_mcts_search_park in the same launch (its
+                                          `streams` NULL or the one above) */
+    int64_t reserved[4];               /* 0 */
+} iago_search_explore_args;
+
+/*
+ * Whole self-play games (iago_mcts_search_persistent with max_turns > 0, a stream included) that EXPLORE in their first
+ * explore_turns turns: at a searched turn t < explore_turns of the game with global id G (its index, a stream: its game
+ * id) the move is not the most visited child but drawn in proportion to the root's visit counts, in integers:
+ *   - n[a]: the visits of the root's children, the mover's legal moves in ascending cell order -- the turn's rec_pi row;
+ *     N = sum n[a];
+ *   - w: word t & 3 of Philox4x32-10 on the counter (rollout->id_base + G, t >> 2, 0, 0) under the key rollout->seed with
+ *     its high word XOR IAGO_EXPLORE_KEY; r = (uint64(w) * N) >> 32;
+ *   - the move is the lowest cell a with sum_{b <= a} n[b] > r (a cell without visits is never drawn).
+ * N == 0 (children, none visited): the first maximum, as without the draw; no children: ctl[4] is raised as before.  The
+ * record keeps its shape (valid 1, rec_pi the visit row, rec_move the drawn move) and the drawn child becomes the root.
+ * Turns from explore_turns on, and everything with explore_turns = 0, are iago_mcts_search_persistent's (with `streams`
+ * iago_mcts_search_split's, with `park` iago_mcts_search_park's), bit for bit.  Refused (IAGO_ERR_INVALID): null args, an
+ * explore_turns outside 0 .. IAGO_MAX_TURNS, reserved fields not 0, a bad `park`, max_turns == 0, and match codes (2 / 3)
+ * in `active` (read as iago_mcts_search_park reads it; not in a stream).
+ */
+IAGO_API int iago_mcts_search_explore(const iago_mcts_search_args *args, const iago_search_explore_args *explore, void *stream);
+
+/*
+ * iago_mcts_best_move's sibling for the turn loop: move[g] of every game with active[g] != 0 (active NULL: every game) is
+ * drawn by the rule above from the children of its tree's root, with id game_id[g] (the GLOBAL id, id_base + G, as its 32
+ * bits) and turn turn[g], under `seed` (the rollout seed; the XOR is applied here).  visits (optional [n_games][64]): the
+ * root's visit counts by action, as iago_mcts_best_move writes them.  N == 0: the first maximum; no children: -2.
+ * Refused (IAGO_ERR_INVALID): a bad tree, null game_id, turn or move.
+ */
+IAGO_API int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
+                                 const int32_t *turn, int8_t *move, int32_t *visits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

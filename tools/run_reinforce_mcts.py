@@ -6,7 +6,7 @@ policy net, a fixed random-init Value net, shipped RolloutPolicy) -> SelfPlayRes
 ReinforceTrainer.step_from_tuples (gather, canonical order, double-softmax REINFORCE update,
 ChainerAdam + weight decay; the search engine re-captures its graph when the weights change).
 One JSON line.
-    python3 tools/run_reinforce_mcts.py [iters=1000] [games=64] [sims=20]"""
+    python3 tools/run_reinforce_mcts.py [iters=1000] [games=64] [sims=20] [explore_turns=0]"""
 import json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +18,7 @@ from iago_amd.train_rl import ReinforceTrainer  # noqa: E402
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 games = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 sims = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+explore = int(sys.argv[4]) if len(sys.argv) > 4 else 0   # turns whose moves are drawn from the visit counts
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -28,9 +29,7 @@ sp = engine.SelfPlayEngine(m)
 
 
 def one():
-    tr.model1.eval()
-    res = sp.play(sims)
-    return tr.step_from_tuples(res.tuples()), res
+    return tr.step_from_self_play(sp, sims, explore_turns=explore)
 
 
 for _ in range(2):
