@@ -53,9 +53,10 @@ SERVING_SYMBOLS = [
     "iago_mcts_search_explore", "iago_mcts_draw_move",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
-# (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True))
+# (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
+# (network.SLPolicy.visits_grads, train_rl.ReinforceTrainer.step_from_tuples(target="visits"))
 TRAINING_SYMBOLS = [
-    "iago_value_grad_workspace_bytes", "iago_value_mse_grad",
+    "iago_value_grad_workspace_bytes", "iago_value_mse_grad", "iago_policy_visits_grad",
 ]
 
 
@@ -104,6 +105,13 @@ class PolicyGradArgs(C.Structure):
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
         ("overflow", C.c_void_p),
     ]
+
+
+class PolicyVisitsGradArgs(C.Structure):
+    """Mirror of iago_policy_visits_grad_args (include/iago_hip_training.h): PolicyGradArgs with action / reward
+    replaced by visits / weight."""
+    _fields_ = [("visits", t) if f == "action" else ("weight", t) if f == "reward" else (f, t)
+                for f, t in PolicyGradArgs._fields_]
 
 
 class ValueGradArgs(C.Structure):
@@ -355,6 +363,7 @@ def lib():
     L.iago_adam_chainer.argtypes = [C.POINTER(AdamArgs), vp]
     L.iago_value_grad_workspace_bytes.argtypes = [i64]
     L.iago_value_mse_grad.argtypes = [C.POINTER(ValueGradArgs), vp]
+    L.iago_policy_visits_grad.argtypes = [C.POINTER(PolicyVisitsGradArgs), vp]
     L.iago_split_nchw.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.iago_merge_nchw.argtypes = [vp, vp, vp, i64, i32, vp]
     L.iago_value_stem.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]

@@ -352,6 +352,86 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
+// ---- What the heads of SLPolicy's two losses share (head_grad_kernel, head_visits_grad_kernel): one wave per board,
+// lane = cell
+// x[c] = block 8's output at this lane's cell, the exact values hi + lo 2^-11
+__device__ __forceinline__ void head_load_x8(const uint4 *x_hi, const uint4 *x_lo, int64_t b, int lane, float (&x)[128])
+{
+#pragma unroll
+    for (int cb = 0; cb < 8; cb++) {
+        const int64_t at = ((b * 8 + cb) * 64 + lane) * 2;
+        const uint4 h0 = x_hi[at], h1 = x_hi[at + 1], l0 = x_lo[at], l1 = x_lo[at + 1];
+        const __half2 *hh0 = (const __half2 *)&h0, *hh1 = (const __half2 *)&h1;
+        const __half2 *ll0 = (const __half2 *)&l0, *ll1 = (const __half2 *)&l1;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float2 a = __half22float2(hh0[k]), c2 = __half22float2(ll0[k]);
+            const float2 d = __half22float2(hh1[k]), e2 = __half22float2(ll1[k]);
+            x[16 * cb + 2 * k] = a.x + c2.x * (1.0f / 2048.0f);
+            x[16 * cb + 2 * k + 1] = a.y + c2.y * (1.0f / 2048.0f);
+            x[16 * cb + 8 + 2 * k] = d.x + e2.x * (1.0f / 2048.0f);
+            x[16 * cb + 8 + 2 * k + 1] = d.y + e2.y * (1.0f / 2048.0f);
+        }
+    }
+}
+// p = softmax(conv9 . x + bias10) over the board (F.softmax, network.py:46); shifted = logit - max logit and
+// sum = sum exp(shifted): log p = shifted - log(sum)
+__device__ __forceinline__ float head_softmax(const float *w9, const float (&x)[128], float my_b10, float &shifted,
+                                              float &sum)
+{
+    float logit = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 128; c++)
+        logit = fmaf(w9[c], x[c], logit);
+    logit += my_b10;
+    shifted = logit - wave_max(logit);
+    const float ex = expf(shifted);
+    sum = wave_sum(ex);
+    return ex / sum;
+}
+// dl = the loss's gradient at this cell's logit: acc9 += dl x (dW9), dY8 = [x8 > 0] dl w9 to dy, its largest magnitude
+__device__ __forceinline__ void head_write_back(float dl, const float (&x)[128], const float *w9, float4v *dy, int64_t b,
+                                                int lane, float (&acc9)[128], float &big)
+{
+#pragma unroll
+    for (int cb = 0; cb < 8; cb++) {
+#pragma unroll
+        for (int qt = 0; qt < 4; qt++) {
+            float4v v;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int c = 16 * cb + 4 * qt + k;
+                acc9[c] = fmaf(dl, x[c], acc9[c]);
+                v[k] = x[c] > 0.0f ? dl * w9[c] : 0.0f;
+                big = fmaxf(big, fabsf(v[k]));
+            }
+            dy[((b * 8 + cb) * 64 + lane) * 4 + qt] = v;
+        }
+    }
+}
+// a workgroup's partial sums to part[blockIdx.x][HEAD_PART], the largest magnitude to max_bits
+__device__ __forceinline__ void head_finish(float (*red)[HEAD_PART], const float (&acc9)[128], float acc_b,
+                                            float acc_loss, float big, uint32_t *max_bits, float *part)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    big = wave_max(big);
+    if (lane == 0 && big > 0.0f)
+        atomicMax(max_bits, __float_as_uint(big));
+#pragma unroll
+    for (int c = 0; c < 128; c++) {
+        const float s = wave_sum(acc9[c]);
+        if (lane == 0)
+            red[wv][c] = s;
+    }
+    red[wv][128 + lane] = acc_b;
+    if (lane == 0)
+        red[wv][192] = acc_loss; // (the same in every lane)
+    __syncthreads();
+    if (threadIdx.x < HEAD_PART)
+        part[(int64_t)blockIdx.x * HEAD_PART + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
 __global__ __launch_bounds__(256) void head_grad_kernel(HeadGradParams P)
 {
     __shared__ float red[4][HEAD_PART];
@@ -363,31 +443,9 @@ __global__ __launch_bounds__(256) void head_grad_kernel(HeadGradParams P)
     float acc_b = 0.0f, acc_loss = 0.0f, big = 0.0f;
     const float my_b10 = P.b10[lane];
     for (int64_t b = (int64_t)blockIdx.x * 4 + wv; b < P.n; b += (int64_t)gridDim.x * 4) {
-        float x[128];
-#pragma unroll
-        for (int cb = 0; cb < 8; cb++) {
-            const int64_t at = ((b * 8 + cb) * 64 + lane) * 2;
-            const uint4 h0 = P.x_hi[at], h1 = P.x_hi[at + 1], l0 = P.x_lo[at], l1 = P.x_lo[at + 1];
-            const __half2 *hh0 = (const __half2 *)&h0, *hh1 = (const __half2 *)&h1;
-            const __half2 *ll0 = (const __half2 *)&l0, *ll1 = (const __half2 *)&l1;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float2 a = __half22float2(hh0[k]), c2 = __half22float2(ll0[k]);
-                const float2 d = __half22float2(hh1[k]), e2 = __half22float2(ll1[k]);
-                x[16 * cb + 2 * k] = a.x + c2.x * (1.0f / 2048.0f);
-                x[16 * cb + 2 * k + 1] = a.y + c2.y * (1.0f / 2048.0f);
-                x[16 * cb + 8 + 2 * k] = d.x + e2.x * (1.0f / 2048.0f);
-                x[16 * cb + 8 + 2 * k + 1] = d.y + e2.y * (1.0f / 2048.0f);
-            }
-        }
-        float logit = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 128; c++)
-            logit = fmaf(P.w9[c], x[c], logit);
-        logit += my_b10;
-        const float m = wave_max(logit);
-        const float ex = expf(logit - m);
-        const float p = ex / wave_sum(ex);                          // F.softmax, network.py:46
+        float x[128], shifted, sum;
+        head_load_x8(P.x_hi, P.x_lo, b, lane, x);
+        const float p = head_softmax(P.w9, x, my_b10, shifted, sum);
         if (P.probs)
             P.probs[b * 64 + lane] = p;
         const int a = P.action[b];
@@ -404,38 +462,65 @@ __global__ __launch_bounds__(256) void head_grad_kernel(HeadGradParams P)
         const float g = z * P.inv_n * (ex2 / s2 - (lane == a ? 1.0f : 0.0f));
         const float dl = p * (g - wave_sum(g * p));                 // through the model's softmax
         acc_b += dl;
-#pragma unroll
-        for (int cb = 0; cb < 8; cb++) {
-#pragma unroll
-            for (int qt = 0; qt < 4; qt++) {
-                float4v v;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int c = 16 * cb + 4 * qt + k;
-                    acc9[c] = fmaf(dl, x[c], acc9[c]);
-                    v[k] = x[c] > 0.0f ? dl * P.w9[c] : 0.0f;
-                    big = fmaxf(big, fabsf(v[k]));
-                }
-                P.dy[((b * 8 + cb) * 64 + lane) * 4 + qt] = v;
-            }
-        }
+        head_write_back(dl, x, P.w9, P.dy, b, lane, acc9, big);
     }
-    big = wave_max(big);
-    if (lane == 0 && big > 0.0f)
-        atomicMax(P.max_bits, __float_as_uint(big));
+    head_finish(red, acc9, acc_b, acc_loss, big, P.max_bits, P.part);
+}
+
+// ---- The head of SLPolicy under the visit-count loss: the cross-entropy of the model's output (ONE softmax) against
+// the search's visit distribution t = n / N of the row (engine.SelfPlayResult.tuples()["pi"]), weighted per row:
+//   loss = sum_b w_b sum_{a: n[a] > 0} -t[a] log p[a] / n_mean,  log p = (logit - max) - log sum exp(logit - max)
+//   dlogits = (w / n_mean) (p - t)
+// (never logf(p): a cell whose p underflowed keeps a finite log p).  A row with N == 0 contributes nothing; so does a
+// row with a negative count, which raises bit 1 of `bad` besides.  Launch shape, partial sums and dY8 as
+// head_grad_kernel.
+struct HeadVisitsGradParams {
+    const uint4 *x_hi, *x_lo;  // [n][8][64][16] f16: the output of block 8
+    const float *w9, *b10;     // [128], [64]
+    const int32_t *visits;     // [n][64]
+    const float *weight;       // optional [n] (NULL: 1)
+    float inv_n;               // 1 / (rows the mean divides by)
+    int64_t n;
+    float4v *dy;               // [n][8][64][16] float32
+    uint32_t *max_bits;
+    float *part;               // [gridDim.x][193]: dW9 (128), dbias10 (64), loss (1) of each workgroup
+    float *probs;              // optional [n][64]: the model's output
+    uint32_t *bad;             // optional: bit 1 raised by a negative count
+};
+
+__global__ __launch_bounds__(256) void head_visits_grad_kernel(HeadVisitsGradParams P)
+{
+    __shared__ float red[4][HEAD_PART];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float acc9[128];
 #pragma unroll
-    for (int c = 0; c < 128; c++) {
-        const float s = wave_sum(acc9[c]);
-        if (lane == 0)
-            red[wv][c] = s;
+    for (int c = 0; c < 128; c++)
+        acc9[c] = 0.0f;
+    float acc_b = 0.0f, acc_loss = 0.0f, big = 0.0f;
+    const float my_b10 = P.b10[lane];
+    for (int64_t b = (int64_t)blockIdx.x * 4 + wv; b < P.n; b += (int64_t)gridDim.x * 4) {
+        float x[128], shifted, sum;
+        head_load_x8(P.x_hi, P.x_lo, b, lane, x);
+        const float p = head_softmax(P.w9, x, my_b10, shifted, sum);
+        if (P.probs)
+            P.probs[b * 64 + lane] = p;
+        const int32_t nv = P.visits[b * 64 + lane];
+        const float w = P.weight ? P.weight[b] : 1.0f;
+        int64_t total = nv;                                         // (64 bits: any int32 counts sum without wrapping)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1)
+            total += __shfl_xor(total, d);
+        const bool negative = __ballot(nv < 0) != 0;
+        if (negative && lane == 0 && P.bad)
+            atomicOr(P.bad, 2u); // (the caller must not use this update)
+        const bool live = total > 0 && !negative;
+        const float t = live ? (float)nv / (float)total : 0.0f;
+        acc_loss += w * wave_sum(t > 0.0f ? -t * (shifted - logf(sum)) : 0.0f);
+        const float dl = live ? w * P.inv_n * (p - t) : 0.0f;
+        acc_b += dl;
+        head_write_back(dl, x, P.w9, P.dy, b, lane, acc9, big);
     }
-    red[wv][128 + lane] = acc_b;
-    if (lane == 0)
-        red[wv][192] = acc_loss; // (the same in every lane)
-    __syncthreads();
-    if (threadIdx.x < HEAD_PART)
-        P.part[(int64_t)blockIdx.x * HEAD_PART + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    head_finish(red, acc9, acc_b, acc_loss, big, P.max_bits, P.part);
 }
 
 // out[j] = (j == 192 ? inv_n : 1) * sum over the workgroups' partial sums: one wave per output, lane l takes the partial
@@ -1068,6 +1153,50 @@ int iago_policy_reinforce_grad(const iago_policy_grad_args *A, void *stream)
         return IAGO_OK;
     };
     return pg_trunk_grad(T, A->workspace, stream, "iago_policy_reinforce_grad", head);
+}
+
+int iago_policy_visits_grad(const iago_policy_visits_grad_args *A, void *stream)
+{
+    if (!A)
+        return iago_fail(IAGO_ERR_INVALID, "iago_policy_visits_grad: null arguments");
+    const int64_t n = A->n;
+    if (n <= 0 || A->n_mean <= 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_policy_visits_grad: n and n_mean must be positive");
+    if (!A->own || !A->opp || !A->visits || !A->w1 || !A->b1 || !A->w9 || !A->b10 || !A->g_w1 || !A->g_b1 ||
+        !A->g_w9 || !A->g_b10 || !A->loss || !A->workspace)
+        return iago_fail(IAGO_ERR_INVALID, "iago_policy_visits_grad: null pointer");
+    for (int k = 0; k < 7; k++)
+        if (!A->w_hi[k] || !A->w_lo[k] || !A->wt_hi[k] || !A->wt_lo[k] || !A->bias[k] || !A->g_w[k] || !A->g_b[k])
+            return iago_fail(IAGO_ERR_INVALID, "iago_policy_visits_grad: null pointer (blocks 2..8)");
+    if (A->workspace_bytes < iago_policy_grad_workspace_bytes(n) || ((uintptr_t)A->workspace & 255))
+        return iago_fail(IAGO_ERR_INVALID, "iago_policy_visits_grad: workspace too small or not 256-byte aligned "
+                                           "(iago_policy_grad_workspace_bytes)");
+    const PgTrunk T = {A->own, A->opp, n, A->w1, A->b1, A->w_hi, A->w_lo, A->wt_hi, A->wt_lo, A->bias,
+                       A->g_w1, A->g_b1, A->g_w, A->g_b, A->overflow};
+    // head + loss, forward and backward: the cross-entropy against the rows' visit distributions
+    auto head = [&](const PgScratch &S) {
+        hipStream_t st = (hipStream_t)stream;
+        const float inv_n = 1.0f / (float)A->n_mean;
+        HeadVisitsGradParams H;
+        H.x_hi = (const uint4 *)S.x_hi[7];
+        H.x_lo = (const uint4 *)S.x_lo[7];
+        H.w9 = A->w9;
+        H.b10 = A->b10;
+        H.visits = A->visits;
+        H.weight = A->weight;
+        H.inv_n = inv_n;
+        H.n = n;
+        H.dy = (float4v *)S.dyf;
+        H.max_bits = S.max_bits + 7;
+        H.part = S.hpart;
+        H.probs = A->probs;
+        H.bad = A->overflow;
+        hipLaunchKernelGGL(head_visits_grad_kernel, dim3(PG_GRID), dim3(256), 0, st, H);
+        hipLaunchKernelGGL(head_reduce_kernel, dim3((HEAD_PART + 3) / 4), dim3(256), 0, st, (const float *)S.hpart,
+                           PG_GRID, inv_n, A->g_w9, A->g_b10, A->loss);
+        return IAGO_OK;
+    };
+    return pg_trunk_grad(T, A->workspace, stream, "iago_policy_visits_grad", head);
 }
 
 // the head's scratch behind the trunk's: h9, dh10, dpre9 per board, the two head kernels' partial sums

@@ -180,21 +180,18 @@ class SLPolicy(nn.Module, _NpzMixin):
 
     GRAD_CHUNK_ROWS = int(os.environ.get("IAGO_GRAD_CHUNK_ROWS", "4096"))   # 1.25 GB of scratch per chunk
 
-    def reinforce_grads(self, own, opp, action, reward, n_mean=None, probs=None):
-        """src/train_rl.py:61-65 on the matrix units in split-f16 arithmetic (iago_policy_reinforce_grad):
-        cleargrads + loss.backward() for loss = mean(softmax_cross_entropy(self(x), action) * reward); every
-        parameter's .grad is overwritten.  own / opp: the recorded positions (own = the mover); action in 0 .. 63 (an
-        action outside raises bit 1 of the module's overflow word: ReinforceTrainer reads it before Adam).  Returns the loss (0-dim device tensor).  The first two f16 pieces of the search
-        path's three-piece weights are the forward's.  The kernels' scratch (308 KB per row + 247 MB, kept between
-        calls) is freed by ops.release_grad_workspace()."""
-        from . import ops
+    def _grads_in_chunks(self, who, own, opp, n_mean, probs, call):
+        """What reinforce_grads and visits_grads share: every parameter's .grad made ready, then call(lo, hi, n_mean,
+        common) -> loss for the rows lo .. hi, common = the keywords both ops entry points take (the weights' forms,
+        the gradients' tensors, probs[lo:hi], the module's overflow word), over the whole batch in chunks of
+        GRAD_CHUNK_ROWS rows."""
         convs = [getattr(self, "block%d" % k).conv for k in range(2, 9)]
         params = [self.block1.conv.weight, self.block1.conv.bias, self.conv9.weight, self.bias10.b]
         for c in convs:
             params += [c.weight, c.bias]
         for p in params:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError("reinforce_grads: float32 CUDA parameters expected")
+                raise ValueError("%s: float32 CUDA parameters expected" % who)
             if p.grad is None:
                 p.grad = torch.empty_like(p)
         layers = [(hi, mid, bias) for hi, mid, lo, bias in self._split3_layers()]
@@ -203,16 +200,13 @@ class SLPolicy(nn.Module, _NpzMixin):
                      w9=self.conv9.weight.grad, b10=self.bias10.b.grad)
         n = own.numel()
         n_mean = n if n_mean is None else n_mean
-        own, opp = own.contiguous(), opp.contiguous()
-        action, reward = action.to(torch.int32).contiguous(), reward.to(torch.float32).contiguous()
         layers_t = self._bwd_layers()
 
         def rows(lo, hi):
-            return ops.policy_reinforce_grad(own[lo:hi], opp[lo:hi], action[lo:hi], reward[lo:hi], n_mean,
-                                             self.block1.conv.weight.detach(), self.block1.conv.bias.detach(), layers,
-                                             layers_t, self.conv9.weight.detach(), self.bias10.b.detach(), grads,
-                                             probs=None if probs is None else probs[lo:hi],
-                                             overflow=self._overflow_flag(own.device))
+            return call(lo, hi, n_mean, dict(
+                w1=self.block1.conv.weight.detach(), b1=self.block1.conv.bias.detach(), layers=layers,
+                layers_t=layers_t, w9=self.conv9.weight.detach(), b10=self.bias10.b.detach(), grads=grads,
+                probs=None if probs is None else probs[lo:hi], overflow=self._overflow_flag(own.device)))
         # The kernels' scratch is 308 KB per row: a PV-MCTS round of 1024 games (~61 k rows, both colours) would take
         # 18 GB at once.  Larger batches run in chunks of GRAD_CHUNK_ROWS rows, every chunk dividing by the same
         # n_mean, the chunks' gradients added in chunk order (deterministic); a batch within one chunk is one call.
@@ -229,6 +223,45 @@ class SLPolicy(nn.Module, _NpzMixin):
         for t, p in zip(total, params):
             p.grad.copy_(t)
         return loss
+
+    def reinforce_grads(self, own, opp, action, reward, n_mean=None, probs=None):
+        """src/train_rl.py:61-65 on the matrix units in split-f16 arithmetic (iago_policy_reinforce_grad):
+        cleargrads + loss.backward() for loss = mean(softmax_cross_entropy(self(x), action) * reward); every
+        parameter's .grad is overwritten.  own / opp: the recorded positions (own = the mover); action in 0 .. 63 (an
+        action outside raises bit 1 of the module's overflow word: ReinforceTrainer reads it before Adam).  Returns the loss (0-dim device tensor).  The first two f16 pieces of the search
+        path's three-piece weights are the forward's.  The kernels' scratch (308 KB per row + 247 MB, kept between
+        calls) is freed by ops.release_grad_workspace()."""
+        from . import ops
+        own, opp = own.contiguous(), opp.contiguous()
+        action, reward = action.to(torch.int32).contiguous(), reward.to(torch.float32).contiguous()
+        return self._grads_in_chunks(
+            "reinforce_grads", own, opp, n_mean, probs,
+            lambda lo, hi, n_mean, common: ops.policy_reinforce_grad(own[lo:hi], opp[lo:hi], action[lo:hi],
+                                                                      reward[lo:hi], n_mean, **common))
+
+    def visits_grads(self, own, opp, visits, weight=None, n_mean=None, probs=None):
+        """The policy trained toward the search's own visit distribution, on the kernels of reinforce_grads
+        (iago_policy_visits_grad): every parameter's .grad is overwritten with the gradient of
+        loss = sum_b weight_b * cross_entropy(softmax(self.logits(x_b)), visits_b / sum(visits_b)) / n_mean
+        -- ONE softmax, unlike the reference's REINFORCE loss; train_rl.visits_loss_from_logits is the same formula in
+        torch.  own / opp: the searched positions (own = the mover); visits: int32 (n, 64), the root's visit row
+        (SelfPlayResult.tuples()["pi"]); a row of zeros contributes nothing, a negative count raises bit 1 of the
+        module's overflow word (ReinforceTrainer reads it before Adam); weight: (n,) or None = 1; n_mean: the row
+        count the mean divides by (default n).  Returns the loss (0-dim device tensor).  Chunks and scratch as
+        reinforce_grads."""
+        from . import ops
+        n = own.numel()
+        if not isinstance(visits, torch.Tensor) or visits.dtype != torch.int32 or tuple(visits.shape) != (n, 64):
+            raise ValueError("visits_grads: visits must be an int32 tensor of shape (n, 64) = (%d, 64)" % n)
+        if weight is not None and tuple(weight.shape) != (n,):
+            raise ValueError("visits_grads: weight must have shape (n,) = (%d,)" % n)
+        own, opp, visits = own.contiguous(), opp.contiguous(), visits.contiguous()
+        weight = None if weight is None else weight.to(torch.float32).contiguous()
+        return self._grads_in_chunks(
+            "visits_grads", own, opp, n_mean, probs,
+            lambda lo, hi, n_mean, common: ops.policy_visits_grad(own[lo:hi], opp[lo:hi], visits[lo:hi],
+                                                                   None if weight is None else weight[lo:hi],
+                                                                   n_mean, **common))
 
     def _split3_template(self):
         """iago_policy_split3_args with this module's weights, rebuilt when they change."""

@@ -608,19 +608,13 @@ def release_grad_workspace():
     _grad_workspace.clear()
 
 
-def policy_reinforce_grad(own, opp, action, reward, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs=None,
-                          overflow=None):
-    """iago_policy_reinforce_grad (include/iago_hip.h): the gradients of mean(softmax_cross_entropy(model(x), a) * r)
-    (src/train_rl.py:61-65) written to `grads` = dict(w1, b1, w=[7], b=[7], w9, b10) of float32 tensors in the
-    parameters' shapes.  layers: 7 x (w_hi, w_lo, bias) as for conv3x3_split; layers_t: 7 x (wt_hi, wt_lo) from
-    split_weights_transposed.  Returns the loss (0-dim float32 device tensor)."""
+def _policy_grad_common(A, own, opp, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs, overflow):
+    """The fields iago_policy_grad_args and iago_policy_visits_grad_args share.  Returns the loss's device word."""
     n = own.numel()
     dev = own.device
     ws = policy_grad_workspace(dev, n)
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    A = _lib.PolicyGradArgs()
     A.own, A.opp = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp")
-    A.action, A.reward = _dev(action, torch.int32, "action"), _dev(reward, torch.float32, "reward")
     A.n, A.n_mean = n, int(n_mean)
     A.w1, A.b1 = _dev(w1, torch.float32, "w1"), _dev(b1, torch.float32, "b1")
     for k in range(7):
@@ -636,7 +630,39 @@ def policy_reinforce_grad(own, opp, action, reward, n_mean, w1, b1, layers, laye
     A.probs = _dev(probs, torch.float32, "probs") if probs is not None else None
     A.workspace, A.workspace_bytes = ws.data_ptr(), ws.numel()
     A.overflow = _flag(overflow)
+    return loss
+
+
+def policy_reinforce_grad(own, opp, action, reward, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs=None,
+                          overflow=None):
+    """iago_policy_reinforce_grad (include/iago_hip.h): the gradients of mean(softmax_cross_entropy(model(x), a) * r)
+    (src/train_rl.py:61-65) written to `grads` = dict(w1, b1, w=[7], b=[7], w9, b10) of float32 tensors in the
+    parameters' shapes.  layers: 7 x (w_hi, w_lo, bias) as for conv3x3_split; layers_t: 7 x (wt_hi, wt_lo) from
+    split_weights_transposed.  Returns the loss (0-dim float32 device tensor)."""
+    A = _lib.PolicyGradArgs()
+    loss = _policy_grad_common(A, own, opp, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs, overflow)
+    A.action, A.reward = _dev(action, torch.int32, "action"), _dev(reward, torch.float32, "reward")
     check(_lib.lib().iago_policy_reinforce_grad(C.byref(A), _stream()), "iago_policy_reinforce_grad")
+    return loss
+
+
+def policy_visits_grad(own, opp, visits, weight, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs=None,
+                       overflow=None):
+    """iago_policy_visits_grad (include/iago_hip_training.h): the gradients of the cross-entropy of model(x) against
+    the rows' visit distributions visits / sum(visits), weighted per row, summed and divided by n_mean; written to
+    `grads` as policy_reinforce_grad writes them (the same layers, layers_t).  visits: (n, 64) int32, >= 0 (a negative
+    count raises bit 1 of `overflow`); weight: (n,) float32 or None (1 for every row).  Returns the loss (0-dim float32
+    device tensor)."""
+    n = own.numel()
+    if visits.dtype != torch.int32 or tuple(visits.shape) != (n, 64):
+        raise ValueError("policy_visits_grad: visits must be int32 (n, 64)")
+    if weight is not None and tuple(weight.shape) != (n,):
+        raise ValueError("policy_visits_grad: weight must be (n,)")
+    A = _lib.PolicyVisitsGradArgs()
+    loss = _policy_grad_common(A, own, opp, n_mean, w1, b1, layers, layers_t, w9, b10, grads, probs, overflow)
+    A.visits = _dev(visits, torch.int32, "visits")
+    A.weight = _dev(weight, torch.float32, "weight") if weight is not None else None
+    check(_lib.lib().iago_policy_visits_grad(C.byref(A), _stream()), "iago_policy_visits_grad")
     return loss
 
 

@@ -164,6 +164,38 @@ def reinforce_loss(model, own, opp, actions, rewards, pad_to=None):
     return torch.sum(c * rewards.to(torch.float32)) / n              # F.mean(c * r)
 
 
+def visits_loss_from_logits(logits, visits, weight=None, n_mean=None):
+    """The cross-entropy of softmax(logits) against the rows' visit distributions, as iago_policy_visits_grad computes
+    it (include/iago_hip_training.h): with t = visits / sum(visits) per row (a row of zeros: t = 0, the row contributes
+    nothing), loss = sum_b weight_b sum_{a: visits[b, a] > 0} -t[b, a] log_softmax(logits)[b, a] / n_mean.  Pure
+    torch, any device, the dtype of `logits`; n_mean: the row count the mean divides by (default: the rows)."""
+    v = visits.to(logits.dtype)
+    total = v.sum(dim=1, keepdim=True)
+    t = torch.where(total > 0, v / total.clamp(min=1), torch.zeros_like(v))
+    logp = torch.log_softmax(logits, dim=1)
+    # (where, not a product: a cell without visits drops out even where its log p is -inf)
+    row = -torch.where(visits > 0, t * logp, torch.zeros_like(logp)).sum(dim=1)
+    if weight is not None:
+        row = row * weight.to(logits.dtype)
+    return row.sum() / (logits.shape[0] if n_mean is None else n_mean)
+
+
+def visits_loss(model, own, opp, visits, weight=None, pad_to=None):
+    """visits_loss_from_logits through model.logits on the positions' planes: the float32 autograd form of
+    SLPolicy.visits_grads.  pad_to: as reinforce_loss -- the batch rounded up with rows of zero visits (exactly 0 to
+    the loss and its gradient; the mean still divides by the true count)."""
+    n = own.numel()
+    if pad_to and n % pad_to:
+        extra = pad_to - n % pad_to
+        own = torch.cat([own, own[:1].expand(extra)])
+        opp = torch.cat([opp, opp[:1].expand(extra)])
+        visits = torch.cat([visits, torch.zeros((extra, 64), dtype=visits.dtype, device=visits.device)])
+        if weight is not None:
+            weight = torch.cat([weight, torch.zeros(extra, dtype=weight.dtype, device=weight.device)])
+    x = ops.encode_planes(own.contiguous(), opp.contiguous())
+    return visits_loss_from_logits(model.logits(x), visits, weight, n_mean=n)
+
+
 class ReinforceTrainer(object):
     """The loop of src/train_rl.py:28-81 with the reference's constants."""
 
@@ -255,29 +287,33 @@ class ReinforceTrainer(object):
         self.gather_seconds += time.perf_counter() - t0  # (bench.py: `gather_ms` of the weak-scaling set)
         return tup, n_win
 
-    def _update(self, own, opp, actions, rewards):
-        """src/train_rl.py:55-66 on a gathered batch: loss, backward, Adam step; every replica
-        then takes rank 0's parameters (one collective)."""
+    def _native(self, own):
+        """Whether an update of these rows runs on the split-f16 gradient kernels."""
         # (the split-f16 kernels clamp at the f16 range like the three-piece forward: a model set to `split3 = False`
         # -- the documented remedy when activations leave that range -- takes float32 autograd here as well)
-        if (NATIVE_GRAD and isinstance(self.model1, network.SLPolicy) and getattr(self.model1, "split3", False)
-                and own.is_cuda):
-            loss = self.model1.reinforce_grads(own, opp, actions, rewards)
-            # the forward's saturation word and the loss in ONE read-back, BEFORE Adam is applied and broadcast: the
-            # gradients of a clamped net (or of a row with an action outside 0 .. 63) must not reach the parameters
-            flag = self.model1._overflow_flag(own.device)
-            loss_v, bad = torch.stack([loss.to(torch.float64), flag[0].to(torch.float64)]).tolist()
-            if bad:
-                flag.zero_()
-                raise _lib.IagoError(
-                    "REINFORCE update: %s; no update was applied.  Set `model1.split3 = False` (float32 forward and "
-                    "autograd update) or IAGO_NATIVE_GRAD=0 (float32 autograd update only)"
-                    % ("an action lies outside 0 .. 63" if int(bad) & 2 else
-                       "an activation of the update's forward left the f16 range of the split kernels (|a| > 65000) "
-                       "or is NaN"))
-            self.opt.update()
-            idist.broadcast_tensors(list(self.model1.parameters()))  # replicas stay identical
-            return torch.tensor(loss_v, dtype=torch.float32)
+        return bool(NATIVE_GRAD and isinstance(self.model1, network.SLPolicy) and getattr(self.model1, "split3", False)
+                    and own.is_cuda)
+
+    def _apply_native(self, loss, device, what, bad_rows):
+        """The end of an update whose gradients the split-f16 kernels left in .grad: the forward's saturation word and
+        the loss in ONE read-back, BEFORE Adam is applied and broadcast -- the gradients of a clamped net (or of a row
+        that raised bit 1: `bad_rows` says what that means for this loss) must not reach the parameters."""
+        flag = self.model1._overflow_flag(device)
+        loss_v, bad = torch.stack([loss.to(torch.float64), flag[0].to(torch.float64)]).tolist()
+        if bad:
+            flag.zero_()
+            raise _lib.IagoError(
+                "%s: %s; no update was applied.  Set `model1.split3 = False` (float32 forward and "
+                "autograd update) or IAGO_NATIVE_GRAD=0 (float32 autograd update only)"
+                % (what, bad_rows if int(bad) & 2 else
+                   "an activation of the update's forward left the f16 range of the split kernels (|a| > 65000) "
+                   "or is NaN"))
+        self.opt.update()
+        idist.broadcast_tensors(list(self.model1.parameters()))  # replicas stay identical
+        return torch.tensor(loss_v, dtype=torch.float32)
+
+    def _apply_autograd(self, own, loss_of):
+        """The float32 autograd form of an update: loss_of(pad_to) -> the loss, backward, Adam, broadcast."""
         self.model1.train()
         for p in self.model1.parameters():
             p.grad = None
@@ -286,14 +322,30 @@ class ReinforceTrainer(object):
         # new shape costs a 15 s solver search on a fresh box: seen once inside a 1000-round run with multiples of 512)
         n = int(own.numel())
         granule = max(512, (1 << max(n - 1, 1).bit_length()) // 4)
-        loss = reinforce_loss(self.model1, own, opp, actions, rewards, pad_to=granule)
+        loss = loss_of(granule)
         loss.backward()
         self.opt.update()
         idist.broadcast_tensors(list(self.model1.parameters()))  # replicas stay identical
         return loss
 
-    def step_from_tuples(self, tup, colour=None):
-        """One REINFORCE update from the tuples of a PV-MCTS self-play round (BASELINE
+    def _update(self, own, opp, actions, rewards):
+        """src/train_rl.py:55-66 on a gathered batch: loss, backward, Adam step; every replica
+        then takes rank 0's parameters (one collective)."""
+        if self._native(own):
+            loss = self.model1.reinforce_grads(own, opp, actions, rewards)
+            return self._apply_native(loss, own.device, "REINFORCE update", "an action lies outside 0 .. 63")
+        return self._apply_autograd(own, lambda pad: reinforce_loss(self.model1, own, opp, actions, rewards, pad_to=pad))
+
+    def _update_visits(self, own, opp, visits):
+        """One update toward the search's visit distributions on a gathered batch (SLPolicy.visits_grads, or
+        visits_loss through float32 autograd under _update's condition), then Adam and the broadcast as _update."""
+        if self._native(own):
+            loss = self.model1.visits_grads(own, opp, visits)
+            return self._apply_native(loss, own.device, "visit-count update", "a visit count is negative")
+        return self._apply_autograd(own, lambda pad: visits_loss(self.model1, own, opp, visits, pad_to=pad))
+
+    def step_from_tuples(self, tup, colour=None, target="move"):
+        """One update from the tuples of a PV-MCTS self-play round (BASELINE
         configs[4]: "self-play feeding train_rl.py REINFORCE update on gathered (s, pi, z)"):
         tup = engine.SelfPlayResult.tuples() of THIS rank's games -- own / opp (the searched
         position, own = the mover), move (the move played = argmax of pi), z (the game's result
@@ -303,7 +355,15 @@ class ReinforceTrainer(object):
         planes, y = the action, r = the result).  colour = 1 keeps the learner's plies only, as
         the reference records them (src/rl_self_play.py:134-138); None = both colours (in PV-MCTS
         self-play both sides are the learner).  The win rate / snapshot gating of step() belongs
-        to games against a pool opponent and is not touched.  Returns dict(loss, n_tuples)."""
+        to games against a pool opponent and is not touched.  Returns dict(loss, n_tuples).
+
+        target = "move" is that REINFORCE update; target = "visits" trains the policy toward the search's own visit
+        distribution instead: the rows' `pi` (the root's visit counts) are gathered with the other fields, in the same
+        canonical order, and ONE update runs on the cross-entropy of the model's output against pi / sum(pi), every
+        row weighing 1 (visits_loss_from_logits; z is not used).  The dict then also carries kl = loss - the mean
+        entropy of the targets: the cross-entropy cannot fall below that entropy, kl is what is left to learn."""
+        if target not in ("move", "visits"):
+            raise ValueError("step_from_tuples: target must be 'move' or 'visits', got %r" % (target,))
         keep = slice(None)
         if colour is not None:
             keep = tup["colour"] == colour
@@ -320,25 +380,39 @@ class ReinforceTrainer(object):
             if any(live[i][1] >= live[i + 1][0] for i in range(len(live) - 1)):
                 raise ValueError("step_from_tuples: the ranks' game id ranges overlap (%s): build every rank's "
                                  "BatchedMCTS with game_id_base = iago_amd.dist.shard_range(n_games)[0]" % live)
-        g = _canonical(idist.gather_tuples(dict(own=tup["own"][keep], opp=tup["opp"][keep],
-                                                action=tup["move"][keep], z=tup["z"][keep], key=key[keep])))
+        fields = dict(own=tup["own"][keep], opp=tup["opp"][keep], action=tup["move"][keep], z=tup["z"][keep],
+                      key=key[keep])
+        if target == "visits":
+            fields["pi"] = tup["pi"][keep]
+        g = _canonical(idist.gather_tuples(fields))
         if g["z"].numel() == 0:
             raise ValueError("step_from_tuples: no tuples")
-        loss = self._update(g["own"], g["opp"], g["action"], g["z"])
-        out = dict(loss=float(loss.item()), n_tuples=int(g["z"].numel()))
+        if target == "visits":
+            pi = g["pi"].to(torch.int32).contiguous()
+            loss = self._update_visits(g["own"], g["opp"], pi)
+            out = dict(loss=float(loss.item()), n_tuples=int(g["z"].numel()))
+            # the targets' mean entropy in float64 (after the update: off its path)
+            v = pi.to(torch.float64)
+            t = v / v.sum(dim=1, keepdim=True).clamp(min=1)
+            entropy = -(torch.where(t > 0, t * torch.log(t.clamp(min=1e-300)), torch.zeros_like(t))).sum() / pi.shape[0]
+            out["kl"] = out["loss"] - float(entropy.item())
+        else:
+            loss = self._update(g["own"], g["opp"], g["action"], g["z"])
+            out = dict(loss=float(loss.item()), n_tuples=int(g["z"].numel()))
         self.model1.check_saturation()
         self.log.append(out)
         return out
 
-    def step_from_self_play(self, self_play, n_sims, colour=None, explore_turns=None, **play_kw):
+    def step_from_self_play(self, self_play, n_sims, colour=None, explore_turns=None, target="move", **play_kw):
         """One MCTS-fed round: self_play (an engine.SelfPlayEngine of THIS rank's games, its BatchedMCTS built with
         game_id_base = idist.shard_range(n_games)[0]) plays its batch with n_sims playouts per move and the tuples go
         through step_from_tuples.  explore_turns (and any other keyword of SelfPlayEngine.play) is passed on: the
         first turns' moves drawn from the visit counts, keyed by the GLOBAL game id, so the ranks' shards explore as
-        one batch would.  Returns step_from_tuples' dict and the round's SelfPlayResult."""
+        one batch would.  target: step_from_tuples' ("move" or "visits").  Returns step_from_tuples' dict and the
+        round's SelfPlayResult."""
         self.model1.eval()
         res = self_play.play(n_sims, explore_turns=explore_turns, **play_kw)
-        return self.step_from_tuples(res.tuples(), colour=colour), res
+        return self.step_from_tuples(res.tuples(), colour=colour, target=target), res
 
     def step(self):
         """One set + one update; returns dict(rate, loss, saved)."""

@@ -1,6 +1,7 @@
 /*
  * iago_hip_training.h -- training the nets on the library's own kernels: the supervised update of the Value net
- * (train_value.py).  Same conventions as iago_hip.h; part of the library's ABI (iago_abi_version).
+ * (train_value.py), SLPolicy on the search's visit counts.  Same conventions as iago_hip.h; part of the library's ABI
+ * (iago_abi_version).
  */
 #ifndef IAGO_HIP_TRAINING_H
 #define IAGO_HIP_TRAINING_H
@@ -53,6 +54,46 @@ typedef struct iago_value_grad_args {
 /* bytes of the workspace of iago_value_mse_grad for n rows (-1 for n < 0) */
 IAGO_API int64_t iago_value_grad_workspace_bytes(int64_t n);
 IAGO_API int iago_value_mse_grad(const iago_value_grad_args *args, void *stream);
+
+/*
+ * iago_policy_visits_grad: SLPolicy trained on the search's own visit counts -- the cross-entropy of the model's
+ *   output against the distribution of the root's visits (engine.SelfPlayResult.tuples()["pi"]) -- on the kernels of
+ *   iago_policy_reinforce_grad (iago_hip.h): the same forward with every block's output kept, the same blocks 8..2,
+ *   reduction and block 1; only the head and the loss differ.  Per row b, with n[a] = visits[b][a], N = sum_a n[a]
+ *   (summed in integers) and w = weight[b]:
+ *     logit = conv9 . x8 + bias10[cell],  m = max logit,  s = sum exp(logit - m),  p = exp(logit - m) / s
+ *     t[a] = n[a] / N (float32),  row loss = w sum_{a: n[a] > 0} -t[a] ((logit[a] - m) - log s)
+ *     loss = sum_b row loss / n_mean,  dlogits[a] = (w / n_mean) (p[a] - t[a])
+ *   ONE softmax (the model's output), log p in its log-softmax form: a cell whose p underflowed keeps a finite log p.
+ *   A row with N == 0 contributes nothing to the loss or to any gradient.  No temperature, no masking to the legal
+ *   moves.  Deterministic (fixed summation orders), no host synchronisation.
+ *   own / opp [n]: the searched positions, own = the mover; visits [n][64] int32, >= 0; weight: optional [n] float32
+ *   (NULL = 1 for every row; rows added as padding carry 0 or all-zero visits); n_mean: the row count the mean divides
+ *   by.  Weights, gradients, loss, probs and workspace (iago_policy_grad_workspace_bytes(n) bytes, 256-byte aligned)
+ *   as in iago_policy_grad_args.  overflow: bit 0 as for iago_conv3x3_split (the forward left the f16 range); bit 1
+ *   is raised by a negative count (that row contributes nothing): that call's loss and gradients must not be used.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or required pointer, n <= 0, n_mean <= 0, or
+ *   a workspace too small or misaligned.
+ */
+typedef struct iago_policy_visits_grad_args {
+    const uint64_t *own, *opp;
+    const int32_t *visits;
+    const float *weight;
+    int64_t n, n_mean;
+    const float *w1, *b1;
+    const void *w_hi[7], *w_lo[7], *wt_hi[7], *wt_lo[7];
+    const float *bias[7];
+    const float *w9, *b10;
+    float *g_w1, *g_b1;
+    float *g_w[7], *g_b[7];
+    float *g_w9, *g_b10;
+    float *loss;
+    float *probs;
+    void *workspace;
+    int64_t workspace_bytes;
+    uint32_t *overflow;
+} iago_policy_visits_grad_args;
+IAGO_API int iago_policy_visits_grad(const iago_policy_visits_grad_args *args, void *stream);
 
 #ifdef __cplusplus
 }
