@@ -54,9 +54,10 @@ SERVING_SYMBOLS = [
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
-# (network.SLPolicy.visits_grads, train_rl.ReinforceTrainer.step_from_tuples(target="visits"))
+# (network.SLPolicy.visits_grads, train_rl.ReinforceTrainer.step_from_tuples(target="visits")), minibatches out of a
+# replay window of self-play rows in random board symmetries (ops.replay_sample, replay.ReplayWindow)
 TRAINING_SYMBOLS = [
-    "iago_value_grad_workspace_bytes", "iago_value_mse_grad", "iago_policy_visits_grad",
+    "iago_value_grad_workspace_bytes", "iago_value_mse_grad", "iago_policy_visits_grad", "iago_replay_sample",
 ]
 
 
@@ -130,6 +131,23 @@ class ValueGradArgs(C.Structure):
         ("loss", C.c_void_p), ("pred", C.c_void_p), ("h9", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
         ("overflow", C.c_void_p),
+    ]
+
+
+REPLAY_KEY = 0x52504C59   # a replay window's draws: Philox key = the window's seed with its high word XOR this ("RPLY")
+REPLAY_BAD_ROW = 1        # bit of iago_replay_sample's flags: a supplied slot or variant was out of range
+
+
+class ReplaySampleArgs(C.Structure):
+    """Mirror of iago_replay_sample_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("pi", C.c_void_p), ("move", C.c_void_p), ("z", C.c_void_p),
+        ("capacity", C.c_int64), ("count", C.c_int64), ("n", C.c_int64),
+        ("seed", C.c_uint64), ("step", C.c_uint32), ("reserved0", C.c_uint32),
+        ("slot_in", C.c_void_p), ("sym_in", C.c_void_p),
+        ("own_out", C.c_void_p), ("opp_out", C.c_void_p), ("pi_out", C.c_void_p), ("move_out", C.c_void_p),
+        ("z_out", C.c_void_p), ("result_out", C.c_void_p), ("slot_out", C.c_void_p), ("sym_out", C.c_void_p),
+        ("flags", C.c_void_p),
     ]
 
 
@@ -364,6 +382,7 @@ def lib():
     L.iago_value_grad_workspace_bytes.argtypes = [i64]
     L.iago_value_mse_grad.argtypes = [C.POINTER(ValueGradArgs), vp]
     L.iago_policy_visits_grad.argtypes = [C.POINTER(PolicyVisitsGradArgs), vp]
+    L.iago_replay_sample.argtypes = [C.POINTER(ReplaySampleArgs), vp]
     L.iago_split_nchw.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.iago_merge_nchw.argtypes = [vp, vp, vp, i64, i32, vp]
     L.iago_value_stem.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]

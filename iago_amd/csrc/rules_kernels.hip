@@ -1,6 +1,7 @@
 // rules_kernels.hip -- batched Othello rule kernels (gfx950) + their C ABI.
 // Entry points and the reference interfaces they replace: include/iago_hip.h.
 #include "abi_common.hpp"
+#include "board_sym_dev.hpp"
 #include "othello_dev.hpp"
 #include "sample_dev.hpp"
 
@@ -221,22 +222,6 @@ __global__ __launch_bounds__(BLOCK) void bias_relu_kernel(float4 *__restrict__ x
     x[i] = v;
 }
 
-
-// Board symmetries on a bitboard (bit a = row*8+col).
-__device__ __forceinline__ uint64_t bb_transpose(uint64_t x) // (y,x) -> (x,y)
-{
-    uint64_t t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;
-    x ^= t ^ (t << 7);
-    t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull;
-    x ^= t ^ (t << 14);
-    t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull;
-    x ^= t ^ (t << 28);
-    return x;
-}
-// np.rot90 (counter-clockwise): (y,x) -> (7-x, y) = transpose, then flip the rows
-__device__ __forceinline__ uint64_t bb_rot90(uint64_t x) { return __builtin_bswap64(bb_transpose(x)); }
-__device__ __forceinline__ int act_rot90(int a) { return a < 0 ? a : (7 - (a & 7)) * 8 + (a >> 3); }
-__device__ __forceinline__ int act_transpose(int a) { return a < 0 ? a : (a & 7) * 8 + (a >> 3); }
 
 __global__ __launch_bounds__(BLOCK) void augment8_kernel(
     const uint64_t *__restrict__ own, const uint64_t *__restrict__ opp,

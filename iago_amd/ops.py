@@ -144,6 +144,63 @@ def augment8(own, opp, action):
     return oo, po, ao
 
 
+def replay_sample(own, opp, pi, move, z, count, n=None, seed=0, step=0, slot=None, sym=None, flags=None):
+    """iago_replay_sample (include/iago_hip_training.h): n rows out of the window own / opp (capacity,) int64, pi
+    (capacity, 64) int32, move / z (capacity,) int8 whose slots 0 .. count-1 are filled, every row in one of the
+    board's eight symmetries (ops.augment8's variants) -- position, visit row and move together.  slot / sym None: row
+    j's slot and variant are drawn from Philox on (j, step) under seed ^ (REPLAY_KEY << 32), with replacement; slot
+    (n,) int32 and sym (n,) uint8: those are taken (n defaults to their length).  flags: optional int32 word, or-ed
+    into -- bit 0: a supplied slot or variant was out of range (that row is zeros, move -1).  Returns a dict own,
+    opp, pi, move, z, result (float32 z), slot, sym."""
+    capacity = own.numel()
+    for name, t in (("opp", opp), ("move", move), ("z", z)):
+        if t.numel() != capacity:
+            raise ValueError("replay_sample: %s has %d entries, own has %d" % (name, t.numel(), capacity))
+    if pi.dim() != 2 or tuple(pi.shape) != (capacity, 64):
+        raise ValueError("replay_sample: pi must be (%d, 64), got %s" % (capacity, tuple(pi.shape)))
+    if (slot is None) != (sym is None):
+        raise ValueError("replay_sample: slot and sym go together (both or neither)")
+    if slot is not None:
+        if n is None:
+            n = slot.numel()
+        if slot.numel() != n or sym.numel() != n:
+            raise ValueError("replay_sample: slot / sym have %d / %d entries for n = %d" % (slot.numel(), sym.numel(), n))
+    if n is None:
+        raise ValueError("replay_sample: n is needed where the kernel draws")
+    n = int(n)
+    dev = own.device
+    out = dict(own=torch.empty(n, dtype=torch.int64, device=dev), opp=torch.empty(n, dtype=torch.int64, device=dev),
+               pi=torch.empty((n, 64), dtype=torch.int32, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               z=torch.empty(n, dtype=torch.int8, device=dev), result=torch.empty(n, dtype=torch.float32, device=dev),
+               slot=torch.empty(n, dtype=torch.int32, device=dev), sym=torch.empty(n, dtype=torch.uint8, device=dev))
+    a = _lib.ReplaySampleArgs()
+    a.own, a.opp, a.pi = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), _dev(pi, torch.int32, "pi")
+    a.move, a.z = _dev(move, torch.int8, "move"), _dev(z, torch.int8, "z")
+    a.capacity, a.count, a.n = capacity, int(count), n
+    a.seed, a.step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF
+    if slot is not None:
+        a.slot_in, a.sym_in = _dev(slot, torch.int32, "slot"), _dev(sym, torch.uint8, "sym")
+    a.own_out, a.opp_out, a.pi_out = out["own"].data_ptr(), out["opp"].data_ptr(), out["pi"].data_ptr()
+    a.move_out, a.z_out, a.result_out = out["move"].data_ptr(), out["z"].data_ptr(), out["result"].data_ptr()
+    a.slot_out, a.sym_out = out["slot"].data_ptr(), out["sym"].data_ptr()
+    a.flags = _dev(flags, torch.int32, "flags") if flags is not None else None
+    check(_lib.lib().iago_replay_sample(C.byref(a), _stream()), "iago_replay_sample")
+    return out
+
+
+def augment8_visits(own, opp, action, pi):
+    """ops.augment8 with the rows' visit counts: (8, n) own, opp (int64) and action (int8) in augment8's layout, and
+    (8, n, 64) int32 visit rows -- pi[v, i, m_v(a)] = pi[i, a].  iago_replay_sample's given mode over the n rows as a
+    window: slot = i, sym = v."""
+    n = own.numel()
+    dev = own.device
+    slot = torch.arange(n, dtype=torch.int32, device=dev).repeat(8)
+    sym = torch.arange(8, dtype=torch.uint8, device=dev).repeat_interleave(n)
+    z = torch.zeros(n, dtype=torch.int8, device=dev)
+    r = replay_sample(own, opp, pi, action, z, n, slot=slot, sym=sym)
+    return r["own"].reshape(8, n), r["opp"].reshape(8, n), r["move"].reshape(8, n), r["pi"].reshape(8, n, 64)
+
+
 def bias_relu_(x, bias):
     """In place max(x + bias[c], 0) on a (n, C, 8, 8) float32 tensor: the epilogue
     of network.Block (network.py:9-13) as one pass."""

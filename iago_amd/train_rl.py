@@ -344,6 +344,43 @@ class ReinforceTrainer(object):
             return self._apply_native(loss, own.device, "visit-count update", "a visit count is negative")
         return self._apply_autograd(own, lambda pad: visits_loss(self.model1, own, opp, visits, pad_to=pad))
 
+    def _gather_rows(self, tup, colour, with_pi, who):
+        """The front half of an update from a round's tuples: the colour filter, the check that the ranks' game ids do
+        not overlap, the all-gather and the canonical (turn, game) order.  Returns the gathered columns own, opp,
+        action, z (and pi with with_pi): the same rows in the same order on every rank."""
+        keep = slice(None)
+        if colour is not None:
+            keep = tup["colour"] == colour
+        key = tup["turn"].to(torch.int64) * (1 << 32) + tup["game"].to(torch.int64)
+        if idist.world_size() > 1:
+            # the canonical order needs globally unique game ids: every rank must have built its
+            # engine with its own game_id_base (idist.shard_range); with the default 0 everywhere the
+            # ranks also play IDENTICAL games, whose duplicate rows would silently enter the update
+            gm = tup["game"].to(torch.int64)
+            span = torch.stack([gm.min(), gm.max()]) if gm.numel() else torch.tensor([1, 0], device=key.device)
+            spans = idist.gather_tuples(dict(lo=span[:1], hi=span[1:]))
+            lo, hi = spans["lo"].tolist(), spans["hi"].tolist()
+            live = sorted((a, b) for a, b in zip(lo, hi) if a <= b)
+            if any(live[i][1] >= live[i + 1][0] for i in range(len(live) - 1)):
+                raise ValueError("%s: the ranks' game id ranges overlap (%s): build every rank's "
+                                 "BatchedMCTS with game_id_base = iago_amd.dist.shard_range(n_games)[0]" % (who, live))
+        fields = dict(own=tup["own"][keep], opp=tup["opp"][keep], action=tup["move"][keep], z=tup["z"][keep],
+                      key=key[keep])
+        if with_pi:
+            fields["pi"] = tup["pi"][keep]
+        g = _canonical(idist.gather_tuples(fields))
+        if g["z"].numel() == 0:
+            raise ValueError("%s: no tuples" % who)
+        return g
+
+    @staticmethod
+    def _visits_kl(loss, pi):
+        """loss - the mean entropy of the rows' visit distributions, the entropy in float64."""
+        v = pi.to(torch.float64)
+        t = v / v.sum(dim=1, keepdim=True).clamp(min=1)
+        entropy = -(torch.where(t > 0, t * torch.log(t.clamp(min=1e-300)), torch.zeros_like(t))).sum() / pi.shape[0]
+        return loss - float(entropy.item())
+
     def step_from_tuples(self, tup, colour=None, target="move"):
         """One update from the tuples of a PV-MCTS self-play round (BASELINE
         configs[4]: "self-play feeding train_rl.py REINFORCE update on gathered (s, pi, z)"):
@@ -364,41 +401,42 @@ class ReinforceTrainer(object):
         entropy of the targets: the cross-entropy cannot fall below that entropy, kl is what is left to learn."""
         if target not in ("move", "visits"):
             raise ValueError("step_from_tuples: target must be 'move' or 'visits', got %r" % (target,))
-        keep = slice(None)
-        if colour is not None:
-            keep = tup["colour"] == colour
-        key = tup["turn"].to(torch.int64) * (1 << 32) + tup["game"].to(torch.int64)
-        if idist.world_size() > 1:
-            # the canonical order needs globally unique game ids: every rank must have built its
-            # engine with its own game_id_base (idist.shard_range); with the default 0 everywhere the
-            # ranks also play IDENTICAL games, whose duplicate rows would silently enter the update
-            gm = tup["game"].to(torch.int64)
-            span = torch.stack([gm.min(), gm.max()]) if gm.numel() else torch.tensor([1, 0], device=key.device)
-            spans = idist.gather_tuples(dict(lo=span[:1], hi=span[1:]))
-            lo, hi = spans["lo"].tolist(), spans["hi"].tolist()
-            live = sorted((a, b) for a, b in zip(lo, hi) if a <= b)
-            if any(live[i][1] >= live[i + 1][0] for i in range(len(live) - 1)):
-                raise ValueError("step_from_tuples: the ranks' game id ranges overlap (%s): build every rank's "
-                                 "BatchedMCTS with game_id_base = iago_amd.dist.shard_range(n_games)[0]" % live)
-        fields = dict(own=tup["own"][keep], opp=tup["opp"][keep], action=tup["move"][keep], z=tup["z"][keep],
-                      key=key[keep])
-        if target == "visits":
-            fields["pi"] = tup["pi"][keep]
-        g = _canonical(idist.gather_tuples(fields))
-        if g["z"].numel() == 0:
-            raise ValueError("step_from_tuples: no tuples")
+        g = self._gather_rows(tup, colour, with_pi=target == "visits", who="step_from_tuples")
         if target == "visits":
             pi = g["pi"].to(torch.int32).contiguous()
             loss = self._update_visits(g["own"], g["opp"], pi)
             out = dict(loss=float(loss.item()), n_tuples=int(g["z"].numel()))
-            # the targets' mean entropy in float64 (after the update: off its path)
-            v = pi.to(torch.float64)
-            t = v / v.sum(dim=1, keepdim=True).clamp(min=1)
-            entropy = -(torch.where(t > 0, t * torch.log(t.clamp(min=1e-300)), torch.zeros_like(t))).sum() / pi.shape[0]
-            out["kl"] = out["loss"] - float(entropy.item())
+            out["kl"] = self._visits_kl(out["loss"], pi)   # (after the update: off its path)
         else:
             loss = self._update(g["own"], g["opp"], g["action"], g["z"])
             out = dict(loss=float(loss.item()), n_tuples=int(g["z"].numel()))
+        self.model1.check_saturation()
+        self.log.append(out)
+        return out
+
+    def add_to_window(self, window, tup, colour=None):
+        """The rows of a round's tuples into a replay.ReplayWindow: tup, colour, the all-gather and the canonical order
+        as step_from_tuples(target="visits") takes them, the gathered rows appended -- every rank's window then holds
+        the same rows in the same slots.  Returns the number of rows added."""
+        g = self._gather_rows(tup, colour, with_pi=True, who="add_to_window")
+        return window.add(dict(own=g["own"], opp=g["opp"], pi=g["pi"], move=g["action"], z=g["z"]))
+
+    def step_from_window(self, window, n_rows, target="visits", step=None):
+        """One update from n_rows rows drawn out of the window (ReplayWindow.sample: with replacement, each row in a
+        drawn board symmetry; step None = the window's own counter).  No gather: every rank's window holds the same
+        rows and the draw does not depend on the rank.  target as step_from_tuples.  Returns dict(loss, n_tuples,
+        step), with kl (on the sampled rows) for target = "visits"."""
+        if target not in ("move", "visits"):
+            raise ValueError("step_from_window: target must be 'move' or 'visits', got %r" % (target,))
+        used = window.step if step is None else step
+        rows = window.sample(n_rows, step=step)
+        if target == "visits":
+            loss = self._update_visits(rows["own"], rows["opp"], rows["pi"])
+            out = dict(loss=float(loss.item()), n_tuples=int(n_rows), step=int(used))
+            out["kl"] = self._visits_kl(out["loss"], rows["pi"])
+        else:
+            loss = self._update(rows["own"], rows["opp"], rows["move"], rows["z"])
+            out = dict(loss=float(loss.item()), n_tuples=int(n_rows), step=int(used))
         self.model1.check_saturation()
         self.log.append(out)
         return out

@@ -92,6 +92,24 @@ class SupervisedTrainer(object):
         self.opt.update()
         return loss_v
 
+    def _step(self, own, opp, labels):
+        """One minibatch update (the model in training mode): the loss as a Python float."""
+        if self.native:
+            return self._native_step(own, opp, labels)
+        for p in self.model.parameters():
+            p.grad = None
+        loss, _ = self.loss_fn(self.model, own, opp, labels)
+        loss.backward()
+        self.opt.update()
+        return float(loss.item())
+
+    def step_rows(self, own, opp, labels):
+        """One update on the given rows as ONE minibatch (rows sampled elsewhere: replay.ReplayWindow.sample's own, opp
+        and `result` for a Value net) -- a minibatch of epoch() without the permutation; a native Value step draws its
+        dropout mask from the trainer's generator as there.  Returns the loss."""
+        self.model.train()
+        return self._step(own, opp, labels)
+
     def epoch(self, own, opp, labels):
         """One shuffled sweep (train_policy.py:46-62); returns the mean minibatch loss."""
         n = own.numel()
@@ -100,16 +118,7 @@ class SupervisedTrainer(object):
         total, count = 0.0, 0
         for lo in range(0, n, MINIBATCH):
             idx = perm[lo:lo + MINIBATCH]
-            if self.native:
-                total += self._native_step(own[idx], opp[idx], labels[idx])
-                count += 1
-                continue
-            for p in self.model.parameters():
-                p.grad = None
-            loss, _ = self.loss_fn(self.model, own[idx], opp[idx], labels[idx])
-            loss.backward()
-            self.opt.update()
-            total += float(loss.item())
+            total += self._step(own[idx], opp[idx], labels[idx])
             count += 1
         return total / max(count, 1)
 

@@ -1,7 +1,7 @@
 /*
  * iago_hip_training.h -- training the nets on the library's own kernels: the supervised update of the Value net
- * (train_value.py), SLPolicy on the search's visit counts.  Same conventions as iago_hip.h; part of the library's ABI
- * (iago_abi_version).
+ * (train_value.py), SLPolicy on the search's visit counts, minibatches out of a replay window of self-play rows.  Same
+ * conventions as iago_hip.h; part of the library's ABI (iago_abi_version).
  */
 #ifndef IAGO_HIP_TRAINING_H
 #define IAGO_HIP_TRAINING_H
@@ -94,6 +94,47 @@ typedef struct iago_policy_visits_grad_args {
     uint32_t *overflow;
 } iago_policy_visits_grad_args;
 IAGO_API int iago_policy_visits_grad(const iago_policy_visits_grad_args *args, void *stream);
+
+/*
+ * iago_replay_sample: a minibatch out of a device-resident window of self-play rows, every row in one of the board's
+ *   eight symmetries -- position, visit row and move together.  The window (all [capacity], slots 0 .. count-1
+ *   filled): own / opp (own = the mover), pi [capacity][64] int32 (the root's visit counts by cell), move (int8, -1 =
+ *   none), z (int8, the result from the mover's view).  1 <= count <= capacity < 2^31; n: the rows to produce.
+ *   The draw of output row j (slot_in and sym_in both NULL), in integers, with replacement:
+ *     c = Philox4x32-10 on the counter (uint32(j), step, 0, 0), key = seed with its high word XOR 0x52504C59 ("RPLY":
+ *     key words seed & 0xFFFFFFFF and (seed >> 32) ^ 0x52504C59, as the explore draw of iago_mcts_search_explore
+ *     splits its seed),  slot = (uint64(c[0]) * count) >> 32,  sym = c[1] & 7
+ *   With slot_in (int32 [n]) and sym_in (uint8 [n]) both set the kernel takes them instead: the plain gather and
+ *   transform (the full augmentation is this mode with sym = 0 .. 7 per row).  Exactly one of them: IAGO_ERR_INVALID.
+ *   Variant k is iago_augment8's variant k (iago_hip.h): 0 the identity, 1 .. 3 successive counter-clockwise quarter
+ *   turns (cell (y,x) -> (7-x, y)), 4 the transpose of variant 3, 5 .. 7 three more turns.  With m_k its cell map:
+ *     own_out / opp_out have bit m_k(a) set where the source has bit a set,  pi_out[j][m_k(a)] = pi[slot][a],
+ *     move_out = m_k(move) (-1 stays -1),  z_out = z,  result_out = float32(z) (optional: what iago_value_mse_grad
+ *     takes),  slot_out / sym_out (optional): the row's slot and variant.
+ *   A supplied slot outside [0, count) or sym > 7 is checked on the device: nothing is read for that row, it is
+ *   written as zeros with move_out = -1 (slot_out / sym_out repeat what was supplied) and bit 0 of *flags (optional,
+ *   one word, or-ed into: the caller clears it) is raised.  No floats in the draw, plain stores, no workspace.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or required pointer, n <= 0, count <= 0,
+ *   count > capacity, capacity >= 2^31, or only one of slot_in / sym_in.
+ */
+typedef struct iago_replay_sample_args {
+    const uint64_t *own, *opp;
+    const int32_t *pi;
+    const int8_t *move, *z;
+    int64_t capacity, count, n;
+    uint64_t seed;
+    uint32_t step, reserved0;
+    const int32_t *slot_in;
+    const uint8_t *sym_in;
+    uint64_t *own_out, *opp_out;
+    int32_t *pi_out;
+    int8_t *move_out, *z_out;
+    float *result_out;
+    int32_t *slot_out;
+    uint8_t *sym_out;
+    uint32_t *flags;
+} iago_replay_sample_args;
+IAGO_API int iago_replay_sample(const iago_replay_sample_args *args, void *stream);
 
 #ifdef __cplusplus
 }

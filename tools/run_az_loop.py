@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""The PV-MCTS training loop on a replay window: per round one exploring self-play (`games` lockstep games played to
+the end, `sims` playouts per move, explore_turns = 8, the learner as the search's policy net, the Value net it
+trains as the search's value net, shipped RolloutPolicy) -> ReinforceTrainer.add_to_window (a window of
+`window_rounds` rounds' rows) -> `updates_per_round` times one ReplayWindow.sample of `rows` rows (with replacement,
+every row in a drawn board symmetry), each feeding BOTH the visit-count update of SLPolicy (_update_visits) and one
+native minibatch of the Value net on the rows' results (SupervisedTrainer.step_rows).  One JSON line.
+    python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]"""
+import json, os, sys, time
+import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from iago_amd import engine, network, ops  # noqa: E402
+from iago_amd.replay import ReplayWindow  # noqa: E402
+from iago_amd.train_rl import ReinforceTrainer  # noqa: E402
+from iago_amd.train_supervised import SupervisedTrainer  # noqa: E402
+
+arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
+iters, games, sims, window_rounds, updates, rows = arg(1, 100), arg(2, 64), arg(3, 20), arg(4, 8), arg(5, 4), arg(6, 1024)
+w, b = bench.shipped_rollout_weights()
+torch.manual_seed(0)
+tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
+vt = SupervisedTrainer(network.Value(), "value", seed=0, native=True)
+m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
+                       capacity=engine.suggest_capacity(sims, 15), seed=1)   # default engine: the persistent search
+sp = engine.SelfPlayEngine(m)
+window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
+kls, vlosses = [], []
+
+
+def one():
+    tr.model1.eval()
+    vt.model.eval()
+    res = sp.play(sims, explore_turns=8)
+    added = tr.add_to_window(window, res.tuples())
+    for _ in range(updates):
+        s = window.sample(rows)
+        loss = float(tr._update_visits(s["own"], s["opp"], s["pi"]).item())
+        kls.append(tr._visits_kl(loss, s["pi"]))
+        vlosses.append(vt.step_rows(s["own"], s["opp"], s["result"]))
+    return added
+
+
+for _ in range(2):
+    one()
+torch.cuda.synchronize()
+first = len(kls)
+t0 = time.perf_counter()
+added = 0
+for i in range(iters):
+    added += one()
+    if (i + 1) % 25 == 0:
+        print("round %d, %.1f s" % (i + 1, time.perf_counter() - t0), file=sys.stderr, flush=True)
+torch.cuda.synchronize()
+dt = time.perf_counter() - t0
+print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d playouts per move, explore_turns 8) -> "
+                            "replay window of %d rows -> %d x (sample %d rows in random symmetries -> SLPolicy on the "
+                            "visit counts + Value on the results, native), 1 x MI355X"
+                            % (games, sims, window.capacity, updates, rows),
+                  "rounds": iters, "seconds": dt, "rounds_per_sec": iters / dt,
+                  "rows_added": added, "rows_added_per_sec": added / dt,
+                  "rows_trained": iters * updates * rows, "rows_trained_per_sec": iters * updates * rows / dt,
+                  "window_count": window.count, "window_total": window.total,
+                  "kl_first": kls[first], "kl_last": kls[-1],
+                  "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
+                  "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t)}))
