@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("IAGO_HIP_LIB") or os.path.join(HERE, "libiago_hip.so")
 
 IAGO_OK = 0
+IAGO_ERR_INVALID, IAGO_ERR_HIP, IAGO_ERR_CAPACITY = -1, -2, -3
 IAGO_MAX_TURNS = 128
 IAGO_ROLLOUT_TABLE_FLOATS = 3 * 2 * 256 * 8 + 64 + 4 + 2 * 512
 ROLLOUT_MODE_INDEX = 3 * 2 * 256 * 8 + 64  # blob[mode] == 1.0: product form
@@ -50,7 +51,7 @@ EXPERIMENTAL_SYMBOLS = [
 # the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
-    "iago_mcts_search_explore", "iago_mcts_draw_move",
+    "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -428,6 +429,7 @@ def lib():
     L.iago_mcts_search_park.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchParkArgs), vp]
     L.iago_mcts_search_explore.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchExploreArgs), vp]
     L.iago_mcts_draw_move.argtypes = [tp, vp, C.c_uint64, vp, vp, vp, vp, vp]
+    L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)

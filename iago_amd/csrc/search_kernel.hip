@@ -319,6 +319,7 @@ __device__ __forceinline__ bool wg_handoff_or(bool x)
 // a thread of a game workgroup: its game (a wave search: its slot and tree), its place in the group of 8, its path
 struct Slot {
     int tid, gl;          // the thread, its game's number within the workgroup
+    int wg;               // the workgroup's number among its search's game workgroups (blockIdx.x unless an arena launch)
     uint32_t r;           // lane within the game's 8
     Lane8 L;
     bool mine, exists;    // a lane of one of the workgroup's games (a wave search: every thread); that game exists
@@ -379,15 +380,16 @@ template <> struct GameShared<true> : GameLds {
 };
 
 template <bool WAVE>
-__device__ __forceinline__ Slot make_slot(const SearchParams &S)
+__device__ __forceinline__ Slot make_slot(const SearchParams &S, const int wg)
 {
     Slot I;
+    I.wg = wg;
     I.tid = threadIdx.x;
     I.gl = I.tid >> 3;
     I.L = make_lane8(threadIdx.x);
     I.r = I.L.l8;
     I.mine = I.tid < 8 * S.games_per_wg; // (WAVE: 32 slots, every thread)
-    I.g = (int64_t)blockIdx.x * S.games_per_wg + I.gl;
+    I.g = (int64_t)wg * S.games_per_wg + I.gl;
     I.W = WAVE ? S.wave : 1;
     I.n_slots = WAVE ? S.n_slots : S.T.n_games;
     I.exists = I.mine && I.g < I.n_slots;
@@ -955,7 +957,7 @@ __device__ __forceinline__ bool rollout_passes(const SearchParams &S, const iago
     if (I.tid == 0)
         sh.wg_count[2 + (n_roll == 0 ? 0 : n_roll <= 16 ? 1 : n_roll <= 20 ? 2 : 3)]++; // (diagnostic: totals[10], [13..15])
     const iago_row::RowHandoff hand = {sh.h_own, sh.h_opp, sh.h_stream, sh.h_game, sh.h_z,
-                                       (int32_t)((int64_t)blockIdx.x * S.games_per_wg)};
+                                       (int32_t)((int64_t)I.wg * S.games_per_wg)};
 #pragma unroll 1
     for (int at = 0; at < n_now; at += 16) {
         iago_row::rollout_row_body<false, true, true>(R, 0u, sh.roll_list + at, table_ready, &hand);
@@ -1015,7 +1017,7 @@ __device__ __forceinline__ bool iteration_end(const SearchParams &S, const Slot 
                                               const CtlWords &c, const long long t0, int &contrib, bool &in_play)
 {
     const Tree &T = S.T;
-    if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] < S.trace_rows - T.n_games) {
+    if (S.trace && I.wg == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] < S.trace_rows - T.n_games) {
         const int64_t iters = (int64_t)sh.wg_count[0];
         S.trace[4 * iters + 0] = wall_clock64() - t0;
         S.trace[4 * iters + 1] = __hip_atomic_load(&S.ctl[ctl_tail(0)], RLX_AGENT) + __hip_atomic_load(&S.ctl[ctl_tail(1)], RLX_AGENT);
@@ -1074,7 +1076,7 @@ __device__ __forceinline__ bool iteration_end(const SearchParams &S, const Slot 
 __device__ __forceinline__ bool stream_claim(const SearchParams &S, const Slot &I, GameLds &sh, Game &G, bool &in_play)
 {
     const Tree &T = S.T;
-    const int n_here = (int)min((int64_t)S.games_per_wg, I.n_slots - (int64_t)blockIdx.x * S.games_per_wg); // its slots
+    const int n_here = (int)min((int64_t)S.games_per_wg, I.n_slots - (int64_t)I.wg * S.games_per_wg); // its slots
     if (I.tid == 0)
         sh.claimed = __hip_atomic_fetch_add(&S.ctl[CTL_NEXT_GAME], (uint32_t)n_here, RLX_AGENT);
     __syncthreads();
@@ -1132,10 +1134,10 @@ __device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, G
 }
 
 template <bool WAVE, bool PARK = false>
-__device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0)
+__device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0, const int wg)
 {
     __shared__ GameShared<WAVE> sh;
-    const Slot I = make_slot<WAVE>(S);
+    const Slot I = make_slot<WAVE>(S, wg);
     // (a stream: slot g starts game g while there is one -- `active` is not read)
     const bool first = I.exists && I.gt < S.games_total && (S.stream || S.active[I.gt] != 0);
     Game G;
@@ -1258,12 +1260,12 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
 // share the weight stream, which bounds the one-board walk: 46 instead of 70 us of CU time per board; the same
 // products in the same order per board: bit-identical values).
 __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_trunk::TrunkRParams &VP,
-                                              const iago_policy::PolicyParams &PP, const long long t0)
+                                              const iago_policy::PolicyParams &PP, const long long t0, const int wg)
 {
     __shared__ __align__(16) uint32_t job[32]; // up to two entries of 6 words (kind | game, reply tag, own lo / hi, opp lo / hi); [28..]: status, count
     const int tid = threadIdx.x;
-    const int64_t row0 = 4 * (int64_t)blockIdx.x; // this workgroup's rows of wg_own / wg_opp / out / probs (two in use)
-    const uint32_t home = ((int)(blockIdx.x & 7u) >= 8 - S.policy_xcds) ? KIND_POLICY : KIND_VALUE;
+    const int64_t row0 = 4 * (int64_t)wg; // this workgroup's rows of wg_own / wg_opp / out / probs (two in use)
+    const uint32_t home = ((int)((uint32_t)wg & 7u) >= 8 - S.policy_xcds) ? KIND_POLICY : KIND_VALUE;
     // Tickets are handed out by fetch-and-add whenever the ring shows an entry waiting: several workgroups that saw the
     // same entry all take one, and the later ones wait in fetch() for the ring's next entries.  (Measured and dropped,
     // round 5: head moved by compare-and-swap bounded by the tail, so that nobody is committed to an entry that does not
@@ -1473,11 +1475,12 @@ __device__ __forceinline__ void search_body(const SearchParams &S, const iago_ro
                                             const iago_policy::PolicyParams &PP)
 {
     const long long t0 = wall_clock64();
-    if (blockIdx.x == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
+    const int wg = (int)blockIdx.x;
+    if (wg == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
-    if ((int)blockIdx.x < S.n_game_wgs)
-        game_workgroup<WAVE, PARK>(S, R, t0);
-    net_workgroup(S, VP, PP, t0);
+    if (wg < S.n_game_wgs)
+        game_workgroup<WAVE, PARK>(S, R, t0, wg);
+    net_workgroup(S, VP, PP, t0, wg);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_kernel(
@@ -1505,7 +1508,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_kernel(SearchParams S,
                                                                                                    iago_row::HwParams R)
 {
-    game_workgroup<false>(S, R, wall_clock64());
+    game_workgroup<false>(S, R, wall_clock64(), (int)blockIdx.x);
 }
 
 // The whole-game search that hands its games over at park_empties (iago_mcts_search_park): the single launch and the game
@@ -1519,7 +1522,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_park_kernel(SearchParams S,
                                                                                                         iago_row::HwParams R)
 {
-    game_workgroup<false, true>(S, R, wall_clock64());
+    game_workgroup<false, true>(S, R, wall_clock64(), (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_net_kernel(
@@ -1528,7 +1531,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const long long t0 = wall_clock64();
     if (blockIdx.x == 0 && threadIdx.x == 0)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x, RLX_AGENT);
-    net_workgroup(S, VP, PP, t0);
+    net_workgroup(S, VP, PP, t0, (int)blockIdx.x);
+}
+
+// The ARENA (iago_mcts_search_arena): TWO searches of the kind above in one grid, each with its own nets, trees, rings
+// and constants -- they share the grid and the clock, nothing else.  Agent A's game workgroups come first, then B's
+// (all of them dispatched first, as in the single search), then the net workgroups.  A workgroup has a HOME agent:
+// a game workgroup its own; a net workgroup the parity of its block index -- workgroup i runs on XCD i mod 8, so the
+// even XCDs serve A and the odd ones B, and with the home rings of `policy_xcds` = 2 (XCD 6 / 7: the policy ring) an
+// XCD's L2 still holds ONE weight set.  Whoever has nothing left to do for its home agent -- every game workgroup of
+// that agent has finished, or it gave up -- serves the other agent's rings to that search's end (net_workgroup's
+// prologue restages the other nets' LDS weights).  No net workgroup waits for another, and with two net workgroups
+// resident (consecutive block indices: one of each parity) both agents have a server while their games run.
+// Both parameter sets are kernel arguments; a workgroup picks its set by a uniform choice on its block index and reads
+// it with scalar loads, so there is ONE body of game and net code in the kernel, not two.
+struct ArenaSet {
+    SearchParams S;
+    iago_row::HwParams R;
+    iago_trunk::TrunkRParams VP;
+    iago_policy::PolicyParams PP;
+};
+struct ArenaArgs {
+    ArenaSet set[2]; // agent A, agent B
+};
+static_assert(sizeof(ArenaArgs) <= 4096, "the arena's two parameter sets must fit the kernel argument segment");
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_arena_kernel(ArenaArgs P)
+{
+    const long long t0 = wall_clock64();
+    const int b = (int)blockIdx.x;
+    const int ga = P.set[0].S.n_game_wgs, games = ga + P.set[1].S.n_game_wgs;
+    if (b == 0 && threadIdx.x == 0) {
+        __hip_atomic_store(&P.set[0].S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)games, RLX_AGENT);
+        __hip_atomic_store(&P.set[1].S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)games, RLX_AGENT);
+    }
+    const int home = b < games ? (b >= ga ? 1 : 0) : (b & 1);
+    if (b < games) {
+        const ArenaSet &X = P.set[home];
+        game_workgroup<false>(X.S, X.R, t0, home ? b - ga : b);
+    }
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {
+        const ArenaSet &X = P.set[home ^ pass];
+        net_workgroup(X.S, X.VP, X.PP, t0, b); // (rows of wg_own / wg_opp by the block index: one owner per row in both agents' arrays)
+    }
 }
 
 } // namespace
@@ -1818,30 +1864,46 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     return S;
 }
 
+// the nets' and the rollouts' parameters of a launch
+int net_params(const iago_mcts_search_args *a, iago_trunk::TrunkRParams &VP, iago_policy::PolicyParams &PP, iago_row::HwParams &R)
+{
+    if (const int rc = iago_trunk::value_params_of(a->value, VP))
+        return rc;
+    VP.count_lo = 0;
+    VP.count_hi = 0x7fffffff;
+    if (const int rc = iago_policy::policy_params_of(a->policy, PP))
+        return rc;
+    R = iago_row::hw_params_of(a->rollout);
+    R.own = a->cur_own;
+    R.opp = a->cur_opp;
+    R.mask = a->roll;
+    R.stream_ids = a->done;
+    return IAGO_OK;
+}
+
+// every polled word starts from zero: the control block, the request ring and the reply mailboxes
+int zero_polled(const iago_mcts_search_args *a, int64_t n_slots, void *stream)
+{
+    if (hipMemsetAsync(a->ctl, 0, 64, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(a->q_slots, 0, (size_t)2 * QCAP * 64, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(a->rep_v, 0, (size_t)n_slots * 8, (hipStream_t)stream) != hipSuccess ||
+        hipMemsetAsync(a->rep_p, 0, (size_t)n_slots * 512, (hipStream_t)stream) != hipSuccess)
+        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_persistent: hipMemsetAsync failed");
+    return IAGO_OK;
+}
+
 // the zeroing of the polled words and the launch: one kernel, or the role split's two on their masked streams
 int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp, const iago_search_wave_args *wv,
                   bool park, const SearchGrid &G, const SearchParams &S)
 {
     iago_trunk::TrunkRParams VP;
-    if (const int rc = iago_trunk::value_params_of(a->value, VP))
-        return rc;
-    VP.count_lo = 0;
-    VP.count_hi = 0x7fffffff;
     iago_policy::PolicyParams PP;
-    if (const int rc = iago_policy::policy_params_of(a->policy, PP))
+    iago_row::HwParams R;
+    if (const int rc = net_params(a, VP, PP, R))
         return rc;
-    iago_row::HwParams R = iago_row::hw_params_of(a->rollout);
-    R.own = a->cur_own;
-    R.opp = a->cur_opp;
-    R.mask = a->roll;
-    R.stream_ids = a->done;
     constexpr int lds = search_lds(); // (reserved for the kernel by iago_mcts_search_capacity)
-    // every polled word starts from zero: the control block, the request ring and the reply mailboxes
-    if (hipMemsetAsync(a->ctl, 0, 64, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->q_slots, 0, (size_t)2 * QCAP * 64, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_v, 0, (size_t)G.n_slots * 8, (hipStream_t)stream) != hipSuccess ||
-        hipMemsetAsync(a->rep_p, 0, (size_t)G.n_slots * 512, (hipStream_t)stream) != hipSuccess)
-        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_persistent: hipMemsetAsync failed");
+    if (const int rc = zero_polled(a, G.n_slots, stream))
+        return rc;
     if (wv) {
         static std::atomic<uint64_t> configured_wave{0};
         if (iago_reserve_lds((const void *)search_wave_kernel, lds, configured_wave,
@@ -1999,6 +2061,116 @@ extern "C" int iago_mcts_search_explore(const iago_mcts_search_args *a, const ia
                                       "a match's moves are not drawn from the visit counts"))
         return rc;
     return search_launch(a, stream, ex->streams, nullptr, ex->park, ex->explore_turns);
+}
+
+namespace {
+// the arena's sets share nothing a search writes: two pointers that are the same array
+bool arena_shared(const iago_mcts_search_args *a, const iago_mcts_search_args *b)
+{
+    const void *pa[] = {a->ctl, a->q_slots, a->rep_v, a->rep_p, a->tree, a->tree->nodes, a->tree->n_nodes, a->tree->root,
+                        a->tree->overflow, a->cur_node, a->cur_own, a->cur_opp, a->path, a->done, a->roll, a->leaf_value,
+                        a->rollout->z, a->wg_own, a->wg_opp};
+    const void *pb[] = {b->ctl, b->q_slots, b->rep_v, b->rep_p, b->tree, b->tree->nodes, b->tree->n_nodes, b->tree->root,
+                        b->tree->overflow, b->cur_node, b->cur_own, b->cur_opp, b->path, b->done, b->roll, b->leaf_value,
+                        b->rollout->z, b->wg_own, b->wg_opp};
+    for (size_t i = 0; i < sizeof(pa) / sizeof(pa[0]); i++)
+        if (pa[i] == pb[i])
+            return true;
+    // (a position table holds ONE value net's values)
+    return a->vtable_slots > 0 && b->vtable_slots > 0 && a->vtable == b->vtable;
+}
+} // namespace
+
+extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago_mcts_search_args *b, void *stream)
+{
+    if (!a || !b)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: null args");
+    const iago_mcts_search_args *const set[2] = {a, b};
+    for (int i = 0; i < 2; i++) {
+        if (set[i]->max_turns != 0 || set[i]->games_total != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: one search per agent and launch (max_turns 0, "
+                                               "games_total 0): a game's two trees live in different workgroups");
+        if (const int rc = check_args(set[i], nullptr))
+            return rc;
+        const int m = has_match_codes(set[i]->active, set[i]->tree->n_games, (hipStream_t)stream);
+        if (m < 0)
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: cannot read `active`");
+        if (m)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: match codes in `active` (0 / 1 expected)");
+    }
+    if (arena_shared(a, b))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: the two argument sets share a tree, ctl, q_slots, reply "
+                                           "or state arrays, or a position table (each agent needs its own)");
+    const int want = a->net_workgroups > b->net_workgroups ? a->net_workgroups : b->net_workgroups;
+    if (want < 2)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: net_workgroups >= 2 expected (a server per agent)");
+    SearchGrid G[2];
+    int32_t cus = 0, per_cu = 0;
+    if (const int rc = iago_mcts_search_capacity(&cus, &per_cu))
+        return rc;
+    constexpr int lds = search_lds();
+    static std::atomic<uint64_t> configured_arena{0};
+    if (iago_reserve_lds((const void *)search_arena_kernel, lds, configured_arena,
+                         "iago_mcts_search_arena: cannot reserve the nets' LDS image"))
+        return IAGO_ERR_HIP;
+    // (the arena kernel's own workgroups per CU, asked of the runtime once per device)
+    static std::atomic<int32_t> per_known[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: hipGetDevice failed");
+    int per = per_known[dev & 63].load(std::memory_order_acquire);
+    if (per == 0) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)search_arena_kernel, 256, (size_t)lds) != hipSuccess)
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: the device does not answer");
+        if (per < 1)
+            return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: the arena kernel does not fit a CU of this device");
+        per_known[dev & 63].store(per, std::memory_order_release);
+    }
+    // the CUs the launch may count on: the smaller positive max_cus of the two sets, else the device's
+    int64_t use_cus = cus;
+    for (int i = 0; i < 2; i++)
+        if (set[i]->max_cus > 0 && set[i]->max_cus < use_cus)
+            use_cus = set[i]->max_cus;
+    const int64_t resident = use_cus * per;
+    int64_t games = 0;
+    for (int i = 0; i < 2; i++) {
+        G[i].gpw = set[i]->games_per_workgroup > 0 ? set[i]->games_per_workgroup : GAMES_PER_WG;
+        G[i].n_slots = set[i]->tree->n_games;
+        G[i].n_game_wgs = (G[i].n_slots + G[i].gpw - 1) / G[i].gpw;
+        G[i].path_lds_cap = SEARCH_IMG_TOP;
+        G[i].game_lds = 0;
+        games += G[i].n_game_wgs;
+    }
+    if (games + 2 > resident)
+        return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: both agents' game workgroups and two net workgroups do "
+                                            "not fit the device together (fewer games per launch, or one search after the other)");
+    const int64_t net_wgs = want < resident - games ? want : resident - games;
+    const int64_t grid = games + net_wgs;
+    ArenaArgs args;
+    ArenaSet *const P = args.set;
+    for (int i = 0; i < 2; i++) {
+        const iago_mcts_search_args *x = set[i];
+        G[i].net_wgs = net_wgs;
+        G[i].grid = grid;
+        if (x->value->n < 4 * grid || x->policy->n < 4 * grid || x->value->planes || x->value->index || x->value->n_dev ||
+            x->policy->index || x->policy->n_dev || !x->value->own || x->value->own != x->wg_own ||
+            x->value->opp != x->wg_opp || x->policy->own != x->wg_own || x->policy->opp != x->wg_opp)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: each agent's nets read their rows from its wg_own / "
+                                               "wg_opp (four rows per workgroup of the WHOLE grid: n >= 4 x (both agents' game "
+                                               "workgroups + net workgroups)), no gather list, no device count");
+        P[i].S = search_params(x, G[i], nullptr);
+        if (const int rc = net_params(x, P[i].VP, P[i].PP, P[i].R))
+            return rc;
+    }
+    // one clock for the launch: the larger limit; an agent that gives up says so in its own ctl and the other finishes
+    const long long limit = P[0].S.clock_limit > P[1].S.clock_limit ? P[0].S.clock_limit : P[1].S.clock_limit;
+    P[0].S.clock_limit = limit;
+    P[1].S.clock_limit = limit;
+    for (int i = 0; i < 2; i++)
+        if (const int rc = zero_polled(set[i], G[i].n_slots, stream))
+            return rc;
+    hipLaunchKernelGGL(search_arena_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, args);
+    return iago_check_launch("iago_mcts_search_arena");
 }
 
 extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)

@@ -1182,6 +1182,44 @@ class BatchedMCTS(object):
         opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games; park = dict(empties,
         parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park); explore_turns
         (an int > 0): those games' moves of the turns below it drawn from the visit counts (iago_mcts_search_explore)."""
+        a, keep = self._search_args(own, opp, active, n_sims, game)
+        ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
+        if ev is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        if self.wave_entry:
+            if game is not None:
+                raise ValueError("whole games in one launch are not available to the wave search (the turn loop is)")
+            w = _lib.SearchWaveArgs()
+            w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
+            self._wave_active = active
+            check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
+        elif park is not None or explore_turns:
+            k = None
+            if park is not None:
+                k = _lib.SearchParkArgs()
+                k.park_empties = int(park["empties"])
+                k.parked, k.stones, k.pass_flg = (park["parked"].data_ptr(), park["stones"].data_ptr(),
+                                                  park["pass_flg"].data_ptr())
+            # (the role split where today's launch takes it, else the single launch)
+            if explore_turns:
+                ops.search_explore(a, explore_turns, streams=self._split, park=k)
+            else:
+                k.streams = self._split
+                check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
+        elif self._split is not None:
+            check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
+        else:
+            check(_lib.lib().iago_mcts_search_persistent(C.byref(a), _stream()), "iago_mcts_search_persistent")
+        if ev is not None:
+            e1.record()
+            ev.append((e0, e1))
+        self._ps_keep = keep + (park,)   # alive until the next launch
+
+    def _search_args(self, own, opp, active, n_sims, game=None):
+        """The iago_mcts_search_args of a launch of the persistent search (own, opp, active, n_sims, game: as
+        _launch_persistent takes them) and what they point to: (args, keep) -- the caller holds `keep` until the launch
+        has run."""
         if self.rollout_hook is not None:
             raise ValueError("rollout_hook is not available in the persistent search (z_log_rows records the z)")
         ps = self._ps
@@ -1226,38 +1264,17 @@ class BatchedMCTS(object):
             a.vtable, a.vtable_slots = self._vtable.data_ptr(), self._vtable.numel() // 4
         if getattr(self, "trace", None) is not None:   # (diagnostic: tools/exp_persistent_trace.py)
             a.trace, a.trace_rows = self.trace.data_ptr(), self.trace.shape[0]
-        ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if self.wave_entry:
-            if game is not None:
-                raise ValueError("whole games in one launch are not available to the wave search (the turn loop is)")
-            w = _lib.SearchWaveArgs()
-            w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
-            self._wave_active = active
-            check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
-        elif park is not None or explore_turns:
-            k = None
-            if park is not None:
-                k = _lib.SearchParkArgs()
-                k.park_empties = int(park["empties"])
-                k.parked, k.stones, k.pass_flg = (park["parked"].data_ptr(), park["stones"].data_ptr(),
-                                                  park["pass_flg"].data_ptr())
-            # (the role split where today's launch takes it, else the single launch)
-            if explore_turns:
-                ops.search_explore(a, explore_turns, streams=self._split, park=k)
-            else:
-                k.streams = self._split
-                check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
-        elif self._split is not None:
-            check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
-        else:
-            check(_lib.lib().iago_mcts_search_persistent(C.byref(a), _stream()), "iago_mcts_search_persistent")
-        if ev is not None:
-            e1.record()
-            ev.append((e0, e1))
-        self._ps_keep = (keep_v, keep_p, ro, va, pa, own, opp, active, game, park)   # alive until the next launch
+        return a, (keep_v, keep_p, ro, va, pa, own, opp, active, game)
+
+    def reserve_net_rows(self, workgroups):
+        """Rows of wg_own / wg_opp (four per workgroup) for a launch of `workgroups` workgroups that may all walk this
+        engine's nets -- more than its own grid when the launch is an arena's (ops.search_arena)."""
+        ps, rows = self._ps, 4 * int(workgroups)
+        if ps["wg_own"].numel() < rows:
+            kw = dict(device=ps["wg_own"].device)
+            ps.update(wg_own=torch.zeros(rows, dtype=torch.int64, **kw), wg_opp=torch.zeros(rows, dtype=torch.int64, **kw),
+                      wg_v=torch.zeros(rows, dtype=torch.float32, **kw),
+                      wg_probs=torch.zeros((rows, 64), dtype=torch.float32, **kw))
 
     def _forget_stale_values(self):
         """The stored values belong to the weights that computed them: once the value net's parameters have changed,
@@ -1305,15 +1322,7 @@ class BatchedMCTS(object):
                 self._policy_key = key
             if self._la_stale_any:
                 self._refresh_priors(own, opp, active)
-        if used > self.tree.capacity // 2 and used > self._live_after_compaction * 5 // 4:
-            # a pool is half full: free the nodes that subtree reuse left behind (what the
-            # reference's garbage collector does after MCTS.py:149-152) before this search adds
-            # its own.  A pool that fills up all the same is reported below.  (Not again until
-            # the pool has grown by a quarter over what the last pass left: a live tree that
-            # itself fills half the pool would otherwise be re-laid before every search.)
-            self.tree.compact()
-            self.n_compactions += 1
-            self._live_after_compaction = int(self.tree.n_nodes.max().item())
+        self._compact_if_half_full(used)
         if self.persistent and self.rollout_hook is None:
             self._search_persistent(own, opp, active, n_sims, n_active)
         elif self.async_steps and self.rollout_hook is None:
@@ -1333,6 +1342,18 @@ class BatchedMCTS(object):
                 self.simulate(own, opp, active, n_active)
         if check:
             self.raise_errors(self.error_flags().tolist())
+
+    def _compact_if_half_full(self, used):
+        """Before a search: `used` = the nodes of the fullest pool."""
+        if used > self.tree.capacity // 2 and used > self._live_after_compaction * 5 // 4:
+            # a pool is half full: free the nodes that subtree reuse left behind (what the
+            # reference's garbage collector does after MCTS.py:149-152) before this search adds
+            # its own.  A pool that fills up all the same is reported below.  (Not again until
+            # the pool has grown by a quarter over what the last pass left: a live tree that
+            # itself fills half the pool would otherwise be re-laid before every search.)
+            self.tree.compact()
+            self.n_compactions += 1
+            self._live_after_compaction = int(self.tree.n_nodes.max().item())
 
     def error_flags(self):
         """Device tensor int64[5]: pools that overflowed, the look-ahead's error word, the saturation
@@ -1959,6 +1980,235 @@ class SelfPlayEngine(object):
                 cols["score"].append(torch.cat([r.score[:rows, :w], r.score.new_zeros((pad, w))]))
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))
+        return res
+
+
+class ArenaResult(SelfPlayResult):
+    """The games of ArenaEngine.play: PV-MCTS with agent A's nets against PV-MCTS with agent B's.  As a SelfPlayResult
+    (valid 1 where the mover searched, 0 for a pass or no turn; pi the MOVER's visit row), with agent: (T, B) uint8, whose
+    turn it was (0 = A, 1 = B: the colour rule, searched or not), and a_colour: (B,) int8, the colour A played in each
+    game."""
+
+    def score(self):
+        """A's results: dict(wins, draws, losses, n, win_rate), a draw counting 1/2 (MatchResult.score's arithmetic)."""
+        z = self.z.to(torch.int32) * torch.where(self.a_colour == 1, 1, -1).to(torch.int32)
+        wins, draws, losses = (int(v) for v in torch.stack([(z > 0).sum(), (z == 0).sum(), (z < 0).sum()]).tolist())
+        n = wins + draws + losses
+        return dict(wins=wins, draws=draws, losses=losses, n=n, win_rate=(wins + 0.5 * draws) / n if n else float("nan"))
+
+    def tuples(self, agent=None):
+        """SelfPlayResult.tuples() -- the searched rows, in the shape ReinforceTrainer.add_to_window takes -- of both
+        agents (None) or of the rows agent 0 (A) / 1 (B) searched only."""
+        if agent is None:
+            return SelfPlayResult.tuples(self)
+        if isinstance(agent, bool) or agent not in (0, 1):
+            raise ValueError("tuples: agent is None, 0 (A) or 1 (B), not %r" % (agent,))
+        full = self.valid
+        try:
+            self.valid = ((full == 1) & (self.agent == agent)).to(full.dtype)
+            return SelfPlayResult.tuples(self)
+        finally:
+            self.valid = full
+
+
+class ArenaEngine(object):
+    """Whole games between TWO PV-MCTS agents, each with its own nets and search constants: mcts_a and mcts_b, two
+    BatchedMCTS on the persistent search (wave == 1) with equal n_games and device and separate tree pools.  What
+    SelfPlayEngine.play_match cannot say -- whether this round's prior, value net and lmbda together beat last round's,
+    100 playouts against 400, lmbda 0.5 against 0 -- is ArenaResult.score().
+
+    The two engines should differ in `game_id_base` or `seed`: otherwise game g's rollouts draw the SAME Philox stream on
+    both sides (the streams are keyed by seed, game id and playout count, and both engines count their playouts alike).
+
+    The turn is self-play's (SelfPlayEngine._play_turns without colours: every mover with a legal move searches, no
+    forced final move); the one difference is who searches.  At turn t the mover of game g is A iff a_colour[g] ==
+    (1 if t % 2 == 0 else 2); A searches its movers from its tree, B its movers from its tree, the move is the mover's
+    best_move (below explore_turns: its draw_move, keyed by that engine's own seed and id), and BOTH trees advance by
+    every move.  One ops.play_turn and one host readback per turn.  Two forms, the same games record for record:
+    sequential (mcts_a.search, then mcts_b.search) and one launch per turn (iago_mcts_search_arena: both searches in one
+    grid); either way both engines' sim_counter advance by their n_sims every turn, whoever had movers.
+
+    Not here: whole arena games in one launch (a game's two trees live in different workgroups), the role split and more
+    games per agent than a single launch holds, solve_empties, streams, more than two agents, an Elo table."""
+
+    # play(one_launch=None): the form that measured faster at 1024 games x 100 playouts (LABNOTES.md, "Arena")
+    ONE_LAUNCH_DEFAULT = False
+
+    def __init__(self, mcts_a, mcts_b, max_turns=_lib.IAGO_MAX_TURNS):
+        for name, m in (("mcts_a", mcts_a), ("mcts_b", mcts_b)):
+            if not getattr(m, "persistent", False):
+                raise ValueError("%s must be a BatchedMCTS on the persistent search" % name)
+            if getattr(m, "wave", 1) != 1 or getattr(m, "wave_entry", False):
+                raise ValueError("%s must have wave == 1 (the arena searches one playout per tree at a time)" % name)
+        if mcts_b is mcts_a or mcts_b.tree is mcts_a.tree:
+            raise ValueError("mcts_b must have a tree pool of its own (two engines, two pools)")
+        if mcts_b.n_games != mcts_a.n_games:
+            raise ValueError("mcts_b must have mcts_a's n_games (%d, not %d)" % (mcts_a.n_games, mcts_b.n_games))
+        if mcts_b.cur_own.device != mcts_a.cur_own.device:
+            raise ValueError("mcts_b must be on mcts_a's device (%s, not %s)" % (mcts_a.cur_own.device, mcts_b.cur_own.device))
+        if isinstance(max_turns, bool) or not isinstance(max_turns, numbers.Integral) or not 1 <= max_turns <= _lib.IAGO_MAX_TURNS:
+            raise ValueError("max_turns must be an int in [1, %d], not %r" % (_lib.IAGO_MAX_TURNS, max_turns))
+        self.a, self.b = mcts_a, mcts_b
+        self.B = mcts_a.n_games
+        self.max_turns = int(max_turns)
+        self.device = mcts_a.cur_own.device
+        self.net_workgroups = None   # of the one launch (None: not sized yet; 0: it does not fit this device)
+        self.n_arena_launches = 0
+
+    def _colours(self, a_colour):
+        """play's a_colour as a (B,) int8 tensor of 1 / 2 (validated as play_match's mcts_colour is).  None: A plays
+        colour 1 in the games [0, B/2) and colour 2 in the rest -- blocks, not alternation, so that at every turn each
+        agent's movers fill whole game workgroups (a workgroup without a mover finishes at once and serves nets)."""
+        B, dev = self.B, self.device
+        if a_colour is None:
+            col = torch.full((B,), 2, dtype=torch.int8, device=dev)
+            col[:B // 2] = 1
+            return col
+        what = "play: a_colour is None, 1, 2 or a (%d,) integer tensor of 1 / 2" % B
+        if isinstance(a_colour, torch.Tensor):
+            if tuple(a_colour.shape) != (B,) or a_colour.is_floating_point() or a_colour.is_complex():
+                raise ValueError(what)
+            col = a_colour.to(device=dev, dtype=torch.int8)
+            if not bool(((col == 1) | (col == 2)).all()) or not torch.equal(col.to(a_colour.dtype).cpu(), a_colour.cpu()):
+                raise ValueError("play: a_colour holds values other than 1 and 2")
+            return col
+        if isinstance(a_colour, bool) or not isinstance(a_colour, numbers.Integral) or a_colour not in (1, 2):
+            raise ValueError(what)
+        return torch.full((B,), int(a_colour), dtype=torch.int8, device=dev)
+
+    @staticmethod
+    def _n_sims(n_sims):
+        """play's n_sims: an int >= 1 for both agents, or a pair (n_a, n_b) of them."""
+        pair = tuple(n_sims) if isinstance(n_sims, (tuple, list)) else (n_sims, n_sims)
+        if len(pair) != 2 or any(isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1 for n in pair):
+            raise ValueError("play: n_sims is an int >= 1 or a pair (n_a, n_b) of them, not %r" % (n_sims,))
+        return int(pair[0]), int(pair[1])
+
+    def _size_launch(self):
+        """The one launch's net workgroups (0: both agents' game workgroups and two net workgroups do not fit), and each
+        engine's rows of wg_own / wg_opp for them: any workgroup of the arena's grid may walk either agent's nets."""
+        a, b = self.a, self.b
+        resident = min(a.resident_workgroups, b.resident_workgroups)
+        games = sum(-(-m.n_games // m.games_per_workgroup) for m in (a, b))
+        net = min(max(a.net_workgroups, b.net_workgroups, 2), resident - games)
+        self.net_workgroups = net if net >= 2 else 0
+        if self.net_workgroups:
+            for m in (a, b):
+                m.reserve_net_rows(games + self.net_workgroups)
+
+    def _search_both(self, own, opp, s_a, s_b, n_a, n_b, counts, one_launch):
+        """The turn's searches: A's movers s_a from A's tree, B's movers s_b from B's.  counts: [A's games searched, the
+        nodes of A's fullest pool, B's, B's].  Returns the launches it took."""
+        a, b = self.a, self.b
+        c_a, c_b = [int(v) for v in counts[:2]], [int(v) for v in counts[2:4]]
+        if one_launch and self.net_workgroups is None:
+            self._size_launch()
+        # (a turn at which one agent has no mover is ONE launch anyway: today's)
+        if one_launch and self.net_workgroups and c_a[0] and c_b[0]:
+            for m, c in ((a, c_a), (b, c_b)):
+                m._forget_stale_values()
+                m._fresh_count.zero_()
+                m._compact_if_half_full(c[1])
+            args_a, keep_a = a._search_args(own, opp, s_a, n_a)
+            args_b, keep_b = b._search_args(own, opp, s_b, n_b)
+            args_a.net_workgroups = args_b.net_workgroups = self.net_workgroups
+            rc = ops.search_arena(args_a, args_b, check_result=False)
+            if rc == _lib.IAGO_OK:
+                a._ps_keep, b._ps_keep = keep_a + (None,), keep_b + (None,)   # alive until the next launch
+                for m, c, n in ((a, c_a, n_a), (b, c_b, n_b)):
+                    m.sim_counter = (m.sim_counter + n) & 0xFFFFFFFF
+                    m.n_leaf_evals += c[0] * n
+                self.n_arena_launches += 1
+                return 1
+            if rc != _lib.IAGO_ERR_CAPACITY:
+                check(rc, "iago_mcts_search_arena")
+            self.net_workgroups = 0   # (nothing was launched: the sequential form from here on)
+        a.search(own, opp, s_a, n_a, counts=c_a, check=False)   # (sim_counter: + n_sims whoever searched)
+        b.search(own, opp, s_b, n_b, counts=c_b, check=False)
+        return (1 if c_a[0] else 0) + (1 if c_b[0] else 0)
+
+    def play(self, n_sims, a_colour=None, record=True, explore_turns=None, one_launch=None):
+        """B games from the opening, both trees fresh.  n_sims: playouts per move, an int or a pair (n_a, n_b); a_colour:
+        the colour A plays, 1, 2 or a (B,) integer tensor of 1 / 2 (None: 1 in the first half of the games, 2 in the
+        rest); explore_turns: as SelfPlayEngine.play's, each mover drawing with its own engine's seed and id; one_launch:
+        True = one iago_mcts_search_arena launch per turn (the sequential form where the library answers
+        IAGO_ERR_CAPACITY), False = the sequential form, None = ONE_LAUNCH_DEFAULT.  Returns an ArenaResult."""
+        n_a, n_b = self._n_sims(n_sims)
+        col = self._colours(a_colour)
+        e = ops.explore_turns_arg(explore_turns) or 0
+        if one_launch is not None and not isinstance(one_launch, bool):
+            raise ValueError("play: one_launch is None, True or False, not %r" % (one_launch,))
+        one = self.ONE_LAUNCH_DEFAULT if one_launch is None else one_launch
+        a, b, B, T, dev = self.a, self.b, self.B, self.max_turns, self.device
+        a.tree.reset()
+        b.tree.reset()
+        own = torch.full((B,), START_OWN, dtype=torch.int64, device=dev)
+        opp = torch.full((B,), START_OPP, dtype=torch.int64, device=dev)
+        stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
+        pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        rec = None
+        if record:
+            rec = dict(own=torch.zeros((T, B), dtype=torch.int64, device=dev), opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
+                       pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev),
+                       valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
+                       move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
+                       agent=torch.zeros((T, B), dtype=torch.uint8, device=dev))
+        legal = ops.legal_moves(own, opp)
+        active = (legal != 0).to(torch.uint8)
+        legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
+
+        def movers(t, active):
+            a_turn = col == (1 if t % 2 == 0 else 2)
+            on = active.bool()
+            return a_turn, on & a_turn, on & ~a_turn
+
+        t, launches = 0, 0
+        a_turn, on_a, on_b = movers(t, active)
+        s_a, s_b = on_a.to(torch.uint8), on_b.to(torch.uint8)
+        counts = torch.cat([a.search_counts(s_a), b.search_counts(s_b)]).tolist()
+        while t < T:
+            # ONE readback per turn (below): both engines' flags, the check of the moves, the end-of-game test and the
+            # counts the next searches start from
+            launches += self._search_both(own, opp, s_a, s_b, n_a, n_b, counts, one)
+            mv_a, vis_a = a.draw_move(t, s_a) if t < e else a.best_move(s_a)
+            mv_b, vis_b = b.draw_move(t, s_b) if t < e else b.best_move(s_b)
+            none = torch.full_like(mv_a, -1)
+            mv = torch.where(on_a, mv_a, torch.where(on_b, mv_b, none))
+            if record:
+                rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t] = own, opp, s_a | s_b, mv
+                rec["pi"][t] = vis_a * s_a.reshape(B, 1).to(torch.int32) + vis_b * s_b.reshape(B, 1).to(torch.int32)
+                rec["agent"][t] = (~a_turn).to(torch.uint8)
+            live = done ^ 1   # game.py:84,108,140 (the games not yet done): both trees follow every move
+            a.update_with_move(mv, live)
+            b.update_with_move(mv, live)
+            ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
+            legal, legal_next = legal_next, legal
+            active, active_next = active_next, active
+            t += 1
+            a_turn, on_a, on_b = movers(t, active)
+            s_a, s_b = on_a.to(torch.uint8), on_b.to(torch.uint8)
+            back = torch.cat([a.error_flags(), b.error_flags(), (mv == -2).any().to(torch.int64).reshape(1),
+                              done.all().to(torch.int64).reshape(1), a.search_counts(s_a), b.search_counts(s_b)]).tolist()
+            a.raise_errors(back[:5])
+            b.raise_errors(back[5:10])
+            if back[10]:
+                # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
+                raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
+            if t % 2 == 0 and back[11]:
+                break
+            counts = back[12:16]
+        res = ArenaResult()
+        res.game_id_base = a.game_id_base
+        res.n_turns, res.launches, res.game_turns = t, launches, None
+        res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
+        p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)   # colour 1's stones are `own` after an even number of turns
+        res.z = ops.judge(p1, p2)
+        res.final_p1, res.final_p2 = p1, p2
+        res.a_colour = col
+        if record:
+            for name, v in rec.items():
+                setattr(res, name, v[:t])
         return res
 
 

@@ -1170,3 +1170,20 @@ def search_explore(args, explore_turns, streams=None, park=None):
     e.streams = streams
     e.park = C.addressof(park) if park is not None else None
     check(_lib.lib().iago_mcts_search_explore(C.byref(args), C.byref(e), _stream()), "iago_mcts_search_explore")
+
+
+def search_arena(args_a, args_b, check_result=True):
+    """iago_mcts_search_arena (include/iago_hip_serving.h): the searches of `args_a` and `args_b` (two
+    _lib.MctsSearchArgs, each a complete search of iago_mcts_search_persistent with its own nets, trees and rings) in
+    ONE launch.  Either may be None (the library refuses it, like everything else it documents).  Returns the library's
+    code; check_result (default): anything but IAGO_OK raises IagoError -- with the code in its `rc` -- instead.  The
+    caller keeps both sets and everything they point to alive until the launch has run."""
+    rc = _lib.lib().iago_mcts_search_arena(C.byref(args_a) if args_a is not None else None,
+                                           C.byref(args_b) if args_b is not None else None, _stream())
+    if check_result and rc != _lib.IAGO_OK:
+        try:
+            check(rc, "iago_mcts_search_arena")
+        except _lib.IagoError as err:
+            err.rc = rc
+            raise
+    return rc

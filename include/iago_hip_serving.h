@@ -192,6 +192,33 @@ IAGO_API int iago_mcts_search_explore(const iago_mcts_search_args *args, const i
 IAGO_API int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
                                  const int32_t *turn, int8_t *move, int32_t *visits, void *stream);
 
+/* ------------------------------------------------------------------ arena */
+
+/*
+ * TWO searches of iago_mcts_search_persistent in ONE launch, each with its own nets: agent A (`a`) and agent B (`b`) are
+ * complete argument sets of today's kind -- tree pool, roots and `active`, value / policy / rollout arguments, c_puct,
+ * lmbda, n_thr, n_sims, cur_*, path, done, roll, leaf_value, rings (q_slots, ctl, rep_v / rep_p), totals, wg_own /
+ * wg_opp, optional position table -- that share nothing but the grid and the clock.  Each agent's trees, moves, draws
+ * and totals[0..1] are those of iago_mcts_search_persistent(a) / (b) run alone, bit for bit.
+ *   - The grid: A's game workgroups, then B's, then the net workgroups -- the larger net_workgroups of the two sets
+ *     (>= 2), cut to what is resident beside the games (the smaller positive max_cus of the two counts).
+ *   - A net workgroup's HOME agent is the parity of its block index (even: A, odd: B; workgroup i runs on XCD i mod 8,
+ *     so an XCD's L2 holds one agent's weights), its home ring inside that agent as in the single search.  It serves its
+ *     home agent until that search is over -- every game workgroup of the agent has finished, or the agent gave up, or
+ *     the clock limit passed -- then the other agent's; a game workgroup whose games are done does the same, its own
+ *     agent first.
+ *   - Every workgroup of the grid may walk either agent's nets: EACH agent's value->n and policy->n is at least
+ *     4 x (both agents' game workgroups + the net workgroups) rows of its own wg_own / wg_opp.
+ *   - The clock limit is the larger time_limit_ms.  An agent that gives up says so in ITS ctl[3]; the other one finishes.
+ * Refused (IAGO_ERR_INVALID, nothing launched): a null set; whole games or a stream (max_turns > 0, games_total > 0:
+ * the two trees of an arena game live in different workgroups); match codes (2 / 3) in an `active` (read back on
+ * `stream` when device memory); two sets that share a tree, ctl, q_slots, reply or state arrays, wg_own / wg_opp or a
+ * position table; net_workgroups < 2 in both; whatever iago_mcts_search_persistent refuses in either set.
+ * IAGO_ERR_CAPACITY: both agents' game workgroups and two net workgroups do not fit the device together.  The wave
+ * search, the role split, the hand-over and the exploring draw are not available here.
+ */
+IAGO_API int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago_mcts_search_args *b, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,11 @@ trains as the search's value net, shipped RolloutPolicy) -> ReinforceTrainer.add
 `window_rounds` rounds' rows) -> `updates_per_round` times one ReplayWindow.sample of `rows` rows (with replacement,
 every row in a drawn board symmetry), each feeding BOTH the visit-count update of SLPolicy (_update_visits) and one
 native minibatch of the Value net on the rows' results (SupervisedTrainer.step_rows).  One JSON line.
-    python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]"""
-import json, os, sys, time
+arena_every = k > 0: every k rounds the current nets play `games` arena games (engine.ArenaEngine, `sims` playouts a side)
+against a frozen copy of the nets of k rounds ago, and the scores (the current nets' side) join the JSON line.
+    python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
+                                 [arena_every=0]"""
+import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +21,7 @@ from iago_amd.train_supervised import SupervisedTrainer  # noqa: E402
 
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 iters, games, sims, window_rounds, updates, rows = arg(1, 100), arg(2, 64), arg(3, 20), arg(4, 8), arg(5, 4), arg(6, 1024)
+arena_every = arg(7, 0)
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -27,6 +31,27 @@ m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_t
 sp = engine.SelfPlayEngine(m)
 window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
 kls, vlosses = [], []
+arena_scores = []
+if arena_every > 0:
+    # the nets of k rounds ago: a frozen module pair of its own, an engine and tree pool of its own (other seed and ids)
+    old_p, old_v = copy.deepcopy(tr.model1).eval(), copy.deepcopy(vt.model).eval()
+    m_now = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
+                               capacity=engine.suggest_capacity(sims, 15), seed=3)
+    m_old = engine.BatchedMCTS(games, old_p, old_v, ops.RolloutWeights(w, b), n_thr=15,
+                               capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games)
+    arena = engine.ArenaEngine(m_now, m_old)
+
+
+def gate(i):
+    """After round i + 1: the current nets against the frozen ones, then the frozen ones take the current weights."""
+    tr.model1.eval()
+    vt.model.eval()
+    s = arena.play(sims, record=False).score()
+    arena_scores.append(dict(round=i + 1, **s))
+    with torch.no_grad():
+        for old, new in ((old_p, tr.model1), (old_v, vt.model)):
+            for q, p in zip(old.parameters(), new.parameters()):
+                q.copy_(p)
 
 
 def one():
@@ -50,6 +75,8 @@ t0 = time.perf_counter()
 added = 0
 for i in range(iters):
     added += one()
+    if arena_every > 0 and (i + 1) % arena_every == 0:
+        gate(i)
     if (i + 1) % 25 == 0:
         print("round %d, %.1f s" % (i + 1, time.perf_counter() - t0), file=sys.stderr, flush=True)
 torch.cuda.synchronize()
@@ -64,4 +91,5 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "window_count": window.count, "window_total": window.total,
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
-                  "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t)}))
+                  "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t),
+                  **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {})}))
