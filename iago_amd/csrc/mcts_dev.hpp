@@ -235,13 +235,35 @@ __device__ __forceinline__ void backup_climb(const Tree &T, int64_t base, int no
 // high word XOR EXPLORE_KEY, r = (uint64(w) * N) >> 32, the move is the lowest cell a with sum_{b <= a} n[b] > r
 // (N == 0: the most visited child's first-maximum rule stays)
 constexpr uint32_t EXPLORE_KEY = 0x4558504Cu; // ("EXPL")
+constexpr uint32_t CAP_KEY = 0x43415050u;     // ("CAPP": the playout cap, below)
+
+// word turn & 3 of Philox4x32-10 on (id, turn >> 2, 0, 0) under (key0, key1)
+__device__ __forceinline__ uint32_t turn_word(uint32_t key0, uint32_t key1, uint32_t id, uint32_t turn)
+{
+    uint32_t c[4] = {id, turn >> 2, 0u, 0u};
+    philox4x32_10(c, key0, key1);
+    const uint32_t lo = (turn & 1u) ? c[1] : c[0], hi = (turn & 1u) ? c[3] : c[2]; // (selects: no indexed array)
+    return (turn & 2u) ? hi : lo;
+}
 
 __device__ __forceinline__ uint32_t explore_word(uint32_t key0, uint32_t key1, uint32_t id, uint32_t turn)
 {
-    uint32_t c[4] = {id, turn >> 2, 0u, 0u};
-    philox4x32_10(c, key0, key1 ^ EXPLORE_KEY);
-    const uint32_t lo = (turn & 1u) ? c[1] : c[0], hi = (turn & 1u) ? c[3] : c[2]; // (selects: no indexed array)
-    return (turn & 2u) ? hi : lo;
+    return turn_word(key0, key1 ^ EXPLORE_KEY, id, turn);
+}
+
+// ---- playout-cap randomisation ("Playout cap"): a searched turn is FULL (n_sims playouts, a policy
+// target) when the top byte of its word is below full_per_256, else FAST (the first n_fast playouts of the same search).
+// The word is explore_word's -- word turn & 3 of Philox4x32-10 on (game id, turn >> 2, 0, 0) -- under a key of its own:
+// the rollouts' key with its high word XOR CAP_KEY.  (The persistent search draws both words at ONE call site of turn_word,
+// the key chosen per lane: a second Philox body cost it a register)
+__device__ __forceinline__ uint32_t cap_word(uint32_t key0, uint32_t key1, uint32_t id, uint32_t turn)
+{
+    return turn_word(key0, key1 ^ CAP_KEY, id, turn);
+}
+
+__device__ __forceinline__ bool cap_fast_turn(uint32_t w, uint32_t full_per_256)
+{
+    return (w >> 24) >= full_per_256;
 }
 
 // the draw's threshold r in [0, total)

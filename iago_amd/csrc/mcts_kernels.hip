@@ -260,6 +260,18 @@ __global__ __launch_bounds__(BLOCK) void draw_move_kernel(Tree T, const uint8_t 
     move[g] = (int8_t)best;
 }
 
+// draw_move_kernel's sibling for the playout cap (iago_mcts_cap_mask): fast[i] = whether turn[i] of game game_id[i] is a
+// fast turn -- mcts_dev.hpp's rule, the word the one launch draws at that turn's boundary
+__global__ __launch_bounds__(BLOCK) void cap_mask_kernel(uint32_t key0, uint32_t key1, const int32_t *__restrict__ game_id,
+                                                         const int32_t *__restrict__ turn, uint32_t full_per_256, int64_t n,
+                                                         uint8_t *__restrict__ fast)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n)
+        return;
+    fast[i] = cap_fast_turn(cap_word(key0, key1, (uint32_t)game_id[i], (uint32_t)turn[i]), full_per_256) ? 1 : 0;
+}
+
 __global__ __launch_bounds__(BLOCK) void advance_root_kernel(Tree T, const uint8_t *__restrict__ mask,
                                                              const int8_t *__restrict__ move)
 {
@@ -1042,6 +1054,20 @@ int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint6
     hipLaunchKernelGGL(draw_move_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0, (hipStream_t)stream, *tree,
                        active, (uint32_t)seed, (uint32_t)(seed >> 32), game_id, turn, move, visits);
     return iago_check_launch("iago_mcts_draw_move");
+}
+
+int iago_mcts_cap_mask(uint64_t seed, const int32_t *game_id, const int32_t *turn, int32_t full_per_256, int64_t n,
+                       uint8_t *fast, void *stream)
+{
+    if (n < 0 || (n > 0 && (!game_id || !turn || !fast)))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_cap_mask: n >= 0, game_id, turn and fast expected");
+    if (full_per_256 < 1 || full_per_256 > 256)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_cap_mask: full_per_256 must be in [1, 256]");
+    if (n == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(cap_mask_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), game_id, turn, (uint32_t)full_per_256, n, fast);
+    return iago_check_launch("iago_mcts_cap_mask");
 }
 
 int iago_mcts_advance_root(const iago_mcts_tree *tree, const uint8_t *mask, const int8_t *move,

@@ -153,6 +153,9 @@ struct SearchParams {
     // exploring self-play (iago_mcts_search_explore; 0: off): the move of a searched turn below explore_turns is drawn in
     // proportion to the root's visit counts (mcts_dev.hpp, explore_draw8) instead of taken as the most visited one
     int32_t explore_turns;
+    // playout-cap randomisation (iago_mcts_search_cap; cap_fast 0: off): a searched turn whose Philox word says FAST
+    // (mcts_dev.hpp, cap_word: top byte >= cap_full_256) ends its search after cap_fast playouts and records valid 4
+    int32_t cap_fast, cap_full_256;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -360,6 +363,10 @@ struct GameLds {
     uint64_t h_own[GAMES_PER_WG], h_opp[GAMES_PER_WG];
     int32_t h_stream[GAMES_PER_WG];
     int32_t h_game[GAMES_PER_WG]; // the game each slot plays (the slot itself unless a stream), read at its end
+    // the playouts of each slot's current search (S.n_sims; a fast turn of the playout cap: S.cap_fast) and whether the
+    // turn is a fast one -- in LDS like the two above: the kernel has no register left for a per-game word
+    int32_t h_budget[GAMES_PER_WG];
+    uint8_t h_fast[GAMES_PER_WG];
     // (diagnostic counters of the workgroup, kept by thread 0 in LDS: as per-thread 64-bit registers they were 12 VGPRs
     // live across the whole loop -- what the game launch of the role split spilled to scratch memory)
     uint32_t wg_count[6]; // [0] iterations, [1] idle iterations, [2..5] iterations with 0 / 1..16 / 17..20 / more games rolled out
@@ -445,7 +452,7 @@ __device__ __forceinline__ void finish_playout(const SearchParams &S, const Slot
         atomicAdd((unsigned long long *)&S.totals[9], 1ull); // (diagnostic: playouts over time)
     if (I.r == 0u)
         S.done[I.g] = G.turn * S.n_sims + G.n_done;
-    G.state = G.n_done >= S.n_sims ? I.search_end : ST_READY;
+    G.state = G.n_done >= sh.h_budget[I.gl] ? I.search_end : ST_READY;
 }
 
 // ---- 1. replies (the games' lanes): the priors, a match's policy distribution, or the value the game waits for.  (The 8
@@ -509,7 +516,8 @@ __device__ __forceinline__ int most_visited(const Tree &T, const Slot &I, uint64
     return best_n >= 0 ? best_a : -2;
 }
 
-// the turn's record: the position before it, valid (1: searched, 2: played without a search, 0: no turn), the move
+// the turn's record: the position before it, valid (1: searched, 4: searched as a fast turn of the playout cap, 2: played
+// without a search, 0: no turn), the move
 __device__ __forceinline__ void record_turn(const SearchParams &S, const Slot &I, const GameLds &sh, const Game &G, int valid,
                                             int mv, const int (&row_n)[8])
 {
@@ -585,8 +593,10 @@ __device__ __forceinline__ void play_move(const SearchParams &S, const Slot &I, 
 // over instead -- the turn it stands at, its position (own = the mover) and its books, by game id -- and the game is done
 // S.explore_turns > 0 (iago_mcts_search_explore): the move of a searched turn below it is the draw from the visit counts
 // -- the row the turn records -- keyed by the game's id and its turn
+// S.cap_fast > 0 (iago_mcts_search_cap): a turn that searches draws its budget -- S.n_sims playouts, or the first
+// S.cap_fast of them (a fast turn: valid 4) -- keyed the same way; the stream stride, the move and the books are untouched
 template <bool PARK>
-__device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_row::HwParams &R, const Slot &I, const GameLds &sh,
+__device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_row::HwParams &R, const Slot &I, GameLds &sh,
                                               Game &G, const Cursor &C, bool &busy, const long long t0)
 {
     const Tree &T = S.T;
@@ -595,6 +605,19 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_
         if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
             break;
         busy = busy || at_move || at_turn || at_draw;
+        // the turn's Philox word, at ONE call site: explore_word at a turn's end (the draw, below), cap_word at a turn's
+        // start -- the budget of the search this turn runs if the mover searches it (a turn that passes or parks leaves a
+        // word nobody reads; the 8 lanes write the same word, before the legal set and the root are live)
+        const bool explores = S.explore_turns > 0 && at_move && G.turn < S.explore_turns;
+        const bool caps = S.cap_fast > 0 && at_turn;
+        uint32_t w = 0u;
+        if (__builtin_amdgcn_ballot_w64(explores || caps) != 0ull)
+            w = turn_word(R.key0, R.key1 ^ (caps ? CAP_KEY : EXPLORE_KEY), R.id_base + (uint32_t)sh.h_game[I.gl], (uint32_t)G.turn);
+        if (caps) {
+            const bool fast = cap_fast_turn(w, (uint32_t)S.cap_full_256);
+            sh.h_budget[I.gl] = fast ? S.cap_fast : S.n_sims;
+            sh.h_fast[I.gl] = fast ? 1 : 0;
+        }
         const uint64_t lg = group8_legal(to_lane(G.g_own, I.L), to_lane(G.g_opp, I.L), I.L);
         const bool can_move = lg != 0ull && !G.g_over;
         // a match (active 2: PV-MCTS plays colour 1, 3: colour 2; game.py:96-118): the final move when it is the only one
@@ -638,14 +661,10 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_
         const int rfc = moving ? T.nodes[I.base + root].first_child : -1;
         int row_n[8];
         int best = most_visited(T, I, lg, rfc, at_move, row_n);
-        if (S.explore_turns > 0) {
-            // (once per turn; every lane takes part in the group's sums.  No child visited, or none at all: `best` stays)
-            const bool explores = at_move && G.turn < S.explore_turns;
-            if (__builtin_amdgcn_ballot_w64(explores) != 0ull) {
-                const uint32_t w = explore_word(R.key0, R.key1, R.id_base + (uint32_t)sh.h_game[I.gl], (uint32_t)G.turn);
-                const int drawn_a = explore_draw8(row_n, I.r, w);
-                best = (explores && drawn_a < 64) ? drawn_a : best;
-            }
+        // (once per turn; every lane takes part in the group's sums.  No child visited, or none at all: `best` stays)
+        if (__builtin_amdgcn_ballot_w64(explores) != 0ull) {
+            const int drawn_a = explore_draw8(row_n, I.r, w);
+            best = (explores && drawn_a < 64) ? drawn_a : best;
         }
         if (moving) {
             int mv = -1;
@@ -659,7 +678,7 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_
             if (forced)
                 mv = (int)__builtin_ctzll(lg); // game.py:97-98
             if (S.rec_move)
-                record_turn(S, I, sh, G, at_move ? 1 : (drawn ? 2 : 0), mv, row_n);
+                record_turn(S, I, sh, G, at_move ? ((S.cap_fast > 0 && sh.h_fast[I.gl]) ? 4 : 1) : (drawn ? 2 : 0), mv, row_n);
             // for the games not over, and not after a forced final move (game.py:97-98)
             if (!G.g_over && !forced && I.r == 0u)
                 advance_root(T, I, lg, rfc, mv);
@@ -1159,8 +1178,11 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
         S.done[I.g] = 0;
         S.roll[I.g] = 0;
     }
-    if (I.mine)
+    if (I.mine) {
         sh.h_game[I.gl] = (int32_t)I.gt; // (the 8 lanes write the same word; each reads back its own store; a wave: the tree's id)
+        sh.h_budget[I.gl] = S.n_sims;    // (every search of the launch, unless a capped turn says otherwise)
+        sh.h_fast[I.gl] = 0;
+    }
     const bool whole_game = I.whole && I.exists && I.g < S.games_total;
     start_game(G, whole_game ? S.game_own[I.g] : 0ull, whole_game ? S.game_opp[I.g] : 0ull);
     if (whole_game && G.state == ST_DONE && I.r == 0u)
@@ -1861,6 +1883,8 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.park_stones = nullptr;
     S.park_pass = nullptr;
     S.explore_turns = 0;
+    S.cap_fast = 0;
+    S.cap_full_256 = 256;
     return S;
 }
 
@@ -1951,7 +1975,8 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
 }
 
 int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
-                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr, int explore_turns = 0)
+                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr, int explore_turns = 0,
+                  int cap_fast = 0, int cap_full_256 = 256)
 {
     SearchGrid G;
     if (const int rc = check_args(a, wv))
@@ -1960,6 +1985,8 @@ int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_stre
         return rc;
     SearchParams S = search_params(a, G, wv);
     S.explore_turns = explore_turns;
+    S.cap_fast = cap_fast;
+    S.cap_full_256 = cap_full_256;
     if (pk) {
         S.park_empties = pk->park_empties;
         S.parked = pk->parked;
@@ -2061,6 +2088,30 @@ extern "C" int iago_mcts_search_explore(const iago_mcts_search_args *a, const ia
                                       "a match's moves are not drawn from the visit counts"))
         return rc;
     return search_launch(a, stream, ex->streams, nullptr, ex->park, ex->explore_turns);
+}
+
+extern "C" int iago_mcts_search_cap(const iago_mcts_search_args *a, const iago_search_cap_args *cap, void *stream)
+{
+    if (!a || !cap)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: null args");
+    for (int i = 0; i < 4; i++)
+        if (cap->reserved[i] != 0 || cap->reserved0 != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: reserved fields must be 0");
+    if (cap->n_fast < 1 || cap->n_fast > a->n_sims)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: n_fast must be in [1, n_sims]");
+    if (cap->full_per_256 < 1 || cap->full_per_256 > 256)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: full_per_256 must be in [1, 256]");
+    if (cap->explore_turns < 0 || cap->explore_turns > IAGO_MAX_TURNS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: explore_turns must be in [0, 128]");
+    if (cap->park) {
+        if (const int rc = check_park(cap->park, "iago_mcts_search_cap (park)"))
+            return rc;
+        if (cap->park->streams && cap->park->streams != cap->streams)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap (park): park->streams must be NULL or `streams`");
+    }
+    if (const int rc = self_play_only(a, stream, "iago_mcts_search_cap", "a match's searches are not capped"))
+        return rc;
+    return search_launch(a, stream, cap->streams, nullptr, cap->park, cap->explore_turns, cap->n_fast, cap->full_per_256);
 }
 
 namespace {

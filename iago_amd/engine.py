@@ -1177,11 +1177,13 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None, explore_turns=None):
+    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None, explore_turns=None, playout_cap=None):
         """iago_mcts_search_persistent: one search from the roots (own, opp), or -- game = dict(max_turns, own,
         opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games; park = dict(empties,
         parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park); explore_turns
-        (an int > 0): those games' moves of the turns below it drawn from the visit counts (iago_mcts_search_explore)."""
+        (an int > 0): those games' moves of the turns below it drawn from the visit counts (iago_mcts_search_explore);
+        playout_cap = (n_fast, full_per_256): those games' searched turns full or fast (iago_mcts_search_cap, which
+        carries the other two)."""
         a, keep = self._search_args(own, opp, active, n_sims, game)
         ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
         if ev is not None:
@@ -1194,7 +1196,7 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
-        elif park is not None or explore_turns:
+        elif park is not None or explore_turns or playout_cap is not None:
             k = None
             if park is not None:
                 k = _lib.SearchParkArgs()
@@ -1202,7 +1204,9 @@ class BatchedMCTS(object):
                 k.parked, k.stones, k.pass_flg = (park["parked"].data_ptr(), park["stones"].data_ptr(),
                                                   park["pass_flg"].data_ptr())
             # (the role split where today's launch takes it, else the single launch)
-            if explore_turns:
+            if playout_cap is not None:
+                ops.search_cap(a, playout_cap[0], playout_cap[1], explore_turns=explore_turns, streams=self._split, park=k)
+            elif explore_turns:
                 ops.search_explore(a, explore_turns, streams=self._split, park=k)
             else:
                 k.streams = self._split
@@ -1355,10 +1359,15 @@ class BatchedMCTS(object):
             self.n_compactions += 1
             self._live_after_compaction = int(self.tree.n_nodes.max().item())
 
-    def error_flags(self):
+    def gave_up_word(self):
+        """Device copy (no sync) of the persistent search's gave-up word, None for the other engines.  Every launch
+        clears the word: a caller that launches again before it reads error_flags() keeps this and passes it there."""
+        return self._ps["ctl"][3].to(torch.int64) if self.persistent else None
+
+    def error_flags(self, gave_up_before=None):
         """Device tensor int64[5]: pools that overflowed, the look-ahead's error word, the saturation
         flags of the value and the policy net (0 where a net has none), the persistent search's
-        gave-up word."""
+        gave-up word -- ORed with gave_up_before, an earlier launch's gave_up_word()."""
         dev = self.cur_own.device
         zero = torch.zeros((), dtype=torch.int64, device=dev)
         parts = [self.tree.overflow.sum().to(torch.int64),
@@ -1366,7 +1375,8 @@ class BatchedMCTS(object):
         for fn in (self.value_fn, self.policy_fn):
             f = getattr(fn, "__dict__", {}).get("_ovf") if hasattr(fn, "check_saturation") else None
             parts.append(f.reshape(-1)[0].to(torch.int64) if f is not None and f.device == dev else zero)
-        parts.append(self._ps["ctl"][3].to(torch.int64) if self.persistent else zero)
+        gave = self._ps["ctl"][3].to(torch.int64) if self.persistent else zero
+        parts.append(gave if gave_up_before is None else gave | gave_up_before)
         return torch.stack(parts)
 
     def raise_errors(self, flags):
@@ -1445,14 +1455,25 @@ class BatchedMCTS(object):
     def draw_move(self, turn, active=None, want_visits=True):
         """best_move for exploring self-play: the move drawn in proportion to the visit counts of the root's children
         (ops.draw_move), game g under the id game_id_base + g at turn `turn` (an int: every game's)."""
+        ids, turns = self._turn_ids(turn)
+        ops.draw_move(self.tree.ref(), active, self.seed, ids, turns, self.move, self.visits if want_visits else None)
+        return self.move, self.visits
+
+    def _turn_ids(self, turn):
+        """(the games' global ids game_id_base + g as their 32 bits, `turn` for every game): two (n_games,) int32."""
         ids = getattr(self, "_draw_ids", None)
         if ids is None or ids[0] != self.game_id_base:
             g = (torch.arange(self.n_games, dtype=torch.int64, device=self.move.device) + self.game_id_base) & 0xFFFFFFFF
             ids = self._draw_ids = (self.game_id_base, torch.where(g >= (1 << 31), g - (1 << 32), g).to(torch.int32),
                                     torch.zeros(self.n_games, dtype=torch.int32, device=self.move.device))
         ids[2].fill_(int(turn))
-        ops.draw_move(self.tree.ref(), active, self.seed, ids[1], ids[2], self.move, self.visits if want_visits else None)
-        return self.move, self.visits
+        return ids[1], ids[2]
+
+    def cap_mask(self, turn, full_per_256):
+        """The playout cap's decision for turn `turn` (an int: every game's): a fresh (n_games,) uint8, 1 where the turn
+        is a fast one for game g under the id game_id_base + g (ops.playout_cap_mask)."""
+        ids, turns = self._turn_ids(turn)
+        return ops.playout_cap_mask(self.seed, ids, turns, full_per_256)
 
     def update_with_move(self, move, mask=None):
         """MCTS.update_with_move (MCTS.py:149-154); move int8 tensor, -1 = pass."""
@@ -1466,7 +1487,8 @@ class SelfPlayResult(object):
 
     own/opp: (T, B) int64 positions before each searched move (own = mover),
     pi: (T, B, 64) int32 root visit counts, valid: (T, B) uint8 (1: the game searched and moved
-    at that turn; 3: the move is the exact endgame solver's, solve_empties; 0: a pass or no turn),
+    at that turn; 4: it searched a FAST turn of the playout cap, playout_cap; 3: the move is the exact endgame
+    solver's, solve_empties; 0: a pass or no turn),
     move: (T, B) int8, score: (T, B) int8 the exact final disc difference from the mover's view on
     the solved rows (0 elsewhere), z: (B,) int8 result from colour 1's view,
     mover: (T,) colour to move at that turn (1 or 2)."""
@@ -1476,6 +1498,11 @@ class SelfPlayResult(object):
     def tuples(self):
         """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view."""
         return self._rows(1, True)
+
+    def fast_tuples(self):
+        """tuples() of the FAST turns of the playout cap (valid == 4): searched with n_fast playouts, so not policy
+        targets -- the game's result still labels them."""
+        return self._rows(_lib.REC_FAST, True)
 
     def solved_tuples(self):
         """Flat rows of the moves the endgame solver played (valid == 3): own, opp, move, score (the exact final disc
@@ -1615,7 +1642,7 @@ class SelfPlayEngine(object):
         return res
 
     def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None, solve_empties=None,
-                         explore_turns=None):
+                         explore_turns=None, playout_cap=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
@@ -1625,7 +1652,8 @@ class SelfPlayEngine(object):
         solve_empties = k: TWO launches -- the games hand over at their first turn of at most k empties
         (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the same
         records (valid 3, score), and the one readback follows both.  explore_turns (an int > 0): the searched moves of
-        the turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore)."""
+        the turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore).  playout_cap =
+        (n_fast, full_per_256): every searched turn is full or fast, in the launch (iago_mcts_search_cap)."""
         m, T = self.mcts, self.max_turns
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
@@ -1642,7 +1670,8 @@ class SelfPlayEngine(object):
             park = dict(empties=solve_empties, parked=torch.zeros(B, dtype=torch.uint8, device=dev),
                         stones=torch.zeros(B, dtype=torch.int32, device=dev),
                         pass_flg=torch.zeros(B, dtype=torch.uint8, device=dev))
-        m._launch_persistent(None, None, active, n_sims, game=g, park=park, explore_turns=explore_turns)
+        kw = {} if playout_cap is None else dict(playout_cap=playout_cap)   # (off: today's call, argument for argument)
+        m._launch_persistent(None, None, active, n_sims, game=g, park=park, explore_turns=explore_turns, **kw)
         if park is not None:
             # (own / opp / n_turns: a parked game's position and turn in, its final position and turn count out)
             out = ops.play_endgame(own, opp, g["n_turns"], park["stones"], park["pass_flg"], park["parked"], max_turns=T,
@@ -1653,7 +1682,9 @@ class SelfPlayEngine(object):
                           g["n_turns"].max().to(torch.int64).reshape(1),
                           (rec["valid"] == 1).sum().to(torch.int64).reshape(1),
                           m._ps["ctl"][7].to(torch.int64).reshape(1),
-                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)] + played_out).tolist()
+                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)] + played_out +
+                         ([] if playout_cap is None else
+                          [(rec["valid"] == _lib.REC_FAST).sum().to(torch.int64).reshape(1)])).tolist()
         m.net_workgroups_launched = int(back[8])
         if back[0] and not back[4]:
             # a pool filled up (the launch cannot compact): nothing of this attempt counts
@@ -1669,7 +1700,7 @@ class SelfPlayEngine(object):
             ops.check_play_endgame(back[10:15], out, solve_empties, ops.ENDGAME_TIME_LIMIT_MS)
         t = int(back[6])
         m.sim_counter = (m.sim_counter + t * n_sims) & 0xFFFFFFFF
-        m.n_leaf_evals += int(back[7]) * n_sims
+        m.n_leaf_evals += int(back[7]) * n_sims + (0 if playout_cap is None else int(back[-1]) * playout_cap[0])
         # a game's boards after n_turns[g] swaps of sides; colour 1's stones are `own` after an even number
         even = (g["n_turns"] % 2 == 0)
         p1, p2 = torch.where(even, own, opp), torch.where(even, opp, own)
@@ -1729,14 +1760,18 @@ class SelfPlayEngine(object):
         sol = searched & (_empties(own, opp) <= k)
         return searched & ~sol, sol
 
-    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None, explore_turns=None):
+    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None, explore_turns=None,
+                    playout_cap=None):
         """The games from (own, opp) turn by turn into res: a search from every root that is searched, the move, the
         books, in lockstep.  colours None: self-play, every active game searched; else play_match's (B,) int8 colours
         of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced.  solve_empties = k:
         a game that would search at a position of at most k empties leaves the search mask; the solver (ops.solve_endgame,
         EXACT: one launch per turn for all such games) gives its move, recorded with valid 3 and the exact score, and
         its flags join the turn's readback.  explore_turns (self-play): the searched moves of the turns below it are
-        drawn from the visit counts (BatchedMCTS.draw_move) instead of best_move's."""
+        drawn from the visit counts (BatchedMCTS.draw_move) instead of best_move's.  playout_cap = (n_fast,
+        full_per_256) (self-play): TWO searches per turn from the same sim_counter -- the turn's full games
+        (BatchedMCTS.cap_mask) with n_sims playouts, its fast ones with n_fast, recorded with valid 4 -- and the counter
+        n_sims on, once."""
         m, B, T = self.mcts, self.B, self.max_turns
         k = solve_empties
         explore_turns = explore_turns or 0
@@ -1762,11 +1797,34 @@ class SelfPlayEngine(object):
         if k is not None:
             full, none = torch.full_like(own, -1), torch.zeros_like(own)
             unsolved = torch.zeros(1, dtype=torch.int64, device=dev)
-        counts = m.search_counts(s_act).tolist()
+        cap, gave_up = playout_cap, None
+
+        def split(turn, s_act):
+            # (the searched games of turn `turn`: the full ones, the fast ones)
+            fast = m.cap_mask(turn, cap[1]) & s_act
+            return s_act ^ fast, fast
+        if cap is not None:
+            s_full, s_fast = split(t, s_act)
+            counts = m.search_counts(s_full).tolist()
+            counts_fast = m.search_counts(s_fast).tolist()
+        else:
+            counts = m.search_counts(s_act).tolist()
         while t < T:
             # ONE readback per turn (below): the flags of this turn's search, the check of its
             # moves, the end-of-game test and the counts the next search starts from
-            m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
+            if cap is None:
+                m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
+            else:
+                # (a fast turn is the first n_fast playouts of the full turn's search: the same Philox streams)
+                s0 = m.sim_counter
+                if counts[0] + counts_fast[0] > 0:
+                    m._compact_if_half_full(int(counts[1]))   # (once, for both searches: used = 0 keeps them from it)
+                m.search(own, opp, s_full, n_sims, counts=(counts[0], 0), check=False)
+                # (the fast games' launch clears the gave-up word of the full games': kept on the device for `back`)
+                gave_up = m.gave_up_word()
+                m.sim_counter = s0
+                m.search(own, opp, s_fast, cap[0], counts=(counts_fast[0], 0), check=False)
+                m.sim_counter = (s0 + n_sims) & 0xFFFFFFFF
             move, visits = m.draw_move(t, s_act) if t < explore_turns else m.best_move(s_act)
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
@@ -1778,6 +1836,8 @@ class SelfPlayEngine(object):
             if colours is None:
                 mv = torch.where(searched, move, torch.full_like(move, -1))
                 valid, live = s_act, done ^ 1   # game.py:84,108,140 (the games not yet done)
+                if cap is not None:
+                    valid = s_act + (_lib.REC_FAST - 1) * s_fast
             else:
                 with torch.no_grad():
                     if hasattr(pf, "forward_boards_split3"):
@@ -1811,9 +1871,12 @@ class SelfPlayEngine(object):
                 s_act = searched.to(torch.uint8)
             # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64, a solved
             # one a legal move)
-            back = torch.cat([m.error_flags(), (mv == -2).any().to(torch.int64).reshape(1),
+            if cap is not None:
+                s_full, s_fast = split(t, s_act)
+            back = torch.cat([m.error_flags(gave_up), (mv == -2).any().to(torch.int64).reshape(1),
                               bad_draw, done.all().to(torch.int64).reshape(1),
-                              m.search_counts(s_act)] + ([unsolved] if k is not None else [])).tolist()
+                              m.search_counts(s_act if cap is None else s_full)] + ([unsolved] if k is not None else []) +
+                             ([m.search_counts(s_fast)] if cap is not None else [])).tolist()
             m.raise_errors(back[:5])
             if back[5]:
                 # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
@@ -1826,6 +1889,8 @@ class SelfPlayEngine(object):
             if t % 2 == 0 and back[7]:
                 break
             counts = back[8:10]
+            if cap is not None:
+                counts_fast = back[-2:]
         # colour 1's stones are `own` after an even number of turns
         p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
         self._finish(res, p1, p2, t, t)
@@ -1834,7 +1899,7 @@ class SelfPlayEngine(object):
                 setattr(res, res.SCORE_RECORD if name == "score" else name, v[:t])
         return res
 
-    def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None):
+    def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -1850,17 +1915,28 @@ class SelfPlayEngine(object):
         (include/iago_hip_serving.h, iago_mcts_search_explore): with n the turn's visit row `pi`, N its sum and w the
         Philox word of (seed ^ EXPLORE_SEED_XOR; game_id_base + g, t), the lowest cell a with sum_{b <= a} n[b] >
         (w * N) >> 32.  The record keeps its shape (valid 1, pi the visit row, move the drawn move); the one launch and
-        the turn loop play the same games; solve_empties composes (a parked turn is not searched, so not drawn)."""
+        the turn loop play the same games; solve_empties composes (a parked turn is not searched, so not drawn).
+        playout_cap = (n_fast, full_per_256) (None, the default: off): playout-cap randomisation.  Every searched turn
+        t of game g is FULL -- n_sims playouts, valid 1, a policy target -- when the top byte of the Philox word of
+        (seed ^ CAP_SEED_XOR; game_id_base + g, t) is below full_per_256 (1 .. 256), else FAST: the first n_fast (1 ..
+        n_sims) playouts of the same search, the move played as ever (the most visited child; below explore_turns the
+        draw), recorded with valid 4 and its visit row, kept out of tuples() and given by fast_tuples().  sim_counter
+        advances by n_sims per turn all the same.  The one launch (iago_mcts_search_cap) and the turn loop play the same
+        games; solve_empties and explore_turns compose."""
         k = _solve_empties_arg(solve_empties)
         e = ops.explore_turns_arg(explore_turns)
+        c = ops.playout_cap_arg(playout_cap, n_sims)
         kw = {} if e is None else dict(explore_turns=e)   # (off: today's calls, argument for argument)
+        if c is not None:
+            kw["playout_cap"] = c
         res = self._one_launch(n_sims, self.B, handicap, record, solve_empties=k, **kw)
         if res is None:
             res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult(), solve_empties=k,
                                    **kw)
         return res
 
-    def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None):
+    def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
+                    playout_cap=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -1871,10 +1947,14 @@ class SelfPlayEngine(object):
         columns (tuples() give the game ids game_id_base ..); n_turns is the longest game's, `launches` the launches it
         took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch.  solve_empties: as in play() --
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
-        as in play() -- game G draws with its own id, whichever slot plays it."""
+        as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
+        turns are full or fast by its own id."""
         k = _solve_empties_arg(solve_empties)
         e = ops.explore_turns_arg(explore_turns)
+        c = ops.playout_cap_arg(playout_cap, n_sims)
         kw = {} if e is None else dict(explore_turns=e)
+        if c is not None:
+            kw["playout_cap"] = c
         m, T = self.mcts, self.max_turns
         n_games = int(n_games)
         if n_games < 1:
@@ -1930,7 +2010,7 @@ class SelfPlayEngine(object):
         res.mcts_colour = col
         return res
 
-    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None, explore_turns=None):
+    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None, explore_turns=None, playout_cap=None):
         """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same
         sim_counter, the first n_games columns kept."""
         m, B = self.mcts, self.B
@@ -1944,8 +2024,9 @@ class SelfPlayEngine(object):
                     hc = torch.zeros(B, dtype=torch.int64, device=handicap.device)
                     hc[:w] = handicap[k * B:k * B + w]
                 m.game_id_base, m.sim_counter = base + k * B, s0
+                kw = {} if playout_cap is None else dict(playout_cap=playout_cap)
                 parts.append((self.play(n_sims, handicap=hc, record=record, solve_empties=solve_empties,
-                                        explore_turns=explore_turns), w))
+                                        explore_turns=explore_turns, **kw), w))
         finally:
             m.game_id_base = base
         res = SelfPlayResult()

@@ -1172,6 +1172,50 @@ def search_explore(args, explore_turns, streams=None, park=None):
     check(_lib.lib().iago_mcts_search_explore(C.byref(args), C.byref(e), _stream()), "iago_mcts_search_explore")
 
 
+def playout_cap_arg(cap, n_sims):
+    """playout_cap of SelfPlayEngine.play / play_stream: None (off), or (n_fast, full_per_256) -- two ints, 1 <= n_fast <=
+    n_sims and 1 <= full_per_256 <= 256 -- returned as a tuple of ints."""
+    if cap is None:
+        return None
+    try:
+        n_fast, full = cap
+    except (TypeError, ValueError):
+        raise ValueError("playout_cap must be None or (n_fast, full_per_256), not %r" % (cap,))
+    for v in (n_fast, full):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("playout_cap must be None or (n_fast, full_per_256), two ints, not %r" % (cap,))
+    if not 1 <= n_fast <= int(n_sims):
+        raise ValueError("playout_cap: n_fast must be in [1, n_sims = %d], not %r" % (int(n_sims), n_fast))
+    if not 1 <= full <= 256:
+        raise ValueError("playout_cap: full_per_256 must be in [1, 256], not %r" % (full,))
+    return int(n_fast), int(full)
+
+
+def playout_cap_mask(seed, game_id, turn, full_per_256, out=None):
+    """iago_mcts_cap_mask (include/iago_hip_serving.h): (n,) uint8, 1 where turn[i] of the game with GLOBAL id game_id[i]
+    (id_base + g, as its 32 bits) is a FAST turn of the playout cap: word turn & 3 of Philox4x32-10 on (game_id, turn >> 2,
+    0, 0) under seed ^ CAP_SEED_XOR, fast iff (w >> 24) >= full_per_256.  game_id / turn: (n,) int32."""
+    n = game_id.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=game_id.device)
+    check(_lib.lib().iago_mcts_cap_mask(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(game_id, torch.int32, "game_id"),
+                                        _dev(turn, torch.int32, "turn"), int(full_per_256), n, _dev(out, torch.uint8, "fast"),
+                                        _stream()), "iago_mcts_cap_mask")
+    return out
+
+
+def search_cap(args, n_fast, full_per_256, explore_turns=0, streams=None, park=None):
+    """iago_mcts_search_cap (include/iago_hip_serving.h): the whole-game launch of `args` (a _lib.MctsSearchArgs) under
+    playout-cap randomisation -- a searched turn is full (args.n_sims playouts, valid 1) with probability full_per_256 /
+    256, else fast (n_fast playouts, valid 4); explore_turns, streams, park: as search_explore takes them.  The caller
+    keeps `args`, `park` and everything they point to alive until the launch has run."""
+    c = _lib.SearchCapArgs()
+    c.n_fast, c.full_per_256, c.explore_turns = int(n_fast), int(full_per_256), int(explore_turns or 0)
+    c.streams = streams
+    c.park = C.addressof(park) if park is not None else None
+    check(_lib.lib().iago_mcts_search_cap(C.byref(args), C.byref(c), _stream()), "iago_mcts_search_cap")
+
+
 def search_arena(args_a, args_b, check_result=True):
     """iago_mcts_search_arena (include/iago_hip_serving.h): the searches of `args_a` and `args_b` (two
     _lib.MctsSearchArgs, each a complete search of iago_mcts_search_persistent with its own nets, trees and rings) in

@@ -192,6 +192,49 @@ IAGO_API int iago_mcts_search_explore(const iago_mcts_search_args *args, const i
 IAGO_API int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
                                  const int32_t *turn, int8_t *move, int32_t *visits, void *stream);
 
+/* ------------------------------------------------------------------ playout-cap randomisation */
+
+#define IAGO_CAP_KEY 0x43415050u /* ("CAPP") the cap's Philox key: the rollout seed with its high word XOR this */
+
+typedef struct iago_search_cap_args {
+    int32_t n_fast;                    /* 1 .. n_sims: the playouts of a fast turn */
+    int32_t full_per_256;              /* 1 .. 256: a searched turn is full with probability full_per_256 / 256 */
+    int32_t explore_turns;             /* 0 .. IAGO_MAX_TURNS: as iago_search_explore_args' (0 = no draw) */
+    int32_t reserved0;                 /* 0 */
+    iago_search_streams *streams;      /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    const iago_search_park_args *park; /* optional: the hand-over of iago_mcts_search_park in the same launch (its
+                                          `streams` NULL or the one above) */
+    int64_t reserved[4];               /* 0 */
+} iago_search_cap_args;
+
+/*
+ * Whole self-play games (iago_mcts_search_persistent with max_turns > 0, a stream included) under PLAYOUT-CAP
+ * RANDOMISATION: every searched turn t (the game's turn counter, passes included) of the game with global id G is FULL or
+ * FAST, in integers:
+ *   - w: word t & 3 of Philox4x32-10 on the counter (rollout->id_base + G, t >> 2, 0, 0) under the key rollout->seed with
+ *     its high word XOR IAGO_CAP_KEY (a key of its own: not the explore draw's, a match's or the replay window's);
+ *   - the turn is full iff (w >> 24) < full_per_256, else fast.
+ * A full turn runs n_sims playouts and records valid 1; a fast turn runs n_fast playouts and records valid 4, rec_pi and
+ * rec_move filled as for a full turn.  Playout p of turn t draws the rollout stream rollout->stream_id + t * n_sims + p on
+ * both kinds of turn -- a fast turn is the first n_fast playouts of the full turn's search -- and `done`, the tree carried
+ * to the next turn, the move (the most visited child; below explore_turns the draw of iago_mcts_search_explore) and the
+ * books are iago_mcts_search_persistent's.  A fast root that ends without children raises ctl[4] as a full one does.
+ * With full_per_256 = 256 every turn is full: that launch, bit for bit (`streams`: iago_mcts_search_split's, `park`:
+ * iago_mcts_search_park's, explore_turns > 0: iago_mcts_search_explore's).  Refused (IAGO_ERR_INVALID): null args, n_fast
+ * outside 1 .. n_sims, full_per_256 outside 1 .. 256, reserved fields not 0, an explore_turns outside 0 ..
+ * IAGO_MAX_TURNS, a bad `park`, max_turns == 0, and match codes (2 / 3) in `active` (read as iago_mcts_search_park reads
+ * it; not in a stream).  The wave search, matches and the arena do not cap.
+ */
+IAGO_API int iago_mcts_search_cap(const iago_mcts_search_args *args, const iago_search_cap_args *cap, void *stream);
+
+/*
+ * The rule above for the turn loop, one thread per game: fast[i] = 1 where turn[i] of the game with GLOBAL id game_id[i]
+ * (id_base + G, as its 32 bits) is a fast turn under `seed` (the rollout seed; the XOR is applied here), else 0.
+ * Refused (IAGO_ERR_INVALID): n < 0, a null array with n > 0, full_per_256 outside 1 .. 256.
+ */
+IAGO_API int iago_mcts_cap_mask(uint64_t seed, const int32_t *game_id, const int32_t *turn, int32_t full_per_256, int64_t n,
+                                uint8_t *fast, void *stream);
+
 /* ------------------------------------------------------------------ arena */
 
 /*
