@@ -15,6 +15,7 @@ P = prior + 0.1, U = c*P*sqrt(N)/(0.01+n), root evaluated itself for its first
 n_thr simulations, no sign flip in backup, pass = action -1, subtree reuse.
 The wall-clock budget (10 s per move, MCTS.py:142) becomes a simulation count.
 """
+import collections
 import ctypes as C
 import numbers
 import os
@@ -36,6 +37,25 @@ def _p(t):
 
 
 _stream = ops._stream   # the current HIP stream as a void*
+
+# The rules of a batch of games beyond plain PV-MCTS, validated once (_play_rules) and handed on as ONE value:
+# solve_empties (None: off, else an int in [0, 20]), explore_turns (an int, 0: off), playout_cap (None: off, else
+# (n_fast, full_per_256)) -- as SelfPlayEngine.play documents them.
+PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap")
+NO_RULES = PlayRules(None, 0, None)
+
+
+def _read_back(values):
+    """The device values of the dict `values` (0-dim tensors or short integer vectors; None: left out) on the host after
+    ONE torch.cat(...).tolist() -- one host synchronisation: a dict under the same names, an int for a 0-dim value, a
+    list of ints for a vector."""
+    values = {k: v for k, v in values.items() if v is not None}
+    flat = torch.cat([v.to(torch.int64).reshape(-1) for v in values.values()]).tolist()
+    out, at = {}, 0
+    for k, v in values.items():
+        out[k] = flat[at] if v.dim() == 0 else flat[at:at + v.numel()]
+        at += v.numel()
+    return out
 
 _SEARCH_STREAMS = {}    # (device, game CUs) -> iago_search_streams* (None: this runtime gives no CU-masked streams)
 
@@ -1177,18 +1197,24 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _launch_persistent(self, own, opp, active, n_sims, game=None, park=None, explore_turns=None, playout_cap=None):
+    def _launch_persistent(self, own, opp, active, n_sims, rules=NO_RULES, game=None, park=None):
         """iago_mcts_search_persistent: one search from the roots (own, opp), or -- game = dict(max_turns, own,
-        opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games; park = dict(empties,
-        parked, stones, pass_flg): those games handed over at `empties` empties (iago_mcts_search_park); explore_turns
-        (an int > 0): those games' moves of the turns below it drawn from the visit counts (iago_mcts_search_explore);
-        playout_cap = (n_fast, full_per_256): those games' searched turns full or fast (iago_mcts_search_cap, which
-        carries the other two)."""
+        opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games under `rules` (a
+        PlayRules).  park = dict(parked, stones, pass_flg), given with rules.solve_empties: those games handed over at
+        that many empties (iago_mcts_search_park); rules.explore_turns: their moves of the turns below it drawn from the
+        visit counts (iago_mcts_search_explore, which carries the hand-over); rules.playout_cap: their searched turns
+        full or fast (iago_mcts_search_cap, which carries the other two).  The role split where it is set up, else the
+        single launch, whichever entry point takes the games."""
         a, keep = self._search_args(own, opp, active, n_sims, game)
         ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
         if ev is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
+        k = None
+        if park is not None:
+            k = _lib.SearchParkArgs()
+            k.park_empties = int(rules.solve_empties)
+            k.parked, k.stones, k.pass_flg = park["parked"].data_ptr(), park["stones"].data_ptr(), park["pass_flg"].data_ptr()
         if self.wave_entry:
             if game is not None:
                 raise ValueError("whole games in one launch are not available to the wave search (the turn loop is)")
@@ -1196,21 +1222,13 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
-        elif park is not None or explore_turns or playout_cap is not None:
-            k = None
-            if park is not None:
-                k = _lib.SearchParkArgs()
-                k.park_empties = int(park["empties"])
-                k.parked, k.stones, k.pass_flg = (park["parked"].data_ptr(), park["stones"].data_ptr(),
-                                                  park["pass_flg"].data_ptr())
-            # (the role split where today's launch takes it, else the single launch)
-            if playout_cap is not None:
-                ops.search_cap(a, playout_cap[0], playout_cap[1], explore_turns=explore_turns, streams=self._split, park=k)
-            elif explore_turns:
-                ops.search_explore(a, explore_turns, streams=self._split, park=k)
-            else:
-                k.streams = self._split
-                check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
+        elif rules.playout_cap is not None:
+            ops.search_cap(a, *rules.playout_cap, explore_turns=rules.explore_turns, streams=self._split, park=k)
+        elif rules.explore_turns:
+            ops.search_explore(a, rules.explore_turns, streams=self._split, park=k)
+        elif k is not None:
+            k.streams = self._split
+            check(_lib.lib().iago_mcts_search_park(C.byref(a), C.byref(k), _stream()), "iago_mcts_search_park")
         elif self._split is not None:
             check(_lib.lib().iago_mcts_search_split(C.byref(a), self._split, _stream()), "iago_mcts_search_split")
         else:
@@ -1592,6 +1610,41 @@ def _solve_empties_arg(k):
     return int(k)
 
 
+def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None):
+    """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
+    where its own validator refuses it.  Off is (None, 0, None): explore_turns is an int in the record."""
+    return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
+                     ops.playout_cap_arg(playout_cap, n_sims))
+
+
+def _colour_arg(colour, B, dev, name, or_none=""):
+    """A colour argument -- 1, 2 or a (B,) integer tensor of 1 / 2 -- as a (B,) int8 tensor of 1 / 2 on `dev`.  name:
+    the argument as the messages call it ("play_match: mcts_colour"); or_none: "None, " where the caller takes None."""
+    what = "%s is %s1, 2 or a (%d,) integer tensor of 1 / 2" % (name, or_none, B)
+    if isinstance(colour, torch.Tensor):
+        if tuple(colour.shape) != (B,) or colour.is_floating_point() or colour.is_complex():
+            raise ValueError(what)
+        col = colour.to(device=dev, dtype=torch.int8)
+        if not bool(((col == 1) | (col == 2)).all()) or not torch.equal(col.to(colour.dtype).cpu(), colour.cpu()):
+            raise ValueError("%s holds values other than 1 and 2" % name)
+        return col
+    if isinstance(colour, bool) or not isinstance(colour, numbers.Integral) or colour not in (1, 2):
+        raise ValueError(what)
+    return torch.full((B,), int(colour), dtype=torch.int8, device=dev)
+
+
+class _Side(object):
+    """One searching side of the turn loop (SelfPlayEngine._play_turns): an engine, its playouts per move and the colour
+    it searches -- a (B,) int8 tensor of 1 / 2, None: both.  The loop keeps the side's turn on it: `mine` (bool) and
+    `act` (uint8), the games it searches and moves in, and `counts`, search_counts(act) on the host; under a playout cap
+    `full` / `fast`, act's two parts, with `counts` / `counts_fast` theirs and `gave_up` the full games' gave-up word;
+    `move` / `visits`, its engine's best_move or draw_move."""
+
+    def __init__(self, mcts, n_sims, colour=None):
+        self.mcts, self.n_sims, self.colour = mcts, n_sims, colour
+        self.gave_up = None
+
+
 def _empties(own, opp):
     """(n,) int32: 64 - popcount(own | opp), the true count of empty squares (stone_num ignores handicap stones)."""
     cells = torch.arange(64, device=own.device)
@@ -1602,11 +1655,13 @@ class SelfPlayEngine(object):
     """Whole games on the B boards of a BatchedMCTS, three ways.  play(): lockstep PV-MCTS self-play -- both colours
     search the shared tree, moves are the most visited children, passes advance the tree with -1 (game.py:117-142 turn
     structure, both sides driven by MCTS.get_move).  play_stream(): n_games such games through the B slots.
-    play_match(): PV-MCTS against the SL policy (game.py --auto).  Two paths behind them, the same games record for
-    record: ONE launch of the persistent search that walks every game through its own turns (_play_persistent, wherever
-    _whole_games_in_one_launch allows it), and the turn loop (_play_turns: a search and a host readback per turn, self-play
-    being the match in which every game is searched and no move is drawn or forced), which is also the replay of a batch
-    whose launch filled a pool up (n_replayed counts those)."""
+    play_match(): PV-MCTS against the SL policy (game.py --auto).  Each validates its rules once (_play_rules: a
+    PlayRules) and hands them on as one value.  Two paths behind them, the same games record for record: ONE launch of
+    the persistent search that walks every game through its own turns (_play_persistent, wherever
+    _whole_games_in_one_launch allows it), and the turn loop (_play_turns: a search per searching side and ONE host
+    readback per turn; self-play is one side that searches both colours, a match one side of one colour with the other
+    colour's moves drawn from the policy net, ArenaEngine's games two sides), which is also the replay of a batch whose
+    launch filled a pool up (n_replayed counts those)."""
 
     def __init__(self, mcts, max_turns=_lib.IAGO_MAX_TURNS):
         self.mcts = mcts
@@ -1641,20 +1696,20 @@ class SelfPlayEngine(object):
         res.final_p1, res.final_p2 = p1, p2
         return res
 
-    def _play_persistent(self, n_sims, own, opp, record, games_total=0, active=None, res=None, solve_empties=None,
-                         explore_turns=None, playout_cap=None):
+    def _play_persistent(self, n_sims, own, opp, record, rules, games_total=0, active=None, res=None):
         """The whole game of every board in ONE launch (iago_mcts_search_persistent with max_turns > 0): each
         game walks through its own turns -- search, most visited move, update_with_move, the stone, the books
         -- with no barrier between the games' turns.  Same moves, visit counts and results as the turn-by-turn
         loop below (tests/test_search_persistent_gpu.py).  games_total > 0: the games_total games of own / opp
         as a stream through the B slots (play_stream).  active: (B,) uint8 kinds of game (play_match's codes), default
         all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up.
-        solve_empties = k: TWO launches -- the games hand over at their first turn of at most k empties
-        (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the same
-        records (valid 3, score), and the one readback follows both.  explore_turns (an int > 0): the searched moves of
-        the turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore).  playout_cap =
+        rules (a PlayRules): solve_empties = k: TWO launches -- the games hand over at their first turn of at most k
+        empties (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the
+        same records (valid 3, score), and the one readback follows both.  explore_turns > 0: the searched moves of the
+        turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore).  playout_cap =
         (n_fast, full_per_256): every searched turn is full or fast, in the launch (iago_mcts_search_cap)."""
         m, T = self.mcts, self.max_turns
+        solve_empties, cap = rules.solve_empties, rules.playout_cap
         B = games_total or self.B        # (the result's columns: one per game)
         dev = own.device
         rec = self._new_records(B)
@@ -1665,42 +1720,41 @@ class SelfPlayEngine(object):
         m._forget_stale_values()
         # (what the launch accumulates into, in case a pool fills up and the batch is replayed turn by turn)
         keep = [(t, t.clone()) for t in (m._ps["totals"], m.z_log_n, m.stats) if t is not None]
-        park, played_out = None, []
+        park = None
         if solve_empties is not None:
-            park = dict(empties=solve_empties, parked=torch.zeros(B, dtype=torch.uint8, device=dev),
+            park = dict(parked=torch.zeros(B, dtype=torch.uint8, device=dev),
                         stones=torch.zeros(B, dtype=torch.int32, device=dev),
                         pass_flg=torch.zeros(B, dtype=torch.uint8, device=dev))
-        kw = {} if playout_cap is None else dict(playout_cap=playout_cap)   # (off: today's call, argument for argument)
-        m._launch_persistent(None, None, active, n_sims, game=g, park=park, explore_turns=explore_turns, **kw)
+        m._launch_persistent(None, None, active, n_sims, rules, game=g, park=park)
+        out = None
         if park is not None:
             # (own / opp / n_turns: a parked game's position and turn in, its final position and turn count out)
             out = ops.play_endgame(own, opp, g["n_turns"], park["stones"], park["pass_flg"], park["parked"], max_turns=T,
                                    max_empties=solve_empties, records={k: rec[k] for k in ("own", "opp", "valid", "move", "score")},
                                    check_result=False)
-            played_out = [out["ctl"].to(torch.int64), (out["finished"] != park["parked"]).sum().reshape(1)]
-        back = torch.cat([m.error_flags(), m._ps["ctl"][4].to(torch.int64).reshape(1),
-                          g["n_turns"].max().to(torch.int64).reshape(1),
-                          (rec["valid"] == 1).sum().to(torch.int64).reshape(1),
-                          m._ps["ctl"][7].to(torch.int64).reshape(1),
-                          m._ps["ctl"][_lib.CTL_BAD_DRAW].to(torch.int64).reshape(1)] + played_out +
-                         ([] if playout_cap is None else
-                          [(rec["valid"] == _lib.REC_FAST).sum().to(torch.int64).reshape(1)])).tolist()
-        m.net_workgroups_launched = int(back[8])
-        if back[0] and not back[4]:
+        ctl = m._ps["ctl"]
+        back = _read_back(dict(
+            flags=m.error_flags(), no_children=ctl[4], turns=g["n_turns"].max(), full_rows=(rec["valid"] == 1).sum(),
+            net_workgroups=ctl[7], bad_draw=ctl[_lib.CTL_BAD_DRAW], endgame_ctl=out and out["ctl"],
+            unfinished=out and (out["finished"] != park["parked"]).sum(),
+            fast_rows=(rec["valid"] == _lib.REC_FAST).sum() if cap is not None else None))
+        m.net_workgroups_launched = back["net_workgroups"]
+        overflow, _, _, _, gave_up = back["flags"]
+        if overflow and not gave_up:
             # a pool filled up (the launch cannot compact): nothing of this attempt counts
             for t, was in keep:
                 t.copy_(was)
             return None
-        m.raise_errors(back[:5])
-        if back[5]:
+        m.raise_errors(back["flags"])
+        if back["no_children"]:
             raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
-        if back[9]:
+        if back["bad_draw"]:
             raise _lib.IagoError(_BAD_DRAW)
         if park is not None:
-            ops.check_play_endgame(back[10:15], out, solve_empties, ops.ENDGAME_TIME_LIMIT_MS)
-        t = int(back[6])
+            ops.check_play_endgame(back["endgame_ctl"] + [back["unfinished"]], out, solve_empties, ops.ENDGAME_TIME_LIMIT_MS)
+        t = back["turns"]
         m.sim_counter = (m.sim_counter + t * n_sims) & 0xFFFFFFFF
-        m.n_leaf_evals += int(back[7]) * n_sims + (0 if playout_cap is None else int(back[-1]) * playout_cap[0])
+        m.n_leaf_evals += back["full_rows"] * n_sims + (0 if cap is None else back["fast_rows"] * cap[0])
         # a game's boards after n_turns[g] swaps of sides; colour 1's stones are `own` after an even number
         even = (g["n_turns"] % 2 == 0)
         p1, p2 = torch.where(even, own, opp), torch.where(even, opp, own)
@@ -1724,58 +1778,58 @@ class SelfPlayEngine(object):
                 and os.environ.get("IAGO_PERSISTENT_GAMES", "1") != "0"
                 and 2 * m.tree.capacity >= suggest_capacity(n_sims, m.n_thr, moves=min(self.max_turns, 64)))
 
-    def _one_launch(self, n_sims, n, handicap, record, applies=True, **kw):
-        """Fresh trees, then the n games in one launch (_play_persistent(**kw)) wherever the persistent search applies
-        (and the caller's own condition does) and the pools can hold a whole game without compaction.  None where it
+    def _one_launch(self, n_sims, n, handicap, record, rules, applies=True, **kw):
+        """Fresh trees, then the n games in one launch (_play_persistent(rules, **kw)) wherever the persistent search
+        applies (and the caller's own condition does) and the pools can hold a whole game without compaction.  None where it
         does not -- and where a pool filled up all the same (n_replayed) -- with the trees fresh for the caller's
         fallback, whose searches (one launch per turn) compact a pool that is half full.  Same games either way."""
         m = self.mcts
         m.tree.reset()
         if not (applies and self._whole_games_in_one_launch(n_sims)):
             return None
-        res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, **kw)
+        res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, rules, **kw)
         if res is None:
             self.n_replayed += 1
             m.tree.reset()
         return res
 
-    def _movers(self, colours, t, active, legal, stone_num):
-        """Who moves at turn t in the games `active`: (the games searched as a uint8 mask and as a bool one, the games
-        whose move the policy draws, the games whose move is forced).  Self-play (colours None) searches them all."""
-        on = active.bool()
-        if colours is None:
-            return active, on, None, None
-        mcts_moves = colours == (1 if t % 2 == 0 else 2)
-        # game.py:97-98: the only move of the last empty square, either side, no search
-        forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
-        searched = on & mcts_moves & ~forced
-        return searched.to(torch.uint8), searched, on & ~mcts_moves & ~forced, forced
+    def _search_sides(self, sides, own, opp, rules):
+        """The turn's searches, one side after the other (check=False: the loop reads every side's flags back).  Under a
+        playout cap TWO searches per side from the same sim_counter -- a fast turn is the first n_fast playouts of the
+        full turn's search: the same Philox streams -- and the counter n_sims on, once.  Returns 1: a SelfPlayResult's
+        `launches` counts the turns."""
+        for s in sides:
+            m = s.mcts
+            if rules.playout_cap is None:
+                m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False)   # (sim_counter: + n_sims whoever searched)
+                continue
+            s0 = m.sim_counter
+            if s.counts[0] + s.counts_fast[0] > 0:
+                m._compact_if_half_full(int(s.counts[1]))   # (once, for both searches: used = 0 keeps them from it)
+            m.search(own, opp, s.full, s.n_sims, counts=(s.counts[0], 0), check=False)
+            # (the fast games' launch clears the gave-up word of the full games': kept on the device for the readback)
+            s.gave_up = m.gave_up_word()
+            m.sim_counter = s0
+            m.search(own, opp, s.fast, rules.playout_cap[0], counts=(s.counts_fast[0], 0), check=False)
+            m.sim_counter = (s0 + s.n_sims) & 0xFFFFFFFF
+        return 1
 
-    def _solved_turn(self, k, least, t, searched, own, opp):
-        """solve_empties = k at turn t: (the games of `searched` that still search, the games whose move the solver
-        plays) -- those of `searched` at a position of at most k empties.  least: the fewest empties any game started
-        with; a turn takes at most one, so before turn least - k no game can be there and nothing is launched."""
-        if k is None or least - t > k:
-            return searched, None
-        sol = searched & (_empties(own, opp) <= k)
-        return searched & ~sol, sol
-
-    def _play_turns(self, n_sims, own, opp, record, res, colours=None, solve_empties=None, explore_turns=None,
-                    playout_cap=None):
-        """The games from (own, opp) turn by turn into res: a search from every root that is searched, the move, the
-        books, in lockstep.  colours None: self-play, every active game searched; else play_match's (B,) int8 colours
-        of PV-MCTS, the other colour's moves drawn from the policy net and a final only move forced.  solve_empties = k:
-        a game that would search at a position of at most k empties leaves the search mask; the solver (ops.solve_endgame,
-        EXACT: one launch per turn for all such games) gives its move, recorded with valid 3 and the exact score, and
-        its flags join the turn's readback.  explore_turns (self-play): the searched moves of the turns below it are
-        drawn from the visit counts (BatchedMCTS.draw_move) instead of best_move's.  playout_cap = (n_fast,
-        full_per_256) (self-play): TWO searches per turn from the same sim_counter -- the turn's full games
-        (BatchedMCTS.cap_mask) with n_sims playouts, its fast ones with n_fast, recorded with valid 4 -- and the counter
-        n_sims on, once."""
-        m, B, T = self.mcts, self.B, self.max_turns
-        k = solve_empties
-        explore_turns = explore_turns or 0
-        dev = own.device
+    def _play_turns(self, sides, own, opp, record, res, rules, policy_moves=False, search=None):
+        """The games from (own, opp) turn by turn into res, in lockstep: per turn a search from every root that a side
+        searches, the move, the books, and ONE host readback.  sides: the _Side's that search -- one of colour None is
+        self-play (every active game searched), one of a colour with policy_moves is play_match (the other colour's
+        moves drawn from the first side's policy net, a final only move forced: searched by nobody), two of
+        complementary colours are the arena's agents; every side's tree follows every move.  search(sides, own, opp,
+        rules) -> launches runs the turn's searches: by default _search_sides, the one thing ArenaEngine replaces;
+        res.launches is the sum of what it returns.  rules (a PlayRules): solve_empties = k: a game that would search at
+        a position of at most k empties leaves the search mask; the solver (ops.solve_endgame, EXACT: one launch per turn
+        for all such games) gives its move, recorded with valid 3 and the exact score, and its flags join the turn's
+        readback.  explore_turns: the searched moves of the turns below it are drawn from the visit counts
+        (BatchedMCTS.draw_move) instead of best_move's.  playout_cap = (n_fast, full_per_256): the turn's full games
+        (BatchedMCTS.cap_mask) search n_sims playouts, its fast ones n_fast, recorded with valid 4 (_search_sides)."""
+        B, T, dev = self.B, self.max_turns, own.device
+        k, cap = rules.solve_empties, rules.playout_cap
+        search = search or self._search_sides
         stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -1783,120 +1837,130 @@ class SelfPlayEngine(object):
         legal = ops.legal_moves(own, opp)
         active = (legal != 0).to(torch.uint8)
         legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
-        bad_draw = torch.zeros(1, dtype=torch.int64, device=dev)   # (self-play draws nothing)
-        if colours is not None:
+        none = torch.full((B,), -1, dtype=torch.int8, device=dev)
+        if policy_moves:
+            m0 = sides[0].mcts
             cells = torch.arange(64, device=dev)
-            key = m.seed ^ _lib.MATCH_SEED_XOR
-            pf = m.policy_fn
-        t = 0
-        s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
-        least = 0 if k is None else int(_empties(own, opp).min().item())
-        searched, sol = self._solved_turn(k, least, t, searched, own, opp)
-        if sol is not None:
-            s_act = searched.to(torch.uint8)
+            key, pf = m0.seed ^ _lib.MATCH_SEED_XOR, m0.policy_fn
         if k is not None:
-            full, none = torch.full_like(own, -1), torch.zeros_like(own)
-            unsolved = torch.zeros(1, dtype=torch.int64, device=dev)
-        cap, gave_up = playout_cap, None
+            # (the fewest empties any game starts with: a turn takes at most one, so before turn least - k no game can be
+            # at k empties and nothing is launched for the solver)
+            least = int(_empties(own, opp).min().item())
+            full_board, no_board = torch.full_like(own, -1), torch.zeros_like(own)
 
-        def split(turn, s_act):
-            # (the searched games of turn `turn`: the full ones, the fast ones)
-            fast = m.cap_mask(turn, cap[1]) & s_act
-            return s_act ^ fast, fast
-        if cap is not None:
-            s_full, s_fast = split(t, s_act)
-            counts = m.search_counts(s_full).tolist()
-            counts_fast = m.search_counts(s_fast).tolist()
-        else:
-            counts = m.search_counts(s_act).tolist()
+        def movers(t):
+            """Who moves at turn t: every side's `mine` / `act` (under a cap `full` / `fast` too).  Returns the games
+            whose move the policy draws, those whose move is forced, those whose move the solver plays (None where there
+            are none of the kind) and, as device values by name, the counts the turn's searches start from."""
+            on = active.bool()
+            drawn = forced = sol = at_end = None
+            if policy_moves:
+                # game.py:97-98: the only move of the last empty square, either side, no search
+                forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
+                drawn = on & ~forced
+            if k is not None and least - t <= k:
+                at_end = _empties(own, opp) <= k
+            counts = {}
+            for i, s in enumerate(sides):
+                mine = on if s.colour is None else on & (s.colour == (1 if t % 2 == 0 else 2))
+                if policy_moves:
+                    drawn, mine = drawn & ~mine, mine & ~forced
+                if at_end is not None:
+                    sol = mine & at_end if sol is None else sol | (mine & at_end)
+                    mine = mine & ~at_end
+                s.mine, s.act = mine, active if mine is on else mine.to(torch.uint8)
+                if cap is None:
+                    counts["counts", i] = s.mcts.search_counts(s.act)
+                else:
+                    s.fast = s.mcts.cap_mask(t, cap[1]) & s.act
+                    s.full = s.act ^ s.fast
+                    counts["counts", i] = s.mcts.search_counts(s.full)
+                    counts["counts_fast", i] = s.mcts.search_counts(s.fast)
+            return drawn, forced, sol, counts
+
+        def start_from(back):
+            for i, s in enumerate(sides):
+                s.counts, s.counts_fast = back["counts", i], back.get(("counts_fast", i))
+
+        t, launched = 0, 0
+        drawn, forced, sol, counts = movers(t)
+        start_from(_read_back(counts))
         while t < T:
-            # ONE readback per turn (below): the flags of this turn's search, the check of its
-            # moves, the end-of-game test and the counts the next search starts from
-            if cap is None:
-                m.search(own, opp, s_act, n_sims, counts=counts, check=False)   # (sim_counter: + n_sims whoever searched)
-            else:
-                # (a fast turn is the first n_fast playouts of the full turn's search: the same Philox streams)
-                s0 = m.sim_counter
-                if counts[0] + counts_fast[0] > 0:
-                    m._compact_if_half_full(int(counts[1]))   # (once, for both searches: used = 0 keeps them from it)
-                m.search(own, opp, s_full, n_sims, counts=(counts[0], 0), check=False)
-                # (the fast games' launch clears the gave-up word of the full games': kept on the device for `back`)
-                gave_up = m.gave_up_word()
-                m.sim_counter = s0
-                m.search(own, opp, s_fast, cap[0], counts=(counts_fast[0], 0), check=False)
-                m.sim_counter = (s0 + n_sims) & 0xFFFFFFFF
-            move, visits = m.draw_move(t, s_act) if t < explore_turns else m.best_move(s_act)
+            # ONE readback per turn (below): every side's flags of this turn's search, the checks of its moves, the
+            # end-of-game test and the counts the next searches start from
+            launched += search(sides, own, opp, rules)
+            for s in sides:
+                s.move, s.visits = s.mcts.draw_move(t, s.act) if t < rules.explore_turns else s.mcts.best_move(s.act)
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
-                ex = ops.solve_endgame(torch.where(sol, own, full), torch.where(sol, opp, none), mode="exact",
+                ex = ops.solve_endgame(torch.where(sol, own, full_board), torch.where(sol, opp, no_board), mode="exact",
                                        max_empties=k, check_result=False)
-                unsolved = (ex["solved"] == 0).any().to(torch.int64).reshape(1)
-                move = torch.where(sol, ex["move"], move)
-                searched = searched | sol   # (from here on: the games PV-MCTS moves in)
-            if colours is None:
-                mv = torch.where(searched, move, torch.full_like(move, -1))
-                valid, live = s_act, done ^ 1   # game.py:84,108,140 (the games not yet done)
-                if cap is not None:
-                    valid = s_act + (_lib.REC_FAST - 1) * s_fast
-            else:
+            mv = none
+            if policy_moves:
                 with torch.no_grad():
                     if hasattr(pf, "forward_boards_split3"):
                         probs = pf.forward_boards_split3(own, opp)
                     else:
                         probs = pf(ops.encode_planes(own, opp))
                 draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)), seed=key,
-                                        id_base=m.game_id_base, step=t, stream_id=0)
+                                        id_base=m0.game_id_base, step=t, stream_id=0)
                 only = ((legal.reshape(B, 1) >> cells) & 1).argmax(dim=1).to(torch.int8)
-                mv = torch.where(searched, move, torch.where(drawn, draw, torch.where(forced, only, torch.full_like(move, -1))))
-                if record:
-                    valid = s_act + 2 * (drawn | forced).to(torch.uint8)
-                live = ((done == 0) & ~forced).to(torch.uint8)   # game.py:107,113,140
-                bad_draw = (drawn & (draw == 64)).any().to(torch.int64).reshape(1)
+                mv = torch.where(drawn, draw, torch.where(forced, only, none))
+            for s in reversed(sides):
+                mv = torch.where(s.mine, s.move, mv)
+            if sol is not None:
+                mv = torch.where(sol, ex["move"], mv)
             if record:
+                valid = pi = None
+                for s in sides:   # (a game has one mover: the sides' rows do not overlap)
+                    v = s.act if cap is None else s.act + (_lib.REC_FAST - 1) * s.fast
+                    p = s.visits * s.act.reshape(B, 1).to(torch.int32)
+                    valid, pi = (v, p) if valid is None else (valid | v, pi + p)
+                if policy_moves:
+                    valid = valid + 2 * (drawn | forced).to(torch.uint8)
                 if sol is not None:
                     valid = valid + 3 * sol.to(torch.uint8)
                     rec["score"][t] = torch.where(sol, ex["score"], torch.zeros_like(ex["score"]))
-                rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t] = own, opp, valid, mv
-                rec["pi"][t] = visits * s_act.reshape(B, 1).to(torch.int32)
-            m.update_with_move(mv, live)
+                rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t], rec["pi"][t] = own, opp, valid, mv, pi
+            # game.py:84,108,140: the games not yet done -- less, in a match, the forced moves (game.py:107,113)
+            live = ((done == 0) & ~forced).to(torch.uint8) if policy_moves else done ^ 1
+            for s in sides:
+                s.mcts.update_with_move(mv, live)
             # the move, stone_num / pass_flg, `while game.stone_num < 64` once per pair of turns
             # (game.py:117-142,253-255), the swap of sides, the next mover's legal moves
             ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
             legal, legal_next = legal_next, legal
             active, active_next = active_next, active
             t += 1
-            s_act, searched, drawn, forced = self._movers(colours, t, active, legal, stone_num)
-            searched, sol = self._solved_turn(k, least, t, searched, own, opp)
-            if sol is not None:
-                s_act = searched.to(torch.uint8)
             # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64, a solved
             # one a legal move)
-            if cap is not None:
-                s_full, s_fast = split(t, s_act)
-            back = torch.cat([m.error_flags(gave_up), (mv == -2).any().to(torch.int64).reshape(1),
-                              bad_draw, done.all().to(torch.int64).reshape(1),
-                              m.search_counts(s_act if cap is None else s_full)] + ([unsolved] if k is not None else []) +
-                             ([m.search_counts(s_fast)] if cap is not None else [])).tolist()
-            m.raise_errors(back[:5])
-            if back[5]:
+            checks = dict(no_children=(mv == -2).any(), all_done=done.all(),
+                          bad_draw=(drawn & (draw == 64)).any() if policy_moves else None,
+                          unsolved=(ex["solved"] == 0).any() if sol is not None else None)
+            drawn, forced, sol, counts = movers(t)
+            back = _read_back({**{("flags", i): s.mcts.error_flags(s.gave_up) for i, s in enumerate(sides)},
+                               **checks, **counts})
+            for i, s in enumerate(sides):
+                s.mcts.raise_errors(back["flags", i])
+            if back["no_children"]:
                 # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
                 raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
-            if back[6]:
+            if back.get("bad_draw"):
                 raise _lib.IagoError(_BAD_DRAW)
-            if k is not None and back[10]:
+            if back.get("unsolved"):
                 raise _lib.IagoError("solve_empties = %d: the endgame solver refused or did not finish a position at "
                                      "turn %d" % (k, t - 1))
-            if t % 2 == 0 and back[7]:
+            if t % 2 == 0 and back["all_done"]:
                 break
-            counts = back[8:10]
-            if cap is not None:
-                counts_fast = back[-2:]
+            start_from(back)
         # colour 1's stones are `own` after an even number of turns
         p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
-        self._finish(res, p1, p2, t, t)
+        self._finish(res, p1, p2, t, launched)
         if record:
             for name, v in rec.items():
-                setattr(res, res.SCORE_RECORD if name == "score" else name, v[:t])
+                name = res.SCORE_RECORD if name == "score" else name
+                if name is not None:   # (an ArenaResult keeps no score record)
+                    setattr(res, name, v[:t])
         return res
 
     def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None):
@@ -1923,16 +1987,14 @@ class SelfPlayEngine(object):
         draw), recorded with valid 4 and its visit row, kept out of tuples() and given by fast_tuples().  sim_counter
         advances by n_sims per turn all the same.  The one launch (iago_mcts_search_cap) and the turn loop play the same
         games; solve_empties and explore_turns compose."""
-        k = _solve_empties_arg(solve_empties)
-        e = ops.explore_turns_arg(explore_turns)
-        c = ops.playout_cap_arg(playout_cap, n_sims)
-        kw = {} if e is None else dict(explore_turns=e)   # (off: today's calls, argument for argument)
-        if c is not None:
-            kw["playout_cap"] = c
-        res = self._one_launch(n_sims, self.B, handicap, record, solve_empties=k, **kw)
+        return self._play(n_sims, handicap, record, _play_rules(n_sims, solve_empties, explore_turns, playout_cap))
+
+    def _play(self, n_sims, handicap, record, rules):
+        """play() under validated rules (a PlayRules)."""
+        res = self._one_launch(n_sims, self.B, handicap, record, rules)
         if res is None:
-            res = self._play_turns(n_sims, *self._start_boards(self.B, handicap), record, SelfPlayResult(), solve_empties=k,
-                                   **kw)
+            res = self._play_turns([_Side(self.mcts, n_sims)], *self._start_boards(self.B, handicap), record,
+                                   SelfPlayResult(), rules)
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
@@ -1949,12 +2011,7 @@ class SelfPlayEngine(object):
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
         turns are full or fast by its own id."""
-        k = _solve_empties_arg(solve_empties)
-        e = ops.explore_turns_arg(explore_turns)
-        c = ops.playout_cap_arg(playout_cap, n_sims)
-        kw = {} if e is None else dict(explore_turns=e)
-        if c is not None:
-            kw["playout_cap"] = c
+        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap)
         m, T = self.mcts, self.max_turns
         n_games = int(n_games)
         if n_games < 1:
@@ -1965,25 +2022,10 @@ class SelfPlayEngine(object):
         if handicap is not None and tuple(handicap.shape) != (n_games,):
             raise ValueError("play_stream: handicap is an (n_games,) int64 tensor")
         plain = getattr(m, "z_log", None) is None and getattr(m, "trace", None) is None
-        res = self._one_launch(n_sims, n_games, handicap, record, applies=plain, games_total=n_games, solve_empties=k, **kw)
+        res = self._one_launch(n_sims, n_games, handicap, record, rules, applies=plain, games_total=n_games)
         if res is None:
-            res = self._play_batches(n_sims, n_games, handicap, record, k, **kw)
+            res = self._play_batches(n_sims, n_games, handicap, record, rules)
         return res
-
-    def _match_colours(self, mcts_colour):
-        """play_match's mcts_colour as a (B,) int8 device tensor of 1 / 2."""
-        dev = self.mcts.cur_own.device
-        if isinstance(mcts_colour, torch.Tensor):
-            if tuple(mcts_colour.shape) != (self.B,) or mcts_colour.is_floating_point() or mcts_colour.is_complex():
-                raise ValueError("play_match: mcts_colour is 1, 2 or a (%d,) integer tensor of 1 / 2" % self.B)
-            col = mcts_colour.to(device=dev, dtype=torch.int8)
-            if not bool(((col == 1) | (col == 2)).all()) or not torch.equal(col.to(mcts_colour.dtype).cpu(),
-                                                                            mcts_colour.cpu()):
-                raise ValueError("play_match: mcts_colour holds values other than 1 and 2")
-            return col
-        if isinstance(mcts_colour, bool) or not isinstance(mcts_colour, numbers.Integral) or mcts_colour not in (1, 2):
-            raise ValueError("play_match: mcts_colour is 1, 2 or a (%d,) integer tensor of 1 / 2" % self.B)
-        return torch.full((self.B,), int(mcts_colour), dtype=torch.int8, device=dev)
 
     def play_match(self, n_sims, mcts_colour=2, record=True, solve_empties=None):
         """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
@@ -2000,19 +2042,20 @@ class SelfPlayEngine(object):
         precedence (valid 2), and not the policy's turns.  Such a match ALWAYS runs through the turn loop (launches =
         its turns): a one-launch match cannot hand its games over, the policy side needs the net workgroups to the last
         move."""
-        k = _solve_empties_arg(solve_empties)
-        col = self._match_colours(mcts_colour)
+        rules = _play_rules(n_sims, solve_empties)
+        col = _colour_arg(mcts_colour, self.B, self.mcts.cur_own.device, "play_match: mcts_colour")
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
-        res = self._one_launch(n_sims, self.B, None, record, applies=k is None, active=codes, res=MatchResult())
+        res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None, active=codes,
+                               res=MatchResult())
         if res is None:
-            res = self._play_turns(n_sims, *self._start_boards(self.B), record, MatchResult(), colours=col,
-                                   solve_empties=k)
+            res = self._play_turns([_Side(self.mcts, n_sims, col)], *self._start_boards(self.B), record, MatchResult(),
+                                   rules, policy_moves=True)
         res.mcts_colour = col
         return res
 
-    def _play_batches(self, n_sims, n_games, handicap, record, solve_empties=None, explore_turns=None, playout_cap=None):
-        """play_stream's batch loop: ceil(n_games / B) play() calls, batch k with game_id_base + k B and the same
-        sim_counter, the first n_games columns kept."""
+    def _play_batches(self, n_sims, n_games, handicap, record, rules):
+        """play_stream's batch loop: ceil(n_games / B) batches of play() under `rules`, batch k with game_id_base + k B
+        and the same sim_counter, the first n_games columns kept."""
         m, B = self.mcts, self.B
         base, s0 = m.game_id_base, m.sim_counter
         parts = []
@@ -2024,9 +2067,7 @@ class SelfPlayEngine(object):
                     hc = torch.zeros(B, dtype=torch.int64, device=handicap.device)
                     hc[:w] = handicap[k * B:k * B + w]
                 m.game_id_base, m.sim_counter = base + k * B, s0
-                kw = {} if playout_cap is None else dict(playout_cap=playout_cap)
-                parts.append((self.play(n_sims, handicap=hc, record=record, solve_empties=solve_empties,
-                                        explore_turns=explore_turns, **kw), w))
+                parts.append((self._play(n_sims, hc, record, rules), w))
         finally:
             m.game_id_base = base
         res = SelfPlayResult()
@@ -2070,6 +2111,8 @@ class ArenaResult(SelfPlayResult):
     turn it was (0 = A, 1 = B: the colour rule, searched or not), and a_colour: (B,) int8, the colour A played in each
     game."""
 
+    SCORE_RECORD = None   # (no solver in the arena: no `score` record)
+
     def score(self):
         """A's results: dict(wins, draws, losses, n, win_rate), a draw counting 1/2 (MatchResult.score's arithmetic)."""
         z = self.z.to(torch.int32) * torch.where(self.a_colour == 1, 1, -1).to(torch.int32)
@@ -2101,13 +2144,14 @@ class ArenaEngine(object):
     The two engines should differ in `game_id_base` or `seed`: otherwise game g's rollouts draw the SAME Philox stream on
     both sides (the streams are keyed by seed, game id and playout count, and both engines count their playouts alike).
 
-    The turn is self-play's (SelfPlayEngine._play_turns without colours: every mover with a legal move searches, no
-    forced final move); the one difference is who searches.  At turn t the mover of game g is A iff a_colour[g] ==
-    (1 if t % 2 == 0 else 2); A searches its movers from its tree, B its movers from its tree, the move is the mover's
-    best_move (below explore_turns: its draw_move, keyed by that engine's own seed and id), and BOTH trees advance by
-    every move.  One ops.play_turn and one host readback per turn.  Two forms, the same games record for record:
-    sequential (mcts_a.search, then mcts_b.search) and one launch per turn (iago_mcts_search_arena: both searches in one
-    grid); either way both engines' sim_counter advance by their n_sims every turn, whoever had movers.
+    The games run through SelfPlayEngine._play_turns with two sides of complementary colours (every mover with a legal
+    move searches, no forced final move): the turn loop is self-play's, the one difference is who searches.  At turn t
+    the mover of game g is A iff a_colour[g] == (1 if t % 2 == 0 else 2); A searches its movers from its tree, B its
+    movers from its tree, the move is the mover's best_move (below explore_turns: its draw_move, keyed by that engine's
+    own seed and id), and BOTH trees advance by every move.  One ops.play_turn and one host readback per turn.  The
+    turn's searches are this class's (_search_both), in two forms, the same games record for record: sequential
+    (mcts_a.search, then mcts_b.search) and one launch per turn (iago_mcts_search_arena: both searches in one grid);
+    either way both engines' sim_counter advance by their n_sims every turn, whoever had movers.
 
     Not here: whole arena games in one launch (a game's two trees live in different workgroups), the role split and more
     games per agent than a single launch holds, solve_empties, streams, more than two agents, an Elo table."""
@@ -2145,17 +2189,7 @@ class ArenaEngine(object):
             col = torch.full((B,), 2, dtype=torch.int8, device=dev)
             col[:B // 2] = 1
             return col
-        what = "play: a_colour is None, 1, 2 or a (%d,) integer tensor of 1 / 2" % B
-        if isinstance(a_colour, torch.Tensor):
-            if tuple(a_colour.shape) != (B,) or a_colour.is_floating_point() or a_colour.is_complex():
-                raise ValueError(what)
-            col = a_colour.to(device=dev, dtype=torch.int8)
-            if not bool(((col == 1) | (col == 2)).all()) or not torch.equal(col.to(a_colour.dtype).cpu(), a_colour.cpu()):
-                raise ValueError("play: a_colour holds values other than 1 and 2")
-            return col
-        if isinstance(a_colour, bool) or not isinstance(a_colour, numbers.Integral) or a_colour not in (1, 2):
-            raise ValueError(what)
-        return torch.full((B,), int(a_colour), dtype=torch.int8, device=dev)
+        return _colour_arg(a_colour, B, dev, "play: a_colour", "None, ")
 
     @staticmethod
     def _n_sims(n_sims):
@@ -2177,11 +2211,11 @@ class ArenaEngine(object):
             for m in (a, b):
                 m.reserve_net_rows(games + self.net_workgroups)
 
-    def _search_both(self, own, opp, s_a, s_b, n_a, n_b, counts, one_launch):
-        """The turn's searches: A's movers s_a from A's tree, B's movers s_b from B's.  counts: [A's games searched, the
-        nodes of A's fullest pool, B's, B's].  Returns the launches it took."""
+    def _search_both(self, sides, own, opp, one_launch):
+        """The turn's searches for the turn loop: A's movers (sides[0].act) from A's tree, B's (sides[1].act) from B's,
+        each side's `counts` being [its games searched, the nodes of its fullest pool].  Returns the launches it took."""
         a, b = self.a, self.b
-        c_a, c_b = [int(v) for v in counts[:2]], [int(v) for v in counts[2:4]]
+        (s_a, n_a, c_a), (s_b, n_b, c_b) = ((s.act, s.n_sims, [int(v) for v in s.counts]) for s in sides)
         if one_launch and self.net_workgroups is None:
             self._size_launch()
         # (a turn at which one agent has no mover is ONE launch anyway: today's)
@@ -2216,80 +2250,21 @@ class ArenaEngine(object):
         IAGO_ERR_CAPACITY), False = the sequential form, None = ONE_LAUNCH_DEFAULT.  Returns an ArenaResult."""
         n_a, n_b = self._n_sims(n_sims)
         col = self._colours(a_colour)
-        e = ops.explore_turns_arg(explore_turns) or 0
+        rules = _play_rules(n_a, explore_turns=explore_turns)
         if one_launch is not None and not isinstance(one_launch, bool):
             raise ValueError("play: one_launch is None, True or False, not %r" % (one_launch,))
         one = self.ONE_LAUNCH_DEFAULT if one_launch is None else one_launch
-        a, b, B, T, dev = self.a, self.b, self.B, self.max_turns, self.device
-        a.tree.reset()
-        b.tree.reset()
-        own = torch.full((B,), START_OWN, dtype=torch.int64, device=dev)
-        opp = torch.full((B,), START_OPP, dtype=torch.int64, device=dev)
-        stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
-        pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        rec = None
-        if record:
-            rec = dict(own=torch.zeros((T, B), dtype=torch.int64, device=dev), opp=torch.zeros((T, B), dtype=torch.int64, device=dev),
-                       pi=torch.zeros((T, B, 64), dtype=torch.int32, device=dev),
-                       valid=torch.zeros((T, B), dtype=torch.uint8, device=dev),
-                       move=torch.full((T, B), -1, dtype=torch.int8, device=dev),
-                       agent=torch.zeros((T, B), dtype=torch.uint8, device=dev))
-        legal = ops.legal_moves(own, opp)
-        active = (legal != 0).to(torch.uint8)
-        legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
-
-        def movers(t, active):
-            a_turn = col == (1 if t % 2 == 0 else 2)
-            on = active.bool()
-            return a_turn, on & a_turn, on & ~a_turn
-
-        t, launches = 0, 0
-        a_turn, on_a, on_b = movers(t, active)
-        s_a, s_b = on_a.to(torch.uint8), on_b.to(torch.uint8)
-        counts = torch.cat([a.search_counts(s_a), b.search_counts(s_b)]).tolist()
-        while t < T:
-            # ONE readback per turn (below): both engines' flags, the check of the moves, the end-of-game test and the
-            # counts the next searches start from
-            launches += self._search_both(own, opp, s_a, s_b, n_a, n_b, counts, one)
-            mv_a, vis_a = a.draw_move(t, s_a) if t < e else a.best_move(s_a)
-            mv_b, vis_b = b.draw_move(t, s_b) if t < e else b.best_move(s_b)
-            none = torch.full_like(mv_a, -1)
-            mv = torch.where(on_a, mv_a, torch.where(on_b, mv_b, none))
-            if record:
-                rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t] = own, opp, s_a | s_b, mv
-                rec["pi"][t] = vis_a * s_a.reshape(B, 1).to(torch.int32) + vis_b * s_b.reshape(B, 1).to(torch.int32)
-                rec["agent"][t] = (~a_turn).to(torch.uint8)
-            live = done ^ 1   # game.py:84,108,140 (the games not yet done): both trees follow every move
-            a.update_with_move(mv, live)
-            b.update_with_move(mv, live)
-            ops.play_turn(own, opp, mv, active, stone_num, pass_flg, done, t % 2 == 1, legal_next, active_next)
-            legal, legal_next = legal_next, legal
-            active, active_next = active_next, active
-            t += 1
-            a_turn, on_a, on_b = movers(t, active)
-            s_a, s_b = on_a.to(torch.uint8), on_b.to(torch.uint8)
-            back = torch.cat([a.error_flags(), b.error_flags(), (mv == -2).any().to(torch.int64).reshape(1),
-                              done.all().to(torch.int64).reshape(1), a.search_counts(s_a), b.search_counts(s_b)]).tolist()
-            a.raise_errors(back[:5])
-            b.raise_errors(back[5:10])
-            if back[10]:
-                # what max() over an empty children dict raises in MCTS.get_move (MCTS.py:147)
-                raise ValueError("a searched root has no children: n_sims is below the expansion threshold n_thr")
-            if t % 2 == 0 and back[11]:
-                break
-            counts = back[12:16]
-        res = ArenaResult()
-        res.game_id_base = a.game_id_base
-        res.n_turns, res.launches, res.game_turns = t, launches, None
-        res.mover = [1 if k % 2 == 0 else 2 for k in range(t)]
-        p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)   # colour 1's stones are `own` after an even number of turns
-        res.z = ops.judge(p1, p2)
-        res.final_p1, res.final_p2 = p1, p2
+        self.a.tree.reset()
+        self.b.tree.reset()
+        loop = SelfPlayEngine(self.a, self.max_turns)
+        res = loop._play_turns([_Side(self.a, n_a, col), _Side(self.b, n_b, 3 - col)], *loop._start_boards(self.B), record,
+                               ArenaResult(), rules,
+                               search=lambda sides, own, opp, rules: self._search_both(sides, own, opp, one))
         res.a_colour = col
         if record:
-            for name, v in rec.items():
-                setattr(res, name, v[:t])
+            # (whose turn it was is the colour rule, searched or not: A's where the turn's mover has A's colour)
+            mover = torch.tensor(res.mover, dtype=torch.int8, device=self.device).reshape(-1, 1)
+            res.agent = (col.reshape(1, self.B) != mover).to(torch.uint8)
         return res
 
 

@@ -300,7 +300,7 @@ def test_guards(nets):
     codes[5] = _lib.MATCH_MCTS_COLOUR_2
     m.tree.reset()
     with pytest.raises(_lib.IagoError, match=r"\(-1\)"):
-        e._play_persistent(N_SIMS, *e._start_boards(SLOTS), True, active=codes, explore_turns=EXPLORE)
+        e._play_persistent(N_SIMS, *e._start_boards(SLOTS), True, engine.PlayRules(None, EXPLORE, None), active=codes)
     err = _lib.lib().iago_last_error()
     assert err.startswith(b"iago_mcts_search_explore") and b"match codes" in err
     m.close()

@@ -3,6 +3,7 @@ iago_mcts_search_cap, iago_mcts_cap_mask): every searched turn is full (n_sims p
 n_fast playouts of the same search, valid 4) by the integer rule of tests/playout_cap_ref.py, and everything else is the
 plain engine's.  Sizes of test_explore_gpu.py: 64 slots, n_thr 15, capacity 4096, random-init nets, the shipped rollout
 weights; 32 playouts, 18 on a fast turn (a fresh root expands at its 16th), a quarter of the turns full."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -267,27 +268,30 @@ def test_tuples_are_the_full_rows_and_fast_tuples_the_fast_ones(capped):
 
 
 def test_none_is_todays_play(nets, plain, monkeypatch):
-    from iago_amd import engine, ops
+    """playout_cap = None launches what the plain engine launches: iago_mcts_search_persistent, or iago_mcts_search_split
+    where the engine set the role split up -- once for whole games in one launch, once per searched turn in the turn
+    loop -- and never the hand-over's, the draw's or the cap's entry point."""
+    from iago_amd import _lib, ops
 
     def never(*a, **k):
         raise AssertionError("playout_cap = None reached the playout cap's entry points")
     monkeypatch.setattr(ops, "search_cap", never)
     monkeypatch.setattr(ops, "playout_cap_mask", never)
-    seen = []
-    real = engine.BatchedMCTS._launch_persistent
-
-    def spy(self, *a, **k):
-        seen.append((len(a), sorted(k)))
-        return real(self, *a, **k)
-    monkeypatch.setattr(engine.BatchedMCTS, "_launch_persistent", spy)
+    lib, calls = _lib.lib(), collections.Counter()
+    for name in ("persistent", "split", "park", "explore", "cap"):
+        def counted(*a, _f=getattr(lib, "iago_mcts_search_" + name), _name=name):
+            calls[_name] += 1
+            return _f(*a)
+        monkeypatch.setattr(lib, "iago_mcts_search_" + name, counted)
     s = _play(nets, playout_cap=None)
-    assert s["launches"] == 1 and seen == [(4, ["explore_turns", "game", "park"])]
+    entry = "split" if s["split"] else "persistent"
+    assert s["launches"] == 1 and dict(calls) == {entry: 1}
     _same(s, plain)
-    seen.clear()
+    calls.clear()
     monkeypatch.setenv("IAGO_PERSISTENT_GAMES", "0")
     s = _play(nets, playout_cap=None)
-    # (a launch per turn that somebody searches, each with today's four arguments)
-    assert s["launches"] == s["n_turns"] and all(x == (4, []) for x in seen) and 1 < len(seen) <= s["n_turns"]
+    # (a launch per turn that somebody searches, each through the plain engine's entry point)
+    assert s["launches"] == s["n_turns"] and set(calls) == {entry} and 1 < calls[entry] <= s["n_turns"]
     _same(s, plain)
 
 
@@ -343,7 +347,7 @@ def test_guards(nets):
     a3, keep3 = m._search_args(own, opp, active, N_SIMS)          # (one search: max_turns == 0)
     refused(a3, b"whole games")
     with pytest.raises(_lib.IagoError, match=r"\(-1\)"):
-        e._play_persistent(N_SIMS, own, opp, True, active=codes, playout_cap=CAP)
+        e._play_persistent(N_SIMS, own, opp, True, engine.PlayRules(None, 0, CAP), active=codes)
     assert int(m._ps["ctl"][3].item()) == 0
     m.close()
 

@@ -44,7 +44,8 @@ def main():
 
     def selfplay():
         ms[0].tree.reset()
-        return sp._play_turns(args.sims, *sp._start_boards(B), False, engine.SelfPlayResult())
+        return sp._play_turns([engine._Side(ms[0], args.sims)], *sp._start_boards(B), False, engine.SelfPlayResult(),
+                              engine.NO_RULES)
 
     forms = [("one_launch", lambda: arena.play(args.sims, record=False, one_launch=True)),
              ("sequential", lambda: arena.play(args.sims, record=False, one_launch=False)),
