@@ -156,6 +156,9 @@ struct SearchParams {
     // playout-cap randomisation (iago_mcts_search_cap; cap_fast 0: off): a searched turn whose Philox word says FAST
     // (mcts_dev.hpp, cap_word: top byte >= cap_full_256) ends its search after cap_fast playouts and records valid 4
     int32_t cap_fast, cap_full_256;
+    // the descent jumps over a pass chain it remembers from the game's last playout (descend; IAGO_SEARCH_CHAIN_SKIP):
+    // timing only.  totals[16] then counts the levels jumped over
+    int32_t chain_skip;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -369,7 +372,12 @@ struct GameLds {
     uint8_t h_fast[GAMES_PER_WG];
     // (diagnostic counters of the workgroup, kept by thread 0 in LDS: as per-thread 64-bit registers they were 12 VGPRs
     // live across the whole loop -- what the game launch of the role split spilled to scratch memory)
-    uint32_t wg_count[6]; // [0] iterations, [1] idle iterations, [2..5] iterations with 0 / 1..16 / 17..20 / more games rolled out
+    uint32_t wg_count[7]; // [0] iterations, [1] idle iterations, [2..5] iterations with 0 / 1..16 / 17..20 / more games rolled out,
+                          // [6] levels of remembered pass chains the descents jumped over
+    // the pass chain at the end of each game's last recorded path (descend): ch_from = the first path index from which
+    // every step down to the path's last entry (index ch_len - 1) went from a node with ONE child to that child, a pass
+    // (-1: nothing remembered); ch_run: the same index for the path being recorded
+    int32_t ch_from[GAMES_PER_WG], ch_len[GAMES_PER_WG], ch_run[GAMES_PER_WG];
     int32_t roll_list[GAMES_PER_WG]; // games whose leaf is rolled out in this iteration, packed
     uint32_t roll_wave[BLOCK / 64], roll_wave_old[BLOCK / 64];
     // pacing: the workgroup's changes of CTL_PROGRESS / CTL_PLAYING in an iteration, which go out as one atomic each;
@@ -605,6 +613,8 @@ __device__ __forceinline__ void turn_boundary(const SearchParams &S, const iago_
         if (__builtin_amdgcn_ballot_w64(at_move || at_turn || at_draw) == 0ull)
             break;
         busy = busy || at_move || at_turn || at_draw;
+        if (at_move || at_turn || at_draw)
+            sh.ch_from[I.gl] = -1; // (the root moves, or the tree is a fresh one: the remembered pass chain is void)
         // the turn's Philox word, at ONE call site: explore_word at a turn's end (the draw, below), cap_word at a turn's
         // start -- the budget of the search this turn runs if the mover searches it (a turn that passes or parks leaves a
         // word nobody reads; the 8 lanes write the same word, before the legal set and the root are live)
@@ -723,6 +733,15 @@ __device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I,
     if (descending && C.fc >= 0 && I.r == 0u)
         S.T.overflow[I.gt] = 1; // path longer than MAX_DEPTH: reported like a full pool
     C.leaf = C.node;
+    if constexpr (!WAVE) {
+        // the path's final run of pass levels, for the game's next playout -- unless the descent was cut off or the path
+        // did not fit its buffer
+        if (S.chain_skip && I.r == 0u) {
+            const int run = sh.ch_run[I.gl];
+            sh.ch_from[I.gl] = (!descending && C.path_n <= S.path_stride && run < C.path_n - 1) ? run : -1;
+            sh.ch_len[I.gl] = C.path_n;
+        }
+    }
     const float c = __uint_as_float(C.vbits);
     C.leaf_fresh = I.need_v && c != c;
     bool ask = C.leaf_fresh;
@@ -800,7 +819,7 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
 
 // Node.select: two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
 template <bool WAVE>
-__device__ __forceinline__ void select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
+__device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
 {
     const int kk = descending ? C.k : 0;
     const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv));
@@ -822,12 +841,14 @@ __device__ __forceinline__ void select_child(const SearchParams &S, const Slot &
     argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
     argmax_step_payload<DPP_HALF_MIRROR>(best_v, best_i, pl);
     uint64_t own = C.own, opp = C.opp;
-    place_stone(own, opp, descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1, I.L);
+    const int action = descending ? (int)(int8_t)(pl[2] & 0xFFu) : -1;
+    place_stone(own, opp, action, I.L);
     if (descending) {
         C.own = own;
         C.opp = opp;
         cursor_to<WAVE>(C, C.fc + best_i, pl[0], pl[1], pl[2], pl[2] >> 16, pl[3]);
     }
+    return action;
 }
 
 // ---- 4. descent (MCTS.py:105-133; the games' lanes): from the root, or on from the leaf whose priors arrived, to a node
@@ -855,8 +876,52 @@ __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, Ga
         C.path_n = 0;
         C.may_expand = true;
     }
+    // The remembered pass chain (plain search).  A pass child is the only child its parent will ever have and a pass
+    // places no stone, so the final run of pass levels of a game's path is the same list of nodes playout after playout
+    // -- and the last playout's copy of it is still in the path buffer.  A game that is about to record path index
+    // ch_from and stands on the node already there takes the entries up to ch_len - 1 as they are and goes on at the last
+    // of them: ONE record instead of one per level (each a round trip to memory, walked in lockstep by the wave's eight
+    // games).  Which nodes the path holds, what they count and where the playout ends are the walk's; timing only.
+    // jump_at: the path index at which this game may jump (-1: none); jumped: the levels it jumped over in this call, which
+    // count against MAX_DEPTH like the walk's (-1: the game ran into that bound after a jump)
+    int jump_at = -1, jumped = 0;
+    if constexpr (!WAVE) {
+        if (S.chain_skip) {
+            jump_at = descending ? sh.ch_from[I.gl] : -1;
+            if (fresh_start && I.r == 0u)
+                sh.ch_run[I.gl] = 0;
+        }
+    }
     const bool went = descending;
     for (int depth = 0; depth < MAX_DEPTH; depth++) {
+        if constexpr (!WAVE) {
+            if (descending && depth + jumped >= MAX_DEPTH) { // (the walk's loop would have ended here)
+                descending = false;
+                jumped = -1;
+            }
+            if (descending && !skip_record && C.path_n == jump_at) {
+                const int len = sh.ch_len[I.gl], n_skip = len - 1 - jump_at;
+                const int last = path_entry(I.path_at, I.gpath, len - 1);
+                if (path_entry(I.path_at, I.gpath, jump_at) == C.node && depth + n_skip < MAX_DEPTH) {
+                    uint4 s0, l0;
+                    node_record(S.T, I.base + last, s0, l0);
+                    if (n_skip & 1) { // (a pass places nothing; c = 3 - c)
+                        const uint64_t t = C.own;
+                        C.own = C.opp;
+                        C.opp = t;
+                    }
+                    cursor_to<WAVE>(C, last, l0.x, s0.x, l0.z, l0.w, s0.w);
+                    C.path_n = len;
+                    skip_record = true; // (the entry is there)
+                    jumped = n_skip;
+                    st_levels += n_skip; // (the levels of the reference's descent, one child each)
+                    st_children += n_skip;
+                    if (I.r == 0u)
+                        atomicAdd(&sh.wg_count[6], (uint32_t)n_skip);
+                }
+                jump_at = -1;
+            }
+        }
         if (descending && !skip_record) {
             if (I.r == 0u) {
                 if (C.path_n < S.path_stride) {
@@ -879,10 +944,13 @@ __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, Ga
         st_levels += descending ? 1 : 0;
         st_children += descending ? C.k : 0;
         // Chains of pass nodes.  At the end of a game neither side has a move, and the reference goes on expanding: a pass
-        // child under the pass child, one level deeper every n_thr visits (MCTS.py:109-117) -- the last turns of a game
-        // descend through 65 such levels per playout on average (400 playouts per move; LABNOTES.md).  A node with ONE
-        // child leaves nothing to choose (max over one element, MCTS.py:46): when that is so for every game of the wave
-        // that still descends and all those children are passes, the level is the child's record and the swap of sides
+        // child under the pass child, one level deeper every n_thr visits (MCTS.py:109-117) -- with 1 .. 3 empties at the
+        // root a playout's path is 15 .. 25 nodes long at 100 playouts per move, and 61 % of all levels of a 400-playout
+        // game are such levels (LABNOTES.md).  A game that was here in its last playout jumps over them (above); a level
+        // that is still walked -- a chain's first playout, a path the last playout did not take -- is this one: a node
+        // with ONE child leaves nothing to choose (max over one element, MCTS.py:46), and when that is so for every game
+        // of the wave that still descends and all those children are passes, the level is the child's record and the swap
+        // of sides, without the scoring
         if (__builtin_amdgcn_ballot_w64(descending && C.k != 1) == 0ull) {
             uint4 s0, l0;
             node_record(S.T, descending ? I.base + C.fc : I.base, s0, l0);
@@ -897,8 +965,16 @@ __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, Ga
                 continue;
             }
         }
-        select_child<WAVE>(S, I, C, descending);
+        const bool one = C.k == 1;
+        const int action = select_child<WAVE>(S, I, C, descending);
+        if constexpr (!WAVE) {
+            // (a step that is no pass level: a pass chain can begin at the child, the next index to be recorded, at the earliest)
+            if (S.chain_skip && descending && I.r == 0u && !(one && action < 0))
+                sh.ch_run[I.gl] = C.path_n;
+        }
     }
+    if constexpr (!WAVE)
+        descending = descending || jumped < 0;
     if (went) {
         if (need_prior)
             ask_priors(S, I, sh, G, C);
@@ -1110,6 +1186,7 @@ __device__ __forceinline__ bool stream_claim(const SearchParams &S, const Slot &
             atomicAdd(&sh.pace[1], 1); // (in play again: CTL_PLAYING at the next iteration's end)
         }
         sh.h_game[I.gl] = (int32_t)next;
+        sh.ch_from[I.gl] = -1; // (a fresh tree)
         G.state = ST_TURN;
         in_play = true;
     }
@@ -1147,6 +1224,8 @@ __device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, G
         atomicAdd((unsigned long long *)&S.totals[13], (unsigned long long)sh.wg_count[3]);
         atomicAdd((unsigned long long *)&S.totals[14], (unsigned long long)sh.wg_count[4]);
         atomicAdd((unsigned long long *)&S.totals[15], (unsigned long long)sh.wg_count[5]);
+        if (S.chain_skip) // (a caller that sets the flag gives totals [17])
+            atomicAdd((unsigned long long *)&S.totals[16], (unsigned long long)sh.wg_count[6]);
         atomicAdd((unsigned long long *)&S.totals[7], (unsigned long long)(wall_clock64() - t0));
         __hip_atomic_fetch_add(&S.ctl[CTL_FINISHED], 1u, RLX_AGENT);
     }
@@ -1182,6 +1261,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
         sh.h_game[I.gl] = (int32_t)I.gt; // (the 8 lanes write the same word; each reads back its own store; a wave: the tree's id)
         sh.h_budget[I.gl] = S.n_sims;    // (every search of the launch, unless a capped turn says otherwise)
         sh.h_fast[I.gl] = 0;
+        sh.ch_from[I.gl] = -1; // (no path yet, no remembered pass chain)
     }
     const bool whole_game = I.whole && I.exists && I.g < S.games_total;
     start_game(G, whole_game ? S.game_own[I.g] : 0ull, whole_game ? S.game_opp[I.g] : 0ull);
@@ -1190,7 +1270,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     Cursor C = {};
     C.fc = -1;
     int st_levels = 0, st_children = 0;
-    if (I.tid < 6)
+    if (I.tid < 7)
         sh.wg_count[I.tid] = 0u;
     bool deferred = false;    // this game's rollout was put off to the next iteration's first pass
     bool table_ready = false; // the rollout's factor table is in LDS (from the first pass on)
@@ -1659,6 +1739,12 @@ struct iago_search_streams {
 };
 
 namespace {
+// games_per_workgroup without its flag (IAGO_SEARCH_CHAIN_SKIP)
+int games_per_wg_of(const iago_mcts_search_args *a)
+{
+    return a->games_per_workgroup > 0 ? (a->games_per_workgroup & ~IAGO_SEARCH_CHAIN_SKIP) : a->games_per_workgroup;
+}
+
 // the arguments of a launch (what does not depend on the device)
 int check_args(const iago_mcts_search_args *a, const iago_search_wave_args *wv)
 {
@@ -1698,7 +1784,7 @@ int check_args(const iago_mcts_search_args *a, const iago_search_wave_args *wv)
         ro->uniforms || ro->throughput_hint != 0)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: product-form rollout of the n games without "
                                            "trace / uniforms expected");
-    const int gpw = a->games_per_workgroup;
+    const int gpw = games_per_wg_of(a);
     if (!wv && gpw > 0 && gpw != 8 && gpw != 16 && gpw != 24 && gpw != 32)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: games_per_workgroup is 0 (= 32), 8, 16 or 32");
     if (a->max_cus < 0)
@@ -1721,7 +1807,7 @@ struct SearchGrid {
 // workgroups of this kernel per CU (its registers and LDS allow one).
 int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iago_search_wave_args *wv, bool park, SearchGrid &G)
 {
-    G.gpw = wv ? GAMES_PER_WG : a->games_per_workgroup > 0 ? a->games_per_workgroup : GAMES_PER_WG;
+    G.gpw = wv ? GAMES_PER_WG : games_per_wg_of(a) > 0 ? games_per_wg_of(a) : GAMES_PER_WG;
     G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
     G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
     int32_t cus = 0, per_cu = 0;
@@ -1885,6 +1971,8 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.explore_turns = 0;
     S.cap_fast = 0;
     S.cap_full_256 = 256;
+    // (the wave search's descent keeps its in-flight counts per node and walks every level)
+    S.chain_skip = (!wv && a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_CHAIN_SKIP)) ? 1 : 0;
     return S;
 }
 
@@ -2185,7 +2273,7 @@ extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago
     const int64_t resident = use_cus * per;
     int64_t games = 0;
     for (int i = 0; i < 2; i++) {
-        G[i].gpw = set[i]->games_per_workgroup > 0 ? set[i]->games_per_workgroup : GAMES_PER_WG;
+        G[i].gpw = games_per_wg_of(set[i]) > 0 ? games_per_wg_of(set[i]) : GAMES_PER_WG;
         G[i].n_slots = set[i]->tree->n_games;
         G[i].n_game_wgs = (G[i].n_slots + G[i].gpw - 1) / G[i].gpw;
         G[i].path_lds_cap = SEARCH_IMG_TOP;

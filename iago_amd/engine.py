@@ -212,9 +212,17 @@ class BatchedMCTS(object):
                  n_thr=15, capacity=4096, seed=0, game_id_base=0, device="cuda", use_graph=False,
                  sync_free=None, lookahead=None, lookahead_slots=None, value_cache=None, lookahead_overlap=None,
                  z_log_rows=0, async_steps=None, async_parts=None, value_ahead=None, persistent=None,
-                 net_workgroups=None, max_cus=None, split=None, wave=1, virtual_loss=1.0):
+                 net_workgroups=None, max_cus=None, split=None, wave=1, virtual_loss=1.0, chain_skip=True,
+                 path_stride=None):
         if n_thr < 1:
             raise ValueError("n_thr must be >= 1")
+        # (the persistent search) chain_skip: a descent jumps over the pass chain it remembers from its game's last
+        # playout (IAGO_SEARCH_CHAIN_SKIP: timing only, same trees; False: every level is walked -- the A/B switch).
+        # path_stride: entries of a game's path buffer (None: 520, the descent's own bound of 512 levels and a margin; at
+        # least 8).  A path that does not fit is reported like a full pool; 32 paths that fit a workgroup's LDS live there
+        if path_stride is not None and (isinstance(path_stride, bool) or int(path_stride) != path_stride or path_stride < 8):
+            raise ValueError("path_stride must be None or an int >= 8, not %r" % (path_stride,))
+        self.chain_skip = bool(chain_skip)
         # Wave search (iago_mcts_search_wave in include/iago_hip_serving.h): `wave` playouts of every tree in flight at
         # once, steered by virtual visits (an in-flight visit counts as a loss of `virtual_loss`), descents and backups
         # in slot order -- deterministic, and with wave = 1 today's search bit for bit.  For ONE game (MCTS.get_move)
@@ -510,14 +518,14 @@ class BatchedMCTS(object):
                 self.net_workgroups = max(1, min(int(net_workgroups), self.resident_workgroups
                                                  - max(self.split_cus, self.resident_workgroups // 8)))
             grid = n_gw + self.net_workgroups
-            self.PATH_STRIDE = 520
+            self.PATH_STRIDE = 520 if path_stride is None else int(path_stride)
             i64 = torch.int64
             self._ps = dict(
                 path=torch.zeros((ns, self.PATH_STRIDE), dtype=torch.int32, **kw),
                 done=torch.zeros(ns, dtype=torch.int32, **kw), roll=torch.zeros(ns, dtype=torch.uint8, **kw),
                 q_slots=torch.zeros(2 * _lib.SEARCH_QUEUE_ENTRIES * 8, dtype=i64, **kw), ctl=torch.zeros(16, dtype=torch.int32, **kw),
                 rep_v=torch.zeros(ns, dtype=i64, **kw), rep_p=torch.zeros(ns * 64, dtype=i64, **kw),
-                totals=torch.zeros(16, dtype=i64, **kw), wg_own=torch.zeros(4 * grid, dtype=i64, **kw),
+                totals=torch.zeros(17, dtype=i64, **kw), wg_own=torch.zeros(4 * grid, dtype=i64, **kw),
                 wg_opp=torch.zeros(4 * grid, dtype=i64, **kw), wg_v=torch.zeros(4 * grid, dtype=torch.float32, **kw),
                 wg_probs=torch.zeros((4 * grid, 64), dtype=torch.float32, **kw))
             # position table of the value net (iago_mcts_search_args.vtable): 2^20 entries of 32 bytes, shared by the
@@ -1258,7 +1266,7 @@ class BatchedMCTS(object):
         a.active = active.data_ptr()
         a.c_puct, a.lmbda, a.n_thr, a.n_sims = self.c_puct, self.lmbda, self.n_thr, int(n_sims)
         a.net_workgroups, a.time_limit_ms = self.net_workgroups, self.time_limit_ms
-        a.games_per_workgroup = self.games_per_workgroup
+        a.games_per_workgroup = self.games_per_workgroup | (_lib.SEARCH_CHAIN_SKIP if self.chain_skip else 0)
         a.pace_margin = self.pace_margin
         a.max_cus = self.max_cus
         a.value, a.policy, a.rollout = C.addressof(va), C.addressof(pa), C.addressof(ro.args)

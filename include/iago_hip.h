@@ -188,7 +188,6 @@ typedef struct iago_rollout_args {
  */
 IAGO_API int iago_rollout(const iago_rollout_args *args, void *stream);
 
-
 /* ------------------------------------------------------------------- nets */
 
 /*
@@ -381,7 +380,6 @@ IAGO_API int iago_mcts_compact(const iago_mcts_tree *tree, const iago_mcts_tree 
  * [n_games][slots][64] float32, the queue arrays [q_capacity].
  */
 
-
 /* (optional extensions of the per-playout engine, measured slower and kept for reproduction only: their state structs and
    entry points are in include/iago_hip_experimental.h) */
 struct iago_mcts_async;
@@ -455,7 +453,6 @@ IAGO_API int iago_mcts_descend(const iago_mcts_tree *tree, const uint64_t *root_
                                const iago_mcts_lookahead *la, int64_t *fresh_index, int32_t *fresh_count,
                                int64_t *fresh_total, void *stream);
 
-
 /*
  * A whole search -- n_sims playouts of every active game, the loop of MCTS.get_move (MCTS.py:139-147)
  * around MCTS.playout (MCTS.py:105-133) -- as ONE persistent launch in which every game runs on its
@@ -488,6 +485,9 @@ IAGO_API int iago_mcts_descend(const iago_mcts_tree *tree, const uint64_t *root_
  */
 #define IAGO_SEARCH_QUEUE_ENTRIES 4096
 #define IAGO_SEARCH_GAMES_PER_WORKGROUP 32   /* games a game workgroup owns (at most, and by default) */
+/* OR-ed into games_per_workgroup: a descent jumps over the pass chain it remembers from its game's last playout (timing
+   only: same trees, moves, records and overflow flags); totals is then [17], totals[16] the levels jumped over */
+#define IAGO_SEARCH_CHAIN_SKIP 0x100
 typedef struct iago_mcts_search_args {
     const iago_mcts_tree *tree;
     const uint64_t *root_own, *root_opp;

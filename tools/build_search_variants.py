@@ -51,29 +51,33 @@ def request_log(s):
 def phase_stamps(s):
     """Game workgroup 0's iteration by phase (100 MHz stamps of thread 0), at the driver loop's phase calls: replies +
     moves, descent, the control words' loads, the rollouts (packing + passes), the backups, the end of the iteration (two
-    barriers, pacing); summed in iago_game_phases[0..5], the iterations in [7]."""
-    s = patch(s, "namespace {\nusing namespace iago;", "__device__ unsigned long long iago_game_phases[8];\nnamespace {\nusing namespace iago;")
+    barriers, pacing); summed in iago_game_phases[0..5], the iterations in [7].  Only the iterations in which the
+    workgroup's first game stands at turn iago_game_phase_from or later are stamped (0, the default: all of them;
+    iago_debug_game_phases_from sets it): the end of a batch, where the pass chains are, on its own."""
+    s = patch(s, "namespace {\nusing namespace iago;", "__device__ unsigned long long iago_game_phases[8];\n"
+              "__device__ int iago_game_phase_from;\nnamespace {\nusing namespace iago;")
     s = patch(s, """    for (;;) {
-        const long long c_it = WAVE ? wall_clock64() : 0;""", """    long long ph[6] = {0, 0, 0, 0, 0, 0};
+        const long long c_it = WAVE ? wall_clock64() : 0;""", """    long long ph[6] = {0, 0, 0, 0, 0, 0}, ph_it = 0;
     for (;;) {
         const long long c_it = WAVE ? wall_clock64() : 0;
-        long long c_a = wall_clock64();""")
+        long long c_a = wall_clock64();
+        const bool ph_on = G.turn >= iago_game_phase_from; // (thread 0: the workgroup's first game)""")
     for i, anchor in enumerate(("        const long long c_desc = WAVE ? wall_clock64() : 0;\n",
                                 "        const CtlWords c = read_ctl(S, I.tid);\n",
                                 "        const bool rolled = rollout_passes(",
                                 "        // the leaf's value is at hand (stored or from the table)",
                                 "        const bool stop = iteration_end(")):
-        s = patch(s, anchor, "        { const long long c = wall_clock64(); ph[%d] += c - c_a; c_a = c; }\n" % i + anchor)
+        s = patch(s, anchor, "        { const long long c = wall_clock64(); ph[%d] += ph_on ? c - c_a : 0; c_a = c; }\n" % i + anchor)
     s = patch(s, """        if (!__syncthreads_or(busy)) {
             if (I.tid == 0)
-                sh.wg_count[1]++;""", """        { const long long c = wall_clock64(); ph[5] += c - c_a; c_a = c; }
+                sh.wg_count[1]++;""", """        { const long long c = wall_clock64(); ph[5] += ph_on ? c - c_a : 0; c_a = c; ph_it += ph_on ? 1 : 0; }
         if (!__syncthreads_or(busy)) {
             if (I.tid == 0)
                 sh.wg_count[1]++;""")
     s = patch(s, """    epilogue<WAVE>(S, I, sh, G, st_levels, st_children, t0);""", """    if (I.tid == 0 && blockIdx.x == 0) {
         for (int i = 0; i < 6; i++)
             atomicAdd(&iago_game_phases[i], (unsigned long long)ph[i]);
-        atomicAdd(&iago_game_phases[7], (unsigned long long)sh.wg_count[0]);
+        atomicAdd(&iago_game_phases[7], (unsigned long long)ph_it);
     }
     epilogue<WAVE>(S, I, sh, G, st_levels, st_children, t0);""")
     s += """
@@ -87,6 +91,10 @@ extern "C" __attribute__((visibility("default"))) int iago_debug_game_phases(uns
             return -1;
     }
     return 0;
+}
+extern "C" __attribute__((visibility("default"))) int iago_debug_game_phases_from(int turn)
+{
+    return hipMemcpyToSymbol(HIP_SYMBOL(iago_game_phase_from), &turn, sizeof(int)) == hipSuccess ? 0 : -1;
 }
 """
     return s
