@@ -34,7 +34,9 @@
 #include "sample_dev.hpp"
 #include "../../include/iago_hip_serving.h"
 
+#include <algorithm>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -1679,9 +1681,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
 }
 
-} // namespace
-
-namespace {
 constexpr int search_lds() { return SEARCH_IMG_TOP + iago_trunk::W1_LDS + iago_policy::W1_LDS + iago_trunk::HEAD_W_LDS + 192 * 4; }
 
 // (iago_mcts_search_streams_create: one launch per masked stream of a kernel that needs more scratch memory per lane than
@@ -1698,34 +1697,77 @@ __global__ void search_scratch_warm_kernel(uint32_t *out, int n)
     if (n == 0x7fffffff && out)
         out[0] = sum;
 }
+
+// The kernels a search can be launched as, and what the runtime has said of each.  It is asked once per device (a
+// process may drive several): every launch comes through here.
+enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, N_FORMS };
+
+struct FormCache {
+    const void *kernel;
+    std::atomic<uint64_t> reserved{0}; // devices on which its dynamic LDS is reserved (iago_reserve_lds's bits)
+    int static_lds = -1;               // bytes; -1 = not asked yet
+    struct {
+        int lds = -1, per_cu = 0, cus = 0; // workgroups per CU at `lds` bytes of dynamic LDS (-1 = not asked yet); the
+    } on[64];                              // device's CUs, where a caller counts them too (0 = not asked yet)
+} form_cache[N_FORMS] = {{(const void *)search_kernel},      {(const void *)search_wave_kernel},
+                         {(const void *)search_park_kernel}, {(const void *)search_game_kernel},
+                         {(const void *)search_game_park_kernel}, {(const void *)search_net_kernel},
+                         {(const void *)search_arena_kernel}};
+std::mutex form_cache_mutex; // (static_lds and on[]; `reserved` is iago_reserve_lds's own)
+
+// reserves `bytes` of dynamic LDS for the form on the current device; `who`: the message of a failure
+int reserve_lds(Form f, int bytes, const char *who) { return iago_reserve_lds(form_cache[f].kernel, bytes, form_cache[f].reserved, who); }
+
+// the form's static LDS; false: the runtime does not answer
+bool static_lds_of(Form f, int &bytes)
+{
+    std::lock_guard<std::mutex> lock(form_cache_mutex);
+    hipFuncAttributes fa;
+    if (form_cache[f].static_lds < 0 && hipFuncGetAttributes(&fa, form_cache[f].kernel) == hipSuccess)
+        form_cache[f].static_lds = (int)fa.sharedSizeBytes;
+    bytes = form_cache[f].static_lds;
+    return bytes >= 0;
+}
+
+// the form's workgroups per CU of device `dev` at `lds` bytes of dynamic LDS, and the device's CUs where `cus` is given;
+// false: the device does not answer.  One answer is kept per device: that for the LDS size asked about last
+bool residency_of(Form f, int dev, int lds, int &per_cu, int *cus)
+{
+    std::lock_guard<std::mutex> lock(form_cache_mutex);
+    auto &r = form_cache[f].on[dev & 63];
+    if (cus && r.cus < 1 && hipDeviceGetAttribute(&r.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+        r.cus = 0;
+        return false;
+    }
+    if (r.lds != lds) {
+        r.lds = -1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.per_cu, form_cache[f].kernel, 256, (size_t)lds) != hipSuccess)
+            return false;
+        r.lds = lds;
+    }
+    per_cu = r.per_cu;
+    if (cus)
+        *cus = r.cus;
+    return true;
+}
+
 } // namespace
 
 extern "C" int iago_mcts_search_capacity(int32_t *cus, int32_t *workgroups_per_cu)
 {
     if (!cus || !workgroups_per_cu)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_capacity: null pointer");
-    static std::atomic<uint64_t> configured{0};
-    if (iago_reserve_lds((const void *)search_kernel, search_lds(), configured,
-                         "iago_mcts_search_capacity: cannot reserve the nets' LDS image"))
+    if (reserve_lds(F_SINGLE, search_lds(), "iago_mcts_search_capacity: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
-    // (asked of the runtime once per device: every launch comes through here)
-    static std::atomic<int32_t> known[64]; // cus << 8 | workgroups per CU, 0 = not asked yet
-    int dev = 0;
+    int dev = 0, n_cu = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_capacity: hipGetDevice failed");
-    int32_t k = known[dev & 63].load(std::memory_order_acquire);
-    if (k == 0) {
-        int n_cu = 0, per = 0;
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)search_kernel, 256, (size_t)search_lds()) != hipSuccess)
-            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_capacity: the device does not answer");
-        if (n_cu < 1 || per < 1 || per > 255)
-            return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_capacity: the search kernel does not fit a CU of this device");
-        k = (int32_t)(n_cu << 8 | per);
-        known[dev & 63].store(k, std::memory_order_release);
-    }
-    *cus = k >> 8;
-    *workgroups_per_cu = k & 255;
+    if (!residency_of(F_SINGLE, dev, search_lds(), per, &n_cu))
+        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_capacity: the device does not answer");
+    if (n_cu < 1 || per < 1 || per > 255)
+        return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_capacity: the search kernel does not fit a CU of this device");
+    *cus = n_cu;
+    *workgroups_per_cu = per;
     return IAGO_OK;
 }
 
@@ -1739,6 +1781,15 @@ struct iago_search_streams {
 };
 
 namespace {
+// What an entry point asks of a launch beyond iago_mcts_search_args.  The default is the plain search.
+struct LaunchRequest {
+    iago_search_streams *streams = nullptr;       // the role split's two launches on these
+    const iago_search_wave_args *wave = nullptr;  // the wave search
+    const iago_search_park_args *park = nullptr;  // whole games handed over at park_empties
+    int explore_turns = 0;                        // turns whose moves are drawn from the visit counts
+    int cap_fast = 0, cap_full_256 = 256;         // the playout cap: playouts of a fast turn, full turns in 256
+};
+
 // games_per_workgroup without its flag (IAGO_SEARCH_CHAIN_SKIP)
 int games_per_wg_of(const iago_mcts_search_args *a)
 {
@@ -1797,27 +1848,49 @@ int check_args(const iago_mcts_search_args *a, const iago_search_wave_args *wv)
 
 struct SearchGrid {
     int gpw;                                 // games (a wave search: slots) per game workgroup
+    int chain_skip;                          // IAGO_SEARCH_CHAIN_SKIP of games_per_workgroup
     int64_t n_slots, n_game_wgs, net_wgs, grid;
     int path_lds_cap, game_lds;              // the games' paths in dynamic LDS: bytes a workgroup may use; the game launch's
 };
+
+// the games' side of a grid: slots, game workgroups, and the games' recorded paths in the launch's dynamic LDS when
+// they fit there (else in the caller's array)
+void size_games(const iago_mcts_search_args *a, const iago_search_wave_args *wv, SearchGrid &G)
+{
+    G.gpw = wv || games_per_wg_of(a) <= 0 ? GAMES_PER_WG : games_per_wg_of(a);
+    // (the wave search's descent keeps its in-flight counts per node and walks every level)
+    G.chain_skip = (!wv && a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_CHAIN_SKIP)) ? 1 : 0;
+    G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
+    G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
+    G.path_lds_cap = SEARCH_IMG_TOP;
+    G.game_lds = 0;
+}
+
+// the CUs a launch may count on: max_cus where it is positive and smaller, else the device's
+int cus_to_count_on(int max_cus, int cus) { return max_cus > 0 && max_cus < cus ? max_cus : cus; }
+
+// the nets of a set walk the rows of its wg_own / wg_opp, four per workgroup of the launch's grid; `msg`: the refusal
+int check_net_rows(const iago_mcts_search_args *a, int64_t grid, const char *msg)
+{
+    if (a->value->n < 4 * grid || a->policy->n < 4 * grid || a->value->planes || a->value->index || a->value->n_dev ||
+        a->policy->index || a->policy->n_dev || !a->value->own || a->value->own != a->wg_own ||
+        a->value->opp != a->wg_opp || a->policy->own != a->wg_own || a->policy->opp != a->wg_opp)
+        return iago_fail(IAGO_ERR_INVALID, msg);
+    return IAGO_OK;
+}
 
 // The grid follows the device: every game workgroup must be resident together with at least one net workgroup (a game
 // waits for replies only net workgroups give), and a net workgroup beyond what fits would only start when another one
 // ends -- at the end of the launch.  Resident workgroups = CUs the launch may count on (max_cus, else the device's) x
 // workgroups of this kernel per CU (its registers and LDS allow one).
-int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iago_search_wave_args *wv, bool park, SearchGrid &G)
+int size_grid(const iago_mcts_search_args *a, const LaunchRequest &q, SearchGrid &G)
 {
-    G.gpw = wv ? GAMES_PER_WG : games_per_wg_of(a) > 0 ? games_per_wg_of(a) : GAMES_PER_WG;
-    G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
-    G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
+    size_games(a, q.wave, G);
     int32_t cus = 0, per_cu = 0;
     if (const int rc = iago_mcts_search_capacity(&cus, &per_cu))
         return rc;
-    int64_t resident = (int64_t)(a->max_cus > 0 && a->max_cus < cus ? a->max_cus : cus) * per_cu;
-    // the games' recorded paths in the launch's dynamic LDS when they fit there (else in the caller's array)
-    G.path_lds_cap = SEARCH_IMG_TOP;
-    G.game_lds = 0;
-    if (sp) {
+    int64_t resident = (int64_t)cus_to_count_on(a->max_cus, cus) * per_cu;
+    if (const iago_search_streams *sp = q.streams) {
         // Role split: the game launch has sp->game_cus CUs of its own and the net launch all the others.  A game
         // workgroup keeps its paths in LDS when TWO workgroups with them fit a CU (else in the caller's array)
         int dev = 0;
@@ -1825,37 +1898,17 @@ int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iag
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: the streams belong to another device");
         if (a->max_cus != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
+        const Form game = q.park ? F_GAME_PARK : F_GAME; // (park: the game launch's other instantiation, with books of its own)
         const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
-        // (asked of the runtime once per device and LDS size: every launch comes through here)
-        // (park: the game launch's other instantiation, with books of its own)
-        const void *game_kernel = park ? (const void *)search_game_park_kernel : (const void *)search_game_kernel;
-        static std::atomic<int32_t> static_lds_of[2] = {{-1}, {-1}};
-        std::atomic<int32_t> &static_lds = static_lds_of[park ? 1 : 0];
-        int32_t fixed = static_lds.load(std::memory_order_acquire);
-        if (fixed < 0) {
-            hipFuncAttributes fa;
-            if (hipFuncGetAttributes(&fa, game_kernel) != hipSuccess)
-                return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: hipFuncGetAttributes failed");
-            fixed = (int32_t)fa.sharedSizeBytes;
-            static_lds.store(fixed, std::memory_order_release);
-        }
+        int fixed = 0, per_game = 0;
+        if (!static_lds_of(game, fixed))
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: hipFuncGetAttributes failed");
         G.game_lds = (want + (size_t)fixed + 256u) * 2u <= (size_t)160 * 1024u ? (int)want : 0;
         G.path_lds_cap = G.game_lds;
-        static std::atomic<uint64_t> configured_game_of[2] = {{0}, {0}};
-        if (G.game_lds && iago_reserve_lds(game_kernel, 96 * 1024, configured_game_of[park ? 1 : 0],
-                                           "iago_mcts_search_split: cannot reserve the game workgroups' LDS"))
+        if (G.game_lds && reserve_lds(game, 96 * 1024, "iago_mcts_search_split: cannot reserve the game workgroups' LDS"))
             return IAGO_ERR_HIP;
-        static std::atomic<uint64_t> occ_known_of[2][64]; // per device: LDS bytes << 8 | workgroups per CU (+ 1 << 63: valid)
-        std::atomic<uint64_t> *occ_known = occ_known_of[park ? 1 : 0];
-        int per_game = 0;
-        const uint64_t seen = occ_known[dev & 63].load(std::memory_order_acquire);
-        if ((seen >> 63) && ((seen >> 8) & 0xFFFFFFull) == (uint64_t)G.game_lds) {
-            per_game = (int)(seen & 0xFF);
-        } else {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_game, game_kernel, 256, (size_t)G.game_lds) != hipSuccess)
-                return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: the device does not answer");
-            occ_known[dev & 63].store((1ull << 63) | ((uint64_t)G.game_lds << 8) | (uint64_t)(per_game & 0xFF), std::memory_order_release);
-        }
+        if (!residency_of(game, dev, G.game_lds, per_game, nullptr))
+            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: the device does not answer");
         if (G.n_game_wgs > (int64_t)sp->game_cus * per_game)
             return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_split: the game workgroups do not fit the game launch's CUs "
                                                 "(more game CUs, fewer games per launch, or the single launch)");
@@ -1870,20 +1923,17 @@ int size_grid(const iago_mcts_search_args *a, iago_search_streams *sp, const iag
     if (G.n_game_wgs + 1 > resident)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_persistent: the game workgroups and one net workgroup do not "
                                             "fit the device together (fewer games per launch, or the per-playout launches)");
-    G.net_wgs = a->net_workgroups < resident - G.n_game_wgs ? a->net_workgroups : resident - G.n_game_wgs;
+    G.net_wgs = std::min<int64_t>(a->net_workgroups, resident - G.n_game_wgs);
     G.grid = G.n_game_wgs + G.net_wgs;
-    if (a->value->n < 4 * G.grid || a->policy->n < 4 * G.grid || a->value->planes || a->value->index || a->value->n_dev ||
-        a->policy->index || a->policy->n_dev || !a->value->own || a->value->own != a->wg_own ||
-        a->value->opp != a->wg_opp || a->policy->own != a->wg_own || a->policy->opp != a->wg_opp)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_persistent: the nets read their rows from wg_own / wg_opp "
-                                           "(four rows per workgroup of the grid: n >= 4 x (game + net workgroups)), no gather list, no "
-                                           "device count");
-    return IAGO_OK;
+    return check_net_rows(a, G.grid, "iago_mcts_search_persistent: the nets read their rows from wg_own / wg_opp "
+                                     "(four rows per workgroup of the grid: n >= 4 x (game + net workgroups)), no gather list, no "
+                                     "device count");
 }
 
-// the kernels' parameters: the arguments, the grid, the tuning knobs of the environment
-SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, const iago_search_wave_args *wv)
+// the kernels' parameters: the arguments, the grid, the request, the tuning knobs of the environment
+SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, const LaunchRequest &q)
 {
+    const iago_search_wave_args *wv = q.wave;
     SearchParams S;
     S.T = *a->tree;
     S.root_own = a->root_own;
@@ -1964,15 +2014,14 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.vtable_mask = a->vtable_slots > 0 ? (uint32_t)(a->vtable_slots - 1) : 0u;
     S.trace = a->trace_rows > 0 ? a->trace : nullptr;
     S.trace_rows = a->trace_rows;
-    S.park_empties = -1;
-    S.parked = nullptr;
-    S.park_stones = nullptr;
-    S.park_pass = nullptr;
-    S.explore_turns = 0;
-    S.cap_fast = 0;
-    S.cap_full_256 = 256;
-    // (the wave search's descent keeps its in-flight counts per node and walks every level)
-    S.chain_skip = (!wv && a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_CHAIN_SKIP)) ? 1 : 0;
+    S.park_empties = q.park ? q.park->park_empties : -1;
+    S.parked = q.park ? q.park->parked : nullptr;
+    S.park_stones = q.park ? q.park->stones : nullptr;
+    S.park_pass = q.park ? q.park->pass_flg : nullptr;
+    S.explore_turns = q.explore_turns;
+    S.cap_fast = q.cap_fast;
+    S.cap_full_256 = q.cap_full_256;
+    S.chain_skip = G.chain_skip;
     return S;
 }
 
@@ -2005,53 +2054,46 @@ int zero_polled(const iago_mcts_search_args *a, int64_t n_slots, void *stream)
 }
 
 // the zeroing of the polled words and the launch: one kernel, or the role split's two on their masked streams
-int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp, const iago_search_wave_args *wv,
-                  bool park, const SearchGrid &G, const SearchParams &S)
+int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequest &q, const SearchGrid &G, const SearchParams &S)
 {
     iago_trunk::TrunkRParams VP;
     iago_policy::PolicyParams PP;
     iago_row::HwParams R;
     if (const int rc = net_params(a, VP, PP, R))
         return rc;
-    constexpr int lds = search_lds(); // (reserved for the kernel by iago_mcts_search_capacity)
+    constexpr int lds = search_lds();
     if (const int rc = zero_polled(a, G.n_slots, stream))
         return rc;
-    if (wv) {
-        static std::atomic<uint64_t> configured_wave{0};
-        if (iago_reserve_lds((const void *)search_wave_kernel, lds, configured_wave,
-                             "iago_mcts_search_wave: cannot reserve the nets' LDS image"))
-            return IAGO_ERR_HIP;
-        hipLaunchKernelGGL(search_wave_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
-        return iago_check_launch("iago_mcts_search_wave");
-    }
-    if (!sp && park) {
-        static std::atomic<uint64_t> configured_park{0};
-        if (iago_reserve_lds((const void *)search_park_kernel, lds, configured_park,
-                             "iago_mcts_search_park: cannot reserve the nets' LDS image"))
-            return IAGO_ERR_HIP;
-        hipLaunchKernelGGL(search_park_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
-        return iago_check_launch("iago_mcts_search_park");
-    }
+    const dim3 grid((unsigned)G.grid), block(256);
+    iago_search_streams *const sp = q.streams;
     if (!sp) {
-        hipLaunchKernelGGL(search_kernel, dim3((unsigned)G.grid), dim3(256), lds, (hipStream_t)stream, S, R, VP, PP);
-        return iago_check_launch("iago_mcts_search_persistent");
+        const Form f = q.wave ? F_WAVE : q.park ? F_PARK : F_SINGLE;
+        const char *const who = q.wave ? "iago_mcts_search_wave" : q.park ? "iago_mcts_search_park" : "iago_mcts_search_persistent";
+        // (the search kernel's LDS: reserved by iago_mcts_search_capacity)
+        if (f != F_SINGLE && reserve_lds(f, lds, q.wave ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
+                                                        : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
+            return IAGO_ERR_HIP;
+        switch (f) {
+        case F_WAVE: hipLaunchKernelGGL(search_wave_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
+        case F_PARK: hipLaunchKernelGGL(search_park_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
+        default: hipLaunchKernelGGL(search_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
+        }
+        return iago_check_launch(who);
     }
     // both launches after everything queued on the caller's stream so far (the zeroing above included), the caller's
     // stream after both.  The game launch first: the net workgroups leave when the game workgroups have finished
-    static std::atomic<uint64_t> configured_net{0};
-    if (iago_reserve_lds((const void *)search_net_kernel, lds, configured_net,
-                         "iago_mcts_search_split: cannot reserve the nets' LDS image"))
+    if (reserve_lds(F_NET, lds, "iago_mcts_search_split: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    if (park)
-        hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
+    if (q.park)
+        hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
     else
-        hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), dim3(256), G.game_lds, sp->game, S, R);
+        hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
     int rc = iago_check_launch("iago_mcts_search_split (game launch)");
     if (rc == IAGO_OK) {
-        hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)G.net_wgs), dim3(256), lds, sp->net, S, VP, PP);
+        hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)G.net_wgs), block, lds, sp->net, S, VP, PP);
         rc = iago_check_launch("iago_mcts_search_split (net launch)");
     }
     // (also after a failed launch: whatever did start is waited for by the caller's stream)
@@ -2062,30 +2104,20 @@ int launch_search(const iago_mcts_search_args *a, void *stream, iago_search_stre
     return rc;
 }
 
-int search_launch(const iago_mcts_search_args *a, void *stream, iago_search_streams *sp,
-                  const iago_search_wave_args *wv = nullptr, const iago_search_park_args *pk = nullptr, int explore_turns = 0,
-                  int cap_fast = 0, int cap_full_256 = 256)
+// every launch but the arena's: the checks, the grid, the parameters, the launch
+int search_launch(const iago_mcts_search_args *a, void *stream, const LaunchRequest &q)
 {
     SearchGrid G;
-    if (const int rc = check_args(a, wv))
+    if (const int rc = check_args(a, q.wave))
         return rc;
-    if (const int rc = size_grid(a, sp, wv, pk != nullptr, G))
+    if (const int rc = size_grid(a, q, G))
         return rc;
-    SearchParams S = search_params(a, G, wv);
-    S.explore_turns = explore_turns;
-    S.cap_fast = cap_fast;
-    S.cap_full_256 = cap_full_256;
-    if (pk) {
-        S.park_empties = pk->park_empties;
-        S.parked = pk->parked;
-        S.park_stones = pk->stones;
-        S.park_pass = pk->pass_flg;
-        if (hipMemsetAsync(pk->parked, 0, (size_t)S.games_total, (hipStream_t)stream) != hipSuccess) {
-            (void)hipGetLastError();
-            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_park: clearing parked");
-        }
+    const SearchParams S = search_params(a, G, q);
+    if (q.park && hipMemsetAsync(q.park->parked, 0, (size_t)S.games_total, (hipStream_t)stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_park: clearing parked");
     }
-    return launch_search(a, stream, sp, wv, pk != nullptr, G, S);
+    return launch_search(a, stream, q, G, S);
 }
 
 // (iago_mcts_search_park) whether `active` [n] holds a match's codes: read where it lies -- host memory as it is, device
@@ -2130,79 +2162,46 @@ int self_play_only(const iago_mcts_search_args *a, void *stream, const char *who
     return IAGO_OK;
 }
 
+// the reserved fields of an option struct
+int check_reserved(const int64_t (&reserved)[4], int32_t reserved0, const char *who)
+{
+    for (int i = 0; i < 4; i++)
+        if (reserved[i] != 0 || reserved0 != 0)
+            return iago_fail(IAGO_ERR_INVALID, (std::string(who) + ": reserved fields must be 0").c_str());
+    return IAGO_OK;
+}
+
 // the hand-over's own arguments
 int check_park(const iago_search_park_args *pk, const char *who)
 {
     const std::string w(who);
     if (!pk->parked || !pk->stones || !pk->pass_flg)
         return iago_fail(IAGO_ERR_INVALID, (w + ": parked, stones and pass_flg expected").c_str());
-    for (int i = 0; i < 4; i++)
-        if (pk->reserved[i] != 0 || pk->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, (w + ": reserved fields must be 0").c_str());
+    if (const int rc = check_reserved(pk->reserved, pk->reserved0, who))
+        return rc;
     if (pk->park_empties < 0 || pk->park_empties > IAGO_ENDGAME_MAX_EMPTIES)
         return iago_fail(IAGO_ERR_INVALID, (w + ": park_empties must be in [0, 20]").c_str());
     return IAGO_OK;
 }
-} // namespace
 
-extern "C" int iago_mcts_search_park(const iago_mcts_search_args *a, const iago_search_park_args *pk, void *stream)
+// iago_mcts_search_explore and iago_mcts_search_cap from the options they share on: explore_turns, a hand-over on the
+// same streams, self-play games only (`why`), the launch
+int explore_launch(const iago_mcts_search_args *a, void *stream, const LaunchRequest &q, const char *who, const char *why)
 {
-    if (!a || !pk)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: null args");
-    if (const int rc = check_park(pk, "iago_mcts_search_park"))
-        return rc;
-    if (const int rc = self_play_only(a, stream, "iago_mcts_search_park",
-                                      "a match's policy side needs the net workgroups to its last move"))
-        return rc;
-    return search_launch(a, stream, pk->streams, nullptr, pk);
-}
-
-extern "C" int iago_mcts_search_explore(const iago_mcts_search_args *a, const iago_search_explore_args *ex, void *stream)
-{
-    if (!a || !ex)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: null args");
-    for (int i = 0; i < 4; i++)
-        if (ex->reserved[i] != 0 || ex->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: reserved fields must be 0");
-    if (ex->explore_turns < 0 || ex->explore_turns > IAGO_MAX_TURNS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: explore_turns must be in [0, 128]");
-    if (ex->park) {
-        if (const int rc = check_park(ex->park, "iago_mcts_search_explore (park)"))
+    const std::string w(who);
+    if (q.explore_turns < 0 || q.explore_turns > IAGO_MAX_TURNS)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": explore_turns must be in [0, 128]").c_str());
+    if (q.park) {
+        if (const int rc = check_park(q.park, (w + " (park)").c_str()))
             return rc;
-        if (ex->park->streams && ex->park->streams != ex->streams)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore (park): park->streams must be NULL or `streams`");
+        if (q.park->streams && q.park->streams != q.streams)
+            return iago_fail(IAGO_ERR_INVALID, (w + " (park): park->streams must be NULL or `streams`").c_str());
     }
-    if (const int rc = self_play_only(a, stream, "iago_mcts_search_explore",
-                                      "a match's moves are not drawn from the visit counts"))
+    if (const int rc = self_play_only(a, stream, who, why))
         return rc;
-    return search_launch(a, stream, ex->streams, nullptr, ex->park, ex->explore_turns);
+    return search_launch(a, stream, q);
 }
 
-extern "C" int iago_mcts_search_cap(const iago_mcts_search_args *a, const iago_search_cap_args *cap, void *stream)
-{
-    if (!a || !cap)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: null args");
-    for (int i = 0; i < 4; i++)
-        if (cap->reserved[i] != 0 || cap->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: reserved fields must be 0");
-    if (cap->n_fast < 1 || cap->n_fast > a->n_sims)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: n_fast must be in [1, n_sims]");
-    if (cap->full_per_256 < 1 || cap->full_per_256 > 256)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: full_per_256 must be in [1, 256]");
-    if (cap->explore_turns < 0 || cap->explore_turns > IAGO_MAX_TURNS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: explore_turns must be in [0, 128]");
-    if (cap->park) {
-        if (const int rc = check_park(cap->park, "iago_mcts_search_cap (park)"))
-            return rc;
-        if (cap->park->streams && cap->park->streams != cap->streams)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap (park): park->streams must be NULL or `streams`");
-    }
-    if (const int rc = self_play_only(a, stream, "iago_mcts_search_cap", "a match's searches are not capped"))
-        return rc;
-    return search_launch(a, stream, cap->streams, nullptr, cap->park, cap->explore_turns, cap->n_fast, cap->full_per_256);
-}
-
-namespace {
 // the arena's sets share nothing a search writes: two pointers that are the same array
 bool arena_shared(const iago_mcts_search_args *a, const iago_mcts_search_args *b)
 {
@@ -2220,6 +2219,85 @@ bool arena_shared(const iago_mcts_search_args *a, const iago_mcts_search_args *b
 }
 } // namespace
 
+extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)
+{
+    return search_launch(a, stream, LaunchRequest());
+}
+
+extern "C" int iago_mcts_search_split(const iago_mcts_search_args *a, iago_search_streams *streams, void *stream)
+{
+    if (!streams)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: null streams");
+    LaunchRequest q;
+    q.streams = streams;
+    return search_launch(a, stream, q);
+}
+
+extern "C" int iago_mcts_search_wave(const iago_mcts_search_args *a, const iago_search_wave_args *w, void *stream)
+{
+    if (!a || !w)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: null args");
+    if (w->width != 1 && w->width != 8 && w->width != 16 && w->width != 32)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: width is 1, 8, 16 or 32");
+    if (!(w->vloss >= 0.0f && w->vloss <= 3.4028235e38f))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: vloss >= 0 (finite) expected");
+    if (a->max_turns != 0 || a->games_total != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: one search per launch (max_turns 0, games_total 0): "
+                                           "whole games take iago_mcts_search_persistent");
+    LaunchRequest q;
+    q.wave = w;
+    return search_launch(a, stream, q);
+}
+
+extern "C" int iago_mcts_search_park(const iago_mcts_search_args *a, const iago_search_park_args *pk, void *stream)
+{
+    if (!a || !pk)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_park: null args");
+    if (const int rc = check_park(pk, "iago_mcts_search_park"))
+        return rc;
+    if (const int rc = self_play_only(a, stream, "iago_mcts_search_park",
+                                      "a match's policy side needs the net workgroups to its last move"))
+        return rc;
+    LaunchRequest q;
+    q.streams = pk->streams;
+    q.park = pk;
+    return search_launch(a, stream, q);
+}
+
+extern "C" int iago_mcts_search_explore(const iago_mcts_search_args *a, const iago_search_explore_args *ex, void *stream)
+{
+    if (!a || !ex)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_explore: null args");
+    if (const int rc = check_reserved(ex->reserved, ex->reserved0, "iago_mcts_search_explore"))
+        return rc;
+    LaunchRequest q;
+    q.streams = ex->streams;
+    q.park = ex->park;
+    q.explore_turns = ex->explore_turns;
+    return explore_launch(a, stream, q, "iago_mcts_search_explore", "a match's moves are not drawn from the visit counts");
+}
+
+extern "C" int iago_mcts_search_cap(const iago_mcts_search_args *a, const iago_search_cap_args *cap, void *stream)
+{
+    if (!a || !cap)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: null args");
+    if (const int rc = check_reserved(cap->reserved, cap->reserved0, "iago_mcts_search_cap"))
+        return rc;
+    if (cap->n_fast < 1 || cap->n_fast > a->n_sims)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: n_fast must be in [1, n_sims]");
+    if (cap->full_per_256 < 1 || cap->full_per_256 > 256)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_cap: full_per_256 must be in [1, 256]");
+    LaunchRequest q;
+    q.streams = cap->streams;
+    q.park = cap->park;
+    q.explore_turns = cap->explore_turns;
+    q.cap_fast = cap->n_fast;
+    q.cap_full_256 = cap->full_per_256;
+    return explore_launch(a, stream, q, "iago_mcts_search_cap", "a match's searches are not capped");
+}
+
+// The arena's own rules: two sets that share nothing, no match codes, one clock, and for both agents the rows of the
+// WHOLE grid (any workgroup may walk either agent's nets).  The grid is the single search's, summed over the two sets.
 extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago_mcts_search_args *b, void *stream)
 {
     if (!a || !b)
@@ -2243,62 +2321,45 @@ extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago
     const int want = a->net_workgroups > b->net_workgroups ? a->net_workgroups : b->net_workgroups;
     if (want < 2)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: net_workgroups >= 2 expected (a server per agent)");
-    SearchGrid G[2];
+    // the device's CUs are the search kernel's answer, the workgroups per CU the arena kernel's own
     int32_t cus = 0, per_cu = 0;
     if (const int rc = iago_mcts_search_capacity(&cus, &per_cu))
         return rc;
     constexpr int lds = search_lds();
-    static std::atomic<uint64_t> configured_arena{0};
-    if (iago_reserve_lds((const void *)search_arena_kernel, lds, configured_arena,
-                         "iago_mcts_search_arena: cannot reserve the nets' LDS image"))
+    if (reserve_lds(F_ARENA, lds, "iago_mcts_search_arena: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
-    // (the arena kernel's own workgroups per CU, asked of the runtime once per device)
-    static std::atomic<int32_t> per_known[64];
-    int dev = 0;
+    int dev = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: hipGetDevice failed");
-    int per = per_known[dev & 63].load(std::memory_order_acquire);
-    if (per == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)search_arena_kernel, 256, (size_t)lds) != hipSuccess)
-            return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: the device does not answer");
-        if (per < 1)
-            return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: the arena kernel does not fit a CU of this device");
-        per_known[dev & 63].store(per, std::memory_order_release);
-    }
-    // the CUs the launch may count on: the smaller positive max_cus of the two sets, else the device's
-    int64_t use_cus = cus;
-    for (int i = 0; i < 2; i++)
-        if (set[i]->max_cus > 0 && set[i]->max_cus < use_cus)
-            use_cus = set[i]->max_cus;
-    const int64_t resident = use_cus * per;
+    if (!residency_of(F_ARENA, dev, lds, per, nullptr))
+        return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: the device does not answer");
+    if (per < 1)
+        return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: the arena kernel does not fit a CU of this device");
+    // (the CUs the launch may count on: the smaller positive max_cus of the two sets, else the device's)
+    const int64_t resident = (int64_t)cus_to_count_on(b->max_cus, cus_to_count_on(a->max_cus, cus)) * per;
+    SearchGrid G[2];
     int64_t games = 0;
     for (int i = 0; i < 2; i++) {
-        G[i].gpw = games_per_wg_of(set[i]) > 0 ? games_per_wg_of(set[i]) : GAMES_PER_WG;
-        G[i].n_slots = set[i]->tree->n_games;
-        G[i].n_game_wgs = (G[i].n_slots + G[i].gpw - 1) / G[i].gpw;
-        G[i].path_lds_cap = SEARCH_IMG_TOP;
-        G[i].game_lds = 0;
+        size_games(set[i], nullptr, G[i]);
         games += G[i].n_game_wgs;
     }
     if (games + 2 > resident)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: both agents' game workgroups and two net workgroups do "
                                             "not fit the device together (fewer games per launch, or one search after the other)");
-    const int64_t net_wgs = want < resident - games ? want : resident - games;
+    const int64_t net_wgs = std::min<int64_t>(want, resident - games);
     const int64_t grid = games + net_wgs;
     ArenaArgs args;
     ArenaSet *const P = args.set;
     for (int i = 0; i < 2; i++) {
-        const iago_mcts_search_args *x = set[i];
         G[i].net_wgs = net_wgs;
         G[i].grid = grid;
-        if (x->value->n < 4 * grid || x->policy->n < 4 * grid || x->value->planes || x->value->index || x->value->n_dev ||
-            x->policy->index || x->policy->n_dev || !x->value->own || x->value->own != x->wg_own ||
-            x->value->opp != x->wg_opp || x->policy->own != x->wg_own || x->policy->opp != x->wg_opp)
-            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_arena: each agent's nets read their rows from its wg_own / "
-                                               "wg_opp (four rows per workgroup of the WHOLE grid: n >= 4 x (both agents' game "
-                                               "workgroups + net workgroups)), no gather list, no device count");
-        P[i].S = search_params(x, G[i], nullptr);
-        if (const int rc = net_params(x, P[i].VP, P[i].PP, P[i].R))
+        if (const int rc = check_net_rows(set[i], grid,
+                                          "iago_mcts_search_arena: each agent's nets read their rows from its wg_own / "
+                                          "wg_opp (four rows per workgroup of the WHOLE grid: n >= 4 x (both agents' game "
+                                          "workgroups + net workgroups)), no gather list, no device count"))
+            return rc;
+        P[i].S = search_params(set[i], G[i], LaunchRequest());
+        if (const int rc = net_params(set[i], P[i].VP, P[i].PP, P[i].R))
             return rc;
     }
     // one clock for the launch: the larger limit; an agent that gives up says so in its own ctl and the other finishes
@@ -2310,32 +2371,6 @@ extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago
             return rc;
     hipLaunchKernelGGL(search_arena_kernel, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, args);
     return iago_check_launch("iago_mcts_search_arena");
-}
-
-extern "C" int iago_mcts_search_persistent(const iago_mcts_search_args *a, void *stream)
-{
-    return search_launch(a, stream, nullptr);
-}
-
-extern "C" int iago_mcts_search_wave(const iago_mcts_search_args *a, const iago_search_wave_args *w, void *stream)
-{
-    if (!a || !w)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: null args");
-    if (w->width != 1 && w->width != 8 && w->width != 16 && w->width != 32)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: width is 1, 8, 16 or 32");
-    if (!(w->vloss >= 0.0f && w->vloss <= 3.4028235e38f))
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: vloss >= 0 (finite) expected");
-    if (a->max_turns != 0 || a->games_total != 0)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_wave: one search per launch (max_turns 0, games_total 0): "
-                                           "whole games take iago_mcts_search_persistent");
-    return search_launch(a, stream, nullptr, w);
-}
-
-extern "C" int iago_mcts_search_split(const iago_mcts_search_args *a, iago_search_streams *streams, void *stream)
-{
-    if (!streams)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: null streams");
-    return search_launch(a, stream, streams);
 }
 
 extern "C" int iago_mcts_search_streams_create(int32_t game_cus, iago_search_streams **out)
