@@ -49,11 +49,12 @@ EXPERIMENTAL_SYMBOLS = [
 ]
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
 # the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=)),
-# playout-cap randomisation (SelfPlayEngine.play(playout_cap=))
+# playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
+    "iago_mcts_root_noise", "iago_mcts_search_noise",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -230,6 +231,9 @@ EXPLORE_KEY = 0x4558504C  # exploring self-play's draws from the visit counts: t
 EXPLORE_SEED_XOR = EXPLORE_KEY << 32
 CAP_KEY = 0x43415050      # the playout cap's full / fast decision per turn: the same, with this word (IAGO_CAP_KEY)
 CAP_SEED_XOR = CAP_KEY << 32
+NOISE_KEY = 0x44495249    # the root noise's urn draws: the same, with this word (IAGO_NOISE_KEY)
+NOISE_SEED_XOR = NOISE_KEY << 32
+NOISE_DRAWS = 256         # root_noise=(alpha_256, eps_256): the urn's draws N unless the caller gives a third number
 CTL_BAD_DRAW = 13         # ctl word a match raises when a policy draw found no mass on the legal moves
 REC_DRAWN = 2             # rec_valid of a move played without a search (a policy draw or a forced final move)
 REC_FAST = 4              # rec_valid of a searched FAST turn of the playout cap (n_fast playouts; not a policy target)
@@ -312,6 +316,21 @@ class SearchCapArgs(C.Structure):
     _fields_ = [
         ("n_fast", C.c_int32), ("full_per_256", C.c_int32), ("explore_turns", C.c_int32), ("reserved0", C.c_int32),
         ("streams", C.c_void_p), ("park", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
+class RootNoise(C.Structure):
+    """Mirror of iago_root_noise (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("alpha_256", C.c_int32), ("eps_256", C.c_int32), ("draws", C.c_int32), ("reserved0", C.c_int32),
+        ("counts", C.c_void_p),
+    ]
+
+
+class SearchNoiseArgs(C.Structure):
+    """Mirror of iago_search_noise_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("noise", RootNoise), ("streams", C.c_void_p), ("reserved", C.c_int64 * 4),
     ]
 
 
@@ -445,6 +464,8 @@ def lib():
     L.iago_mcts_draw_move.argtypes = [tp, vp, C.c_uint64, vp, vp, vp, vp, vp]
     L.iago_mcts_search_cap.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchCapArgs), vp]
     L.iago_mcts_cap_mask.argtypes = [C.c_uint64, vp, vp, i32, i64, vp, vp]
+    L.iago_mcts_root_noise.argtypes = [tp, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(RootNoise), vp]
+    L.iago_mcts_search_noise.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchNoiseArgs), vp]
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int

@@ -7,8 +7,10 @@
 #pragma once
 #include "abi_common.hpp"
 #include "othello_dev.hpp"
+#include "../../include/iago_hip_serving.h" // (iago_root_noise)
 
 #include <math.h>
+#include <string>
 
 namespace iago_mcts {
 using namespace iago;
@@ -303,6 +305,91 @@ __device__ __forceinline__ int explore_draw8(const int (&row_n)[8], uint32_t l8,
     a = min(a, dpp_u32<DPP_XOR2>(a));
     a = min(a, dpp_u32<DPP_HALF_MIRROR>(a));
     return blk == 0u ? 64 : (int)a;
+}
+
+// ---- root noise ("Root noise"; the contract is iago_hip_serving.h's): at a searched turn the priors
+// of the root's K >= 2 children are mixed with the shares of a Polya urn over the mover's legal cells, in integers.  The
+// urn: c[a] = 0; draw j = 0 .. N-1 takes the cell by explore_draw8's rule from the weights alpha_256 + 256 c[a] (their
+// total is K alpha_256 + 256 j) with word j & 3 of Philox4x32-10 on (game id, turn, j >> 2, 0) under the rollouts' key
+// with its high word XOR NOISE_KEY, and adds 1 to its c.  The counts are Dirichlet-multinomial(N, alpha_256 / 256).
+constexpr uint32_t NOISE_KEY = IAGO_NOISE_KEY; // ("DIRI")
+
+// (host) the noise's own arguments, for both entry points that take them
+inline int check_root_noise(const iago_root_noise *nz, const char *who)
+{
+    const std::string w(who);
+    if (!nz)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": null noise arguments").c_str());
+    if (nz->reserved0 != 0)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": reserved fields must be 0").c_str());
+    if (nz->alpha_256 < 1 || nz->alpha_256 > 4096)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": alpha_256 must be in [1, 4096]").c_str());
+    if (nz->eps_256 < 0 || nz->eps_256 > 256)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": eps_256 must be in [0, 256]").c_str());
+    if (nz->draws < 16 || nz->draws > 1024 || (nz->draws & (nz->draws - 1)) != 0)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": draws must be a power of two in [16, 1024]").c_str());
+    if (!nz->counts)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": null counts buffer").c_str());
+    return IAGO_OK;
+}
+
+// the urn across the 8 lanes of a game: the counts of this lane's 8 cells (8 l8 ..) after `draws` draws over the legal set
+// lg, c[i] in 0 .. draws.  Every lane of the group takes part; lg with fewer than two cells: zeros, nothing drawn (the
+// loop still runs while another game of the wave draws: `draws` is uniform)
+__device__ __forceinline__ void noise_urn8(uint64_t lg, uint32_t l8, uint32_t key0, uint32_t key1, uint32_t id, uint32_t turn,
+                                           uint32_t alpha_256, uint32_t draws, uint32_t (&c)[8])
+{
+    const bool urn = (lg & (lg - 1ull)) != 0ull;
+    const uint32_t row = urn ? (uint32_t)(lg >> (8u * l8)) & 0xFFu : 0u;
+    int wt[8]; // the weights alpha_256 + 256 c of this lane's legal cells, 0 off the legal set (< 2^20; their sum < 2^32)
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        wt[i] = ((row >> i) & 1u) ? (int)alpha_256 : 0;
+    if (__builtin_amdgcn_ballot_w64(urn) != 0ull) {
+#pragma unroll 1
+        for (uint32_t blk = 0u; blk < draws; blk += 4u) {
+            uint32_t w[4] = {id, turn, blk >> 2, 0u};
+            philox4x32_10(w, key0, key1 ^ NOISE_KEY);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t a = (uint32_t)explore_draw8(wt, l8, w[q]); // (64 where the game draws nothing: no lane's cell)
+#pragma unroll
+                for (int i = 0; i < 8; i++)
+                    wt[i] += (a == 8u * l8 + (uint32_t)i) ? 256 : 0;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        c[i] = ((row >> i) & 1u) ? ((uint32_t)wt[i] - alpha_256) >> 8 : 0u;
+}
+
+// the mix of a root child's stored prior p (what init_node wrote: prior + 0.1) with its count c: p keep + term, keep =
+// (256 - eps_256) / 256 and term = eps_256 c / (256 N) both exact in float32 (eps_256 c <= 2^18, N = 2^draws_log2), the
+// product and the sum each rounded once, as numpy rounds them
+__device__ __forceinline__ float noise_mix(float p, uint32_t c, uint32_t eps_256, uint32_t draws_log2)
+{
+#pragma clang fp contract(off)
+    const float keep = (float)(256u - eps_256) * 0.00390625f;
+    const float term = (float)(eps_256 * c) * __uint_as_float((127u - 8u - draws_log2) << 23);
+    const float kept = p * keep;
+    return kept + term;
+}
+
+// the mix on the EXISTING children of node `root` (a reused subtree: first child rfc >= 0, the children are the legal
+// moves lg in ascending cell order, two or more): lane l8 rewrites the priors of its row's cells
+__device__ __forceinline__ void noise_remix_children(const Tree &T, int64_t base, int rfc, uint64_t lg, uint32_t l8,
+                                                     const uint32_t (&c)[8], uint32_t eps_256, uint32_t draws_log2)
+{
+    uint32_t row = (uint32_t)(lg >> (8u * l8)) & 0xFFu;
+    int at = rfc + __popcll(lg & ((1ull << (8u * l8)) - 1ull));
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        if ((row >> i) & 1u) {
+            T.nodes[base + at].p = noise_mix(T.nodes[base + at].p, c[i], eps_256, draws_log2);
+            at++;
+        }
+    }
 }
 
 // Diagnostic record of the parity tests (tests/test_mcts_production_gpu.py): the z every playout of game g backed up, in

@@ -272,6 +272,39 @@ __global__ __launch_bounds__(BLOCK) void cap_mask_kernel(uint32_t key0, uint32_t
     fast[i] = cap_fast_turn(cap_word(key0, key1, (uint32_t)game_id[i], (uint32_t)turn[i]), full_per_256) ? 1 : 0;
 }
 
+// cap_mask_kernel's sibling for the root noise (iago_mcts_root_noise), 8 lanes per game: the urn's counts of turn[g] of
+// game game_id[g] over the legal moves of the root position -- mcts_dev.hpp's rule -- into the game's counts row, and the
+// mix on the children the root already has (a reused subtree).  A root that expands in the turn's search takes its row
+// there (iago_mcts_search_noise).  Inactive games: nothing written
+__global__ __launch_bounds__(BLOCK) void root_noise_kernel(Tree T, const uint8_t *__restrict__ active,
+                                                           const uint64_t *__restrict__ root_own,
+                                                           const uint64_t *__restrict__ root_opp, uint32_t key0, uint32_t key1,
+                                                           const int32_t *__restrict__ game_id, const int32_t *__restrict__ turn,
+                                                           uint32_t alpha_256, uint32_t eps_256, uint32_t draws_log2,
+                                                           uint16_t *__restrict__ counts)
+{
+    const int64_t g = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 3;
+    const Lane8 L = make_lane8(threadIdx.x);
+    const bool live = g < T.n_games && (!active || active[g] != 0);
+    const uint64_t own = live ? root_own[g] : 0ull, opp = live ? root_opp[g] : 0ull;
+    const uint64_t lg = live ? group8_legal(to_lane(own, L), to_lane(opp, L), L) : 0ull; // (own = opp = 0: no move)
+    uint32_t c[8];
+    noise_urn8(lg, L.l8, key0, key1, live ? (uint32_t)game_id[g] : 0u, live ? (uint32_t)turn[g] : 0u, alpha_256,
+               1u << draws_log2, c);
+    if (!live)
+        return;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        counts[g * 64 + (int)(8u * L.l8) + i] = (uint16_t)c[i];
+    const int64_t base = g * (int64_t)T.capacity;
+    const int root = T.root[g];
+    const int rfc = T.nodes[base + root].first_child;
+    // (the children of a root are the mover's legal moves: two or more of them, or the one Node(node, 1.0) that stays; a
+    // tree that does not belong to the position is left alone)
+    if (rfc >= 0 && (lg & (lg - 1ull)) != 0ull && (int)T.nodes[base + root].n_children == __popcll(lg))
+        noise_remix_children(T, base, rfc, lg, L.l8, c, eps_256, draws_log2);
+}
+
 __global__ __launch_bounds__(BLOCK) void advance_root_kernel(Tree T, const uint8_t *__restrict__ mask,
                                                              const int8_t *__restrict__ move)
 {
@@ -1068,6 +1101,25 @@ int iago_mcts_cap_mask(uint64_t seed, const int32_t *game_id, const int32_t *tur
     hipLaunchKernelGGL(cap_mask_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, (hipStream_t)stream, (uint32_t)seed,
                        (uint32_t)(seed >> 32), game_id, turn, (uint32_t)full_per_256, n, fast);
     return iago_check_launch("iago_mcts_cap_mask");
+}
+
+int iago_mcts_root_noise(const iago_mcts_tree *tree, const uint8_t *active, const uint64_t *root_own,
+                         const uint64_t *root_opp, uint64_t seed, const int32_t *game_id, const int32_t *turn,
+                         const iago_root_noise *noise, void *stream)
+{
+    if (check_tree(tree, "iago_mcts_root_noise: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (!root_own || !root_opp || !game_id || !turn)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_root_noise: null pointer (root_own, root_opp, game_id and turn expected)");
+    if (const int rc = check_root_noise(noise, "iago_mcts_root_noise"))
+        return rc;
+    if (tree->n_games == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(root_noise_kernel, dim3(grid_for(tree->n_games * 8)), dim3(BLOCK), 0, (hipStream_t)stream, *tree,
+                       active, root_own, root_opp, (uint32_t)seed, (uint32_t)(seed >> 32), game_id, turn,
+                       (uint32_t)noise->alpha_256, (uint32_t)noise->eps_256, (uint32_t)__builtin_ctz((uint32_t)noise->draws),
+                       noise->counts);
+    return iago_check_launch("iago_mcts_root_noise");
 }
 
 int iago_mcts_advance_root(const iago_mcts_tree *tree, const uint8_t *mask, const int8_t *move,

@@ -161,6 +161,10 @@ struct SearchParams {
     // the descent jumps over a pass chain it remembers from the game's last playout (descend; IAGO_SEARCH_CHAIN_SKIP):
     // timing only.  totals[16] then counts the levels jumped over
     int32_t chain_skip;
+    // root noise (iago_mcts_search_noise; the NOISE instantiations alone read these): eps_256, log2 of the urn's draws and
+    // the counts rows [n_games][64] that iago_mcts_root_noise wrote before the launch, read where a root expands
+    uint16_t *noise_counts;
+    int32_t noise_eps, noise_lg;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -789,6 +793,9 @@ __device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I,
 
 // Node.expand of the cursor node once it has n_thr visits (MCTS.py:109): a pass child or a single legal move without
 // a net, else with the priors -- which, when they have not arrived, the descent stops to ask for
+// NOISE: the children of the game's ROOT (the path's first node) are created with the mixed priors, from the game's counts
+// row (iago_mcts_root_noise wrote it before the launch)
+template <bool NOISE>
 __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cursor &C, bool &descending, bool have_priors,
                                        bool &need_prior)
 {
@@ -809,6 +816,15 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
                 const int nf = (int)fc1 - 1;
                 make_children(T, I.base, nf, C.node, lg, I.r,
                               [&](int a) { return __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a])); });
+                if constexpr (NOISE) {
+                    if (C.path_n == 1 && kn > 1) {
+                        uint32_t c[8];
+#pragma unroll
+                        for (int i = 0; i < 8; i++)
+                            c[i] = S.noise_counts[I.g * 64 + (int)(8u * I.r) + i];
+                        noise_remix_children(T, I.base, nf, lg, I.r, c, (uint32_t)S.noise_eps, (uint32_t)S.noise_lg);
+                    }
+                }
                 if (I.r == 0u)
                     link_children(T, I.base + C.node, nf, kn);
                 C.fc = nf;
@@ -856,7 +872,7 @@ __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I
 // ---- 4. descent (MCTS.py:105-133; the games' lanes): from the root, or on from the leaf whose priors arrived, to a node
 // that waits for its priors or to the playout's leaf.  A wave search: one step of its trees' slot order (the slot whose
 // turn it is), seeing the in-flight visits and the expansions of the slots before it.  Returns whether the game descended
-template <bool WAVE>
+template <bool WAVE, bool NOISE>
 __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, GameShared<WAVE> &sh, Game &G, Cursor &C,
                                         int pace_limit, int &st_levels, int &st_children)
 {
@@ -938,7 +954,7 @@ __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, Ga
             C.path_n++;
         }
         skip_record = false;
-        expand(S, I, C, descending, have_priors, need_prior);
+        expand<NOISE>(S, I, C, descending, have_priors, need_prior);
         have_priors = false;
         descending = descending && C.fc >= 0; // leaf reached (MCTS.py:107)
         if (__builtin_amdgcn_ballot_w64(descending) == 0ull)
@@ -1233,7 +1249,7 @@ __device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, G
     }
 }
 
-template <bool WAVE, bool PARK = false>
+template <bool WAVE, bool PARK = false, bool NOISE = false>
 __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0, const int wg)
 {
     __shared__ GameShared<WAVE> sh;
@@ -1303,7 +1319,7 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
         for (int sub = 0; sub < (WAVE ? I.W : 1); sub++) {
             bool went = false;
             if (I.mine) {
-                went = descend<WAVE>(S, I, sh, G, C, pace_limit, st_levels, st_children);
+                went = descend<WAVE, NOISE>(S, I, sh, G, C, pace_limit, st_levels, st_children);
                 busy = busy || went;
             }
             if constexpr (WAVE) {
@@ -1574,7 +1590,7 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
 // ONE grid: the game workgroups first (they are dispatched first, so all of them are resident whatever else
 // holds CUs; a net workgroup never waits for another net workgroup, so one that finds no CU free simply starts
 // late), then the net workgroups.  A game workgroup whose games are done serves the queue like the others.
-template <bool WAVE, bool PARK = false>
+template <bool WAVE, bool PARK = false, bool NOISE = false>
 __device__ __forceinline__ void search_body(const SearchParams &S, const iago_row::HwParams &R, const iago_trunk::TrunkRParams &VP,
                                             const iago_policy::PolicyParams &PP)
 {
@@ -1583,7 +1599,7 @@ __device__ __forceinline__ void search_body(const SearchParams &S, const iago_ro
     if (wg == 0 && threadIdx.x == 0) // (what the launch was given: the host sized the grid from the device)
         __hip_atomic_store(&S.ctl[CTL_NET_WGS], (uint32_t)gridDim.x - (uint32_t)S.n_game_wgs, RLX_AGENT);
     if (wg < S.n_game_wgs)
-        game_workgroup<WAVE, PARK>(S, R, t0, wg);
+        game_workgroup<WAVE, PARK, NOISE>(S, R, t0, wg);
     net_workgroup(S, VP, PP, t0, wg);
 }
 
@@ -1627,6 +1643,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                                                                                                         iago_row::HwParams R)
 {
     game_workgroup<false, true>(S, R, wall_clock64(), (int)blockIdx.x);
+}
+
+// The search with root noise (iago_mcts_search_noise: one search per launch): again instantiations of their own, for the
+// single launch and the role split's game launch.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_noise_kernel(
+    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+{
+    search_body<false, false, true>(S, R, VP, PP);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_noise_kernel(SearchParams S,
+                                                                                                         iago_row::HwParams R)
+{
+    game_workgroup<false, false, true>(S, R, wall_clock64(), (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_net_kernel(
@@ -1700,7 +1730,7 @@ __global__ void search_scratch_warm_kernel(uint32_t *out, int n)
 
 // The kernels a search can be launched as, and what the runtime has said of each.  It is asked once per device (a
 // process may drive several): every launch comes through here.
-enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, N_FORMS };
+enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, F_NOISE, F_GAME_NOISE, N_FORMS };
 
 struct FormCache {
     const void *kernel;
@@ -1712,7 +1742,8 @@ struct FormCache {
 } form_cache[N_FORMS] = {{(const void *)search_kernel},      {(const void *)search_wave_kernel},
                          {(const void *)search_park_kernel}, {(const void *)search_game_kernel},
                          {(const void *)search_game_park_kernel}, {(const void *)search_net_kernel},
-                         {(const void *)search_arena_kernel}};
+                         {(const void *)search_arena_kernel},     {(const void *)search_noise_kernel},
+                         {(const void *)search_game_noise_kernel}};
 std::mutex form_cache_mutex; // (static_lds and on[]; `reserved` is iago_reserve_lds's own)
 
 // reserves `bytes` of dynamic LDS for the form on the current device; `who`: the message of a failure
@@ -1788,6 +1819,7 @@ struct LaunchRequest {
     const iago_search_park_args *park = nullptr;  // whole games handed over at park_empties
     int explore_turns = 0;                        // turns whose moves are drawn from the visit counts
     int cap_fast = 0, cap_full_256 = 256;         // the playout cap: playouts of a fast turn, full turns in 256
+    const iago_root_noise *noise = nullptr;       // root noise: the counts rows applied where a root expands
 };
 
 // games_per_workgroup without its flag (IAGO_SEARCH_CHAIN_SKIP)
@@ -1898,7 +1930,8 @@ int size_grid(const iago_mcts_search_args *a, const LaunchRequest &q, SearchGrid
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: the streams belong to another device");
         if (a->max_cus != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
-        const Form game = q.park ? F_GAME_PARK : F_GAME; // (park: the game launch's other instantiation, with books of its own)
+        // (park, noise: the game launch's other instantiations, with books of their own)
+        const Form game = q.noise ? F_GAME_NOISE : q.park ? F_GAME_PARK : F_GAME;
         const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
         int fixed = 0, per_game = 0;
         if (!static_lds_of(game, fixed))
@@ -2022,6 +2055,9 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.cap_fast = q.cap_fast;
     S.cap_full_256 = q.cap_full_256;
     S.chain_skip = G.chain_skip;
+    S.noise_counts = q.noise ? q.noise->counts : nullptr;
+    S.noise_eps = q.noise ? q.noise->eps_256 : 0;
+    S.noise_lg = q.noise ? __builtin_ctz((unsigned)q.noise->draws) : 0;
     return S;
 }
 
@@ -2067,13 +2103,18 @@ int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequ
     const dim3 grid((unsigned)G.grid), block(256);
     iago_search_streams *const sp = q.streams;
     if (!sp) {
-        const Form f = q.wave ? F_WAVE : q.park ? F_PARK : F_SINGLE;
-        const char *const who = q.wave ? "iago_mcts_search_wave" : q.park ? "iago_mcts_search_park" : "iago_mcts_search_persistent";
+        const Form f = q.wave ? F_WAVE : q.noise ? F_NOISE : q.park ? F_PARK : F_SINGLE;
+        const char *const who = q.wave    ? "iago_mcts_search_wave"
+                                : q.noise ? "iago_mcts_search_noise"
+                                : q.park  ? "iago_mcts_search_park"
+                                          : "iago_mcts_search_persistent";
         // (the search kernel's LDS: reserved by iago_mcts_search_capacity)
-        if (f != F_SINGLE && reserve_lds(f, lds, q.wave ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
-                                                        : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
+        if (f != F_SINGLE && reserve_lds(f, lds, q.wave    ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
+                                                 : q.noise ? "iago_mcts_search_noise: cannot reserve the nets' LDS image"
+                                                           : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
             return IAGO_ERR_HIP;
         switch (f) {
+        case F_NOISE: hipLaunchKernelGGL(search_noise_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         case F_WAVE: hipLaunchKernelGGL(search_wave_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         case F_PARK: hipLaunchKernelGGL(search_park_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         default: hipLaunchKernelGGL(search_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
@@ -2087,7 +2128,9 @@ int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequ
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    if (q.park)
+    if (q.noise)
+        hipLaunchKernelGGL(search_game_noise_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
+    else if (q.park)
         hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
     else
         hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
@@ -2294,6 +2337,23 @@ extern "C" int iago_mcts_search_cap(const iago_mcts_search_args *a, const iago_s
     q.cap_fast = cap->n_fast;
     q.cap_full_256 = cap->full_per_256;
     return explore_launch(a, stream, q, "iago_mcts_search_cap", "a match's searches are not capped");
+}
+
+extern "C" int iago_mcts_search_noise(const iago_mcts_search_args *a, const iago_search_noise_args *nz, void *stream)
+{
+    if (!a || !nz)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_noise: null args");
+    if (const int rc = check_reserved(nz->reserved, 0, "iago_mcts_search_noise"))
+        return rc;
+    if (const int rc = check_root_noise(&nz->noise, "iago_mcts_search_noise"))
+        return rc;
+    if (a->max_turns != 0 || a->games_total != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_noise: one search per launch (max_turns 0, games_total 0): whole "
+                                           "games with root noise run turn by turn");
+    LaunchRequest q;
+    q.streams = nz->streams;
+    q.noise = &nz->noise;
+    return search_launch(a, stream, q);
 }
 
 // The arena's own rules: two sets that share nothing, no match codes, one clock, and for both agents the rows of the

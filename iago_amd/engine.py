@@ -40,8 +40,8 @@ _stream = ops._stream   # the current HIP stream as a void*
 
 # The rules of a batch of games beyond plain PV-MCTS, validated once (_play_rules) and handed on as ONE value:
 # solve_empties (None: off, else an int in [0, 20]), explore_turns (an int, 0: off), playout_cap (None: off, else
-# (n_fast, full_per_256)) -- as SelfPlayEngine.play documents them.
-PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap")
+# (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)) -- as SelfPlayEngine.play documents them.
+PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise", defaults=(None,))
 NO_RULES = PlayRules(None, 0, None)
 
 
@@ -1199,9 +1199,16 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _search_persistent(self, own, opp, active, n_sims, n_active):
-        """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent)."""
-        self._launch_persistent(own, opp, active, n_sims)
+    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0):
+        """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent).  root_noise = (alpha_256, eps_256,
+        draws): the urn of turn `turn` first (ops.root_noise: the counts rows, the mix on the children the roots have),
+        then the launch that applies the rows where a root expands (iago_mcts_search_noise)."""
+        if root_noise is None:
+            self._launch_persistent(own, opp, active, n_sims)
+        else:
+            ids, turns = self._turn_ids(turn)
+            ops.root_noise(self.tree.ref(), active, own, opp, self.seed, ids, turns, root_noise, self._noise_rows())
+            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, root_noise))
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
@@ -1211,8 +1218,9 @@ class BatchedMCTS(object):
         PlayRules).  park = dict(parked, stones, pass_flg), given with rules.solve_empties: those games handed over at
         that many empties (iago_mcts_search_park); rules.explore_turns: their moves of the turns below it drawn from the
         visit counts (iago_mcts_search_explore, which carries the hand-over); rules.playout_cap: their searched turns
-        full or fast (iago_mcts_search_cap, which carries the other two).  The role split where it is set up, else the
-        single launch, whichever entry point takes the games."""
+        full or fast (iago_mcts_search_cap, which carries the other two).  rules.root_noise (one search only, no `game`):
+        a root that expands takes the counts row ops.root_noise left (iago_mcts_search_noise).  The role split where it
+        is set up, else the single launch, whichever entry point takes the games."""
         a, keep = self._search_args(own, opp, active, n_sims, game)
         ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
         if ev is not None:
@@ -1230,6 +1238,10 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
+        elif rules.root_noise is not None:
+            if game is not None:
+                raise ValueError("whole games in one launch are not available with root noise (the turn loop is)")
+            ops.search_noise(a, rules.root_noise, self._noise_rows(), streams=self._split)
         elif rules.playout_cap is not None:
             ops.search_cap(a, *rules.playout_cap, explore_turns=rules.explore_turns, streams=self._split, park=k)
         elif rules.explore_turns:
@@ -1319,17 +1331,39 @@ class BatchedMCTS(object):
                     self._vtable.zero_()
             self._value_key = key
 
+    def _noise_rows(self):
+        """The root noise's counts rows, (n_games, 64) int16, one per slot (iago_root_noise.counts)."""
+        rows = getattr(self, "_noise_counts", None)
+        if rows is None:
+            rows = self._noise_counts = torch.zeros((self.n_games, 64), dtype=torch.int16, device=self.cur_own.device)
+        return rows
+
+    def _root_noise_arg(self, root_noise):
+        """search()'s root_noise, validated: offered for the persistent engine only."""
+        noise = ops.root_noise_arg(root_noise)
+        if noise is not None and (not getattr(self, "persistent", False) or getattr(self, "wave_entry", False)
+                                  or self.rollout_hook is not None or getattr(self, "use_graph", False)
+                                  or getattr(self, "async_steps", False) or getattr(self, "lookahead", 0)):
+            raise ValueError("root_noise is offered for the persistent search only (not use_graph, async steps, the "
+                             "look-ahead, rollout_hook or the wave search)")
+        return noise
+
     def search_counts(self, active):
         """Device tensor int64[2]: games in `active`, nodes of the fullest pool -- what search()
         reads back before it starts (a caller that batches its readbacks passes them in)."""
         return torch.stack([active.sum().to(torch.int64), self.tree.n_nodes.max().to(torch.int64)])
 
-    def search(self, own, opp, active, n_sims, counts=None, check=True):
+    def search(self, own, opp, active, n_sims, counts=None, check=True, root_noise=None, turn=0):
         """n_sims playouts from the current roots; (own, opp) = root positions
         with own = side to move; active: uint8 mask of participating games.
         counts: (games in `active`, nodes of the fullest pool) when the caller has read
         search_counts() back already; check=False: the error flags are not read back here (one
-        host sync each) -- the caller reads error_flags() and calls raise_errors()."""
+        host sync each) -- the caller reads error_flags() and calls raise_errors().
+        root_noise = (alpha_256, eps_256[, draws]) (None, the default: off; the persistent engine only, else
+        ValueError): the priors of every active root's children are mixed with the shares of the Polya urn of turn
+        `turn` of game game_id_base + g (include/iago_hip_serving.h, iago_mcts_root_noise) for the whole of this search,
+        once -- children the root has are rewritten before the first playout, a root that expands creates them mixed."""
+        noise = self._root_noise_arg(root_noise)
         n_active, used = (int(v) for v in (self.search_counts(active).tolist() if counts is None else counts))
         if n_active == 0:
             # (the playout counter advances all the same: a game's Philox streams are keyed by ITS turn and
@@ -1353,7 +1387,9 @@ class BatchedMCTS(object):
             if self._la_stale_any:
                 self._refresh_priors(own, opp, active)
         self._compact_if_half_full(used)
-        if self.persistent and self.rollout_hook is None:
+        if noise is not None:
+            self._search_persistent(own, opp, active, n_sims, n_active, noise, turn)
+        elif self.persistent and self.rollout_hook is None:
             self._search_persistent(own, opp, active, n_sims, n_active)
         elif self.async_steps and self.rollout_hook is None:
             self._search_async(own, opp, active, n_sims, n_active)
@@ -1618,11 +1654,11 @@ def _solve_empties_arg(k):
     return int(k)
 
 
-def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None):
+def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None):
     """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
-    where its own validator refuses it.  Off is (None, 0, None): explore_turns is an int in the record."""
+    where its own validator refuses it.  Off is (None, 0, None, None): explore_turns is an int in the record."""
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
-                     ops.playout_cap_arg(playout_cap, n_sims))
+                     ops.playout_cap_arg(playout_cap, n_sims), ops.root_noise_arg(root_noise))
 
 
 def _colour_arg(colour, B, dev, name, or_none=""):
@@ -1715,7 +1751,8 @@ class SelfPlayEngine(object):
         empties (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the
         same records (valid 3, score), and the one readback follows both.  explore_turns > 0: the searched moves of the
         turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore).  playout_cap =
-        (n_fast, full_per_256): every searched turn is full or fast, in the launch (iago_mcts_search_cap)."""
+        (n_fast, full_per_256): every searched turn is full or fast, in the launch (iago_mcts_search_cap).  (Games with
+        root_noise do not come here: _one_launch.)"""
         m, T = self.mcts, self.max_turns
         solve_empties, cap = rules.solve_empties, rules.playout_cap
         B = games_total or self.B        # (the result's columns: one per game)
@@ -1793,7 +1830,8 @@ class SelfPlayEngine(object):
         fallback, whose searches (one launch per turn) compact a pool that is half full.  Same games either way."""
         m = self.mcts
         m.tree.reset()
-        if not (applies and self._whole_games_in_one_launch(n_sims)):
+        # (root noise: the urn is drawn per turn by a launch of its own, ops.root_noise -- the turn loop)
+        if not (applies and rules.root_noise is None and self._whole_games_in_one_launch(n_sims)):
             return None
         res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, rules, **kw)
         if res is None:
@@ -1804,17 +1842,19 @@ class SelfPlayEngine(object):
     def _search_sides(self, sides, own, opp, rules):
         """The turn's searches, one side after the other (check=False: the loop reads every side's flags back).  Under a
         playout cap TWO searches per side from the same sim_counter -- a fast turn is the first n_fast playouts of the
-        full turn's search: the same Philox streams -- and the counter n_sims on, once.  Returns 1: a SelfPlayResult's
-        `launches` counts the turns."""
+        full turn's search: the same Philox streams -- and the counter n_sims on, once.  Under root noise the search (of
+        a cap's two the full games' alone: a fast turn searches the clean priors) takes rules.root_noise and the side's
+        turn.  Returns 1: a SelfPlayResult's `launches` counts the turns."""
         for s in sides:
             m = s.mcts
+            kw = {} if rules.root_noise is None else dict(root_noise=rules.root_noise, turn=s.turn)   # (off: today's calls)
             if rules.playout_cap is None:
-                m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False)   # (sim_counter: + n_sims whoever searched)
+                m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False, **kw)   # (sim_counter: + n_sims whoever searched)
                 continue
             s0 = m.sim_counter
             if s.counts[0] + s.counts_fast[0] > 0:
                 m._compact_if_half_full(int(s.counts[1]))   # (once, for both searches: used = 0 keeps them from it)
-            m.search(own, opp, s.full, s.n_sims, counts=(s.counts[0], 0), check=False)
+            m.search(own, opp, s.full, s.n_sims, counts=(s.counts[0], 0), check=False, **kw)
             # (the fast games' launch clears the gave-up word of the full games': kept on the device for the readback)
             s.gave_up = m.gave_up_word()
             m.sim_counter = s0
@@ -1876,7 +1916,7 @@ class SelfPlayEngine(object):
                 if at_end is not None:
                     sol = mine & at_end if sol is None else sol | (mine & at_end)
                     mine = mine & ~at_end
-                s.mine, s.act = mine, active if mine is on else mine.to(torch.uint8)
+                s.mine, s.act, s.turn = mine, active if mine is on else mine.to(torch.uint8), t
                 if cap is None:
                     counts["counts", i] = s.mcts.search_counts(s.act)
                 else:
@@ -1971,7 +2011,8 @@ class SelfPlayEngine(object):
                     setattr(res, name, v[:t])
         return res
 
-    def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None):
+    def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None,
+             root_noise=None):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -1994,11 +2035,25 @@ class SelfPlayEngine(object):
         n_sims) playouts of the same search, the move played as ever (the most visited child; below explore_turns the
         draw), recorded with valid 4 and its visit row, kept out of tuples() and given by fast_tuples().  sim_counter
         advances by n_sims per turn all the same.  The one launch (iago_mcts_search_cap) and the turn loop play the same
-        games; solve_empties and explore_turns compose."""
-        return self._play(n_sims, handicap, record, _play_rules(n_sims, solve_empties, explore_turns, playout_cap))
+        games; solve_empties and explore_turns compose.
+        root_noise = (alpha_256, eps_256[, draws]) (None, the default: off): Dirichlet-style noise on the root's priors,
+        in integers (include/iago_hip_serving.h, iago_mcts_root_noise).  At every searched turn t of game g with K >= 2
+        legal moves a Polya urn -- every legal cell starts with mass alpha = alpha_256 / 256 (1 .. 4096), `draws` draws N
+        (a power of two in 16 .. 1024, default 256) each in proportion to alpha + the cell's count so far, Philox words
+        of (seed ^ NOISE_SEED_XOR; game_id_base + g, t, j >> 2) -- gives counts c that are Dirichlet-multinomial(N,
+        alpha), and the stored prior p of the root's child a becomes p (256 - eps_256) / 256 + eps_256 c[a] / (256 N)
+        (eps_256 0 .. 256), two float32 roundings, for the whole of the turn's search.  Under playout_cap only the FULL
+        turns are noised (a fast turn searches the clean priors, so it is no longer a prefix of the full turn's search).
+        The records keep their shape.  Such games ALWAYS run through the turn loop (launches = their turns; per turn
+        iago_mcts_root_noise, then iago_mcts_search_noise, on the role split where the engine has it), and play_stream
+        through the batch loop; solve_empties, explore_turns and playout_cap compose; eps_256 = 0 plays the games of
+        root_noise=None."""
+        return self._play(n_sims, handicap, record,
+                          _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise))
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
+        self.mcts._root_noise_arg(rules.root_noise)   # (the persistent engine only: refused before anything is reset)
         res = self._one_launch(n_sims, self.B, handicap, record, rules)
         if res is None:
             res = self._play_turns([_Side(self.mcts, n_sims)], *self._start_boards(self.B, handicap), record,
@@ -2006,7 +2061,7 @@ class SelfPlayEngine(object):
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
-                    playout_cap=None):
+                    playout_cap=None, root_noise=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -2018,9 +2073,10 @@ class SelfPlayEngine(object):
         took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch.  solve_empties: as in play() --
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
-        turns are full or fast by its own id."""
-        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap)
+        turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id."""
+        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise)
         m, T = self.mcts, self.max_turns
+        m._root_noise_arg(rules.root_noise)
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError("play_stream: n_games >= 1 expected")

@@ -1216,6 +1216,66 @@ def search_cap(args, n_fast, full_per_256, explore_turns=0, streams=None, park=N
     check(_lib.lib().iago_mcts_search_cap(C.byref(args), C.byref(c), _stream()), "iago_mcts_search_cap")
 
 
+def root_noise_arg(noise):
+    """root_noise of SelfPlayEngine.play / play_stream / BatchedMCTS.search: None (off), or (alpha_256, eps_256[, draws])
+    -- ints, 1 <= alpha_256 <= 4096 (alpha = alpha_256 / 256), 0 <= eps_256 <= 256 (eps = eps_256 / 256), draws a power of
+    two in [16, 1024] (default _lib.NOISE_DRAWS) -- returned as a tuple of three ints."""
+    if noise is None:
+        return None
+    what = "root_noise must be None or (alpha_256, eps_256[, draws]), ints, not %r" % (noise,)
+    try:
+        vals = tuple(noise)
+    except TypeError:
+        raise ValueError(what)
+    if len(vals) not in (2, 3) or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals):
+        raise ValueError(what)
+    alpha, eps, draws = (vals + (_lib.NOISE_DRAWS,))[:3]
+    if not 1 <= alpha <= 4096:
+        raise ValueError("root_noise: alpha_256 must be in [1, 4096], not %r" % (alpha,))
+    if not 0 <= eps <= 256:
+        raise ValueError("root_noise: eps_256 must be in [0, 256], not %r" % (eps,))
+    if not 16 <= draws <= 1024 or draws & (draws - 1):
+        raise ValueError("root_noise: draws must be a power of two in [16, 1024], not %r" % (draws,))
+    return int(alpha), int(eps), int(draws)
+
+
+def _root_noise_struct(noise, counts, into=None):
+    nz = _lib.RootNoise() if into is None else into
+    nz.alpha_256, nz.eps_256, nz.draws = (int(v) for v in noise)
+    # (the counts, 0 .. 1024, as int16: the same bits as the library's uint16, and a dtype every torch op takes)
+    nz.counts = _dev(counts, torch.int16, "counts") if counts is not None else None
+    return nz
+
+
+def root_noise(tree, active, root_own, root_opp, seed, game_id, turn, noise, counts):
+    """iago_mcts_root_noise (include/iago_hip_serving.h): the root noise of the turn loop.  For every game with active[g]
+    != 0 (active None: every game) the Polya urn of turn[g] of the game with GLOBAL id game_id[g] over the legal moves of
+    the mover of (root_own[g], root_opp[g]) -- noise = (alpha_256, eps_256, draws); draw j takes the lowest legal cell a
+    with sum_{b <= a} (alpha_256 + 256 c[b]) > (w_j * (K alpha_256 + 256 j)) >> 32, w_j word j & 3 of Philox4x32-10 on
+    (game_id, turn, j >> 2, 0) under seed ^ NOISE_SEED_XOR -- written to counts[g] ((n_games, 64) int16, 0 off the legal
+    set and for K < 2), and the mix p * (256 - eps_256) / 256 + eps_256 c / (256 draws) applied to the children the tree's
+    root already has.  Inactive games' rows and trees are not touched.  tree: TreePool.ref(); game_id / turn (n_games,)
+    int32.  Returns counts."""
+    nz = _root_noise_struct(noise, counts)
+    check(_lib.lib().iago_mcts_root_noise(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                          _dev(root_own, torch.int64, "root_own"), _dev(root_opp, torch.int64, "root_opp"),
+                                          C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(game_id, torch.int32, "game_id"),
+                                          _dev(turn, torch.int32, "turn"), C.byref(nz), _stream()), "iago_mcts_root_noise")
+    return counts
+
+
+def search_noise(args, noise, counts, streams=None):
+    """iago_mcts_search_noise (include/iago_hip_serving.h): the ONE search of `args` (a _lib.MctsSearchArgs, max_turns 0)
+    in which a root that expands creates its children with the mixed priors of its row of `counts` -- the (n_games, 64)
+    int16 rows root_noise() left for this turn; noise = (alpha_256, eps_256, draws) as given there; streams: the role
+    split's handle or None.  The caller keeps `args`, `counts` and everything they point to alive until the launch has
+    run."""
+    z = _lib.SearchNoiseArgs()
+    _root_noise_struct(noise, counts, z.noise)
+    z.streams = streams
+    check(_lib.lib().iago_mcts_search_noise(C.byref(args), C.byref(z), _stream()), "iago_mcts_search_noise")
+
+
 def search_arena(args_a, args_b, check_result=True):
     """iago_mcts_search_arena (include/iago_hip_serving.h): the searches of `args_a` and `args_b` (two
     _lib.MctsSearchArgs, each a complete search of iago_mcts_search_persistent with its own nets, trees and rings) in

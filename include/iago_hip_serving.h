@@ -235,6 +235,71 @@ IAGO_API int iago_mcts_search_cap(const iago_mcts_search_args *args, const iago_
 IAGO_API int iago_mcts_cap_mask(uint64_t seed, const int32_t *game_id, const int32_t *turn, int32_t full_per_256, int64_t n,
                                 uint8_t *fast, void *stream);
 
+/* ------------------------------------------------------------------ root noise */
+
+#define IAGO_NOISE_KEY 0x44495249u /* ("DIRI") the urn's Philox key: the rollout seed with its high word XOR this */
+
+typedef struct iago_root_noise {
+    int32_t alpha_256; /* 1 .. 4096: alpha = alpha_256 / 256, the mass every legal cell starts with */
+    int32_t eps_256;   /* 0 .. 256: eps = eps_256 / 256, the noise's share of a mixed prior */
+    int32_t draws;     /* N: a power of two in 16 .. 1024, the urn's draws */
+    int32_t reserved0; /* 0 */
+    uint16_t *counts;  /* [n_games][64] the urn's counts by cell, one row per SLOT (tree) */
+} iago_root_noise;
+
+/*
+ * ROOT NOISE in self-play, Dirichlet-style and in integers: at a searched turn t (the game's turn counter, passes
+ * included) of the game with global id G, the priors of the root's children are mixed with the shares of a Polya urn.  Let
+ * the mover have K legal moves, their cells in ascending order.
+ *   - K < 2: nothing happens.  The counts are 0 and the single child, or the pass child, keeps its 1.1.
+ *   - K >= 2, the urn: c[a] = 0 on every legal cell.  For j = 0 .. N-1 the weight of legal cell a is alpha_256 + 256 c[a],
+ *     so the total is W = K alpha_256 + 256 j; w_j is word j & 3 of Philox4x32-10 on the counter (rollout->id_base + G, t,
+ *     j >> 2, 0) under the key rollout->seed with its high word XOR IAGO_NOISE_KEY (a key of its own: not the explore
+ *     draw's, the cap's, a match's or the replay window's); r = (uint64(w_j) * W) >> 32; the drawn cell is the lowest legal
+ *     a with sum_{b <= a} weight[b] > r, and its c grows by 1.  The counts sum to N and are Dirichlet-multinomial(N, alpha):
+ *     the shares c / N have granularity 1 / N and tend to Dirichlet(alpha) as N grows.
+ *   - the mix, on the child's STORED prior p (what Node.__init__ keeps: prior + 0.1, MCTS.py:19): p becomes
+ *     fadd_rn(fmul_rn(p, keep), term) with keep = float32((256 - eps_256) / 256) and term = float32(eps_256 c[a]) *
+ *     2^-(8 + log2 N), both exact in float32; the product and the sum are each rounded once.
+ *   - when: the root's children carry mixed priors for the whole of turn t's search, and the mix is applied ONCE.  A root
+ *     that has children at the turn's start (a reused subtree) has them rewritten before the first playout; a root that
+ *     expands during the turn's search (a fresh root at playout n_thr, a reused one with fewer than n_thr visits) creates
+ *     its children with the mixed priors.  Nothing is undone afterwards: the children of a root were created while it was
+ *     not the root, all but the chosen child are abandoned after the move, and the root moves every turn, passes included.
+ *
+ * iago_mcts_root_noise is the rule's first half for the turn loop, a sibling of iago_mcts_draw_move and
+ * iago_mcts_cap_mask: for every game with active[g] != 0 (active NULL: every game) it draws the urn of turn[g] of the
+ * game with GLOBAL id game_id[g] (id_base + G, as its 32 bits) over the legal moves of the mover of (root_own[g],
+ * root_opp[g]) under `seed` (the rollout seed; the XOR is applied here), writes the counts row noise->counts[g][0 .. 63]
+ * (0 off the legal set) and applies the mix to the children the tree's root already has.  Inactive games' rows and trees
+ * are not touched.  Refused (IAGO_ERR_INVALID, nothing launched): a bad tree, a null array, alpha_256 outside 1 .. 4096,
+ * eps_256 outside 0 .. 256, draws not a power of two in 16 .. 1024, a null counts buffer, reserved0 not 0.
+ */
+IAGO_API int iago_mcts_root_noise(const iago_mcts_tree *tree, const uint8_t *active, const uint64_t *root_own,
+                                  const uint64_t *root_opp, uint64_t seed, const int32_t *game_id, const int32_t *turn,
+                                  const iago_root_noise *noise, void *stream);
+
+typedef struct iago_search_noise_args {
+    iago_root_noise noise;        /* eps_256, draws and the counts buffer iago_mcts_root_noise filled (alpha_256 as there) */
+    iago_search_streams *streams; /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    int64_t reserved[4];          /* 0 */
+} iago_search_noise_args;
+
+/*
+ * The rule's second half: ONE search of iago_mcts_search_persistent (max_turns == 0; with `streams`
+ * iago_mcts_search_split's) in which the tree root of every active game, where it expands in this search, creates its K
+ * >= 2 children with the mixed priors of the game's row of noise.counts -- what iago_mcts_root_noise left there for this
+ * turn.  Everything else -- the playouts, the rollouts' Philox streams, z_log, the totals -- is iago_mcts_search_persistent's;
+ * with eps_256 = 0 the trees are, bit for bit.  `active` is a mask here (!= 0: searched).
+ * Whole games (max_turns > 0, a stream) are NOT available: self-play with root noise runs turn by turn
+ * (SelfPlayEngine's turn loop: iago_mcts_root_noise, then this search, per turn).  Under a playout cap the turn loop gives
+ * the noise to the FULL games' search only (KataGo's rule): a fast turn searches the clean priors, so a fast turn is then
+ * no longer a prefix of the full turn's search, as it is without noise.
+ * Refused (IAGO_ERR_INVALID, nothing launched): null args, what iago_mcts_root_noise refuses of `noise`, reserved fields not
+ * 0, max_turns > 0 or games_total > 0.  The wave search, matches and the arena do not noise.
+ */
+IAGO_API int iago_mcts_search_noise(const iago_mcts_search_args *args, const iago_search_noise_args *noise, void *stream);
+
 /* ------------------------------------------------------------------ arena */
 
 /*
