@@ -49,12 +49,14 @@ EXPERIMENTAL_SYMBOLS = [
 ]
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
 # the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=)),
-# playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=))
+# playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=)), forced
+# playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
     "iago_mcts_root_noise", "iago_mcts_search_noise",
+    "iago_mcts_search_forced", "iago_mcts_prune_visits",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -334,6 +336,14 @@ class SearchNoiseArgs(C.Structure):
     ]
 
 
+class SearchForcedArgs(C.Structure):
+    """Mirror of iago_search_forced_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("noise", RootNoise), ("streams", C.c_void_p), ("k_256", C.c_int32), ("reserved0", C.c_int32),
+        ("reserved", C.c_int64 * 4),
+    ]
+
+
 class ValueSplitArgs(C.Structure):
     """Mirror of iago_value_split_args (include/iago_hip.h)."""
     _fields_ = [
@@ -466,6 +476,8 @@ def lib():
     L.iago_mcts_cap_mask.argtypes = [C.c_uint64, vp, vp, i32, i64, vp, vp]
     L.iago_mcts_root_noise.argtypes = [tp, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(RootNoise), vp]
     L.iago_mcts_search_noise.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchNoiseArgs), vp]
+    L.iago_mcts_search_forced.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchForcedArgs), vp]
+    L.iago_mcts_prune_visits.argtypes = [tp, vp, C.c_float, i32, vp, vp]
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int

@@ -61,6 +61,20 @@ __device__ __forceinline__ double puct_score(float c_puct, float p, float q, int
     return (double)q + u;
 }
 
+// ---- forced playouts ("Forced playouts"; the contract is iago_hip_serving.h's): forced(n, p, N) of a
+// root child with n visits and the STORED prior p under a root of N visits, k = k_256 / 256: n >= 1 and 256 n^2 < (k_256 p)
+// N -- n < sqrt(k p N) without the root.  256 n^2 (n < 2^22) and k_256 p (12 x 24 bits) are exact in float64, the product
+// with N rounds once; no contraction.  k_256 = 0: never
+__device__ __forceinline__ bool forced_child(int n, float p, double k_256, double N)
+{
+#pragma clang fp contract(off)
+    const double dn = (double)n;
+    const double lhs = 256.0 * dn * dn;
+    const double kp = k_256 * (double)p;
+    const double rhs = kp * N;
+    return n >= 1 && lhs < rhs;
+}
+
 // in-flight visits (vv) of a wave search: the score of a child when a playout of the wave is on its way through it --
 // n + vv visits, the in-flight ones counted as a loss of `vloss` each.  vv == 0: puct_score exactly.  (No contraction:
 // the restatement in tests/wave_mcts.py rounds every product and difference on its own)
@@ -76,14 +90,18 @@ __device__ __forceinline__ double wave_score(float c_puct, float p, float q, int
 
 // the score of child j, whose record is (s, l), against the best of its lane so far; strict `>`: the first maximum wins
 // (python max, MCTS.py:46).  pl: the best child's first_child, n_visits, action | n_children << 8 (| vv << 16), v
-template <bool WAVE>
+// FORCE (the noise instantiations of the persistent search alone): a child with forced_child(n, p, force_k, force_n) scores
+// +inf -- the caller gives force_k = k_256 at the root of the search when it has two or more children, 0 anywhere else
+template <bool WAVE, bool FORCE = false>
 __device__ __forceinline__ void score_child(float c_puct, double vloss, uint4 s, uint4 l, int j, double sq, double &best_v,
-                                            int &best_i, uint32_t (&pl)[4])
+                                            int &best_i, uint32_t (&pl)[4], double force_k = 0.0, double force_n = 0.0)
 {
     const float p = __uint_as_float(s.z), q = __uint_as_float(s.y);
     const int n = (int)s.x;
     // (vv < 2^16: at most 32 playouts in flight)
-    const double v = WAVE ? wave_score(c_puct, p, q, n, (int)l.w, sq, vloss) : puct_score(c_puct, p, q, n, sq);
+    double v = WAVE ? wave_score(c_puct, p, q, n, (int)l.w, sq, vloss) : puct_score(c_puct, p, q, n, sq);
+    if constexpr (FORCE)
+        v = forced_child(n, p, force_k, force_n) ? (double)INFINITY : v;
     if (v > best_v) {
         best_v = v;
         best_i = j;

@@ -305,6 +305,72 @@ __global__ __launch_bounds__(BLOCK) void root_noise_kernel(Tree T, const uint8_t
         noise_remix_children(T, base, rfc, lg, L.l8, c, eps_256, draws_log2);
 }
 
+// best_move_kernel's sibling for the policy-target pruning (iago_mcts_prune_visits), 8 lanes per game: the visit row of
+// the root's children with the forced playouts taken out wherever PUCT would not have granted them -- the rule of
+// iago_hip_serving.h with mcts_dev.hpp's forced_child and puct_score.  Pass 1, the children dealt round the lanes: the first
+// child with the most visits (best_move's) and the cells of the children.  Pass 2, lane r the cells of board row r (the
+// children of a root with two or more are its legal moves in ascending cell order, as noise_remix_children walks them):
+// every lane writes its own eight cells, so no cell has two writers.  Fewer than two children: the raw row.  No LDS, no
+// workspace; the loops are bounded by the child's visits.  Inactive games: nothing written
+__global__ __launch_bounds__(BLOCK) void prune_visits_kernel(Tree T, const uint8_t *__restrict__ active, float c_puct,
+                                                             double k_256, int32_t *__restrict__ pruned)
+{
+    const int64_t g = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 3;
+    const uint32_t l8 = threadIdx.x & 7u;
+    const bool live = g < T.n_games && (!active || active[g] != 0);
+    const int64_t base = live ? g * (int64_t)T.capacity : 0;
+    const int root = live ? T.root[g] : 0;
+    const int fc = live ? T.nodes[base + root].first_child : -1;
+    const int k = fc >= 0 ? (int)T.nodes[base + root].n_children : 0;
+    double best_v = -1.0; // (visits as float64, exact: argmax_step's order is python's max over the counts)
+    int best_i = 0x7fffffff;
+    uint64_t cells = 0ull;
+    for (int j = (int)l8; j < k; j += 8) {
+        const int n = T.nodes[base + fc + j].n_visits;
+        const int a = (int)T.nodes[base + fc + j].action;
+        if ((double)n > best_v) {
+            best_v = (double)n;
+            best_i = j;
+        }
+        cells |= a >= 0 ? 1ull << a : 0ull;
+    }
+    argmax_step<DPP_XOR1>(best_v, best_i);
+    argmax_step<DPP_XOR2>(best_v, best_i);
+    argmax_step<DPP_HALF_MIRROR>(best_v, best_i);
+    cells = group8_or(cells);
+    if (!live)
+        return;
+    const bool prune = k >= 2 && __popcll(cells) == k;
+    double big_n = 0.0, sq = 0.0, s_star = 0.0;
+    if (prune) {
+        const int64_t b = base + fc + best_i;
+        big_n = (double)T.nodes[base + root].n_visits;
+        sq = sqrt(big_n);
+        s_star = puct_score(c_puct, T.nodes[b].p, T.nodes[b].q, T.nodes[b].n_visits, sq);
+    }
+    const uint32_t row = (uint32_t)(cells >> (8u * l8)) & 0xFFu;
+    int at = fc + __popcll(cells & ((1ull << (8u * l8)) - 1ull));
+#pragma unroll 1
+    for (int i = 0; i < 8; i++) {
+        int m = 0;
+        if ((row >> i) & 1u) {
+            const int n = T.nodes[base + at].n_visits;
+            m = n;
+            if (prune && at - fc != best_i && n >= 1) {
+                const float p = T.nodes[base + at].p, q = T.nodes[base + at].q;
+                int f = 0; // F: forced_child is monotone in j (256 j^2 grows, the right side stands), so the count ends at the first miss
+                for (int j = 1; j < n && forced_child(j, p, k_256, big_n); j++)
+                    f++;
+                for (int t = 0; t < f && puct_score(c_puct, p, q, m - 1, sq) < s_star; t++)
+                    m--;
+                m = (m < n && m == 1) ? 0 : m;
+            }
+            at++;
+        }
+        pruned[g * 64 + (int)(8u * l8) + i] = m;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void advance_root_kernel(Tree T, const uint8_t *__restrict__ mask,
                                                              const int8_t *__restrict__ move)
 {
@@ -1120,6 +1186,22 @@ int iago_mcts_root_noise(const iago_mcts_tree *tree, const uint8_t *active, cons
                        (uint32_t)noise->alpha_256, (uint32_t)noise->eps_256, (uint32_t)__builtin_ctz((uint32_t)noise->draws),
                        noise->counts);
     return iago_check_launch("iago_mcts_root_noise");
+}
+
+int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256, int32_t *pruned,
+                           void *stream)
+{
+    if (check_tree(tree, "iago_mcts_prune_visits: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (k_256 < 1 || k_256 > 4096)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_prune_visits: k_256 must be in [1, 4096]");
+    if (!pruned)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_prune_visits: null pruned buffer");
+    if (tree->n_games == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(prune_visits_kernel, dim3(grid_for(tree->n_games * 8)), dim3(BLOCK), 0, (hipStream_t)stream, *tree,
+                       active, c_puct, (double)k_256, pruned);
+    return iago_check_launch("iago_mcts_prune_visits");
 }
 
 int iago_mcts_advance_root(const iago_mcts_tree *tree, const uint8_t *mask, const int8_t *move,

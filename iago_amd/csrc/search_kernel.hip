@@ -165,6 +165,8 @@ struct SearchParams {
     // the counts rows [n_games][64] that iago_mcts_root_noise wrote before the launch, read where a root expands
     uint16_t *noise_counts;
     int32_t noise_eps, noise_lg;
+    // forced playouts (iago_mcts_search_forced; the NOISE instantiations alone read it): k_256, 0 = none forced
+    int32_t forced_k_256;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -836,11 +838,14 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
 }
 
 // Node.select: two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
-template <bool WAVE>
+// NOISE: at the ROOT of the search (the path's first node) with two or more children a forced child -- mcts_dev.hpp's
+// forced_child of its visits, its stored prior and the root's visits, under S.forced_k_256 -- scores +inf
+template <bool WAVE, bool NOISE>
 __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
 {
     const int kk = descending ? C.k : 0;
     const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv));
+    const double force_k = (NOISE && C.path_n == 1 && kk >= 2) ? (double)S.forced_k_256 : 0.0, force_n = (double)C.nv;
     double best_v = -INFINITY;
     int best_i = 0x7fffffff;
     uint32_t pl[4] = {0u, 0u, 0u, 0u};
@@ -851,9 +856,9 @@ __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I
         uint4 s0, l0, s1, l1;
         node_record(S.T, c0, s0, l0);
         node_record(S.T, c1, s1, l1);
-        score_child<WAVE>(S.c_puct, (double)S.vloss, s0, l0, j0, sq, best_v, best_i, pl);
+        score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, s0, l0, j0, sq, best_v, best_i, pl, force_k, force_n);
         if (two)
-            score_child<WAVE>(S.c_puct, (double)S.vloss, s1, l1, j1, sq, best_v, best_i, pl);
+            score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, s1, l1, j1, sq, best_v, best_i, pl, force_k, force_n);
     }
     argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
     argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
@@ -984,7 +989,7 @@ __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, Ga
             }
         }
         const bool one = C.k == 1;
-        const int action = select_child<WAVE>(S, I, C, descending);
+        const int action = select_child<WAVE, NOISE>(S, I, C, descending);
         if constexpr (!WAVE) {
             // (a step that is no pass level: a pass chain can begin at the child, the next index to be recorded, at the earliest)
             if (S.chain_skip && descending && I.r == 0u && !(one && action < 0))
@@ -1820,6 +1825,7 @@ struct LaunchRequest {
     int explore_turns = 0;                        // turns whose moves are drawn from the visit counts
     int cap_fast = 0, cap_full_256 = 256;         // the playout cap: playouts of a fast turn, full turns in 256
     const iago_root_noise *noise = nullptr;       // root noise: the counts rows applied where a root expands
+    int forced_k_256 = 0;                         // forced playouts at the root (with noise): k_256, 0 = none
 };
 
 // games_per_workgroup without its flag (IAGO_SEARCH_CHAIN_SKIP)
@@ -2058,6 +2064,7 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.noise_counts = q.noise ? q.noise->counts : nullptr;
     S.noise_eps = q.noise ? q.noise->eps_256 : 0;
     S.noise_lg = q.noise ? __builtin_ctz((unsigned)q.noise->draws) : 0;
+    S.forced_k_256 = q.noise ? q.forced_k_256 : 0;
     return S;
 }
 
@@ -2353,6 +2360,26 @@ extern "C" int iago_mcts_search_noise(const iago_mcts_search_args *a, const iago
     LaunchRequest q;
     q.streams = nz->streams;
     q.noise = &nz->noise;
+    return search_launch(a, stream, q);
+}
+
+extern "C" int iago_mcts_search_forced(const iago_mcts_search_args *a, const iago_search_forced_args *fz, void *stream)
+{
+    if (!a || !fz)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_forced: null args");
+    if (const int rc = check_reserved(fz->reserved, fz->reserved0, "iago_mcts_search_forced"))
+        return rc;
+    if (const int rc = check_root_noise(&fz->noise, "iago_mcts_search_forced"))
+        return rc;
+    if (fz->k_256 < 1 || fz->k_256 > 4096)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_forced: k_256 must be in [1, 4096]");
+    if (a->max_turns != 0 || a->games_total != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_forced: one search per launch (max_turns 0, games_total 0): whole "
+                                           "games with forced playouts run turn by turn");
+    LaunchRequest q;
+    q.streams = fz->streams;
+    q.noise = &fz->noise;
+    q.forced_k_256 = fz->k_256;
     return search_launch(a, stream, q);
 }
 

@@ -40,8 +40,10 @@ _stream = ops._stream   # the current HIP stream as a void*
 
 # The rules of a batch of games beyond plain PV-MCTS, validated once (_play_rules) and handed on as ONE value:
 # solve_empties (None: off, else an int in [0, 20]), explore_turns (an int, 0: off), playout_cap (None: off, else
-# (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)) -- as SelfPlayEngine.play documents them.
-PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise", defaults=(None,))
+# (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)), forced_playouts (None: off, else k_256,
+# with root_noise) -- as SelfPlayEngine.play documents them.
+PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise forced_playouts",
+                                   defaults=(None, None))
 NO_RULES = PlayRules(None, 0, None)
 
 
@@ -1199,16 +1201,17 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0):
+    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0, forced=None):
         """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent).  root_noise = (alpha_256, eps_256,
         draws): the urn of turn `turn` first (ops.root_noise: the counts rows, the mix on the children the roots have),
-        then the launch that applies the rows where a root expands (iago_mcts_search_noise)."""
+        then the launch that applies the rows where a root expands (iago_mcts_search_noise; forced = k_256: with forced
+        playouts at the root, iago_mcts_search_forced)."""
         if root_noise is None:
             self._launch_persistent(own, opp, active, n_sims)
         else:
             ids, turns = self._turn_ids(turn)
             ops.root_noise(self.tree.ref(), active, own, opp, self.seed, ids, turns, root_noise, self._noise_rows())
-            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, root_noise))
+            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, root_noise, forced))
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
@@ -1219,8 +1222,9 @@ class BatchedMCTS(object):
         that many empties (iago_mcts_search_park); rules.explore_turns: their moves of the turns below it drawn from the
         visit counts (iago_mcts_search_explore, which carries the hand-over); rules.playout_cap: their searched turns
         full or fast (iago_mcts_search_cap, which carries the other two).  rules.root_noise (one search only, no `game`):
-        a root that expands takes the counts row ops.root_noise left (iago_mcts_search_noise).  The role split where it
-        is set up, else the single launch, whichever entry point takes the games."""
+        a root that expands takes the counts row ops.root_noise left (iago_mcts_search_noise), and with
+        rules.forced_playouts the root's select forces (iago_mcts_search_forced).  The role split where it is set up,
+        else the single launch, whichever entry point takes the games."""
         a, keep = self._search_args(own, opp, active, n_sims, game)
         ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
         if ev is not None:
@@ -1241,7 +1245,10 @@ class BatchedMCTS(object):
         elif rules.root_noise is not None:
             if game is not None:
                 raise ValueError("whole games in one launch are not available with root noise (the turn loop is)")
-            ops.search_noise(a, rules.root_noise, self._noise_rows(), streams=self._split)
+            if rules.forced_playouts is None:
+                ops.search_noise(a, rules.root_noise, self._noise_rows(), streams=self._split)
+            else:
+                ops.search_forced(a, rules.root_noise, self._noise_rows(), rules.forced_playouts, streams=self._split)
         elif rules.playout_cap is not None:
             ops.search_cap(a, *rules.playout_cap, explore_turns=rules.explore_turns, streams=self._split, park=k)
         elif rules.explore_turns:
@@ -1353,7 +1360,7 @@ class BatchedMCTS(object):
         reads back before it starts (a caller that batches its readbacks passes them in)."""
         return torch.stack([active.sum().to(torch.int64), self.tree.n_nodes.max().to(torch.int64)])
 
-    def search(self, own, opp, active, n_sims, counts=None, check=True, root_noise=None, turn=0):
+    def search(self, own, opp, active, n_sims, counts=None, check=True, root_noise=None, turn=0, forced_playouts=None):
         """n_sims playouts from the current roots; (own, opp) = root positions
         with own = side to move; active: uint8 mask of participating games.
         counts: (games in `active`, nodes of the fullest pool) when the caller has read
@@ -1362,8 +1369,13 @@ class BatchedMCTS(object):
         root_noise = (alpha_256, eps_256[, draws]) (None, the default: off; the persistent engine only, else
         ValueError): the priors of every active root's children are mixed with the shares of the Polya urn of turn
         `turn` of game game_id_base + g (include/iago_hip_serving.h, iago_mcts_root_noise) for the whole of this search,
-        once -- children the root has are rewritten before the first playout, a root that expands creates them mixed."""
+        once -- children the root has are rewritten before the first playout, a root that expands creates them mixed.
+        forced_playouts = k_256 (None, the default: off; an int in [1, 4096], with root_noise only, else ValueError):
+        forced playouts at the root of this search (include/iago_hip_serving.h, iago_mcts_search_forced) -- a root child
+        with n >= 1 visits and stored prior p scores +inf in Node.select while 256 n^2 < k_256 p N, N the root's visits.
+        pruned_visits() afterwards takes the forced visits out of the visit rows."""
         noise = self._root_noise_arg(root_noise)
+        forced = ops.forced_playouts_arg(forced_playouts, noise)
         n_active, used = (int(v) for v in (self.search_counts(active).tolist() if counts is None else counts))
         if n_active == 0:
             # (the playout counter advances all the same: a game's Philox streams are keyed by ITS turn and
@@ -1388,7 +1400,7 @@ class BatchedMCTS(object):
                 self._refresh_priors(own, opp, active)
         self._compact_if_half_full(used)
         if noise is not None:
-            self._search_persistent(own, opp, active, n_sims, n_active, noise, turn)
+            self._search_persistent(own, opp, active, n_sims, n_active, noise, turn, forced)
         elif self.persistent and self.rollout_hook is None:
             self._search_persistent(own, opp, active, n_sims, n_active)
         elif self.async_steps and self.rollout_hook is None:
@@ -1514,6 +1526,17 @@ class BatchedMCTS(object):
                                              _stream()), "iago_mcts_best_move")
         return self.move, self.visits
 
+    def pruned_visits(self, active=None, forced_playouts=512):
+        """The policy-target pruning of forced playouts (ops.prune_visits) on the trees as they stand: the (n_games, 64)
+        int32 visit rows of the roots of the games in `active` (None: every game) with the forced visits taken out where
+        PUCT would not have granted them, under k_256 = forced_playouts and the engine's c_puct.  The engine's own buffer:
+        the next call overwrites it; the rows of games outside `active` are stale."""
+        k = ops.forced_playouts_arg(forced_playouts, noise=True)   # (the rule reads trees: whatever search wrote them)
+        rows = getattr(self, "_pruned_rows", None)
+        if rows is None:
+            rows = self._pruned_rows = torch.zeros((self.n_games, 64), dtype=torch.int32, device=self.move.device)
+        return ops.prune_visits(self.tree.ref(), active, self.c_puct, k, rows)
+
     def draw_move(self, turn, active=None, want_visits=True):
         """best_move for exploring self-play: the move drawn in proportion to the visit counts of the root's children
         (ops.draw_move), game g under the id game_id_base + g at turn `turn` (an int: every game's)."""
@@ -1556,6 +1579,9 @@ class SelfPlayResult(object):
     mover: (T,) colour to move at that turn (1 or 2)."""
 
     SCORE_RECORD = "score"   # the attribute that holds the `score` record
+    # forced_playouts: (T, B, 64) int32 the RAW visit rows, where `pi` then holds the pruned ones (the same on every row
+    # that was not forced); None without forced playouts
+    pi_raw = None
 
     def tuples(self):
         """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view."""
@@ -1654,11 +1680,20 @@ def _solve_empties_arg(k):
     return int(k)
 
 
-def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None):
+def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None, forced_playouts=None):
     """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
-    where its own validator refuses it.  Off is (None, 0, None, None): explore_turns is an int in the record."""
+    where its own validator refuses it (forced_playouts: an int in [1, 4096], and only with root_noise).  Off is (None, 0,
+    None, None, None): explore_turns is an int in the record."""
+    noise = ops.root_noise_arg(root_noise)
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
-                     ops.playout_cap_arg(playout_cap, n_sims), ops.root_noise_arg(root_noise))
+                     ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise))
+
+
+def _no_forced_playouts(forced_playouts, who):
+    """play_match and the arena do not force: forced playouts live only in noised self-play (play / play_stream)."""
+    if forced_playouts is not None:
+        raise ValueError("%s: forced_playouts is not available (forced playouts live only in the noised self-play of "
+                         "play / play_stream)" % who)
 
 
 def _colour_arg(colour, B, dev, name, or_none=""):
@@ -1844,10 +1879,12 @@ class SelfPlayEngine(object):
         playout cap TWO searches per side from the same sim_counter -- a fast turn is the first n_fast playouts of the
         full turn's search: the same Philox streams -- and the counter n_sims on, once.  Under root noise the search (of
         a cap's two the full games' alone: a fast turn searches the clean priors) takes rules.root_noise and the side's
-        turn.  Returns 1: a SelfPlayResult's `launches` counts the turns."""
+        turn, and with it rules.forced_playouts.  Returns 1: a SelfPlayResult's `launches` counts the turns."""
         for s in sides:
             m = s.mcts
             kw = {} if rules.root_noise is None else dict(root_noise=rules.root_noise, turn=s.turn)   # (off: today's calls)
+            if rules.forced_playouts is not None:
+                kw["forced_playouts"] = rules.forced_playouts
             if rules.playout_cap is None:
                 m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False, **kw)   # (sim_counter: + n_sims whoever searched)
                 continue
@@ -1874,7 +1911,10 @@ class SelfPlayEngine(object):
         for all such games) gives its move, recorded with valid 3 and the exact score, and its flags join the turn's
         readback.  explore_turns: the searched moves of the turns below it are drawn from the visit counts
         (BatchedMCTS.draw_move) instead of best_move's.  playout_cap = (n_fast, full_per_256): the turn's full games
-        (BatchedMCTS.cap_mask) search n_sims playouts, its fast ones n_fast, recorded with valid 4 (_search_sides)."""
+        (BatchedMCTS.cap_mask) search n_sims playouts, its fast ones n_fast, recorded with valid 4 (_search_sides).
+        forced_playouts = k_256: the games the noised search forced (every searched one, under a cap the full ones) record
+        their pruned visit row (BatchedMCTS.pruned_visits) in pi and the raw row in pi_raw; every other row is the raw one
+        in both.  The move comes from the raw counts."""
         B, T, dev = self.B, self.max_turns, own.device
         k, cap = rules.solve_empties, rules.playout_cap
         search = search or self._search_sides
@@ -1882,6 +1922,8 @@ class SelfPlayEngine(object):
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         rec = self._new_records(B) if record else None
+        if record and rules.forced_playouts is not None:
+            rec["pi_raw"] = torch.zeros_like(rec["pi"])
         legal = ops.legal_moves(own, opp)
         active = (legal != 0).to(torch.uint8)
         legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
@@ -1964,6 +2006,11 @@ class SelfPlayEngine(object):
                     v = s.act if cap is None else s.act + (_lib.REC_FAST - 1) * s.fast
                     p = s.visits * s.act.reshape(B, 1).to(torch.int32)
                     valid, pi = (v, p) if valid is None else (valid | v, pi + p)
+                if rules.forced_playouts is not None:
+                    rec["pi_raw"][t] = pi
+                    for s in sides:   # (the forced games: the noised search's)
+                        f = s.act if cap is None else s.full
+                        pi = torch.where(f.reshape(B, 1) != 0, s.mcts.pruned_visits(f, rules.forced_playouts), pi)
                 if policy_moves:
                     valid = valid + 2 * (drawn | forced).to(torch.uint8)
                 if sol is not None:
@@ -2012,7 +2059,7 @@ class SelfPlayEngine(object):
         return res
 
     def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None,
-             root_noise=None):
+             root_noise=None, forced_playouts=None):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -2047,9 +2094,19 @@ class SelfPlayEngine(object):
         The records keep their shape.  Such games ALWAYS run through the turn loop (launches = their turns; per turn
         iago_mcts_root_noise, then iago_mcts_search_noise, on the role split where the engine has it), and play_stream
         through the batch loop; solve_empties, explore_turns and playout_cap compose; eps_256 = 0 plays the games of
-        root_noise=None."""
+        root_noise=None.
+        forced_playouts = k_256 (None, the default: off; an int in 1 .. 4096, k = k_256 / 256, KataGo's k = 2 is 512;
+        only with root_noise, else ValueError -- root_noise=(alpha_256, 0) forces without mixing): KataGo's forced playouts
+        and policy-target pruning (include/iago_hip_serving.h, iago_mcts_search_forced / iago_mcts_prune_visits).  In every
+        noised search a child of the ROOT with n >= 1 visits and stored (mixed) prior p is taken before any other while
+        256 n^2 < k_256 p N, N the root's visits; after the search every child but the most visited one gives back up to
+        as many visits as were forced, one at a time while its PUCT score stays below the most visited child's, and a
+        child left with one visit gives that back too.  The move is chosen from the RAW counts as ever; `pi` records the
+        PRUNED row and the new record `pi_raw` the raw one (tuples() hand the trainer the pruned targets).  Under
+        playout_cap only the FULL turns are forced and pruned: a fast row's pi is its raw row.  Without forced playouts
+        the result's pi_raw is None."""
         return self._play(n_sims, handicap, record,
-                          _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise))
+                          _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts))
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
@@ -2061,7 +2118,7 @@ class SelfPlayEngine(object):
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
-                    playout_cap=None, root_noise=None):
+                    playout_cap=None, root_noise=None, forced_playouts=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -2073,8 +2130,9 @@ class SelfPlayEngine(object):
         took (1: the stream); sim_counter ends n_turns x n_sims on, as after one batch.  solve_empties: as in play() --
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
-        turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id."""
-        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise)
+        turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id.
+        forced_playouts: as in play(), with the record pi_raw."""
+        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts)
         m, T = self.mcts, self.max_turns
         m._root_noise_arg(rules.root_noise)
         n_games = int(n_games)
@@ -2091,7 +2149,7 @@ class SelfPlayEngine(object):
             res = self._play_batches(n_sims, n_games, handicap, record, rules)
         return res
 
-    def play_match(self, n_sims, mcts_colour=2, record=True, solve_empties=None):
+    def play_match(self, n_sims, mcts_colour=2, record=True, solve_empties=None, forced_playouts=None):
         """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
         `game.py --auto` (game.py:96-145,246-262) -- with the engine's nets: in game g PV-MCTS plays colour
         mcts_colour[g] (1 moves first; an int: every game; 2, the default, is the reference's setting) and the policy
@@ -2105,7 +2163,8 @@ class SelfPlayEngine(object):
         exact solver's move at its turns of at most k empties (valid 3) -- not the forced final move, which keeps
         precedence (valid 2), and not the policy's turns.  Such a match ALWAYS runs through the turn loop (launches =
         its turns): a one-launch match cannot hand its games over, the policy side needs the net workgroups to the last
-        move."""
+        move.  forced_playouts: None; anything else is a ValueError (a match has no root noise and does not force)."""
+        _no_forced_playouts(forced_playouts, "play_match")
         rules = _play_rules(n_sims, solve_empties)
         col = _colour_arg(mcts_colour, self.B, self.mcts.cur_own.device, "play_match: mcts_colour")
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
@@ -2151,6 +2210,8 @@ class SelfPlayEngine(object):
         res.final_p2 = torch.cat([r.final_p2[:w] for r, w in parts])
         if record:
             cols = {k: [] for k in ("own", "opp", "valid", "move", "pi", "score")}
+            if rules.forced_playouts is not None:
+                cols["pi_raw"] = []
             for r, w in parts:
                 dev, rows = r.z.device, min(r.n_turns, t)
                 pad = t - rows
@@ -2163,6 +2224,8 @@ class SelfPlayEngine(object):
                 cols["valid"].append(torch.cat([r.valid[:rows, :w], r.valid.new_zeros((pad, w))]))
                 cols["move"].append(torch.cat([r.move[:rows, :w], r.move.new_full((pad, w), -1)]))
                 cols["pi"].append(torch.cat([r.pi[:rows, :w], r.pi.new_zeros((pad, w, 64))]))
+                if "pi_raw" in cols:
+                    cols["pi_raw"].append(torch.cat([r.pi_raw[:rows, :w], r.pi_raw.new_zeros((pad, w, 64))]))
                 cols["score"].append(torch.cat([r.score[:rows, :w], r.score.new_zeros((pad, w))]))
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))
@@ -2306,12 +2369,14 @@ class ArenaEngine(object):
         b.search(own, opp, s_b, n_b, counts=c_b, check=False)
         return (1 if c_a[0] else 0) + (1 if c_b[0] else 0)
 
-    def play(self, n_sims, a_colour=None, record=True, explore_turns=None, one_launch=None):
+    def play(self, n_sims, a_colour=None, record=True, explore_turns=None, one_launch=None, forced_playouts=None):
         """B games from the opening, both trees fresh.  n_sims: playouts per move, an int or a pair (n_a, n_b); a_colour:
         the colour A plays, 1, 2 or a (B,) integer tensor of 1 / 2 (None: 1 in the first half of the games, 2 in the
         rest); explore_turns: as SelfPlayEngine.play's, each mover drawing with its own engine's seed and id; one_launch:
         True = one iago_mcts_search_arena launch per turn (the sequential form where the library answers
-        IAGO_ERR_CAPACITY), False = the sequential form, None = ONE_LAUNCH_DEFAULT.  Returns an ArenaResult."""
+        IAGO_ERR_CAPACITY), False = the sequential form, None = ONE_LAUNCH_DEFAULT.  forced_playouts: None; anything else
+        is a ValueError (the arena has no root noise and does not force).  Returns an ArenaResult."""
+        _no_forced_playouts(forced_playouts, "ArenaEngine.play")
         n_a, n_b = self._n_sims(n_sims)
         col = self._colours(a_colour)
         rules = _play_rules(n_a, explore_turns=explore_turns)

@@ -1276,6 +1276,44 @@ def search_noise(args, noise, counts, streams=None):
     check(_lib.lib().iago_mcts_search_noise(C.byref(args), C.byref(z), _stream()), "iago_mcts_search_noise")
 
 
+def forced_playouts_arg(k_256, noise):
+    """forced_playouts of SelfPlayEngine.play / play_stream / BatchedMCTS.search: None (off), or k_256, an int in [1,
+    4096] (k = k_256 / 256; KataGo's k = 2 is 512), which requires root noise (`noise` as root_noise_arg returned it;
+    root_noise=(alpha_256, 0) forces without mixing).  Returned as an int."""
+    if k_256 is None:
+        return None
+    if isinstance(k_256, bool) or not isinstance(k_256, numbers.Integral) or not 1 <= k_256 <= 4096:
+        raise ValueError("forced_playouts must be None or an int k_256 in [1, 4096], not %r" % (k_256,))
+    if noise is None:
+        raise ValueError("forced_playouts requires root_noise (root_noise=(alpha_256, 0) forces without mixing)")
+    return int(k_256)
+
+
+def search_forced(args, noise, counts, k_256, streams=None):
+    """iago_mcts_search_forced (include/iago_hip_serving.h): search_noise() with forced playouts -- at the ROOT of every
+    active game's search, when it has two or more children, a child with n >= 1 visits and stored prior p for which
+    float64(256 n n) < (float64(k_256) * float64(p)) * float64(N), N the root's visits, scores +inf in Node.select.
+    args, noise, counts, streams: as search_noise takes them; k_256 an int in [1, 4096]."""
+    z = _lib.SearchForcedArgs()
+    _root_noise_struct(noise, counts, z.noise)
+    z.streams = streams
+    z.k_256 = int(k_256)
+    check(_lib.lib().iago_mcts_search_forced(C.byref(args), C.byref(z), _stream()), "iago_mcts_search_forced")
+
+
+def prune_visits(tree, active, c_puct, k_256, pruned):
+    """iago_mcts_prune_visits (include/iago_hip_serving.h): the policy-target pruning of forced playouts.  For every game
+    with active[g] != 0 (active None: every game) the visit row of the tree's root into pruned[g] ((n_games, 64) int32)
+    with, for a root of K >= 2 children, every child c other than the first most visited one b reduced from its n visits
+    to m: F = the number of j in 1 .. n - 1 with forced(j, p_c, N); m = n; while n - m < F and the PUCT score of c with
+    m - 1 visits is below b's score, m -= 1; m = 0 if m < n and m == 1.  Fewer than two children: the raw row.  Inactive
+    games' rows are not touched; the trees are only read.  tree: TreePool.ref().  Returns pruned."""
+    check(_lib.lib().iago_mcts_prune_visits(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                            C.c_float(float(c_puct)), int(k_256), _dev(pruned, torch.int32, "pruned"),
+                                            _stream()), "iago_mcts_prune_visits")
+    return pruned
+
+
 def search_arena(args_a, args_b, check_result=True):
     """iago_mcts_search_arena (include/iago_hip_serving.h): the searches of `args_a` and `args_b` (two
     _lib.MctsSearchArgs, each a complete search of iago_mcts_search_persistent with its own nets, trees and rings) in

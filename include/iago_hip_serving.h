@@ -300,6 +300,53 @@ typedef struct iago_search_noise_args {
  */
 IAGO_API int iago_mcts_search_noise(const iago_mcts_search_args *args, const iago_search_noise_args *noise, void *stream);
 
+/* ------------------------------------------------------------------ forced playouts and policy-target pruning */
+
+/*
+ * FORCED PLAYOUTS at the root of a noised search, and the pruning that takes them out of the policy target again (KataGo's
+ * two rules), in exact arithmetic.  k_256 is an integer in 1 .. 4096, k = k_256 / 256 (KataGo's k = 2 is 512).
+ *   forced(n, p, N):  n >= 1  and  float64(256 n n) < (float64(k_256) * float64(p)) * float64(N)
+ * with n a child's visits, p its STORED float32 prior (after the + 0.1 of Node.__init__ and after the turn's noise mix) and
+ * N the root's n_visits, the number whose square root Node.select takes.  The left side and the first product are exact in
+ * float64, the second product rounds once; no contraction.  It says n < sqrt(k p N) without the root.
+ *   - selection: in Node.select at the ROOT OF THE SEARCH only (the path's first node), when the root has K >= 2 children, a
+ *     child with forced(n, p, N) scores +inf instead of Q + u; every other child scores as ever and the argmax is the first
+ *     maximum, so the lowest-indexed forced child is taken.  Nothing changes below the root.  A reused root carries its N
+ *     and its children's n from the turn before: the rule reads them as they are.
+ *   - pruning, after the turn's search, for a root with K >= 2 children: b is the first child with the most visits
+ *     (iago_mcts_best_move's), sq = sqrt(float64(N)), S* = Q_b + u_b as Node.select scores b under sq.  For every other
+ *     child c with n >= 1 visits: F is the number of j in 1 .. n - 1 with forced(j, p_c, N); m = n; while n - m < F and the
+ *     score of c with m - 1 visits (its Q and p as they are) is below S*, m -= 1; then, if m < n and m == 1, m = 0.  The
+ *     pruned row has m at c's cell, n_b at b's, 0 off the children.  A root with fewer than two children keeps its raw row.
+ *     The MOVE is still chosen from the raw counts (iago_mcts_best_move, iago_mcts_draw_move): only the target changes.
+ *
+ * iago_mcts_search_forced is iago_mcts_search_noise -- the same ONE search per launch, the same counts rows of
+ * iago_mcts_root_noise, the single launch or with `streams` the role split -- with the selection rule above at every
+ * active game's root.  Forcing lives only where the root noise lives: eps_256 = 0 forces without mixing.  The whole-game
+ * launch, streams, the wave search, matches, the arena and the per-playout kernels do not force.
+ * Refused (IAGO_ERR_INVALID, nothing launched): what iago_mcts_search_noise refuses (null args, a bad `noise`, reserved
+ * fields not 0, max_turns > 0 or games_total > 0), k_256 outside 1 .. 4096.
+ */
+typedef struct iago_search_forced_args {
+    iago_root_noise noise;        /* as iago_search_noise_args.noise */
+    iago_search_streams *streams; /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    int32_t k_256;                /* 1 .. 4096: k = k_256 / 256 */
+    int32_t reserved0;            /* 0 */
+    int64_t reserved[4];          /* 0 */
+} iago_search_forced_args;
+
+IAGO_API int iago_mcts_search_forced(const iago_mcts_search_args *args, const iago_search_forced_args *forced, void *stream);
+
+/*
+ * The pruning rule above on the trees as they stand, a sibling of iago_mcts_best_move: for every game with active[g] != 0
+ * (active NULL: every game) the pruned visit row of the tree's root into pruned[g][0 .. 63] -- for a root with fewer than
+ * two children the raw row iago_mcts_best_move gives (0 everywhere for a root without children or with a pass child).
+ * c_puct: the search's.  The trees are only read; inactive games' rows are not touched.
+ * Refused (IAGO_ERR_INVALID, nothing launched): a bad tree, k_256 outside 1 .. 4096, null `pruned`.
+ */
+IAGO_API int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
+                                    int32_t *pruned /* [n_games][64] */, void *stream);
+
 /* ------------------------------------------------------------------ arena */
 
 /*

@@ -11,8 +11,11 @@ cap_fast = n > 0: playout-cap randomisation, playout_cap = (n, cap_full) -- a qu
 window still receives tuples() only, the full turns' rows.
 noise_eps = e > 0: root noise, root_noise = (noise_alpha, e) in 256ths (alpha 77 / 256 = 0.3, eps 64 / 256 = 0.25 are
 the usual setting) -- off by default; such rounds play through the turn loop.
+forced_k = k > 0 (with noise_eps > 0): forced playouts and policy-target pruning, forced_playouts = k in 256ths (512 is
+KataGo's k = 2) -- the window then receives the PRUNED visit rows; 0 = off.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
-                                 [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]"""
+                                 [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
+                                 [forced_k=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +31,7 @@ iters, games, sims, window_rounds, updates, rows = arg(1, 100), arg(2, 64), arg(
 arena_every = arg(7, 0)
 playout_cap = (arg(8, 0), arg(9, 64)) if arg(8, 0) > 0 else None
 root_noise = (arg(11, 77), arg(10, 0)) if arg(10, 0) > 0 else None
+forced_playouts = arg(12, 0) if arg(12, 0) > 0 else None
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -63,7 +67,7 @@ def gate(i):
 def one():
     tr.model1.eval()
     vt.model.eval()
-    res = sp.play(sims, explore_turns=8, playout_cap=playout_cap, root_noise=root_noise)
+    res = sp.play(sims, explore_turns=8, playout_cap=playout_cap, root_noise=root_noise, forced_playouts=forced_playouts)
     added = tr.add_to_window(window, res.tuples())
     for _ in range(updates):
         s = window.sample(rows)
@@ -98,5 +102,5 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
-                  "root_noise": root_noise,
+                  "root_noise": root_noise, "forced_playouts": forced_playouts,
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {})}))
