@@ -13,6 +13,9 @@ reference's one-playout-at-a-time order.
 solve_empties = k: at a root with at most k empties get_move plays the exact endgame solver's move (the lowest-indexed
 move of the best final disc difference, engine.solve_endgame) and runs no search; n_solved counts these moves.  None,
 the default, always searches.
+
+backup = "reference" (the default: the reference's update_recursive, the same value at every level) or "negamax" (the
+sign turns at every level: engine.backup_arg; the persistent search only, with or without wave=).
 """
 import time
 
@@ -34,7 +37,7 @@ class MCTS(object):
 
     def __init__(self, lmbda=0.5, c_puct=1, n_thr=15, time_limit=10, policy_net=None,
                  value_net=None, rollout_weights=None, n_sims=None, capacity=65536, seed=0,
-                 use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None):
+                 use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None, backup="reference"):
         if policy_net is None or (value_net is None and lmbda < 1):
             raise ValueError("policy_net / value_net are required (the reference loads "
                              "./models/sl_model.npz and ./models/value_model.npz here)")
@@ -43,8 +46,8 @@ class MCTS(object):
         self.policy_net, self.value_net = policy_net, value_net
         self._m = engine.BatchedMCTS(1, policy_net, value_net, rollout_weights, lmbda=lmbda,
                                      c_puct=c_puct, n_thr=n_thr, capacity=capacity, seed=seed,
-                                     use_graph=use_graph, wave=wave, virtual_loss=virtual_loss)
-        self.wave = wave
+                                     use_graph=use_graph, wave=wave, virtual_loss=virtual_loss, backup=backup)
+        self.wave, self.backup = wave, self._m.backup
         self.chunk = max(8, 4 * wave)   # playouts per search of the time-limited loop
         self._one = torch.ones(1, dtype=torch.uint8, device="cuda")
         if solve_empties is not None and (isinstance(solve_empties, bool) or not isinstance(solve_empties, int) or

@@ -224,6 +224,7 @@ class MctsValueAhead(C.Structure):
 SEARCH_QUEUE_ENTRIES = 4096   # IAGO_SEARCH_QUEUE_ENTRIES
 SEARCH_GAMES_PER_WORKGROUP = 32   # IAGO_SEARCH_GAMES_PER_WORKGROUP
 SEARCH_CHAIN_SKIP = 0x100         # IAGO_SEARCH_CHAIN_SKIP (OR-ed into games_per_workgroup; totals is then [17])
+SEARCH_NEGAMAX = 0x200            # IAGO_SEARCH_NEGAMAX (include/iago_hip_serving.h; OR-ed in likewise: the negamax backup rule)
 # whole-game launches (max_turns > 0, games_total = 0): iago_mcts_search_args.active[g] selects the game's kind
 MATCH_MCTS_COLOUR_1 = 2   # a match: PV-MCTS plays colour 1 (moves first), the SL policy colour 2
 MATCH_MCTS_COLOUR_2 = 3   # a match: PV-MCTS plays colour 2, the SL policy colour 1 (the reference's game.py --auto)

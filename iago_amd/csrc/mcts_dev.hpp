@@ -240,7 +240,19 @@ __device__ __forceinline__ void visit(const Tree &T, int64_t at, float lv)
     *nq = make_uint2((uint32_t)n, __float_as_uint(q + (lv - q) / (float)n)); // MCTS.py:63
 }
 
+// What visit() takes at index d of a playout's path of path_n nodes (0: the root, path_n - 1: the leaf), lv the leaf's value
+// from the leaf mover's view.  The reference's rule (negamax == 0): lv at every level.  The negamax rule
+// (IAGO_SEARCH_NEGAMAX; DESIGN.md section 7, "Backup rule"): a node's Q is the value for the player who moved INTO it, so
+// the leaf takes -lv and the sign turns once per parent -- +lv where path_n - 1 - d is odd.  (-lv is exact)
+// negamax is 0 or 1: the sign bit is turned by arithmetic (path_n - 1 - d even <=> path_n - d odd), not by a select whose
+// lane mask the search kernels would have to keep
+__device__ __forceinline__ float backup_value(int negamax, float lv, int path_n, int d)
+{
+    return __uint_as_float(__float_as_uint(lv) ^ (((uint32_t)(path_n - d) & (uint32_t)negamax) << 31));
+}
+
 // Node.update_recursive (MCTS.py:65-72) from `node` up to the root: the same value at every level, no sign flip
+// (the per-playout launches keep the reference's rule)
 __device__ __forceinline__ void backup_climb(const Tree &T, int64_t base, int node, float lv)
 {
     for (int depth = 0; node >= 0 && depth <= MAX_DEPTH; depth++) {

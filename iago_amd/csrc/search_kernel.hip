@@ -167,6 +167,10 @@ struct SearchParams {
     int32_t noise_eps, noise_lg;
     // forced playouts (iago_mcts_search_forced; the NOISE instantiations alone read it): k_256, 0 = none forced
     int32_t forced_k_256;
+    // the backup rule (backup_game; IAGO_SEARCH_NEGAMAX): 0 = the reference's, the leaf's value at every level of the path;
+    // 1 = negamax, its sign turned from level to level (mcts_dev.hpp, backup_value).  (In the struct's tail padding: no
+    // parameter of the kernels moves)
+    int32_t negamax;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -289,7 +293,8 @@ __device__ __forceinline__ int path_entry(int path_at, const int32_t *gpath, int
 // unless a wave search, which also takes the playout's in-flight visit off every node of the path)
 template <bool WAVE>
 __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, uint32_t r, int leaf, bool fresh, float vg,
-                                            int path_n, const int8_t zl, const int path_at, const int64_t gt)
+                                            int path_n, const int8_t zl, const int negamax, const int path_at,
+                                            const int64_t gt)
 {
     const int64_t base = gt * (int64_t)S.T.capacity;
     const float lmbda = S.lmbda;
@@ -304,9 +309,13 @@ __device__ __forceinline__ void backup_game(const SearchParams &S, int64_t g, ui
     }
     const int len = path_n < S.path_stride ? path_n : S.path_stride;
     const int32_t *const gpath = S.path + g * (int64_t)S.path_stride;
+    // (the backup rule: a lane's indices d = r, r + 8, .. are of one parity, so one value per lane; the parity is that of
+    // the path's true length path_n, not of the `len` the buffer holds.  The reference's rule: lv itself.  `negamax`:
+    // S.negamax, from the workgroup's LDS)
+    const float lvd = backup_value(negamax, lv, path_n, (int)r);
     for (int d = (int)r; d < len; d += 8) {
         const int node = path_entry(path_at, gpath, d);
-        visit(S.T, base + node, lv);
+        visit(S.T, base + node, lvd);
         if constexpr (WAVE)
             S.T.nodes[base + node].reserved1 -= 1; // vv: this playout is no longer in flight
     }
@@ -392,6 +401,9 @@ struct GameLds {
     // pace[2]: the progress above which a game holds; pace[3]: the iteration's budget of requests nobody waits for
     int32_t pace[4];
     uint32_t claimed; // a stream: the first game id of the block the workgroup claimed
+    // S.negamax, read by the backups from here: as a kernel argument it is one more scalar kept (and spilled) across the
+    // whole loop
+    int32_t negamax;
     int8_t h_z[GAMES_PER_WG];
 };
 // a wave search adds, per tree of the workgroup, the slots of its current wave that have descended (the next one to go),
@@ -462,7 +474,7 @@ __device__ __forceinline__ void cursor_to(Cursor &C, int node, uint32_t fc, uint
 __device__ __forceinline__ void finish_playout(const SearchParams &S, const Slot &I, const GameLds &sh, Game &G,
                                                const Cursor &C, bool fresh, float v)
 {
-    backup_game<false>(S, I.g, I.r, C.leaf, fresh, v, C.path_n, sh.h_z[I.gl], I.path_at, I.g);
+    backup_game<false>(S, I.g, I.r, C.leaf, fresh, v, C.path_n, sh.h_z[I.gl], sh.negamax, I.path_at, I.g);
     G.n_done++;
     if (S.trace && I.r == 0u)
         atomicAdd((unsigned long long *)&S.totals[9], 1ull); // (diagnostic: playouts over time)
@@ -1101,7 +1113,7 @@ __device__ __forceinline__ void wave_backups(const SearchParams &S, const Slot &
     if (wg_handoff_or(ready)) {
         for (int j = 0; j < I.W; j++) {
             if (ready && I.s_in == j && G.state == ST_HAVE_VALUE) {
-                backup_game<true>(S, I.g, I.r, C.leaf, C.leaf_fresh, C.v_reply, C.path_n, sh.h_z[I.gl], I.path_at, I.gt);
+                backup_game<true>(S, I.g, I.r, C.leaf, C.leaf_fresh, C.v_reply, C.path_n, sh.h_z[I.gl], sh.negamax, I.path_at, I.gt);
                 if (S.trace && I.r == 0u)
                     atomicAdd((unsigned long long *)&S.totals[9], 1ull);
             }
@@ -1295,6 +1307,8 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
     int st_levels = 0, st_children = 0;
     if (I.tid < 7)
         sh.wg_count[I.tid] = 0u;
+    if (I.tid == 7)
+        sh.negamax = S.negamax;
     bool deferred = false;    // this game's rollout was put off to the next iteration's first pass
     bool table_ready = false; // the rollout's factor table is in LDS (from the first pass on)
     int contrib = 0;          // pacing: what this game has added to CTL_PROGRESS / whether CTL_PLAYING counts it
@@ -1828,10 +1842,11 @@ struct LaunchRequest {
     int forced_k_256 = 0;                         // forced playouts at the root (with noise): k_256, 0 = none
 };
 
-// games_per_workgroup without its flag (IAGO_SEARCH_CHAIN_SKIP)
+// games_per_workgroup without its flags (IAGO_SEARCH_CHAIN_SKIP, IAGO_SEARCH_NEGAMAX)
+constexpr int SEARCH_FLAGS = IAGO_SEARCH_CHAIN_SKIP | IAGO_SEARCH_NEGAMAX;
 int games_per_wg_of(const iago_mcts_search_args *a)
 {
-    return a->games_per_workgroup > 0 ? (a->games_per_workgroup & ~IAGO_SEARCH_CHAIN_SKIP) : a->games_per_workgroup;
+    return a->games_per_workgroup > 0 ? (a->games_per_workgroup & ~SEARCH_FLAGS) : a->games_per_workgroup;
 }
 
 // the arguments of a launch (what does not depend on the device)
@@ -1887,6 +1902,7 @@ int check_args(const iago_mcts_search_args *a, const iago_search_wave_args *wv)
 struct SearchGrid {
     int gpw;                                 // games (a wave search: slots) per game workgroup
     int chain_skip;                          // IAGO_SEARCH_CHAIN_SKIP of games_per_workgroup
+    int negamax;                             // IAGO_SEARCH_NEGAMAX of games_per_workgroup (the wave search has it too)
     int64_t n_slots, n_game_wgs, net_wgs, grid;
     int path_lds_cap, game_lds;              // the games' paths in dynamic LDS: bytes a workgroup may use; the game launch's
 };
@@ -1898,6 +1914,7 @@ void size_games(const iago_mcts_search_args *a, const iago_search_wave_args *wv,
     G.gpw = wv || games_per_wg_of(a) <= 0 ? GAMES_PER_WG : games_per_wg_of(a);
     // (the wave search's descent keeps its in-flight counts per node and walks every level)
     G.chain_skip = (!wv && a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_CHAIN_SKIP)) ? 1 : 0;
+    G.negamax = (a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_NEGAMAX)) ? 1 : 0;
     G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
     G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
     G.path_lds_cap = SEARCH_IMG_TOP;
@@ -2061,6 +2078,7 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.cap_fast = q.cap_fast;
     S.cap_full_256 = q.cap_full_256;
     S.chain_skip = G.chain_skip;
+    S.negamax = G.negamax;
     S.noise_counts = q.noise ? q.noise->counts : nullptr;
     S.noise_eps = q.noise ? q.noise->eps_256 : 0;
     S.noise_lg = q.noise ? __builtin_ctz((unsigned)q.noise->draws) : 0;

@@ -92,6 +92,24 @@ def _split_arg(want):
     return n
 
 
+BACKUP_RULES = ("reference", "negamax")
+
+
+def backup_arg(x):
+    """backup=: the rule by which a playout's leaf value climbs its path -- "reference" (the reference's
+    Node.update_recursive: the same value at every level) or "negamax" (the sign turns at every level: a node's Q is the
+    value for the player who moved into it; include/iago_hip_serving.h, IAGO_SEARCH_NEGAMAX).  The canonical string, or
+    ValueError."""
+    if isinstance(x, str) and x in BACKUP_RULES:
+        return x
+    raise ValueError("backup: \"reference\" or \"negamax\" expected, not %r" % (x,))
+
+
+_NEGAMAX_NEEDS = ("backup=\"negamax\" is offered for the persistent search only (the per-playout launches -- "
+                  "persistent=False, use_graph, the look-ahead, asynchronous steps and what a rollout_hook selects -- keep "
+                  "the reference's rule)")
+
+
 def suggest_capacity(n_sims, n_thr=15, moves=64, branching=12):
     """Nodes per game that a whole self-play game needs without ever compacting the pools:
     every expansion adds ~`branching` children, a search adds at most
@@ -215,9 +233,32 @@ class BatchedMCTS(object):
                  sync_free=None, lookahead=None, lookahead_slots=None, value_cache=None, lookahead_overlap=None,
                  z_log_rows=0, async_steps=None, async_parts=None, value_ahead=None, persistent=None,
                  net_workgroups=None, max_cus=None, split=None, wave=1, virtual_loss=1.0, chain_skip=True,
-                 path_stride=None):
+                 path_stride=None, backup="reference"):
         if n_thr < 1:
             raise ValueError("n_thr must be >= 1")
+        # (what the caller asked for explicitly, before the defaults below fill the options in: any of these selects
+        # the per-playout launches unless `persistent` says otherwise)
+        per_playout_asked = bool(use_graph or async_steps or value_ahead or lookahead is not None
+                                 or lookahead_overlap is not None or sync_free is not None)
+        env_p = os.environ.get("IAGO_PERSISTENT")
+
+        def schedule(can):
+            """The persistent search (True) or the per-playout launches, `can` saying whether the former applies: ON wherever
+            it does unless the caller asks for the per-playout launches (a rollout hook comes later); the environment
+            variable IAGO_PERSISTENT=0 / 1 overrides both (measurements: tools/time_value_ahead.py)."""
+            if env_p in ("0", "1"):
+                return can and env_p == "1"
+            return can and not per_playout_asked if persistent is None else persistent
+
+        # backup: the backup rule of the persistent search, "reference" (the default: today's trees bit for bit) or
+        # "negamax" (IAGO_SEARCH_NEGAMAX; backup_arg).  The per-playout launches have the reference's rule only.  A caller
+        # who asks for them and for "negamax" is refused here, before anything is allocated; where the ENGINE takes them
+        # (the persistent search does not apply: the nets, the rollout weights, too many games) the refusal comes once that
+        # is known, below -- after the tree pool and the state tensors exist, which the exception then frees.  A rollout
+        # hook, set after construction, is refused where it would be used (_backup_check)
+        self.backup = backup_arg(backup)
+        if self.backup == "negamax" and not schedule(True):
+            raise ValueError(_NEGAMAX_NEEDS)
         # (the persistent search) chain_skip: a descent jumps over the pass chain it remembers from its game's last
         # playout (IAGO_SEARCH_CHAIN_SKIP: timing only, same trees; False: every level is walked -- the A/B switch).
         # path_stride: entries of a game's path buffer (None: 520, the descent's own bound of 512 levels and a margin; at
@@ -239,10 +280,6 @@ class BatchedMCTS(object):
         ns = n_games * self.wave          # the slots: per-playout state of the search, W per tree
         # (checked before anything is allocated)
         want = _split_arg(split if split is not None else os.environ.get("IAGO_SEARCH_SPLIT", "auto"))
-        # (what the caller asked for explicitly, before the defaults below fill the options in: any of these selects
-        # the per-playout launches unless `persistent` says otherwise)
-        per_playout_asked = bool(use_graph or async_steps or value_ahead or lookahead is not None
-                                 or lookahead_overlap is not None or sync_free is not None)
         self.n_games = n_games
         self.policy_fn, self.value_fn, self.rollout_weights = policy_fn, value_fn, rollout_weights
         self.lmbda, self.c_puct, self.n_thr = float(lmbda), float(c_puct), int(n_thr)
@@ -352,20 +389,15 @@ class BatchedMCTS(object):
                  and getattr(policy_fn, "search_args", None) is not None and getattr(policy_fn, "split3", False)
                  and rollout_weights is not None and not rollout_weights.log_form and 0.0 <= self.lmbda < 1.0
                  and ns <= _lib.SEARCH_QUEUE_ENTRIES)
-        # Default: ON wherever it applies, unless the caller asks for the per-playout launches (use_graph,
-        # look-ahead / asynchronous-step / value-look-ahead options, a rollout hook comes later); the environment
-        # variable IAGO_PERSISTENT=0 / 1 overrides both (measurements: tools/time_value_ahead.py).
-        env_p = os.environ.get("IAGO_PERSISTENT")
-        if env_p in ("0", "1"):
-            persistent = can_p and env_p == "1"
-        elif persistent is None:
-            persistent = can_p and not per_playout_asked
+        persistent = schedule(can_p)
         if persistent and not can_p:
             raise ValueError("persistent needs the split-f16 value net and the three-piece policy net (modules with "
                              "search_args), product-form rollout weights, lmbda < 1 and at most %d games (the games' "
                              "workgroups may take half of the %d workgroups this device keeps resident)"
                              % (self.resident_workgroups // 2 * self.games_per_workgroup, self.resident_workgroups))
         self.persistent = bool(persistent)
+        if self.backup == "negamax" and not self.persistent:
+            raise ValueError(_NEGAMAX_NEEDS)
         if self.wave > 1 and not self.persistent:
             raise ValueError("wave > 1 needs the persistent search (the split-f16 value net, the three-piece policy net, "
                              "product-form rollout weights, lmbda < 1, at most %d slots)" % _lib.SEARCH_QUEUE_ENTRIES)
@@ -1285,7 +1317,8 @@ class BatchedMCTS(object):
         a.active = active.data_ptr()
         a.c_puct, a.lmbda, a.n_thr, a.n_sims = self.c_puct, self.lmbda, self.n_thr, int(n_sims)
         a.net_workgroups, a.time_limit_ms = self.net_workgroups, self.time_limit_ms
-        a.games_per_workgroup = self.games_per_workgroup | (_lib.SEARCH_CHAIN_SKIP if self.chain_skip else 0)
+        a.games_per_workgroup = (self.games_per_workgroup | (_lib.SEARCH_CHAIN_SKIP if self.chain_skip else 0)
+                                 | (_lib.SEARCH_NEGAMAX if self.backup == "negamax" else 0))
         a.pace_margin = self.pace_margin
         a.max_cus = self.max_cus
         a.value, a.policy, a.rollout = C.addressof(va), C.addressof(pa), C.addressof(ro.args)
@@ -1345,6 +1378,14 @@ class BatchedMCTS(object):
             rows = self._noise_counts = torch.zeros((self.n_games, 64), dtype=torch.int16, device=self.cur_own.device)
         return rows
 
+    def _backup_check(self):
+        """backup="negamax" is the persistent search's alone: a rollout hook (set after construction) would send search()
+        and SelfPlayEngine's turns through the per-playout launches, whose backup is the reference's.  Refused where a
+        search or a round of games begins, before anything is reset."""
+        if getattr(self, "backup", "reference") == "negamax" and (not getattr(self, "persistent", False)
+                                                                  or getattr(self, "rollout_hook", None) is not None):
+            raise ValueError(_NEGAMAX_NEEDS)
+
     def _root_noise_arg(self, root_noise):
         """search()'s root_noise, validated: offered for the persistent engine only."""
         noise = ops.root_noise_arg(root_noise)
@@ -1374,6 +1415,7 @@ class BatchedMCTS(object):
         forced playouts at the root of this search (include/iago_hip_serving.h, iago_mcts_search_forced) -- a root child
         with n >= 1 visits and stored prior p scores +inf in Node.select while 256 n^2 < k_256 p N, N the root's visits.
         pruned_visits() afterwards takes the forced visits out of the visit rows."""
+        self._backup_check()
         noise = self._root_noise_arg(root_noise)
         forced = ops.forced_playouts_arg(forced_playouts, noise)
         n_active, used = (int(v) for v in (self.search_counts(active).tolist() if counts is None else counts))
@@ -2110,6 +2152,7 @@ class SelfPlayEngine(object):
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
+        self.mcts._backup_check()
         self.mcts._root_noise_arg(rules.root_noise)   # (the persistent engine only: refused before anything is reset)
         res = self._one_launch(n_sims, self.B, handicap, record, rules)
         if res is None:
@@ -2134,6 +2177,7 @@ class SelfPlayEngine(object):
         forced_playouts: as in play(), with the record pi_raw."""
         rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts)
         m, T = self.mcts, self.max_turns
+        m._backup_check()
         m._root_noise_arg(rules.root_noise)
         n_games = int(n_games)
         if n_games < 1:
@@ -2167,6 +2211,7 @@ class SelfPlayEngine(object):
         _no_forced_playouts(forced_playouts, "play_match")
         rules = _play_rules(n_sims, solve_empties)
         col = _colour_arg(mcts_colour, self.B, self.mcts.cur_own.device, "play_match: mcts_colour")
+        self.mcts._backup_check()   # (a hooked negamax engine: refused before anything is reset)
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
         res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None, active=codes,
                                res=MatchResult())
@@ -2383,6 +2428,8 @@ class ArenaEngine(object):
         if one_launch is not None and not isinstance(one_launch, bool):
             raise ValueError("play: one_launch is None, True or False, not %r" % (one_launch,))
         one = self.ONE_LAUNCH_DEFAULT if one_launch is None else one_launch
+        for m in (self.a, self.b):   # (a hooked negamax engine: refused before anything is reset)
+            BatchedMCTS._backup_check(m)
         self.a.tree.reset()
         self.b.tree.reset()
         loop = SelfPlayEngine(self.a, self.max_turns)

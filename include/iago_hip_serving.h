@@ -43,6 +43,24 @@ typedef struct iago_search_wave_args {
  */
 IAGO_API int iago_mcts_search_wave(const iago_mcts_search_args *args, const iago_search_wave_args *wave, void *stream);
 
+/*
+ * The negamax backup: OR-ed into iago_mcts_search_args.games_per_workgroup (a positive one, like
+ * IAGO_SEARCH_CHAIN_SKIP; both are stripped before the number is read), for every entry point that takes those
+ * arguments -- the single launch, the role split, whole games, streams and matches, park / explore / cap / noise /
+ * forced, the wave search, and each argument set of iago_mcts_search_arena on its own (A and B may differ).
+ * Without it a playout's leaf value lv (leaf_mix of the value net and the rollout, both from the leaf mover's view) is
+ * added unchanged to every node of the path, the reference's Node.update_recursive.  With it a node's Q is the value
+ * from the view of the player who moved INTO the node: of the path node[0] (the root) .. node[L] (the leaf), node[d]
+ * is visited with +lv where L - d is odd and with -lv where it is even -- update_recursive starting with -lv at the
+ * leaf and negating once per parent.  A pass is a move: pass children are levels like any other.  The negation is
+ * exact and Node.update's arithmetic is unchanged.  leaf_value[], z_log, the stored values (node.v, the position
+ * table, values walked ahead), the selection rule, forced playouts and their pruning, the wave search's virtual loss
+ * and the moves read from the visit counts are untouched; the root's own Q plays no part in selection.
+ * The per-playout launches (iago_mcts_mix_backup_lookahead, iago_mcts_mix_backup, iago_mcts_backup) keep the
+ * reference's rule.
+ */
+#define IAGO_SEARCH_NEGAMAX 0x200
+
 /* ------------------------------------------------------------------ exact endgame */
 
 #define IAGO_ENDGAME_EXACT 0          /* mode: the exact final disc difference */

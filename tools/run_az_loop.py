@@ -13,9 +13,11 @@ noise_eps = e > 0: root noise, root_noise = (noise_alpha, e) in 256ths (alpha 77
 the usual setting) -- off by default; such rounds play through the turn loop.
 forced_k = k > 0 (with noise_eps > 0): forced playouts and policy-target pruning, forced_playouts = k in 256ths (512 is
 KataGo's k = 2) -- the window then receives the PRUNED visit rows; 0 = off.
+backup = 1: the negamax backup rule (engine.BatchedMCTS(backup="negamax")) in self-play and on both sides of the gate;
+0, the default: the reference's rule.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
-                                 [forced_k=0]"""
+                                 [forced_k=0] [backup=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,12 +34,13 @@ arena_every = arg(7, 0)
 playout_cap = (arg(8, 0), arg(9, 64)) if arg(8, 0) > 0 else None
 root_noise = (arg(11, 77), arg(10, 0)) if arg(10, 0) > 0 else None
 forced_playouts = arg(12, 0) if arg(12, 0) > 0 else None
+backup = engine.backup_arg("negamax" if arg(13, 0) else "reference")
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
 vt = SupervisedTrainer(network.Value(), "value", seed=0, native=True)
 m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                       capacity=engine.suggest_capacity(sims, 15), seed=1)   # default engine: the persistent search
+                       capacity=engine.suggest_capacity(sims, 15), seed=1, backup=backup)   # default engine: the persistent search
 sp = engine.SelfPlayEngine(m)
 window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
 kls, vlosses = [], []
@@ -46,9 +49,9 @@ if arena_every > 0:
     # the nets of k rounds ago: a frozen module pair of its own, an engine and tree pool of its own (other seed and ids)
     old_p, old_v = copy.deepcopy(tr.model1).eval(), copy.deepcopy(vt.model).eval()
     m_now = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                               capacity=engine.suggest_capacity(sims, 15), seed=3)
+                               capacity=engine.suggest_capacity(sims, 15), seed=3, backup=backup)
     m_old = engine.BatchedMCTS(games, old_p, old_v, ops.RolloutWeights(w, b), n_thr=15,
-                               capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games)
+                               capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games, backup=backup)
     arena = engine.ArenaEngine(m_now, m_old)
 
 
@@ -102,5 +105,5 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
-                  "root_noise": root_noise, "forced_playouts": forced_playouts,
+                  "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup,
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {})}))
