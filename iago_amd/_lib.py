@@ -50,13 +50,15 @@ EXPERIMENTAL_SYMBOLS = [
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
 # the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=)),
 # playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=)), forced
-# playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=))
+# playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=)), the fixed-depth alpha-beta opponent and its
+# random openings (ops.alphabeta_moves, ops.random_moves; SelfPlayEngine.play_match(opponent=AlphaBeta(d)))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
     "iago_mcts_root_noise", "iago_mcts_search_noise",
     "iago_mcts_search_forced", "iago_mcts_prune_visits",
+    "iago_alphabeta_moves", "iago_random_moves",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -240,6 +242,9 @@ NOISE_DRAWS = 256         # root_noise=(alpha_256, eps_256): the urn's draws N u
 CTL_BAD_DRAW = 13         # ctl word a match raises when a policy draw found no mass on the legal moves
 REC_DRAWN = 2             # rec_valid of a move played without a search (a policy draw or a forced final move)
 REC_FAST = 4              # rec_valid of a searched FAST turn of the playout cap (n_fast playouts; not a policy target)
+REC_OPENING = 5           # rec_valid of a random opening move (play_match(opening_turns=): nobody searched)
+OPENING_KEY = 0x4F50454E  # a match's random openings: Philox key = the seed with its high word XOR this (IAGO_OPENING_KEY)
+OPENING_SEED_XOR = OPENING_KEY << 32
 
 
 class MctsSearchArgs(C.Structure):
@@ -295,6 +300,19 @@ class PlayEndgameArgs(C.Structure):
         ("max_turns", C.c_int32), ("max_empties", C.c_int32), ("time_limit_ms", C.c_int32), ("reserved0", C.c_int32),
         ("rec_own", C.c_void_p), ("rec_opp", C.c_void_p), ("rec_valid", C.c_void_p), ("rec_move", C.c_void_p),
         ("rec_score", C.c_void_p), ("finished", C.c_void_p), ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
+ALPHABETA_MAX_DEPTH = 10   # IAGO_ALPHABETA_MAX_DEPTH
+
+
+class AlphaBetaArgs(C.Structure):
+    """Mirror of iago_alphabeta_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("n", C.c_int64),
+        ("depth", C.c_int32), ("time_limit_ms", C.c_int32),
+        ("score", C.c_void_p), ("move", C.c_void_p), ("nodes", C.c_void_p), ("done", C.c_void_p),
+        ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
     ]
 
 
@@ -480,6 +498,8 @@ def lib():
     L.iago_mcts_search_forced.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchForcedArgs), vp]
     L.iago_mcts_prune_visits.argtypes = [tp, vp, C.c_float, i32, vp, vp]
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
+    L.iago_alphabeta_moves.argtypes = [C.POINTER(AlphaBetaArgs), vp]
+    L.iago_random_moves.argtypes = [vp, vp, i64, C.c_uint64, C.c_uint32, C.c_uint32, i32, vp, vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int
     L.iago_policy_grad_workspace_bytes.restype = i64   # (bytes: beyond 2^31 from ~7,000 rows on)

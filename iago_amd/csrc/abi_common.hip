@@ -41,6 +41,22 @@ int iago_reserve_lds(const void *kernel, int bytes, std::atomic<uint64_t> &done,
     return IAGO_OK;
 }
 
+int iago_device_cus()
+{
+    static std::atomic<int> cus{0};
+    int c = cus.load(std::memory_order_relaxed);
+    if (c > 0)
+        return c;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) !=
+                                                 hipSuccess || c <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    cus.store(c, std::memory_order_relaxed);
+    return c;
+}
+
 extern "C" {
 
 int iago_abi_version(void) { return 13; }

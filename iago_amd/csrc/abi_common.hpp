@@ -9,6 +9,9 @@ int iago_fail(int code, const char *msg);
 // hipGetLastError() after a launch -> IAGO_OK / IAGO_ERR_HIP.
 int iago_check_launch(const char *where);
 
+// The current device's compute units (asked once per process); 0 when there is no HIP device.
+int iago_device_cus();
+
 #include <atomic>
 // One-time hipFuncSetAttribute(MaxDynamicSharedMemorySize) per (kernel, device): `done` is a
 // per-kernel bit mask of the devices already configured.  Safe from several threads (a lost

@@ -27,8 +27,6 @@
 
 #include "../../include/iago_hip_serving.h"
 
-#include <atomic>
-
 using namespace iago;
 using namespace iago::lane;
 
@@ -73,16 +71,6 @@ __device__ __forceinline__ int final_score(uint64_t own, uint64_t opp, int32_t w
 {
     const int d = __popcll(own) - __popcll(opp); // empty squares go to nobody (judge)
     return wld ? (d > 0) - (d < 0) : d;
-}
-
-__device__ __forceinline__ uint64_t legal_of(uint64_t own, uint64_t opp, const ShiftAmounts &SA)
-{
-    return legal_moves_1(own, opp, rev64(own), rev64(opp), SA);
-}
-
-__device__ __forceinline__ uint64_t flips_of(uint64_t own, uint64_t opp, uint32_t m)
-{
-    return flips_1(own, opp, rev64(own), rev64(opp), m);
 }
 
 // The untried move to search next: fewest opponent replies first above ORDER_EMPTIES empties, else the lowest index.
@@ -450,23 +438,6 @@ __global__ __launch_bounds__(WAVE) void play_endgame_kernel(PlayParams P)
     }
 }
 
-std::atomic<int> g_cus{0};
-
-int device_cus()
-{
-    int c = g_cus.load(std::memory_order_relaxed);
-    if (c > 0)
-        return c;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                 hipSuccess || c <= 0) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    g_cus.store(c, std::memory_order_relaxed);
-    return c;
-}
-
 } // namespace
 
 extern "C" int iago_solve_endgame(const iago_endgame_args *a, void *stream)
@@ -496,7 +467,7 @@ extern "C" int iago_solve_endgame(const iago_endgame_args *a, void *stream)
         (void)hipGetLastError();
         return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame: clearing solved");
     }
-    const int cus = device_cus();
+    const int cus = iago_device_cus();
     if (cus <= 0)
         return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame: no HIP device");
 
@@ -559,7 +530,7 @@ extern "C" int iago_play_endgame(const iago_play_endgame_args *a, void *stream)
         (void)hipGetLastError();
         return iago_fail(IAGO_ERR_HIP, "iago_play_endgame: clearing finished");
     }
-    const int cus = device_cus();
+    const int cus = iago_device_cus();
     if (cus <= 0)
         return iago_fail(IAGO_ERR_HIP, "iago_play_endgame: no HIP device");
 

@@ -1,7 +1,8 @@
 // othello_lane.hpp -- Othello rules with ONE LANE PER BOARD: legal moves and flips of a board that a lane
 // holds alone in two u64 (own = side to move, bit a = row*8+col), no cross-lane traffic.
 //
-// Shared by the leaf rollout (rollout_lpb_kernel.hip) and the endgame solver (endgame_kernel.hip).  Rules follow
+// Shared by the leaf rollout (rollout_lpb_kernel.hip), the endgame solver (endgame_kernel.hip) and the fixed-depth
+// alpha-beta opponent (alphabeta_kernel.hip).  Rules follow
 // the reference exactly (game.py:180-235); the rollout's bit-exact parity tests are tests/test_rollout_gpu.py, the
 // solver's tests/test_endgame_gpu.py.
 #pragma once
@@ -148,6 +149,17 @@ __device__ __forceinline__ uint64_t flips_1(uint64_t own, uint64_t opp, uint64_t
                                             uint32_t pos)
 {
     return flips_4(own, opp, pos) | rev64(flips_4(ro, rp, 63u - pos));
+}
+
+// the same two from the boards alone (the solver's and the alpha-beta opponent's nodes keep no reversed boards)
+__device__ __forceinline__ uint64_t legal_of(uint64_t own, uint64_t opp, const ShiftAmounts &SA)
+{
+    return legal_moves_1(own, opp, rev64(own), rev64(opp), SA);
+}
+
+__device__ __forceinline__ uint64_t flips_of(uint64_t own, uint64_t opp, uint32_t m)
+{
+    return flips_1(own, opp, rev64(own), rev64(opp), m);
 }
 
 // index of the lowest set bit; 31 for x = 0 (v_ffbl_b32 returns -1 then)

@@ -47,6 +47,21 @@ PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns pla
 NO_RULES = PlayRules(None, 0, None)
 
 
+class AlphaBeta(collections.namedtuple("AlphaBeta", "depth")):
+    """The fixed-depth alpha-beta opponent of SelfPlayEngine.play_match(opponent=): ops.alphabeta_moves at `depth` (an
+    int in [1, 10]), the outside yardstick that owes nothing to the nets."""
+    __slots__ = ()
+
+    def __new__(cls, depth):
+        return super(AlphaBeta, cls).__new__(cls, ops.alphabeta_depth_arg(depth))
+
+
+# a match beyond PV-MCTS against its own policy net, validated by play_match: opponent (None: the policy net, else an
+# AlphaBeta), opening_turns (an even int in [0, 16]: the turns both colours play ops.random_moves'), id_mod (the games
+# that share an opening: game g draws with id g mod id_mod)
+MatchRules = collections.namedtuple("MatchRules", "opponent opening_turns id_mod")
+
+
 def _read_back(values):
     """The device values of the dict `values` (0-dim tensors or short integer vectors; None: left out) on the host after
     ONE torch.cat(...).tolist() -- one host synchronisation: a dict under the same names, an int for a 0-dim value, a
@@ -1668,8 +1683,9 @@ _BAD_DRAW = ("a match's policy draw met NaN / inf / zero probability mass on the
 class MatchResult(SelfPlayResult):
     """The games of SelfPlayEngine.play_match: PV-MCTS against the SL policy (game.py:96-145,246-262).  As a
     SelfPlayResult, with valid 1 where PV-MCTS searched, 2 where a move was played without a search (the policy's
-    draw, or a final move that was the only one: pi is 0 there), 3 where PV-MCTS played the endgame solver's move
-    (solve_empties), 0 for a pass or no turn; mcts_colour: (B,) int8, the colour PV-MCTS played in each game.  score()
+    draw -- or the move of play_match's `opponent` --, or a final move that was the only one: pi is 0 there), 3 where
+    PV-MCTS played the endgame solver's move (solve_empties), 5 where either colour played a random opening move
+    (opening_turns), 0 for a pass or no turn; mcts_colour: (B,) int8, the colour PV-MCTS played in each game.  score()
     being the match's result, the (T, B) record of the solved rows' exact scores is `solved_score` here."""
 
     SCORE_RECORD = "solved_score"
@@ -1736,6 +1752,24 @@ def _no_forced_playouts(forced_playouts, who):
     if forced_playouts is not None:
         raise ValueError("%s: forced_playouts is not available (forced playouts live only in the noised self-play of "
                          "play / play_stream)" % who)
+
+
+def _match_rules(opponent, opening_turns, paired, mcts_colour, B):
+    """The MatchRules of play_match from its arguments: opponent None or an AlphaBeta, opening_turns an even int in
+    [0, 16], paired a bool that needs an even B and no mcts_colour beside it."""
+    if opponent is not None and not isinstance(opponent, AlphaBeta):
+        raise ValueError("play_match: opponent must be None (the policy net) or an AlphaBeta(depth), not %r" % (opponent,))
+    e = opening_turns
+    if isinstance(e, bool) or not isinstance(e, numbers.Integral) or not 0 <= e <= 16 or e % 2:
+        raise ValueError("play_match: opening_turns must be an even int in [0, 16], not %r" % (e,))
+    if not isinstance(paired, bool):
+        raise ValueError("play_match: paired must be True or False, not %r" % (paired,))
+    if paired and mcts_colour is not None:
+        raise ValueError("play_match: paired sets mcts_colour (colour 1 in the first half of the games, 2 in the second): "
+                         "pass one of the two")
+    if paired and B % 2:
+        raise ValueError("play_match: paired needs an even number of games, not %d" % B)
+    return MatchRules(opponent, int(e), B // 2 if paired else B)
 
 
 def _colour_arg(colour, B, dev, name, or_none=""):
@@ -1941,7 +1975,7 @@ class SelfPlayEngine(object):
             m.sim_counter = (s0 + s.n_sims) & 0xFFFFFFFF
         return 1
 
-    def _play_turns(self, sides, own, opp, record, res, rules, policy_moves=False, search=None):
+    def _play_turns(self, sides, own, opp, record, res, rules, policy_moves=False, search=None, match=None):
         """The games from (own, opp) turn by turn into res, in lockstep: per turn a search from every root that a side
         searches, the move, the books, and ONE host readback.  sides: the _Side's that search -- one of colour None is
         self-play (every active game searched), one of a colour with policy_moves is play_match (the other colour's
@@ -1956,9 +1990,13 @@ class SelfPlayEngine(object):
         (BatchedMCTS.cap_mask) search n_sims playouts, its fast ones n_fast, recorded with valid 4 (_search_sides).
         forced_playouts = k_256: the games the noised search forced (every searched one, under a cap the full ones) record
         their pruned visit row (BatchedMCTS.pruned_visits) in pi and the raw row in pi_raw; every other row is the raw one
-        in both.  The move comes from the raw counts."""
+        in both.  The move comes from the raw counts.  match (a MatchRules, with policy_moves): the other colour's
+        moves are ops.alphabeta_moves' where it names an opponent (one launch per turn, its `done` flags in the turn's
+        readback), still recorded with valid 2; at the turns below its opening_turns nobody searches or draws and both
+        colours play ops.random_moves' move, recorded with valid 5 (REC_OPENING)."""
         B, T, dev = self.B, self.max_turns, own.device
         k, cap = rules.solve_empties, rules.playout_cap
+        opponent, opening_turns = (match.opponent, match.opening_turns) if match is not None else (None, 0)
         search = search or self._search_sides
         stone_num = torch.full((B,), 4, dtype=torch.int32, device=dev)  # game.py:32
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -1978,14 +2016,19 @@ class SelfPlayEngine(object):
             # (the fewest empties any game starts with: a turn takes at most one, so before turn least - k no game can be
             # at k empties and nothing is launched for the solver)
             least = int(_empties(own, opp).min().item())
+        if k is not None or opponent is not None:
             full_board, no_board = torch.full_like(own, -1), torch.zeros_like(own)
 
         def movers(t):
             """Who moves at turn t: every side's `mine` / `act` (under a cap `full` / `fast` too).  Returns the games
-            whose move the policy draws, those whose move is forced, those whose move the solver plays (None where there
-            are none of the kind) and, as device values by name, the counts the turn's searches start from."""
-            on = active.bool()
+            whose move the policy (or the match's opponent) draws, those whose move is forced, those whose move the
+            solver plays, those that play a random opening move (None where there are none of the kind) and, as device
+            values by name, the counts the turn's searches start from."""
+            everyone = active.bool()
             drawn = forced = sol = at_end = None
+            # (an opening turn: every game that can move plays a random move, nobody searches or draws)
+            opening = everyone if t < opening_turns else None
+            on = everyone if opening is None else torch.zeros_like(everyone)
             if policy_moves:
                 # game.py:97-98: the only move of the last empty square, either side, no search
                 forced = on & (stone_num > 62) & ((legal & (legal - 1)) == 0)
@@ -2000,7 +2043,7 @@ class SelfPlayEngine(object):
                 if at_end is not None:
                     sol = mine & at_end if sol is None else sol | (mine & at_end)
                     mine = mine & ~at_end
-                s.mine, s.act, s.turn = mine, active if mine is on else mine.to(torch.uint8), t
+                s.mine, s.act, s.turn = mine, active if mine is everyone else mine.to(torch.uint8), t
                 if cap is None:
                     counts["counts", i] = s.mcts.search_counts(s.act)
                 else:
@@ -2008,14 +2051,14 @@ class SelfPlayEngine(object):
                     s.full = s.act ^ s.fast
                     counts["counts", i] = s.mcts.search_counts(s.full)
                     counts["counts_fast", i] = s.mcts.search_counts(s.fast)
-            return drawn, forced, sol, counts
+            return drawn, forced, sol, opening, counts
 
         def start_from(back):
             for i, s in enumerate(sides):
                 s.counts, s.counts_fast = back["counts", i], back.get(("counts_fast", i))
 
         t, launched = 0, 0
-        drawn, forced, sol, counts = movers(t)
+        drawn, forced, sol, opening, counts = movers(t)
         start_from(_read_back(counts))
         while t < T:
             # ONE readback per turn (below): every side's flags of this turn's search, the checks of its moves, the
@@ -2028,16 +2071,25 @@ class SelfPlayEngine(object):
                 ex = ops.solve_endgame(torch.where(sol, own, full_board), torch.where(sol, opp, no_board), mode="exact",
                                        max_empties=k, check_result=False)
             mv = none
-            if policy_moves:
-                with torch.no_grad():
-                    if hasattr(pf, "forward_boards_split3"):
-                        probs = pf.forward_boards_split3(own, opp)
-                    else:
-                        probs = pf(ops.encode_planes(own, opp))
-                draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)), seed=key,
-                                        id_base=m0.game_id_base, step=t, stream_id=0)
+            ab = None
+            if policy_moves and opening is None:
+                if opponent is not None:
+                    # (a game that the opponent does not move in sends a full board: no search, no refusal)
+                    ab = ops.alphabeta_moves(torch.where(drawn, own, full_board), torch.where(drawn, opp, no_board),
+                                             opponent.depth, check_result=False)
+                    draw = ab["move"]
+                else:
+                    with torch.no_grad():
+                        if hasattr(pf, "forward_boards_split3"):
+                            probs = pf.forward_boards_split3(own, opp)
+                        else:
+                            probs = pf(ops.encode_planes(own, opp))
+                    draw = ops.sample_moves(probs.reshape(B, 64), torch.where(drawn, legal, torch.zeros_like(legal)),
+                                            seed=key, id_base=m0.game_id_base, step=t, stream_id=0)
                 only = ((legal.reshape(B, 1) >> cells) & 1).argmax(dim=1).to(torch.int8)
                 mv = torch.where(drawn, draw, torch.where(forced, only, none))
+            elif opening is not None:
+                mv = torch.where(opening, ops.random_moves(own, opp, m0.seed, m0.game_id_base, match.id_mod, t), none)
             for s in reversed(sides):
                 mv = torch.where(s.mine, s.move, mv)
             if sol is not None:
@@ -2054,7 +2106,9 @@ class SelfPlayEngine(object):
                         f = s.act if cap is None else s.full
                         pi = torch.where(f.reshape(B, 1) != 0, s.mcts.pruned_visits(f, rules.forced_playouts), pi)
                 if policy_moves:
-                    valid = valid + 2 * (drawn | forced).to(torch.uint8)
+                    valid = valid + _lib.REC_DRAWN * (drawn | forced).to(torch.uint8)
+                if opening is not None:
+                    valid = valid + _lib.REC_OPENING * opening.to(torch.uint8)
                 if sol is not None:
                     valid = valid + 3 * sol.to(torch.uint8)
                     rec["score"][t] = torch.where(sol, ex["score"], torch.zeros_like(ex["score"]))
@@ -2072,9 +2126,10 @@ class SelfPlayEngine(object):
             # (mv is -2 only where best_move found a searched root without children: a drawn move is -1 .. 64, a solved
             # one a legal move)
             checks = dict(no_children=(mv == -2).any(), all_done=done.all(),
-                          bad_draw=(drawn & (draw == 64)).any() if policy_moves else None,
-                          unsolved=(ex["solved"] == 0).any() if sol is not None else None)
-            drawn, forced, sol, counts = movers(t)
+                          bad_draw=(drawn & (draw == 64)).any() if policy_moves and opening is None else None,
+                          unsolved=(ex["solved"] == 0).any() if sol is not None else None,
+                          unfinished=(ab["done"] == 0).any() if ab is not None else None)
+            drawn, forced, sol, opening, counts = movers(t)
             back = _read_back({**{("flags", i): s.mcts.error_flags(s.gave_up) for i, s in enumerate(sides)},
                                **checks, **counts})
             for i, s in enumerate(sides):
@@ -2087,6 +2142,9 @@ class SelfPlayEngine(object):
             if back.get("unsolved"):
                 raise _lib.IagoError("solve_empties = %d: the endgame solver refused or did not finish a position at "
                                      "turn %d" % (k, t - 1))
+            if back.get("unfinished"):
+                raise _lib.IagoError("play_match: the alpha-beta opponent (depth %d) did not finish a position at turn %d"
+                                     % (opponent.depth, t - 1))
             if t % 2 == 0 and back["all_done"]:
                 break
             start_from(back)
@@ -2193,7 +2251,8 @@ class SelfPlayEngine(object):
             res = self._play_batches(n_sims, n_games, handicap, record, rules)
         return res
 
-    def play_match(self, n_sims, mcts_colour=2, record=True, solve_empties=None, forced_playouts=None):
+    def play_match(self, n_sims, mcts_colour=None, record=True, solve_empties=None, forced_playouts=None, opponent=None,
+                   opening_turns=0, paired=False):
         """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
         `game.py --auto` (game.py:96-145,246-262) -- with the engine's nets: in game g PV-MCTS plays colour
         mcts_colour[g] (1 moves first; an int: every game; 2, the default, is the reference's setting) and the policy
@@ -2207,17 +2266,37 @@ class SelfPlayEngine(object):
         exact solver's move at its turns of at most k empties (valid 3) -- not the forced final move, which keeps
         precedence (valid 2), and not the policy's turns.  Such a match ALWAYS runs through the turn loop (launches =
         its turns): a one-launch match cannot hand its games over, the policy side needs the net workgroups to the last
-        move.  forced_playouts: None; anything else is a ValueError (a match has no root noise and does not force)."""
+        move.  forced_playouts: None; anything else is a ValueError (a match has no root noise and does not force).
+        opponent = AlphaBeta(d) (None, the default: the policy net): the other colour's moves are the fixed-depth
+        alpha-beta search's (ops.alphabeta_moves at depth d: the lowest-indexed move of the best value), an opponent that
+        owes nothing to the nets.  Its move is recorded with valid 2 and advances the tree like any move; the only final
+        move keeps its precedence; solve_empties still applies to PV-MCTS's turns alone; a position the opponent does not
+        finish raises IagoError.  opening_turns = e (an even int in [0, 16]; 0, the default: none): at the turns below e
+        nobody searches and both colours play ops.random_moves' move -- the r-th lowest legal cell, r = (w * K) >> 32 with
+        w the Philox word of (seed ^ OPENING_SEED_XOR; game_id_base + g mod id_mod, t) -- recorded with valid 5
+        (REC_OPENING: tuples() never see them), so that a batch against a deterministic opponent is many games.
+        ("Nobody searches": no game is in the search's mask.  The turn loop still launches the search with an empty mask
+        at an opening turn, as it does at the opponent's turns, which keeps sim_counter advancing by n_sims per turn.)
+        paired = True (needs an even B, and no mcts_colour: it sets it): games g and g + B / 2 draw the same opening
+        (id_mod = B / 2, else B) and PV-MCTS plays colour 1 in the first half and colour 2 in the second.  With an
+        opponent or opening_turns > 0 the match ALWAYS runs through the turn loop (launches = its turns); with all three at
+        their defaults it is the match above, argument for argument.  mcts_colour: None is 2, or with paired the halves."""
         _no_forced_playouts(forced_playouts, "play_match")
         rules = _play_rules(n_sims, solve_empties)
-        col = _colour_arg(mcts_colour, self.B, self.mcts.cur_own.device, "play_match: mcts_colour")
+        match = _match_rules(opponent, opening_turns, paired, mcts_colour, self.B)
+        dev = self.mcts.cur_own.device
+        if paired:
+            col = torch.cat([torch.full((self.B // 2,), c, dtype=torch.int8, device=dev) for c in (1, 2)])
+        else:
+            col = _colour_arg(2 if mcts_colour is None else mcts_colour, self.B, dev, "play_match: mcts_colour")
         self.mcts._backup_check()   # (a hooked negamax engine: refused before anything is reset)
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
-        res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None, active=codes,
-                               res=MatchResult())
+        plain = match.opponent is None and match.opening_turns == 0
+        res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None and plain,
+                               active=codes, res=MatchResult())
         if res is None:
             res = self._play_turns([_Side(self.mcts, n_sims, col)], *self._start_boards(self.B), record, MatchResult(),
-                                   rules, policy_moves=True)
+                                   rules, policy_moves=True, match=None if plain else match)
         res.mcts_colour = col
         return res
 

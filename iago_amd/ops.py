@@ -1135,6 +1135,68 @@ def check_play_endgame(back, out, max_empties, time_limit_ms):
     raise err
 
 
+def alphabeta_depth_arg(depth):
+    """depth of alphabeta_moves / engine.AlphaBeta: an int in [1, 10], returned as an int."""
+    if isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not 1 <= depth <= _lib.ALPHABETA_MAX_DEPTH:
+        raise ValueError("alpha-beta depth must be an int in [1, %d], not %r" % (_lib.ALPHABETA_MAX_DEPTH, depth))
+    return int(depth)
+
+
+def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True):
+    """A fixed-depth alpha-beta search on a hand-written evaluation for every position (iago_alphabeta_moves,
+    include/iago_hip_serving.h): the opponent that owes nothing to the nets.
+
+    own / opp: (n,) int64 CUDA tensors, own = side to move; depth: an int in [1, 10] (ValueError otherwise), one value
+    per launch.  Returns a dict of device tensors: score (n,) int16 = search(own, opp, depth), move (n,) int8 = the
+    lowest-indexed move whose value equals the score (-1: the side to move must pass, -2: the game is over), nodes
+    (n,) int64, done (n,) uint8, ctl (4,) int32.  check_result (one host sync): raise IagoError when the launch gave up
+    at time_limit_ms, refused a position (own & opp != 0) or overflowed its stack (ctl[3]); the result is the error's
+    `result` attribute."""
+    depth = alphabeta_depth_arg(depth)
+    n = own.numel()
+    if opp.numel() != n:
+        raise ValueError("own/opp sizes differ")
+    dev = own.device
+    out = dict(score=torch.empty(n, dtype=torch.int16, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               nodes=torch.empty(n, dtype=torch.int64, device=dev), done=torch.empty(n, dtype=torch.uint8, device=dev),
+               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev))
+    a = _lib.AlphaBetaArgs()
+    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
+    a.depth, a.time_limit_ms = depth, int(time_limit_ms)
+    a.score, a.move = _dev(out["score"], torch.int16, "score"), _dev(out["move"], torch.int8, "move")
+    a.nodes, a.done = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["done"], torch.uint8, "done")
+    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
+    check(_lib.lib().iago_alphabeta_moves(C.byref(a), _stream()), "iago_alphabeta_moves")
+    if check_result:
+        gave_up, _, refused, overflow = (int(v) for v in out["ctl"].tolist())
+        if gave_up or refused or overflow:
+            if overflow:
+                what = "a position needed more stack frames than depth = %d sizes (ctl[3] set)" % depth
+            elif gave_up:
+                what = "gave up at its clock limit (%d ms): %d of %d positions unfinished" % (
+                    time_limit_ms, n - int(out["done"].sum().item()), n)
+            else:
+                what = "%d positions refused (own & opp != 0)" % refused
+            err = _lib.IagoError("iago_alphabeta_moves: " + what)
+            err.result = out
+            raise err
+    return out
+
+
+def random_moves(own, opp, seed, id_base, id_mod, turn):
+    """The random opening draw (iago_random_moves, include/iago_hip_serving.h): (n,) int8, the move of every game's mover
+    (own to move) -- with K >= 1 legal moves the r-th lowest legal cell, r = (w * K) >> 32, w = word turn & 3 of
+    Philox4x32-10 on (id_base + g mod id_mod, turn >> 2, 0, 0) under seed ^ OPENING_SEED_XOR; -1 where it has none."""
+    n = own.numel()
+    if opp.numel() != n:
+        raise ValueError("own/opp sizes differ")
+    move = torch.empty(n, dtype=torch.int8, device=own.device)
+    check(_lib.lib().iago_random_moves(_dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n,
+                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(id_base) & 0xFFFFFFFF, int(id_mod),
+                                       int(turn), _dev(move, torch.int8, "move"), _stream()), "iago_random_moves")
+    return move
+
+
 def explore_turns_arg(k):
     """explore_turns of SelfPlayEngine.play / play_stream: None or 0 (off: None is returned), or a positive int (at most
     IAGO_MAX_TURNS turns are drawn, a larger value means every turn)."""

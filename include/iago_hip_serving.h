@@ -392,6 +392,62 @@ IAGO_API int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *a
  */
 IAGO_API int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago_mcts_search_args *b, void *stream);
 
+/* ------------------------------------------------------------------ a fixed-depth alpha-beta opponent */
+
+#define IAGO_ALPHABETA_MAX_DEPTH 10
+#define IAGO_OPENING_KEY 0x4F50454Eu /* ("OPEN") the opening draws' Philox key: the seed with its high word XOR this */
+
+typedef struct iago_alphabeta_args {
+    const uint64_t *own; /* [n] side to move (bit a = row*8+col) */
+    const uint64_t *opp; /* [n] its opponent */
+    int64_t n;
+    int32_t depth;         /* 1 .. IAGO_ALPHABETA_MAX_DEPTH, one value per launch */
+    int32_t time_limit_ms; /* 1 .. IAGO_ENDGAME_MAX_TIME_MS: the launch gives up after this long on the device clock */
+    int16_t *score;        /* [n] out */
+    int8_t *move;          /* [n] out */
+    int64_t *nodes;        /* [n] out: nodes visited, leaves included */
+    uint8_t *done;         /* [n] out: 1 = score and move are the search's */
+    uint32_t *ctl;         /* [IAGO_ENDGAME_CTL_WORDS] cleared by the call; [0] != 0: gave up, [1]: the claim counter,
+                              [2]: positions refused, [3] != 0: a stack overflow */
+    int64_t reserved[4];   /* 0 */
+} iago_alphabeta_args;
+
+/*
+ * A fixed-depth negamax search on a hand-written evaluation for n positions, one lane per position: an opponent that
+ * owes nothing to the nets.  The rule, in integers, on the library's rules (a side with no legal move passes, the game
+ * ends when neither side can move):
+ *   search(own, opp, d):
+ *       no legal move: neither side has one -> terminal(own, opp), at any depth; else -search(opp, own, d) (a pass in
+ *       place: it costs no depth);
+ *       d == 0 -> eval(own, opp);
+ *       else the maximum over the legal moves m of -search(play(own, opp, m), d - 1).
+ *   terminal = 10000 sign(D) + 100 D, D = #own - #opp (empty squares to nobody), so |terminal| <= 16400;
+ *   eval = sum_k v_k (popcount(own & M_k) - popcount(opp & M_k)) + 8 (popcount(legal(own, opp)) - popcount(legal(opp, own)))
+ *   over the seven classes (v, M) that partition the board and are invariant under its eight symmetries:
+ *       100 0x8100000000000081   -20 0x4281000000008142   -50 0x0042000000004200   10 0x2400810000810024
+ *         5 0x1800008181000018    -2 0x003C424242423C00    -1 0x00003C3C3C3C0000
+ *   |eval| < 10000: any decided game outranks any heuristic; every value fits an int16 (the root's window is +-32767).
+ * score[i] = search(own, opp, depth); move[i] = the LOWEST-indexed move whose value equals it -- found with
+ * iago_solve_endgame's root rule, so (score, move) depend on neither move order nor pruning; -1: the mover must pass
+ * (score is the negated value for the opponent), -2: the game is over.  nodes[i] counts the nodes visited.
+ * A position with own & opp != 0 is refused: done[i] = 0, ctl[2] counts it.  done[] and ctl are cleared on `stream`
+ * before the launch; it stops on its own clock after time_limit_ms (ctl[0] != 0, the unfinished positions keep
+ * done[i] = 0).  Host-side refusals (IAGO_ERR_INVALID, nothing launched): a null args / ctl, a null array with n > 0,
+ * n < 0, a depth or time_limit_ms out of range, reserved fields not 0.
+ */
+IAGO_API int iago_alphabeta_moves(const iago_alphabeta_args *args, void *stream);
+
+/*
+ * The random opening of a match against that opponent, a thread per game: the mover of game g (own[g] to move) with
+ * K >= 1 legal moves plays the r-th lowest legal cell, r = (uint64(w) * K) >> 32, w = word turn & 3 of Philox4x32-10 on
+ * the counter (id_base + g mod id_mod, turn >> 2, 0, 0) under the key `seed` with its high word XOR IAGO_OPENING_KEY (the
+ * raw word, no float).  move[g] = -1 where the mover has no legal move.  id_mod = n / 2 gives games g and g + n / 2 the
+ * same draws (a paired match), id_mod = n every game its own.  Refused (IAGO_ERR_INVALID): a null array with n > 0,
+ * n < 0, id_mod == 0, a turn outside 0 .. IAGO_MAX_TURNS - 1.
+ */
+IAGO_API int iago_random_moves(const uint64_t *own, const uint64_t *opp, int64_t n, uint64_t seed, uint32_t id_base,
+                               uint32_t id_mod, int32_t turn, int8_t *move, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,9 +15,12 @@ forced_k = k > 0 (with noise_eps > 0): forced playouts and policy-target pruning
 KataGo's k = 2) -- the window then receives the PRUNED visit rows; 0 = off.
 backup = 1: the negamax backup rule (engine.BatchedMCTS(backup="negamax")) in self-play and on both sides of the gate;
 0, the default: the reference's rule.
+yardstick_every = k > 0: every k rounds the current nets play `games` games (paired, 8 random opening turns, `sims`
+playouts a move) against the fixed-depth alpha-beta opponent of depth yardstick_depth (SelfPlayEngine.play_match(opponent=
+engine.AlphaBeta(d))), the one opponent that owes nothing to the nets, and the scores join the JSON line; 0 = off.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
-                                 [forced_k=0] [backup=0]"""
+                                 [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +38,7 @@ playout_cap = (arg(8, 0), arg(9, 64)) if arg(8, 0) > 0 else None
 root_noise = (arg(11, 77), arg(10, 0)) if arg(10, 0) > 0 else None
 forced_playouts = arg(12, 0) if arg(12, 0) > 0 else None
 backup = engine.backup_arg("negamax" if arg(13, 0) else "reference")
+yardstick_every, yardstick_depth = arg(14, 0), arg(15, 2)
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -53,6 +57,21 @@ if arena_every > 0:
     m_old = engine.BatchedMCTS(games, old_p, old_v, ops.RolloutWeights(w, b), n_thr=15,
                                capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games, backup=backup)
     arena = engine.ArenaEngine(m_now, m_old)
+yardstick_scores = []
+if yardstick_every > 0:
+    # an engine and tree pool of its own on the CURRENT nets (other seed and ids), against engine.AlphaBeta
+    m_yard = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
+                                capacity=engine.suggest_capacity(sims, 15), seed=5, game_id_base=2 * games, backup=backup)
+    yard = engine.SelfPlayEngine(m_yard)
+    opponent = engine.AlphaBeta(yardstick_depth)
+
+
+def yardstick(i):
+    """After round i + 1: the current nets against the fixed opponent."""
+    tr.model1.eval()
+    vt.model.eval()
+    s = yard.play_match(sims, opponent=opponent, opening_turns=8, paired=games % 2 == 0, record=False).score()
+    yardstick_scores.append(dict(round=i + 1, **s))
 
 
 def gate(i):
@@ -90,6 +109,8 @@ for i in range(iters):
     added += one()
     if arena_every > 0 and (i + 1) % arena_every == 0:
         gate(i)
+    if yardstick_every > 0 and (i + 1) % yardstick_every == 0:
+        yardstick(i)
     if (i + 1) % 25 == 0:
         print("round %d, %.1f s" % (i + 1, time.perf_counter() - t0), file=sys.stderr, flush=True)
 torch.cuda.synchronize()
@@ -106,4 +127,6 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
                   "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup,
-                  **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {})}))
+                  **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {}),
+                  **({"yardstick_every": yardstick_every, "yardstick_depth": yardstick_depth,
+                      "yardstick": yardstick_scores} if yardstick_every > 0 else {})}))
