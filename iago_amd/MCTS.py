@@ -16,6 +16,9 @@ the default, always searches.
 
 backup = "reference" (the default: the reference's update_recursive, the same value at every level) or "negamax" (the
 sign turns at every level: engine.backup_arg; the persistent search only, with or without wave=).
+
+selection = "reference" (the default: the reference's Node.select, priors prob + 0.1 and 0.01 + n under the exploration
+term) or "alphazero" (priors prob, 1 + n: engine.selection_arg; the persistent search only, with or without wave=).
 """
 import time
 
@@ -37,7 +40,8 @@ class MCTS(object):
 
     def __init__(self, lmbda=0.5, c_puct=1, n_thr=15, time_limit=10, policy_net=None,
                  value_net=None, rollout_weights=None, n_sims=None, capacity=65536, seed=0,
-                 use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None, backup="reference"):
+                 use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None, backup="reference",
+                 selection="reference"):
         if policy_net is None or (value_net is None and lmbda < 1):
             raise ValueError("policy_net / value_net are required (the reference loads "
                              "./models/sl_model.npz and ./models/value_model.npz here)")
@@ -46,8 +50,9 @@ class MCTS(object):
         self.policy_net, self.value_net = policy_net, value_net
         self._m = engine.BatchedMCTS(1, policy_net, value_net, rollout_weights, lmbda=lmbda,
                                      c_puct=c_puct, n_thr=n_thr, capacity=capacity, seed=seed,
-                                     use_graph=use_graph, wave=wave, virtual_loss=virtual_loss, backup=backup)
-        self.wave, self.backup = wave, self._m.backup
+                                     use_graph=use_graph, wave=wave, virtual_loss=virtual_loss, backup=backup,
+                                     selection=selection)
+        self.wave, self.backup, self.selection = wave, self._m.backup, self._m.selection
         self.chunk = max(8, 4 * wave)   # playouts per search of the time-limited loop
         self._one = torch.ones(1, dtype=torch.uint8, device="cuda")
         if solve_empties is not None and (isinstance(solve_empties, bool) or not isinstance(solve_empties, int) or

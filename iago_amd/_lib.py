@@ -57,7 +57,7 @@ SERVING_SYMBOLS = [
     "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
     "iago_mcts_root_noise", "iago_mcts_search_noise",
-    "iago_mcts_search_forced", "iago_mcts_prune_visits",
+    "iago_mcts_search_forced", "iago_mcts_prune_visits", "iago_mcts_prune_visits_rule",
     "iago_alphabeta_moves", "iago_random_moves",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
@@ -227,6 +227,7 @@ SEARCH_QUEUE_ENTRIES = 4096   # IAGO_SEARCH_QUEUE_ENTRIES
 SEARCH_GAMES_PER_WORKGROUP = 32   # IAGO_SEARCH_GAMES_PER_WORKGROUP
 SEARCH_CHAIN_SKIP = 0x100         # IAGO_SEARCH_CHAIN_SKIP (OR-ed into games_per_workgroup; totals is then [17])
 SEARCH_NEGAMAX = 0x200            # IAGO_SEARCH_NEGAMAX (include/iago_hip_serving.h; OR-ed in likewise: the negamax backup rule)
+SEARCH_PUCT_AZ = 0x400            # IAGO_SEARCH_PUCT_AZ (include/iago_hip_serving.h; OR-ed in likewise: the AlphaZero selection rule)
 # whole-game launches (max_turns > 0, games_total = 0): iago_mcts_search_args.active[g] selects the game's kind
 MATCH_MCTS_COLOUR_1 = 2   # a match: PV-MCTS plays colour 1 (moves first), the SL policy colour 2
 MATCH_MCTS_COLOUR_2 = 3   # a match: PV-MCTS plays colour 2, the SL policy colour 1 (the reference's game.py --auto)
@@ -497,6 +498,7 @@ def lib():
     L.iago_mcts_search_noise.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchNoiseArgs), vp]
     L.iago_mcts_search_forced.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchForcedArgs), vp]
     L.iago_mcts_prune_visits.argtypes = [tp, vp, C.c_float, i32, vp, vp]
+    L.iago_mcts_prune_visits_rule.argtypes = [tp, vp, C.c_float, i32, i32, vp, vp]
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
     L.iago_alphabeta_moves.argtypes = [C.POINTER(AlphaBetaArgs), vp]
     L.iago_random_moves.argtypes = [vp, vp, i64, C.c_uint64, C.c_uint32, C.c_uint32, i32, vp, vp]

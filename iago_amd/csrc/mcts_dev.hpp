@@ -34,7 +34,8 @@ __device__ __forceinline__ void init_node(const Tree &T, int64_t i, int parent, 
         T.nodes[i].v = __builtin_nanf(""); // value_func(node) not evaluated yet
 }
 
-// Node(None, 1.0) as game g's only node, its root (MCTS.py:81,154; one lane)
+// Node(None, 1.0) as game g's only node, its root (MCTS.py:81,154; one lane).  1.1 under either selection rule (below): a
+// root's prior is never read
 __device__ __forceinline__ void fresh_root(const Tree &T, int64_t g, int64_t base)
 {
     init_node(T, base, -1, -2, 1.0f + 0.1f);
@@ -49,15 +50,26 @@ __device__ __forceinline__ void node_record(const Tree &T, int64_t at, uint4 &s,
     l = ((const uint4 *)&T.nodes[at])[1];
 }
 
+// ---- the selection rule ("Selection rule"; the contract is iago_hip_serving.h's, IAGO_SEARCH_PUCT_AZ): two
+// constants, uniform over a launch.  prior_off is added to the prior a child stores (make_children), visit_off to the
+// visits in the exploration term's denominator (puct_score, wave_score).  The reference's rule: 0.1f and 0.01 (MCTS.py:19,
+// 49) -- the same operations on the same bits as the literals were, so its trees are what they always were.  The AlphaZero
+// rule: 0.0f and 1.0 -- P = prob (x + 0.0f is x for the policy's positive outputs), U = c_puct P sqrt(N) / (1 + n).  A
+// root made by fresh_root keeps 1.0f + 0.1f under both (its prior is never read).  The per-playout kernels
+// (mcts_kernels.hip) pass the reference's pair
+constexpr float PRIOR_OFF_REFERENCE = 0.1f, PRIOR_OFF_ALPHAZERO = 0.0f;
+constexpr double VISIT_OFF_REFERENCE = 0.01, VISIT_OFF_ALPHAZERO = 1.0;
+
 // ---- Node.select (MCTS.py:39-49)
 
 // Node.get_value (MCTS.py:75-76) of a child with prior p, value q and n visits under a parent with sq =
-// np.sqrt(parent.n_visits): float32 c_puct * P, float64 sqrt, divide and add, as numpy >= 2 promotes them (MCTS.py:49)
-__device__ __forceinline__ double puct_score(float c_puct, float p, float q, int n, double sq)
+// np.sqrt(parent.n_visits): float32 c_puct * P, float64 sqrt, divide and add, as numpy >= 2 promotes them (MCTS.py:49).
+// visit_off: the rule's (above)
+__device__ __forceinline__ double puct_score(float c_puct, float p, float q, int n, double sq, double visit_off)
 {
 #pragma clang fp contract(off)
     const float cp = c_puct * p;
-    const double u = (double)cp * sq / (0.01 + (double)n);
+    const double u = (double)cp * sq / (visit_off + (double)n);
     return (double)q + u;
 }
 
@@ -78,12 +90,13 @@ __device__ __forceinline__ bool forced_child(int n, float p, double k_256, doubl
 // in-flight visits (vv) of a wave search: the score of a child when a playout of the wave is on its way through it --
 // n + vv visits, the in-flight ones counted as a loss of `vloss` each.  vv == 0: puct_score exactly.  (No contraction:
 // the restatement in tests/wave_mcts.py rounds every product and difference on its own)
-__device__ __forceinline__ double wave_score(float c_puct, float p, float q, int n, int vv, double sq, double vloss)
+__device__ __forceinline__ double wave_score(float c_puct, float p, float q, int n, int vv, double sq, double vloss,
+                                             double visit_off)
 {
 #pragma clang fp contract(off)
     const float cp = c_puct * p;
     const int nc = n + vv;
-    const double u = (double)cp * sq / (0.01 + (double)nc);
+    const double u = (double)cp * sq / (visit_off + (double)nc);
     const double qe = vv == 0 ? (double)q : ((double)q * (double)n - vloss * (double)vv) / (double)nc;
     return qe + u;
 }
@@ -93,13 +106,14 @@ __device__ __forceinline__ double wave_score(float c_puct, float p, float q, int
 // FORCE (the noise instantiations of the persistent search alone): a child with forced_child(n, p, force_k, force_n) scores
 // +inf -- the caller gives force_k = k_256 at the root of the search when it has two or more children, 0 anywhere else
 template <bool WAVE, bool FORCE = false>
-__device__ __forceinline__ void score_child(float c_puct, double vloss, uint4 s, uint4 l, int j, double sq, double &best_v,
-                                            int &best_i, uint32_t (&pl)[4], double force_k = 0.0, double force_n = 0.0)
+__device__ __forceinline__ void score_child(float c_puct, double vloss, double visit_off, uint4 s, uint4 l, int j, double sq,
+                                            double &best_v, int &best_i, uint32_t (&pl)[4], double force_k = 0.0,
+                                            double force_n = 0.0)
 {
     const float p = __uint_as_float(s.z), q = __uint_as_float(s.y);
     const int n = (int)s.x;
     // (vv < 2^16: at most 32 playouts in flight)
-    double v = WAVE ? wave_score(c_puct, p, q, n, (int)l.w, sq, vloss) : puct_score(c_puct, p, q, n, sq);
+    double v = WAVE ? wave_score(c_puct, p, q, n, (int)l.w, sq, vloss, visit_off) : puct_score(c_puct, p, q, n, sq, visit_off);
     if constexpr (FORCE)
         v = forced_child(n, p, force_k, force_n) ? (double)INFINITY : v;
     if (v > best_v) {
@@ -177,21 +191,22 @@ __device__ __forceinline__ uint32_t alloc_children(const Tree &T, int64_t g, int
 
 // the children of `node` for its legal moves lg, from pool index fc on.  No move (a pass child, action -1) or a single
 // one: Node(node, 1.0) without a net (MCTS.py:112-117), by lane 0.  Else Node.expand (MCTS.py:27-37): lane r creates the
-// children of board row r in ascending order of the move, child a with prior(a) + 0.1 (MCTS.py:19)
+// children of board row r in ascending order of the move, child a with prior(a) + prior_off (MCTS.py:19: + 0.1; the
+// selection rule's, above -- the lone child stores 1.0f + prior_off)
 template <class Prior>
 __device__ __forceinline__ void make_children(const Tree &T, int64_t base, int fc, int node, uint64_t lg, uint32_t r,
-                                              Prior prior)
+                                              float prior_off, Prior prior)
 {
     if ((lg & (lg - 1ull)) == 0ull) {
         if (r == 0u)
-            init_node(T, base + fc, node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + 0.1f);
+            init_node(T, base + fc, node, lg ? (int)__builtin_ctzll(lg) : -1, 1.0f + prior_off);
     } else {
         uint32_t row = (uint32_t)(lg >> (8u * r)) & 0xFFu;
         int at = fc + __popcll(lg & ((1ull << (8u * r)) - 1ull));
         while (row) {
             const int a = (int)(8u * r) + __builtin_ctz(row);
             row &= row - 1u;
-            init_node(T, base + at, node, a, prior(a) + 0.1f);
+            init_node(T, base + at, node, a, prior(a) + prior_off);
             at++;
         }
     }
@@ -394,7 +409,7 @@ __device__ __forceinline__ void noise_urn8(uint64_t lg, uint32_t l8, uint32_t ke
         c[i] = ((row >> i) & 1u) ? ((uint32_t)wt[i] - alpha_256) >> 8 : 0u;
 }
 
-// the mix of a root child's stored prior p (what init_node wrote: prior + 0.1) with its count c: p keep + term, keep =
+// the mix of a root child's stored prior p (what init_node wrote: prior + the selection rule's prior_off) with its count c: p keep + term, keep =
 // (256 - eps_256) / 256 and term = eps_256 c / (256 N) both exact in float32 (eps_256 c <= 2^18, N = 2^draws_log2), the
 // product and the sum each rounded once, as numpy rounds them
 __device__ __forceinline__ float noise_mix(float p, uint32_t c, uint32_t eps_256, uint32_t draws_log2)

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(BLOCK) void select_kernel(
         int best_i = 0x7fffffff;
         for (int j = (int)L.l8; j < k; j += 8) {
             const int64_t c = base + fc + j;
-            const double v = puct_score(c_puct, T.nodes[c].p, T.nodes[c].q, T.nodes[c].n_visits, sq);
+            const double v = puct_score(c_puct, T.nodes[c].p, T.nodes[c].q, T.nodes[c].n_visits, sq, VISIT_OFF_REFERENCE);
             if (v > best_v) { // strict: the lane's first maximum
                 best_v = v;
                 best_i = j;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(BLOCK) void expand_kernel(Tree T, const int32_t *__
     if (!live || fc1 == 0u)
         return;
     const int fc = (int)fc1 - 1;
-    make_children(T, base, fc, node, lg, r, [&](int a) { return probs[i * 64 + a]; });
+    make_children(T, base, fc, node, lg, r, PRIOR_OFF_REFERENCE, [&](int a) { return probs[i * 64 + a]; });
     if (r == 0u)
         link_children(T, base + node, fc, k);
 }
@@ -307,13 +307,14 @@ __global__ __launch_bounds__(BLOCK) void root_noise_kernel(Tree T, const uint8_t
 
 // best_move_kernel's sibling for the policy-target pruning (iago_mcts_prune_visits), 8 lanes per game: the visit row of
 // the root's children with the forced playouts taken out wherever PUCT would not have granted them -- the rule of
-// iago_hip_serving.h with mcts_dev.hpp's forced_child and puct_score.  Pass 1, the children dealt round the lanes: the first
+// iago_hip_serving.h with mcts_dev.hpp's forced_child and puct_score (visit_off: the selection rule's, 0.01 unless
+// iago_mcts_prune_visits_rule asks for the other).  Pass 1, the children dealt round the lanes: the first
 // child with the most visits (best_move's) and the cells of the children.  Pass 2, lane r the cells of board row r (the
 // children of a root with two or more are its legal moves in ascending cell order, as noise_remix_children walks them):
 // every lane writes its own eight cells, so no cell has two writers.  Fewer than two children: the raw row.  No LDS, no
 // workspace; the loops are bounded by the child's visits.  Inactive games: nothing written
 __global__ __launch_bounds__(BLOCK) void prune_visits_kernel(Tree T, const uint8_t *__restrict__ active, float c_puct,
-                                                             double k_256, int32_t *__restrict__ pruned)
+                                                             double k_256, double visit_off, int32_t *__restrict__ pruned)
 {
     const int64_t g = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 3;
     const uint32_t l8 = threadIdx.x & 7u;
@@ -346,7 +347,7 @@ __global__ __launch_bounds__(BLOCK) void prune_visits_kernel(Tree T, const uint8
         const int64_t b = base + fc + best_i;
         big_n = (double)T.nodes[base + root].n_visits;
         sq = sqrt(big_n);
-        s_star = puct_score(c_puct, T.nodes[b].p, T.nodes[b].q, T.nodes[b].n_visits, sq);
+        s_star = puct_score(c_puct, T.nodes[b].p, T.nodes[b].q, T.nodes[b].n_visits, sq, visit_off);
     }
     const uint32_t row = (uint32_t)(cells >> (8u * l8)) & 0xFFu;
     int at = fc + __popcll(cells & ((1ull << (8u * l8)) - 1ull));
@@ -361,7 +362,7 @@ __global__ __launch_bounds__(BLOCK) void prune_visits_kernel(Tree T, const uint8
                 int f = 0; // F: forced_child is monotone in j (256 j^2 grows, the right side stands), so the count ends at the first miss
                 for (int j = 1; j < n && forced_child(j, p, k_256, big_n); j++)
                     f++;
-                for (int t = 0; t < f && puct_score(c_puct, p, q, m - 1, sq) < s_star; t++)
+                for (int t = 0; t < f && puct_score(c_puct, p, q, m - 1, sq, visit_off) < s_star; t++)
                     m--;
                 m = (m < n && m == 1) ? 0 : m;
             }
@@ -600,7 +601,7 @@ __global__ __launch_bounds__(BLOCK) void expand_cached_kernel(Tree T, const uint
         return;
     const int fc = (int)fc1 - 1;
     const float *probs = k > 1 ? cached_priors(A, g, tag, r == 0u) : nullptr; // (one child: a node without a net)
-    make_children(T, base, fc, node, lg, r, [&](int a) { return probs[a]; });
+    make_children(T, base, fc, node, lg, r, PRIOR_OFF_REFERENCE, [&](int a) { return probs[a]; });
     if (r == 0u)
         link_children(T, base + node, fc, k);
 }
@@ -681,7 +682,7 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
                     const int nf = (int)fc1 - 1;
                     // (one child: a node without a net)
                     const float *probs = kn > 1 ? cached_priors(A, g, tag, r == 0u) : nullptr;
-                    make_children(T, base, nf, node, lg, r, [&](int a) { return probs[a]; });
+                    make_children(T, base, nf, node, lg, r, PRIOR_OFF_REFERENCE, [&](int a) { return probs[a]; });
                     if (r == 0u) {
                         link_children(T, base + node, nf, kn);
                         if (A.va_x_count) {
@@ -721,9 +722,9 @@ __global__ __launch_bounds__(BLOCK) void descend_kernel(
             uint4 s0, l0, s1, l1;
             node_record(T, c0, s0, l0);
             node_record(T, c1, s1, l1);
-            score_child<false>(c_puct, 0.0, s0, l0, j0, sq, best_v, best_i, pl);
+            score_child<false>(c_puct, 0.0, VISIT_OFF_REFERENCE, s0, l0, j0, sq, best_v, best_i, pl);
             if (two)
-                score_child<false>(c_puct, 0.0, s1, l1, j1, sq, best_v, best_i, pl);
+                score_child<false>(c_puct, 0.0, VISIT_OFF_REFERENCE, s1, l1, j1, sq, best_v, best_i, pl);
         }
         argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
         argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
@@ -1188,20 +1189,41 @@ int iago_mcts_root_noise(const iago_mcts_tree *tree, const uint8_t *active, cons
     return iago_check_launch("iago_mcts_root_noise");
 }
 
-int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256, int32_t *pruned,
-                           void *stream)
+// both pruning entry points, WHO (a string literal) naming the one called in its refusals; visit_off is its selection rule's
+#define IAGO_PRUNE_VISITS(WHO, tree, active, c_puct, k_256, visit_off, pruned, stream)                                        \
+    prune_visits(WHO, WHO ": bad tree", WHO ": k_256 must be in [1, 4096]", WHO ": null pruned buffer", tree, active, c_puct, \
+                 k_256, visit_off, pruned, stream)
+
+static int prune_visits(const char *who, const char *bad_tree, const char *bad_k, const char *null_pruned,
+                        const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256, double visit_off,
+                        int32_t *pruned, void *stream)
 {
-    if (check_tree(tree, "iago_mcts_prune_visits: bad tree"))
+    if (check_tree(tree, bad_tree))
         return IAGO_ERR_INVALID;
     if (k_256 < 1 || k_256 > 4096)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_prune_visits: k_256 must be in [1, 4096]");
+        return iago_fail(IAGO_ERR_INVALID, bad_k);
     if (!pruned)
-        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_prune_visits: null pruned buffer");
+        return iago_fail(IAGO_ERR_INVALID, null_pruned);
     if (tree->n_games == 0)
         return IAGO_OK;
     hipLaunchKernelGGL(prune_visits_kernel, dim3(grid_for(tree->n_games * 8)), dim3(BLOCK), 0, (hipStream_t)stream, *tree,
-                       active, c_puct, (double)k_256, pruned);
-    return iago_check_launch("iago_mcts_prune_visits");
+                       active, c_puct, (double)k_256, visit_off, pruned);
+    return iago_check_launch(who);
+}
+
+int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256, int32_t *pruned,
+                           void *stream)
+{
+    return IAGO_PRUNE_VISITS("iago_mcts_prune_visits", tree, active, c_puct, k_256, VISIT_OFF_REFERENCE, pruned, stream);
+}
+
+int iago_mcts_prune_visits_rule(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
+                                int32_t flags, int32_t *pruned, void *stream)
+{
+    if (flags & ~IAGO_SEARCH_PUCT_AZ)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_prune_visits_rule: flags is 0 or IAGO_SEARCH_PUCT_AZ");
+    return IAGO_PRUNE_VISITS("iago_mcts_prune_visits_rule", tree, active, c_puct, k_256,
+                             (flags & IAGO_SEARCH_PUCT_AZ) ? VISIT_OFF_ALPHAZERO : VISIT_OFF_REFERENCE, pruned, stream);
 }
 
 int iago_mcts_advance_root(const iago_mcts_tree *tree, const uint8_t *mask, const int8_t *move,

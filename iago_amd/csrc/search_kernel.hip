@@ -168,9 +168,15 @@ struct SearchParams {
     // forced playouts (iago_mcts_search_forced; the NOISE instantiations alone read it): k_256, 0 = none forced
     int32_t forced_k_256;
     // the backup rule (backup_game; IAGO_SEARCH_NEGAMAX): 0 = the reference's, the leaf's value at every level of the path;
-    // 1 = negamax, its sign turned from level to level (mcts_dev.hpp, backup_value).  (In the struct's tail padding: no
-    // parameter of the kernels moves)
+    // 1 = negamax, its sign turned from level to level (mcts_dev.hpp, backup_value)
     int32_t negamax;
+    // the selection rule (mcts_dev.hpp, "the selection rule"; IAGO_SEARCH_PUCT_AZ): what a new child's stored prior adds to
+    // the policy's output, and what the exploration term's denominator adds to the visits.  0.1f and 0.01: the
+    // reference's; 0.0f and 1.0: AlphaZero's.  Uniform over the launch: scalar operands, no branch, no instantiation.
+    // (The struct's last fields: prior_off fills the padding after negamax, visit_off adds 8 bytes, by which the kernel
+    // parameters after a SearchParams move)
+    float prior_off;
+    double visit_off;
 };
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
@@ -828,7 +834,7 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
             const uint32_t fc1 = alloc_children(T, I.gt, kn, I.r == 0u);
             if (fc1 != 0u) {
                 const int nf = (int)fc1 - 1;
-                make_children(T, I.base, nf, C.node, lg, I.r,
+                make_children(T, I.base, nf, C.node, lg, I.r, S.prior_off,
                               [&](int a) { return __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a])); });
                 if constexpr (NOISE) {
                     if (C.path_n == 1 && kn > 1) {
@@ -868,9 +874,9 @@ __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I
         uint4 s0, l0, s1, l1;
         node_record(S.T, c0, s0, l0);
         node_record(S.T, c1, s1, l1);
-        score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, s0, l0, j0, sq, best_v, best_i, pl, force_k, force_n);
+        score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s0, l0, j0, sq, best_v, best_i, pl, force_k, force_n);
         if (two)
-            score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, s1, l1, j1, sq, best_v, best_i, pl, force_k, force_n);
+            score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s1, l1, j1, sq, best_v, best_i, pl, force_k, force_n);
     }
     argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
     argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
@@ -1842,8 +1848,8 @@ struct LaunchRequest {
     int forced_k_256 = 0;                         // forced playouts at the root (with noise): k_256, 0 = none
 };
 
-// games_per_workgroup without its flags (IAGO_SEARCH_CHAIN_SKIP, IAGO_SEARCH_NEGAMAX)
-constexpr int SEARCH_FLAGS = IAGO_SEARCH_CHAIN_SKIP | IAGO_SEARCH_NEGAMAX;
+// games_per_workgroup without its flags (IAGO_SEARCH_CHAIN_SKIP, IAGO_SEARCH_NEGAMAX, IAGO_SEARCH_PUCT_AZ)
+constexpr int SEARCH_FLAGS = IAGO_SEARCH_CHAIN_SKIP | IAGO_SEARCH_NEGAMAX | IAGO_SEARCH_PUCT_AZ;
 int games_per_wg_of(const iago_mcts_search_args *a)
 {
     return a->games_per_workgroup > 0 ? (a->games_per_workgroup & ~SEARCH_FLAGS) : a->games_per_workgroup;
@@ -1903,6 +1909,7 @@ struct SearchGrid {
     int gpw;                                 // games (a wave search: slots) per game workgroup
     int chain_skip;                          // IAGO_SEARCH_CHAIN_SKIP of games_per_workgroup
     int negamax;                             // IAGO_SEARCH_NEGAMAX of games_per_workgroup (the wave search has it too)
+    int puct_az;                             // IAGO_SEARCH_PUCT_AZ of games_per_workgroup (likewise)
     int64_t n_slots, n_game_wgs, net_wgs, grid;
     int path_lds_cap, game_lds;              // the games' paths in dynamic LDS: bytes a workgroup may use; the game launch's
 };
@@ -1915,6 +1922,7 @@ void size_games(const iago_mcts_search_args *a, const iago_search_wave_args *wv,
     // (the wave search's descent keeps its in-flight counts per node and walks every level)
     G.chain_skip = (!wv && a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_CHAIN_SKIP)) ? 1 : 0;
     G.negamax = (a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_NEGAMAX)) ? 1 : 0;
+    G.puct_az = (a->games_per_workgroup > 0 && (a->games_per_workgroup & IAGO_SEARCH_PUCT_AZ)) ? 1 : 0;
     G.n_slots = a->tree->n_games * (wv ? wv->width : 1);
     G.n_game_wgs = (G.n_slots + G.gpw - 1) / G.gpw;
     G.path_lds_cap = SEARCH_IMG_TOP;
@@ -2079,6 +2087,8 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.cap_full_256 = q.cap_full_256;
     S.chain_skip = G.chain_skip;
     S.negamax = G.negamax;
+    S.prior_off = G.puct_az ? PRIOR_OFF_ALPHAZERO : PRIOR_OFF_REFERENCE;
+    S.visit_off = G.puct_az ? VISIT_OFF_ALPHAZERO : VISIT_OFF_REFERENCE;
     S.noise_counts = q.noise ? q.noise->counts : nullptr;
     S.noise_eps = q.noise ? q.noise->eps_256 : 0;
     S.noise_lg = q.noise ? __builtin_ctz((unsigned)q.noise->draws) : 0;

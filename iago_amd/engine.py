@@ -125,6 +125,24 @@ _NEGAMAX_NEEDS = ("backup=\"negamax\" is offered for the persistent search only 
                   "the reference's rule)")
 
 
+SELECTION_RULES = ("reference", "alphazero")
+
+
+def selection_arg(x):
+    """selection=: the rule by which Node.select scores a child -- "reference" (the reference's: the stored prior is
+    prob + 0.1, the exploration term divides by 0.01 + n) or "alphazero" (the textbook rule: the stored prior is prob,
+    U = c_puct P sqrt(N) / (1 + n); include/iago_hip_serving.h, IAGO_SEARCH_PUCT_AZ).  The canonical string, or
+    ValueError."""
+    if isinstance(x, str) and x in SELECTION_RULES:
+        return x
+    raise ValueError("selection: \"reference\" or \"alphazero\" expected, not %r" % (x,))
+
+
+_ALPHAZERO_NEEDS = ("selection=\"alphazero\" is offered for the persistent search only (the per-playout launches -- "
+                    "persistent=False, use_graph, the look-ahead, asynchronous steps and what a rollout_hook selects -- keep "
+                    "the reference's rule)")
+
+
 def suggest_capacity(n_sims, n_thr=15, moves=64, branching=12):
     """Nodes per game that a whole self-play game needs without ever compacting the pools:
     every expansion adds ~`branching` children, a search adds at most
@@ -248,7 +266,7 @@ class BatchedMCTS(object):
                  sync_free=None, lookahead=None, lookahead_slots=None, value_cache=None, lookahead_overlap=None,
                  z_log_rows=0, async_steps=None, async_parts=None, value_ahead=None, persistent=None,
                  net_workgroups=None, max_cus=None, split=None, wave=1, virtual_loss=1.0, chain_skip=True,
-                 path_stride=None, backup="reference"):
+                 path_stride=None, backup="reference", selection="reference"):
         if n_thr < 1:
             raise ValueError("n_thr must be >= 1")
         # (what the caller asked for explicitly, before the defaults below fill the options in: any of these selects
@@ -274,6 +292,11 @@ class BatchedMCTS(object):
         self.backup = backup_arg(backup)
         if self.backup == "negamax" and not schedule(True):
             raise ValueError(_NEGAMAX_NEEDS)
+        # selection: the selection rule of the persistent search, "reference" (the default: today's trees bit for bit) or
+        # "alphazero" (IAGO_SEARCH_PUCT_AZ; selection_arg).  Offered and refused exactly as backup="negamax" is
+        self.selection = selection_arg(selection)
+        if self.selection == "alphazero" and not schedule(True):
+            raise ValueError(_ALPHAZERO_NEEDS)
         # (the persistent search) chain_skip: a descent jumps over the pass chain it remembers from its game's last
         # playout (IAGO_SEARCH_CHAIN_SKIP: timing only, same trees; False: every level is walked -- the A/B switch).
         # path_stride: entries of a game's path buffer (None: 520, the descent's own bound of 512 levels and a margin; at
@@ -413,6 +436,8 @@ class BatchedMCTS(object):
         self.persistent = bool(persistent)
         if self.backup == "negamax" and not self.persistent:
             raise ValueError(_NEGAMAX_NEEDS)
+        if self.selection == "alphazero" and not self.persistent:
+            raise ValueError(_ALPHAZERO_NEEDS)
         if self.wave > 1 and not self.persistent:
             raise ValueError("wave > 1 needs the persistent search (the split-f16 value net, the three-piece policy net, "
                              "product-form rollout weights, lmbda < 1, at most %d slots)" % _lib.SEARCH_QUEUE_ENTRIES)
@@ -1333,7 +1358,8 @@ class BatchedMCTS(object):
         a.c_puct, a.lmbda, a.n_thr, a.n_sims = self.c_puct, self.lmbda, self.n_thr, int(n_sims)
         a.net_workgroups, a.time_limit_ms = self.net_workgroups, self.time_limit_ms
         a.games_per_workgroup = (self.games_per_workgroup | (_lib.SEARCH_CHAIN_SKIP if self.chain_skip else 0)
-                                 | (_lib.SEARCH_NEGAMAX if self.backup == "negamax" else 0))
+                                 | (_lib.SEARCH_NEGAMAX if self.backup == "negamax" else 0)
+                                 | (_lib.SEARCH_PUCT_AZ if self.selection == "alphazero" else 0))
         a.pace_margin = self.pace_margin
         a.max_cus = self.max_cus
         a.value, a.policy, a.rollout = C.addressof(va), C.addressof(pa), C.addressof(ro.args)
@@ -1394,12 +1420,14 @@ class BatchedMCTS(object):
         return rows
 
     def _backup_check(self):
-        """backup="negamax" is the persistent search's alone: a rollout hook (set after construction) would send search()
-        and SelfPlayEngine's turns through the per-playout launches, whose backup is the reference's.  Refused where a
-        search or a round of games begins, before anything is reset."""
-        if getattr(self, "backup", "reference") == "negamax" and (not getattr(self, "persistent", False)
-                                                                  or getattr(self, "rollout_hook", None) is not None):
+        """backup="negamax" and selection="alphazero" are the persistent search's alone: a rollout hook (set after
+        construction) would send search() and SelfPlayEngine's turns through the per-playout launches, whose rules are the
+        reference's.  Refused where a search or a round of games begins, before anything is reset."""
+        per_playout = not getattr(self, "persistent", False) or getattr(self, "rollout_hook", None) is not None
+        if getattr(self, "backup", "reference") == "negamax" and per_playout:
             raise ValueError(_NEGAMAX_NEEDS)
+        if getattr(self, "selection", "reference") == "alphazero" and per_playout:
+            raise ValueError(_ALPHAZERO_NEEDS)
 
     def _root_noise_arg(self, root_noise):
         """search()'s root_noise, validated: offered for the persistent engine only."""
@@ -1586,12 +1614,15 @@ class BatchedMCTS(object):
     def pruned_visits(self, active=None, forced_playouts=512):
         """The policy-target pruning of forced playouts (ops.prune_visits) on the trees as they stand: the (n_games, 64)
         int32 visit rows of the roots of the games in `active` (None: every game) with the forced visits taken out where
-        PUCT would not have granted them, under k_256 = forced_playouts and the engine's c_puct.  The engine's own buffer:
-        the next call overwrites it; the rows of games outside `active` are stale."""
+        PUCT would not have granted them, under k_256 = forced_playouts, the engine's c_puct and its selection rule (the
+        scores' denominator).  The engine's own buffer: the next call overwrites it; the rows of games outside `active` are
+        stale."""
         k = ops.forced_playouts_arg(forced_playouts, noise=True)   # (the rule reads trees: whatever search wrote them)
         rows = getattr(self, "_pruned_rows", None)
         if rows is None:
             rows = self._pruned_rows = torch.zeros((self.n_games, 64), dtype=torch.int32, device=self.move.device)
+        if getattr(self, "selection", "reference") == "alphazero":
+            return ops.prune_visits(self.tree.ref(), active, self.c_puct, k, rows, _lib.SEARCH_PUCT_AZ)
         return ops.prune_visits(self.tree.ref(), active, self.c_puct, k, rows)
 
     def draw_move(self, turn, active=None, want_visits=True):

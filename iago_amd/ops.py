@@ -1363,13 +1363,21 @@ def search_forced(args, noise, counts, k_256, streams=None):
     check(_lib.lib().iago_mcts_search_forced(C.byref(args), C.byref(z), _stream()), "iago_mcts_search_forced")
 
 
-def prune_visits(tree, active, c_puct, k_256, pruned):
+def prune_visits(tree, active, c_puct, k_256, pruned, flags=0):
     """iago_mcts_prune_visits (include/iago_hip_serving.h): the policy-target pruning of forced playouts.  For every game
     with active[g] != 0 (active None: every game) the visit row of the tree's root into pruned[g] ((n_games, 64) int32)
     with, for a root of K >= 2 children, every child c other than the first most visited one b reduced from its n visits
     to m: F = the number of j in 1 .. n - 1 with forced(j, p_c, N); m = n; while n - m < F and the PUCT score of c with
     m - 1 visits is below b's score, m -= 1; m = 0 if m < n and m == 1.  Fewer than two children: the raw row.  Inactive
-    games' rows are not touched; the trees are only read.  tree: TreePool.ref().  Returns pruned."""
+    games' rows are not touched; the trees are only read.  tree: TreePool.ref().  Returns pruned.
+    flags: 0, or _lib.SEARCH_PUCT_AZ for the trees of a search under the AlphaZero selection rule -- the scores then have
+    its denominator (iago_mcts_prune_visits_rule)."""
+    if flags:
+        check(_lib.lib().iago_mcts_prune_visits_rule(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                                     C.c_float(float(c_puct)), int(k_256), int(flags),
+                                                     _dev(pruned, torch.int32, "pruned"), _stream()),
+              "iago_mcts_prune_visits_rule")
+        return pruned
     check(_lib.lib().iago_mcts_prune_visits(tree, _dev(active, torch.uint8, "active") if active is not None else None,
                                             C.c_float(float(c_puct)), int(k_256), _dev(pruned, torch.int32, "pruned"),
                                             _stream()), "iago_mcts_prune_visits")

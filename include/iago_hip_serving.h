@@ -61,6 +61,29 @@ IAGO_API int iago_mcts_search_wave(const iago_mcts_search_args *args, const iago
  */
 #define IAGO_SEARCH_NEGAMAX 0x200
 
+/*
+ * The AlphaZero selection rule: OR-ed into iago_mcts_search_args.games_per_workgroup (a positive one, like
+ * IAGO_SEARCH_CHAIN_SKIP and IAGO_SEARCH_NEGAMAX; all three are stripped before the number is read), for every entry
+ * point that takes those arguments -- the single launch, the role split, whole games, streams and matches, park /
+ * explore / cap / noise / forced, the wave search, and each argument set of iago_mcts_search_arena on its own (A and B
+ * may differ).  Without it the search selects by the reference's formula.  With it, two changes and no others:
+ *   1. The stored prior.  A child created by Node.expand for move a stores float32(prob[a]); the reference stores
+ *      float32(float32(prob[a]) + float32(0.1)).  The single-move child and the pass child (Node(node, 1.0) without a
+ *      net) store 1.0, not 1.1.  A root created as Node(None, 1.0) -- iago_mcts_reset (which takes no flags), a game's
+ *      start inside a launch, a stream's next game, a move that is no child of the root -- stores 1.1 under BOTH rules: a
+ *      root's prior is never read.  A root reached by subtree reuse is a former child and keeps what it stored.
+ *   2. The score.  Q + float64(float32(c_puct * P)) * sqrt(float64(N_parent)) / (1.0 + n) in float64, every operation
+ *      rounded on its own; the reference divides by 0.01 + n.  The wave search's denominator is 1.0 + n + vv, its Q_eff
+ *      unchanged.  An unvisited child's Q stays 0; the first maximum still wins.
+ * Expansion at n_thr, the leaf mix, both backup rules, the value cache and the position table, the pass-chain skip and
+ * the move read from the visit counts are untouched.  Root noise mixes the STORED prior as it stands (the mix's own
+ * arithmetic is unchanged), so under this rule it is p (1 - eps) + eps c / N on the policy's p; a forced child is judged
+ * by its STORED prior as it stands, n < sqrt(k p N) on the (mixed) policy's p.  The pruning scores with the rule's
+ * denominator: iago_mcts_prune_visits_rule.
+ * The per-playout launches (iago_mcts_select, iago_mcts_expand and their kin) keep the reference's rule.
+ */
+#define IAGO_SEARCH_PUCT_AZ 0x400
+
 /* ------------------------------------------------------------------ exact endgame */
 
 #define IAGO_ENDGAME_EXACT 0          /* mode: the exact final disc difference */
@@ -364,6 +387,15 @@ IAGO_API int iago_mcts_search_forced(const iago_mcts_search_args *args, const ia
  */
 IAGO_API int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
                                     int32_t *pruned /* [n_games][64] */, void *stream);
+
+/*
+ * iago_mcts_prune_visits under a selection rule: flags = 0 is that entry point exactly; flags = IAGO_SEARCH_PUCT_AZ scores
+ * S* and every "score of c with m - 1 visits" with the AlphaZero rule's denominator, 1.0 + n (the trees of a search under
+ * IAGO_SEARCH_PUCT_AZ).  forced() reads the stored priors as they are under both.
+ * Refused (IAGO_ERR_INVALID, nothing launched): any other bit of flags, and what iago_mcts_prune_visits refuses.
+ */
+IAGO_API int iago_mcts_prune_visits_rule(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
+                                         int32_t flags, int32_t *pruned /* [n_games][64] */, void *stream);
 
 /* ------------------------------------------------------------------ arena */
 

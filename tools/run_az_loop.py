@@ -18,9 +18,11 @@ backup = 1: the negamax backup rule (engine.BatchedMCTS(backup="negamax")) in se
 yardstick_every = k > 0: every k rounds the current nets play `games` games (paired, 8 random opening turns, `sims`
 playouts a move) against the fixed-depth alpha-beta opponent of depth yardstick_depth (SelfPlayEngine.play_match(opponent=
 engine.AlphaBeta(d))), the one opponent that owes nothing to the nets, and the scores join the JSON line; 0 = off.
+selection = 1: the AlphaZero selection rule (engine.BatchedMCTS(selection="alphazero")) in self-play, on both sides of
+the gate and against the yardstick; 0, the default: the reference's rule.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
-                                 [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2]"""
+                                 [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,12 +41,14 @@ root_noise = (arg(11, 77), arg(10, 0)) if arg(10, 0) > 0 else None
 forced_playouts = arg(12, 0) if arg(12, 0) > 0 else None
 backup = engine.backup_arg("negamax" if arg(13, 0) else "reference")
 yardstick_every, yardstick_depth = arg(14, 0), arg(15, 2)
+selection = engine.selection_arg("alphazero" if arg(16, 0) else "reference")
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
 vt = SupervisedTrainer(network.Value(), "value", seed=0, native=True)
 m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                       capacity=engine.suggest_capacity(sims, 15), seed=1, backup=backup)   # default engine: the persistent search
+                       capacity=engine.suggest_capacity(sims, 15), seed=1, backup=backup,
+                       selection=selection)   # default engine: the persistent search
 sp = engine.SelfPlayEngine(m)
 window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
 kls, vlosses = [], []
@@ -53,15 +57,18 @@ if arena_every > 0:
     # the nets of k rounds ago: a frozen module pair of its own, an engine and tree pool of its own (other seed and ids)
     old_p, old_v = copy.deepcopy(tr.model1).eval(), copy.deepcopy(vt.model).eval()
     m_now = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                               capacity=engine.suggest_capacity(sims, 15), seed=3, backup=backup)
+                               capacity=engine.suggest_capacity(sims, 15), seed=3, backup=backup,
+                               selection=selection)
     m_old = engine.BatchedMCTS(games, old_p, old_v, ops.RolloutWeights(w, b), n_thr=15,
-                               capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games, backup=backup)
+                               capacity=engine.suggest_capacity(sims, 15), seed=4, game_id_base=games, backup=backup,
+                               selection=selection)
     arena = engine.ArenaEngine(m_now, m_old)
 yardstick_scores = []
 if yardstick_every > 0:
     # an engine and tree pool of its own on the CURRENT nets (other seed and ids), against engine.AlphaBeta
     m_yard = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                                capacity=engine.suggest_capacity(sims, 15), seed=5, game_id_base=2 * games, backup=backup)
+                                capacity=engine.suggest_capacity(sims, 15), seed=5, game_id_base=2 * games, backup=backup,
+                                selection=selection)
     yard = engine.SelfPlayEngine(m_yard)
     opponent = engine.AlphaBeta(yardstick_depth)
 
@@ -126,7 +133,7 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
-                  "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup,
+                  "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup, "selection": selection,
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {}),
                   **({"yardstick_every": yardstick_every, "yardstick_depth": yardstick_depth,
                       "yardstick": yardstick_scores} if yardstick_every > 0 else {})}))

@@ -5,7 +5,12 @@ opening_turns=8, paired=True) -- --games games per cell, every random opening pl
 once as colour 2 -- at every playout count of --sims, under both backup rules, against every depth of --depths.
 
     python tools/run_yardstick.py [--games 1024] [--sims 100,400] [--depths 1,2,4,6] [--backups reference,negamax]
+                                  [--selections reference] [--c-pucts 1.0] [--append]
                                   [--opening-turns 8] [--seed 5] [--out profiles/alphabeta_yardstick.json]
+
+--selections: the selection rules (engine.selection_arg: "reference", "alphazero"), --c-pucts: the exploration constants;
+every combination with --backups and --sims is a row of cells.  --append: the cells are added to those --out already
+holds (same games, opening turns and seed, or refused) instead of replacing them.
 
 Per cell: PV-MCTS's wins / draws / losses, its score (a draw counting 1/2) with the 95 % Wilson interval, overall and per
 colour, the turns of the longest game and the wall time of the match (one untimed warm-up match per engine before its
@@ -31,6 +36,9 @@ def main():
     ap.add_argument("--sims", default="100,400")
     ap.add_argument("--depths", default="1,2,4,6")
     ap.add_argument("--backups", default="reference,negamax")
+    ap.add_argument("--selections", default="reference")
+    ap.add_argument("--c-pucts", default="1.0")
+    ap.add_argument("--append", action="store_true")
     ap.add_argument("--opening-turns", type=int, default=8)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "alphabeta_yardstick.json"))
@@ -41,34 +49,48 @@ def main():
     rollout = network.RolloutPolicy().load_npz(os.path.join(GOLDEN, "rollout_model.npz")).eval()
     B = args.games
     cells = []
-    for backup in args.backups.split(","):
-        for sims in (int(s) for s in args.sims.split(",")):
-            m = engine.BatchedMCTS(B, policy, value, ops.RolloutWeights(*rollout.kernel_weights()), lmbda=0.5, c_puct=1.0,
-                                   n_thr=15, seed=args.seed, persistent=True, backup=backup,
-                                   capacity=engine.suggest_capacity(sims, 15, moves=64))
-            eng = engine.SelfPlayEngine(m)
-            kw = dict(opening_turns=args.opening_turns, paired=True, record=False)
-            eng.play_match(sims, opponent=engine.AlphaBeta(1), **kw)   # warm-up (allocator, code objects): not counted
-            for depth in (int(d) for d in args.depths.split(",")):
-                m.sim_counter = 0
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                r = eng.play_match(sims, opponent=engine.AlphaBeta(depth), **kw)
-                torch.cuda.synchronize()
-                s = time.perf_counter() - t0
-                z = r.z.to(torch.int32) * torch.where(r.mcts_colour == 1, 1, -1).to(torch.int32)
-                c = r.mcts_colour
-                cells.append(dict(backup=backup, n_sims=sims, depth=depth, s=round(s, 2), turns=r.n_turns,
-                                  mcts=dict(overall=tally(z), as_colour_1=tally(z[c == 1]), as_colour_2=tally(z[c == 2]))))
-                print(json.dumps(cells[-1]), file=sys.stderr, flush=True)
-            m.close()
-    out = dict(tool="run_yardstick", games=B, opening_turns=args.opening_turns, paired=True, seed=args.seed,
-               device=torch.cuda.get_device_name(0), cells=cells)
-    line = json.dumps(out)
+    if args.append and os.path.exists(args.out):
+        with open(args.out) as f:
+            old = json.loads(f.readline())
+        if (old["games"], old["opening_turns"], old["seed"]) != (B, args.opening_turns, args.seed):
+            raise SystemExit("--append: %s holds cells of other games, opening turns or seed" % args.out)
+        cells = old["cells"]
+
+    def save():
+        line = json.dumps(dict(tool="run_yardstick", games=B, opening_turns=args.opening_turns, paired=True, seed=args.seed,
+                               device=torch.cuda.get_device_name(0), cells=cells))
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        return line
+
+    line = None
+    rows = [(backup, selection, c_puct, sims) for backup in args.backups.split(",")
+            for selection in args.selections.split(",") for c_puct in (float(c) for c in args.c_pucts.split(","))
+            for sims in (int(s) for s in args.sims.split(","))]
+    for backup, selection, c_puct, sims in rows:
+        m = engine.BatchedMCTS(B, policy, value, ops.RolloutWeights(*rollout.kernel_weights()), lmbda=0.5, c_puct=c_puct,
+                               n_thr=15, seed=args.seed, persistent=True, backup=backup, selection=selection,
+                               capacity=engine.suggest_capacity(sims, 15, moves=64))
+        eng = engine.SelfPlayEngine(m)
+        kw = dict(opening_turns=args.opening_turns, paired=True, record=False)
+        eng.play_match(sims, opponent=engine.AlphaBeta(1), **kw)   # warm-up (allocator, code objects): not counted
+        for depth in (int(d) for d in args.depths.split(",")):
+            m.sim_counter = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = eng.play_match(sims, opponent=engine.AlphaBeta(depth), **kw)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+            z = r.z.to(torch.int32) * torch.where(r.mcts_colour == 1, 1, -1).to(torch.int32)
+            c = r.mcts_colour
+            cells.append(dict(backup=backup, selection=selection, c_puct=c_puct, n_sims=sims, depth=depth, s=round(s, 2),
+                              turns=r.n_turns,
+                              mcts=dict(overall=tally(z), as_colour_1=tally(z[c == 1]), as_colour_2=tally(z[c == 2]))))
+            print(json.dumps(cells[-1]), file=sys.stderr, flush=True)
+        m.close()
+        line = save()   # (after every row: a run that is cut short keeps the rows it finished)
     print(line)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(line + "\n")
 
 
 if __name__ == "__main__":
