@@ -18,6 +18,10 @@
 //     with the fewest replies (ties: lowest index), else index order.  Only `nodes` depends on it;
 //   * the root's tie rule is the solver's: every move that could tie the best value with a lower index is searched with
 //     a window that keeps the tie exact, so `move` is the lowest-indexed move reaching the score whatever the order.
+// iago_alphabeta_moves_split spreads every root over many lanes: the first one or two plies are expanded into JOBS
+// (position, depth left) on the device, the same search runs a lane per job (search_wave<true>: the job count read from
+// ctl, every lane's depth from its job), and a thread per root takes the values back.  Every job has the full window,
+// so its value and its node count are those of iago_alphabeta_moves on that position, whatever else runs beside it.
 #include "abi_common.hpp"
 #include "othello_dev.hpp"
 #include "othello_lane.hpp"
@@ -41,6 +45,10 @@ constexpr int CTL_GAVE_UP = 0;
 constexpr int CTL_CLAIM = 1;
 constexpr int CTL_REFUSED = 2;
 constexpr int CTL_OVERFLOW = 3;
+// iago_alphabeta_moves_split's further words
+constexpr int CTL_JOBS_LO = 4;
+constexpr int CTL_JOBS_HI = 5;
+constexpr int CTL_JOB_OVERFLOW = 6;
 
 enum Phase : uint32_t { CLAIM = 0, ENTER = 1, NEXT = 2, RETURN = 3, DONE = 4 };
 
@@ -273,17 +281,46 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack &K, uint32_t 
     return true;
 }
 
-__global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
+// The jobs of iago_alphabeta_moves_split as the search reads and answers them: positions with a depth of their own
+struct JobParams {
+    const uint64_t *own;
+    const uint64_t *opp;
+    const int8_t *path;      // [jobs][4]: depth left, first move, second move, 0
+    int16_t *score;
+    int8_t *move;
+    int64_t *nodes;
+    uint8_t *done;
+    uint32_t *ctl;
+    int32_t levels;          // stack frames per lane: the launch's depth
+    long long clock_limit;
+};
+
+// The search of a wave, lane per position: JOBS = false over the n positions of P at P.depth (a refused position is
+// counted and skipped), JOBS = true over the jobs of a split search -- their number read from ctl (none after an
+// overflow of the job arrays), every lane's depth read from its job.
+template <bool JOBS, class Params>
+__device__ __forceinline__ void search_wave(const Params &P, unsigned char *stack_lds)
 {
-    extern __shared__ __align__(16) unsigned char stack_lds[];
     const uint32_t lane = threadIdx.x;
     const Stack K = make_stack(stack_lds, P.levels);
     const ShiftAmounts SA = opaque_shift_amounts();
     const long long t0 = wall_clock64();
 
+    int64_t n;
+    if constexpr (JOBS) {
+        n = P.ctl[CTL_JOB_OVERFLOW] != 0u ? 0 : (int64_t)P.ctl[CTL_JOBS_LO];
+        if ((int64_t)blockIdx.x * WAVE >= n) // nothing to claim: the wave leaves at once
+            return;
+    } else {
+        n = P.n;
+    }
+
     Search s = {};
     s.phase = CLAIM;
     int64_t pos = 0;
+    int depth = 0;
+    if constexpr (!JOBS)
+        depth = P.depth;
 
     while (true) {
         if (s.phase == CLAIM) {
@@ -291,18 +328,23 @@ __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
                 s.phase = DONE;
             } else {
                 pos = (int64_t)atomicAdd(&P.ctl[CTL_CLAIM], 1u);
-                if (pos >= P.n) {
+                if (pos >= n) {
                     s.phase = DONE;
                 } else {
                     const uint64_t own = P.own[pos], opp = P.opp[pos];
-                    if ((own & opp) != 0ull) {
-                        // refused: done stays 0
-                        atomicAdd(&P.ctl[CTL_REFUSED], 1u);
-                        P.score[pos] = 0;
-                        P.move[pos] = 0;
-                        P.nodes[pos] = 0;
-                    } else {
+                    if constexpr (JOBS) {
+                        depth = P.path[4 * pos];
                         search_begin(s, own, opp);
+                    } else {
+                        if ((own & opp) != 0ull) {
+                            // refused: done stays 0
+                            atomicAdd(&P.ctl[CTL_REFUSED], 1u);
+                            P.score[pos] = 0;
+                            P.move[pos] = 0;
+                            P.nodes[pos] = 0;
+                        } else {
+                            search_begin(s, own, opp);
+                        }
                     }
                 }
             }
@@ -316,7 +358,7 @@ __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
             break;
         }
 
-        if (!search_step(s, K, lane, P.depth, SA)) {
+        if (!search_step(s, K, lane, depth, SA)) {
             atomicOr(&P.ctl[CTL_OVERFLOW], 1u);
             s.phase = CLAIM;
             continue;
@@ -330,6 +372,234 @@ __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
             s.phase = CLAIM;
         }
     }
+}
+
+__global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    search_wave<false>(P, stack_lds);
+}
+
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(8, 8))) void alphabeta_jobs_kernel(JobParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    search_wave<true>(P, stack_lds);
+}
+
+// ---- iago_alphabeta_moves_split: the roots' jobs counted, summed and written, (searched: alphabeta_jobs_kernel,) and
+// taken back.  Every stage is a launch of its own on the caller's stream: a stage reads what the one before it wrote.
+
+constexpr int SPLIT_BLOCK = 256;
+constexpr int SCAN_BLOCK = 1024;
+
+struct SplitParams {
+    const uint64_t *own;
+    const uint64_t *opp;
+    int64_t n;
+    int32_t depth;
+    int32_t split;
+    int32_t *job_count;
+    int64_t *job_first;
+    int64_t capacity;
+    uint64_t *job_own;
+    uint64_t *job_opp;
+    int32_t *job_root;
+    int8_t *job_path;
+    uint8_t *job_done;
+    uint32_t *ctl;
+};
+
+// The jobs of root i in canonical order (first move ascending, then second move): counted, and with WRITE written from
+// job_first[i] on.  A node is a job when no split ply is left or its mover has no legal move, else it is expanded.
+template <bool WRITE>
+__device__ __forceinline__ int expand_root(const SplitParams &P, int64_t i, uint64_t own, uint64_t opp,
+                                           const ShiftAmounts &SA)
+{
+    int64_t at = 0;
+    if constexpr (WRITE)
+        at = P.job_first[i];
+    int count = 0;
+    auto job = [&](uint64_t o, uint64_t p, int d, int m1, int m2) {
+        if constexpr (WRITE) {
+            const int64_t j = at + count;
+            if (j < P.capacity) { // (always: the total fits or nothing is written)
+                P.job_own[j] = o;
+                P.job_opp[j] = p;
+                P.job_root[j] = (int32_t)i;
+                P.job_path[4 * j + 0] = (int8_t)d;
+                P.job_path[4 * j + 1] = (int8_t)m1;
+                P.job_path[4 * j + 2] = (int8_t)m2;
+                P.job_path[4 * j + 3] = 0;
+                P.job_done[j] = 0;
+            }
+        }
+        count++;
+    };
+    uint64_t legal = legal_of(own, opp, SA);
+    if (legal == 0ull) {
+        job(own, opp, P.depth, -1, -1); // a root that must pass, or a finished game
+        return count;
+    }
+    while (legal) {
+        const uint32_t m1 = lowest_bit(legal);
+        legal &= legal - 1ull;
+        const uint64_t f = flips_of(own, opp, m1);
+        const uint64_t cown = opp & ~f, copp = own | f | (1ull << m1);
+        uint64_t replies = P.split >= 2 ? legal_of(cown, copp, SA) : 0ull;
+        if (replies == 0ull) {
+            job(cown, copp, P.depth - 1, (int)m1, -1); // the last split ply, or a child that cannot move
+            continue;
+        }
+        while (replies) {
+            const uint32_t m2 = lowest_bit(replies);
+            replies &= replies - 1ull;
+            const uint64_t g = flips_of(cown, copp, m2);
+            job(copp & ~g, cown | g | (1ull << m2), P.depth - 2, (int)m1, (int)m2);
+        }
+    }
+    return count;
+}
+
+__global__ __launch_bounds__(SPLIT_BLOCK) void split_count_kernel(SplitParams P)
+{
+    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
+    if (i >= P.n)
+        return;
+    const ShiftAmounts SA = opaque_shift_amounts();
+    const uint64_t own = P.own[i], opp = P.opp[i];
+    int count = 0;
+    if ((own & opp) != 0ull)
+        atomicAdd(&P.ctl[CTL_REFUSED], 1u); // refused: no job, done stays 0
+    else
+        count = expand_root<false>(P, i, own, opp, SA);
+    P.job_count[i] = count;
+}
+
+// job_first = the exclusive sum of job_count, the total into ctl: ONE workgroup, SCAN_BLOCK roots per round.
+// capacity < 0: the count-only form, which has no overflow.
+__global__ __launch_bounds__(SCAN_BLOCK) void split_scan_kernel(const int32_t *count, int64_t *first, int64_t n,
+                                                                int64_t capacity, uint32_t *ctl)
+{
+    __shared__ long long wave_sum[SCAN_BLOCK / WAVE];
+    const int lane = threadIdx.x % WAVE, w = threadIdx.x / WAVE;
+    long long carry = 0;
+    for (int64_t base = 0; base < n; base += SCAN_BLOCK) {
+        const int64_t i = base + threadIdx.x;
+        const long long c = i < n ? count[i] : 0;
+        long long x = c;
+        for (int o = 1; o < WAVE; o <<= 1) {
+            const long long y = __shfl_up(x, o);
+            if (lane >= o)
+                x += y;
+        }
+        if (lane == WAVE - 1)
+            wave_sum[w] = x;
+        __syncthreads();
+        long long before = 0, total = 0;
+        for (int k = 0; k < SCAN_BLOCK / WAVE; k++) {
+            const long long v = wave_sum[k];
+            before += k < w ? v : 0;
+            total += v;
+        }
+        if (i < n)
+            first[i] = carry + before + x - c;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        ctl[CTL_JOBS_LO] = (uint32_t)carry;
+        ctl[CTL_JOBS_HI] = (uint32_t)((unsigned long long)carry >> 32);
+        if (capacity >= 0 && carry > capacity)
+            ctl[CTL_JOB_OVERFLOW] = 1u;
+    }
+}
+
+__global__ __launch_bounds__(SPLIT_BLOCK) void split_write_kernel(SplitParams P)
+{
+    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
+    if (i >= P.n || P.ctl[CTL_JOB_OVERFLOW] != 0u || P.job_count[i] == 0)
+        return;
+    const ShiftAmounts SA = opaque_shift_amounts();
+    expand_root<true>(P, i, P.own[i], P.opp[i], SA);
+}
+
+struct ReduceParams {
+    int64_t n;
+    const int32_t *job_count;
+    const int64_t *job_first;
+    const int8_t *job_path;
+    const int16_t *job_score;
+    const int8_t *job_move;
+    const int64_t *job_nodes;
+    const uint8_t *job_done;
+    int16_t *score;
+    int8_t *move;
+    int64_t *nodes;
+    uint8_t *done;
+    const uint32_t *ctl;
+};
+
+// A thread per root: its run of jobs minimaxed back, the sign turned once per ply of the path; the first maximum in
+// canonical order is the lowest-indexed move of the best value.
+__global__ __launch_bounds__(SPLIT_BLOCK) void split_reduce_kernel(ReduceParams P)
+{
+    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
+    if (i >= P.n || P.ctl[CTL_JOB_OVERFLOW] != 0u)
+        return;
+    const int count = P.job_count[i];
+    if (count == 0) { // refused: done stays 0
+        P.score[i] = 0;
+        P.move[i] = 0;
+        P.nodes[i] = 0;
+        return;
+    }
+    const int64_t j0 = P.job_first[i];
+    int best = NEG_INF, best_m = -1;
+    int child_m = -1, child_best = NEG_INF; // the expanded child whose jobs are being taken back
+    int64_t nodes = 1;
+    bool all = true;
+    for (int64_t j = j0; j < j0 + count; j++) {
+        all = all && P.job_done[j] != 0;
+        nodes += P.job_nodes[j];
+        const int m1 = P.job_path[4 * j + 1], m2 = P.job_path[4 * j + 2];
+        const int v = P.job_score[j];
+        if (m1 < 0) { // the root is the job
+            best = v;
+            best_m = P.job_move[j];
+            nodes--;
+            continue;
+        }
+        if (m1 != child_m && child_m >= 0) {
+            if (-child_best > best) {
+                best = -child_best;
+                best_m = child_m;
+            }
+            child_m = -1;
+        }
+        if (m2 < 0) { // the child is the job
+            if (-v > best) {
+                best = -v;
+                best_m = m1;
+            }
+        } else {
+            if (child_m < 0) {
+                child_m = m1;
+                child_best = NEG_INF;
+                nodes++;
+            }
+            child_best = max(child_best, -v);
+        }
+    }
+    if (child_m >= 0 && -child_best > best) {
+        best = -child_best;
+        best_m = child_m;
+    }
+    if (!all) // (a give-up: the unfinished jobs hold nothing)
+        return;
+    P.score[i] = (int16_t)best;
+    P.move[i] = (int8_t)best_m;
+    P.nodes[i] = nodes;
+    P.done[i] = 1;
 }
 
 // ---- iago_random_moves: the opening draw, a thread per game
@@ -413,6 +683,118 @@ extern "C" int iago_alphabeta_moves(const iago_alphabeta_args *a, void *stream)
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     hipLaunchKernelGGL(alphabeta_kernel, dim3(grid), dim3(WAVE), lds, s, P);
     return iago_check_launch("iago_alphabeta_moves");
+}
+
+extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, void *stream)
+{
+    const char *who = "iago_alphabeta_moves_split";
+    if (!a)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null args");
+    if (a->n < 0 || a->n > INT32_MAX || (a->n > 0 && (!a->own || !a->opp || !a->job_count || !a->job_first)) || !a->ctl)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null pointer, negative n or n above 2^31 - 1");
+    if (a->depth < 2 || a->depth > IAGO_ALPHABETA_MAX_DEPTH)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: depth must be in [2, 10]");
+    if (a->split < 1 || a->split > IAGO_ALPHABETA_MAX_SPLIT || a->split >= a->depth)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: split must be 1 or 2 and below depth");
+    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: time_limit_ms must be in [1, 600000]");
+    if (a->job_capacity < 0 || a->job_capacity > INT32_MAX)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: job_capacity must be in [0, 2^31 - 1]");
+    const int job_arrays = (a->job_own != nullptr) + (a->job_opp != nullptr) + (a->job_root != nullptr) +
+                           (a->job_path != nullptr) + (a->job_score != nullptr) + (a->job_move != nullptr) +
+                           (a->job_nodes != nullptr) + (a->job_done != nullptr);
+    if ((job_arrays != 0 && job_arrays != 8) || (job_arrays == 0 && a->job_capacity != 0))
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: the job arrays are all given, or all null with "
+                                           "job_capacity 0 (the count-only form)");
+    const bool count_only = job_arrays == 0;
+    if (!count_only && a->n > 0 && (!a->score || !a->move || !a->nodes || !a->done))
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null score, move, nodes or done");
+    if (a->reserved0 != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: reserved fields must be 0");
+    for (int i = 0; i < 4; i++)
+        if (a->reserved[i] != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: reserved fields must be 0");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(a->ctl, 0, IAGO_ALPHABETA_SPLIT_CTL_WORDS * sizeof(uint32_t), s) != hipSuccess) {
+        (void)hipGetLastError();
+        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: clearing ctl");
+    }
+    if (a->n == 0)
+        return IAGO_OK;
+    if (!count_only && hipMemsetAsync(a->done, 0, (size_t)a->n, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: clearing done");
+    }
+    const int cus = iago_device_cus();
+    if (cus <= 0)
+        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: no HIP device");
+
+    // 1. expand: count, sum, write
+    SplitParams E;
+    E.own = a->own;
+    E.opp = a->opp;
+    E.n = a->n;
+    E.depth = a->depth;
+    E.split = a->split;
+    E.job_count = a->job_count;
+    E.job_first = a->job_first;
+    E.capacity = a->job_capacity;
+    E.job_own = a->job_own;
+    E.job_opp = a->job_opp;
+    E.job_root = a->job_root;
+    E.job_path = a->job_path;
+    E.job_done = a->job_done;
+    E.ctl = a->ctl;
+    const unsigned roots_grid = (unsigned)((a->n + SPLIT_BLOCK - 1) / SPLIT_BLOCK);
+    hipLaunchKernelGGL(split_count_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, E);
+    hipLaunchKernelGGL(split_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, (const int32_t *)a->job_count, a->job_first,
+                       a->n, count_only ? (int64_t)-1 : a->job_capacity, a->ctl);
+    if (count_only)
+        return iago_check_launch(who);
+    hipLaunchKernelGGL(split_write_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, E);
+
+    // 2. search: the lanes of iago_alphabeta_moves over the jobs
+    JobParams J;
+    J.own = a->job_own;
+    J.opp = a->job_opp;
+    J.path = a->job_path;
+    J.score = a->job_score;
+    J.move = a->job_move;
+    J.nodes = a->job_nodes;
+    J.done = a->job_done;
+    J.ctl = a->ctl;
+    J.levels = a->depth; // the deepest job is a root that must pass: the launch's depth
+    J.clock_limit = (long long)a->time_limit_ms * 100000ll;
+    const int lds = J.levels * WAVE * FRAME_BYTES;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alphabeta_jobs_kernel, WAVE, lds) != hipSuccess ||
+        per_cu <= 0) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    const int64_t want = (a->job_capacity + WAVE - 1) / WAVE;
+    const int64_t cap = (int64_t)cus * per_cu;
+    const unsigned grid = (unsigned)(want < cap ? want : cap);
+    if (grid > 0)
+        hipLaunchKernelGGL(alphabeta_jobs_kernel, dim3(grid), dim3(WAVE), lds, s, J);
+
+    // 3. reduce
+    ReduceParams R;
+    R.n = a->n;
+    R.job_count = a->job_count;
+    R.job_first = a->job_first;
+    R.job_path = a->job_path;
+    R.job_score = a->job_score;
+    R.job_move = a->job_move;
+    R.job_nodes = a->job_nodes;
+    R.job_done = a->job_done;
+    R.score = a->score;
+    R.move = a->move;
+    R.nodes = a->nodes;
+    R.done = a->done;
+    R.ctl = a->ctl;
+    hipLaunchKernelGGL(split_reduce_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, R);
+    return iago_check_launch(who);
 }
 
 extern "C" int iago_random_moves(const uint64_t *own, const uint64_t *opp, int64_t n, uint64_t seed, uint32_t id_base,

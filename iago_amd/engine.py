@@ -47,13 +47,21 @@ PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns pla
 NO_RULES = PlayRules(None, 0, None)
 
 
-class AlphaBeta(collections.namedtuple("AlphaBeta", "depth")):
+class AlphaBeta(collections.namedtuple("AlphaBeta", "depth split", defaults=(0,))):
     """The fixed-depth alpha-beta opponent of SelfPlayEngine.play_match(opponent=): ops.alphabeta_moves at `depth` (an
-    int in [1, 10]), the outside yardstick that owes nothing to the nets."""
+    int in [1, 10]), the outside yardstick that owes nothing to the nets.  split (0, the default: none; 1 or 2, below
+    depth): every root's search spread over the lanes (ops.alphabeta_moves(split=)): the same moves."""
     __slots__ = ()
 
-    def __new__(cls, depth):
-        return super(AlphaBeta, cls).__new__(cls, ops.alphabeta_depth_arg(depth))
+    def __new__(cls, depth, split=0):
+        depth = ops.alphabeta_depth_arg(depth)
+        return super(AlphaBeta, cls).__new__(cls, depth, ops.alphabeta_split_arg(split, depth))
+
+
+# The room play_match gives a split launch of n positions, in jobs: n x this, by split.  (1024 random-play positions of
+# 20 to 40 empties: at most 22 / 279 jobs for one root, 11 / 130 on average.)  A turn whose jobs do not fit is answered
+# by the unsplit launch: the same moves.
+ALPHABETA_JOBS_PER_ROOT = {1: 32, 2: 1024}
 
 
 # a match beyond PV-MCTS against its own policy net, validated by play_match: opponent (None: the policy net, else an
@@ -1720,6 +1728,9 @@ class MatchResult(SelfPlayResult):
     being the match's result, the (T, B) record of the solved rows' exact scores is `solved_score` here."""
 
     SCORE_RECORD = "solved_score"
+    # the turns of a match against AlphaBeta(depth, split) whose jobs did not fit the launch's room, answered by the
+    # unsplit launch (the same moves)
+    split_overflows = 0
 
     def tuples(self):
         """SelfPlayResult.tuples() of the positions PV-MCTS searched (valid == 1) only."""
@@ -1790,6 +1801,8 @@ def _match_rules(opponent, opening_turns, paired, mcts_colour, B):
     [0, 16], paired a bool that needs an even B and no mcts_colour beside it."""
     if opponent is not None and not isinstance(opponent, AlphaBeta):
         raise ValueError("play_match: opponent must be None (the policy net) or an AlphaBeta(depth), not %r" % (opponent,))
+    if opponent is not None:   # (a record made past AlphaBeta's own checks, _make or _replace)
+        opponent = AlphaBeta(*opponent)
     e = opening_turns
     if isinstance(e, bool) or not isinstance(e, numbers.Integral) or not 0 <= e <= 16 or e % 2:
         raise ValueError("play_match: opening_turns must be an even int in [0, 16], not %r" % (e,))
@@ -2024,7 +2037,9 @@ class SelfPlayEngine(object):
         in both.  The move comes from the raw counts.  match (a MatchRules, with policy_moves): the other colour's
         moves are ops.alphabeta_moves' where it names an opponent (one launch per turn, its `done` flags in the turn's
         readback), still recorded with valid 2; at the turns below its opening_turns nobody searches or draws and both
-        colours play ops.random_moves' move, recorded with valid 5 (REC_OPENING)."""
+        colours play ops.random_moves' move, recorded with valid 5 (REC_OPENING).  An opponent with a split is launched
+        with room for B x ALPHABETA_JOBS_PER_ROOT[split] jobs; a turn whose jobs do not fit is answered by the unsplit launch
+        (chosen on the device) and counted in res.split_overflows from the turn's readback."""
         B, T, dev = self.B, self.max_turns, own.device
         k, cap = rules.solve_empties, rules.playout_cap
         opponent, opening_turns = (match.opponent, match.opening_turns) if match is not None else (None, 0)
@@ -2088,7 +2103,7 @@ class SelfPlayEngine(object):
             for i, s in enumerate(sides):
                 s.counts, s.counts_fast = back["counts", i], back.get(("counts_fast", i))
 
-        t, launched = 0, 0
+        t, launched, split_overflows = 0, 0, 0
         drawn, forced, sol, opening, counts = movers(t)
         start_from(_read_back(counts))
         while t < T:
@@ -2102,12 +2117,23 @@ class SelfPlayEngine(object):
                 ex = ops.solve_endgame(torch.where(sol, own, full_board), torch.where(sol, opp, no_board), mode="exact",
                                        max_empties=k, check_result=False)
             mv = none
-            ab = None
+            ab = ab_over = None
             if policy_moves and opening is None:
                 if opponent is not None:
                     # (a game that the opponent does not move in sends a full board: no search, no refusal)
                     ab = ops.alphabeta_moves(torch.where(drawn, own, full_board), torch.where(drawn, opp, no_board),
-                                             opponent.depth, check_result=False)
+                                             opponent.depth, check_result=False, split=opponent.split,
+                                             job_capacity=B * ALPHABETA_JOBS_PER_ROOT[opponent.split]
+                                             if opponent.split else None)
+                    if opponent.split:
+                        # A turn whose jobs did not fit is answered by the unsplit launch: the same moves.  It is chosen
+                        # on the device -- with the jobs in their room every game sends it a full board, one node --,
+                        # so an overflow costs no readback of its own and never plays a wrong move.
+                        ab_over = ab["ctl"][6] != 0
+                        whole = ops.alphabeta_moves(torch.where(drawn & ab_over, own, full_board),
+                                                    torch.where(drawn & ab_over, opp, no_board), opponent.depth,
+                                                    check_result=False)
+                        ab = {k: torch.where(ab_over, whole[k], ab[k]) for k in ("move", "done")}
                     draw = ab["move"]
                 else:
                     with torch.no_grad():
@@ -2159,7 +2185,7 @@ class SelfPlayEngine(object):
             checks = dict(no_children=(mv == -2).any(), all_done=done.all(),
                           bad_draw=(drawn & (draw == 64)).any() if policy_moves and opening is None else None,
                           unsolved=(ex["solved"] == 0).any() if sol is not None else None,
-                          unfinished=(ab["done"] == 0).any() if ab is not None else None)
+                          unfinished=(ab["done"] == 0).any() if ab is not None else None, split_overflow=ab_over)
             drawn, forced, sol, opening, counts = movers(t)
             back = _read_back({**{("flags", i): s.mcts.error_flags(s.gave_up) for i, s in enumerate(sides)},
                                **checks, **counts})
@@ -2176,9 +2202,12 @@ class SelfPlayEngine(object):
             if back.get("unfinished"):
                 raise _lib.IagoError("play_match: the alpha-beta opponent (depth %d) did not finish a position at turn %d"
                                      % (opponent.depth, t - 1))
+            split_overflows += int(back.get("split_overflow") or 0)
             if t % 2 == 0 and back["all_done"]:
                 break
             start_from(back)
+        if opponent is not None:
+            res.split_overflows = split_overflows
         # colour 1's stones are `own` after an even number of turns
         p1, p2 = (own, opp) if t % 2 == 0 else (opp, own)
         self._finish(res, p1, p2, t, launched)
@@ -2302,7 +2331,10 @@ class SelfPlayEngine(object):
         alpha-beta search's (ops.alphabeta_moves at depth d: the lowest-indexed move of the best value), an opponent that
         owes nothing to the nets.  Its move is recorded with valid 2 and advances the tree like any move; the only final
         move keeps its precedence; solve_empties still applies to PV-MCTS's turns alone; a position the opponent does not
-        finish raises IagoError.  opening_turns = e (an even int in [0, 16]; 0, the default: none): at the turns below e
+        finish raises IagoError.  AlphaBeta(d, split=1 or 2) plays the same moves from ops.alphabeta_moves(split=), every
+        root's search spread over the lanes, with room for B x ALPHABETA_JOBS_PER_ROOT[split] jobs per turn and still one
+        readback per turn: a turn whose jobs do not fit takes the unsplit launch's moves and is counted in the result's
+        split_overflows.  opening_turns = e (an even int in [0, 16]; 0, the default: none): at the turns below e
         nobody searches and both colours play ops.random_moves' move -- the r-th lowest legal cell, r = (w * K) >> 32 with
         w the Philox word of (seed ^ OPENING_SEED_XOR; game_id_base + g mod id_mod, t) -- recorded with valid 5
         (REC_OPENING: tuples() never see them), so that a batch against a deterministic opponent is many games.

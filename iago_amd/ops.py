@@ -1142,7 +1142,75 @@ def alphabeta_depth_arg(depth):
     return int(depth)
 
 
-def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True):
+def alphabeta_split_arg(split, depth):
+    """split of alphabeta_moves / engine.AlphaBeta beside its depth: 0 (no split), 1 or 2, and below depth; returned as
+    an int."""
+    if isinstance(split, bool) or not isinstance(split, numbers.Integral) or not 0 <= split <= _lib.ALPHABETA_MAX_SPLIT:
+        raise ValueError("alpha-beta split must be 0, 1 or 2, not %r" % (split,))
+    if split >= depth:
+        raise ValueError("alpha-beta split must be below the depth: split %d at depth %d" % (split, depth))
+    return int(split)
+
+
+def alphabeta_job_count(ctl):
+    """The jobs a split launch needed, from the host values of its ctl words."""
+    return (int(ctl[4]) & 0xFFFFFFFF) | ((int(ctl[5]) & 0xFFFFFFFF) << 32)
+
+
+def _alphabeta_moves_split(own, opp, n, depth, split, time_limit_ms, job_capacity, check_result):
+    """alphabeta_moves with split > 0 (iago_alphabeta_moves_split)."""
+    dev = own.device
+    lib = _lib.lib()
+    a = _lib.AlphaBetaSplitArgs()
+    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
+    a.depth, a.split, a.time_limit_ms = depth, split, int(time_limit_ms)
+    out = dict(score=torch.empty(n, dtype=torch.int16, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               nodes=torch.empty(n, dtype=torch.int64, device=dev), done=torch.empty(n, dtype=torch.uint8, device=dev),
+               ctl=torch.empty(_lib.ALPHABETA_SPLIT_CTL_WORDS, dtype=torch.int32, device=dev),
+               job_count=torch.empty(n, dtype=torch.int32, device=dev),
+               job_first=torch.empty(n, dtype=torch.int64, device=dev))
+    a.job_count, a.job_first = _dev(out["job_count"], torch.int32, "job_count"), _dev(out["job_first"], torch.int64, "job_first")
+    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
+    if job_capacity is None:
+        # the count-only form and one readback: the arrays hold the jobs exactly
+        check(lib.iago_alphabeta_moves_split(C.byref(a), _stream()), "iago_alphabeta_moves_split")
+        job_capacity = alphabeta_job_count(out["ctl"].tolist())
+    cap = int(job_capacity)
+    a.score, a.move = _dev(out["score"], torch.int16, "score"), _dev(out["move"], torch.int8, "move")
+    a.nodes, a.done = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["done"], torch.uint8, "done")
+    a.job_capacity = cap
+    for k, dt, cols in (("job_own", torch.int64, 1), ("job_opp", torch.int64, 1), ("job_root", torch.int32, 1),
+                        ("job_path", torch.int8, 4), ("job_score", torch.int16, 1), ("job_move", torch.int8, 1),
+                        ("job_nodes", torch.int64, 1), ("job_done", torch.uint8, 1)):
+        # (an empty tensor has no address, and null arrays are the count-only form: room for one job at least)
+        t = torch.empty(max(cap, 1) * cols, dtype=dt, device=dev)
+        setattr(a, k, _dev(t, dt, k))
+        out[k] = t[:cap * cols].reshape(cap, 4) if cols == 4 else t[:cap]
+    out["job_capacity"] = cap
+    check(lib.iago_alphabeta_moves_split(C.byref(a), _stream()), "iago_alphabeta_moves_split")
+    if check_result:
+        ctl = out["ctl"].tolist()
+        out["jobs"] = alphabeta_job_count(ctl)
+        gave_up, _, refused, overflow = (int(v) for v in ctl[:4])
+        if ctl[6] or gave_up or refused or overflow:
+            if ctl[6]:
+                what = "the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap)
+            elif overflow:
+                what = "a job needed more stack frames than depth = %d sizes (ctl[3] set)" % depth
+            elif gave_up:
+                what = "gave up at its clock limit (%d ms): %d of %d positions unfinished" % (
+                    time_limit_ms, n - int(out["done"].sum().item()), n)
+            else:
+                what = "%d positions refused (own & opp != 0)" % refused
+            err = _lib.IagoError("iago_alphabeta_moves_split: " + what)
+            err.result = out
+            if ctl[6]:
+                err.jobs_needed = out["jobs"]
+            raise err
+    return out
+
+
+def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True, split=0, job_capacity=None):
     """A fixed-depth alpha-beta search on a hand-written evaluation for every position (iago_alphabeta_moves,
     include/iago_hip_serving.h): the opponent that owes nothing to the nets.
 
@@ -1151,11 +1219,27 @@ def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_
     lowest-indexed move whose value equals the score (-1: the side to move must pass, -2: the game is over), nodes
     (n,) int64, done (n,) uint8, ctl (4,) int32.  check_result (one host sync): raise IagoError when the launch gave up
     at time_limit_ms, refused a position (own & opp != 0) or overflowed its stack (ctl[3]); the result is the error's
-    `result` attribute."""
+    `result` attribute.
+
+    split = 1 or 2 (0, the default: the call above, argument for argument; anything else, or split >= depth, is a
+    ValueError): the same score, move and done from iago_alphabeta_moves_split, which spreads every root's search over
+    the lanes -- the first `split` plies expanded into jobs on the device, the jobs searched a lane each, their values
+    taken back per root.  nodes is then the nodes expanded + the jobs' own.  job_capacity: the jobs the launch has room
+    for; None takes a count-only launch and one readback first and allocates exactly, an int takes no readback -- where
+    the jobs do not fit nothing is searched, every done is 0, ctl[6] is set, and check_result raises an IagoError with
+    the count needed in `jobs_needed`.  The dict then also holds ctl (8,) int32 (ctl[4] / [5]: the jobs needed),
+    job_count (n,) int32, job_first (n,) int64, the job arrays job_own, job_opp, job_root, job_path (depth left, first
+    move, second move, 0), job_score, job_move, job_nodes, job_done, job_capacity and, with check_result, `jobs`."""
     depth = alphabeta_depth_arg(depth)
+    split = alphabeta_split_arg(split, depth)
+    if job_capacity is not None and (isinstance(job_capacity, bool) or not isinstance(job_capacity, numbers.Integral)
+                                     or not 0 <= job_capacity < 2 ** 31):
+        raise ValueError("job_capacity must be None or an int in [0, 2^31), not %r" % (job_capacity,))
     n = own.numel()
     if opp.numel() != n:
         raise ValueError("own/opp sizes differ")
+    if split:
+        return _alphabeta_moves_split(own, opp, n, depth, split, time_limit_ms, job_capacity, check_result)
     dev = own.device
     out = dict(score=torch.empty(n, dtype=torch.int16, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
                nodes=torch.empty(n, dtype=torch.int64, device=dev), done=torch.empty(n, dtype=torch.uint8, device=dev),

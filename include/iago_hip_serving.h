@@ -469,6 +469,67 @@ typedef struct iago_alphabeta_args {
  */
 IAGO_API int iago_alphabeta_moves(const iago_alphabeta_args *args, void *stream);
 
+#define IAGO_ALPHABETA_MAX_SPLIT 2
+#define IAGO_ALPHABETA_SPLIT_CTL_WORDS 8
+
+typedef struct iago_alphabeta_split_args {
+    const uint64_t *own; /* [n] side to move */
+    const uint64_t *opp; /* [n] its opponent */
+    int64_t n;           /* at most 2^31 - 1 */
+    int32_t depth;         /* 2 .. IAGO_ALPHABETA_MAX_DEPTH */
+    int32_t split;         /* 1 .. IAGO_ALPHABETA_MAX_SPLIT, and at most depth - 1: the plies expanded into jobs */
+    int32_t time_limit_ms; /* 1 .. IAGO_ENDGAME_MAX_TIME_MS, of the search stage */
+    int32_t reserved0;     /* 0 */
+    int16_t *score;        /* [n] out */
+    int8_t *move;          /* [n] out */
+    int64_t *nodes;        /* [n] out */
+    uint8_t *done;         /* [n] out: 1 = every job of the root finished, score and move are the search's */
+    int32_t *job_count;    /* [n] out: the jobs of root i */
+    int64_t *job_first;    /* [n] out: the index of its first job (the exclusive sum of job_count) */
+    int64_t job_capacity;  /* the jobs the arrays below hold, at most 2^31 - 1 */
+    uint64_t *job_own;     /* [job_capacity] out: the job's side to move */
+    uint64_t *job_opp;     /* [job_capacity] out */
+    int32_t *job_root;     /* [job_capacity] out: the root it belongs to */
+    int8_t *job_path;      /* [job_capacity][4] out: depth left, first move, second move (-1 where absent), 0 */
+    int16_t *job_score;    /* [job_capacity] out: search(job_own, job_opp, depth left) */
+    int8_t *job_move;      /* [job_capacity] out */
+    int64_t *job_nodes;    /* [job_capacity] out */
+    uint8_t *job_done;     /* [job_capacity] out */
+    uint32_t *ctl;         /* [IAGO_ALPHABETA_SPLIT_CTL_WORDS] cleared by the call; [0] != 0: gave up, [1]: the claim
+                              counter, [2]: positions refused, [3] != 0: a stack overflow, [4] / [5]: the low / high word
+                              of the jobs needed, [6] != 0: they exceed job_capacity (nothing was searched), [7]: 0 */
+    int64_t reserved[4];   /* 0 */
+} iago_alphabeta_split_args;
+
+/*
+ * iago_alphabeta_moves with every root's search spread over many lanes: the same (score, move) for every position, bit
+ * for bit, from one call on `stream` with no host round trip inside it.  The rule, in integers: a node (own, opp) with d
+ * depth left and k split plies left (the root: depth, split)
+ *   - is a JOB (own, opp, d) when k == 0 or its mover has no legal move: its value is search(own, opp, d) from its
+ *     mover's view, what iago_alphabeta_moves returns for that position at depth d, found with the full window, and its
+ *     nodes are that call's;
+ *   - is EXPANDED otherwise: its children are its legal moves in ascending index, each with (d - 1, k - 1), its value
+ *     the maximum of the negated children's values.
+ * So a root that must pass or whose game is over is one job of the full depth and its move is the job's (-1 / -2); a
+ * child that cannot move is one job of depth - 1; every other job has depth - split >= 1 left.  move[i] is the
+ * lowest-indexed move whose value equals score[i]; nodes[i] = the nodes expanded (the root, and at split 2 every
+ * expanded child) + the sum of its jobs' nodes, so it depends on no timing.
+ * Three stages: (1) the jobs of every root are counted (job_count), summed (job_first; ctl[4] / [5] = their total) and
+ * written in canonical order -- root ascending, then first move, then second move; (2) the lanes of
+ * iago_alphabeta_moves' search claim jobs one at a time, each with its own depth; (3) a thread per root takes its run of
+ * jobs back, the sign turned once per ply of the path.  More jobs than job_capacity: ctl[6] is set, nothing is
+ * searched, every done[i] stays 0 and nothing is written past the capacity.  The COUNT-ONLY form -- every job_* array
+ * null and job_capacity 0 -- writes job_count, job_first and ctl[4] / [5] and launches nothing else (score, move, nodes
+ * and done may be null then; ctl[6] stays 0).  A position with own & opp != 0 is refused as there: ctl[2] counts it, it
+ * has no job and done[i] = 0.  The give-up is the search stage's, as there: ctl[0] != 0, done[i] = 0 for every root with
+ * an unfinished job.  Host-side refusals (IAGO_ERR_INVALID, nothing launched): a null args / ctl / own / opp /
+ * job_count / job_first with n > 0, n < 0 or above 2^31 - 1, a depth above IAGO_ALPHABETA_MAX_DEPTH, a split outside
+ * 1 .. IAGO_ALPHABETA_MAX_SPLIT or not below depth, a time_limit_ms out of range, a job_capacity below 0 or above
+ * 2^31 - 1, some but not all job_* arrays null or null ones with a capacity, a null score / move / nodes / done outside
+ * the count-only form, reserved fields not 0.
+ */
+IAGO_API int iago_alphabeta_moves_split(const iago_alphabeta_split_args *args, void *stream);
+
 /*
  * The random opening of a match against that opponent, a thread per game: the mover of game g (own[g] to move) with
  * K >= 1 legal moves plays the r-th lowest legal cell, r = (uint64(w) * K) >> 32, w = word turn & 3 of Philox4x32-10 on

@@ -6,11 +6,13 @@ once as colour 2 -- at every playout count of --sims, under both backup rules, a
 
     python tools/run_yardstick.py [--games 1024] [--sims 100,400] [--depths 1,2,4,6] [--backups reference,negamax]
                                   [--selections reference] [--c-pucts 1.0] [--append]
-                                  [--opening-turns 8] [--seed 5] [--out profiles/alphabeta_yardstick.json]
+                                  [--opening-turns 8] [--seed 5] [--split 0] [--out profiles/alphabeta_yardstick.json]
 
 --selections: the selection rules (engine.selection_arg: "reference", "alphazero"), --c-pucts: the exploration constants;
 every combination with --backups and --sims is a row of cells.  --append: the cells are added to those --out already
-holds (same games, opening turns and seed, or refused) instead of replacing them.
+holds (same games, opening turns and seed, or refused) instead of replacing them.  --split: the opponent's root split
+(engine.AlphaBeta(depth, split): the same moves, launched over more lanes), at a depth that has no room for it the
+largest split below the depth; a cell records the split it ran with and the turns whose jobs overflowed their room.
 
 Per cell: PV-MCTS's wins / draws / losses, its score (a draw counting 1/2) with the 95 % Wilson interval, overall and per
 colour, the turns of the longest game and the wall time of the match (one untimed warm-up match per engine before its
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--append", action="store_true")
     ap.add_argument("--opening-turns", type=int, default=8)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--split", type=int, default=0, choices=(0, 1, 2))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "alphabeta_yardstick.json"))
     args = ap.parse_args()
     from iago_amd import engine, network, ops
@@ -79,13 +82,14 @@ def main():
             m.sim_counter = 0
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            r = eng.play_match(sims, opponent=engine.AlphaBeta(depth), **kw)
+            split = min(args.split, depth - 1)
+            r = eng.play_match(sims, opponent=engine.AlphaBeta(depth, split=split), **kw)
             torch.cuda.synchronize()
             s = time.perf_counter() - t0
             z = r.z.to(torch.int32) * torch.where(r.mcts_colour == 1, 1, -1).to(torch.int32)
             c = r.mcts_colour
             cells.append(dict(backup=backup, selection=selection, c_puct=c_puct, n_sims=sims, depth=depth, s=round(s, 2),
-                              turns=r.n_turns,
+                              turns=r.n_turns, split=split, split_overflows=r.split_overflows,
                               mcts=dict(overall=tally(z), as_colour_1=tally(z[c == 1]), as_colour_2=tally(z[c == 2]))))
             print(json.dumps(cells[-1]), file=sys.stderr, flush=True)
         m.close()
