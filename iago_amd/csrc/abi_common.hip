@@ -57,6 +57,51 @@ int iago_device_cus()
     return c;
 }
 
+static int search_fail(const char *who, const char *what, const char *name)
+{
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: %s%s", who, what, name);
+    return iago_fail(IAGO_ERR_HIP, msg);
+}
+
+int iago_search_prepare(const char *who, uint32_t *ctl, int ctl_words, uint8_t *done, const char *done_name, int64_t n,
+                        hipStream_t s, int *cus)
+{
+    *cus = 0;
+    if (hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint32_t), s) != hipSuccess) {
+        (void)hipGetLastError();
+        return search_fail(who, "clearing ", "ctl");
+    }
+    if (n == 0)
+        return IAGO_OK;
+    if (done && hipMemsetAsync(done, 0, (size_t)n, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return search_fail(who, "clearing ", done_name);
+    }
+    *cus = iago_device_cus();
+    if (*cus <= 0)
+        return search_fail(who, "no HIP device", "");
+    return IAGO_OK;
+}
+
+void iago_search_launch(const void *kernel, void *params, int levels, int frame_bytes, int64_t lanes, int cus,
+                        hipStream_t s)
+{
+    const int wave = 64;
+    const int lds = levels * wave * frame_bytes;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, wave, lds) != hipSuccess || per_cu <= 0) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    const int64_t want = (lanes + wave - 1) / wave;
+    const int64_t cap = (int64_t)cus * per_cu;
+    const unsigned grid = (unsigned)(want < cap ? want : cap);
+    void *args[] = {params};
+    if (grid > 0)
+        (void)hipLaunchKernel(kernel, dim3(grid), dim3(wave), args, lds, s); // (an error stays for iago_check_launch)
+}
+
 extern "C" {
 
 int iago_abi_version(void) { return 13; }

@@ -12,6 +12,19 @@ int iago_check_launch(const char *where);
 // The current device's compute units (asked once per process); 0 when there is no HIP device.
 int iago_device_cus();
 
+// The host side of a lane-per-position search launch (lane_search.hpp), in two steps so that a caller may enqueue
+// stages of its own between them.  iago_search_prepare: ctl's first ctl_words words cleared; n == 0: IAGO_OK with
+// *cus = 0, there is nothing to launch; else the n bytes of `done` cleared (a null `done` is skipped) and the device's
+// compute units in *cus.  Errors are recorded as "<who>: clearing ctl", "<who>: clearing <done_name>",
+// "<who>: no HIP device".
+int iago_search_prepare(const char *who, uint32_t *ctl, int ctl_words, uint8_t *done, const char *done_name, int64_t n,
+                        hipStream_t s, int *cus);
+// iago_search_launch: `kernel` (one wave per workgroup, one params struct, levels x 64 x frame_bytes of dynamic LDS)
+// with a lane per `lanes`, but never more workgroups than the CUs hold at once -- the give-up is per wave's own
+// clock, so every workgroup must be resident.  No launch for lanes == 0.  The caller asks iago_check_launch.
+void iago_search_launch(const void *kernel, void *params, int levels, int frame_bytes, int64_t lanes, int cus,
+                        hipStream_t s);
+
 #include <atomic>
 // One-time hipFuncSetAttribute(MaxDynamicSharedMemorySize) per (kernel, device): `done` is a
 // per-kernel bit mask of the devices already configured.  Safe from several threads (a lost

@@ -6,25 +6,22 @@
 //   -search(opp, own, d), a pass in place that costs no depth.  d == 0 -> eval(own, opp).  Else the maximum over the
 //   legal moves m of -search(play(own, opp, m), d - 1).
 //   terminal = 10000 sign(D) + 100 D, D = #own - #opp; eval = the seven square classes below + 8 x the mobility difference.
-// The kernel has the shape of endgame_kernel.hip: one LANE PER POSITION, the node in registers, an explicit stack in LDS
-// laid out [level][lane] (32 B per level: own, opp, the untried moves and one packed word of alpha / beta / best as
-// int16, the pass flag and the move tried), passes in place without a frame, positions claimed from a counter in ctl,
-// the wall clock read once per step.  What differs from the solver:
-//   * the depth of a node is its level, not its empties: a node of remaining depth 1 pushes no frame -- each of its
-//     children is a LEAF, evaluated in the parent in one step (eval is antisymmetric, so a leaf whose mover must pass
-//     needs no second look: its value is eval or, when neither side can move, terminal);
-//   * values are int16 (|eval| < 10000 <= |terminal| <= 16400 unless the game is drawn), the window is +-32767;
+// The search is lane_search.hpp's, the one of endgame_kernel.hip -- a lane per position, the node in registers, an
+// explicit stack in LDS, passes in place, positions claimed from ctl, the root's tie rule -- on YardstickRules below:
+//   * a node's remaining levels are the depth left, not its empties: a node of remaining depth 1 pushes no frame -- each
+//     of its children is a LEAF, evaluated in the parent in one step (eval is antisymmetric, so a leaf whose mover must
+//     pass needs no second look: its value is eval or, when neither side can move, terminal);
+//   * values are int16 (|eval| < 10000 <= |terminal| <= 16400 unless the game is drawn), the window is +-32767, a frame
+//     is 32 B per level and lane (alpha / beta / best as int16);
 //   * move order below the root's tie rule: a corner first, then at nodes of remaining depth >= ORDER_DEPTH the move
-//     with the fewest replies (ties: lowest index), else index order.  Only `nodes` depends on it;
-//   * the root's tie rule is the solver's: every move that could tie the best value with a lower index is searched with
-//     a window that keeps the tie exact, so `move` is the lowest-indexed move reaching the score whatever the order.
+//     with the fewest replies (ties: lowest index), else index order.  Only `nodes` depends on it.
 // iago_alphabeta_moves_split spreads every root over many lanes: the first one or two plies are expanded into JOBS
-// (position, depth left) on the device, the same search runs a lane per job (search_wave<true>: the job count read from
-// ctl, every lane's depth from its job), and a thread per root takes the values back.  Every job has the full window,
+// (position, depth left) on the device, the same search runs a lane per job (alphabeta_jobs_kernel: the job count read
+// from ctl, every lane's depth from its job), and a thread per root takes the values back.  Every job has the full window,
 // so its value and its node count are those of iago_alphabeta_moves on that position, whatever else runs beside it.
 #include "abi_common.hpp"
+#include "lane_search.hpp"
 #include "othello_dev.hpp"
-#include "othello_lane.hpp"
 
 #include "../../include/iago_hip_serving.h"
 
@@ -33,52 +30,14 @@ using namespace iago::lane;
 
 namespace {
 
-constexpr int WAVE = 64;           // one wave per workgroup: the stack is the wave's own
 constexpr int ORDER_DEPTH = 3;     // nodes with at least this much depth left try their moves fewest replies first
-constexpr int NEG_INF = -32768;    // below every value
-constexpr int WINDOW = 32767;      // the root's window is (-WINDOW, WINDOW)
-constexpr int FRAME_BYTES = 32;    // per level and lane: own, opp, moves, info (u64 each)
 constexpr uint32_t OPEN_KEY = IAGO_OPENING_KEY;
 constexpr uint64_t CORNERS = 0x8100000000000081ull;
 
-constexpr int CTL_GAVE_UP = 0;
-constexpr int CTL_CLAIM = 1;
-constexpr int CTL_REFUSED = 2;
-constexpr int CTL_OVERFLOW = 3;
-// iago_alphabeta_moves_split's further words
+// iago_alphabeta_moves_split's further ctl words
 constexpr int CTL_JOBS_LO = 4;
 constexpr int CTL_JOBS_HI = 5;
 constexpr int CTL_JOB_OVERFLOW = 6;
-
-enum Phase : uint32_t { CLAIM = 0, ENTER = 1, NEXT = 2, RETURN = 3, DONE = 4 };
-
-struct AlphaBetaParams {
-    const uint64_t *own;
-    const uint64_t *opp;
-    int64_t n;
-    int16_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *done;
-    uint32_t *ctl;
-    int32_t depth;
-    int32_t levels;          // stack frames per lane
-    long long clock_limit;   // wall_clock64 ticks (100 MHz)
-};
-
-// alpha, beta, best as int16 (offset 32768), pass flag, move tried
-__device__ __forceinline__ uint64_t pack_info(int alpha, int beta, int best, uint32_t passed, uint32_t m)
-{
-    const uint32_t lo = (uint32_t)(alpha + 32768) | ((uint32_t)(beta + 32768) << 16);
-    const uint32_t hi = (uint32_t)(best + 32768) | (passed << 16) | (m << 17);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ int terminal_value(uint64_t own, uint64_t opp)
-{
-    const int d = __popcll(own) - __popcll(opp); // empty squares go to nobody (judge)
-    return 10000 * ((d > 0) - (d < 0)) + 100 * d;
-}
 
 template <int V>
 __device__ __forceinline__ int class_term(uint64_t own, uint64_t opp, uint64_t mask)
@@ -95,191 +54,97 @@ __device__ __forceinline__ int eval_value(uint64_t own, uint64_t opp, uint64_t l
            class_term<-1>(own, opp, 0x00003C3C3C3C0000ull) + 8 * (__popcll(lo) - __popcll(lp));
 }
 
-// search(own, opp, 0): terminal when neither side can move, else eval (a mover that must pass: -eval(opp, own) = eval)
-__device__ __forceinline__ int leaf_value(uint64_t own, uint64_t opp, const ShiftAmounts &SA)
-{
-    const uint64_t lo = legal_of(own, opp, SA), lp = legal_of(opp, own, SA);
-    return (lo | lp) == 0ull ? terminal_value(own, opp) : eval_value(own, opp, lo, lp);
-}
+struct YardstickRules {
+    using Info = uint64_t;
+    static constexpr int NEG_INF = -32768;
+    static constexpr bool COUNT_LAST = false;
+    static constexpr bool LEAF_CHILDREN = true;
 
-// The untried move to search next: a corner, else (depth left >= ORDER_DEPTH) the fewest opponent replies, else the
-// lowest index.
-__device__ __forceinline__ uint32_t pick_move(uint64_t own, uint64_t opp, uint64_t moves, int rem, const ShiftAmounts &SA)
-{
-    const uint64_t corners = moves & CORNERS;
-    uint32_t best_m = lowest_bit(corners != 0ull ? corners : moves);
-    if (corners == 0ull && rem >= ORDER_DEPTH) {
-        uint32_t best_mob = 65u;
-        uint64_t rest = moves;
-        while (rest) {
-            const uint32_t m = lowest_bit(rest);
-            rest &= rest - 1ull;
-            const uint64_t f = flips_of(own, opp, m);
-            const uint32_t mob = (uint32_t)__popcll(legal_of(opp & ~f, own | f | (1ull << m), SA));
-            if (mob < best_mob) {
-                best_mob = mob;
-                best_m = m;
-            }
-        }
+    __device__ __forceinline__ int window() const { return 32767; }
+
+    __device__ __forceinline__ int terminal(uint64_t own, uint64_t opp) const
+    {
+        const int d = __popcll(own) - __popcll(opp); // empty squares go to nobody (judge)
+        return 10000 * ((d > 0) - (d < 0)) + 100 * d;
     }
-    return best_m;
-}
 
-// a lane's search: the node it works on, the value on its way back, the level, the root's books
-struct Search {
-    uint32_t phase;
-    uint64_t own, opp, moves;
-    int alpha, beta, best, v;
-    int d;
-    uint32_t passed;
-    int root_move;
-    int64_t nodes;
-};
-
-// the wave's stack in LDS, [level][lane]
-struct Stack {
-    uint64_t *own, *opp, *moves, *info;
-    int levels;
-};
-
-__device__ __forceinline__ Stack make_stack(unsigned char *lds, int levels)
-{
-    Stack K;
-    K.own = (uint64_t *)lds;
-    K.opp = K.own + levels * WAVE;
-    K.moves = K.opp + levels * WAVE;
-    K.info = K.moves + levels * WAVE;
-    K.levels = levels;
-    return K;
-}
-
-__device__ __forceinline__ void search_begin(Search &s, uint64_t own, uint64_t opp)
-{
-    s.own = own;
-    s.opp = opp;
-    s.d = 0;
-    s.alpha = -WINDOW;
-    s.beta = WINDOW;
-    s.nodes = 0;
-    s.root_move = -1;
-    s.phase = ENTER;
-}
-
-__device__ __forceinline__ bool search_done(const Search &s) { return s.phase == RETURN && s.d == 0; }
-
-// the value v of the child reached by move m, back in its parent (the node in s)
-__device__ __forceinline__ void take_back(Search &s, int m, int v)
-{
-    if (s.d == 0 && !s.passed) {
-        // root: the lowest index among the moves of the best value (the window kept every tie exact)
-        if (v > s.best || (v == s.best && m < s.root_move)) {
-            s.best = v;
-            s.root_move = m;
-        }
-    } else {
-        s.best = max(s.best, v);
-        s.alpha = max(s.alpha, s.best);
-        if (s.alpha >= s.beta)
-            s.moves = 0ull; // cut-off
+    // search(own, opp, 0): terminal when neither side can move, else eval (a mover that must pass: -eval(opp, own) = eval)
+    __device__ __forceinline__ int leaf(uint64_t own, uint64_t opp, const ShiftAmounts &SA) const
+    {
+        const uint64_t lo = legal_of(own, opp, SA), lp = legal_of(opp, own, SA);
+        return (lo | lp) == 0ull ? terminal(own, opp) : eval_value(own, opp, lo, lp);
     }
-}
 
-// One step of a lane that is searching (phase ENTER, NEXT or RETURN below the root; any other phase: nothing): one node
-// entered, one child's value taken back, or one leaf evaluated.  false: the stack would overflow (cannot happen: a
-// frame is pushed at levels 0 .. depth - 2) -- nothing was written past it, the caller drops the position.
-__device__ __forceinline__ bool search_step(Search &s, const Stack &K, uint32_t lane, int depth, const ShiftAmounts &SA)
-{
-    if (s.phase == ENTER) {
-        s.nodes++;
-        s.passed = 0u;
-        uint64_t legal = legal_of(s.own, s.opp, SA);
-        if (legal == 0ull) {
-            const uint64_t other = legal_of(s.opp, s.own, SA);
-            if (other == 0ull) { // neither side can move: the game is over
-                s.v = terminal_value(s.own, s.opp);
-                if (s.d == 0)
-                    s.root_move = -2;
-                s.phase = RETURN;
-            } else { // pass in place
-                const uint64_t t = s.own;
-                s.own = s.opp;
-                s.opp = t;
-                const int a = s.alpha;
-                s.alpha = -s.beta;
-                s.beta = -a;
-                s.passed = 1u;
-                legal = other;
-            }
-        }
-        if (s.phase == ENTER) {
-            s.moves = legal;
-            s.best = NEG_INF;
-            if (s.d == 0)
-                s.root_move = s.passed ? -1 : 64; // 64: no move yet (above every index)
-            s.phase = NEXT;
-        }
-    } else if (s.phase == RETURN && s.d > 0) {
-        // the child's value, back in the parent
-        s.d--;
-        const int k = s.d * WAVE + (int)lane;
-        s.own = K.own[k];
-        s.opp = K.opp[k];
-        s.moves = K.moves[k];
-        const uint64_t info = K.info[k];
+    // a corner, else (depth left >= ORDER_DEPTH) the fewest opponent replies, else the lowest index
+    __device__ __forceinline__ uint32_t pick_move(uint64_t own, uint64_t opp, uint64_t moves, int rem,
+                                                  const ShiftAmounts &SA) const
+    {
+        const uint64_t corners = moves & CORNERS;
+        if (corners != 0ull)
+            return lowest_bit(corners);
+        return rem >= ORDER_DEPTH ? fewest_replies(own, opp, moves, SA) : lowest_bit(moves);
+    }
+
+    // alpha, beta, best as int16 (offset 32768), pass flag, move tried
+    static __device__ __forceinline__ Info pack(int alpha, int beta, int best, uint32_t passed, uint32_t m)
+    {
+        const uint32_t lo = (uint32_t)(alpha + 32768) | ((uint32_t)(beta + 32768) << 16);
+        const uint32_t hi = (uint32_t)(best + 32768) | (passed << 16) | (m << 17);
+        return ((uint64_t)hi << 32) | lo;
+    }
+
+    static __device__ __forceinline__ int unpack(Info info, Search &s)
+    {
         const uint32_t lo = (uint32_t)info, hi = (uint32_t)(info >> 32);
         s.alpha = (int)(lo & 0xFFFFu) - 32768;
         s.beta = (int)(lo >> 16) - 32768;
         s.best = (int)(hi & 0xFFFFu) - 32768;
         s.passed = (hi >> 16) & 1u;
-        take_back(s, (int)(hi >> 17), -s.v);
-        s.phase = NEXT;
+        return (int)(hi >> 17);
+    }
+};
+
+constexpr int NEG_INF = YardstickRules::NEG_INF;
+
+// what a finished search answers, for both params below
+template <class Params>
+__device__ __forceinline__ void write_answer(const Params &P, int64_t pos, const Search &s)
+{
+    P.score[pos] = (int16_t)s.v;
+    P.move[pos] = (int8_t)s.root_move;
+    P.nodes[pos] = s.nodes;
+    P.done[pos] = 1;
+}
+
+struct AlphaBetaParams {
+    const uint64_t *own;
+    const uint64_t *opp;
+    int64_t n;
+    int16_t *score;
+    int8_t *move;
+    int64_t *nodes;
+    uint8_t *done;
+    uint32_t *ctl;
+    int32_t depth;
+    int32_t levels;          // stack frames per lane
+    long long clock_limit;   // wall_clock64 ticks (100 MHz)
+
+    __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &) const
+    {
+        o = own[pos];
+        p = opp[pos];
+        if ((o & p) == 0ull)
+            return true;
+        // refused: done stays 0
+        atomicAdd(&ctl[CTL_REFUSED], 1u);
+        score[pos] = 0;
+        move[pos] = 0;
+        nodes[pos] = 0;
+        return false;
     }
 
-    if (s.phase == NEXT) {
-        const bool root = s.d == 0 && !s.passed;
-        const int rem = depth - s.d;
-        uint32_t m = 0u;
-        int a_child = s.alpha;
-        bool go = false;
-        while (s.moves != 0ull) {
-            m = pick_move(s.own, s.opp, s.moves, rem, SA);
-            s.moves &= ~(1ull << m);
-            if (root && s.best > NEG_INF) // a tie of a lower index must come back exact, a higher one must beat best
-                a_child = max(s.alpha, (int)m < s.root_move ? s.best - 1 : s.best);
-            if (a_child < s.beta) {
-                go = true;
-                break;
-            }
-        }
-        if (go) {
-            const uint64_t f = flips_of(s.own, s.opp, m);
-            const uint64_t cown = s.opp & ~f, copp = s.own | f | (1ull << m);
-            if (rem <= 1) {
-                // a child with no depth left: a leaf, valued here without a frame
-                s.nodes++;
-                take_back(s, (int)m, -leaf_value(cown, copp, SA));
-            } else {
-                if (s.d >= K.levels) // cannot happen (d <= depth - 2): never write past the stack
-                    return false;
-                const int k = s.d * WAVE + (int)lane;
-                K.own[k] = s.own;
-                K.opp[k] = s.opp;
-                K.moves[k] = s.moves;
-                K.info[k] = pack_info(s.alpha, s.beta, s.best, s.passed, m);
-                s.own = cown;
-                s.opp = copp;
-                s.alpha = -s.beta;
-                s.beta = -a_child;
-                s.d++;
-                s.phase = ENTER;
-            }
-        } else {
-            s.v = s.passed ? -s.best : s.best;
-            s.phase = RETURN;
-        }
-    }
-    return true;
-}
+    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const { write_answer(*this, pos, s); }
+};
 
 // The jobs of iago_alphabeta_moves_split as the search reads and answers them: positions with a depth of their own
 struct JobParams {
@@ -293,97 +158,32 @@ struct JobParams {
     uint32_t *ctl;
     int32_t levels;          // stack frames per lane: the launch's depth
     long long clock_limit;
+
+    __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &depth) const
+    {
+        o = own[pos];
+        p = opp[pos];
+        depth = path[4 * pos];
+        return true;
+    }
+
+    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const { write_answer(*this, pos, s); }
 };
-
-// The search of a wave, lane per position: JOBS = false over the n positions of P at P.depth (a refused position is
-// counted and skipped), JOBS = true over the jobs of a split search -- their number read from ctl (none after an
-// overflow of the job arrays), every lane's depth read from its job.
-template <bool JOBS, class Params>
-__device__ __forceinline__ void search_wave(const Params &P, unsigned char *stack_lds)
-{
-    const uint32_t lane = threadIdx.x;
-    const Stack K = make_stack(stack_lds, P.levels);
-    const ShiftAmounts SA = opaque_shift_amounts();
-    const long long t0 = wall_clock64();
-
-    int64_t n;
-    if constexpr (JOBS) {
-        n = P.ctl[CTL_JOB_OVERFLOW] != 0u ? 0 : (int64_t)P.ctl[CTL_JOBS_LO];
-        if ((int64_t)blockIdx.x * WAVE >= n) // nothing to claim: the wave leaves at once
-            return;
-    } else {
-        n = P.n;
-    }
-
-    Search s = {};
-    s.phase = CLAIM;
-    int64_t pos = 0;
-    int depth = 0;
-    if constexpr (!JOBS)
-        depth = P.depth;
-
-    while (true) {
-        if (s.phase == CLAIM) {
-            if (__hip_atomic_load(&P.ctl[CTL_GAVE_UP], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                s.phase = DONE;
-            } else {
-                pos = (int64_t)atomicAdd(&P.ctl[CTL_CLAIM], 1u);
-                if (pos >= n) {
-                    s.phase = DONE;
-                } else {
-                    const uint64_t own = P.own[pos], opp = P.opp[pos];
-                    if constexpr (JOBS) {
-                        depth = P.path[4 * pos];
-                        search_begin(s, own, opp);
-                    } else {
-                        if ((own & opp) != 0ull) {
-                            // refused: done stays 0
-                            atomicAdd(&P.ctl[CTL_REFUSED], 1u);
-                            P.score[pos] = 0;
-                            P.move[pos] = 0;
-                            P.nodes[pos] = 0;
-                        } else {
-                            search_begin(s, own, opp);
-                        }
-                    }
-                }
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(s.phase != DONE) == 0ull)
-            break;
-        if (wall_clock64() - t0 > P.clock_limit) {
-            // give up: the unfinished positions keep done = 0 (cleared before the launch)
-            if (s.phase != DONE)
-                __hip_atomic_store(&P.ctl[CTL_GAVE_UP], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-
-        if (!search_step(s, K, lane, depth, SA)) {
-            atomicOr(&P.ctl[CTL_OVERFLOW], 1u);
-            s.phase = CLAIM;
-            continue;
-        }
-
-        if (search_done(s)) {
-            P.score[pos] = (int16_t)s.v;
-            P.move[pos] = (int8_t)s.root_move;
-            P.nodes[pos] = s.nodes;
-            P.done[pos] = 1;
-            s.phase = CLAIM;
-        }
-    }
-}
 
 __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
 {
     extern __shared__ __align__(16) unsigned char stack_lds[];
-    search_wave<false>(P, stack_lds);
+    search_wave(P, YardstickRules{}, P.n, P.depth, stack_lds);
 }
 
+// over the jobs of a split search: their number read from ctl (none after an overflow of the job arrays)
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(8, 8))) void alphabeta_jobs_kernel(JobParams P)
 {
     extern __shared__ __align__(16) unsigned char stack_lds[];
-    search_wave<true>(P, stack_lds);
+    const int64_t n = P.ctl[CTL_JOB_OVERFLOW] != 0u ? 0 : (int64_t)P.ctl[CTL_JOBS_LO];
+    if ((int64_t)blockIdx.x * WAVE >= n) // nothing to claim: the wave leaves at once
+        return;
+    search_wave(P, YardstickRules{}, n, 0, stack_lds);
 }
 
 // ---- iago_alphabeta_moves_split: the roots' jobs counted, summed and written, (searched: alphabeta_jobs_kernel,) and
@@ -632,6 +432,7 @@ __global__ __launch_bounds__(256) void random_moves_kernel(const uint64_t *own, 
 
 extern "C" int iago_alphabeta_moves(const iago_alphabeta_args *a, void *stream)
 {
+    const char *who = "iago_alphabeta_moves";
     if (!a)
         return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: null args");
     if (a->n < 0 || (a->n > 0 && (!a->own || !a->opp || !a->score || !a->move || !a->nodes || !a->done)) || !a->ctl)
@@ -644,19 +445,10 @@ extern "C" int iago_alphabeta_moves(const iago_alphabeta_args *a, void *stream)
         if (a->reserved[i] != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: reserved fields must be 0");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(a->ctl, 0, 4 * sizeof(uint32_t), s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves: clearing ctl");
-    }
-    if (a->n == 0)
-        return IAGO_OK;
-    if (hipMemsetAsync(a->done, 0, (size_t)a->n, s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves: clearing done");
-    }
-    const int cus = iago_device_cus();
-    if (cus <= 0)
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves: no HIP device");
+    int cus = 0;
+    const int rc = iago_search_prepare(who, a->ctl, 4, a->done, "done", a->n, s, &cus);
+    if (rc != IAGO_OK || cus == 0)
+        return rc;
 
     AlphaBetaParams P;
     P.own = a->own;
@@ -670,19 +462,8 @@ extern "C" int iago_alphabeta_moves(const iago_alphabeta_args *a, void *stream)
     P.depth = a->depth;
     P.levels = a->depth; // a frame is pushed by a node with >= 2 levels below it: levels 0 .. depth - 2
     P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
-    const int lds = P.levels * WAVE * FRAME_BYTES;
-    // every workgroup resident at once (the give-up is per wave's own clock): at most what the CUs hold
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alphabeta_kernel, WAVE, lds) != hipSuccess ||
-        per_cu <= 0) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    const int64_t want = (a->n + WAVE - 1) / WAVE;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    hipLaunchKernelGGL(alphabeta_kernel, dim3(grid), dim3(WAVE), lds, s, P);
-    return iago_check_launch("iago_alphabeta_moves");
+    iago_search_launch((const void *)alphabeta_kernel, &P, P.levels, Stack<YardstickRules>::FRAME_BYTES, a->n, cus, s);
+    return iago_check_launch(who);
 }
 
 extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, void *stream)
@@ -715,19 +496,11 @@ extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, vo
         if (a->reserved[i] != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: reserved fields must be 0");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(a->ctl, 0, IAGO_ALPHABETA_SPLIT_CTL_WORDS * sizeof(uint32_t), s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: clearing ctl");
-    }
-    if (a->n == 0)
-        return IAGO_OK;
-    if (!count_only && hipMemsetAsync(a->done, 0, (size_t)a->n, s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: clearing done");
-    }
-    const int cus = iago_device_cus();
-    if (cus <= 0)
-        return iago_fail(IAGO_ERR_HIP, "iago_alphabeta_moves_split: no HIP device");
+    int cus = 0;
+    const int rc = iago_search_prepare(who, a->ctl, IAGO_ALPHABETA_SPLIT_CTL_WORDS, count_only ? nullptr : a->done,
+                                       "done", a->n, s, &cus);
+    if (rc != IAGO_OK || cus == 0)
+        return rc;
 
     // 1. expand: count, sum, write
     SplitParams E;
@@ -765,18 +538,8 @@ extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, vo
     J.ctl = a->ctl;
     J.levels = a->depth; // the deepest job is a root that must pass: the launch's depth
     J.clock_limit = (long long)a->time_limit_ms * 100000ll;
-    const int lds = J.levels * WAVE * FRAME_BYTES;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alphabeta_jobs_kernel, WAVE, lds) != hipSuccess ||
-        per_cu <= 0) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    const int64_t want = (a->job_capacity + WAVE - 1) / WAVE;
-    const int64_t cap = (int64_t)cus * per_cu;
-    const unsigned grid = (unsigned)(want < cap ? want : cap);
-    if (grid > 0)
-        hipLaunchKernelGGL(alphabeta_jobs_kernel, dim3(grid), dim3(WAVE), lds, s, J);
+    iago_search_launch((const void *)alphabeta_jobs_kernel, &J, J.levels, Stack<YardstickRules>::FRAME_BYTES,
+                       a->job_capacity, cus, s);
 
     // 3. reduce
     ReduceParams R;

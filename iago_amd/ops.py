@@ -1015,22 +1015,29 @@ ENDGAME_MODES = {"exact": _lib.ENDGAME_EXACT, "wld": _lib.ENDGAME_WLD}
 ENDGAME_TIME_LIMIT_MS = 60000
 
 
+def _check_search_ctl(who, out, ctl, overflow, gave_up, refused, first=None, **attrs):
+    """Raise IagoError (the result as its `result` attribute, attrs as further ones) unless a lane-search launch
+    finished everything.  ctl: its words on the host.  The caller's phrases: `first` (a fault of its own, before the
+    others), overflow, gave_up (a callable: it reads a tensor back), refused (with a %d for the count)."""
+    g, _, r, o = (int(v) for v in ctl[:4])
+    if not (first or g or r or o):
+        return
+    err = _lib.IagoError("%s: %s" % (who, first or (overflow if o else gave_up() if g else refused % r)))
+    err.result = out
+    for k, v in attrs.items():
+        setattr(err, k, v)
+    raise err
+
+
 def _check_endgame_ctl(out, n, max_empties, time_limit_ms):
     """Raise IagoError (with the result as its `result` attribute) unless the launch finished every position."""
-    gave_up, _, refused, overflow = (int(v) for v in out["ctl"].tolist())
-    if not (gave_up or refused or overflow):
-        return
-    if overflow:
-        what = ("a position needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped "
-                "with solved = 0 and its outputs unwritten" % max_empties)
-    elif gave_up:
-        what = "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
-            time_limit_ms, n - int(out["solved"].sum().item()), n)
-    else:
-        what = "%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % (refused, max_empties)
-    err = _lib.IagoError("iago_solve_endgame: " + what)
-    err.result = out
-    raise err
+    _check_search_ctl(
+        "iago_solve_endgame", out, out["ctl"].tolist(),
+        "a position needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped "
+        "with solved = 0 and its outputs unwritten" % max_empties,
+        lambda: "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
+            time_limit_ms, n - int(out["solved"].sum().item()), n),
+        "%%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % max_empties)
 
 
 def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS,
@@ -1152,6 +1159,9 @@ def alphabeta_split_arg(split, depth):
     return int(split)
 
 
+_ALPHABETA_GAVE_UP = "gave up at its clock limit (%d ms): %d of %d positions unfinished"
+
+
 def alphabeta_job_count(ctl):
     """The jobs a split launch needed, from the host values of its ctl words."""
     return (int(ctl[4]) & 0xFFFFFFFF) | ((int(ctl[5]) & 0xFFFFFFFF) << 32)
@@ -1191,22 +1201,12 @@ def _alphabeta_moves_split(own, opp, n, depth, split, time_limit_ms, job_capacit
     if check_result:
         ctl = out["ctl"].tolist()
         out["jobs"] = alphabeta_job_count(ctl)
-        gave_up, _, refused, overflow = (int(v) for v in ctl[:4])
-        if ctl[6] or gave_up or refused or overflow:
-            if ctl[6]:
-                what = "the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap)
-            elif overflow:
-                what = "a job needed more stack frames than depth = %d sizes (ctl[3] set)" % depth
-            elif gave_up:
-                what = "gave up at its clock limit (%d ms): %d of %d positions unfinished" % (
-                    time_limit_ms, n - int(out["done"].sum().item()), n)
-            else:
-                what = "%d positions refused (own & opp != 0)" % refused
-            err = _lib.IagoError("iago_alphabeta_moves_split: " + what)
-            err.result = out
-            if ctl[6]:
-                err.jobs_needed = out["jobs"]
-            raise err
+        short = dict(first="the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap),
+                     jobs_needed=out["jobs"]) if ctl[6] else {}
+        _check_search_ctl("iago_alphabeta_moves_split", out, ctl,
+                          "a job needed more stack frames than depth = %d sizes (ctl[3] set)" % depth,
+                          lambda: _ALPHABETA_GAVE_UP % (time_limit_ms, n - int(out["done"].sum().item()), n),
+                          "%d positions refused (own & opp != 0)", **short)
     return out
 
 
@@ -1252,18 +1252,10 @@ def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_
     a.ctl = _dev(out["ctl"], torch.int32, "ctl")
     check(_lib.lib().iago_alphabeta_moves(C.byref(a), _stream()), "iago_alphabeta_moves")
     if check_result:
-        gave_up, _, refused, overflow = (int(v) for v in out["ctl"].tolist())
-        if gave_up or refused or overflow:
-            if overflow:
-                what = "a position needed more stack frames than depth = %d sizes (ctl[3] set)" % depth
-            elif gave_up:
-                what = "gave up at its clock limit (%d ms): %d of %d positions unfinished" % (
-                    time_limit_ms, n - int(out["done"].sum().item()), n)
-            else:
-                what = "%d positions refused (own & opp != 0)" % refused
-            err = _lib.IagoError("iago_alphabeta_moves: " + what)
-            err.result = out
-            raise err
+        _check_search_ctl("iago_alphabeta_moves", out, out["ctl"].tolist(),
+                          "a position needed more stack frames than depth = %d sizes (ctl[3] set)" % depth,
+                          lambda: _ALPHABETA_GAVE_UP % (time_limit_ms, n - int(out["done"].sum().item()), n),
+                          "%d positions refused (own & opp != 0)")
     return out
 
 
