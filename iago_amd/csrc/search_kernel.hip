@@ -122,8 +122,8 @@ struct SearchParams {
     // games that start from one position keep meeting each other's positions (9.5 % of the value requests of 1024 games
     // x 100 playouts repeat a position asked for before: LABNOTES.md).  Direct-mapped, 32-byte entries {seq, own, opp,
     // value bits} under a per-entry sequence lock, every word an agent-scope atomic
-    u64 *vtable;
-    uint32_t vtable_mask;  // slots - 1 (slots a power of two), 0 = no table
+    u64 *vtable;           // nullptr = no table
+    uint32_t vtable_mask;  // slots - 1 (slots a power of two; 0: ONE slot, every position's -- never the sign of "no table")
     int64_t *trace;        // optional diagnostic [trace_rows][4]: game workgroup 0 samples (ticks, tail, head, finished) per iteration
     int32_t trace_rows;
     int32_t policy_xcds;   // XCDs (of 8) whose workgroups serve the POLICY ring first
@@ -771,7 +771,7 @@ __device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I,
     const float c = __uint_as_float(C.vbits);
     C.leaf_fresh = I.need_v && c != c;
     bool ask = C.leaf_fresh;
-    if (S.vtable_mask) {
+    if (S.vtable) {
         // has any game of any launch asked for this position before?
         uint32_t hit = 0u, bits = 0u, by = 0u;
         if (C.leaf_fresh && I.r == 0u && vtable_get(S, C.own, C.opp, bits, by)) {
@@ -1187,7 +1187,7 @@ __device__ __forceinline__ bool iteration_end(const SearchParams &S, const Slot 
         int limit = 0x7fffffff;
         sh.pace[3] = 0;
         const int32_t wait0 = (int32_t)(c.t0 - c.h0), wait1 = (int32_t)(c.t1 - c.h1);
-        if (S.ahead_idle >= 0 && S.vtable_mask && I.n_slots <= (int64_t)(QCAP / 2u) && c.idle >= (uint32_t)S.ahead_idle &&
+        if (S.ahead_idle >= 0 && S.vtable && I.n_slots <= (int64_t)(QCAP / 2u) && c.idle >= (uint32_t)S.ahead_idle &&
             wait0 <= 0 && wait1 <= 0)
             // this iteration's share of the ring for requests nobody waits for: the games' own requests (at most one
             // each) and TWO iterations' worth of these (the workgroups look at the rings at different moments: a second
@@ -1594,7 +1594,7 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
                 const uint32_t bits = __float_as_uint(res_v[tid]);
                 if ((job[6 * tid] & 0x7FFFFFFFu) != NOBODY)
                     st(&S.rep_v[(int64_t)(job[6 * tid] & 0x7FFFFFFFu)], ((u64)job[6 * tid + 1] << 32) | bits);
-                if (S.vtable_mask) {
+                if (S.vtable) {
                     const uint32_t asked = job[6 * tid] & 0x7FFFFFFFu;
                     put_e = vtable_put_begin(S, ((uint64_t)job[6 * tid + 3] << 32) | job[6 * tid + 2],
                                              ((uint64_t)job[6 * tid + 5] << 32) | job[6 * tid + 4], bits,

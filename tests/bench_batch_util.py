@@ -13,6 +13,7 @@ import torch
 
 from oracle import mcts_py
 from oracle import oracle as orc
+from tests import table_util
 
 
 def make_nets():
@@ -179,31 +180,11 @@ def audit_table(B, n_walk, n_games=None):
     """(iii): the position table after the batch; every entry's writer is one of the batch's n_games games (default:
     the records' game count)."""
     n_games = B["valid"].shape[1] if n_games is None else n_games
-    tab = B["table"]
-    seq, own, opp, val = tab[:, 0], tab[:, 1], tab[:, 2], tab[:, 3]
-    used = np.nonzero(seq)[0]
-    assert len(used) > 1000
-    assert not np.any(seq[used] & np.uint64(1)), "an entry was left with an odd sequence word"
-    assert np.array_equal(val[used] >> np.uint64(32), seq[used] & np.uint64(0xFFFFFFFF)), "value word / sequence word mismatch"
-    writer = (seq[used] >> np.uint64(32)).astype(np.int64)
-    assert writer.min() >= 0 and writer.max() < n_games        # the game that asked (or walked ahead)
-    assert not np.any(own[used] & opp[used])                     # positions: disjoint stones, the centre occupied
-    rs = np.random.RandomState(5)
-    pick = used if len(used) <= n_walk else rs.choice(used, n_walk, replace=False)
-    ops, value = B["ops"], B["value"]
-    o, p = ops.bits_to_tensor(own[pick]), ops.bits_to_tensor(opp[pick])
-    idx = torch.arange(len(pick), dtype=torch.int64, device="cuda")
-    one = torch.ones(1, dtype=torch.int32, device="cuda")
-    out = torch.full((len(pick),), float("nan"), dtype=torch.float32, device="cuda")
-    with torch.no_grad():
-        for i in range(len(pick)):      # ONE board per launch: the one-board walk (value to out[index[0]])
-            value.forward_boards_counted(o, p, idx[i:i + 1], one, out)
-    got = out.cpu().numpy().view(np.uint32)
-    want = (val[pick] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    bad = np.nonzero(got != want)[0]
-    assert len(bad) == 0, "%d of %d table values differ from the one-board walk (first: slot %d)" % (
-        len(bad), len(pick), int(pick[bad[0]]))
-    return len(used), len(pick)
+    # (tests/table_util.py: no odd sequence word, value word and sequence word agree, the writers, disjoint stones, every
+    # entry in the slot a lookup reads, and n_walk sampled entries against the one-board walk, ONE board per launch)
+    n_used, n_walked = table_util.audit(B["table"], B["value"], n_writers=n_games, n_walk=n_walk)
+    assert n_used > 1000
+    return n_used, n_walked
 
 
 def replay_match(s, g, n_sims, n_thr=15, on_turn=None):

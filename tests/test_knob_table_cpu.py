@@ -35,7 +35,7 @@ RESULT_KNOBS = {
     "IAGO_PERSISTENT_PAIR": "tests/test_knob_forms_gpu.py::test_setting_gives_the_default_results",
     "IAGO_PERSISTENT_POLICY_XCDS": "tests/test_knob_forms_gpu.py::test_setting_gives_the_default_results",
     "IAGO_PERSISTENT_AHEAD": "tests/test_search_persistent_gpu.py::test_values_ahead_on_idle_net_workgroups",
-    "IAGO_PERSISTENT_TABLE": "tests/test_search_wave_gpu.py::test_wave_trees_do_not_depend_on_nets_or_table",
+    "IAGO_PERSISTENT_TABLE": "tests/test_position_table_gpu.py::test_b_trees_do_not_depend_on_the_tables_size",
     "IAGO_PERSISTENT_CUS": "tests/test_search_persistent_gpu.py::test_grid_follows_the_device",         # max_cus=
 }
 

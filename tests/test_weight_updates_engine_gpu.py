@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import table_util
 from tests.conftest import GOLDEN, load_json
 from tests.gpu_util import delta, fresh, random_positions
 
@@ -109,22 +110,11 @@ def _equal(a, b):
 
 def audit_table(m, value):
     """Every entry of the position table holds, bit for bit, the current value net's value of its position (the
-    one-board walk: what a launch would take from it).  Returns the entries in use."""
-    tab = m._vtable.reshape(-1, 4)
-    used = torch.nonzero(tab[:, 0]).reshape(-1)
-    n = int(used.numel())
-    if n == 0:
-        return 0
-    own, opp = tab[used, 1].contiguous(), tab[used, 2].contiguous()
-    out = torch.full((n,), float("nan"), dtype=torch.float32, device="cuda")
-    with torch.no_grad():
-        value.forward_boards_counted(own, opp, torch.arange(n, device="cuda"),
-                                     torch.full((1,), n, dtype=torch.int32, device="cuda"), out)
-    want = (tab[used, 3] & 0xFFFFFFFF).to(torch.int32)
-    got = out.view(torch.int32)
-    bad = int((got != want).sum().item())
-    assert bad == 0, "%d of %d table entries hold a value of other weights" % (bad, n)
-    return n
+    one-board walk: what a launch would take from it), every entry in use walked -- and is a published entry of one of
+    the launch's writers in the slot a lookup reads (tests/table_util.py).  Returns the entries in use."""
+    n_used, n_walked = table_util.audit(m, value)
+    assert n_walked == n_used
+    return n_used
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
