@@ -48,13 +48,15 @@ EXPERIMENTAL_SYMBOLS = [
     "iago_mcts_expand_cached", "iago_mcts_fresh_leaves",
 ]
 # include/iago_hip_serving.h: searching ONE position fast -- W playouts of a tree in flight (engine.BatchedMCTS(wave=W)),
-# the exact endgame solver (ops.solve_endgame, engine.solve_endgame), exploring self-play (SelfPlayEngine.play(explore_turns=)),
+# the exact endgame solver (ops.solve_endgame, engine.solve_endgame; every optimal move and every move's value:
+# ops.solve_endgame_moves, engine.endgame_errors, SelfPlayEngine.play(solved_targets=True)), exploring self-play (SelfPlayEngine.play(explore_turns=)),
 # playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=)), forced
 # playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=)), the fixed-depth alpha-beta opponent and its
 # random openings (ops.alphabeta_moves, ops.random_moves; SelfPlayEngine.play_match(opponent=AlphaBeta(d))), that
 # search with every root spread over the lanes (ops.alphabeta_moves(split=), AlphaBeta(d, split))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
+    "iago_solve_endgame_moves", "iago_play_endgame_moves",
     "iago_mcts_search_explore", "iago_mcts_draw_move", "iago_mcts_search_arena",
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
     "iago_mcts_root_noise", "iago_mcts_search_noise",
@@ -305,6 +307,26 @@ class PlayEndgameArgs(C.Structure):
     ]
 
 
+ENDGAME_MOVES_BEST = 0     # IAGO_ENDGAME_MOVES_BEST
+ENDGAME_MOVES_ALL = 1      # IAGO_ENDGAME_MOVES_ALL
+ENDGAME_NO_MOVE = -128     # IAGO_ENDGAME_NO_MOVE
+
+
+class EndgameMovesArgs(C.Structure):
+    """Mirror of iago_endgame_moves_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("n", C.c_int64),
+        ("mode", C.c_int32), ("moves", C.c_int32), ("max_empties", C.c_int32), ("time_limit_ms", C.c_int32),
+        ("score", C.c_void_p), ("move", C.c_void_p), ("nodes", C.c_void_p), ("solved", C.c_void_p),
+        ("best", C.c_void_p), ("move_score", C.c_void_p), ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
+class PlayEndgameMovesArgs(C.Structure):
+    """Mirror of iago_play_endgame_moves_args (include/iago_hip_serving.h)."""
+    _fields_ = [("play", PlayEndgameArgs), ("rec_best", C.c_void_p), ("reserved", C.c_int64 * 4)]
+
+
 ALPHABETA_MAX_DEPTH = 10   # IAGO_ALPHABETA_MAX_DEPTH
 
 
@@ -507,6 +529,8 @@ def lib():
     L.iago_selfplay_policy.argtypes = [C.POINTER(SelfplayPolicyArgs), vp]
     L.iago_solve_endgame.argtypes = [C.POINTER(EndgameArgs), vp]
     L.iago_play_endgame.argtypes = [C.POINTER(PlayEndgameArgs), vp]
+    L.iago_solve_endgame_moves.argtypes = [C.POINTER(EndgameMovesArgs), vp]
+    L.iago_play_endgame_moves.argtypes = [C.POINTER(PlayEndgameMovesArgs), vp]
     L.iago_mcts_search_park.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchParkArgs), vp]
     L.iago_mcts_search_explore.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchExploreArgs), vp]
     L.iago_mcts_draw_move.argtypes = [tp, vp, C.c_uint64, vp, vp, vp, vp, vp]

@@ -55,6 +55,7 @@ __device__ __forceinline__ int eval_value(uint64_t own, uint64_t opp, uint64_t l
 }
 
 struct YardstickRules {
+    static constexpr RootRule ROOT = LOWEST;
     using Info = uint64_t;
     static constexpr int NEG_INF = -32768;
     static constexpr bool COUNT_LAST = false;

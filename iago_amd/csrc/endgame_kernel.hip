@@ -25,8 +25,10 @@ namespace {
 
 constexpr int ORDER_EMPTIES = 6;  // nodes with more empties than this try their moves fastest first
 
-// The final disc difference (wld: its sign); scores are in [-64, 64].
-struct SolverRules {
+// The final disc difference (wld: its sign); scores are in [-64, 64].  ROOT_: the root's rule (lane_search.hpp).
+template <RootRule ROOT_>
+struct SolverRulesT {
+    static constexpr RootRule ROOT = ROOT_;
     using Info = uint32_t;
     static constexpr int NEG_INF = -100;
     static constexpr bool COUNT_LAST = true;
@@ -64,6 +66,8 @@ struct SolverRules {
         return (int)(info >> 25);
     }
 };
+
+using SolverRules = SolverRulesT<LOWEST>; // iago_solve_endgame, iago_play_endgame
 
 struct EndgameParams {
     const uint64_t *own;
@@ -109,6 +113,36 @@ __global__ __launch_bounds__(WAVE) void endgame_kernel(EndgameParams P)
     search_wave(P, SolverRules{P.wld}, P.n, 0, stack_lds);
 }
 
+// iago_solve_endgame_moves: the same launch on the root rules BEST and ALL, with the set of the optimal moves and (ALL)
+// the row of per-move values (filled with IAGO_ENDGAME_NO_MOVE before the launch: the search writes the legal moves)
+struct MovesParams : EndgameParams {
+    uint64_t *best;
+    int8_t *move_score;
+
+    __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &empties) const
+    {
+        if (EndgameParams::admit(pos, o, p, empties))
+            return true;
+        best[pos] = 0ull;
+        return false;
+    }
+
+    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
+    {
+        best[pos] = s.best_set;
+        EndgameParams::finish(pos, s);
+    }
+
+    __device__ __forceinline__ int8_t *row(int64_t pos) const { return move_score + 64 * pos; }
+};
+
+template <RootRule ROOT>
+__global__ __launch_bounds__(WAVE) void endgame_moves_kernel(MovesParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    search_wave(P, SolverRulesT<ROOT>{P.wld}, P.n, 0, stack_lds);
+}
+
 // ---- iago_play_endgame: whole games from a late position to their end, both sides solving every turn
 
 struct PlayParams {
@@ -129,12 +163,13 @@ struct PlayParams {
 // One LANE PER GAME, claimed from the counter: at every turn the mover's position is solved with search_step (EXACT) and
 // the move is played with the books of the persistent search's play_move (game.py:117-142,253-255): a stone per move, a
 // pass after a pass sets stones = 64, the end of the game is tested once per pair of turns.  TURN: at a turn's start.
-__global__ __launch_bounds__(WAVE) void play_endgame_kernel(PlayParams P)
+// Rules: SolverRules, or (iago_play_endgame_moves, P.rec_best) the root rule BEST: the same move, and the set it is of.
+template <class Rules, class Params>
+__device__ __forceinline__ void play_endgame_games(const Params &P, unsigned char *stack_lds)
 {
-    extern __shared__ __align__(16) unsigned char stack_lds[];
     const uint32_t lane = threadIdx.x;
-    const SolverRules R{0};
-    const Stack<SolverRules> K = make_stack<SolverRules>(stack_lds, P.levels);
+    const Rules R{0};
+    const Stack<Rules> K = make_stack<Rules>(stack_lds, P.levels);
     const ShiftAmounts SA = opaque_shift_amounts();
     const long long t0 = wall_clock64();
 
@@ -202,6 +237,8 @@ __global__ __launch_bounds__(WAVE) void play_endgame_kernel(PlayParams P)
             P.rec_valid[row] = moved ? 3 : 0;
             P.rec_move[row] = (int8_t)(moved ? s.root_move : -1);
             P.rec_score[row] = (int8_t)(moved ? s.v : 0);
+            if constexpr (Rules::ROOT != LOWEST)
+                P.rec_best[row] = moved ? s.best_set : 0ull;
             // the stone and the swap of sides
             const uint64_t f = moved ? flips_of(g_own, g_opp, (uint32_t)s.root_move) | (1ull << s.root_move) : 0ull;
             const uint64_t nown = g_opp & ~f;
@@ -231,8 +268,48 @@ __global__ __launch_bounds__(WAVE) void play_endgame_kernel(PlayParams P)
     }
 }
 
+__global__ __launch_bounds__(WAVE) void play_endgame_kernel(PlayParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    play_endgame_games<SolverRules>(P, stack_lds);
+}
+
+struct PlayMovesParams : PlayParams {
+    uint64_t *rec_best;
+};
+
+__global__ __launch_bounds__(WAVE) void play_endgame_moves_kernel(PlayMovesParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    play_endgame_games<SolverRulesT<BEST>>(P, stack_lds);
+}
+
 // a frame is pushed by a node with >= 2 empties: levels 0 .. max_empties - 2
 int stack_levels(int max_empties) { return max_empties > 2 ? max_empties - 1 : 1; }
+
+// the kernel's params from iago_play_endgame's arguments
+void fill_play_params(PlayParams &P, const iago_play_endgame_args *a)
+{
+    P.own = a->own;
+    P.opp = a->opp;
+    P.turn = a->turn;
+    P.stones = a->stones;
+    P.pass_flg = a->pass_flg;
+    P.parked = a->parked;
+    P.n = a->n;
+    P.stride = a->stride;
+    P.rec_own = a->rec_own;
+    P.rec_opp = a->rec_opp;
+    P.rec_valid = a->rec_valid;
+    P.rec_move = a->rec_move;
+    P.rec_score = a->rec_score;
+    P.finished = a->finished;
+    P.ctl = a->ctl;
+    P.max_turns = a->max_turns;
+    P.max_empties = a->max_empties;
+    P.levels = stack_levels(a->max_empties);
+    P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
+}
 
 } // namespace
 
@@ -303,25 +380,99 @@ extern "C" int iago_play_endgame(const iago_play_endgame_args *a, void *stream)
         return rc;
 
     PlayParams P;
+    fill_play_params(P, a);
+    iago_search_launch((const void *)play_endgame_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
+    return iago_check_launch(who);
+}
+
+extern "C" int iago_solve_endgame_moves(const iago_endgame_moves_args *a, void *stream)
+{
+    const char *who = "iago_solve_endgame_moves";
+    if (!a)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: null args");
+    if (a->n < 0 ||
+        (a->n > 0 && (!a->own || !a->opp || !a->score || !a->move || !a->nodes || !a->solved || !a->best)) || !a->ctl)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: null pointer or negative n");
+    if (a->mode != IAGO_ENDGAME_EXACT && a->mode != IAGO_ENDGAME_WLD)
+        return iago_fail(IAGO_ERR_INVALID,
+                         "iago_solve_endgame_moves: mode must be IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD");
+    if (a->moves != IAGO_ENDGAME_MOVES_BEST && a->moves != IAGO_ENDGAME_MOVES_ALL)
+        return iago_fail(IAGO_ERR_INVALID,
+                         "iago_solve_endgame_moves: moves must be IAGO_ENDGAME_MOVES_BEST or IAGO_ENDGAME_MOVES_ALL");
+    const bool all = a->moves == IAGO_ENDGAME_MOVES_ALL;
+    if (!all && a->move_score)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: move_score must be NULL under IAGO_ENDGAME_MOVES_BEST");
+    if (all && a->n > 0 && !a->move_score)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: move_score is required under IAGO_ENDGAME_MOVES_ALL");
+    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: max_empties must be in [0, 20]");
+    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: time_limit_ms must be in [1, 600000]");
+    for (int i = 0; i < 4; i++)
+        if (a->reserved[i] != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: reserved fields must be 0");
+    hipStream_t s = (hipStream_t)stream;
+    int cus = 0;
+    const int rc = iago_search_prepare(who, a->ctl, 4, a->solved, "solved", a->n, s, &cus);
+    if (rc != IAGO_OK || cus == 0)
+        return rc;
+    // every cell starts as "no move": the search writes the legal moves of the roots it admits
+    if (all && hipMemsetAsync(a->move_score, IAGO_ENDGAME_NO_MOVE & 0xFF, (size_t)a->n * 64, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame_moves: clearing move_score");
+    }
+
+    MovesParams P;
     P.own = a->own;
     P.opp = a->opp;
-    P.turn = a->turn;
-    P.stones = a->stones;
-    P.pass_flg = a->pass_flg;
-    P.parked = a->parked;
     P.n = a->n;
-    P.stride = a->stride;
-    P.rec_own = a->rec_own;
-    P.rec_opp = a->rec_opp;
-    P.rec_valid = a->rec_valid;
-    P.rec_move = a->rec_move;
-    P.rec_score = a->rec_score;
-    P.finished = a->finished;
+    P.score = a->score;
+    P.move = a->move;
+    P.nodes = a->nodes;
+    P.solved = a->solved;
     P.ctl = a->ctl;
-    P.max_turns = a->max_turns;
+    P.wld = a->mode == IAGO_ENDGAME_WLD;
     P.max_empties = a->max_empties;
     P.levels = stack_levels(a->max_empties);
     P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
-    iago_search_launch((const void *)play_endgame_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
+    P.best = a->best;
+    P.move_score = a->move_score;
+    const void *kernel = all ? (const void *)endgame_moves_kernel<ALL> : (const void *)endgame_moves_kernel<BEST>;
+    iago_search_launch(kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
+    return iago_check_launch(who);
+}
+
+extern "C" int iago_play_endgame_moves(const iago_play_endgame_moves_args *m, void *stream)
+{
+    const char *who = "iago_play_endgame_moves";
+    if (!m)
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: null args");
+    const iago_play_endgame_args *a = &m->play;
+    if (a->n < 0 || !a->ctl ||
+        (a->n > 0 && (!a->own || !a->opp || !a->turn || !a->stones || !a->pass_flg || !a->parked || !a->rec_own ||
+                      !a->rec_opp || !a->rec_valid || !a->rec_move || !a->rec_score || !a->finished || !m->rec_best)))
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: null pointer or negative n");
+    if (a->stride < a->n)
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: stride >= n expected");
+    if (a->max_turns < 1 || a->max_turns > IAGO_MAX_TURNS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: max_turns must be in [1, IAGO_MAX_TURNS]");
+    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: max_empties must be in [0, 20]");
+    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: time_limit_ms must be in [1, 600000]");
+    for (int i = 0; i < 4; i++)
+        if (a->reserved[i] != 0 || a->reserved0 != 0 || m->reserved[i] != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: reserved fields must be 0");
+    hipStream_t s = (hipStream_t)stream;
+    int cus = 0;
+    const int rc = iago_search_prepare(who, a->ctl, 4, a->finished, "finished", a->n, s, &cus);
+    if (rc != IAGO_OK || cus == 0)
+        return rc;
+
+    PlayMovesParams P;
+    fill_play_params(P, a);
+    P.rec_best = m->rec_best;
+    iago_search_launch((const void *)play_endgame_moves_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus,
+                       s);
     return iago_check_launch(who);
 }

@@ -10,9 +10,11 @@
 //   * one step of the loop is one node entered, one child's value taken back or one leaf valued; lanes that finish a
 //     position claim the next one from a counter in ctl, so a wave is not held back by its one deep position;
 //   * the root alone differs: every move that could tie the best value with a lower index is searched with a window
-//     that keeps that tie exact, so the root's move is the lowest-indexed move reaching the value, whatever the order;
+//     that keeps that tie exact, so the root's move is the lowest-indexed move reaching the value, whatever the order
+//     (the root rule LOWEST; BEST and ALL below also answer the SET of the moves reaching the value);
 //   * every lane reads the wall clock once per step: past the limit the launch gives up (ctl[0] = 1).
 // What a search is ON comes as a RULES struct (an object: it may carry launch state such as the solver's mode):
+//   ROOT                      the root's rule: LOWEST, BEST or ALL (RootRule below)
 //   Info                      the type of a frame's packed word (the frame is 24 B + sizeof(Info) per level and lane)
 //   NEG_INF, window()         below every value; the root's window is (-window(), window())
 //   COUNT_LAST                a node with one level left has one move and is counted directly: the move ends the game
@@ -36,6 +38,19 @@ constexpr int CTL_CLAIM = 1;
 constexpr int CTL_REFUSED = 2;
 constexpr int CTL_OVERFLOW = 3;
 
+// What the root (unless it passed: then it is a node like any other) answers besides its value.  The move order, the
+// window of the root and the first move's search are the same under all three.
+//   LOWEST  the lowest-indexed move reaching the value: a later move that could tie it with a lower index is searched
+//           with alpha = best - 1, one with a higher index with alpha = best (it must beat best);
+//   BEST    the set of the moves reaching the value (Search::best_set): every later move is searched with
+//           alpha = best - 1, whatever its index, so a value equal to best comes back exact (fail-soft) and joins the
+//           set, a higher one replaces it.  root_move is the set's lowest bit: LOWEST's move;
+//   ALL     every move's value: the root's alpha never rises, every move is searched with the root's full window and its
+//           value goes to Search::row[move] (one byte per move); best_set is the argmax, root_move its lowest bit.
+// A root with one level left under COUNT_LAST: its one move is the set and that move's value the root's.  A root that
+// passed or a finished game: the empty set, nothing written to row.
+enum RootRule : int { LOWEST = 0, BEST = 1, ALL = 2 };
+
 // (TURN: iago_play_endgame's own, at a turn's start)
 enum Phase : uint32_t { CLAIM = 0, ENTER = 1, NEXT = 2, RETURN = 3, DONE = 4, TURN = 5 };
 
@@ -48,6 +63,8 @@ struct Search {
     uint32_t passed;
     int root_move;
     int64_t nodes;
+    uint64_t best_set; // BEST, ALL: the root's moves reaching best (LOWEST never reads it: it costs those kernels nothing)
+    int8_t *row;       // ALL: where the root's per-move values go, set by whoever begins the search
 };
 
 // the wave's stack in LDS, [level][lane]
@@ -81,6 +98,7 @@ __device__ __forceinline__ void search_begin(Search &s, uint64_t own, uint64_t o
     s.beta = window;
     s.nodes = 0;
     s.root_move = -1;
+    s.best_set = 0ull;
     s.phase = ENTER;
 }
 
@@ -88,13 +106,27 @@ __device__ __forceinline__ void search_begin(Search &s, uint64_t own, uint64_t o
 __device__ __forceinline__ bool search_done(const Search &s) { return s.phase == RETURN && s.d == 0; }
 
 // the value v of the child reached by move m, back in its parent (the node in s)
+template <class Rules>
 __device__ __forceinline__ void take_back(Search &s, int m, int v)
 {
     if (s.d == 0 && !s.passed) {
-        // root: the lowest index among the moves of the best value (the window kept every tie exact)
-        if (v > s.best || (v == s.best && m < s.root_move)) {
-            s.best = v;
-            s.root_move = m;
+        if constexpr (Rules::ROOT == LOWEST) {
+            // root: the lowest index among the moves of the best value (the window kept every tie exact)
+            if (v > s.best || (v == s.best && m < s.root_move)) {
+                s.best = v;
+                s.root_move = m;
+            }
+        } else {
+            // root: the set of the moves of the best value (a value equal to best came back exact)
+            if constexpr (Rules::ROOT == ALL)
+                s.row[m] = (int8_t)v;
+            if (v > s.best) {
+                s.best = v;
+                s.best_set = 1ull << m;
+            } else if (v == s.best) {
+                s.best_set |= 1ull << m;
+            }
+            s.root_move = (int)lowest_bit(s.best_set);
         }
     } else {
         s.best = max(s.best, v);
@@ -159,8 +191,16 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
                 s.v = R.terminal(s.own | f | (1ull << m), s.opp & ~f);
                 if (s.passed)
                     s.v = -s.v;
-                if (s.d == 0)
+                if (s.d == 0) {
                     s.root_move = s.passed ? -1 : (int)m;
+                    if constexpr (Rules::ROOT != LOWEST) {
+                        if (!s.passed) {
+                            s.best_set = 1ull << m;
+                            if constexpr (Rules::ROOT == ALL)
+                                s.row[m] = (int8_t)s.v;
+                        }
+                    }
+                }
                 s.phase = RETURN;
             } else {
                 s.moves = legal;
@@ -178,7 +218,7 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
         s.opp = K.opp[k];
         s.moves = K.moves[k];
         const int m = Rules::unpack(K.info[k], s);
-        take_back(s, m, -s.v);
+        take_back<Rules>(s, m, -s.v);
         s.phase = NEXT;
     }
 
@@ -191,8 +231,13 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
         while (s.moves != 0ull) {
             m = R.pick_move(s.own, s.opp, s.moves, levels, SA);
             s.moves &= ~(1ull << m);
-            if (root && s.best > Rules::NEG_INF) // a tie of a lower index must come back exact, a higher one must beat best
-                a_child = max(s.alpha, (int)m < s.root_move ? s.best - 1 : s.best);
+            if constexpr (Rules::ROOT == LOWEST) {
+                if (root && s.best > Rules::NEG_INF) // a tie of a lower index must come back exact, a higher one must beat best
+                    a_child = max(s.alpha, (int)m < s.root_move ? s.best - 1 : s.best);
+            } else if constexpr (Rules::ROOT == BEST) {
+                if (root && s.best > Rules::NEG_INF) // every tie must come back exact
+                    a_child = max(s.alpha, s.best - 1);
+            }
             if (a_child < s.beta) {
                 go = true;
                 break;
@@ -204,7 +249,7 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
             if constexpr (Rules::LEAF_CHILDREN) {
                 if (levels <= 1) { // a child with no level left: a leaf, valued here without a frame
                     s.nodes++;
-                    take_back(s, (int)m, -R.leaf(cown, copp, SA));
+                    take_back<Rules>(s, (int)m, -R.leaf(cown, copp, SA));
                     return true;
                 }
             }
@@ -232,7 +277,8 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
 // The search of a wave, lane per position, over the indices below n.  P, the kernel's params: ctl, levels (stack frames
 // per lane), clock_limit (wall_clock64 ticks), and how an index becomes a search and an answer --
 //   admit(pos, own, opp, levels0) -> true: search (own, opp) with levels0 levels; false: refused (counted and answered)
-//   finish(pos, s): the outputs of the finished search s.
+//   finish(pos, s): the outputs of the finished search s;
+//   row(pos) (Rules::ROOT == ALL only): where the per-move values of the root go, 64 bytes.
 // levels0 comes in as the launch's own where every position has the same (admit leaves it), else as 0.
 template <class Rules, class Params>
 __device__ __forceinline__ void search_wave(const Params &P, const Rules &R, int64_t n, int levels0,
@@ -256,8 +302,11 @@ __device__ __forceinline__ void search_wave(const Params &P, const Rules &R, int
                 uint64_t own, opp;
                 if (pos >= n)
                     s.phase = DONE;
-                else if (P.admit(pos, own, opp, levels0))
+                else if (P.admit(pos, own, opp, levels0)) {
                     search_begin(s, own, opp, R.window());
+                    if constexpr (Rules::ROOT == ALL)
+                        s.row = P.row(pos);
+                }
             }
         }
         if (__builtin_amdgcn_ballot_w64(s.phase != DONE) == 0ull)

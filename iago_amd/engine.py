@@ -41,9 +41,10 @@ _stream = ops._stream   # the current HIP stream as a void*
 # The rules of a batch of games beyond plain PV-MCTS, validated once (_play_rules) and handed on as ONE value:
 # solve_empties (None: off, else an int in [0, 20]), explore_turns (an int, 0: off), playout_cap (None: off, else
 # (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)), forced_playouts (None: off, else k_256,
-# with root_noise) -- as SelfPlayEngine.play documents them.
-PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise forced_playouts",
-                                   defaults=(None, None))
+# with root_noise), solved_targets (False: off; True, with solve_empties: the solved turns record the set of their
+# optimal moves) -- as SelfPlayEngine.play documents them.
+PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise forced_playouts "
+                                   "solved_targets", defaults=(None, None, False))
 NO_RULES = PlayRules(None, 0, None)
 
 
@@ -1678,6 +1679,9 @@ class SelfPlayResult(object):
     # forced_playouts: (T, B, 64) int32 the RAW visit rows, where `pi` then holds the pruned ones (the same on every row
     # that was not forced); None without forced playouts
     pi_raw = None
+    # solved_targets: (T, B) int64 the set of the optimal moves of every solved row (bit a: move a reaches `score`), 0 on
+    # every other row; None without solved targets
+    best = None
 
     def tuples(self):
         """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view."""
@@ -1690,8 +1694,16 @@ class SelfPlayResult(object):
 
     def solved_tuples(self):
         """Flat rows of the moves the endgame solver played (valid == 3): own, opp, move, score (the exact final disc
-        difference from the mover's view), z (from the mover's view), colour, game, turn."""
-        return self._rows(3, False)
+        difference from the mover's view), z (from the mover's view), colour, game, turn.  Where the games recorded
+        solved targets (play(solved_targets=True)) also best, the set of the row's optimal moves (int64, bit a: move a
+        reaches the score; `move` is its lowest bit), and pi (rows, 64) int32 with 1 on every optimal move: the rows then
+        have every column ReplayWindow.add and ReinforceTrainer.step_from_tuples(..., target="visits") take."""
+        rows = self._rows(3, False)
+        if self.best is not None:
+            rows["best"] = self.best.reshape(-1)[self.valid.reshape(-1) == 3]
+            cells = torch.arange(64, device=rows["best"].device)
+            rows["pi"] = ((rows["best"].reshape(-1, 1) >> cells) & 1).to(torch.int32)
+        return rows
 
     def _rows(self, kind, searched):
         m = self.valid.reshape(-1) == kind
@@ -1780,13 +1792,19 @@ def _solve_empties_arg(k):
     return int(k)
 
 
-def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None, forced_playouts=None):
+def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None, forced_playouts=None,
+                solved_targets=False):
     """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
     where its own validator refuses it (forced_playouts: an int in [1, 4096], and only with root_noise).  Off is (None, 0,
-    None, None, None): explore_turns is an int in the record."""
+    None, None, None): explore_turns is an int in the record.  solved_targets: a bool, True only with solve_empties."""
     noise = ops.root_noise_arg(root_noise)
+    if not isinstance(solved_targets, bool):
+        raise ValueError("solved_targets must be a bool, not %r" % (solved_targets,))
+    if solved_targets and solve_empties is None:
+        raise ValueError("solved_targets records the solver's optimal moves: it needs solve_empties")
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
-                     ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise))
+                     ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise),
+                     solved_targets)
 
 
 def _no_forced_playouts(forced_playouts, who):
@@ -1904,7 +1922,8 @@ class SelfPlayEngine(object):
         all self-play; res: the result object to fill (default a SelfPlayResult).  None: a pool filled up.
         rules (a PlayRules): solve_empties = k: TWO launches -- the games hand over at their first turn of at most k
         empties (iago_mcts_search_park), then iago_play_endgame plays every game to its end under perfect play, into the
-        same records (valid 3, score), and the one readback follows both.  explore_turns > 0: the searched moves of the
+        same records (valid 3, score; with solved_targets iago_play_endgame_moves, and the record best), and the one
+        readback follows both.  explore_turns > 0: the searched moves of the
         turns below it are drawn from the visit counts, in the launch (iago_mcts_search_explore).  playout_cap =
         (n_fast, full_per_256): every searched turn is full or fast, in the launch (iago_mcts_search_cap).  (Games with
         root_noise do not come here: _one_launch.)"""
@@ -1915,6 +1934,8 @@ class SelfPlayEngine(object):
         rec = self._new_records(B)
         g = dict(max_turns=T, games_total=games_total, own=own, opp=opp, n_turns=torch.zeros(B, dtype=torch.int32, device=dev),
                  **{"rec_" + k: v for k, v in rec.items()})
+        if rules.solved_targets:   # (the play-out's own record: the search's launch does not see it)
+            rec["best"] = torch.zeros((T, B), dtype=torch.int64, device=dev)
         if active is None:
             active = torch.ones(self.B, dtype=torch.uint8, device=dev)
         m._forget_stale_values()
@@ -1930,8 +1951,9 @@ class SelfPlayEngine(object):
         if park is not None:
             # (own / opp / n_turns: a parked game's position and turn in, its final position and turn count out)
             out = ops.play_endgame(own, opp, g["n_turns"], park["stones"], park["pass_flg"], park["parked"], max_turns=T,
-                                   max_empties=solve_empties, records={k: rec[k] for k in ("own", "opp", "valid", "move", "score")},
-                                   check_result=False)
+                                   max_empties=solve_empties, records={k: rec[k] for k in ("own", "opp", "valid", "move", "score")
+                                                                       + (("best",) if rules.solved_targets else ())},
+                                   check_result=False, **({"best": True} if rules.solved_targets else {}))
         ctl = m._ps["ctl"]
         back = _read_back(dict(
             flags=m.error_flags(), no_children=ctl[4], turns=g["n_turns"].max(), full_rows=(rec["valid"] == 1).sum(),
@@ -1970,6 +1992,8 @@ class SelfPlayEngine(object):
             res.opp = torch.where(played, rec["opp"][:t], torch.where(tw, p2.reshape(1, B), p1.reshape(1, B)))
             res.valid, res.move, res.pi = rec["valid"][:t], rec["move"][:t], rec["pi"][:t]
             setattr(res, res.SCORE_RECORD, rec["score"][:t])
+            if rules.solved_targets:
+                res.best = rec["best"][:t]
         return res
 
     def _whole_games_in_one_launch(self, n_sims):
@@ -2029,7 +2053,8 @@ class SelfPlayEngine(object):
         res.launches is the sum of what it returns.  rules (a PlayRules): solve_empties = k: a game that would search at
         a position of at most k empties leaves the search mask; the solver (ops.solve_endgame, EXACT: one launch per turn
         for all such games) gives its move, recorded with valid 3 and the exact score, and its flags join the turn's
-        readback.  explore_turns: the searched moves of the turns below it are drawn from the visit counts
+        readback; with solved_targets ops.solve_endgame_moves(moves="best") instead, and the record best.
+        explore_turns: the searched moves of the turns below it are drawn from the visit counts
         (BatchedMCTS.draw_move) instead of best_move's.  playout_cap = (n_fast, full_per_256): the turn's full games
         (BatchedMCTS.cap_mask) search n_sims playouts, its fast ones n_fast, recorded with valid 4 (_search_sides).
         forced_playouts = k_256: the games the noised search forced (every searched one, under a cap the full ones) record
@@ -2050,6 +2075,8 @@ class SelfPlayEngine(object):
         rec = self._new_records(B) if record else None
         if record and rules.forced_playouts is not None:
             rec["pi_raw"] = torch.zeros_like(rec["pi"])
+        if record and rules.solved_targets:
+            rec["best"] = torch.zeros((T, B), dtype=torch.int64, device=dev)
         legal = ops.legal_moves(own, opp)
         active = (legal != 0).to(torch.uint8)
         legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
@@ -2114,8 +2141,12 @@ class SelfPlayEngine(object):
                 s.move, s.visits = s.mcts.draw_move(t, s.act) if t < rules.explore_turns else s.mcts.best_move(s.act)
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
-                ex = ops.solve_endgame(torch.where(sol, own, full_board), torch.where(sol, opp, no_board), mode="exact",
-                                       max_empties=k, check_result=False)
+                if rules.solved_targets:   # (the same score and move, and the set of the optimal moves)
+                    ex = ops.solve_endgame_moves(torch.where(sol, own, full_board), torch.where(sol, opp, no_board),
+                                                 mode="exact", moves="best", max_empties=k, check_result=False)
+                else:
+                    ex = ops.solve_endgame(torch.where(sol, own, full_board), torch.where(sol, opp, no_board), mode="exact",
+                                           max_empties=k, check_result=False)
             mv = none
             ab = ab_over = None
             if policy_moves and opening is None:
@@ -2169,6 +2200,8 @@ class SelfPlayEngine(object):
                 if sol is not None:
                     valid = valid + 3 * sol.to(torch.uint8)
                     rec["score"][t] = torch.where(sol, ex["score"], torch.zeros_like(ex["score"]))
+                    if rules.solved_targets:
+                        rec["best"][t] = torch.where(sol, ex["best"], torch.zeros_like(ex["best"]))
                 rec["own"][t], rec["opp"][t], rec["valid"][t], rec["move"][t], rec["pi"][t] = own, opp, valid, mv, pi
             # game.py:84,108,140: the games not yet done -- less, in a match, the forced moves (game.py:107,113)
             live = ((done == 0) & ~forced).to(torch.uint8) if policy_moves else done ^ 1
@@ -2219,7 +2252,7 @@ class SelfPlayEngine(object):
         return res
 
     def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None,
-             root_noise=None, forced_playouts=None):
+             root_noise=None, forced_playouts=None, solved_targets=False):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -2264,9 +2297,16 @@ class SelfPlayEngine(object):
         child left with one visit gives that back too.  The move is chosen from the RAW counts as ever; `pi` records the
         PRUNED row and the new record `pi_raw` the raw one (tuples() hand the trainer the pruned targets).  Under
         playout_cap only the FULL turns are forced and pruned: a fast row's pi is its raw row.  Without forced playouts
-        the result's pi_raw is None."""
+        the result's pi_raw is None.
+        solved_targets = True (False, the default: off; only with solve_empties, else ValueError): every solved turn also
+        records the SET of its optimal moves in `best` ((T, B) int64: bit a set iff move a reaches the turn's exact
+        score; 0 on every row that is not solved) -- the turn loop through ops.solve_endgame_moves(moves="best"), the
+        play-out launch through iago_play_endgame_moves: the same records, and every other record as without it.
+        solved_tuples() then carries best and a 0 / 1 `pi`, a noise-free policy target for the plies the search never
+        sees.  Without it the result's best is None."""
         return self._play(n_sims, handicap, record,
-                          _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts))
+                          _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts,
+                                      solved_targets))
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
@@ -2279,7 +2319,7 @@ class SelfPlayEngine(object):
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
-                    playout_cap=None, root_noise=None, forced_playouts=None):
+                    playout_cap=None, root_noise=None, forced_playouts=None, solved_targets=False):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -2292,8 +2332,8 @@ class SelfPlayEngine(object):
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
         turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id.
-        forced_playouts: as in play(), with the record pi_raw."""
-        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts)
+        forced_playouts: as in play(), with the record pi_raw.  solved_targets: as in play(), with the record best."""
+        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts, solved_targets)
         m, T = self.mcts, self.max_turns
         m._backup_check()
         m._root_noise_arg(rules.root_noise)
@@ -2399,6 +2439,8 @@ class SelfPlayEngine(object):
             cols = {k: [] for k in ("own", "opp", "valid", "move", "pi", "score")}
             if rules.forced_playouts is not None:
                 cols["pi_raw"] = []
+            if rules.solved_targets:
+                cols["best"] = []
             for r, w in parts:
                 dev, rows = r.z.device, min(r.n_turns, t)
                 pad = t - rows
@@ -2413,6 +2455,8 @@ class SelfPlayEngine(object):
                 cols["pi"].append(torch.cat([r.pi[:rows, :w], r.pi.new_zeros((pad, w, 64))]))
                 if "pi_raw" in cols:
                     cols["pi_raw"].append(torch.cat([r.pi_raw[:rows, :w], r.pi_raw.new_zeros((pad, w, 64))]))
+                if "best" in cols:
+                    cols["best"].append(torch.cat([r.best[:rows, :w], r.best.new_zeros((pad, w))]))
                 cols["score"].append(torch.cat([r.score[:rows, :w], r.score.new_zeros((pad, w))]))
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))
@@ -2669,3 +2713,43 @@ def solve_endgame(own, opp, mode="exact", split_depth=0, time_limit_ms=ops.ENDGA
     return dict(score=torch.from_numpy(val[0].astype(np.int8)).to(dev), move=torch.from_numpy(mov[0].astype(np.int8)).to(dev),
                 nodes=torch.from_numpy(cnt[0]).to(dev), solved=torch.ones(n, dtype=torch.uint8, device=dev),
                 ctl=res["ctl"])
+
+
+def endgame_errors(own, opp, move, max_empties=_lib.ENDGAME_MAX_EMPTIES, mode="exact", time_limit_ms=ops.ENDGAME_TIME_LIMIT_MS):
+    """The loss against perfect play of moves actually played: how many discs (mode "wld": outcomes) each move gives
+    away.  own / opp: (n,) int64 positions, own = the mover; move: (n,) integer tensor, the move played there.  Rows
+    with move < 0 (a pass, no turn) or more than max_empties empties are skipped and counted; the others are solved in
+    ONE launch of ops.solve_endgame_moves(moves="all"), which knows the exact value of every move.  Returns a dict: as
+    device tensors over the rows kept, in their order, index (their row numbers in the input), score (the position's
+    value), played (the value of the move played), loss = score - played (>= 0), optimal (loss == 0) and blunder (the
+    sign of the value changed: a win given away, or a draw turned into a loss); as Python numbers rows, skipped,
+    mean_loss, optimal_rate and blunder_rate (nan without rows).  A move that is not legal is a ValueError naming the
+    row; a position the solver refuses (own & opp != 0) raises ops.solve_endgame_moves' IagoError."""
+    n = own.numel()
+    if opp.numel() != n or move.numel() != n:
+        raise ValueError("endgame_errors: own / opp / move sizes differ")
+    k = _solve_empties_arg(max_empties)
+    if k is None:
+        raise ValueError("endgame_errors: max_empties must be an int in [0, %d]" % _lib.ENDGAME_MAX_EMPTIES)
+    own, opp, move = own.reshape(n), opp.reshape(n), move.reshape(n).to(torch.int64)
+    keep = (move >= 0) & (_empties(own, opp) <= k)
+    index = torch.nonzero(keep).reshape(-1)
+    r = ops.solve_endgame_moves(own[index].contiguous(), opp[index].contiguous(), mode=mode, moves="all", max_empties=k,
+                                time_limit_ms=time_limit_ms)
+    mv = move[index]
+    played = r["move_score"].to(torch.int32).gather(1, mv.clamp(max=63).reshape(-1, 1)).reshape(-1)
+    illegal = (played == _lib.ENDGAME_NO_MOVE) | (mv > 63)
+    score = r["score"].to(torch.int32)
+    loss = score - played
+    optimal, blunder = loss == 0, torch.sign(played) != torch.sign(score)
+    legal = ~illegal
+    rows = int(index.numel())
+    back = _read_back(dict(illegal=illegal.any(), first=index[illegal.to(torch.int64).argmax()] if rows else None,
+                           loss=(loss * legal).sum(), optimal=(optimal & legal).sum(), blunder=(blunder & legal).sum()))
+    if back["illegal"]:
+        i = back["first"]
+        raise ValueError("endgame_errors: row %d: move %d is not a legal move of the side to move" % (i, int(move[i].item())))
+    rate = (lambda v: v / rows) if rows else (lambda v: float("nan"))
+    return dict(index=index, score=score, played=played, loss=loss, optimal=optimal, blunder=blunder, rows=rows,
+                skipped=n - rows, mean_loss=rate(back["loss"]), optimal_rate=rate(back["optimal"]),
+                blunder_rate=rate(back["blunder"]))

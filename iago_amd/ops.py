@@ -1029,10 +1029,10 @@ def _check_search_ctl(who, out, ctl, overflow, gave_up, refused, first=None, **a
     raise err
 
 
-def _check_endgame_ctl(out, n, max_empties, time_limit_ms):
+def _check_endgame_ctl(out, n, max_empties, time_limit_ms, who="iago_solve_endgame"):
     """Raise IagoError (with the result as its `result` attribute) unless the launch finished every position."""
     _check_search_ctl(
-        "iago_solve_endgame", out, out["ctl"].tolist(),
+        who, out, out["ctl"].tolist(),
         "a position needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped "
         "with solved = 0 and its outputs unwritten" % max_empties,
         lambda: "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
@@ -1072,9 +1072,49 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     return out
 
 
+ENDGAME_MOVES = {"best": _lib.ENDGAME_MOVES_BEST, "all": _lib.ENDGAME_MOVES_ALL}
+
+
+def solve_endgame_moves(own, opp, mode="exact", moves="best", max_empties=_lib.ENDGAME_MAX_EMPTIES,
+                        time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True):
+    """solve_endgame with EVERY optimal move (iago_solve_endgame_moves, include/iago_hip_serving.h).
+
+    Returns solve_endgame's dict (score and move are its own, bit for bit) plus best (n,) int64: bit a set iff move a
+    reaches the score (0: the mover must pass, the game is over, the position was refused).  moves "best": the set
+    alone (about 1.1 x solve_endgame's nodes); "all": every legal move is searched with the full window, and
+    move_score (n, 64) int8 holds the value of move a from the mover's view, -128 (IAGO_ENDGAME_NO_MOVE) on every cell
+    that is no legal move of the mover (about 2.2 x the nodes).  check_result: as in solve_endgame."""
+    if mode not in ENDGAME_MODES:
+        raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
+    if moves not in ENDGAME_MOVES:
+        raise ValueError("moves must be 'best' or 'all', got %r" % (moves,))
+    n = own.numel()
+    if opp.numel() != n:
+        raise ValueError("own/opp sizes differ")
+    dev = own.device
+    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
+               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev),
+               best=torch.empty(n, dtype=torch.int64, device=dev))
+    a = _lib.EndgameMovesArgs()
+    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
+    a.mode, a.moves = ENDGAME_MODES[mode], ENDGAME_MOVES[moves]
+    a.max_empties, a.time_limit_ms = int(max_empties), int(time_limit_ms)
+    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
+    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
+    a.best, a.ctl = _dev(out["best"], torch.int64, "best"), _dev(out["ctl"], torch.int32, "ctl")
+    if moves == "all":
+        out["move_score"] = torch.empty((n, 64), dtype=torch.int8, device=dev)
+        a.move_score = _dev(out["move_score"], torch.int8, "move_score")
+    check(_lib.lib().iago_solve_endgame_moves(C.byref(a), _stream()), "iago_solve_endgame_moves")
+    if check_result:
+        _check_endgame_ctl(out, n, max_empties, time_limit_ms, who="iago_solve_endgame_moves")
+    return out
+
+
 def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_MAX_TURNS,
                  max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS, records=None,
-                 check_result=True):
+                 check_result=True, best=False):
     """The parked games of a batch to their end under perfect play (iago_play_endgame, include/iago_hip_serving.h):
     both sides play iago_solve_endgame's EXACT move at every turn, with the books of the whole-game search.
 
@@ -1084,7 +1124,10 @@ def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_M
     (max_turns, stride) tensors own, opp (int64), valid (uint8), move, score (int8) whose rows from each game's turn on
     are written.  Returns the dict of the records + finished (n,) uint8 and ctl (4,) int32.  check_result (one host
     sync): raise IagoError unless every parked game was played to its end (the clock limit, a game refused for
-    own & opp != 0, more than max_empties empties or a turn outside the records; the result is the error's `result`)."""
+    own & opp != 0, more than max_empties empties or a turn outside the records; the result is the error's `result`).
+    best=True (iago_play_endgame_moves): one more record, best (max_turns, stride) int64 -- the set of the moves reaching
+    the turn's score on every solved turn, 0 where valid is 0; records, when given, then holds it too.  Everything else
+    is the same, bit for bit."""
     n = own.numel()
     dev = own.device
     for name, t in (("opp", opp), ("turn", turn), ("stones", stones), ("pass_flg", pass_flg)):
@@ -1101,14 +1144,17 @@ def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_M
                        valid=torch.zeros((T, n), dtype=torch.uint8, device=dev),
                        move=torch.full((T, n), -1, dtype=torch.int8, device=dev),
                        score=torch.zeros((T, n), dtype=torch.int8, device=dev))
+        if best:
+            records["best"] = torch.zeros((T, n), dtype=torch.int64, device=dev)
     stride = records["own"].shape[1] if records["own"].dim() == 2 else n
-    for k in ("own", "opp", "valid", "move", "score"):
+    for k in ("own", "opp", "valid", "move", "score") + (("best",) if best else ()):
         if tuple(records[k].shape) != (T, stride):
             raise ValueError("records[%r] must be (max_turns, stride) = (%d, %d)" % (k, T, stride))
     out = dict(records)
     out["finished"] = torch.empty(n, dtype=torch.uint8, device=dev)
     out["ctl"] = torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev)
-    a = _lib.PlayEndgameArgs()
+    m = _lib.PlayEndgameMovesArgs()
+    a = m.play if best else _lib.PlayEndgameArgs()
     a.own, a.opp, a.turn = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), _dev(turn, torch.int32, "turn")
     a.stones, a.pass_flg = _dev(stones, torch.int32, "stones"), _dev(pass_flg, torch.uint8, "pass_flg")
     a.parked, a.n, a.stride = _dev(parked, torch.uint8, "parked"), n, stride
@@ -1117,7 +1163,11 @@ def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_M
     a.rec_valid, a.rec_move = _dev(out["valid"], torch.uint8, "records valid"), _dev(out["move"], torch.int8, "records move")
     a.rec_score = _dev(out["score"], torch.int8, "records score")
     a.finished, a.ctl = _dev(out["finished"], torch.uint8, "finished"), _dev(out["ctl"], torch.int32, "ctl")
-    check(_lib.lib().iago_play_endgame(C.byref(a), _stream()), "iago_play_endgame")
+    if best:
+        m.rec_best = _dev(out["best"], torch.int64, "records best")
+        check(_lib.lib().iago_play_endgame_moves(C.byref(m), _stream()), "iago_play_endgame_moves")
+    else:
+        check(_lib.lib().iago_play_endgame(C.byref(a), _stream()), "iago_play_endgame")
     if check_result:
         back = torch.cat([out["ctl"].to(torch.int64), (out["finished"] != parked).sum().reshape(1)]).tolist()
         check_play_endgame(back, out, max_empties, time_limit_ms)

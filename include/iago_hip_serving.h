@@ -167,6 +167,65 @@ typedef struct iago_play_endgame_args {
  */
 IAGO_API int iago_play_endgame(const iago_play_endgame_args *args, void *stream);
 
+#define IAGO_ENDGAME_MOVES_BEST 0  /* moves: the set of the optimal moves */
+#define IAGO_ENDGAME_MOVES_ALL 1   /* moves: that set and the value of every legal move */
+#define IAGO_ENDGAME_NO_MOVE (-128) /* move_score: the cell is no legal move of the mover */
+
+typedef struct iago_endgame_moves_args {
+    const uint64_t *own; /* [n] side to move (bit a = row*8+col) */
+    const uint64_t *opp; /* [n] its opponent */
+    int64_t n;
+    int32_t mode;          /* IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD */
+    int32_t moves;         /* IAGO_ENDGAME_MOVES_BEST or IAGO_ENDGAME_MOVES_ALL */
+    int32_t max_empties;   /* 0 .. IAGO_ENDGAME_MAX_EMPTIES: sizes the search stack */
+    int32_t time_limit_ms; /* 1 .. IAGO_ENDGAME_MAX_TIME_MS: the launch gives up after this long on the device clock */
+    int8_t *score;         /* [n] out */
+    int8_t *move;          /* [n] out: the lowest set bit of best[i]; -1: the mover must pass, -2: the game is over */
+    int64_t *nodes;        /* [n] out: nodes visited */
+    uint8_t *solved;       /* [n] out: 1 = the outputs of position i are exact */
+    uint64_t *best;        /* [n] out: bit a set iff move a reaches score[i] */
+    int8_t *move_score;    /* [n][64] out, ALL only (NULL under BEST): the value of move a from the mover's view */
+    uint32_t *ctl;         /* [IAGO_ENDGAME_CTL_WORDS] cleared by the call; [0] != 0: gave up, [2]: positions refused */
+    int64_t reserved[4];   /* 0 */
+} iago_endgame_moves_args;
+
+/*
+ * iago_solve_endgame with EVERY optimal move, and under ALL every move's value.  Same search, same move order, same
+ * rules of the game; score[i] and move[i] are iago_solve_endgame's, bit for bit, in both modes.  The root differs:
+ *   - BEST: after the first move every move of the root is searched with alpha = max(alpha, best - 1), whatever its
+ *     index, so every move that ties the best value comes back exact.  best[i] has bit a set iff move a reaches
+ *     score[i] (under WLD: reaches that outcome -- after a win is found the other moves are still searched, with the
+ *     window (0, 1)).  About 1.1 x the nodes of iago_solve_endgame in mode EXACT.
+ *   - ALL: the root's alpha never rises: every legal move is searched with the full window (-65, 65) (WLD: (-1, 1)),
+ *     move_score[i][a] is its exact value from the mover's view (WLD: its sign), IAGO_ENDGAME_NO_MOVE on every cell
+ *     that is no legal move of the mover; best[i] is the argmax.  nodes[i] is the root plus what each child's
+ *     full-window search visits.  About 2.2 x the nodes.
+ *   - a root that must pass is a node like any other: move -1, best 0, the whole row IAGO_ENDGAME_NO_MOVE; a finished
+ *     game: move -2, best 0, the whole row IAGO_ENDGAME_NO_MOVE; a root with one empty: its move is the set and that
+ *     move's value the score.
+ * A position with own & opp != 0 or with more than max_empties empties is refused: solved[i] = 0, best[i] = 0, its row
+ * IAGO_ENDGAME_NO_MOVE, ctl[2] counts it.  solved[], ctl and move_score are cleared on `stream` before the launch;
+ * score / move / nodes / best / move_score are meaningful where solved[i] = 1.  The clock (ctl[0]) and the stack
+ * overflow word (ctl[3]) are iago_solve_endgame's.  Host-side refusals (IAGO_ERR_INVALID, nothing launched): a null
+ * args / ctl, a null array with n > 0, n < 0, a mode or a `moves` outside the two, move_score given under BEST or
+ * missing under ALL, a max_empties or time_limit_ms out of range, reserved fields not 0.
+ */
+IAGO_API int iago_solve_endgame_moves(const iago_endgame_moves_args *args, void *stream);
+
+typedef struct iago_play_endgame_moves_args {
+    iago_play_endgame_args play; /* iago_play_endgame's arguments, read as it reads them */
+    uint64_t *rec_best;          /* [max_turns][stride] out: the BEST set of every solved turn, 0 where valid is 0 */
+    int64_t reserved[4];         /* 0 */
+} iago_play_endgame_moves_args;
+
+/*
+ * iago_play_endgame with one more record: every turn that writes its row also writes rec_best, the set of the moves
+ * that reach the turn's exact score (iago_solve_endgame_moves, EXACT, BEST), 0 on a pass or no turn.  The move played
+ * is the set's lowest bit: iago_play_endgame's move, so every other output equals iago_play_endgame's bit for bit.
+ * Refusals are iago_play_endgame's, and a null rec_best with n > 0.
+ */
+IAGO_API int iago_play_endgame_moves(const iago_play_endgame_moves_args *args, void *stream);
+
 typedef struct iago_search_park_args {
     int32_t park_empties;         /* 0 .. IAGO_ENDGAME_MAX_EMPTIES */
     int32_t reserved0;            /* 0 */

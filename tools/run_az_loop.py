@@ -20,9 +20,14 @@ playouts a move) against the fixed-depth alpha-beta opponent of depth yardstick_
 engine.AlphaBeta(d))), the one opponent that owes nothing to the nets, and the scores join the JSON line; 0 = off.
 selection = 1: the AlphaZero selection rule (engine.BatchedMCTS(selection="alphazero")) in self-play, on both sides of
 the gate and against the yardstick; 0, the default: the reference's rule.
+solve_empties = k > 0: self-play hands the last k empties to the exact endgame solver (SelfPlayEngine.play(solve_empties=k));
+0, the default: off.  solved_targets = 1 (with solve_empties > 0): the solved turns record the set of their optimal moves
+(play(solved_targets=True)) and solved_tuples() -- pi 1 on every optimal move -- joins the window beside tuples(); the
+JSON line says so and counts those rows.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
-                                 [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]"""
+                                 [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]
+                                 [solve_empties=0] [solved_targets=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +47,8 @@ forced_playouts = arg(12, 0) if arg(12, 0) > 0 else None
 backup = engine.backup_arg("negamax" if arg(13, 0) else "reference")
 yardstick_every, yardstick_depth = arg(14, 0), arg(15, 2)
 selection = engine.selection_arg("alphazero" if arg(16, 0) else "reference")
+solve_empties = arg(17, 0) if arg(17, 0) > 0 else None
+solved_targets = bool(arg(18, 0))
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -52,6 +59,7 @@ m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_t
 sp = engine.SelfPlayEngine(m)
 window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
 kls, vlosses = [], []
+solved_rows = [0]
 arena_scores = []
 if arena_every > 0:
     # the nets of k rounds ago: a frozen module pair of its own, an engine and tree pool of its own (other seed and ids)
@@ -96,8 +104,14 @@ def gate(i):
 def one():
     tr.model1.eval()
     vt.model.eval()
-    res = sp.play(sims, explore_turns=8, playout_cap=playout_cap, root_noise=root_noise, forced_playouts=forced_playouts)
+    extra = {} if solve_empties is None else dict(solve_empties=solve_empties, solved_targets=solved_targets)
+    res = sp.play(sims, explore_turns=8, playout_cap=playout_cap, root_noise=root_noise, forced_playouts=forced_playouts,
+                  **extra)
     added = tr.add_to_window(window, res.tuples())
+    if solved_targets:
+        n = tr.add_to_window(window, res.solved_tuples())
+        solved_rows[0] += n
+        added += n
     for _ in range(updates):
         s = window.sample(rows)
         loss = float(tr._update_visits(s["own"], s["opp"], s["pi"]).item())
@@ -110,6 +124,7 @@ for _ in range(2):
     one()
 torch.cuda.synchronize()
 first = len(kls)
+solved_rows[0] = 0   # (the two warm-up rounds are not counted)
 t0 = time.perf_counter()
 added = 0
 for i in range(iters):
@@ -134,6 +149,8 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
                   "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup, "selection": selection,
+                  "solve_empties": solve_empties, "solved_targets": solved_targets,
+                  **({"solved_rows_added": solved_rows[0]} if solved_targets else {}),
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {}),
                   **({"yardstick_every": yardstick_every, "yardstick_depth": yardstick_depth,
                       "yardstick": yardstick_scores} if yardstick_every > 0 else {})}))

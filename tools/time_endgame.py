@@ -2,14 +2,16 @@
 """Speed of the exact endgame solver (ops.solve_endgame / engine.solve_endgame, include/iago_hip_serving.h).
 
     python tools/time_endgame.py [--batch 4096] [--batch-empties 8,10,12,14,16] [--single-empties 12,14,16,18]
-                                 [--splits 0,1,2,3,4] [--reps 5] [--limit-ms 20000]
+                                 [--splits 0,1,2,3,4] [--reps 5] [--limit-ms 20000] [--moves best,all] [--out FILE]
 
 Positions: seeded SLPolicy-vs-SLPolicy games (rl_self_play.play_batch, the shipped sl_model.npz), the recorded
 positions of colour 1 at exactly E empties.  Prints one JSON line per measurement:
   * batch: `--batch` positions at E empties in one launch, both modes -- positions/s and nodes/s over HIP events;
   * single: one position at E empties through engine.solve_endgame(split_depth=k) -- the median wall time of `--reps`
     positions (host split and minimax included), its nodes.
-A launch that gives up at --limit-ms is reported as such."""
+  * --moves best,all: the batch measurement also through ops.solve_endgame_moves with each of the named root rules,
+    on the same positions (kind "batch_moves": its time and nodes, and both as ratios to the plain launch's).
+A launch that gives up at --limit-ms is reported as such.  --out FILE: the lines also go to FILE, as one JSON list."""
 import argparse
 import json
 import os
@@ -50,13 +52,23 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit-ms", type=int, default=20000)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--moves", default="")
+    ap.add_argument("--out", default="")
     args = ap.parse_args()
     from iago_amd import _lib, engine, network, ops
     policy = network.SLPolicy().load_npz(os.path.join(GOLDEN, "sl_model.npz")).cuda().eval()
     ints = lambda s: [int(x) for x in s.split(",") if x]   # noqa: E731
+    rules = [x for x in args.moves.split(",") if x]
+    lines = []
+
+    def emit(**row):
+        lines.append(dict(tool="time_endgame", **row))
+        print(json.dumps(lines[-1]), flush=True)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     w = positions_at(policy, 6, 64, args.seed)
     ops.solve_endgame(ops.bits_to_tensor(w[0]), ops.bits_to_tensor(w[1]))   # warm-up: code object, allocator
+    for rule in rules:
+        ops.solve_endgame_moves(ops.bits_to_tensor(w[0]), ops.bits_to_tensor(w[1]), moves=rule)
     for E in ints(args.batch_empties):
         o, p = positions_at(policy, E, args.batch, args.seed + 100 * E)
         to, tp = ops.bits_to_tensor(o), ops.bits_to_tensor(p)
@@ -69,10 +81,22 @@ def main():
             s = e0.elapsed_time(e1) / 1e3
             nodes = int(r["nodes"].sum().item())
             solved = int(r["solved"].sum().item())
-            print(json.dumps(dict(tool="time_endgame", kind="batch", empties=E, mode=mode, n=len(o), solved=solved,
-                                  gave_up=bool(r["ctl"][0].item()), s=round(s, 4),
-                                  positions_per_s=round(solved / s, 1), nodes=nodes, mnodes_per_s=round(nodes / s / 1e6, 2),
-                                  max_nodes=int(r["nodes"].max().item()))), flush=True)
+            emit(kind="batch", empties=E, mode=mode, n=len(o), solved=solved, gave_up=bool(r["ctl"][0].item()),
+                 s=round(s, 4), positions_per_s=round(solved / s, 1), nodes=nodes, mnodes_per_s=round(nodes / s / 1e6, 2),
+                 max_nodes=int(r["nodes"].max().item()))
+            for rule in rules:
+                torch.cuda.synchronize()
+                e0.record()
+                q = ops.solve_endgame_moves(to, tp, mode=mode, moves=rule, max_empties=E, time_limit_ms=args.limit_ms,
+                                            check_result=False)
+                e1.record()
+                torch.cuda.synchronize()
+                sq = e0.elapsed_time(e1) / 1e3
+                nq = int(q["nodes"].sum().item())
+                emit(kind="batch_moves", moves=rule, empties=E, mode=mode, n=len(o), solved=int(q["solved"].sum().item()),
+                     gave_up=bool(q["ctl"][0].item()), s=round(sq, 4), nodes=nq, mnodes_per_s=round(nq / sq / 1e6, 2),
+                     time_ratio=round(sq / s, 3), node_ratio=round(nq / nodes, 3),
+                     same_answer=bool((q["score"] == r["score"]).all().item() and (q["move"] == r["move"]).all().item()))
     for E in ints(args.single_empties):
         o, p = positions_at(policy, E, args.reps, args.seed + 1000 + E)
         for k in ints(args.splits):
@@ -89,10 +113,13 @@ def main():
                     break
                 times.append(time.perf_counter() - t0)
                 nodes.append(int(r["nodes"][0].item()))
-            print(json.dumps(dict(tool="time_endgame", kind="single", empties=E, split_depth=k, reps=len(times),
-                                  gave_up=gave_up, median_ms=round(1e3 * float(np.median(times)), 2) if times else None,
-                                  max_ms=round(1e3 * max(times), 2) if times else None,
-                                  median_nodes=int(np.median(nodes)) if nodes else None)), flush=True)
+            emit(kind="single", empties=E, split_depth=k, reps=len(times), gave_up=gave_up,
+                 median_ms=round(1e3 * float(np.median(times)), 2) if times else None,
+                 max_ms=round(1e3 * max(times), 2) if times else None,
+                 median_nodes=int(np.median(nodes)) if nodes else None)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("[\n" + ",\n".join(json.dumps(x, sort_keys=True) for x in lines) + "\n]\n")
 
 
 if __name__ == "__main__":
