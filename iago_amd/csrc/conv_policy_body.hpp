@@ -4,6 +4,7 @@
 // conv_policy_kernel.hip.
 #pragma once
 #include "abi_common.hpp"
+#include "search_request.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -64,8 +65,8 @@ __device__ __forceinline__ void split3(const f2 v, h2 &hi, h2 &mid, h2 &lo)
 
 extern __shared__ __align__(16) char policy_lds[];
 
-// pos / res / w1s: the persistent search's hand-offs through LDS (conv_trunk_body.hpp, Piece): the position (word 2 / 3 =
-// own lo / hi, 4 / 5 = opp lo / hi), the distribution [64] instead of P.probs, block1's weights staged already
+// pos / res / w1s: the persistent search's hand-offs through LDS (conv_trunk_body.hpp, Piece): the request (its position:
+// search_request.hpp), the distribution [64] instead of P.probs, block1's weights staged already
 // head_w (LDS): conv9's weights [128] and bias10 [64] staged there already
 // SRCH: the persistent search's form (all four given; a compile-time choice: conv_trunk_body.hpp, trunk_item)
 template <bool SRCH = false>
@@ -92,8 +93,8 @@ __device__ __forceinline__ void policy_item(const PolicyParams &P, const int64_t
             *(uint4 *)(T + e * 16) = src[e];
     } else {
         const int cell = tid & 63, y = cell >> 3, x = cell & 7;
-        const uint64_t bits0 = SRCH ? (((uint64_t)pos[5] << 32) | pos[4]) : P.opp[b];
-        const uint64_t bits1 = SRCH ? (((uint64_t)pos[3] << 32) | pos[2]) : P.own[b];
+        const uint64_t bits0 = SRCH ? iago_request::opp(pos) : P.opp[b];
+        const uint64_t bits1 = SRCH ? iago_request::own(pos) : P.own[b];
         float in[18];
 #pragma unroll
         for (int c = 0; c < 2; c++)

@@ -5,6 +5,7 @@
 #pragma once
 #include "abi_common.hpp"
 #include "rollout_row_body.hpp"
+#include "search_request.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -70,7 +71,7 @@ struct Piece {
     int layer_lo, layer_hi;
     // the persistent search's hand-offs inside the workgroup, through LDS instead of global memory (a store to global
     // memory read back by the same workgroup is a round trip to L2: ~2 us under load, twice per walk):
-    const uint32_t *pos; // optional, LDS: the boards' positions, six words per board (word 2 / 3 = own lo / hi, 4 / 5 = opp lo / hi)
+    const uint32_t *pos; // optional, LDS: the boards' requests, iago_request::WORDS words per board (search_request.hpp)
     float *res;          // optional, LDS: the walk's values [TB] instead of P.out
     const float *w1s;    // optional, LDS: block1's weights [64][18] and biases [64] staged there already
     const char *head_w;  // optional, LDS: the head's weights staged there already (HEAD_W_* below)
@@ -192,9 +193,9 @@ __device__ __forceinline__ void trunk_item(const TrunkRParams &P, const Piece &W
             const float *pl = P.planes + b * 128;
             uint64_t bits0, bits1;
             if constexpr (SRCH) {
-                const uint32_t *w = W.pos + 6 * board;
-                bits1 = ((uint64_t)w[3] << 32) | w[2];
-                bits0 = ((uint64_t)w[5] << 32) | w[4];
+                const uint32_t *w = W.pos + iago_request::WORDS * board;
+                bits1 = iago_request::own(w);
+                bits0 = iago_request::opp(w);
             } else {
                 bits0 = P.planes ? 0ull : P.opp[b];
                 bits1 = P.planes ? 0ull : P.own[b];

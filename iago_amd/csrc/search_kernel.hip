@@ -26,12 +26,13 @@
 // atomic loads -- the data is the flag, no fence, no cache invalidation that would cost the net
 // workgroups their L2-resident weights.  Ring entry t (ticket t, tag t + 1): 6 granules (kind | game,
 // reply tag, the position's four words); replies: one granule (value) or 64 (priors) tagged with the
-// request's reply tag.  The tree, the cursors and the paths of a game are touched by its own workgroup
+// request's reply tag (search_request.hpp states both layouts, for this file and the walks).  The tree, the cursors and the paths of a game are touched by its own workgroup
 // only.  Every wait is a bounded poll: the launch ends by itself when a clock limit passes (abort word).
 #include "mcts_dev.hpp"
 #include "conv_trunk_body.hpp" // (brings rollout_row_body.hpp)
 #include "conv_policy_body.hpp"
 #include "sample_dev.hpp"
+#include "search_request.hpp"
 #include "../../include/iago_hip_serving.h"
 
 #include <algorithm>
@@ -64,8 +65,11 @@ constexpr int CTL_PROGRESS = 5, CTL_PLAYING = 6;
 constexpr int CTL_NET_WGS = 7;            // net workgroups of this launch (written by the launch: the grid follows the device)
 constexpr int CTL_IDLE = 14;              // net workgroups that found nothing to do at their last look (they poll)
 constexpr int CTL_NEXT_GAME = 12;         // a stream: game ids claimed beyond the first fill (the next one: n_games + this)
-constexpr uint32_t NOBODY = 0x7FFFFFFFu;  // "game" of a request nobody waits for (its value goes to the position table only)
-constexpr uint32_t KIND_VALUE = 0u, KIND_POLICY = 1u;
+// a request's words, a ring's granules and a mailbox's: search_request.hpp (the walks read a request, too)
+namespace rq = iago_request;
+using rq::KIND_POLICY;
+using rq::KIND_VALUE;
+using rq::NOBODY;
 // games of a GAME workgroup: 8 lanes per game in the descent and the backup (16 games = two waves, 32 = all four),
 // rollouts in passes of 16 boards (the 16-lanes-per-board body)
 constexpr int GAMES_PER_WG = IAGO_SEARCH_GAMES_PER_WORKGROUP; // at most (the launch's own number: SearchParams::games_per_wg)
@@ -182,20 +186,101 @@ struct SearchParams {
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
 __device__ __forceinline__ void st(u64 *p, u64 x) { __hip_atomic_store(p, x, RLX_AGENT); }
 
-// one request: 6 granules of entry `t` (one lane)
+// ---- the request rings (one per kind of net work).  Game lanes write them (send_request), wave 0 of a net workgroup
+// reads them (ring_backlog, ring_take, ring_fetch).
+__device__ __forceinline__ u64 *ring_entry(const SearchParams &S, uint32_t q, uint32_t t)
+{
+    return S.q_slots + ((u64)q * QCAP + t % QCAP) * (u64)rq::SLOT_STRIDE;
+}
+
+// one request: the granules of entry `t` (one lane)
 __device__ __forceinline__ void send_request(const SearchParams &S, uint32_t kind, int64_t g, uint32_t reply_tag,
                                              uint64_t own, uint64_t opp)
 {
     const uint32_t t = __hip_atomic_fetch_add(&S.ctl[ctl_tail(kind)], 1u, RLX_AGENT);
-    u64 *e = S.q_slots + ((u64)kind * QCAP + t % QCAP) * 8u;
-    const u64 tag = (u64)(t + 1u) << 32;
-    st(e + 1, tag | reply_tag);
-    st(e + 2, tag | (uint32_t)own);
-    st(e + 3, tag | (uint32_t)(own >> 32));
-    st(e + 4, tag | (uint32_t)opp);
-    st(e + 5, tag | (uint32_t)(opp >> 32));
-    st(e + 0, tag | (kind << 31) | (uint32_t)g);
+    // (ring_entry written out: through the helper the game kernels are the same instructions in another allocation,
+    // 3 to 5 more spilled SGPRs: LABNOTES.md, "The net workgroup in named phases")
+    u64 *e = S.q_slots + ((u64)kind * QCAP + t % QCAP) * (u64)rq::SLOT_STRIDE;
+    st(e + rq::W_TAG, rq::entry_word(t, reply_tag));
+    st(e + rq::W_OWN_LO, rq::entry_word(t, (uint32_t)own));
+    st(e + rq::W_OWN_HI, rq::entry_word(t, (uint32_t)(own >> 32)));
+    st(e + rq::W_OPP_LO, rq::entry_word(t, (uint32_t)opp));
+    st(e + rq::W_OPP_HI, rq::entry_word(t, (uint32_t)(opp >> 32)));
+    st(e + rq::W_WHO, rq::entry_word(t, rq::who_word(kind, (uint32_t)g)));
     atomicAdd((unsigned long long *)&S.totals[(uint32_t)g == NOBODY ? 11 : kind], 1ull);
+}
+
+// (wave 0, uniform; lane 0 looks) the search is over -- every game workgroup has finished: no request can come any
+// more --, aborted, or past its clock
+__device__ __forceinline__ bool search_over(const SearchParams &S, const long long t0)
+{
+    bool out = false;
+    if (threadIdx.x == 0)
+        out = __hip_atomic_load(&S.ctl[CTL_FINISHED], RLX_AGENT) >= (uint32_t)S.n_game_wgs ||
+              __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u || wall_clock64() - t0 > S.clock_limit;
+    return __builtin_amdgcn_ballot_w64(out) != 0ull;
+}
+
+// Tickets are handed out by fetch-and-add whenever the ring shows an entry waiting: several workgroups that saw the
+// same entry all take one, and the later ones wait in ring_fetch for the ring's next entries.  (Measured and dropped,
+// round 5: head moved by compare-and-swap bounded by the tail, so that nobody is committed to an entry that does not
+// exist -- a retry loop took the 1024-game batch from 0.39 to 3.6 s, one attempt per look to 1.76 s: the losers keep
+// polling and retrying on ONE word from all XCDs, same-address atomics serialise, and every claim queues behind them.)
+// (wave 0, uniform; lane 0 looks) entries of ring q beyond the tickets handed out
+__device__ __forceinline__ int ring_backlog(const SearchParams &S, uint32_t q)
+{
+    int d = 0;
+    if (threadIdx.x == 0)
+        d = (int32_t)(__hip_atomic_load(&S.ctl[ctl_tail(q)], RLX_AGENT) - __hip_atomic_load(&S.ctl[ctl_head(q)], RLX_AGENT));
+    return __builtin_amdgcn_readfirstlane(d);
+}
+// (wave 0, uniform) the next ticket of ring q
+__device__ __forceinline__ uint32_t ring_take(const SearchParams &S, uint32_t q)
+{
+    uint32_t t = 0;
+    if (threadIdx.x == 0)
+        t = __hip_atomic_fetch_add(&S.ctl[ctl_head(q)], 1u, RLX_AGENT);
+    return __builtin_amdgcn_readfirstlane(t);
+}
+// wave 0: wait for entry t of ring q (at most max_spins polls; 0 = until it comes or the search is over)
+// -> dst[0 .. WORDS) (LDS); returns 0 = entry read, 1 = not there yet, 2 = the search is over / given up
+__device__ __forceinline__ int ring_fetch(const SearchParams &S, uint32_t q, uint32_t t, uint32_t max_spins, uint32_t *dst,
+                                          const long long t0)
+{
+    const int tid = threadIdx.x;
+    const u64 *e = ring_entry(S, q, t);
+    u64 x = 0;
+    int status = 0;
+    for (uint32_t spins = 0;; spins++) {
+        x = (tid < rq::WORDS) ? ld(e + tid) : 0ull;
+        const bool ok = tid >= rq::WORDS || rq::entry_is(x, t);
+        if (__builtin_amdgcn_ballot_w64(ok) == ~0ull)
+            break;
+        if (max_spins && spins + 1u >= max_spins) {
+            status = 1;
+            break;
+        }
+        if ((spins & 15u) == 15u && search_over(S, t0)) {
+            status = 2;
+            break;
+        }
+        __builtin_amdgcn_s_sleep(8);
+    }
+    if (status == 0 && tid < rq::WORDS)
+        dst[tid] = (uint32_t)x;
+    return status;
+}
+
+// the replies (one lane per granule): a value into the mailbox of the game that waits for it (nobody: into none);
+// word i of a distribution
+__device__ __forceinline__ void reply_value(const SearchParams &S, const uint32_t *r, uint32_t bits)
+{
+    if (rq::game(r) != NOBODY)
+        st(&S.rep_v[(int64_t)rq::game(r)], rq::reply_word(rq::tag(r), bits));
+}
+__device__ __forceinline__ void reply_prior(const SearchParams &S, const uint32_t *r, int i, uint32_t bits)
+{
+    st(&S.rep_p[(int64_t)rq::game(r) * 64 + i], rq::reply_word(rq::tag(r), bits));
 }
 
 __device__ __forceinline__ uint32_t vtable_slot(const SearchParams &S, uint64_t own, uint64_t opp)
@@ -270,18 +355,18 @@ __device__ __forceinline__ int policy_draw(const u64 *rep, uint64_t lg, double u
     double s = 0.0; // np.sum(prob * valid)
 #pragma unroll 1
     for (int j = 0; j < 64; j++)
-        s += ((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0;
+        s += ((lg >> j) & 1ull) ? (double)__uint_as_float(rq::reply_bits(ld(rep + j))) : 0.0;
     double last = 0.0; // cumsum(p / s)[-1]
 #pragma unroll 1
     for (int j = 0; j < 64; j++)
-        last += (((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0) / s;
+        last += (((lg >> j) & 1ull) ? (double)__uint_as_float(rq::reply_bits(ld(rep + j))) : 0.0) / s;
     if (!(s > 0.0) || !(s <= 1.7976931348623157e308) || !(last > 0.0))
         return 64;
     double acc = 0.0;
     int n = 0; // searchsorted(cdf, u, side='right')
 #pragma unroll 1
     for (int j = 0; j < 64; j++) {
-        acc += (((lg >> j) & 1ull) ? (double)__uint_as_float((uint32_t)ld(rep + j)) : 0.0) / s;
+        acc += (((lg >> j) & 1ull) ? (double)__uint_as_float(rq::reply_bits(ld(rep + j))) : 0.0) / s;
         n += acc / last <= u ? 1 : 0;
     }
     return n;
@@ -498,7 +583,7 @@ __device__ __forceinline__ void take_replies(const SearchParams &S, const iago_r
         bool ok = true;
 #pragma unroll
         for (int i = 0; i < 8; i++)
-            ok = ok && (uint32_t)(ld(&S.rep_p[I.g * 64 + (int)I.r * 8 + i]) >> 32) == G.epoch;
+            ok = ok && rq::reply_tag(ld(&S.rep_p[I.g * 64 + (int)I.r * 8 + i])) == G.epoch;
         if (group8_all(ok)) {
             if (G.state == ST_WAIT_DRAW) {
                 // np.random.choice(64, p=prob*valid/np.sum(prob*valid)) (game.py:102-104) with the uniform of
@@ -518,8 +603,8 @@ __device__ __forceinline__ void take_replies(const SearchParams &S, const iago_r
         }
     } else if (G.state == ST_WAIT_VALUE) {
         const u64 x = ld(&S.rep_v[I.g]);
-        if ((uint32_t)(x >> 32) == G.epoch) {
-            C.v_reply = __uint_as_float((uint32_t)x);
+        if (rq::reply_tag(x) == G.epoch) {
+            C.v_reply = __uint_as_float(rq::reply_bits(x));
             G.state = ST_HAVE_VALUE;
         }
     }
@@ -835,7 +920,7 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
             if (fc1 != 0u) {
                 const int nf = (int)fc1 - 1;
                 make_children(T, I.base, nf, C.node, lg, I.r, S.prior_off,
-                              [&](int a) { return __uint_as_float((uint32_t)ld(&S.rep_p[I.g * 64 + a])); });
+                              [&](int a) { return __uint_as_float(rq::reply_bits(ld(&S.rep_p[I.g * 64 + a]))); });
                 if constexpr (NOISE) {
                     if (C.path_n == 1 && kn > 1) {
                         uint32_t c[8];
@@ -1404,70 +1489,43 @@ __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago
 // Two VALUE entries that are in the ring together are walked as a PAIR (trunk_item<true, 2>: the two boards
 // share the weight stream, which bounds the one-board walk: 46 instead of 70 us of CU time per board; the same
 // products in the same order per board: bit-identical values).
-__device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_trunk::TrunkRParams &VP,
-                                              const iago_policy::PolicyParams &PP, const long long t0, const int wg)
-{
-    __shared__ __align__(16) uint32_t job[32]; // up to two entries of 6 words (kind | game, reply tag, own lo / hi, opp lo / hi); [28..]: status, count
-    const int tid = threadIdx.x;
-    const int64_t row0 = 4 * (int64_t)wg; // this workgroup's rows of wg_own / wg_opp / out / probs (two in use)
-    const uint32_t home = ((int)((uint32_t)wg & 7u) >= 8 - S.policy_xcds) ? KIND_POLICY : KIND_VALUE;
-    // Tickets are handed out by fetch-and-add whenever the ring shows an entry waiting: several workgroups that saw the
-    // same entry all take one, and the later ones wait in fetch() for the ring's next entries.  (Measured and dropped,
-    // round 5: head moved by compare-and-swap bounded by the tail, so that nobody is committed to an entry that does not
-    // exist -- a retry loop took the 1024-game batch from 0.39 to 3.6 s, one attempt per look to 1.76 s: the losers keep
-    // polling and retrying on ONE word from all XCDs, same-address atomics serialise, and every claim queues behind them.)
+//
+// net_workgroup is a driver loop over phase functions: the nets' LDS weights, staged once (stage_net_weights) -> per
+// item: the claim of a ticket and its entry, or of two (claim) -> the walk and its reply (answer_value, answer_policy)
+// -> at the search's end, the counters (leave).  The request's words, the ring's and the mailboxes' granules:
+// search_request.hpp; the rings' device functions: beside send_request.
+
+// the workgroup's static LDS: what goes between the claim, the walks and the replies.  (Positions, values and priors
+// go between the request's words and the walks through LDS: a store to global memory read back by this very workgroup
+// was a round trip to L2, ~2 us under load, twice per walk)
+struct NetLds {
+    uint32_t req[2][rq::WORDS]; // up to two requests (the low halves of their entries' granules)
+    uint32_t status, count;     // the claim's outcome (ring_fetch's status; requests claimed), from wave 0 to all
+    float res_v[2], res_p[64];  // a value walk's values, a policy walk's distribution
+};
+// where the nets' staged weights lie in the dynamic LDS
+struct NetWeights {
+    float *w1_val, *w1_pol; // block1's weights and biases
+    char *head_v;           // the value head (conv_trunk_body.hpp, HEAD_W_*)
+    float *head_p;          // conv9 [128], bias10 [64]
+};
+// what a net workgroup carries from one item to the next
+struct NetState {
     // a VALUE ticket taken for a pair whose entry was not there yet: the next round's entry
-    uint32_t carry = 0u;
-    int n_carry = 0;
+    uint32_t carry;
+    int n_carry;
+    u64 *put_e;     // (lanes 0 / 1: the position-table entry whose sequence word is still to be published)
+    u64 put_word;
+    long long t_wait, t_walk, n_pairs;
+};
 
-    // wave 0: wait for entry t of ring q (at most max_spins polls; 0 = until it comes or the search is over)
-    // -> job[6 * which ..]; returns 0 = entry read, 1 = not there yet, 2 = the search is over / given up
-    auto fetch = [&](uint32_t q, uint32_t t, uint32_t max_spins, int which) -> int {
-        const u64 *e = S.q_slots + ((u64)q * QCAP + t % QCAP) * 8u;
-        u64 x = 0;
-        int status = 0;
-        for (uint32_t spins = 0;; spins++) {
-            x = (tid < 6) ? ld(e + tid) : 0ull;
-            const bool ok = tid >= 6 || (uint32_t)(x >> 32) == t + 1u;
-            if (__builtin_amdgcn_ballot_w64(ok) == ~0ull)
-                break;
-            if (max_spins && spins + 1u >= max_spins) {
-                status = 1;
-                break;
-            }
-            if ((spins & 15u) == 15u) {
-                bool out = false;
-                if (tid == 0)
-                    out = __hip_atomic_load(&S.ctl[CTL_FINISHED], RLX_AGENT) >= (uint32_t)S.n_game_wgs ||
-                          __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u || wall_clock64() - t0 > S.clock_limit;
-                if (__builtin_amdgcn_ballot_w64(out) != 0ull) {
-                    status = 2;
-                    break;
-                }
-            }
-            __builtin_amdgcn_s_sleep(8);
-        }
-        if (status == 0 && tid < 6)
-            job[6 * which + tid] = (uint32_t)x;
-        return status;
-    };
-    auto take = [&](uint32_t q) -> uint32_t {
-        uint32_t t = 0;
-        if (tid == 0)
-            t = __hip_atomic_fetch_add(&S.ctl[ctl_head(q)], 1u, RLX_AGENT);
-        return __builtin_amdgcn_readfirstlane(t);
-    };
-    auto backlog = [&](uint32_t q) -> int {
-        int d = 0;
-        if (tid == 0)
-            d = (int32_t)(__hip_atomic_load(&S.ctl[ctl_tail(q)], RLX_AGENT) - __hip_atomic_load(&S.ctl[ctl_head(q)], RLX_AGENT));
-        return __builtin_amdgcn_readfirstlane(d);
-    };
-
+// ---- 0. both nets' block-1 and head weights into the top of the dynamic LDS, once per workgroup
+__device__ __forceinline__ NetWeights stage_net_weights(const iago_trunk::TrunkRParams &VP, const iago_policy::PolicyParams &PP)
+{
+    const int tid = threadIdx.x;
     // block1's weights and biases of both nets, staged ONCE per workgroup at the top of the dynamic LDS (above the
     // walks' images: conv_trunk_body.hpp, Piece::w1s)
     float *const w1_val = (float *)(iago_trunk::trunk_lds + SEARCH_IMG_TOP), *const w1_pol = w1_val + (64 * 18 + 64);
-    __shared__ float res_v[2], res_p[64];
     for (int e = tid; e < 64 * 18 / 4; e += 256) {
         ((float4 *)w1_val)[e] = ((const float4 *)VP.w1)[e];
         ((float4 *)w1_pol)[e] = ((const float4 *)PP.w1)[e];
@@ -1496,119 +1554,150 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
     if (tid < 64)
         head_p[128 + tid] = PP.b10[tid];
     __syncthreads();
-    u64 *put_e = nullptr; // (lanes 0 / 1: the position-table entry whose sequence word is still to be published)
-    u64 put_word = 0;
-    long long t_wait = 0, t_walk = 0, n_pairs = 0;
+    return NetWeights{w1_val, w1_pol, head_v, head_p};
+}
+
+// ---- 1. the claim (wave 0): a ticket and its entry -> L.req[0], and a second VALUE entry -> L.req[1] where
+// `pair_backlog` more wait; L.status / L.count for all waves.  In this order: the ticket carried over from the last
+// claim, an entry waiting in the home ring, else in the other one; nothing anywhere: poll the counters (no ticket is
+// taken for an entry that is not there, so nobody is committed to a ring that stays empty)
+__device__ __forceinline__ void claim(const SearchParams &S, const uint32_t home, NetState &N, NetLds &L, const long long t0)
+{
+    const int tid = threadIdx.x;
+    int status = 2, count = 0;
+    bool polling = false;
+    for (;;) {
+        uint32_t q = home;
+        bool have = N.n_carry > 0;
+        uint32_t t1 = N.carry;
+        if (have) {
+            q = KIND_VALUE;
+            N.n_carry = 0;
+        } else if (ring_backlog(S, home) > 0) {
+            t1 = ring_take(S, home);
+            have = true;
+        } else if (ring_backlog(S, home ^ 1u) > 0) {
+            q = home ^ 1u;
+            t1 = ring_take(S, q);
+            have = true;
+        }
+        if (have) {
+            // (a ticket below the tail: its producer is writing the entry right now; one beyond it -- two
+            // workgroups saw the same entry -- waits for the next entry of that ring)
+            status = ring_fetch(S, q, t1, 0u, L.req[0], t0);
+            count = status == 0 ? 1 : 0;
+            if (status == 0 && q == KIND_VALUE && ring_backlog(S, KIND_VALUE) >= S.pair_backlog) {
+                // (four boards per walk were measured too: the third variant's registers spill in this
+                // kernel and the walks lose more than the shared stream gains: LABNOTES.md, round 4)
+                const uint32_t t2 = ring_take(S, KIND_VALUE);
+                if (ring_fetch(S, KIND_VALUE, t2, 8u, L.req[1], t0) == 0) {
+                    count = 2;
+                } else {
+                    N.carry = t2; // not there yet: the next round's entry
+                    N.n_carry = 1;
+                }
+            }
+            break;
+        }
+        if (search_over(S, t0))
+            break; // status 2: every game workgroup is done (no request can come any more), or given up
+        if (!polling) {
+            polling = true; // (counted while it polls: values ahead of their visit go to idle hands only)
+            if (tid == 0)
+                __hip_atomic_fetch_add(&S.ctl[CTL_IDLE], 1u, RLX_AGENT);
+        }
+        __builtin_amdgcn_s_sleep(16);
+    }
+    if (polling && tid == 0)
+        __hip_atomic_fetch_add(&S.ctl[CTL_IDLE], 0xFFFFFFFFu, RLX_AGENT);
+    if (tid == 0) {
+        L.status = (uint32_t)status;
+        L.count = (uint32_t)count;
+    }
+}
+
+// ---- 2a. a value walk of `count` boards: the values to the games' mailboxes, and into the position table (its first
+// step: vtable_put_begin; the driver's next iteration publishes)
+__device__ __forceinline__ void answer_value(const SearchParams &S, const iago_trunk::TrunkRParams &VP, NetState &N, NetLds &L,
+                                             const NetWeights &Wt, const int64_t row0, const int count)
+{
+    const int tid = threadIdx.x;
+    iago_trunk::Piece W = iago_trunk::whole_walk(VP);
+    W.pos = L.req[0];
+    W.res = L.res_v;
+    W.w1s = Wt.w1_val;
+    W.head_w = Wt.head_v;
+    if (count == 2)
+        iago_trunk::trunk_item<true, 2, true>(VP, W, row0, row0 + count);
+    else
+        iago_trunk::trunk_item<true, 1, true>(VP, W, row0, row0 + count);
+    __syncthreads();
+    if (tid < count) {
+        const uint32_t *r = L.req[tid];
+        const uint32_t bits = __float_as_uint(L.res_v[tid]);
+        reply_value(S, r, bits);
+        if (S.vtable) // (the writer: the game that asked; nobody: the sender, in the request's tag)
+            N.put_e = vtable_put_begin(S, rq::own(r), rq::opp(r), bits, rq::game(r) != NOBODY ? rq::game(r) : rq::tag(r),
+                                       N.put_word);
+    }
+}
+
+// ---- 2b. a policy walk: the distribution to the game's mailbox
+__device__ __forceinline__ void answer_policy(const SearchParams &S, const iago_policy::PolicyParams &PP, NetLds &L,
+                                              const NetWeights &Wt, const int64_t row0)
+{
+    const int tid = threadIdx.x;
+    iago_policy::policy_item<true>(PP, row0, L.req[0], L.res_p, Wt.w1_pol, Wt.head_p);
+    __syncthreads();
+    if (tid < 64)
+        reply_prior(S, L.req[0], tid, __float_as_uint(L.res_p[tid]));
+}
+
+// ---- 3. the search is over: this workgroup's pair walks and its waiting / walking time
+__device__ __forceinline__ void leave(const SearchParams &S, const NetState &N)
+{
+    if (threadIdx.x == 0) {
+        atomicAdd((unsigned long long *)&S.totals[3], (unsigned long long)N.n_pairs);
+        atomicAdd((unsigned long long *)&S.totals[4], (unsigned long long)N.t_wait);
+        atomicAdd((unsigned long long *)&S.totals[5], (unsigned long long)N.t_walk);
+    }
+}
+
+__device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_trunk::TrunkRParams &VP,
+                                              const iago_policy::PolicyParams &PP, const long long t0, const int wg)
+{
+    __shared__ __align__(16) NetLds L;
+    const int tid = threadIdx.x;
+    const int64_t row0 = 4 * (int64_t)wg; // this workgroup's rows of wg_own / wg_opp / out / probs (two in use)
+    // the ring it serves first.  (By value, not a field of NetState: as a field the single launch measured 0.35 % slower
+    // than the parent, twice; LABNOTES.md, "The net workgroup in named phases")
+    const uint32_t home = ((int)((uint32_t)wg & 7u) >= 8 - S.policy_xcds) ? KIND_POLICY : KIND_VALUE;
+    NetState N = {0u, 0, nullptr, 0, 0, 0, 0};
+    const NetWeights Wt = stage_net_weights(VP, PP);
     for (;;) {
         const long long c0 = wall_clock64();
-        if (put_e) {
-            vtable_put_end(put_e, put_word);
-            put_e = nullptr;
+        if (N.put_e) { // (the last value walk's table entry: vtable_put_begin)
+            vtable_put_end(N.put_e, N.put_word);
+            N.put_e = nullptr;
         }
-        if (tid < 64) {
-            int status = 2, count = 0;
-            bool polling = false;
-            // an entry waiting in the home ring, else in the other one; nothing anywhere: poll the counters (no
-            // ticket is taken for an entry that is not there, so nobody is committed to a ring that stays empty)
-            for (;;) {
-                uint32_t q = home;
-                bool have = n_carry > 0;
-                uint32_t t1 = carry;
-                if (have) {
-                    q = KIND_VALUE;
-                    n_carry = 0;
-                } else if (backlog(home) > 0) {
-                    t1 = take(home);
-                    have = true;
-                } else if (backlog(home ^ 1u) > 0) {
-                    q = home ^ 1u;
-                    t1 = take(q);
-                    have = true;
-                }
-                if (have) {
-                    // (a ticket below the tail: its producer is writing the entry right now; one beyond it -- two
-                    // workgroups saw the same entry -- waits for the next entry of that ring)
-                    status = fetch(q, t1, 0u, 0);
-                    count = status == 0 ? 1 : 0;
-                    if (status == 0 && q == KIND_VALUE && backlog(KIND_VALUE) >= S.pair_backlog) {
-                        // (four boards per walk were measured too: the third variant's registers spill in this
-                        // kernel and the walks lose more than the shared stream gains: LABNOTES.md, round 4)
-                        const uint32_t t2 = take(KIND_VALUE);
-                        if (fetch(KIND_VALUE, t2, 8u, 1) == 0) {
-                            count = 2;
-                        } else {
-                            carry = t2; // not there yet: the next round's entry
-                            n_carry = 1;
-                        }
-                    }
-                    break;
-                }
-                bool out = false;
-                if (tid == 0)
-                    out = __hip_atomic_load(&S.ctl[CTL_FINISHED], RLX_AGENT) >= (uint32_t)S.n_game_wgs ||
-                          __hip_atomic_load(&S.ctl[CTL_ABORT], RLX_AGENT) != 0u || wall_clock64() - t0 > S.clock_limit;
-                if (__builtin_amdgcn_ballot_w64(out) != 0ull)
-                    break; // status 2: every game workgroup is done (no request can come any more), or given up
-                if (!polling) {
-                    polling = true; // (counted while it polls: values ahead of their visit go to idle hands only)
-                    if (tid == 0)
-                        __hip_atomic_fetch_add(&S.ctl[CTL_IDLE], 1u, RLX_AGENT);
-                }
-                __builtin_amdgcn_s_sleep(16);
-            }
-            if (polling && tid == 0)
-                __hip_atomic_fetch_add(&S.ctl[CTL_IDLE], 0xFFFFFFFFu, RLX_AGENT);
-            if (tid == 0) {
-                job[28] = (uint32_t)status;
-                job[29] = (uint32_t)count;
-            }
-        }
+        if (tid < 64)
+            claim(S, home, N, L, t0); // ticket -> entry
         __syncthreads();
         const long long c1 = wall_clock64();
-        t_wait += c1 - c0;
-        if (job[28] != 0u) {
-            if (tid == 0) {
-                atomicAdd((unsigned long long *)&S.totals[3], (unsigned long long)n_pairs);
-                atomicAdd((unsigned long long *)&S.totals[4], (unsigned long long)t_wait);
-                atomicAdd((unsigned long long *)&S.totals[5], (unsigned long long)t_walk);
-            }
+        N.t_wait += c1 - c0;
+        if (L.status != 0u) {
+            leave(S, N);
             return;
         }
-        const uint32_t kind = job[0] >> 31;
-        const int count = (int)job[29];
-        n_pairs += count - 1;
-        // (positions, values and priors go between the request's words and the walks through LDS: a store to global
-        // memory read back by this very workgroup was a round trip to L2, ~2 us under load, twice per walk)
-        if (kind == KIND_VALUE) {
-            iago_trunk::Piece W = iago_trunk::whole_walk(VP);
-            W.pos = job;
-            W.res = res_v;
-            W.w1s = w1_val;
-            W.head_w = head_v;
-            if (count == 2)
-                iago_trunk::trunk_item<true, 2, true>(VP, W, row0, row0 + count);
-            else
-                iago_trunk::trunk_item<true, 1, true>(VP, W, row0, row0 + count);
-            __syncthreads();
-            if (tid < count) {
-                const uint32_t bits = __float_as_uint(res_v[tid]);
-                if ((job[6 * tid] & 0x7FFFFFFFu) != NOBODY)
-                    st(&S.rep_v[(int64_t)(job[6 * tid] & 0x7FFFFFFFu)], ((u64)job[6 * tid + 1] << 32) | bits);
-                if (S.vtable) {
-                    const uint32_t asked = job[6 * tid] & 0x7FFFFFFFu;
-                    put_e = vtable_put_begin(S, ((uint64_t)job[6 * tid + 3] << 32) | job[6 * tid + 2],
-                                             ((uint64_t)job[6 * tid + 5] << 32) | job[6 * tid + 4], bits,
-                                             asked != NOBODY ? asked : job[6 * tid + 1], put_word);
-                }
-            }
-        } else {
-            iago_policy::policy_item<true>(PP, row0, job, res_p, w1_pol, head_p);
-            __syncthreads();
-            if (tid < 64)
-                st(&S.rep_p[(int64_t)(job[0] & 0x7FFFFFFFu) * 64 + tid], ((u64)job[1] << 32) | __float_as_uint(res_p[tid]));
-        }
-        __syncthreads(); // the next item re-stages the LDS image and job[]
-        t_walk += wall_clock64() - c1;
+        const uint32_t kind = rq::kind(L.req[0]);
+        const int count = (int)L.count;
+        N.n_pairs += count - 1;
+        if (kind == KIND_VALUE)
+            answer_value(S, VP, N, L, Wt, row0, count); // walk -> reply
+        else
+            answer_policy(S, PP, L, Wt, row0);
+        __syncthreads(); // the next item re-stages the LDS image and the requests
+        N.t_walk += wall_clock64() - c1;
     }
 }
 

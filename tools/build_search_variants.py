@@ -42,8 +42,8 @@ def request_log(s):
     }
 }''')
     # (the timeline rows and the per-game end rows would overwrite the log)
-    s = patch(s, "if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
-              "if (false && S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
+    s = patch(s, "if (S.trace && I.wg == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
+              "if (false && S.trace && I.wg == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
     s = patch(s, "if (S.trace && I.r == 0u && I.g < S.trace_rows) {", "if (false && S.trace && I.r == 0u && I.g < S.trace_rows) {")
     return s
 
@@ -253,22 +253,25 @@ def reply_times(s):
     """Post-mortem of a launch that gave up (round 6): per game, in the `trace` buffer, [0] the clock at its last request,
     [1] the clock at which a net workgroup wrote the reply to that request's mailbox (value or priors), [2] the clock at
     which its workgroup left the loop, [3] state | reply tag << 8 (tools/debug_split_abort.py)."""
-    s = patch(s, "if (S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
-              "if (false && S.trace && blockIdx.x == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
+    s = patch(s, "if (S.trace && I.wg == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <",
+              "if (false && S.trace && I.wg == 0 && I.tid == 0 && (int64_t)sh.wg_count[0] <")
     s = patch(s, "if (S.trace && I.r == 0u && I.g < S.trace_rows) {", "if (false && S.trace && I.r == 0u && I.g < S.trace_rows) {")
     s = patch(s, """    atomicAdd((unsigned long long *)&S.totals[(uint32_t)g == NOBODY ? 11 : kind], 1ull);
 }""", """    atomicAdd((unsigned long long *)&S.totals[(uint32_t)g == NOBODY ? 11 : kind], 1ull);
     if (S.trace && (uint32_t)g != NOBODY && g < S.trace_rows)
         S.trace[4 * g + 0] = wall_clock64();
 }""")
-    s = patch(s, """                    st(&S.rep_v[(int64_t)(job[6 * tid] & 0x7FFFFFFFu)], ((u64)job[6 * tid + 1] << 32) | bits);""",
-              """                    st(&S.rep_v[(int64_t)(job[6 * tid] & 0x7FFFFFFFu)], ((u64)job[6 * tid + 1] << 32) | bits);
-                if (S.trace && (job[6 * tid] & 0x7FFFFFFFu) != NOBODY && (int)(job[6 * tid] & 0x7FFFFFFFu) < S.trace_rows)
-                    S.trace[4 * (int64_t)(job[6 * tid] & 0x7FFFFFFFu) + 1] = wall_clock64();""")
-    s = patch(s, """                st(&S.rep_p[(int64_t)(job[0] & 0x7FFFFFFFu) * 64 + tid], ((u64)job[1] << 32) | __float_as_uint(res_p[tid]));""",
-              """                st(&S.rep_p[(int64_t)(job[0] & 0x7FFFFFFFu) * 64 + tid], ((u64)job[1] << 32) | __float_as_uint(res_p[tid]));
-            if (S.trace && tid == 0 && (int)(job[0] & 0x7FFFFFFFu) < S.trace_rows)
-                S.trace[4 * (int64_t)(job[0] & 0x7FFFFFFFu) + 1] = wall_clock64();""")
+    # (reply_value, reply_prior: r = the request, i = the distribution's word)
+    s = patch(s, """        st(&S.rep_v[(int64_t)rq::game(r)], rq::reply_word(rq::tag(r), bits));""",
+              """    {
+        st(&S.rep_v[(int64_t)rq::game(r)], rq::reply_word(rq::tag(r), bits));
+        if (S.trace && (int)rq::game(r) < S.trace_rows)
+            S.trace[4 * (int64_t)rq::game(r) + 1] = wall_clock64();
+    }""")
+    s = patch(s, """    st(&S.rep_p[(int64_t)rq::game(r) * 64 + i], rq::reply_word(rq::tag(r), bits));""",
+              """    st(&S.rep_p[(int64_t)rq::game(r) * 64 + i], rq::reply_word(rq::tag(r), bits));
+    if (S.trace && i == 0 && (int)rq::game(r) < S.trace_rows)
+        S.trace[4 * (int64_t)rq::game(r) + 1] = wall_clock64();""")
     s = patch(s, """        S.cur_node[I.g] = (int32_t)G.epoch;
         S.leaf_value[I.g] = (float)G.state;""", """        S.cur_node[I.g] = (int32_t)G.epoch;
         S.leaf_value[I.g] = (float)G.state;
@@ -277,37 +280,31 @@ def reply_times(s):
             S.trace[4 * I.g + 3] = (int64_t)G.state | ((int64_t)G.epoch << 8);
         }""")
     # ... and per net workgroup (rows 4096 + blockIdx.x): [0] the clock at its last loop top, [1] the clock when it last began
-    # to wait for a ticket, [2] ring << 32 | ticket it last waited for, [3] stage (1 loop top, 2 waiting in fetch, 3 fetched,
-    # 4 left the kernel)
+    # to wait for a ticket, [2] ring << 32 | ticket it last waited for, [3] stage (1 loop top, 2 waiting in ring_fetch, 3
+    # fetched, 4 left the kernel)
     s = patch(s, """        const long long c0 = wall_clock64();
-        if (put_e) {""", """        const long long c0 = wall_clock64();
+        if (N.put_e) {""", """        const long long c0 = wall_clock64();
         if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows) {
             S.trace[4 * (4096 + (int64_t)blockIdx.x) + 0] = c0;
             S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] = 1;
         }
-        if (put_e) {""")
-    s = patch(s, """        u64 x = 0;
-        int status = 0;
-        for (uint32_t spins = 0;; spins++) {""", """        u64 x = 0;
-        int status = 0;
-        if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows && max_spins == 0u) {
-            S.trace[4 * (4096 + (int64_t)blockIdx.x) + 1] = wall_clock64();
-            S.trace[4 * (4096 + (int64_t)blockIdx.x) + 2] = ((int64_t)q << 32) | t;
-            S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] = 2;
-        }
-        for (uint32_t spins = 0;; spins++) {""")
-    s = patch(s, """        if (status == 0 && tid < 6)
-            job[6 * which + tid] = (uint32_t)x;
-        return status;""", """        if (status == 0 && tid < 6)
-            job[6 * which + tid] = (uint32_t)x;
-        if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows && max_spins == 0u)
-            S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] = 3 + 10 * status;
-        return status;""")
-    s = patch(s, """        if (job[28] != 0u) {
-            if (tid == 0) {""", """        if (job[28] != 0u) {
-            if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows)
+        if (N.put_e) {""")
+    s = patch(s, """    int status = 0;
+    for (uint32_t spins = 0;; spins++) {""", """    int status = 0;
+    if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows && max_spins == 0u) {
+        S.trace[4 * (4096 + (int64_t)blockIdx.x) + 1] = wall_clock64();
+        S.trace[4 * (4096 + (int64_t)blockIdx.x) + 2] = ((int64_t)q << 32) | t;
+        S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] = 2;
+    }
+    for (uint32_t spins = 0;; spins++) {""")
+    s = patch(s, """        dst[tid] = (uint32_t)x;
+    return status;""", """        dst[tid] = (uint32_t)x;
+    if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows && max_spins == 0u)
+        S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] = 3 + 10 * status;
+    return status;""")
+    s = patch(s, """            leave(S, N);""", """            if (S.trace && tid == 0 && 4096 + (int)blockIdx.x < S.trace_rows)
                 S.trace[4 * (4096 + (int64_t)blockIdx.x) + 3] += 100;
-            if (tid == 0) {""")
+            leave(S, N);""")
     # the ticket of a game's last request
     s = patch(s, """    if (S.trace && (uint32_t)g != NOBODY && g < S.trace_rows)
         S.trace[4 * g + 0] = wall_clock64();""", """    if (S.trace && (uint32_t)g != NOBODY && g < S.trace_rows) {
@@ -381,8 +378,9 @@ def main():
                      ("search_replytimes", reply_times), ("search_atomicst", atomic_stores)):
         if only and name not in only:
             continue
-        if not only and name in ("search_walkstamps_noa", "search_walkstamps_nob", "search_unroll4"):
-            continue   # (timing-only builds of round 5's first K loops: their anchors are of that code; kept for the record)
+        if not only and name in ("search_walkstamps_noa", "search_walkstamps_nob", "search_unroll4", "search_epiwrite"):
+            continue   # (timing-only builds of round 5's first K loops and epilogue: their anchors are of that code; kept
+            # for the record)
         path = os.path.join(OUT, name + ".hip")
         open(path, "w").write(fn(src))
         obj = os.path.join(OUT, name + ".o")
