@@ -53,7 +53,8 @@ EXPERIMENTAL_SYMBOLS = [
 # playout-cap randomisation (SelfPlayEngine.play(playout_cap=)), root noise (SelfPlayEngine.play(root_noise=)), forced
 # playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=)), the fixed-depth alpha-beta opponent and its
 # random openings (ops.alphabeta_moves, ops.random_moves; SelfPlayEngine.play_match(opponent=AlphaBeta(d))), that
-# search with every root spread over the lanes (ops.alphabeta_moves(split=), AlphaBeta(d, split))
+# search with every root spread over the lanes (ops.alphabeta_moves(split=), AlphaBeta(d, split)), and the exact solver
+# spread the same way (ops.solve_endgame(split=), ops.solve_endgame_moves(split=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_solve_endgame_moves", "iago_play_endgame_moves",
@@ -61,7 +62,7 @@ SERVING_SYMBOLS = [
     "iago_mcts_search_cap", "iago_mcts_cap_mask",
     "iago_mcts_root_noise", "iago_mcts_search_noise",
     "iago_mcts_search_forced", "iago_mcts_prune_visits", "iago_mcts_prune_visits_rule",
-    "iago_alphabeta_moves", "iago_random_moves", "iago_alphabeta_moves_split",
+    "iago_alphabeta_moves", "iago_random_moves", "iago_alphabeta_moves_split", "iago_solve_endgame_split",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -322,6 +323,24 @@ class EndgameMovesArgs(C.Structure):
     ]
 
 
+ENDGAME_MAX_SPLIT = 2         # IAGO_ENDGAME_MAX_SPLIT
+ENDGAME_SPLIT_CTL_WORDS = 8   # IAGO_ENDGAME_SPLIT_CTL_WORDS
+
+
+class EndgameSplitArgs(C.Structure):
+    """Mirror of iago_endgame_split_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("n", C.c_int64),
+        ("mode", C.c_int32), ("split", C.c_int32), ("max_empties", C.c_int32), ("time_limit_ms", C.c_int32),
+        ("score", C.c_void_p), ("move", C.c_void_p), ("nodes", C.c_void_p), ("solved", C.c_void_p),
+        ("best", C.c_void_p), ("move_score", C.c_void_p),
+        ("job_count", C.c_void_p), ("job_first", C.c_void_p), ("job_capacity", C.c_int64),
+        ("job_own", C.c_void_p), ("job_opp", C.c_void_p), ("job_root", C.c_void_p), ("job_path", C.c_void_p),
+        ("job_score", C.c_void_p), ("job_move", C.c_void_p), ("job_nodes", C.c_void_p), ("job_done", C.c_void_p),
+        ("ctl", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
 class PlayEndgameMovesArgs(C.Structure):
     """Mirror of iago_play_endgame_moves_args (include/iago_hip_serving.h)."""
     _fields_ = [("play", PlayEndgameArgs), ("rec_best", C.c_void_p), ("reserved", C.c_int64 * 4)]
@@ -544,6 +563,7 @@ def lib():
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]
     L.iago_alphabeta_moves.argtypes = [C.POINTER(AlphaBetaArgs), vp]
     L.iago_alphabeta_moves_split.argtypes = [C.POINTER(AlphaBetaSplitArgs), vp]
+    L.iago_solve_endgame_split.argtypes = [C.POINTER(EndgameSplitArgs), vp]
     L.iago_random_moves.argtypes = [vp, vp, i64, C.c_uint64, C.c_uint32, C.c_uint32, i32, vp, vp]
     for name in SYMBOLS[3:] + LAYER_SYMBOLS + EXPERIMENTAL_SYMBOLS + SERVING_SYMBOLS + TRAINING_SYMBOLS:
         getattr(L, name).restype = C.c_int

@@ -19,8 +19,10 @@
 // (position, depth left) on the device, the same search runs a lane per job (alphabeta_jobs_kernel: the job count read
 // from ctl, every lane's depth from its job), and a thread per root takes the values back.  Every job has the full window,
 // so its value and its node count are those of iago_alphabeta_moves on that position, whatever else runs beside it.
+// The expansion, the scan, the job record and the reduction are lane_split.hpp's, shared with iago_solve_endgame_split.
 #include "abi_common.hpp"
 #include "lane_search.hpp"
+#include "lane_split.hpp"
 #include "othello_dev.hpp"
 
 #include "../../include/iago_hip_serving.h"
@@ -33,11 +35,6 @@ namespace {
 constexpr int ORDER_DEPTH = 3;     // nodes with at least this much depth left try their moves fewest replies first
 constexpr uint32_t OPEN_KEY = IAGO_OPENING_KEY;
 constexpr uint64_t CORNERS = 0x8100000000000081ull;
-
-// iago_alphabeta_moves_split's further ctl words
-constexpr int CTL_JOBS_LO = 4;
-constexpr int CTL_JOBS_HI = 5;
-constexpr int CTL_JOB_OVERFLOW = 6;
 
 template <int V>
 __device__ __forceinline__ int class_term(uint64_t own, uint64_t opp, uint64_t mask)
@@ -104,8 +101,6 @@ struct YardstickRules {
         return (int)(hi >> 17);
     }
 };
-
-constexpr int NEG_INF = YardstickRules::NEG_INF;
 
 // what a finished search answers, for both params below
 template <class Params>
@@ -181,227 +176,23 @@ __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(8, 8))) void alphabeta_jobs_kernel(JobParams P)
 {
     extern __shared__ __align__(16) unsigned char stack_lds[];
-    const int64_t n = P.ctl[CTL_JOB_OVERFLOW] != 0u ? 0 : (int64_t)P.ctl[CTL_JOBS_LO];
+    const int64_t n = split_jobs_to_claim(P.ctl);
     if ((int64_t)blockIdx.x * WAVE >= n) // nothing to claim: the wave leaves at once
         return;
     search_wave(P, YardstickRules{}, n, 0, stack_lds);
 }
 
-// ---- iago_alphabeta_moves_split: the roots' jobs counted, summed and written, (searched: alphabeta_jobs_kernel,) and
-// taken back.  Every stage is a launch of its own on the caller's stream: a stage reads what the one before it wrote.
-
-constexpr int SPLIT_BLOCK = 256;
-constexpr int SCAN_BLOCK = 1024;
-
-struct SplitParams {
-    const uint64_t *own;
-    const uint64_t *opp;
-    int64_t n;
+// ---- iago_alphabeta_moves_split: the stages of lane_split.hpp on the opponent's KIND -- a job's depth left is the
+// launch's depth minus the plies of its path, values are int16, the reduction answers score and move alone.
+struct DepthJobs {
+    using Score = int16_t;
+    static constexpr int NEG_INF = YardstickRules::NEG_INF;
+    static constexpr bool MOVES = false;
     int32_t depth;
-    int32_t split;
-    int32_t *job_count;
-    int64_t *job_first;
-    int64_t capacity;
-    uint64_t *job_own;
-    uint64_t *job_opp;
-    int32_t *job_root;
-    int8_t *job_path;
-    uint8_t *job_done;
-    uint32_t *ctl;
+
+    __device__ __forceinline__ bool admits(uint64_t own, uint64_t opp) const { return (own & opp) == 0ull; }
+    __device__ __forceinline__ int left(uint64_t, uint64_t, int plies) const { return depth - plies; }
 };
-
-// The jobs of root i in canonical order (first move ascending, then second move): counted, and with WRITE written from
-// job_first[i] on.  A node is a job when no split ply is left or its mover has no legal move, else it is expanded.
-template <bool WRITE>
-__device__ __forceinline__ int expand_root(const SplitParams &P, int64_t i, uint64_t own, uint64_t opp,
-                                           const ShiftAmounts &SA)
-{
-    int64_t at = 0;
-    if constexpr (WRITE)
-        at = P.job_first[i];
-    int count = 0;
-    auto job = [&](uint64_t o, uint64_t p, int d, int m1, int m2) {
-        if constexpr (WRITE) {
-            const int64_t j = at + count;
-            if (j < P.capacity) { // (always: the total fits or nothing is written)
-                P.job_own[j] = o;
-                P.job_opp[j] = p;
-                P.job_root[j] = (int32_t)i;
-                P.job_path[4 * j + 0] = (int8_t)d;
-                P.job_path[4 * j + 1] = (int8_t)m1;
-                P.job_path[4 * j + 2] = (int8_t)m2;
-                P.job_path[4 * j + 3] = 0;
-                P.job_done[j] = 0;
-            }
-        }
-        count++;
-    };
-    uint64_t legal = legal_of(own, opp, SA);
-    if (legal == 0ull) {
-        job(own, opp, P.depth, -1, -1); // a root that must pass, or a finished game
-        return count;
-    }
-    while (legal) {
-        const uint32_t m1 = lowest_bit(legal);
-        legal &= legal - 1ull;
-        const uint64_t f = flips_of(own, opp, m1);
-        const uint64_t cown = opp & ~f, copp = own | f | (1ull << m1);
-        uint64_t replies = P.split >= 2 ? legal_of(cown, copp, SA) : 0ull;
-        if (replies == 0ull) {
-            job(cown, copp, P.depth - 1, (int)m1, -1); // the last split ply, or a child that cannot move
-            continue;
-        }
-        while (replies) {
-            const uint32_t m2 = lowest_bit(replies);
-            replies &= replies - 1ull;
-            const uint64_t g = flips_of(cown, copp, m2);
-            job(copp & ~g, cown | g | (1ull << m2), P.depth - 2, (int)m1, (int)m2);
-        }
-    }
-    return count;
-}
-
-__global__ __launch_bounds__(SPLIT_BLOCK) void split_count_kernel(SplitParams P)
-{
-    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
-    if (i >= P.n)
-        return;
-    const ShiftAmounts SA = opaque_shift_amounts();
-    const uint64_t own = P.own[i], opp = P.opp[i];
-    int count = 0;
-    if ((own & opp) != 0ull)
-        atomicAdd(&P.ctl[CTL_REFUSED], 1u); // refused: no job, done stays 0
-    else
-        count = expand_root<false>(P, i, own, opp, SA);
-    P.job_count[i] = count;
-}
-
-// job_first = the exclusive sum of job_count, the total into ctl: ONE workgroup, SCAN_BLOCK roots per round.
-// capacity < 0: the count-only form, which has no overflow.
-__global__ __launch_bounds__(SCAN_BLOCK) void split_scan_kernel(const int32_t *count, int64_t *first, int64_t n,
-                                                                int64_t capacity, uint32_t *ctl)
-{
-    __shared__ long long wave_sum[SCAN_BLOCK / WAVE];
-    const int lane = threadIdx.x % WAVE, w = threadIdx.x / WAVE;
-    long long carry = 0;
-    for (int64_t base = 0; base < n; base += SCAN_BLOCK) {
-        const int64_t i = base + threadIdx.x;
-        const long long c = i < n ? count[i] : 0;
-        long long x = c;
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const long long y = __shfl_up(x, o);
-            if (lane >= o)
-                x += y;
-        }
-        if (lane == WAVE - 1)
-            wave_sum[w] = x;
-        __syncthreads();
-        long long before = 0, total = 0;
-        for (int k = 0; k < SCAN_BLOCK / WAVE; k++) {
-            const long long v = wave_sum[k];
-            before += k < w ? v : 0;
-            total += v;
-        }
-        if (i < n)
-            first[i] = carry + before + x - c;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ctl[CTL_JOBS_LO] = (uint32_t)carry;
-        ctl[CTL_JOBS_HI] = (uint32_t)((unsigned long long)carry >> 32);
-        if (capacity >= 0 && carry > capacity)
-            ctl[CTL_JOB_OVERFLOW] = 1u;
-    }
-}
-
-__global__ __launch_bounds__(SPLIT_BLOCK) void split_write_kernel(SplitParams P)
-{
-    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
-    if (i >= P.n || P.ctl[CTL_JOB_OVERFLOW] != 0u || P.job_count[i] == 0)
-        return;
-    const ShiftAmounts SA = opaque_shift_amounts();
-    expand_root<true>(P, i, P.own[i], P.opp[i], SA);
-}
-
-struct ReduceParams {
-    int64_t n;
-    const int32_t *job_count;
-    const int64_t *job_first;
-    const int8_t *job_path;
-    const int16_t *job_score;
-    const int8_t *job_move;
-    const int64_t *job_nodes;
-    const uint8_t *job_done;
-    int16_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *done;
-    const uint32_t *ctl;
-};
-
-// A thread per root: its run of jobs minimaxed back, the sign turned once per ply of the path; the first maximum in
-// canonical order is the lowest-indexed move of the best value.
-__global__ __launch_bounds__(SPLIT_BLOCK) void split_reduce_kernel(ReduceParams P)
-{
-    const int64_t i = (int64_t)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
-    if (i >= P.n || P.ctl[CTL_JOB_OVERFLOW] != 0u)
-        return;
-    const int count = P.job_count[i];
-    if (count == 0) { // refused: done stays 0
-        P.score[i] = 0;
-        P.move[i] = 0;
-        P.nodes[i] = 0;
-        return;
-    }
-    const int64_t j0 = P.job_first[i];
-    int best = NEG_INF, best_m = -1;
-    int child_m = -1, child_best = NEG_INF; // the expanded child whose jobs are being taken back
-    int64_t nodes = 1;
-    bool all = true;
-    for (int64_t j = j0; j < j0 + count; j++) {
-        all = all && P.job_done[j] != 0;
-        nodes += P.job_nodes[j];
-        const int m1 = P.job_path[4 * j + 1], m2 = P.job_path[4 * j + 2];
-        const int v = P.job_score[j];
-        if (m1 < 0) { // the root is the job
-            best = v;
-            best_m = P.job_move[j];
-            nodes--;
-            continue;
-        }
-        if (m1 != child_m && child_m >= 0) {
-            if (-child_best > best) {
-                best = -child_best;
-                best_m = child_m;
-            }
-            child_m = -1;
-        }
-        if (m2 < 0) { // the child is the job
-            if (-v > best) {
-                best = -v;
-                best_m = m1;
-            }
-        } else {
-            if (child_m < 0) {
-                child_m = m1;
-                child_best = NEG_INF;
-                nodes++;
-            }
-            child_best = max(child_best, -v);
-        }
-    }
-    if (child_m >= 0 && -child_best > best) {
-        best = -child_best;
-        best_m = child_m;
-    }
-    if (!all) // (a give-up: the unfinished jobs hold nothing)
-        return;
-    P.score[i] = (int16_t)best;
-    P.move[i] = (int8_t)best_m;
-    P.nodes[i] = nodes;
-    P.done[i] = 1;
-}
 
 // ---- iago_random_moves: the opening draw, a thread per game
 
@@ -504,28 +295,9 @@ extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, vo
         return rc;
 
     // 1. expand: count, sum, write
-    SplitParams E;
-    E.own = a->own;
-    E.opp = a->opp;
-    E.n = a->n;
-    E.depth = a->depth;
-    E.split = a->split;
-    E.job_count = a->job_count;
-    E.job_first = a->job_first;
-    E.capacity = a->job_capacity;
-    E.job_own = a->job_own;
-    E.job_opp = a->job_opp;
-    E.job_root = a->job_root;
-    E.job_path = a->job_path;
-    E.job_done = a->job_done;
-    E.ctl = a->ctl;
-    const unsigned roots_grid = (unsigned)((a->n + SPLIT_BLOCK - 1) / SPLIT_BLOCK);
-    hipLaunchKernelGGL(split_count_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, E);
-    hipLaunchKernelGGL(split_scan_kernel, dim3(1), dim3(SCAN_BLOCK), 0, s, (const int32_t *)a->job_count, a->job_first,
-                       a->n, count_only ? (int64_t)-1 : a->job_capacity, a->ctl);
+    split_expand(split_params_of(a, DepthJobs{a->depth}), count_only, s);
     if (count_only)
         return iago_check_launch(who);
-    hipLaunchKernelGGL(split_write_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, E);
 
     // 2. search: the lanes of iago_alphabeta_moves over the jobs
     JobParams J;
@@ -543,21 +315,7 @@ extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, vo
                        a->job_capacity, cus, s);
 
     // 3. reduce
-    ReduceParams R;
-    R.n = a->n;
-    R.job_count = a->job_count;
-    R.job_first = a->job_first;
-    R.job_path = a->job_path;
-    R.job_score = a->job_score;
-    R.job_move = a->job_move;
-    R.job_nodes = a->job_nodes;
-    R.job_done = a->job_done;
-    R.score = a->score;
-    R.move = a->move;
-    R.nodes = a->nodes;
-    R.done = a->done;
-    R.ctl = a->ctl;
-    hipLaunchKernelGGL(split_reduce_kernel, dim3(roots_grid), dim3(SPLIT_BLOCK), 0, s, R);
+    split_reduce(reduce_params_of<DepthJobs>(a, a->done), s);
     return iago_check_launch(who);
 }
 

@@ -10,10 +10,15 @@
 //   * mode WLD scores the end of the game by its sign: the same search on values in {-1, 0, 1}, window (-1, 1)
 //     around 0 at the root.
 // Past time_limit_ms the launch gives up (ctl[0] = 1), every position it has not finished keeps solved = 0.
+// iago_solve_endgame_split spreads every root over many lanes with the stages of lane_split.hpp (the ones of
+// iago_alphabeta_moves_split): the first one or two plies become JOBS on the device, endgame_jobs_kernel searches a lane
+// per job with the full window -- a job's (score, move, nodes) are iago_solve_endgame's on that position -- and a thread
+// per root takes the values back, with the set of the best moves and every move's value where they are asked for.
 // iago_play_endgame (play_endgame_kernel: one lane per GAME) runs the same search once per turn of a game and plays
 // the moves, to the game's end.
 #include "abi_common.hpp"
 #include "lane_search.hpp"
+#include "lane_split.hpp"
 #include "othello_dev.hpp"
 
 #include "../../include/iago_hip_serving.h"
@@ -141,6 +146,61 @@ __global__ __launch_bounds__(WAVE) void endgame_moves_kernel(MovesParams P)
 {
     extern __shared__ __align__(16) unsigned char stack_lds[];
     search_wave(P, SolverRulesT<ROOT>{P.wld}, P.n, 0, stack_lds);
+}
+
+// ---- iago_solve_endgame_split: the stages of lane_split.hpp on the solver's KIND -- a job's levels are its own
+// empties, values are int8, the reduction also answers the set of the best moves and every move's value.
+struct EmptiesJobs {
+    using Score = int8_t;
+    static constexpr int NEG_INF = SolverRules::NEG_INF;
+    static constexpr bool MOVES = true;
+    int32_t max_empties;
+
+    __device__ __forceinline__ bool admits(uint64_t own, uint64_t opp) const
+    {
+        return (own & opp) == 0ull && 64 - __popcll(own | opp) <= max_empties;
+    }
+    __device__ __forceinline__ int left(uint64_t own, uint64_t opp, int) const { return 64 - __popcll(own | opp); }
+};
+
+// The jobs as the search reads and answers them: positions of an admitted root's subtree, each with its own empties
+struct EndgameJobParams {
+    const uint64_t *own;
+    const uint64_t *opp;
+    int8_t *score;
+    int8_t *move;
+    int64_t *nodes;
+    uint8_t *done;
+    uint32_t *ctl;
+    int32_t wld;
+    int32_t levels;          // stack frames per lane: max_empties'
+    long long clock_limit;
+
+    __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &empties) const
+    {
+        o = own[pos];
+        p = opp[pos];
+        empties = 64 - __popcll(o | p); // (at most the root's, which is at most max_empties)
+        return true;
+    }
+
+    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
+    {
+        score[pos] = (int8_t)s.v;
+        move[pos] = (int8_t)s.root_move;
+        nodes[pos] = s.nodes;
+        done[pos] = 1;
+    }
+};
+
+// over the jobs of a split solve: their number read from ctl (none after an overflow of the job arrays)
+__global__ __launch_bounds__(WAVE) void endgame_jobs_kernel(EndgameJobParams P)
+{
+    extern __shared__ __align__(16) unsigned char stack_lds[];
+    const int64_t n = split_jobs_to_claim(P.ctl);
+    if ((int64_t)blockIdx.x * WAVE >= n) // nothing to claim: the wave leaves at once
+        return;
+    search_wave(P, SolverRules{P.wld}, n, 0, stack_lds);
 }
 
 // ---- iago_play_endgame: whole games from a late position to their end, both sides solving every turn
@@ -439,6 +499,78 @@ extern "C" int iago_solve_endgame_moves(const iago_endgame_moves_args *a, void *
     P.move_score = a->move_score;
     const void *kernel = all ? (const void *)endgame_moves_kernel<ALL> : (const void *)endgame_moves_kernel<BEST>;
     iago_search_launch(kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
+    return iago_check_launch(who);
+}
+
+extern "C" int iago_solve_endgame_split(const iago_endgame_split_args *a, void *stream)
+{
+    const char *who = "iago_solve_endgame_split";
+    if (!a)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null args");
+    if (a->n < 0 || a->n > INT32_MAX || (a->n > 0 && (!a->own || !a->opp || !a->job_count || !a->job_first)) || !a->ctl)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null pointer, negative n or n above 2^31 - 1");
+    if (a->mode != IAGO_ENDGAME_EXACT && a->mode != IAGO_ENDGAME_WLD)
+        return iago_fail(IAGO_ERR_INVALID,
+                         "iago_solve_endgame_split: mode must be IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD");
+    if (a->split < 1 || a->split > IAGO_ENDGAME_MAX_SPLIT)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: split must be 1 or 2");
+    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: max_empties must be in [0, 20]");
+    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: time_limit_ms must be in [1, 600000]");
+    if (a->job_capacity < 0 || a->job_capacity > INT32_MAX)
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: job_capacity must be in [0, 2^31 - 1]");
+    const int job_arrays = (a->job_own != nullptr) + (a->job_opp != nullptr) + (a->job_root != nullptr) +
+                           (a->job_path != nullptr) + (a->job_score != nullptr) + (a->job_move != nullptr) +
+                           (a->job_nodes != nullptr) + (a->job_done != nullptr);
+    if ((job_arrays != 0 && job_arrays != 8) || (job_arrays == 0 && a->job_capacity != 0))
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: the job arrays are all given, or all null with "
+                                           "job_capacity 0 (the count-only form)");
+    const bool count_only = job_arrays == 0;
+    if (!count_only && a->n > 0 && (!a->score || !a->move || !a->nodes || !a->solved))
+        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null score, move, nodes or solved");
+    for (int i = 0; i < 4; i++)
+        if (a->reserved[i] != 0)
+            return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: reserved fields must be 0");
+    static_assert(IAGO_ENDGAME_SPLIT_CTL_WORDS == SPLIT_CTL_WORDS && IAGO_ENDGAME_MAX_SPLIT == MAX_SPLIT, "lane_split.hpp");
+    hipStream_t s = (hipStream_t)stream;
+    int cus = 0;
+    const int rc = iago_search_prepare(who, a->ctl, IAGO_ENDGAME_SPLIT_CTL_WORDS, count_only ? nullptr : a->solved,
+                                       "solved", a->n, s, &cus);
+    if (rc != IAGO_OK || cus == 0)
+        return rc;
+    // every cell starts as "no move": the reduction writes the legal moves of the roots it answers
+    if (!count_only && a->move_score &&
+        hipMemsetAsync(a->move_score, IAGO_ENDGAME_NO_MOVE & 0xFF, (size_t)a->n * 64, s) != hipSuccess) {
+        (void)hipGetLastError();
+        return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame_split: clearing move_score");
+    }
+
+    // 1. expand: count, sum, write
+    split_expand(split_params_of(a, EmptiesJobs{a->max_empties}), count_only, s);
+    if (count_only)
+        return iago_check_launch(who);
+
+    // 2. search: the lanes of iago_solve_endgame over the jobs
+    EndgameJobParams J;
+    J.own = a->job_own;
+    J.opp = a->job_opp;
+    J.score = a->job_score;
+    J.move = a->job_move;
+    J.nodes = a->job_nodes;
+    J.done = a->job_done;
+    J.ctl = a->ctl;
+    J.wld = a->mode == IAGO_ENDGAME_WLD;
+    J.levels = stack_levels(a->max_empties); // the deepest job is a root that must pass: max_empties empties
+    J.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
+    iago_search_launch((const void *)endgame_jobs_kernel, &J, J.levels, Stack<SolverRules>::FRAME_BYTES,
+                       a->job_capacity, cus, s);
+
+    // 3. reduce
+    ReduceParams<EmptiesJobs> R = reduce_params_of<EmptiesJobs>(a, a->solved);
+    R.best = a->best;
+    R.move_score = a->move_score;
+    split_reduce(R, s);
     return iago_check_launch(who);
 }
 

@@ -2715,7 +2715,8 @@ def solve_endgame(own, opp, mode="exact", split_depth=0, time_limit_ms=ops.ENDGA
                 ctl=res["ctl"])
 
 
-def endgame_errors(own, opp, move, max_empties=_lib.ENDGAME_MAX_EMPTIES, mode="exact", time_limit_ms=ops.ENDGAME_TIME_LIMIT_MS):
+def endgame_errors(own, opp, move, max_empties=_lib.ENDGAME_MAX_EMPTIES, mode="exact", time_limit_ms=ops.ENDGAME_TIME_LIMIT_MS,
+                   split=0):
     """The loss against perfect play of moves actually played: how many discs (mode "wld": outcomes) each move gives
     away.  own / opp: (n,) int64 positions, own = the mover; move: (n,) integer tensor, the move played there.  Rows
     with move < 0 (a pass, no turn) or more than max_empties empties are skipped and counted; the others are solved in
@@ -2724,7 +2725,8 @@ def endgame_errors(own, opp, move, max_empties=_lib.ENDGAME_MAX_EMPTIES, mode="e
     value), played (the value of the move played), loss = score - played (>= 0), optimal (loss == 0) and blunder (the
     sign of the value changed: a win given away, or a draw turned into a loss); as Python numbers rows, skipped,
     mean_loss, optimal_rate and blunder_rate (nan without rows).  A move that is not legal is a ValueError naming the
-    row; a position the solver refuses (own & opp != 0) raises ops.solve_endgame_moves' IagoError."""
+    row; a position the solver refuses (own & opp != 0) raises ops.solve_endgame_moves' IagoError.  split (0, 1 or
+    2) goes to ops.solve_endgame_moves: the same answers with every root spread over the lanes."""
     n = own.numel()
     if opp.numel() != n or move.numel() != n:
         raise ValueError("endgame_errors: own / opp / move sizes differ")
@@ -2735,7 +2737,7 @@ def endgame_errors(own, opp, move, max_empties=_lib.ENDGAME_MAX_EMPTIES, mode="e
     keep = (move >= 0) & (_empties(own, opp) <= k)
     index = torch.nonzero(keep).reshape(-1)
     r = ops.solve_endgame_moves(own[index].contiguous(), opp[index].contiguous(), mode=mode, moves="all", max_empties=k,
-                                time_limit_ms=time_limit_ms)
+                                time_limit_ms=time_limit_ms, split=split)
     mv = move[index]
     played = r["move_score"].to(torch.int32).gather(1, mv.clamp(max=63).reshape(-1, 1)).reshape(-1)
     illegal = (played == _lib.ENDGAME_NO_MOVE) | (mv > 63)

@@ -1040,8 +1040,76 @@ def _check_endgame_ctl(out, n, max_empties, time_limit_ms, who="iago_solve_endga
         "%%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % max_empties)
 
 
+def endgame_split_arg(split):
+    """split of solve_endgame / solve_endgame_moves: 0 (no split), 1 or 2, returned as an int."""
+    if isinstance(split, bool) or not isinstance(split, numbers.Integral) or not 0 <= split <= _lib.ENDGAME_MAX_SPLIT:
+        raise ValueError("endgame split must be 0, 1 or 2, not %r" % (split,))
+    return int(split)
+
+
+def _job_capacity_arg(job_capacity):
+    if job_capacity is not None and (isinstance(job_capacity, bool) or not isinstance(job_capacity, numbers.Integral)
+                                     or not 0 <= job_capacity < 2 ** 31):
+        raise ValueError("job_capacity must be None or an int in [0, 2^31), not %r" % (job_capacity,))
+
+
+def _solve_endgame_split(own, opp, n, mode, moves, max_empties, split, time_limit_ms, job_capacity, check_result):
+    """solve_endgame / solve_endgame_moves with split > 0 (iago_solve_endgame_split).  moves: None, "best" or "all"."""
+    dev = own.device
+    lib = _lib.lib()
+    a = _lib.EndgameSplitArgs()
+    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
+    a.mode, a.split = ENDGAME_MODES[mode], split
+    a.max_empties, a.time_limit_ms = int(max_empties), int(time_limit_ms)
+    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
+               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
+               ctl=torch.empty(_lib.ENDGAME_SPLIT_CTL_WORDS, dtype=torch.int32, device=dev))
+    if moves is not None:
+        out["best"] = torch.empty(n, dtype=torch.int64, device=dev)
+    if moves == "all":
+        out["move_score"] = torch.empty((n, 64), dtype=torch.int8, device=dev)
+    out.update(job_count=torch.empty(n, dtype=torch.int32, device=dev),
+               job_first=torch.empty(n, dtype=torch.int64, device=dev))
+    a.job_count, a.job_first = _dev(out["job_count"], torch.int32, "job_count"), _dev(out["job_first"], torch.int64, "job_first")
+    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
+    if job_capacity is None:
+        # the count-only form and one readback: the arrays hold the jobs exactly
+        check(lib.iago_solve_endgame_split(C.byref(a), _stream()), "iago_solve_endgame_split")
+        job_capacity = alphabeta_job_count(out["ctl"].tolist())
+    cap = int(job_capacity)
+    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
+    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
+    if moves is not None:
+        a.best = _dev(out["best"], torch.int64, "best")
+    if moves == "all":
+        a.move_score = _dev(out["move_score"], torch.int8, "move_score")
+    a.job_capacity = cap
+    for k, dt, cols in (("job_own", torch.int64, 1), ("job_opp", torch.int64, 1), ("job_root", torch.int32, 1),
+                        ("job_path", torch.int8, 4), ("job_score", torch.int8, 1), ("job_move", torch.int8, 1),
+                        ("job_nodes", torch.int64, 1), ("job_done", torch.uint8, 1)):
+        # (an empty tensor has no address, and null arrays are the count-only form: room for one job at least)
+        t = torch.empty(max(cap, 1) * cols, dtype=dt, device=dev)
+        setattr(a, k, _dev(t, dt, k))
+        out[k] = t[:cap * cols].reshape(cap, 4) if cols == 4 else t[:cap]
+    out["job_capacity"] = cap
+    check(lib.iago_solve_endgame_split(C.byref(a), _stream()), "iago_solve_endgame_split")
+    if check_result:
+        ctl = out["ctl"].tolist()
+        out["jobs"] = alphabeta_job_count(ctl)
+        short = dict(first="the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap),
+                     jobs_needed=out["jobs"]) if ctl[6] else {}
+        _check_search_ctl(
+            "iago_solve_endgame_split", out, ctl,
+            "a job needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped and its root "
+            "keeps solved = 0" % max_empties,
+            lambda: "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
+                time_limit_ms, n - int(out["solved"].sum().item()), n),
+            "%%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % max_empties, **short)
+    return out
+
+
 def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS,
-                  check_result=True):
+                  check_result=True, split=0, job_capacity=None):
     """The exact value of every position under perfect play (iago_solve_endgame, include/iago_hip_serving.h).
 
     own / opp: (n,) int64 CUDA tensors, own = side to move.  mode "exact": score = the final disc difference
@@ -1050,12 +1118,27 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     pass, -2: the game is over), nodes (n,) int64, solved (n,) uint8, ctl (4,) int32.
     check_result (one host sync): raise IagoError when the launch gave up at time_limit_ms, refused a position
     (own & opp != 0, more than max_empties empties) or dropped one for want of stack (ctl[3]); the result is the
-    error's `result` attribute."""
+    error's `result` attribute.
+
+    split = 1 or 2 (0, the default: the call above, argument for argument; anything else is a ValueError): the same
+    score, move and solved from iago_solve_endgame_split, which spreads every root's search over the lanes -- the first
+    `split` plies expanded into jobs on the device, the jobs solved a lane each with the full window, their values taken
+    back per root.  nodes is then the nodes expanded + the jobs' own.  job_capacity: the jobs the launch has room for;
+    None takes a count-only launch and one readback first and allocates exactly, an int takes no readback -- where the
+    jobs do not fit nothing is searched, every solved is 0, ctl[6] is set, and check_result raises an IagoError with the
+    count needed in `jobs_needed`.  The dict then also holds ctl (8,) int32 (ctl[4] / [5]: the jobs needed), job_count
+    (n,) int32, job_first (n,) int64, the job arrays job_own, job_opp, job_root, job_path (the job's empties, first
+    move, second move, 0), job_score, job_move, job_nodes, job_done, job_capacity and, with check_result, `jobs`."""
     if mode not in ENDGAME_MODES:
         raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
+    split = endgame_split_arg(split)
+    _job_capacity_arg(job_capacity)
     n = own.numel()
     if opp.numel() != n:
         raise ValueError("own/opp sizes differ")
+    if split:
+        return _solve_endgame_split(own, opp, n, mode, None, max_empties, split, time_limit_ms, job_capacity,
+                                    check_result)
     dev = own.device
     out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
                nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
@@ -1076,21 +1159,28 @@ ENDGAME_MOVES = {"best": _lib.ENDGAME_MOVES_BEST, "all": _lib.ENDGAME_MOVES_ALL}
 
 
 def solve_endgame_moves(own, opp, mode="exact", moves="best", max_empties=_lib.ENDGAME_MAX_EMPTIES,
-                        time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True):
+                        time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True, split=0, job_capacity=None):
     """solve_endgame with EVERY optimal move (iago_solve_endgame_moves, include/iago_hip_serving.h).
 
     Returns solve_endgame's dict (score and move are its own, bit for bit) plus best (n,) int64: bit a set iff move a
     reaches the score (0: the mover must pass, the game is over, the position was refused).  moves "best": the set
     alone (about 1.1 x solve_endgame's nodes); "all": every legal move is searched with the full window, and
     move_score (n, 64) int8 holds the value of move a from the mover's view, -128 (IAGO_ENDGAME_NO_MOVE) on every cell
-    that is no legal move of the mover (about 2.2 x the nodes).  check_result: as in solve_endgame."""
+    that is no legal move of the mover (about 2.2 x the nodes).  check_result: as in solve_endgame.
+    split = 1 or 2, job_capacity: as in solve_endgame -- the same best and move_score from iago_solve_endgame_split,
+    whose jobs know every root move's exact value under either `moves`; the dict also holds its job arrays."""
     if mode not in ENDGAME_MODES:
         raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
     if moves not in ENDGAME_MOVES:
         raise ValueError("moves must be 'best' or 'all', got %r" % (moves,))
+    split = endgame_split_arg(split)
+    _job_capacity_arg(job_capacity)
     n = own.numel()
     if opp.numel() != n:
         raise ValueError("own/opp sizes differ")
+    if split:
+        return _solve_endgame_split(own, opp, n, mode, moves, max_empties, split, time_limit_ms, job_capacity,
+                                    check_result)
     dev = own.device
     out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
                nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
@@ -1282,9 +1372,7 @@ def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_
     move, second move, 0), job_score, job_move, job_nodes, job_done, job_capacity and, with check_result, `jobs`."""
     depth = alphabeta_depth_arg(depth)
     split = alphabeta_split_arg(split, depth)
-    if job_capacity is not None and (isinstance(job_capacity, bool) or not isinstance(job_capacity, numbers.Integral)
-                                     or not 0 <= job_capacity < 2 ** 31):
-        raise ValueError("job_capacity must be None or an int in [0, 2^31), not %r" % (job_capacity,))
+    _job_capacity_arg(job_capacity)
     n = own.numel()
     if opp.numel() != n:
         raise ValueError("own/opp sizes differ")

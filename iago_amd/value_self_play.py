@@ -34,7 +34,7 @@ def _softmax_like_reference(out):
 
 
 def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0, draws=None,
-             device="cuda", exact_empties=None):
+             device="cuda", exact_empties=None, exact_split=0):
     """n_games lockstep games.  stop_num: (n_games,) ints in [4, 64] (None: drawn uniformly
     from {4..63} like gen_value_data.py:14, from a generator seeded with `seed`).
     draws: replay mode for ONE game (parity tests): an iterator of the uniforms consumed, in
@@ -47,10 +47,12 @@ def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0,
     exact_empties = k (an int <= 20) adds exact labels: every kept recorded position with at most k empties is solved
     (ops.solve_endgame, win / draw / loss) after the games; z_exact (B,) int8 = its result under perfect play from the
     recorded side's view, exact (B,) bool = where z_exact applies (dropped games: False).  The other keys stay what a
-    call without it returns."""
+    call without it returns.  exact_split (0, 1 or 2) is that call's split: the same labels, every position spread
+    over the lanes."""
     if exact_empties is not None and (isinstance(exact_empties, bool) or not isinstance(exact_empties, int) or
                                       not 0 <= exact_empties <= ops._lib.ENDGAME_MAX_EMPTIES):
         raise ValueError("exact_empties must be None or an int in [0, 20], got %r" % (exact_empties,))
+    exact_split = ops.endgame_split_arg(exact_split)
     B = n_games
     if draws is not None and B != 1:
         raise ValueError("replay mode (draws) plays one game")
@@ -163,7 +165,7 @@ def generate(model_sl, model_rl, n_games, stop_num=None, seed=0, game_id_base=0,
         rows = torch.nonzero(exact).reshape(-1)
         if rows.numel():
             r = ops.solve_endgame(rec_own[rows].contiguous(), rec_opp[rows].contiguous(), mode="wld",
-                                  max_empties=exact_empties)
+                                  max_empties=exact_empties, split=exact_split)
             z_exact[rows] = r["score"]
         out.update(z_exact=z_exact, exact=exact)
     return out

@@ -212,6 +212,74 @@ typedef struct iago_endgame_moves_args {
  */
 IAGO_API int iago_solve_endgame_moves(const iago_endgame_moves_args *args, void *stream);
 
+#define IAGO_ENDGAME_MAX_SPLIT 2
+#define IAGO_ENDGAME_SPLIT_CTL_WORDS 8
+
+typedef struct iago_endgame_split_args {
+    const uint64_t *own; /* [n] side to move (bit a = row*8+col) */
+    const uint64_t *opp; /* [n] its opponent */
+    int64_t n;           /* at most 2^31 - 1 */
+    int32_t mode;          /* IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD */
+    int32_t split;         /* 1 .. IAGO_ENDGAME_MAX_SPLIT: the plies expanded into jobs */
+    int32_t max_empties;   /* 0 .. IAGO_ENDGAME_MAX_EMPTIES: sizes the search stack; a root with more empties is refused */
+    int32_t time_limit_ms; /* 1 .. IAGO_ENDGAME_MAX_TIME_MS, of the search stage */
+    int8_t *score;         /* [n] out */
+    int8_t *move;          /* [n] out */
+    int64_t *nodes;        /* [n] out */
+    uint8_t *solved;       /* [n] out: 1 = every job of the root finished, the outputs of root i are exact */
+    uint64_t *best;        /* [n] out, or NULL (not wanted): bit a set iff move a reaches score[i] */
+    int8_t *move_score;    /* [n][64] out, or NULL (not wanted): the value of move a from the mover's view */
+    int32_t *job_count;    /* [n] out: the jobs of root i */
+    int64_t *job_first;    /* [n] out: the index of its first job (the exclusive sum of job_count) */
+    int64_t job_capacity;  /* the jobs the arrays below hold, at most 2^31 - 1 */
+    uint64_t *job_own;     /* [job_capacity] out: the job's side to move */
+    uint64_t *job_opp;     /* [job_capacity] out */
+    int32_t *job_root;     /* [job_capacity] out: the root it belongs to */
+    int8_t *job_path;      /* [job_capacity][4] out: the job's empties, first move, second move (-1 where absent), 0 */
+    int8_t *job_score;     /* [job_capacity] out: iago_solve_endgame's score of (job_own, job_opp) */
+    int8_t *job_move;      /* [job_capacity] out: its move */
+    int64_t *job_nodes;    /* [job_capacity] out: its nodes */
+    uint8_t *job_done;     /* [job_capacity] out */
+    uint32_t *ctl;         /* [IAGO_ENDGAME_SPLIT_CTL_WORDS] cleared by the call; [0] != 0: gave up, [1]: the claim
+                              counter, [2]: roots refused, [3] != 0: a stack overflow, [4] / [5]: the low / high word of
+                              the jobs needed, [6] != 0: they exceed job_capacity (nothing was searched), [7]: 0 */
+    int64_t reserved[4];   /* 0 */
+} iago_endgame_split_args;
+
+/*
+ * iago_solve_endgame with every root's search spread over many lanes -- the solver's counterpart of
+ * iago_alphabeta_moves_split below, with the same three stages, each a launch of its own on `stream` and no host round
+ * trip between them: score[i], move[i] and solved[i] are iago_solve_endgame's, bit for bit, in both modes.  The rule: a
+ * node (own, opp) with k split plies left (the root: split)
+ *   - is a JOB when k == 0 or its mover has no legal move: its (score, move, nodes) are what iago_solve_endgame
+ *     returns for that position in the launch's mode, found with the full window on a stack of its own empties;
+ *   - is EXPANDED otherwise: its children are its legal moves in ascending index, each with k - 1, its value the
+ *     maximum of the negated children's values.
+ * So a root that must pass or whose game is over is its own job (move -1 / -2), a child that cannot move -- it must
+ * pass, or the game is over -- is one job, and a root with fewer empties than split plies ends in finished-game jobs:
+ * split never has to be below the empties.  move[i] is the lowest-indexed move whose value equals score[i]; nodes[i] =
+ * the nodes expanded (1 for the root, 1 per expanded child; a root that is its own job: none) + the sum of its jobs'
+ * nodes, so it depends on no timing.  Every first move of an expanded root has its exact value here, so two optional
+ * outputs come for free, and equal iago_solve_endgame_moves' under BEST / ALL: best[i] = the set of the moves reaching
+ * score[i]; move_score[i][a] = the value of move a, IAGO_ENDGAME_NO_MOVE on every other cell (the call fills the array
+ * on `stream` before the launches).  A passing root, a finished game and a refused root: best 0, the whole row
+ * IAGO_ENDGAME_NO_MOVE.
+ * The stages: (1) the jobs of every root are counted (job_count), summed (job_first; ctl[4] / [5] = their total) and
+ * written in canonical order -- root ascending, then first move, then second move; (2) the lanes of iago_solve_endgame's
+ * search claim jobs one at a time; (3) a thread per root takes its run of jobs back, the sign turned once per ply of the
+ * path.  More jobs than job_capacity: ctl[6] is set, nothing is searched, every solved[i] stays 0 and nothing is written
+ * past the capacity.  The COUNT-ONLY form -- every job_* array null and job_capacity 0 -- writes job_count, job_first
+ * and ctl[4] / [5] and launches nothing else (score, move, nodes, solved, best and move_score are not touched and may be
+ * null; ctl[6] stays 0).  A root with own & opp != 0 or more than max_empties empties is refused: ctl[2] counts it, it
+ * has no job, solved[i] = 0 (score, move, nodes and best 0).  The give-up is the search stage's: ctl[0] != 0, and a root
+ * with an unfinished job keeps solved[i] = 0 and is not written.  Host-side refusals (IAGO_ERR_INVALID, nothing
+ * launched): a null args / ctl / own / opp / job_count / job_first with n > 0, n < 0 or above 2^31 - 1, a mode outside
+ * the two, a split outside 1 .. IAGO_ENDGAME_MAX_SPLIT, a max_empties or time_limit_ms out of range, a job_capacity below
+ * 0 or above 2^31 - 1, some but not all job_* arrays null or null ones with a capacity, a null score / move / nodes /
+ * solved outside the count-only form, reserved fields not 0.
+ */
+IAGO_API int iago_solve_endgame_split(const iago_endgame_split_args *args, void *stream);
+
 typedef struct iago_play_endgame_moves_args {
     iago_play_endgame_args play; /* iago_play_endgame's arguments, read as it reads them */
     uint64_t *rec_best;          /* [max_turns][stride] out: the BEST set of every solved turn, 0 where valid is 0 */
