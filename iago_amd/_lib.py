@@ -67,9 +67,12 @@ SERVING_SYMBOLS = [
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
 # (network.SLPolicy.visits_grads, train_rl.ReinforceTrainer.step_from_tuples(target="visits")), minibatches out of a
-# replay window of self-play rows in random board symmetries (ops.replay_sample, replay.ReplayWindow)
+# replay window of self-play rows in random board symmetries (ops.replay_sample, replay.ReplayWindow), the rows'
+# canonical forms, the window merged by position up to symmetry and minibatches out of the merged rows
+# (ops.canonical_rows, ops.replay_merge, ops.replay_sample_merged, ReplayWindow.merge / sample(merged=))
 TRAINING_SYMBOLS = [
     "iago_value_grad_workspace_bytes", "iago_value_mse_grad", "iago_policy_visits_grad", "iago_replay_sample",
+    "iago_canonical_rows", "iago_replay_merge", "iago_replay_sample_merged",
 ]
 
 
@@ -160,6 +163,34 @@ class ReplaySampleArgs(C.Structure):
         ("own_out", C.c_void_p), ("opp_out", C.c_void_p), ("pi_out", C.c_void_p), ("move_out", C.c_void_p),
         ("z_out", C.c_void_p), ("result_out", C.c_void_p), ("slot_out", C.c_void_p), ("sym_out", C.c_void_p),
         ("flags", C.c_void_p),
+    ]
+
+
+REPLAY_MERGE_BAD_INPUT = 1   # bits of iago_replay_merge's flags: an order / group / slot the device refused,
+REPLAY_MERGE_OVERFLOW = 2    # a summed cell or z_sum left int32 (stored clamped)
+REPLAY_MERGED_MODES = {"unique": 0, "rows": 1}   # iago_replay_sample_merged's mode
+
+
+class ReplayMergeArgs(C.Structure):
+    """Mirror of iago_replay_merge_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("c_own", C.c_void_p), ("c_opp", C.c_void_p), ("sym", C.c_void_p), ("pi", C.c_void_p), ("z", C.c_void_p),
+        ("count", C.c_int64), ("order", C.c_void_p), ("group", C.c_void_p),
+        ("own_out", C.c_void_p), ("opp_out", C.c_void_p), ("pi_out", C.c_void_p), ("z_sum", C.c_void_p),
+        ("mult", C.c_void_p), ("first", C.c_void_p), ("workspace", C.c_void_p), ("n_unique", C.c_void_p),
+        ("flags", C.c_void_p),
+    ]
+
+
+class ReplaySampleMergedArgs(C.Structure):
+    """Mirror of iago_replay_sample_merged_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("own", C.c_void_p), ("opp", C.c_void_p), ("pi", C.c_void_p), ("z_sum", C.c_void_p), ("mult", C.c_void_p),
+        ("first", C.c_void_p),
+        ("n_unique", C.c_int64), ("count", C.c_int64), ("n", C.c_int64),
+        ("seed", C.c_uint64), ("step", C.c_uint32), ("mode", C.c_int32),
+        ("own_out", C.c_void_p), ("opp_out", C.c_void_p), ("pi_out", C.c_void_p), ("result_out", C.c_void_p),
+        ("z_sum_out", C.c_void_p), ("mult_out", C.c_void_p), ("group_out", C.c_void_p), ("sym_out", C.c_void_p),
     ]
 
 
@@ -506,6 +537,9 @@ def lib():
     L.iago_value_mse_grad.argtypes = [C.POINTER(ValueGradArgs), vp]
     L.iago_policy_visits_grad.argtypes = [C.POINTER(PolicyVisitsGradArgs), vp]
     L.iago_replay_sample.argtypes = [C.POINTER(ReplaySampleArgs), vp]
+    L.iago_canonical_rows.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.iago_replay_merge.argtypes = [C.POINTER(ReplayMergeArgs), vp]
+    L.iago_replay_sample_merged.argtypes = [C.POINTER(ReplaySampleMergedArgs), vp]
     L.iago_split_nchw.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.iago_merge_nchw.argtypes = [vp, vp, vp, i64, i32, vp]
     L.iago_value_stem.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]

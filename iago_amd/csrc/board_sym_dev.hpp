@@ -1,5 +1,6 @@
 // board_sym_dev.hpp -- the board's symmetries on a bitboard and on a cell index (bit a = row*8+col): the two generators
-// of iago_augment8's eight variants (rules_kernels.hip) and of iago_replay_sample's (replay_kernels.hip).
+// of iago_augment8's eight variants (rules_kernels.hip) and of iago_replay_sample's (replay_kernels.hip), and the
+// canonical form of a position under them (iago_canonical_rows, iago_replay_merge).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,36 @@ __device__ __forceinline__ int act_variant_inverse(int d, int k)
     for (int i = 0; i < turns; i++)
         d = act_rot90(d);
     return k < 4 ? d : act_rot90(act_transpose(d));
+}
+
+// The canonical form of a position (iago_canonical_rows): of the eight pairs (bb_variant(own, k), bb_variant(opp, k))
+// the smallest, own compared first, then opp, both as unsigned 64-bit; returns the lowest k that gives it and leaves
+// that pair in own / opp.  The chain of bb_variant walked once: a strict "smaller" keeps the lowest k of a tie.
+__device__ __forceinline__ int bb_canonical(uint64_t &own, uint64_t &opp)
+{
+    uint64_t o = own, p = opp, best_o = own, best_p = opp;
+    int best = 0;
+    for (int k = 1; k < 8; k++) {
+        o = (k == 4) ? bb_transpose(o) : bb_rot90(o);
+        p = (k == 4) ? bb_transpose(p) : bb_rot90(p);
+        if (o < best_o || (o == best_o && p < best_p)) {
+            best_o = o;
+            best_p = p;
+            best = k;
+        }
+    }
+    own = best_o;
+    opp = best_p;
+    return best;
+}
+// act_variant_inverse(d, k) for all eight k at once, byte k of the result: a lane that turns many rows by varying k
+// picks its source cell with one shift (a register array indexed by k would go to scratch).
+__device__ __forceinline__ uint64_t act_variant_inverse_all(int d)
+{
+    uint64_t packed = 0ull;
+    for (int k = 0; k < 8; k++)
+        packed |= (uint64_t)act_variant_inverse(d, k) << (8 * k);
+    return packed;
 }
 
 } // namespace iago

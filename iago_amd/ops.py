@@ -188,6 +188,104 @@ def replay_sample(own, opp, pi, move, z, count, n=None, seed=0, step=0, slot=Non
     return out
 
 
+def canonical_rows(own, opp):
+    """iago_canonical_rows (include/iago_hip_training.h): per row the smallest of the eight pairs (variant k of own,
+    variant k of opp) -- own compared first, then opp, as unsigned 64-bit -- and the lowest k that gives it.  Returns
+    (c_own, c_opp) int64 and sym uint8; every symmetry of a position has the same (c_own, c_opp)."""
+    n = own.numel()
+    if opp.numel() != n:
+        raise ValueError("canonical_rows: opp has %d entries, own has %d" % (opp.numel(), n))
+    c_own, c_opp = torch.empty_like(own), torch.empty_like(opp)
+    sym = torch.empty(n, dtype=torch.uint8, device=own.device)
+    check(_lib.lib().iago_canonical_rows(_dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n,
+                                         c_own.data_ptr(), c_opp.data_ptr(), sym.data_ptr(), _stream()),
+          "iago_canonical_rows")
+    return c_own, c_opp, sym
+
+
+def _unsigned_order(x):
+    """int64 bit patterns as keys whose signed order is the patterns' unsigned order."""
+    return x ^ torch.iinfo(torch.int64).min
+
+
+def replay_merge(own, opp, pi, z, count, meta=None):
+    """iago_replay_merge (include/iago_hip_training.h) over the filled slots 0 .. count-1 of the window own / opp
+    (capacity,) int64, pi (capacity, 64) int32, z (capacity,) int8: the rows canonicalised (canonical_rows), ordered
+    by (c_own, c_opp) as unsigned -- two stable sorts, torch's -- and summed per distinct position on the device.
+    meta: optional int32 (2,) tensor, cleared here: [0] receives n_unique, [1] the flags (_lib.REPLAY_MERGE_*).
+    Returns a dict own, opp (count,), pi (count, 64) int32, z_sum, mult int32, first int64 -- count-sized buffers
+    whose first n_unique entries are the groups, in ascending (own, opp) -- and meta.  Nothing is read back."""
+    capacity, count = own.numel(), int(count)
+    for name, t in (("opp", opp), ("z", z)):
+        if t.numel() != capacity:
+            raise ValueError("replay_merge: %s has %d entries, own has %d" % (name, t.numel(), capacity))
+    if pi.dim() != 2 or tuple(pi.shape) != (capacity, 64):
+        raise ValueError("replay_merge: pi must be (%d, 64), got %s" % (capacity, tuple(pi.shape)))
+    if not 1 <= count <= capacity:
+        raise ValueError("replay_merge: need 1 <= count <= %d, got %d" % (capacity, count))
+    dev = own.device
+    c_own, c_opp, sym = canonical_rows(own[:count], opp[:count])
+    by_opp = torch.sort(_unsigned_order(c_opp), stable=True)[1]
+    order = by_opp[torch.sort(_unsigned_order(c_own)[by_opp], stable=True)[1]]
+    so, sp = c_own[order], c_opp[order]
+    head = torch.ones(count, dtype=torch.int32, device=dev)
+    head[1:] = ((so[1:] != so[:-1]) | (sp[1:] != sp[:-1])).to(torch.int32)
+    group = (torch.cumsum(head, 0) - 1).to(torch.int32)
+    order = order.to(torch.int32)
+    if meta is None:
+        meta = torch.empty(2, dtype=torch.int32, device=dev)
+    meta.zero_()
+    out = dict(own=torch.empty(count, dtype=torch.int64, device=dev), opp=torch.empty(count, dtype=torch.int64, device=dev),
+               pi=torch.empty((count, 64), dtype=torch.int32, device=dev),
+               z_sum=torch.empty(count, dtype=torch.int32, device=dev), mult=torch.empty(count, dtype=torch.int32, device=dev),
+               first=torch.empty(count, dtype=torch.int64, device=dev), meta=meta)
+    a = _lib.ReplayMergeArgs()
+    a.c_own, a.c_opp, a.sym = c_own.data_ptr(), c_opp.data_ptr(), sym.data_ptr()
+    a.pi, a.z, a.count = _dev(pi, torch.int32, "pi"), _dev(z, torch.int8, "z"), count
+    a.order, a.group = _dev(order, torch.int32, "order"), _dev(group, torch.int32, "group")
+    a.own_out, a.opp_out, a.pi_out = out["own"].data_ptr(), out["opp"].data_ptr(), out["pi"].data_ptr()
+    a.z_sum, a.mult, a.first = out["z_sum"].data_ptr(), out["mult"].data_ptr(), out["first"].data_ptr()
+    _dev(meta, torch.int32, "meta")
+    a.n_unique, a.flags = meta.data_ptr(), meta.data_ptr() + 4
+    workspace = torch.empty(count, dtype=torch.int64, device=dev)   # (the large groups' 64-bit sums: cleared by the call)
+    a.workspace = workspace.data_ptr()
+    check(_lib.lib().iago_replay_merge(C.byref(a), _stream()), "iago_replay_merge")
+    return out
+
+
+def replay_sample_merged(own, opp, pi, z_sum, mult, first, count, n, seed=0, step=0, mode="unique"):
+    """iago_replay_sample_merged (include/iago_hip_training.h): n rows out of the n_unique = own.numel() merged rows
+    of a window of count rows, every row in one of the board's eight symmetries.  Row j's group and variant are drawn
+    from replay_sample's Philox stream on (j, step): mode "unique" uniformly over the groups, "rows" uniformly over
+    the window's rows (the group that holds the row, by first).  Returns a dict own, opp, pi (int32 sums), result
+    (float32 z_sum / mult), z_sum, mult, group, sym."""
+    if mode not in _lib.REPLAY_MERGED_MODES:
+        raise ValueError("replay_sample_merged: mode must be 'unique' or 'rows', got %r" % (mode,))
+    groups, n = own.numel(), int(n)
+    for name, t in (("opp", opp), ("z_sum", z_sum), ("mult", mult), ("first", first)):
+        if t.numel() != groups:
+            raise ValueError("replay_sample_merged: %s has %d entries, own has %d" % (name, t.numel(), groups))
+    if pi.dim() != 2 or tuple(pi.shape) != (groups, 64):
+        raise ValueError("replay_sample_merged: pi must be (%d, 64), got %s" % (groups, tuple(pi.shape)))
+    dev = own.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(own=torch.empty(n, dtype=torch.int64, device=dev), opp=torch.empty(n, dtype=torch.int64, device=dev),
+               pi=torch.empty((n, 64), **i32), result=torch.empty(n, dtype=torch.float32, device=dev),
+               z_sum=torch.empty(n, **i32), mult=torch.empty(n, **i32), group=torch.empty(n, **i32),
+               sym=torch.empty(n, dtype=torch.uint8, device=dev))
+    a = _lib.ReplaySampleMergedArgs()
+    a.own, a.opp, a.pi = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), _dev(pi, torch.int32, "pi")
+    a.z_sum, a.mult = _dev(z_sum, torch.int32, "z_sum"), _dev(mult, torch.int32, "mult")
+    a.first = _dev(first, torch.int64, "first")
+    a.n_unique, a.count, a.n = groups, int(count), n
+    a.seed, a.step, a.mode = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _lib.REPLAY_MERGED_MODES[mode]
+    a.own_out, a.opp_out, a.pi_out = out["own"].data_ptr(), out["opp"].data_ptr(), out["pi"].data_ptr()
+    a.result_out, a.z_sum_out, a.mult_out = out["result"].data_ptr(), out["z_sum"].data_ptr(), out["mult"].data_ptr()
+    a.group_out, a.sym_out = out["group"].data_ptr(), out["sym"].data_ptr()
+    check(_lib.lib().iago_replay_sample_merged(C.byref(a), _stream()), "iago_replay_sample_merged")
+    return out
+
+
 def augment8_visits(own, opp, action, pi):
     """ops.augment8 with the rows' visit counts: (8, n) own, opp (int64) and action (int8) in augment8's layout, and
     (8, n, 64) int32 visit rows -- pi[v, i, m_v(a)] = pi[i, a].  iago_replay_sample's given mode over the n rows as a

@@ -8,12 +8,31 @@ need the GPU: one launch draws the rows, with replacement, and turns each into o
 position, visit row and move together.  The draw is in integers and keyed by Philox on (row of the minibatch, step)
 under the window's seed: it depends on nothing else, so the ranks of a multi-GPU run, whose windows hold the same rows
 in the same slots (train_rl.ReinforceTrainer.add_to_window), draw the same minibatch.
+
+Self-play repeats itself: every game opens on the same position, and after one ply there is one position up to the
+board's symmetries.  `merge` groups the rows by canonical position (iago_canonical_rows: the smallest of the eight
+variants), sums each group's visit rows in the canonical frame and its results (iago_replay_merge), and
+`sample(merged="unique" | "rows")` draws out of those groups (iago_replay_sample_merged): the targets of a position are
+then the sum of its searches and its measured mean result, not one noisy copy of either.
 """
 import torch
 
 from . import _lib, ops
 
 COLUMNS = (("own", torch.int64), ("opp", torch.int64), ("pi", torch.int32), ("move", torch.int8), ("z", torch.int8))
+MERGED_COLUMNS = ("own", "opp", "pi", "z_sum", "mult", "first")
+
+
+class MergedRows(object):
+    """A window merged by position up to symmetry (ReplayWindow.merge, iago_replay_merge): n_unique groups, one per
+    distinct canonical position, in ascending (own, opp) as unsigned 64-bit.  own / opp: the canonical boards; pi
+    (n_unique, 64) int32: the group's visit rows, each turned into the canonical frame, summed; z_sum int32: its
+    results summed; mult int32: its rows; first int64: the exclusive prefix sum of mult.  count / total: the window's
+    when the snapshot was taken."""
+
+    def __init__(self, n_unique, count, total, own, opp, pi, z_sum, mult, first):
+        self.n_unique, self.count, self.total = int(n_unique), int(count), int(total)
+        self.own, self.opp, self.pi, self.z_sum, self.mult, self.first = own, opp, pi, z_sum, mult, first
 
 
 class ReplayWindow(object):
@@ -29,6 +48,7 @@ class ReplayWindow(object):
         self.cols = {k: torch.zeros((capacity, 64) if k == "pi" else (capacity,), dtype=dt, device=self.device)
                      for k, dt in COLUMNS}
         self._flags = None
+        self._merged = None
 
     @property
     def count(self):
@@ -67,14 +87,49 @@ class ReplayWindow(object):
                                  "those rows came back as zeros" % self.count)
         return out
 
-    def sample(self, n, step=None):
-        """n rows drawn with replacement, each in a drawn symmetry: a dict own, opp, pi, move, z, result (float32 z, the
-        Value net's label), slot, sym.  step None: the window's own counter, which then advances by one."""
+    def merge(self):
+        """The filled slots merged by position up to symmetry (iago_replay_merge): a MergedRows snapshot of the window
+        as it stands, one row per distinct canonical position.  One readback, of n_unique and the flags.  A summed
+        cell beyond int32 raises IagoError."""
         self._not_empty()
+        c = self.cols
+        m = ops.replay_merge(c["own"], c["opp"], c["pi"], c["z"], self.count)
+        n_unique, flags = m["meta"].tolist()
+        if flags & _lib.REPLAY_MERGE_OVERFLOW:
+            raise _lib.IagoError("ReplayWindow.merge: a summed visit count or result left int32 (2^31 - 1)")
+        if flags or not 1 <= n_unique <= self.count:
+            raise _lib.IagoError("ReplayWindow.merge: the device refused the rows' order (flags %d, %d groups)"
+                                 % (flags, n_unique))
+        return MergedRows(n_unique=n_unique, count=self.count, total=self.total,
+                          **{k: m[k][:n_unique] for k in MERGED_COLUMNS})
+
+    def merged(self):
+        """merge(), kept until rows are added: the snapshot the merged draws read."""
+        if self._merged is None or self._merged.total != self.total:
+            self._merged = None   # (the old snapshot's buffers go before the new one's are made)
+            self._merged = self.merge()
+        return self._merged
+
+    def sample(self, n, step=None, merged=None):
+        """n rows drawn with replacement, each in a drawn symmetry: a dict own, opp, pi, move, z, result (float32 z, the
+        Value net's label), slot, sym.  step None: the window's own counter, which then advances by one.
+
+        merged = "unique" or "rows" draws out of the window merged by position up to symmetry (merged(): rebuilt on
+        the first such draw after rows were added) with iago_replay_sample_merged, under the same key and counter:
+        "unique" uniformly over the distinct positions, "rows" uniformly over the window's rows, each standing for
+        its position.  The dict is then own, opp, pi (the position's summed visit rows, int32), result (float32, the
+        mean of its rows' z), z_sum, mult, group, sym: a merged row has no move and no z."""
+        if merged not in (None, "unique", "rows"):
+            raise ValueError("ReplayWindow.sample: merged must be None, 'unique' or 'rows', got %r" % (merged,))
+        self._not_empty()
+        m = self.merged() if merged is not None else None
         if step is None:
             step = self.step
             self.step += 1
-        return self._run(int(n), step, None, None)
+        if m is None:
+            return self._run(int(n), step, None, None)
+        return ops.replay_sample_merged(m.own, m.opp, m.pi, m.z_sum, m.mult, m.first, m.count, n, seed=self.seed,
+                                        step=step, mode=merged)
 
     def gather(self, slot, sym):
         """The rows of the given slots in the given variants: slot (n,) integers or a tensor, sym the same or one int

@@ -421,15 +421,24 @@ class ReinforceTrainer(object):
         g = self._gather_rows(tup, colour, with_pi=True, who="add_to_window")
         return window.add(dict(own=g["own"], opp=g["opp"], pi=g["pi"], move=g["action"], z=g["z"]))
 
-    def step_from_window(self, window, n_rows, target="visits", step=None):
+    def step_from_window(self, window, n_rows, target="visits", step=None, merged=None):
         """One update from n_rows rows drawn out of the window (ReplayWindow.sample: with replacement, each row in a
         drawn board symmetry; step None = the window's own counter).  No gather: every rank's window holds the same
         rows and the draw does not depend on the rank.  target as step_from_tuples.  Returns dict(loss, n_tuples,
-        step), with kl (on the sampled rows) for target = "visits"."""
+        step), with kl (on the sampled rows) for target = "visits".
+
+        merged = "unique" or "rows" (ReplayWindow.sample's): the rows are positions of the window merged up to
+        symmetry, pi the sum of a position's visit rows -- the update normalises every row, so the sum is the mean
+        weighted by playouts.  A merged row has no move: target = "move" is then a ValueError."""
         if target not in ("move", "visits"):
             raise ValueError("step_from_window: target must be 'move' or 'visits', got %r" % (target,))
+        if merged not in (None, "unique", "rows"):
+            raise ValueError("step_from_window: merged must be None, 'unique' or 'rows', got %r" % (merged,))
+        if merged is not None and target != "visits":
+            raise ValueError("step_from_window: merged rows carry no move, target must be 'visits' with merged=%r"
+                             % (merged,))
         used = window.step if step is None else step
-        rows = window.sample(n_rows, step=step)
+        rows = window.sample(n_rows, step=step) if merged is None else window.sample(n_rows, step=step, merged=merged)
         if target == "visits":
             loss = self._update_visits(rows["own"], rows["opp"], rows["pi"])
             out = dict(loss=float(loss.item()), n_tuples=int(n_rows), step=int(used))

@@ -1,7 +1,8 @@
 /*
  * iago_hip_training.h -- training the nets on the library's own kernels: the supervised update of the Value net
- * (train_value.py), SLPolicy on the search's visit counts, minibatches out of a replay window of self-play rows.  Same
- * conventions as iago_hip.h; part of the library's ABI (iago_abi_version).
+ * (train_value.py), SLPolicy on the search's visit counts, minibatches out of a replay window of self-play rows, and
+ * that window merged by position up to the board's symmetries.  Same conventions as iago_hip.h; part of the library's
+ * ABI (iago_abi_version).
  */
 #ifndef IAGO_HIP_TRAINING_H
 #define IAGO_HIP_TRAINING_H
@@ -135,6 +136,92 @@ typedef struct iago_replay_sample_args {
     uint32_t *flags;
 } iago_replay_sample_args;
 IAGO_API int iago_replay_sample(const iago_replay_sample_args *args, void *stream);
+
+/*
+ * iago_canonical_rows: the canonical form of n rows (own, opp), the one name all eight symmetries of a position share.
+ *   With bb_k the board of variant k (iago_augment8's variants, in its order, as iago_replay_sample turns boards):
+ *     k* = the lowest k in 0 .. 7 whose pair (bb_k(own), bb_k(opp)) is smallest -- own compared first, then opp, both
+ *     as unsigned 64-bit;  c_own / c_opp [n] = that pair,  sym [n] (uint8) = k*.
+ *   Rows are mover-relative (own = the mover), so colour plays no part.  Integers only, one thread per row.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL pointer or n <= 0.
+ */
+IAGO_API int iago_canonical_rows(const uint64_t *own, const uint64_t *opp, int64_t n, uint64_t *c_own, uint64_t *c_opp,
+                                 uint8_t *sym, void *stream);
+
+/*
+ * iago_replay_merge: the filled slots 0 .. count-1 of a replay window merged by position up to symmetry.  A group is
+ *   one distinct canonical pair (c_own, c_opp); groups are numbered in ascending (c_own, c_opp), compared as unsigned.
+ *   The caller canonicalises (iago_canonical_rows over the window: c_own / c_opp / sym, by slot) and orders:
+ *     order [count] int32: the slots in ascending (c_own, c_opp) (ties in any order: integer sums do not depend on it),
+ *     group [count] int32: the group number of order[i] -- 0 at i = 0, then the predecessor's or one more.
+ *   Group g then holds, all [count]-sized buffers of which the first n_unique entries are written:
+ *     own_out[g] / opp_out[g]  the canonical boards,
+ *     pi_out[g][d] (int32)     the sum over its rows of pi[slot][a] with m_sym[slot](a) = d: the visit row turned into
+ *                              the canonical frame exactly as iago_replay_sample turns it by variant sym[slot],
+ *     z_sum[g] (int32)         the sum of z,   mult[g] (int32) the number of its rows,
+ *     first[g] (int64)         the exclusive prefix sum of mult (the group's first sorted row),
+ *     *n_unique (int32)        the number of groups.
+ *   Sums are accumulated in 64 bits; a cell or z_sum that would leave int32 is stored as the nearest end of its range
+ *   (2^31 - 1 above) and raises IAGO_REPLAY_MERGE_OVERFLOW in *flags.  The device checks what it indexes by: a group
+ *   numbering that breaks the rule above merges nothing (*n_unique = 0), a row whose slot lies outside [0, count),
+ *   whose sym is above 7 or whose canonical boards differ from those of its group's first row is left out; each raises
+ *   IAGO_REPLAY_MERGE_BAD_INPUT.  flags: one word, or-ed into; the caller clears it before the call.
+ *   One wave per group, lane = canonical cell, plain stores.  A group of more than 512 rows (the start position, once
+ *   per game of the window) is first summed by one wave per 256 sorted rows, which add their parts with 64-bit integer
+ *   atomics into workspace ([count] int64, need not be initialised: the call clears it); integer sums, so the result
+ *   is the same bits whatever the schedule.  No waiting on the device.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or pointer, count <= 0 or count >= 2^31.
+ */
+#define IAGO_REPLAY_MERGE_BAD_INPUT 1
+#define IAGO_REPLAY_MERGE_OVERFLOW 2
+typedef struct iago_replay_merge_args {
+    const uint64_t *c_own, *c_opp;
+    const uint8_t *sym;
+    const int32_t *pi;
+    const int8_t *z;
+    int64_t count;
+    const int32_t *order, *group;
+    uint64_t *own_out, *opp_out;
+    int32_t *pi_out, *z_sum, *mult;
+    int64_t *first;
+    int64_t *workspace;
+    int32_t *n_unique;
+    uint32_t *flags;
+} iago_replay_merge_args;
+IAGO_API int iago_replay_merge(const iago_replay_merge_args *args, void *stream);
+
+/*
+ * iago_replay_sample_merged: a minibatch out of the merged rows of iago_replay_merge (own / opp / pi / z_sum / mult /
+ *   first, n_unique groups of a window of count rows), every row in one of the board's eight symmetries.  The draw of
+ *   output row j is iago_replay_sample's: c = Philox4x32-10 on the counter (uint32(j), step, 0, 0) under the same key
+ *   split of seed,  sym = c[1] & 7,  and the group g by mode:
+ *     IAGO_REPLAY_MERGED_UNIQUE  g = (uint64(c[0]) * n_unique) >> 32: uniform over positions;
+ *     IAGO_REPLAY_MERGED_ROWS    r = (uint64(c[0]) * count) >> 32, g the group with first[g] <= r < first[g] + mult[g]
+ *                                (binary search on first): positions keep the weight they have in the window.
+ *   Outputs [n]: own_out / opp_out = variant sym of the canonical boards,  pi_out[j][m_sym(a)] = pi[g][a] (int32),
+ *   result_out = float32(z_sum[g]) / float32(mult[g]) (one conversion each, one IEEE division),  z_sum_out, mult_out,
+ *   group_out (int32), sym_out (uint8).  No move or z columns: a merged row has neither.  Integers but for that
+ *   division, plain stores, no workspace.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or pointer, n <= 0, n_unique <= 0,
+ *   n_unique > count, count >= 2^31, or another mode.
+ */
+#define IAGO_REPLAY_MERGED_UNIQUE 0
+#define IAGO_REPLAY_MERGED_ROWS 1
+typedef struct iago_replay_sample_merged_args {
+    const uint64_t *own, *opp;
+    const int32_t *pi, *z_sum, *mult;
+    const int64_t *first;
+    int64_t n_unique, count, n;
+    uint64_t seed;
+    uint32_t step;
+    int32_t mode;
+    uint64_t *own_out, *opp_out;
+    int32_t *pi_out;
+    float *result_out;
+    int32_t *z_sum_out, *mult_out, *group_out;
+    uint8_t *sym_out;
+} iago_replay_sample_merged_args;
+IAGO_API int iago_replay_sample_merged(const iago_replay_sample_merged_args *args, void *stream);
 
 #ifdef __cplusplus
 }

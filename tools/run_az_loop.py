@@ -24,10 +24,15 @@ solve_empties = k > 0: self-play hands the last k empties to the exact endgame s
 0, the default: off.  solved_targets = 1 (with solve_empties > 0): the solved turns record the set of their optimal moves
 (play(solved_targets=True)) and solved_tuples() -- pi 1 on every optimal move -- joins the window beside tuples(); the
 JSON line says so and counts those rows.
+merge = 1 or 2: the minibatches are drawn out of the window merged by position up to symmetry (ReplayWindow.sample(merged=
+"unique") for 1, "rows" for 2): a position's visit rows summed, its results averaged; "unique" draws uniformly over the
+distinct positions, "rows" keeps every position's weight in the window and changes the targets only.  0, the default:
+every row a position of its own (the JSON line's merge is null).  window_unique, the distinct positions of the window
+at the end, is logged beside window_count either way.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
                                  [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]
-                                 [solve_empties=0] [solved_targets=0]"""
+                                 [solve_empties=0] [solved_targets=0] [merge=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,6 +54,7 @@ yardstick_every, yardstick_depth = arg(14, 0), arg(15, 2)
 selection = engine.selection_arg("alphazero" if arg(16, 0) else "reference")
 solve_empties = arg(17, 0) if arg(17, 0) > 0 else None
 solved_targets = bool(arg(18, 0))
+merge = (None, "unique", "rows")[arg(19, 0)]
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
@@ -113,7 +119,7 @@ def one():
         solved_rows[0] += n
         added += n
     for _ in range(updates):
-        s = window.sample(rows)
+        s = window.sample(rows, merged=merge)   # (merged: the first draw of a round rebuilds the window's snapshot)
         loss = float(tr._update_visits(s["own"], s["opp"], s["pi"]).item())
         kls.append(tr._visits_kl(loss, s["pi"]))
         vlosses.append(vt.step_rows(s["own"], s["opp"], s["result"]))
@@ -144,7 +150,8 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "rounds": iters, "seconds": dt, "rounds_per_sec": iters / dt,
                   "rows_added": added, "rows_added_per_sec": added / dt,
                   "rows_trained": iters * updates * rows, "rows_trained_per_sec": iters * updates * rows / dt,
-                  "window_count": window.count, "window_total": window.total,
+                  "window_count": window.count, "window_unique": window.merged().n_unique, "window_total": window.total,
+                  "merge": merge,
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,

@@ -3,7 +3,10 @@
 slots and variants taken as given, index_select of the five columns, the visit rows gathered through a precomputed
 [8][64] permutation table, the boards and moves through ops.augment8 of the selected rows and a pick of each row's
 variant.  Device time per call (events around `reps` calls), and the two results compared.  One JSON line.
-    python3 tools/time_replay_sample.py [window=262144] [rows=4096] [reps=200]"""
+--merged: every row of the window is one of window / 4 positions in a random symmetry (a window with duplicates), and
+the line also carries the merged draws of the same `rows` rows (iago_replay_sample_merged, both modes, through ops and
+through ReplayWindow.sample(merged=) on its kept snapshot), ReplayWindow.merge()'s wall time and n_unique.
+    python3 tools/time_replay_sample.py [window=262144] [rows=4096] [reps=200] [--merged]"""
 import json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,12 +14,19 @@ sys.path.insert(0, ROOT)
 from iago_amd import ops  # noqa: E402
 from iago_amd.replay import ReplayWindow  # noqa: E402
 
-arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
+with_merged = "--merged" in sys.argv
+argv = [x for x in sys.argv if x != "--merged"]
+arg = lambda i, d: int(argv[i]) if len(argv) > i else d  # noqa: E731
 capacity, rows, reps = arg(1, 262144), arg(2, 4096), arg(3, 200)
 g = torch.Generator().manual_seed(0)
 w = ReplayWindow(capacity, seed=3)
 own = torch.randint(-2 ** 63, 2 ** 63 - 1, (capacity,), generator=g, dtype=torch.int64)
 opp = torch.randint(-2 ** 63, 2 ** 63 - 1, (capacity,), generator=g, dtype=torch.int64) & ~own
+if with_merged:
+    pick = torch.randint(0, max(capacity // 4, 1), (capacity,), generator=g)
+    turned = ops.augment8(own[pick].cuda(), opp[pick].cuda(), torch.zeros(capacity, dtype=torch.int8, device="cuda"))
+    k = torch.randint(0, 8, (1, capacity), generator=g).cuda()
+    own, opp = turned[0].gather(0, k)[0], turned[1].gather(0, k)[0]
 w.add(dict(own=own, opp=opp, pi=torch.randint(0, 100, (capacity, 64), generator=g, dtype=torch.int32),
            move=torch.randint(-1, 64, (capacity,), generator=g, dtype=torch.int8),
            z=torch.randint(-1, 2, (capacity,), generator=g, dtype=torch.int8)))
@@ -58,6 +68,21 @@ c = w.cols
 t_sample = timed(lambda: w.sample(rows, step=0))                 # (with the window's read-back of its flag word)
 t_kernel = timed(lambda: ops.replay_sample(c["own"], c["opp"], c["pi"], c["move"], c["z"], w.count, n=rows, seed=3))
 t_torch = timed(lambda: restated(first["slot"], first["sym"]))
+extra = {}
+if with_merged:
+    import time
+    walls = []
+    for _ in range(4):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m = w.merge()
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    extra = {"n_unique": m.n_unique, "largest_group": int(m.mult.max().item()), "merge_wall_ms": min(walls[1:])}
+    for mode in ("unique", "rows"):
+        extra["ops_replay_sample_merged_%s_us" % mode] = timed(lambda: ops.replay_sample_merged(
+            m.own, m.opp, m.pi, m.z_sum, m.mult, m.first, m.count, rows, seed=3, mode=mode))
+        extra["window_sample_merged_%s_us" % mode] = timed(lambda: w.sample(rows, step=0, merged=mode))
 print(json.dumps({"window_rows": capacity, "rows": rows, "reps": reps, "restatement_equal": bool(same),
                   "window_sample_us": t_sample, "ops_replay_sample_us": t_kernel, "torch_restatement_us": t_torch,
-                  "bytes_moved": rows * 2 * 290, "kernel_GBps": rows * 2 * 290 / (t_kernel * 1e-6) / 1e9}))
+                  "bytes_moved": rows * 2 * 290, "kernel_GBps": rows * 2 * 290 / (t_kernel * 1e-6) / 1e9, **extra}))
