@@ -19,8 +19,10 @@
 // (position, depth left) on the device, the same search runs a lane per job (alphabeta_jobs_kernel: the job count read
 // from ctl, every lane's depth from its job), and a thread per root takes the values back.  Every job has the full window,
 // so its value and its node count are those of iago_alphabeta_moves on that position, whatever else runs beside it.
-// The expansion, the scan, the job record and the reduction are lane_split.hpp's, shared with iago_solve_endgame_split.
+// The expansion, the scan, the job record and the reduction are lane_split.hpp's, shared with iago_solve_endgame_split;
+// the entry points' refusals, range checks, params' base and launches are lane_host.hpp's, shared with the solver's.
 #include "abi_common.hpp"
+#include "lane_host.hpp"
 #include "lane_search.hpp"
 #include "lane_split.hpp"
 #include "othello_dev.hpp"
@@ -102,58 +104,21 @@ struct YardstickRules {
     }
 };
 
-// what a finished search answers, for both params below
-template <class Params>
-__device__ __forceinline__ void write_answer(const Params &P, int64_t pos, const Search &s)
-{
-    P.score[pos] = (int16_t)s.v;
-    P.move[pos] = (int8_t)s.root_move;
-    P.nodes[pos] = s.nodes;
-    P.done[pos] = 1;
-}
-
-struct AlphaBetaParams {
-    const uint64_t *own;
-    const uint64_t *opp;
+struct AlphaBetaParams : LaneParams<int16_t> {
     int64_t n;
-    int16_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *done;
-    uint32_t *ctl;
     int32_t depth;
-    int32_t levels;          // stack frames per lane
-    long long clock_limit;   // wall_clock64 ticks (100 MHz)
 
     __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &) const
     {
         o = own[pos];
         p = opp[pos];
-        if ((o & p) == 0ull)
-            return true;
-        // refused: done stays 0
-        atomicAdd(&ctl[CTL_REFUSED], 1u);
-        score[pos] = 0;
-        move[pos] = 0;
-        nodes[pos] = 0;
-        return false;
+        return (o & p) == 0ull || refuse(pos);
     }
-
-    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const { write_answer(*this, pos, s); }
 };
 
 // The jobs of iago_alphabeta_moves_split as the search reads and answers them: positions with a depth of their own
-struct JobParams {
-    const uint64_t *own;
-    const uint64_t *opp;
+struct JobParams : LaneParams<int16_t> {
     const int8_t *path;      // [jobs][4]: depth left, first move, second move, 0
-    int16_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *done;
-    uint32_t *ctl;
-    int32_t levels;          // stack frames per lane: the launch's depth
-    long long clock_limit;
 
     __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &depth) const
     {
@@ -162,8 +127,6 @@ struct JobParams {
         depth = path[4 * pos];
         return true;
     }
-
-    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const { write_answer(*this, pos, s); }
 };
 
 __global__ __launch_bounds__(WAVE) void alphabeta_kernel(AlphaBetaParams P)
@@ -220,103 +183,58 @@ __global__ __launch_bounds__(256) void random_moves_kernel(const uint64_t *own, 
     move[g] = (int8_t)m;
 }
 
+constexpr int FRAME_BYTES = Stack<YardstickRules>::FRAME_BYTES;
+
 } // namespace
 
 extern "C" int iago_alphabeta_moves(const iago_alphabeta_args *a, void *stream)
 {
     const char *who = "iago_alphabeta_moves";
     if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: null args");
-    if (a->n < 0 || (a->n > 0 && (!a->own || !a->opp || !a->score || !a->move || !a->nodes || !a->done)) || !a->ctl)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: null pointer or negative n");
+        return refuse(who, "null args");
+    if (const int rc = check_roots(who, a, a->done))
+        return rc;
     if (a->depth < 1 || a->depth > IAGO_ALPHABETA_MAX_DEPTH)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: depth must be in [1, 10]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: time_limit_ms must be in [1, 600000]");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, 4, a->done, "done", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
+        return refuse(who, "depth must be in [1, 10]");
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved))
         return rc;
 
     AlphaBetaParams P;
-    P.own = a->own;
-    P.opp = a->opp;
+    // a frame is pushed by a node with >= 2 levels below it: levels 0 .. depth - 2
+    fill_lane_params(P, a->own, a->opp, a->score, a->move, a->nodes, a->done, a->ctl, a->depth, a->time_limit_ms);
     P.n = a->n;
-    P.score = a->score;
-    P.move = a->move;
-    P.nodes = a->nodes;
-    P.done = a->done;
-    P.ctl = a->ctl;
     P.depth = a->depth;
-    P.levels = a->depth; // a frame is pushed by a node with >= 2 levels below it: levels 0 .. depth - 2
-    P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
-    iago_search_launch((const void *)alphabeta_kernel, &P, P.levels, Stack<YardstickRules>::FRAME_BYTES, a->n, cus, s);
-    return iago_check_launch(who);
+    return lane_run(who, P, a->done, "done", a->n, nullptr, (const void *)alphabeta_kernel, FRAME_BYTES,
+                    (hipStream_t)stream);
 }
 
 extern "C" int iago_alphabeta_moves_split(const iago_alphabeta_split_args *a, void *stream)
 {
     const char *who = "iago_alphabeta_moves_split";
     if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null args");
-    if (a->n < 0 || a->n > INT32_MAX || (a->n > 0 && (!a->own || !a->opp || !a->job_count || !a->job_first)) || !a->ctl)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null pointer, negative n or n above 2^31 - 1");
-    if (a->depth < 2 || a->depth > IAGO_ALPHABETA_MAX_DEPTH)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: depth must be in [2, 10]");
-    if (a->split < 1 || a->split > IAGO_ALPHABETA_MAX_SPLIT || a->split >= a->depth)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: split must be 1 or 2 and below depth");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: time_limit_ms must be in [1, 600000]");
-    if (a->job_capacity < 0 || a->job_capacity > INT32_MAX)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: job_capacity must be in [0, 2^31 - 1]");
-    const int job_arrays = (a->job_own != nullptr) + (a->job_opp != nullptr) + (a->job_root != nullptr) +
-                           (a->job_path != nullptr) + (a->job_score != nullptr) + (a->job_move != nullptr) +
-                           (a->job_nodes != nullptr) + (a->job_done != nullptr);
-    if ((job_arrays != 0 && job_arrays != 8) || (job_arrays == 0 && a->job_capacity != 0))
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: the job arrays are all given, or all null with "
-                                           "job_capacity 0 (the count-only form)");
-    const bool count_only = job_arrays == 0;
-    if (!count_only && a->n > 0 && (!a->score || !a->move || !a->nodes || !a->done))
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: null score, move, nodes or done");
-    if (a->reserved0 != 0)
-        return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: reserved fields must be 0");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_alphabeta_moves_split: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, IAGO_ALPHABETA_SPLIT_CTL_WORDS, count_only ? nullptr : a->done,
-                                       "done", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
+        return refuse(who, "null args");
+    if (const int rc = split_check_roots(who, a))
         return rc;
+    if (a->depth < 2 || a->depth > IAGO_ALPHABETA_MAX_DEPTH)
+        return refuse(who, "depth must be in [2, 10]");
+    if (a->split < 1 || a->split > IAGO_ALPHABETA_MAX_SPLIT || a->split >= a->depth)
+        return refuse(who, "split must be 1 or 2 and below depth");
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    bool count_only = false;
+    if (const int rc = split_check_jobs(who, a, a->done, "done", &count_only))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved, a->reserved0))
+        return rc;
+    static_assert(IAGO_ALPHABETA_SPLIT_CTL_WORDS == SPLIT_CTL_WORDS && IAGO_ALPHABETA_MAX_SPLIT == MAX_SPLIT,
+                  "lane_split.hpp");
 
-    // 1. expand: count, sum, write
-    split_expand(split_params_of(a, DepthJobs{a->depth}), count_only, s);
-    if (count_only)
-        return iago_check_launch(who);
-
-    // 2. search: the lanes of iago_alphabeta_moves over the jobs
     JobParams J;
-    J.own = a->job_own;
-    J.opp = a->job_opp;
     J.path = a->job_path;
-    J.score = a->job_score;
-    J.move = a->job_move;
-    J.nodes = a->job_nodes;
-    J.done = a->job_done;
-    J.ctl = a->ctl;
-    J.levels = a->depth; // the deepest job is a root that must pass: the launch's depth
-    J.clock_limit = (long long)a->time_limit_ms * 100000ll;
-    iago_search_launch((const void *)alphabeta_jobs_kernel, &J, J.levels, Stack<YardstickRules>::FRAME_BYTES,
-                       a->job_capacity, cus, s);
-
-    // 3. reduce
-    split_reduce(reduce_params_of<DepthJobs>(a, a->done), s);
-    return iago_check_launch(who);
+    return split_run(who, a, count_only, a->done, "done", DepthJobs{a->depth}, (const void *)alphabeta_jobs_kernel, J,
+                     a->depth, FRAME_BYTES, (hipStream_t)stream);
 }
 
 extern "C" int iago_random_moves(const uint64_t *own, const uint64_t *opp, int64_t n, uint64_t seed, uint32_t id_base,

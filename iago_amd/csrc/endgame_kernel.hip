@@ -16,7 +16,10 @@
 // per root takes the values back, with the set of the best moves and every move's value where they are asked for.
 // iago_play_endgame (play_endgame_kernel: one lane per GAME) runs the same search once per turn of a game and plays
 // the moves, to the game's end.
+// What the entry points share with alphabeta_kernel.hip's -- the refusals, the range checks, the params' base, the
+// launches -- is lane_host.hpp's.
 #include "abi_common.hpp"
+#include "lane_host.hpp"
 #include "lane_search.hpp"
 #include "lane_split.hpp"
 #include "othello_dev.hpp"
@@ -74,41 +77,17 @@ struct SolverRulesT {
 
 using SolverRules = SolverRulesT<LOWEST>; // iago_solve_endgame, iago_play_endgame
 
-struct EndgameParams {
-    const uint64_t *own;
-    const uint64_t *opp;
+struct EndgameParams : LaneParams<int8_t> {
     int64_t n;
-    int8_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *solved;
-    uint32_t *ctl;
     int32_t wld;
     int32_t max_empties;
-    int32_t levels;          // stack frames per lane
-    long long clock_limit;   // wall_clock64 ticks (100 MHz)
 
     __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &empties) const
     {
         o = own[pos];
         p = opp[pos];
         empties = 64 - __popcll(o | p);
-        if ((o & p) == 0ull && empties <= max_empties)
-            return true;
-        // refused: solved stays 0
-        atomicAdd(&ctl[CTL_REFUSED], 1u);
-        score[pos] = 0;
-        move[pos] = 0;
-        nodes[pos] = 0;
-        return false;
-    }
-
-    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
-    {
-        score[pos] = (int8_t)s.v;
-        move[pos] = (int8_t)s.root_move;
-        nodes[pos] = s.nodes;
-        solved[pos] = 1;
+        return ((o & p) == 0ull && empties <= max_empties) || refuse(pos);
     }
 };
 
@@ -135,7 +114,7 @@ struct MovesParams : EndgameParams {
     __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
     {
         best[pos] = s.best_set;
-        EndgameParams::finish(pos, s);
+        LaneParams::finish(pos, s);
     }
 
     __device__ __forceinline__ int8_t *row(int64_t pos) const { return move_score + 64 * pos; }
@@ -164,17 +143,8 @@ struct EmptiesJobs {
 };
 
 // The jobs as the search reads and answers them: positions of an admitted root's subtree, each with its own empties
-struct EndgameJobParams {
-    const uint64_t *own;
-    const uint64_t *opp;
-    int8_t *score;
-    int8_t *move;
-    int64_t *nodes;
-    uint8_t *done;
-    uint32_t *ctl;
+struct EndgameJobParams : LaneParams<int8_t> {
     int32_t wld;
-    int32_t levels;          // stack frames per lane: max_empties'
-    long long clock_limit;
 
     __device__ __forceinline__ bool admit(int64_t pos, uint64_t &o, uint64_t &p, int &empties) const
     {
@@ -182,14 +152,6 @@ struct EndgameJobParams {
         p = opp[pos];
         empties = 64 - __popcll(o | p); // (at most the root's, which is at most max_empties)
         return true;
-    }
-
-    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
-    {
-        score[pos] = (int8_t)s.v;
-        move[pos] = (int8_t)s.root_move;
-        nodes[pos] = s.nodes;
-        done[pos] = 1;
     }
 };
 
@@ -344,12 +306,45 @@ __global__ __launch_bounds__(WAVE) void play_endgame_moves_kernel(PlayMovesParam
     play_endgame_games<SolverRulesT<BEST>>(P, stack_lds);
 }
 
+constexpr int FRAME_BYTES = Stack<SolverRules>::FRAME_BYTES; // (the root's rule does not change the frame)
+
 // a frame is pushed by a node with >= 2 empties: levels 0 .. max_empties - 2
 int stack_levels(int max_empties) { return max_empties > 2 ? max_empties - 1 : 1; }
 
-// the kernel's params from iago_play_endgame's arguments
-void fill_play_params(PlayParams &P, const iago_play_endgame_args *a)
+// the root kernels' params from the arguments of iago_solve_endgame and iago_solve_endgame_moves
+template <class Args>
+void fill_endgame_params(EndgameParams &P, const Args *a)
 {
+    fill_lane_params(P, a->own, a->opp, a->score, a->move, a->nodes, a->solved, a->ctl, stack_levels(a->max_empties),
+                     a->time_limit_ms);
+    P.n = a->n;
+    P.wld = a->mode == IAGO_ENDGAME_WLD;
+    P.max_empties = a->max_empties;
+}
+
+// Both play entry points: the checks, the clears and the launch.  m: iago_play_endgame_moves' arguments around a, or null
+int play_endgame(const char *who, const iago_play_endgame_args *a, const iago_play_endgame_moves_args *m, hipStream_t s)
+{
+    if (a->n < 0 || !a->ctl ||
+        (a->n > 0 && (!a->own || !a->opp || !a->turn || !a->stones || !a->pass_flg || !a->parked || !a->rec_own ||
+                      !a->rec_opp || !a->rec_valid || !a->rec_move || !a->rec_score || !a->finished ||
+                      (m && !m->rec_best))))
+        return refuse(who, "null pointer or negative n");
+    if (a->stride < a->n)
+        return refuse(who, "stride >= n expected");
+    if (a->max_turns < 1 || a->max_turns > IAGO_MAX_TURNS)
+        return refuse(who, "max_turns must be in [1, IAGO_MAX_TURNS]");
+    if (const int rc = check_max_empties(who, a->max_empties))
+        return rc;
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved, a->reserved0))
+        return rc;
+    if (m)
+        if (const int rc = check_reserved(who, m->reserved))
+            return rc;
+
+    PlayMovesParams P;
     P.own = a->own;
     P.opp = a->opp;
     P.turn = a->turn;
@@ -368,7 +363,13 @@ void fill_play_params(PlayParams &P, const iago_play_endgame_args *a)
     P.max_turns = a->max_turns;
     P.max_empties = a->max_empties;
     P.levels = stack_levels(a->max_empties);
-    P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
+    P.clock_limit = clock_limit_of(a->time_limit_ms);
+    P.rec_best = m ? m->rec_best : nullptr;
+    if (m)
+        return lane_run(who, P, a->finished, "finished", a->n, nullptr, (const void *)play_endgame_moves_kernel,
+                        FRAME_BYTES, s);
+    return lane_run(who, static_cast<PlayParams &>(P), a->finished, "finished", a->n, nullptr,
+                    (const void *)play_endgame_kernel, FRAME_BYTES, s);
 }
 
 } // namespace
@@ -377,234 +378,91 @@ extern "C" int iago_solve_endgame(const iago_endgame_args *a, void *stream)
 {
     const char *who = "iago_solve_endgame";
     if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: null args");
-    if (a->n < 0 || (a->n > 0 && (!a->own || !a->opp || !a->score || !a->move || !a->nodes || !a->solved)) ||
-        !a->ctl)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: null pointer or negative n");
-    if (a->mode != IAGO_ENDGAME_EXACT && a->mode != IAGO_ENDGAME_WLD)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: mode must be IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD");
-    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: max_empties must be in [0, 20]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: time_limit_ms must be in [1, 600000]");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0 || a->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, 4, a->solved, "solved", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
+        return refuse(who, "null args");
+    if (const int rc = check_roots(who, a, a->solved))
+        return rc;
+    if (const int rc = check_mode(who, a->mode))
+        return rc;
+    if (const int rc = check_max_empties(who, a->max_empties))
+        return rc;
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved, a->reserved0))
         return rc;
 
     EndgameParams P;
-    P.own = a->own;
-    P.opp = a->opp;
-    P.n = a->n;
-    P.score = a->score;
-    P.move = a->move;
-    P.nodes = a->nodes;
-    P.solved = a->solved;
-    P.ctl = a->ctl;
-    P.wld = a->mode == IAGO_ENDGAME_WLD;
-    P.max_empties = a->max_empties;
-    P.levels = stack_levels(a->max_empties);
-    P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
-    iago_search_launch((const void *)endgame_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
-    return iago_check_launch(who);
-}
-
-extern "C" int iago_play_endgame(const iago_play_endgame_args *a, void *stream)
-{
-    const char *who = "iago_play_endgame";
-    if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: null args");
-    if (a->n < 0 || !a->ctl ||
-        (a->n > 0 && (!a->own || !a->opp || !a->turn || !a->stones || !a->pass_flg || !a->parked || !a->rec_own ||
-                      !a->rec_opp || !a->rec_valid || !a->rec_move || !a->rec_score || !a->finished)))
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: null pointer or negative n");
-    if (a->stride < a->n)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: stride >= n expected");
-    if (a->max_turns < 1 || a->max_turns > IAGO_MAX_TURNS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: max_turns must be in [1, IAGO_MAX_TURNS]");
-    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: max_empties must be in [0, 20]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: time_limit_ms must be in [1, 600000]");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0 || a->reserved0 != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, 4, a->finished, "finished", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
-        return rc;
-
-    PlayParams P;
-    fill_play_params(P, a);
-    iago_search_launch((const void *)play_endgame_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
-    return iago_check_launch(who);
+    fill_endgame_params(P, a);
+    return lane_run(who, P, a->solved, "solved", a->n, nullptr, (const void *)endgame_kernel, FRAME_BYTES,
+                    (hipStream_t)stream);
 }
 
 extern "C" int iago_solve_endgame_moves(const iago_endgame_moves_args *a, void *stream)
 {
     const char *who = "iago_solve_endgame_moves";
     if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: null args");
-    if (a->n < 0 ||
-        (a->n > 0 && (!a->own || !a->opp || !a->score || !a->move || !a->nodes || !a->solved || !a->best)) || !a->ctl)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: null pointer or negative n");
-    if (a->mode != IAGO_ENDGAME_EXACT && a->mode != IAGO_ENDGAME_WLD)
-        return iago_fail(IAGO_ERR_INVALID,
-                         "iago_solve_endgame_moves: mode must be IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD");
+        return refuse(who, "null args");
+    if (const int rc = check_roots(who, a, a->solved, a->best != nullptr))
+        return rc;
+    if (const int rc = check_mode(who, a->mode))
+        return rc;
     if (a->moves != IAGO_ENDGAME_MOVES_BEST && a->moves != IAGO_ENDGAME_MOVES_ALL)
-        return iago_fail(IAGO_ERR_INVALID,
-                         "iago_solve_endgame_moves: moves must be IAGO_ENDGAME_MOVES_BEST or IAGO_ENDGAME_MOVES_ALL");
+        return refuse(who, "moves must be IAGO_ENDGAME_MOVES_BEST or IAGO_ENDGAME_MOVES_ALL");
     const bool all = a->moves == IAGO_ENDGAME_MOVES_ALL;
     if (!all && a->move_score)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: move_score must be NULL under IAGO_ENDGAME_MOVES_BEST");
+        return refuse(who, "move_score must be NULL under IAGO_ENDGAME_MOVES_BEST");
     if (all && a->n > 0 && !a->move_score)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: move_score is required under IAGO_ENDGAME_MOVES_ALL");
-    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: max_empties must be in [0, 20]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: time_limit_ms must be in [1, 600000]");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_moves: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, 4, a->solved, "solved", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
+        return refuse(who, "move_score is required under IAGO_ENDGAME_MOVES_ALL");
+    if (const int rc = check_max_empties(who, a->max_empties))
         return rc;
-    // every cell starts as "no move": the search writes the legal moves of the roots it admits
-    if (all && hipMemsetAsync(a->move_score, IAGO_ENDGAME_NO_MOVE & 0xFF, (size_t)a->n * 64, s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame_moves: clearing move_score");
-    }
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved))
+        return rc;
 
     MovesParams P;
-    P.own = a->own;
-    P.opp = a->opp;
-    P.n = a->n;
-    P.score = a->score;
-    P.move = a->move;
-    P.nodes = a->nodes;
-    P.solved = a->solved;
-    P.ctl = a->ctl;
-    P.wld = a->mode == IAGO_ENDGAME_WLD;
-    P.max_empties = a->max_empties;
-    P.levels = stack_levels(a->max_empties);
-    P.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
+    fill_endgame_params(P, a);
     P.best = a->best;
     P.move_score = a->move_score;
     const void *kernel = all ? (const void *)endgame_moves_kernel<ALL> : (const void *)endgame_moves_kernel<BEST>;
-    iago_search_launch(kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus, s);
-    return iago_check_launch(who);
+    return lane_run(who, P, a->solved, "solved", a->n, a->move_score, kernel, FRAME_BYTES, (hipStream_t)stream);
 }
 
 extern "C" int iago_solve_endgame_split(const iago_endgame_split_args *a, void *stream)
 {
     const char *who = "iago_solve_endgame_split";
     if (!a)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null args");
-    if (a->n < 0 || a->n > INT32_MAX || (a->n > 0 && (!a->own || !a->opp || !a->job_count || !a->job_first)) || !a->ctl)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null pointer, negative n or n above 2^31 - 1");
-    if (a->mode != IAGO_ENDGAME_EXACT && a->mode != IAGO_ENDGAME_WLD)
-        return iago_fail(IAGO_ERR_INVALID,
-                         "iago_solve_endgame_split: mode must be IAGO_ENDGAME_EXACT or IAGO_ENDGAME_WLD");
-    if (a->split < 1 || a->split > IAGO_ENDGAME_MAX_SPLIT)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: split must be 1 or 2");
-    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: max_empties must be in [0, 20]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: time_limit_ms must be in [1, 600000]");
-    if (a->job_capacity < 0 || a->job_capacity > INT32_MAX)
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: job_capacity must be in [0, 2^31 - 1]");
-    const int job_arrays = (a->job_own != nullptr) + (a->job_opp != nullptr) + (a->job_root != nullptr) +
-                           (a->job_path != nullptr) + (a->job_score != nullptr) + (a->job_move != nullptr) +
-                           (a->job_nodes != nullptr) + (a->job_done != nullptr);
-    if ((job_arrays != 0 && job_arrays != 8) || (job_arrays == 0 && a->job_capacity != 0))
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: the job arrays are all given, or all null with "
-                                           "job_capacity 0 (the count-only form)");
-    const bool count_only = job_arrays == 0;
-    if (!count_only && a->n > 0 && (!a->score || !a->move || !a->nodes || !a->solved))
-        return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: null score, move, nodes or solved");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_solve_endgame_split: reserved fields must be 0");
-    static_assert(IAGO_ENDGAME_SPLIT_CTL_WORDS == SPLIT_CTL_WORDS && IAGO_ENDGAME_MAX_SPLIT == MAX_SPLIT, "lane_split.hpp");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, IAGO_ENDGAME_SPLIT_CTL_WORDS, count_only ? nullptr : a->solved,
-                                       "solved", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
+        return refuse(who, "null args");
+    if (const int rc = split_check_roots(who, a))
         return rc;
-    // every cell starts as "no move": the reduction writes the legal moves of the roots it answers
-    if (!count_only && a->move_score &&
-        hipMemsetAsync(a->move_score, IAGO_ENDGAME_NO_MOVE & 0xFF, (size_t)a->n * 64, s) != hipSuccess) {
-        (void)hipGetLastError();
-        return iago_fail(IAGO_ERR_HIP, "iago_solve_endgame_split: clearing move_score");
-    }
+    if (const int rc = check_mode(who, a->mode))
+        return rc;
+    if (a->split < 1 || a->split > IAGO_ENDGAME_MAX_SPLIT)
+        return refuse(who, "split must be 1 or 2");
+    if (const int rc = check_max_empties(who, a->max_empties))
+        return rc;
+    if (const int rc = check_time_limit(who, a->time_limit_ms))
+        return rc;
+    bool count_only = false;
+    if (const int rc = split_check_jobs(who, a, a->solved, "solved", &count_only))
+        return rc;
+    if (const int rc = check_reserved(who, a->reserved))
+        return rc;
+    static_assert(IAGO_ENDGAME_SPLIT_CTL_WORDS == SPLIT_CTL_WORDS && IAGO_ENDGAME_MAX_SPLIT == MAX_SPLIT, "lane_split.hpp");
 
-    // 1. expand: count, sum, write
-    split_expand(split_params_of(a, EmptiesJobs{a->max_empties}), count_only, s);
-    if (count_only)
-        return iago_check_launch(who);
-
-    // 2. search: the lanes of iago_solve_endgame over the jobs
     EndgameJobParams J;
-    J.own = a->job_own;
-    J.opp = a->job_opp;
-    J.score = a->job_score;
-    J.move = a->job_move;
-    J.nodes = a->job_nodes;
-    J.done = a->job_done;
-    J.ctl = a->ctl;
     J.wld = a->mode == IAGO_ENDGAME_WLD;
-    J.levels = stack_levels(a->max_empties); // the deepest job is a root that must pass: max_empties empties
-    J.clock_limit = (long long)a->time_limit_ms * 100000ll; // wall_clock64: 100 MHz
-    iago_search_launch((const void *)endgame_jobs_kernel, &J, J.levels, Stack<SolverRules>::FRAME_BYTES,
-                       a->job_capacity, cus, s);
+    return split_run(who, a, count_only, a->solved, "solved", EmptiesJobs{a->max_empties},
+                     (const void *)endgame_jobs_kernel, J, stack_levels(a->max_empties), FRAME_BYTES, (hipStream_t)stream);
+}
 
-    // 3. reduce
-    ReduceParams<EmptiesJobs> R = reduce_params_of<EmptiesJobs>(a, a->solved);
-    R.best = a->best;
-    R.move_score = a->move_score;
-    split_reduce(R, s);
-    return iago_check_launch(who);
+extern "C" int iago_play_endgame(const iago_play_endgame_args *a, void *stream)
+{
+    const char *who = "iago_play_endgame";
+    return a ? play_endgame(who, a, nullptr, (hipStream_t)stream) : refuse(who, "null args");
 }
 
 extern "C" int iago_play_endgame_moves(const iago_play_endgame_moves_args *m, void *stream)
 {
     const char *who = "iago_play_endgame_moves";
-    if (!m)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: null args");
-    const iago_play_endgame_args *a = &m->play;
-    if (a->n < 0 || !a->ctl ||
-        (a->n > 0 && (!a->own || !a->opp || !a->turn || !a->stones || !a->pass_flg || !a->parked || !a->rec_own ||
-                      !a->rec_opp || !a->rec_valid || !a->rec_move || !a->rec_score || !a->finished || !m->rec_best)))
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: null pointer or negative n");
-    if (a->stride < a->n)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: stride >= n expected");
-    if (a->max_turns < 1 || a->max_turns > IAGO_MAX_TURNS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: max_turns must be in [1, IAGO_MAX_TURNS]");
-    if (a->max_empties < 0 || a->max_empties > IAGO_ENDGAME_MAX_EMPTIES)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: max_empties must be in [0, 20]");
-    if (a->time_limit_ms <= 0 || a->time_limit_ms > IAGO_ENDGAME_MAX_TIME_MS)
-        return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: time_limit_ms must be in [1, 600000]");
-    for (int i = 0; i < 4; i++)
-        if (a->reserved[i] != 0 || a->reserved0 != 0 || m->reserved[i] != 0)
-            return iago_fail(IAGO_ERR_INVALID, "iago_play_endgame_moves: reserved fields must be 0");
-    hipStream_t s = (hipStream_t)stream;
-    int cus = 0;
-    const int rc = iago_search_prepare(who, a->ctl, 4, a->finished, "finished", a->n, s, &cus);
-    if (rc != IAGO_OK || cus == 0)
-        return rc;
-
-    PlayMovesParams P;
-    fill_play_params(P, a);
-    P.rec_best = m->rec_best;
-    iago_search_launch((const void *)play_endgame_moves_kernel, &P, P.levels, Stack<SolverRules>::FRAME_BYTES, a->n, cus,
-                       s);
-    return iago_check_launch(who);
+    return m ? play_endgame(who, &m->play, m, (hipStream_t)stream) : refuse(who, "null args");
 }

@@ -280,6 +280,40 @@ __device__ __forceinline__ bool search_step(Search &s, const Stack<Rules> &K, ui
 //   finish(pos, s): the outputs of the finished search s;
 //   row(pos) (Rules::ROOT == ALL only): where the per-move values of the root go, 64 bytes.
 // levels0 comes in as the launch's own where every position has the same (admit leaves it), else as 0.
+
+// What every such params struct holds (lane_host.hpp's fill_lane_params fills it): a kernel's own derives from it and adds
+// admit() and the one or two fields that admit() reads.  Score: the type of a value in memory.
+template <class Score>
+struct LaneParams {
+    const uint64_t *own;
+    const uint64_t *opp;
+    Score *score;
+    int8_t *move;
+    int64_t *nodes;
+    uint8_t *done;
+    uint32_t *ctl;
+    int32_t levels;          // stack frames per lane
+    long long clock_limit;   // wall_clock64 ticks
+
+    // admit()'s false: counted, answered with zeros, the done flag stays 0
+    __device__ __forceinline__ bool refuse(int64_t pos) const
+    {
+        atomicAdd(&ctl[CTL_REFUSED], 1u);
+        score[pos] = 0;
+        move[pos] = 0;
+        nodes[pos] = 0;
+        return false;
+    }
+
+    __device__ __forceinline__ void finish(int64_t pos, const Search &s) const
+    {
+        score[pos] = (Score)s.v;
+        move[pos] = (int8_t)s.root_move;
+        nodes[pos] = s.nodes;
+        done[pos] = 1;
+    }
+};
+
 template <class Rules, class Params>
 __device__ __forceinline__ void search_wave(const Params &P, const Rules &R, int64_t n, int levels0,
                                             unsigned char *stack_lds)

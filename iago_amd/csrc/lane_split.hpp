@@ -317,6 +317,10 @@ ReduceParams<Kind> reduce_params_of(const Args *a, uint8_t *done)
     R.done = done;
     R.best = nullptr;
     R.move_score = nullptr;
+    if constexpr (Kind::MOVES) {
+        R.best = a->best;
+        R.move_score = a->move_score;
+    }
     R.ctl = a->ctl;
     return R;
 }

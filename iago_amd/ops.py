@@ -1110,32 +1110,59 @@ def rollout(own, opp, weights=None, seed=0, id_base=0, stream_id=0, uniforms=Non
 
 
 ENDGAME_MODES = {"exact": _lib.ENDGAME_EXACT, "wld": _lib.ENDGAME_WLD}
+ENDGAME_MOVES = {"best": _lib.ENDGAME_MOVES_BEST, "all": _lib.ENDGAME_MOVES_ALL}
 ENDGAME_TIME_LIMIT_MS = 60000
 
+# What a lane search that did not finish everything says, per family: the stack overflow of an unsplit and of a split
+# launch, the give-up, the refusals.  limit: the solver's max_empties, the yardstick's depth.
+_SOLVER_TEXTS = dict(
+    overflow="a position needed more stack frames than max_empties = %(limit)d sizes (ctl[3] set): it was dropped "
+             "with solved = 0 and its outputs unwritten",
+    job_overflow="a job needed more stack frames than max_empties = %(limit)d sizes (ctl[3] set): it was dropped and its "
+                 "root keeps solved = 0",
+    gave_up="gave up at its clock limit (%(ms)d ms): %(left)d of %(n)d positions unsolved",
+    refused="%(refused)d positions refused (own & opp != 0, or more than max_empties = %(limit)d empties)")
+_ALPHABETA_TEXTS = dict(
+    overflow="a position needed more stack frames than depth = %(limit)d sizes (ctl[3] set)",
+    job_overflow="a job needed more stack frames than depth = %(limit)d sizes (ctl[3] set)",
+    gave_up="gave up at its clock limit (%(ms)d ms): %(left)d of %(n)d positions unfinished",
+    refused="%(refused)d positions refused (own & opp != 0)")
 
-def _check_search_ctl(who, out, ctl, overflow, gave_up, refused, first=None, **attrs):
-    """Raise IagoError (the result as its `result` attribute, attrs as further ones) unless a lane-search launch
-    finished everything.  ctl: its words on the host.  The caller's phrases: `first` (a fault of its own, before the
-    others), overflow, gave_up (a callable: it reads a tensor back), refused (with a %d for the count)."""
-    g, _, r, o = (int(v) for v in ctl[:4])
-    if not (first or g or r or o):
+
+def alphabeta_job_count(ctl):
+    """The jobs a split launch needed, from the host values of its ctl words."""
+    return (int(ctl[4]) & 0xFFFFFFFF) | ((int(ctl[5]) & 0xFFFFFFFF) << 32)
+
+
+def _check_lane_ctl(who, out, ctl, texts, limit, time_limit_ms, n, done_name, job_capacity=None):
+    """Raise IagoError (the result `out` as its `result` attribute) unless a lane-search launch finished every position.
+    ctl: its words on the host; nothing else is read but, after a give-up, the done flags out[done_name] of its n
+    positions.  texts, limit: the family's phrases above.  job_capacity: of a split launch (None: an unsplit one) --
+    where the jobs did not fit (ctl[6]) that comes first, with the count needed as the error's `jobs_needed`."""
+    gave_up, _, refused, overflow = (int(v) for v in ctl[:4])
+    split = job_capacity is not None
+    short = split and int(ctl[6]) != 0
+    if not (short or gave_up or refused or overflow):
         return
-    err = _lib.IagoError("%s: %s" % (who, first or (overflow if o else gave_up() if g else refused % r)))
+    if short:
+        what = "the search needs %d jobs, job_capacity holds %d: nothing was searched" % (
+            alphabeta_job_count(ctl), job_capacity)
+    elif overflow:
+        what = texts["job_overflow" if split else "overflow"] % dict(limit=limit)
+    elif gave_up:
+        what = texts["gave_up"] % dict(ms=time_limit_ms, left=n - int(out[done_name].sum().item()), n=n)
+    else:
+        what = texts["refused"] % dict(refused=refused, limit=limit)
+    err = _lib.IagoError("%s: %s" % (who, what))
     err.result = out
-    for k, v in attrs.items():
-        setattr(err, k, v)
+    if short:
+        err.jobs_needed = alphabeta_job_count(ctl)
     raise err
 
 
 def _check_endgame_ctl(out, n, max_empties, time_limit_ms, who="iago_solve_endgame"):
-    """Raise IagoError (with the result as its `result` attribute) unless the launch finished every position."""
-    _check_search_ctl(
-        who, out, out["ctl"].tolist(),
-        "a position needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped "
-        "with solved = 0 and its outputs unwritten" % max_empties,
-        lambda: "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
-            time_limit_ms, n - int(out["solved"].sum().item()), n),
-        "%%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % max_empties)
+    """_check_lane_ctl for the solver's entry points, on the ctl words of out (read back here)."""
+    _check_lane_ctl(who, out, out["ctl"].tolist(), _SOLVER_TEXTS, max_empties, time_limit_ms, n, "solved")
 
 
 def endgame_split_arg(split):
@@ -1151,59 +1178,99 @@ def _job_capacity_arg(job_capacity):
         raise ValueError("job_capacity must be None or an int in [0, 2^31), not %r" % (job_capacity,))
 
 
-def _solve_endgame_split(own, opp, n, mode, moves, max_empties, split, time_limit_ms, job_capacity, check_result):
-    """solve_endgame / solve_endgame_moves with split > 0 (iago_solve_endgame_split).  moves: None, "best" or "all"."""
-    dev = own.device
-    lib = _lib.lib()
-    a = _lib.EndgameSplitArgs()
+def _lane_outputs(a, own, opp, score_dtype, done_name, ctl_words, time_limit_ms, best=False, move_score=False):
+    """The output dict of a lane-search launch on the positions own / opp -- score, move, nodes, the done flag under its
+    name, ctl and, where asked for, best and move_score -- and the inputs that every Args mirror of the family names
+    alike, filled in a: the positions, n and time_limit_ms.  The outputs' pointers are _fill_outputs'."""
+    n, dev = own.numel(), own.device
+    if opp.numel() != n:
+        raise ValueError("own/opp sizes differ")
     a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
-    a.mode, a.split = ENDGAME_MODES[mode], split
-    a.max_empties, a.time_limit_ms = int(max_empties), int(time_limit_ms)
-    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
-               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
-               ctl=torch.empty(_lib.ENDGAME_SPLIT_CTL_WORDS, dtype=torch.int32, device=dev))
-    if moves is not None:
+    a.time_limit_ms = int(time_limit_ms)
+    out = {"score": torch.empty(n, dtype=score_dtype, device=dev), "move": torch.empty(n, dtype=torch.int8, device=dev),
+           "nodes": torch.empty(n, dtype=torch.int64, device=dev), done_name: torch.empty(n, dtype=torch.uint8, device=dev),
+           "ctl": torch.empty(ctl_words, dtype=torch.int32, device=dev)}
+    if best:
         out["best"] = torch.empty(n, dtype=torch.int64, device=dev)
-    if moves == "all":
+    if move_score:
         out["move_score"] = torch.empty((n, 64), dtype=torch.int8, device=dev)
+    return out
+
+
+def _fill_outputs(a, out, keys=None):
+    """a.<key> = the tensor out[key], for the keys named (None: all of out; every Args mirror names them as out does)."""
+    for k in out if keys is None else keys:
+        setattr(a, k, _dev(out[k], out[k].dtype, k))
+
+
+def _run_lanes(name, a, out, check_result):
+    """The launch of the unsplit entry point `name` on its arguments a; check_result: None, or the check of the host ctl
+    words, as _run_split calls it."""
+    _fill_outputs(a, out)
+    check(getattr(_lib.lib(), name)(C.byref(a), _stream()), name)
+    if check_result:
+        check_result(out["ctl"].tolist(), None)
+    return out
+
+
+def _run_split(name, a, out, job_capacity, check_result):
+    """The launches of the split entry point `name` on its arguments a, which hold everything but the jobs, and the jobs'
+    arrays into out.  job_capacity None: the count-only form and one readback first, the arrays then hold the jobs
+    exactly.  check_result: None, or what checks the launch -- called with its ctl words on the host and the job
+    capacity (a pure function of them: _check_lane_ctl)."""
+    entry = getattr(_lib.lib(), name)
+    n, dev = int(a.n), out["ctl"].device
     out.update(job_count=torch.empty(n, dtype=torch.int32, device=dev),
                job_first=torch.empty(n, dtype=torch.int64, device=dev))
-    a.job_count, a.job_first = _dev(out["job_count"], torch.int32, "job_count"), _dev(out["job_first"], torch.int64, "job_first")
-    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
+    _fill_outputs(a, out, ("ctl", "job_count", "job_first"))
     if job_capacity is None:
-        # the count-only form and one readback: the arrays hold the jobs exactly
-        check(lib.iago_solve_endgame_split(C.byref(a), _stream()), "iago_solve_endgame_split")
+        # (the count-only form: the job arrays null, and the roots' outputs, which it does not write, too)
+        check(entry(C.byref(a), _stream()), name)
         job_capacity = alphabeta_job_count(out["ctl"].tolist())
-    cap = int(job_capacity)
-    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
-    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
-    if moves is not None:
-        a.best = _dev(out["best"], torch.int64, "best")
-    if moves == "all":
-        a.move_score = _dev(out["move_score"], torch.int8, "move_score")
-    a.job_capacity = cap
+    _fill_outputs(a, out)
+    cap = a.job_capacity = int(job_capacity)
     for k, dt, cols in (("job_own", torch.int64, 1), ("job_opp", torch.int64, 1), ("job_root", torch.int32, 1),
-                        ("job_path", torch.int8, 4), ("job_score", torch.int8, 1), ("job_move", torch.int8, 1),
+                        ("job_path", torch.int8, 4), ("job_score", out["score"].dtype, 1), ("job_move", torch.int8, 1),
                         ("job_nodes", torch.int64, 1), ("job_done", torch.uint8, 1)):
         # (an empty tensor has no address, and null arrays are the count-only form: room for one job at least)
         t = torch.empty(max(cap, 1) * cols, dtype=dt, device=dev)
         setattr(a, k, _dev(t, dt, k))
         out[k] = t[:cap * cols].reshape(cap, 4) if cols == 4 else t[:cap]
     out["job_capacity"] = cap
-    check(lib.iago_solve_endgame_split(C.byref(a), _stream()), "iago_solve_endgame_split")
+    check(entry(C.byref(a), _stream()), name)
     if check_result:
         ctl = out["ctl"].tolist()
         out["jobs"] = alphabeta_job_count(ctl)
-        short = dict(first="the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap),
-                     jobs_needed=out["jobs"]) if ctl[6] else {}
-        _check_search_ctl(
-            "iago_solve_endgame_split", out, ctl,
-            "a job needed more stack frames than max_empties = %d sizes (ctl[3] set): it was dropped and its root "
-            "keeps solved = 0" % max_empties,
-            lambda: "gave up at its clock limit (%d ms): %d of %d positions unsolved" % (
-                time_limit_ms, n - int(out["solved"].sum().item()), n),
-            "%%d positions refused (own & opp != 0, or more than max_empties = %d empties)" % max_empties, **short)
+        check_result(ctl, cap)
     return out
+
+
+_SCORE_ONLY = object()   # `moves` of solve_endgame below
+
+
+def _solve_endgame(own, opp, mode, moves, max_empties, time_limit_ms, check_result, split, job_capacity):
+    """solve_endgame (moves: _SCORE_ONLY) and solve_endgame_moves: iago_solve_endgame, iago_solve_endgame_moves or,
+    with split > 0, iago_solve_endgame_split."""
+    if mode not in ENDGAME_MODES:
+        raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
+    if moves is not _SCORE_ONLY and moves not in ENDGAME_MOVES:
+        raise ValueError("moves must be 'best' or 'all', got %r" % (moves,))
+    split = endgame_split_arg(split)
+    _job_capacity_arg(job_capacity)
+    if split:
+        name, a = "iago_solve_endgame_split", _lib.EndgameSplitArgs()
+        a.split = split
+    elif moves is _SCORE_ONLY:
+        name, a = "iago_solve_endgame", _lib.EndgameArgs()
+    else:
+        name, a = "iago_solve_endgame_moves", _lib.EndgameMovesArgs()
+        a.moves = ENDGAME_MOVES[moves]
+    a.mode, a.max_empties = ENDGAME_MODES[mode], int(max_empties)
+    out = _lane_outputs(a, own, opp, torch.int8, "solved", _lib.ENDGAME_SPLIT_CTL_WORDS if split else _lib.ENDGAME_CTL_WORDS,
+                        time_limit_ms, best=moves is not _SCORE_ONLY, move_score=moves == "all")
+    checked = check_result and (lambda ctl, cap: _check_lane_ctl(name, out, ctl, _SOLVER_TEXTS, max_empties,
+                                                                 time_limit_ms, own.numel(), "solved", cap))
+    return _run_split(name, a, out, job_capacity, checked) if split else _run_lanes(name, a, out, checked)
 
 
 def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, time_limit_ms=ENDGAME_TIME_LIMIT_MS,
@@ -1227,33 +1294,7 @@ def solve_endgame(own, opp, mode="exact", max_empties=_lib.ENDGAME_MAX_EMPTIES, 
     count needed in `jobs_needed`.  The dict then also holds ctl (8,) int32 (ctl[4] / [5]: the jobs needed), job_count
     (n,) int32, job_first (n,) int64, the job arrays job_own, job_opp, job_root, job_path (the job's empties, first
     move, second move, 0), job_score, job_move, job_nodes, job_done, job_capacity and, with check_result, `jobs`."""
-    if mode not in ENDGAME_MODES:
-        raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
-    split = endgame_split_arg(split)
-    _job_capacity_arg(job_capacity)
-    n = own.numel()
-    if opp.numel() != n:
-        raise ValueError("own/opp sizes differ")
-    if split:
-        return _solve_endgame_split(own, opp, n, mode, None, max_empties, split, time_limit_ms, job_capacity,
-                                    check_result)
-    dev = own.device
-    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
-               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
-               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev))
-    a = _lib.EndgameArgs()
-    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
-    a.mode, a.max_empties, a.time_limit_ms = ENDGAME_MODES[mode], int(max_empties), int(time_limit_ms)
-    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
-    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
-    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
-    check(_lib.lib().iago_solve_endgame(C.byref(a), _stream()), "iago_solve_endgame")
-    if check_result:
-        _check_endgame_ctl(out, n, max_empties, time_limit_ms)
-    return out
-
-
-ENDGAME_MOVES = {"best": _lib.ENDGAME_MOVES_BEST, "all": _lib.ENDGAME_MOVES_ALL}
+    return _solve_endgame(own, opp, mode, _SCORE_ONLY, max_empties, time_limit_ms, check_result, split, job_capacity)
 
 
 def solve_endgame_moves(own, opp, mode="exact", moves="best", max_empties=_lib.ENDGAME_MAX_EMPTIES,
@@ -1267,37 +1308,7 @@ def solve_endgame_moves(own, opp, mode="exact", moves="best", max_empties=_lib.E
     that is no legal move of the mover (about 2.2 x the nodes).  check_result: as in solve_endgame.
     split = 1 or 2, job_capacity: as in solve_endgame -- the same best and move_score from iago_solve_endgame_split,
     whose jobs know every root move's exact value under either `moves`; the dict also holds its job arrays."""
-    if mode not in ENDGAME_MODES:
-        raise ValueError("mode must be 'exact' or 'wld', got %r" % (mode,))
-    if moves not in ENDGAME_MOVES:
-        raise ValueError("moves must be 'best' or 'all', got %r" % (moves,))
-    split = endgame_split_arg(split)
-    _job_capacity_arg(job_capacity)
-    n = own.numel()
-    if opp.numel() != n:
-        raise ValueError("own/opp sizes differ")
-    if split:
-        return _solve_endgame_split(own, opp, n, mode, moves, max_empties, split, time_limit_ms, job_capacity,
-                                    check_result)
-    dev = own.device
-    out = dict(score=torch.empty(n, dtype=torch.int8, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
-               nodes=torch.empty(n, dtype=torch.int64, device=dev), solved=torch.empty(n, dtype=torch.uint8, device=dev),
-               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev),
-               best=torch.empty(n, dtype=torch.int64, device=dev))
-    a = _lib.EndgameMovesArgs()
-    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
-    a.mode, a.moves = ENDGAME_MODES[mode], ENDGAME_MOVES[moves]
-    a.max_empties, a.time_limit_ms = int(max_empties), int(time_limit_ms)
-    a.score, a.move = _dev(out["score"], torch.int8, "score"), _dev(out["move"], torch.int8, "move")
-    a.nodes, a.solved = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["solved"], torch.uint8, "solved")
-    a.best, a.ctl = _dev(out["best"], torch.int64, "best"), _dev(out["ctl"], torch.int32, "ctl")
-    if moves == "all":
-        out["move_score"] = torch.empty((n, 64), dtype=torch.int8, device=dev)
-        a.move_score = _dev(out["move_score"], torch.int8, "move_score")
-    check(_lib.lib().iago_solve_endgame_moves(C.byref(a), _stream()), "iago_solve_endgame_moves")
-    if check_result:
-        _check_endgame_ctl(out, n, max_empties, time_limit_ms, who="iago_solve_endgame_moves")
-    return out
+    return _solve_endgame(own, opp, mode, moves, max_empties, time_limit_ms, check_result, split, job_capacity)
 
 
 def play_endgame(own, opp, turn, stones, pass_flg, parked=None, max_turns=IAGO_MAX_TURNS,
@@ -1397,57 +1408,6 @@ def alphabeta_split_arg(split, depth):
     return int(split)
 
 
-_ALPHABETA_GAVE_UP = "gave up at its clock limit (%d ms): %d of %d positions unfinished"
-
-
-def alphabeta_job_count(ctl):
-    """The jobs a split launch needed, from the host values of its ctl words."""
-    return (int(ctl[4]) & 0xFFFFFFFF) | ((int(ctl[5]) & 0xFFFFFFFF) << 32)
-
-
-def _alphabeta_moves_split(own, opp, n, depth, split, time_limit_ms, job_capacity, check_result):
-    """alphabeta_moves with split > 0 (iago_alphabeta_moves_split)."""
-    dev = own.device
-    lib = _lib.lib()
-    a = _lib.AlphaBetaSplitArgs()
-    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
-    a.depth, a.split, a.time_limit_ms = depth, split, int(time_limit_ms)
-    out = dict(score=torch.empty(n, dtype=torch.int16, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
-               nodes=torch.empty(n, dtype=torch.int64, device=dev), done=torch.empty(n, dtype=torch.uint8, device=dev),
-               ctl=torch.empty(_lib.ALPHABETA_SPLIT_CTL_WORDS, dtype=torch.int32, device=dev),
-               job_count=torch.empty(n, dtype=torch.int32, device=dev),
-               job_first=torch.empty(n, dtype=torch.int64, device=dev))
-    a.job_count, a.job_first = _dev(out["job_count"], torch.int32, "job_count"), _dev(out["job_first"], torch.int64, "job_first")
-    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
-    if job_capacity is None:
-        # the count-only form and one readback: the arrays hold the jobs exactly
-        check(lib.iago_alphabeta_moves_split(C.byref(a), _stream()), "iago_alphabeta_moves_split")
-        job_capacity = alphabeta_job_count(out["ctl"].tolist())
-    cap = int(job_capacity)
-    a.score, a.move = _dev(out["score"], torch.int16, "score"), _dev(out["move"], torch.int8, "move")
-    a.nodes, a.done = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["done"], torch.uint8, "done")
-    a.job_capacity = cap
-    for k, dt, cols in (("job_own", torch.int64, 1), ("job_opp", torch.int64, 1), ("job_root", torch.int32, 1),
-                        ("job_path", torch.int8, 4), ("job_score", torch.int16, 1), ("job_move", torch.int8, 1),
-                        ("job_nodes", torch.int64, 1), ("job_done", torch.uint8, 1)):
-        # (an empty tensor has no address, and null arrays are the count-only form: room for one job at least)
-        t = torch.empty(max(cap, 1) * cols, dtype=dt, device=dev)
-        setattr(a, k, _dev(t, dt, k))
-        out[k] = t[:cap * cols].reshape(cap, 4) if cols == 4 else t[:cap]
-    out["job_capacity"] = cap
-    check(lib.iago_alphabeta_moves_split(C.byref(a), _stream()), "iago_alphabeta_moves_split")
-    if check_result:
-        ctl = out["ctl"].tolist()
-        out["jobs"] = alphabeta_job_count(ctl)
-        short = dict(first="the search needs %d jobs, job_capacity holds %d: nothing was searched" % (out["jobs"], cap),
-                     jobs_needed=out["jobs"]) if ctl[6] else {}
-        _check_search_ctl("iago_alphabeta_moves_split", out, ctl,
-                          "a job needed more stack frames than depth = %d sizes (ctl[3] set)" % depth,
-                          lambda: _ALPHABETA_GAVE_UP % (time_limit_ms, n - int(out["done"].sum().item()), n),
-                          "%d positions refused (own & opp != 0)", **short)
-    return out
-
-
 def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_result=True, split=0, job_capacity=None):
     """A fixed-depth alpha-beta search on a hand-written evaluation for every position (iago_alphabeta_moves,
     include/iago_hip_serving.h): the opponent that owes nothing to the nets.
@@ -1471,28 +1431,17 @@ def alphabeta_moves(own, opp, depth, time_limit_ms=ENDGAME_TIME_LIMIT_MS, check_
     depth = alphabeta_depth_arg(depth)
     split = alphabeta_split_arg(split, depth)
     _job_capacity_arg(job_capacity)
-    n = own.numel()
-    if opp.numel() != n:
-        raise ValueError("own/opp sizes differ")
     if split:
-        return _alphabeta_moves_split(own, opp, n, depth, split, time_limit_ms, job_capacity, check_result)
-    dev = own.device
-    out = dict(score=torch.empty(n, dtype=torch.int16, device=dev), move=torch.empty(n, dtype=torch.int8, device=dev),
-               nodes=torch.empty(n, dtype=torch.int64, device=dev), done=torch.empty(n, dtype=torch.uint8, device=dev),
-               ctl=torch.empty(_lib.ENDGAME_CTL_WORDS, dtype=torch.int32, device=dev))
-    a = _lib.AlphaBetaArgs()
-    a.own, a.opp, a.n = _dev(own, torch.int64, "own"), _dev(opp, torch.int64, "opp"), n
-    a.depth, a.time_limit_ms = depth, int(time_limit_ms)
-    a.score, a.move = _dev(out["score"], torch.int16, "score"), _dev(out["move"], torch.int8, "move")
-    a.nodes, a.done = _dev(out["nodes"], torch.int64, "nodes"), _dev(out["done"], torch.uint8, "done")
-    a.ctl = _dev(out["ctl"], torch.int32, "ctl")
-    check(_lib.lib().iago_alphabeta_moves(C.byref(a), _stream()), "iago_alphabeta_moves")
-    if check_result:
-        _check_search_ctl("iago_alphabeta_moves", out, out["ctl"].tolist(),
-                          "a position needed more stack frames than depth = %d sizes (ctl[3] set)" % depth,
-                          lambda: _ALPHABETA_GAVE_UP % (time_limit_ms, n - int(out["done"].sum().item()), n),
-                          "%d positions refused (own & opp != 0)")
-    return out
+        name, a = "iago_alphabeta_moves_split", _lib.AlphaBetaSplitArgs()
+        a.split = split
+    else:
+        name, a = "iago_alphabeta_moves", _lib.AlphaBetaArgs()
+    a.depth = depth
+    out = _lane_outputs(a, own, opp, torch.int16, "done", _lib.ALPHABETA_SPLIT_CTL_WORDS if split else _lib.ENDGAME_CTL_WORDS,
+                        time_limit_ms)
+    checked = check_result and (lambda ctl, cap: _check_lane_ctl(name, out, ctl, _ALPHABETA_TEXTS, depth, time_limit_ms,
+                                                                 own.numel(), "done", cap))
+    return _run_split(name, a, out, job_capacity, checked) if split else _run_lanes(name, a, out, checked)
 
 
 def random_moves(own, opp, seed, id_base, id_mod, turn):

@@ -248,3 +248,63 @@ def test_solve_endgame_raises_when_the_stack_word_is_set():
         with pytest.raises(_lib.IagoError, match=what) as e:
             ops._check_endgame_ctl(out, 3, 12, 1000)
         assert e.value.result is out
+
+
+# (family, entry point, phrases, limit, done flag) and what each fault says, word for word
+LANE_FAMILIES = {
+    "solver": dict(
+        who="iago_solve_endgame", texts="_SOLVER_TEXTS", limit=12, done="solved",
+        overflow="a position needed more stack frames than max_empties = 12 sizes (ctl[3] set): it was dropped with "
+                 "solved = 0 and its outputs unwritten",
+        job_overflow="a job needed more stack frames than max_empties = 12 sizes (ctl[3] set): it was dropped and its "
+                     "root keeps solved = 0",
+        gave_up="gave up at its clock limit (1000 ms): 1 of 3 positions unsolved",
+        refused="2 positions refused (own & opp != 0, or more than max_empties = 12 empties)"),
+    "yardstick": dict(
+        who="iago_alphabeta_moves", texts="_ALPHABETA_TEXTS", limit=6, done="done",
+        overflow="a position needed more stack frames than depth = 6 sizes (ctl[3] set)",
+        job_overflow="a job needed more stack frames than depth = 6 sizes (ctl[3] set)",
+        gave_up="gave up at its clock limit (1000 ms): 1 of 3 positions unfinished",
+        refused="2 positions refused (own & opp != 0)"),
+}
+
+
+@pytest.mark.parametrize("family", sorted(LANE_FAMILIES))
+def test_the_lane_searches_result_check_is_a_function_of_the_host_ctl_words(family):
+    """ops._check_lane_ctl, what check_result runs for every entry point of both families, on CPU tensors and made-up
+    ctl words: a clean launch, a give-up, refusals, a stack overflow and -- a split launch -- a job overflow, which comes
+    first and carries the 64-bit count of ctl[4] / [5] as jobs_needed.  The texts are the entry points' own."""
+    import torch
+    from iago_amd import _lib, ops
+    f = LANE_FAMILIES[family]
+    out = {f["done"]: torch.tensor([1, 0, 1], dtype=torch.uint8)}
+
+    def run(who, ctl, job_capacity=None):
+        ops._check_lane_ctl(who, out, ctl, getattr(ops, f["texts"]), f["limit"], 1000, 3, f["done"], job_capacity)
+
+    def raised(who, ctl, job_capacity=None):
+        with pytest.raises(_lib.IagoError) as e:
+            run(who, ctl, job_capacity)
+        assert e.value.result is out
+        return e.value
+
+    who, split = f["who"], f["who"] + "_split"
+    run(who, [0, 3, 0, 0])                                        # clean launches: nothing raised
+    run(split, [0, 9, 0, 0, 9, 0, 0, 0], 9)
+    run(split, [0, 0, 0, 0, 0, 0, 0, 0], 0)
+    for name, ctl, cap, key in ((who, [1, 3, 0, 0], None, "gave_up"), (who, [0, 3, 2, 0], None, "refused"),
+                                (who, [0, 3, 0, 1], None, "overflow"), (who, [1, 3, 2, 1], None, "overflow"),
+                                (who, [1, 3, 2, 0], None, "gave_up"),
+                                (split, [1, 9, 0, 0, 9, 0, 0, 0], 9, "gave_up"),
+                                (split, [0, 9, 2, 0, 9, 0, 0, 0], 9, "refused"),
+                                (split, [0, 9, 0, 1, 9, 0, 0, 0], 9, "job_overflow"),
+                                (split, [1, 9, 2, 1, 9, 0, 0, 0], 9, "job_overflow")):
+        err = raised(name, ctl, cap)
+        assert str(err) == "%s: %s" % (name, f[key]), (name, ctl)
+        assert not hasattr(err, "jobs_needed")
+    # the jobs did not fit: first of all, with the count needed (ctl is read back as int32: a negative low word)
+    for ctl, needed in (([0, 0, 0, 0, 10, 0, 1, 0], 10), ([1, 0, 2, 1, 10, 0, 1, 0], 10),
+                        ([0, 0, 0, 0, -1, 2, 1, 0], 3 * 2 ** 32 - 1)):
+        err = raised(split, ctl, 9)
+        assert str(err) == "%s: the search needs %d jobs, job_capacity holds 9: nothing was searched" % (split, needed)
+        assert err.jobs_needed == needed
