@@ -12,7 +12,8 @@
 //     with three DPP steps (quad_perm xor 1, xor 2, row_half_mirror).
 //   * the rollout policy: lane r evaluates the 8 cells of board row r.
 // Rules follow the reference exactly (game.py:180-235, rl_env.py:88-138); the
-// bit-exact parity tests are tests/test_rules_gpu.py.
+// bit-exact parity tests are tests/test_rules_gpu.py and, on every content of
+// every board line, tests/test_rules_lines_gpu.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -4,7 +4,8 @@
 // Shared by the leaf rollout (rollout_lpb_kernel.hip), the endgame solver (endgame_kernel.hip) and the fixed-depth
 // alpha-beta opponent (alphabeta_kernel.hip).  Rules follow
 // the reference exactly (game.py:180-235); the rollout's bit-exact parity tests are tests/test_rollout_gpu.py, the
-// solver's tests/test_endgame_gpu.py.
+// solver's tests/test_endgame_gpu.py; tests/test_rules_lines_gpu.py holds legal_of / flips_of (through the alpha-beta
+// opponent's root split) and legal_moves_1 / flips_1 (through the rollout) to every content of every board line.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

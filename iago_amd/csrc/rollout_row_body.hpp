@@ -148,7 +148,8 @@ __device__ __forceinline__ uint64_t flips_hw(uint64_t o, uint64_t p, uint32_t po
 // DIAG: the instance of the parity tests (the launch records the action of every turn and / or
 // takes its uniforms from a buffer); a wave alone on its SIMD pays a full issue slot for every
 // instruction, scalar ones and branches included, so the production instance does not even
-// test those pointers.
+// test those pointers.  The parity tests: tests/test_rollout_gpu.py and, legal_hw / flips_hw on every
+// content of every board line in both instances, tests/test_rules_lines_gpu.py.
 // ASYNC: the per-board mask and stream ids of HwParams (prologue only; the turn loop is the same).
 // INDEXED (the persistent search): the 16 boards of the call are boards idx[0..15] (-1 = no board in that row of
 // lanes) instead of boards 16 block_id ..; `table_ready`: the factor table is in LDS already (an earlier call of
