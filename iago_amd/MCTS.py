@@ -19,6 +19,11 @@ sign turns at every level: engine.backup_arg; the persistent search only, with o
 
 selection = "reference" (the default: the reference's Node.select, priors prob + 0.1 and 0.01 + n under the exploration
 term) or "alphazero" (priors prob, 1 + n: engine.selection_arg; the persistent search only, with or without wave=).
+
+gumbel = (m, c_scale_256[, c_visit]) (None, the default: off): get_move runs the Gumbel root search (engine.BatchedMCTS.search(
+gumbel=); include/iago_hip_serving.h) -- a fresh root, n_sims playouts in sequential halving over the top m moves by
+Gumbel + logit, the survivor for a move.  It needs n_sims (the schedule is the budget's), backup="negamax",
+selection="alphazero" and wave=1; the k-th get_move of the object draws as turn k of game `seed`'s id 0.
 """
 import time
 
@@ -41,7 +46,7 @@ class MCTS(object):
     def __init__(self, lmbda=0.5, c_puct=1, n_thr=15, time_limit=10, policy_net=None,
                  value_net=None, rollout_weights=None, n_sims=None, capacity=65536, seed=0,
                  use_graph=False, wave=1, virtual_loss=1.0, solve_empties=None, backup="reference",
-                 selection="reference"):
+                 selection="reference", gumbel=None):
         if policy_net is None or (value_net is None and lmbda < 1):
             raise ValueError("policy_net / value_net are required (the reference loads "
                              "./models/sl_model.npz and ./models/value_model.npz here)")
@@ -61,6 +66,10 @@ class MCTS(object):
                                                                                         solve_empties))
         self.solve_empties = solve_empties
         self.n_solved = 0
+        self.gumbel = self._m._gumbel_arg(gumbel)
+        if self.gumbel is not None and n_sims is None:
+            raise ValueError("gumbel needs n_sims: the halving's schedule is built for the budget")
+        self._turn = 0   # (gumbel: searched get_move calls so far, the draw's turn)
 
     def get_move(self, state, color):
         """MCTS.py:139-147: playouts from the root, then the most visited child."""
@@ -72,6 +81,13 @@ class MCTS(object):
                 if move >= 0:   # (a pass or a finished game: the search answers as it always has)
                     self.n_solved += 1
                     return move
+        if self.gumbel is not None:
+            self._m.search(own, opp, self._one, self.n_sims, gumbel=self.gumbel, turn=self._turn)
+            self._turn += 1
+            move = int(self._m.gumbel_move(self._one)[0].item())
+            if move == -2:
+                raise ValueError("max() arg is an empty sequence: the root has no children (fewer than n_thr playouts)")
+            return move
         if self.n_sims is not None:
             self._m.search(own, opp, self._one, self.n_sims)
         else:

@@ -54,7 +54,8 @@ EXPERIMENTAL_SYMBOLS = [
 # playouts and policy-target pruning (SelfPlayEngine.play(forced_playouts=)), the fixed-depth alpha-beta opponent and its
 # random openings (ops.alphabeta_moves, ops.random_moves; SelfPlayEngine.play_match(opponent=AlphaBeta(d))), that
 # search with every root spread over the lanes (ops.alphabeta_moves(split=), AlphaBeta(d, split)), and the exact solver
-# spread the same way (ops.solve_endgame(split=), ops.solve_endgame_moves(split=))
+# spread the same way (ops.solve_endgame(split=), ops.solve_endgame_moves(split=)), and the Gumbel root search
+# (SelfPlayEngine.play(gumbel=), BatchedMCTS.search(gumbel=))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_solve_endgame_moves", "iago_play_endgame_moves",
@@ -63,6 +64,7 @@ SERVING_SYMBOLS = [
     "iago_mcts_root_noise", "iago_mcts_search_noise",
     "iago_mcts_search_forced", "iago_mcts_prune_visits", "iago_mcts_prune_visits_rule",
     "iago_alphabeta_moves", "iago_random_moves", "iago_alphabeta_moves_split", "iago_solve_endgame_split",
+    "iago_mcts_gumbel_draw", "iago_mcts_search_gumbel", "iago_mcts_gumbel_finish",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
@@ -274,6 +276,9 @@ CAP_KEY = 0x43415050      # the playout cap's full / fast decision per turn: the
 CAP_SEED_XOR = CAP_KEY << 32
 NOISE_KEY = 0x44495249    # the root noise's urn draws: the same, with this word (IAGO_NOISE_KEY)
 NOISE_SEED_XOR = NOISE_KEY << 32
+GUMBEL_KEY = 0x47554D42   # the Gumbel root search's draws: the same, with this word (IAGO_GUMBEL_KEY)
+GUMBEL_SEED_XOR = GUMBEL_KEY << 32
+GUMBEL_C_VISIT = 50       # gumbel=(m, c_scale_256): sigma's c_visit unless the caller gives a third number
 NOISE_DRAWS = 256         # root_noise=(alpha_256, eps_256): the urn's draws N unless the caller gives a third number
 CTL_BAD_DRAW = 13         # ctl word a match raises when a policy draw found no mass on the legal moves
 REC_DRAWN = 2             # rec_valid of a move played without a search (a policy draw or a forced final move)
@@ -454,6 +459,21 @@ class SearchForcedArgs(C.Structure):
     ]
 
 
+class GumbelRoot(C.Structure):
+    """Mirror of iago_gumbel_root (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("gumbel_q16", C.c_void_p), ("ln_q16", C.c_void_p), ("sched", C.c_void_p), ("g", C.c_void_p),
+        ("m", C.c_int32), ("c_scale_256", C.c_int32), ("c_visit", C.c_int32), ("reserved0", C.c_int32),
+    ]
+
+
+class SearchGumbelArgs(C.Structure):
+    """Mirror of iago_search_gumbel_args (include/iago_hip_serving.h)."""
+    _fields_ = [
+        ("gumbel", GumbelRoot), ("streams", C.c_void_p), ("reserved", C.c_int64 * 4),
+    ]
+
+
 class ValueSplitArgs(C.Structure):
     """Mirror of iago_value_split_args (include/iago_hip.h)."""
     _fields_ = [
@@ -592,6 +612,9 @@ def lib():
     L.iago_mcts_root_noise.argtypes = [tp, vp, vp, vp, C.c_uint64, vp, vp, C.POINTER(RootNoise), vp]
     L.iago_mcts_search_noise.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchNoiseArgs), vp]
     L.iago_mcts_search_forced.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchForcedArgs), vp]
+    L.iago_mcts_gumbel_draw.argtypes = [tp, vp, C.c_uint64, vp, vp, C.POINTER(GumbelRoot), vp]
+    L.iago_mcts_search_gumbel.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(SearchGumbelArgs), vp]
+    L.iago_mcts_gumbel_finish.argtypes = [tp, vp, C.POINTER(GumbelRoot), vp, vp, vp, vp, vp]
     L.iago_mcts_prune_visits.argtypes = [tp, vp, C.c_float, i32, vp, vp]
     L.iago_mcts_prune_visits_rule.argtypes = [tp, vp, C.c_float, i32, i32, vp, vp]
     L.iago_mcts_search_arena.argtypes = [C.POINTER(MctsSearchArgs), C.POINTER(MctsSearchArgs), vp]

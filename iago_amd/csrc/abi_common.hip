@@ -1,8 +1,10 @@
 // abi_common.hip -- version, device probe and error reporting of the C ABI.
 #include "abi_common.hpp"
+#include "../../include/iago_hip_serving.h" // (iago_gumbel_root)
 
 #include <stdio.h>
 #include <string.h>
+#include <string>
 
 namespace {
 thread_local char g_err[512] = "";
@@ -12,6 +14,24 @@ int iago_fail(int code, const char *msg)
 {
     snprintf(g_err, sizeof g_err, "%s", msg);
     return code;
+}
+
+int iago_check_gumbel_root(const iago_gumbel_root *gz, const char *who)
+{
+    const std::string w(who);
+    if (!gz)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": null gumbel arguments").c_str());
+    if (gz->reserved0 != 0)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": reserved fields must be 0").c_str());
+    if (gz->m < 2 || gz->m > 64)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": m must be in [2, 64]").c_str());
+    if (gz->c_scale_256 < 1 || gz->c_scale_256 > 4096)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": c_scale_256 must be in [1, 4096]").c_str());
+    if (gz->c_visit < 0 || gz->c_visit > 4096)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": c_visit must be in [0, 4096]").c_str());
+    if (!gz->gumbel_q16 || !gz->ln_q16 || !gz->g)
+        return iago_fail(IAGO_ERR_INVALID, (w + ": null table or draws buffer (gumbel_q16, ln_q16 and g expected)").c_str());
+    return IAGO_OK;
 }
 
 int iago_check_launch(const char *where)

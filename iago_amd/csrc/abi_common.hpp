@@ -9,6 +9,12 @@ int iago_fail(int code, const char *msg);
 // hipGetLastError() after a launch -> IAGO_OK / IAGO_ERR_HIP.
 int iago_check_launch(const char *where);
 
+// The arguments of the Gumbel root search (iago_gumbel_root, include/iago_hip_serving.h) as the three entry points that take
+// them check them: null, reserved0, m in [2, 64], c_scale_256 in [1, 4096], c_visit in [0, 4096], the two tables and g.
+// `who`: the entry point, which the refusal's text begins with.  IAGO_OK or IAGO_ERR_INVALID.
+struct iago_gumbel_root;
+int iago_check_gumbel_root(const iago_gumbel_root *gz, const char *who);
+
 // The current device's compute units (asked once per process); 0 when there is no HIP device.
 int iago_device_cus();
 

@@ -437,6 +437,32 @@ __device__ __forceinline__ void noise_remix_children(const Tree &T, int64_t base
     }
 }
 
+// ---- the Gumbel root search ("Gumbel root search"; the contract is iago_hip_serving.h's): the
+// root's rule in integers, Q16.  The tables (gumbel_q16, ln_q16) and the schedule come from the host; nothing here calls log
+// or exp
+constexpr uint32_t GUMBEL_KEY = IAGO_GUMBEL_KEY; // ("GUMB")
+constexpr int GUMBEL_LN2_Q16 = 45426;            // round(65536 ln 2)
+
+// logit_q16 of a stored prior p > 0: (e - 127) round(65536 ln 2) + ln_q16[f >> 11] of its exponent and mantissa bits
+__device__ __forceinline__ int gumbel_logit_q16(float p, const int32_t *__restrict__ ln_q16)
+{
+    const uint32_t b = __float_as_uint(p);
+    return ((int)((b >> 23) & 0xFFu) - 127) * GUMBEL_LN2_Q16 + ln_q16[(b & 0x7FFFFFu) >> 11];
+}
+
+// q16 of a child with value q after n visits: 0 .. 65536 for q in [-1, 1] (q 32768 is exact in float32; ties to even)
+__device__ __forceinline__ int gumbel_q16(float q, int n)
+{
+    return n > 0 ? (int)rintf(q * 32768.0f) + 32768 : 0;
+}
+
+// g + logit + sigma as a float64 (exact: below 2^53), sigma = ((c_visit + maxN) c_scale_256 q16) >> 8 in int64
+__device__ __forceinline__ double gumbel_score(int g, int logit, int q16, int max_n, int c_visit, int c_scale_256)
+{
+    const int64_t sigma = ((int64_t)(c_visit + max_n) * (int64_t)c_scale_256 * (int64_t)q16) >> 8;
+    return (double)((int64_t)g + (int64_t)logit + sigma);
+}
+
 // Diagnostic record of the parity tests (tests/test_mcts_production_gpu.py): the z every playout of game g backed up, in
 // playout order -- what the oracle's rollout_fn replays (z_log [rows][n_games], z_log_n [n_games] rows written so far)
 __device__ __forceinline__ void log_z(int8_t *z_log, int32_t *z_log_n, int rows, int64_t g, int64_t n_games, int8_t zg)

@@ -305,6 +305,77 @@ __global__ __launch_bounds__(BLOCK) void root_noise_kernel(Tree T, const uint8_t
         noise_remix_children(T, base, rfc, lg, L.l8, c, eps_256, draws_log2);
 }
 
+// root_noise_kernel's sibling for the Gumbel root search (iago_mcts_gumbel_draw), one lane per game and cell: the draw of
+// cell a at turn[g] of game game_id[g] -- table[c0 >> 16], c0 word 0 of Philox4x32-10 on (game id, turn, a, 0) under the
+// rollouts' key with its high word XOR GUMBEL_KEY.  Independent of the priors: it runs before the search.  Inactive games:
+// nothing written
+__global__ __launch_bounds__(BLOCK) void gumbel_draw_kernel(int64_t n_games, const uint8_t *__restrict__ active, uint32_t key0,
+                                                            uint32_t key1, const int32_t *__restrict__ game_id,
+                                                            const int32_t *__restrict__ turn,
+                                                            const int32_t *__restrict__ table, int32_t *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x, g = i >> 6;
+    if (g >= n_games || (active && !active[g]))
+        return;
+    uint32_t c[4] = {(uint32_t)game_id[g], (uint32_t)turn[g], (uint32_t)(i & 63), 0u};
+    philox4x32_10(c, key0, key1 ^ GUMBEL_KEY);
+    out[i] = table[c[0] >> 16];
+}
+
+// best_move_kernel's sibling for the Gumbel root search (iago_mcts_gumbel_finish), one lane per game: the move -- of the
+// root's children with the largest visit count the first maximum of gumbel_score; one child or none: best_move's answer --
+// and the three rows by cell the improved-policy target is made from: n, q (0 where unvisited), logit_q16 (INT32_MIN off
+// the children).  The trees are only read.  Inactive games: nothing written
+__global__ __launch_bounds__(BLOCK) void gumbel_finish_kernel(Tree T, const uint8_t *__restrict__ active,
+                                                              const int32_t *__restrict__ gdraw,
+                                                              const int32_t *__restrict__ ln_q16, int c_visit, int c_scale_256,
+                                                              int8_t *__restrict__ move, int32_t *__restrict__ row_n,
+                                                              float *__restrict__ row_q, int32_t *__restrict__ row_logit)
+{
+    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= T.n_games || (active && !active[g]))
+        return;
+    const int64_t base = g * (int64_t)T.capacity;
+    const int root = T.root[g];
+    const int fc = T.nodes[base + root].first_child;
+    const int k = fc >= 0 ? (int)T.nodes[base + root].n_children : 0;
+    for (int a = 0; a < 64; a++) {
+        row_n[g * 64 + a] = 0;
+        row_q[g * 64 + a] = 0.0f;
+        row_logit[g * 64 + a] = INT32_MIN;
+    }
+    int best = -2, max_n = -1;
+    for (int j = 0; j < k; j++) {
+        const int n = T.nodes[base + fc + j].n_visits;
+        const int a = (int)T.nodes[base + fc + j].action;
+        if (n > max_n) { // (one child: best_move's answer)
+            max_n = n;
+            best = a;
+        }
+        if (a >= 0) {
+            row_n[g * 64 + a] = n;
+            row_q[g * 64 + a] = n > 0 ? T.nodes[base + fc + j].q : 0.0f;
+            row_logit[g * 64 + a] = gumbel_logit_q16(T.nodes[base + fc + j].p, ln_q16);
+        }
+    }
+    if (k >= 2) {
+        double best_v = -INFINITY;
+        for (int j = 0; j < k; j++) {
+            const int n = T.nodes[base + fc + j].n_visits;
+            const int a = (int)T.nodes[base + fc + j].action;
+            if (n != max_n)
+                continue;
+            const double v = gumbel_score(gdraw[g * 64 + (a & 63)], gumbel_logit_q16(T.nodes[base + fc + j].p, ln_q16),
+                                          gumbel_q16(T.nodes[base + fc + j].q, n), max_n, c_visit, c_scale_256);
+            if (v > best_v) { // (strict: the lowest index wins a tie)
+                best_v = v;
+                best = a;
+            }
+        }
+    }
+    move[g] = (int8_t)best;
+}
+
 // best_move_kernel's sibling for the policy-target pruning (iago_mcts_prune_visits), 8 lanes per game: the visit row of
 // the root's children with the forced playouts taken out wherever PUCT would not have granted them -- the rule of
 // iago_hip_serving.h with mcts_dev.hpp's forced_child and puct_score (visit_off: the selection rule's, 0.01 unless
@@ -1187,6 +1258,39 @@ int iago_mcts_root_noise(const iago_mcts_tree *tree, const uint8_t *active, cons
                        (uint32_t)noise->alpha_256, (uint32_t)noise->eps_256, (uint32_t)__builtin_ctz((uint32_t)noise->draws),
                        noise->counts);
     return iago_check_launch("iago_mcts_root_noise");
+}
+
+int iago_mcts_gumbel_draw(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
+                          const int32_t *turn, const iago_gumbel_root *gumbel, void *stream)
+{
+    if (check_tree(tree, "iago_mcts_gumbel_draw: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (!game_id || !turn)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_gumbel_draw: null pointer (game_id and turn expected)");
+    if (const int rc = iago_check_gumbel_root(gumbel, "iago_mcts_gumbel_draw"))
+        return rc;
+    if (tree->n_games == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(gumbel_draw_kernel, dim3(grid_for(tree->n_games * 64)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       (int64_t)tree->n_games, active, (uint32_t)seed, (uint32_t)(seed >> 32), game_id, turn,
+                       gumbel->gumbel_q16, gumbel->g);
+    return iago_check_launch("iago_mcts_gumbel_draw");
+}
+
+int iago_mcts_gumbel_finish(const iago_mcts_tree *tree, const uint8_t *active, const iago_gumbel_root *gumbel, int8_t *move,
+                            int32_t *n, float *q, int32_t *logit, void *stream)
+{
+    if (check_tree(tree, "iago_mcts_gumbel_finish: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (!move || !n || !q || !logit)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_gumbel_finish: null pointer (move, n, q and logit expected)");
+    if (const int rc = iago_check_gumbel_root(gumbel, "iago_mcts_gumbel_finish"))
+        return rc;
+    if (tree->n_games == 0)
+        return IAGO_OK;
+    hipLaunchKernelGGL(gumbel_finish_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0, (hipStream_t)stream, *tree, active,
+                       gumbel->g, gumbel->ln_q16, (int)gumbel->c_visit, (int)gumbel->c_scale_256, move, n, q, logit);
+    return iago_check_launch("iago_mcts_gumbel_finish");
 }
 
 // both pruning entry points, WHO (a string literal) naming the one called in its refusals; visit_off is its selection rule's

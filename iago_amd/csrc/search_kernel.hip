@@ -181,7 +181,17 @@ struct SearchParams {
     // parameters after a SearchParams move)
     float prior_off;
     double visit_off;
+    // the Gumbel root search (iago_mcts_search_gumbel; the ROOT_GUMBEL instantiations alone read these): the draws by cell
+    // [n_games][64] that iago_mcts_gumbel_draw wrote before the launch, the host's ln table and schedule [m + 1][n_sims],
+    // the moves considered and the two constants of sigma.  (After visit_off: the plain kernels' fields stay where they were)
+    const int32_t *gumbel_g, *gumbel_ln;
+    const int16_t *gumbel_sched;
+    int32_t gumbel_m, gumbel_c_visit, gumbel_c_scale;
 };
+
+// The rule at the root of a search (the path's first node), by instantiation: none, root noise with forced playouts
+// (iago_mcts_search_noise / _forced), the Gumbel rule (iago_mcts_search_gumbel).  The plain kernels compile none of it.
+constexpr int ROOT_PLAIN = 0, ROOT_NOISE = 1, ROOT_GUMBEL = 2;
 
 __device__ __forceinline__ u64 ld(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
 __device__ __forceinline__ void st(u64 *p, u64 x) { __hip_atomic_store(p, x, RLX_AGENT); }
@@ -900,7 +910,7 @@ __device__ __forceinline__ void reach_leaf(const SearchParams &S, const Slot &I,
 // a net, else with the priors -- which, when they have not arrived, the descent stops to ask for
 // NOISE: the children of the game's ROOT (the path's first node) are created with the mixed priors, from the game's counts
 // row (iago_mcts_root_noise wrote it before the launch)
-template <bool NOISE>
+template <int NOISE>
 __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cursor &C, bool &descending, bool have_priors,
                                        bool &need_prior)
 {
@@ -921,7 +931,7 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
                 const int nf = (int)fc1 - 1;
                 make_children(T, I.base, nf, C.node, lg, I.r, S.prior_off,
                               [&](int a) { return __uint_as_float(rq::reply_bits(ld(&S.rep_p[I.g * 64 + a]))); });
-                if constexpr (NOISE) {
+                if constexpr (NOISE == ROOT_NOISE) {
                     if (C.path_n == 1 && kn > 1) {
                         uint32_t c[8];
 #pragma unroll
@@ -940,18 +950,64 @@ __device__ __forceinline__ void expand(const SearchParams &S, const Slot &I, Cur
     __threadfence_block(); // the new children are read by the other lanes of the group below
 }
 
+// score_child's sibling under the Gumbel rule: child j of the root, whose record is (s, l), offers its score when it has
+// `want` visits; the same strict `>` and the same payload
+__device__ __forceinline__ void gumbel_child(const SearchParams &S, const Slot &I, uint4 s, uint4 l, int j, int want, int max_n,
+                                             double &best_v, int &best_i, uint32_t (&pl)[4])
+{
+    const int n = (int)s.x;
+    if (n != want)
+        return;
+    const int a = (int)(int8_t)(l.z & 0xFFu);
+    const double v = gumbel_score(S.gumbel_g[I.gt * 64 + (a & 63)], gumbel_logit_q16(__uint_as_float(s.z), S.gumbel_ln),
+                                  gumbel_q16(__uint_as_float(s.y), n), max_n, S.gumbel_c_visit, S.gumbel_c_scale);
+    if (v > best_v) {
+        best_v = v;
+        best_i = j;
+        pl[0] = l.x, pl[1] = (uint32_t)n, pl[2] = l.z & 0xFFFFu, pl[3] = s.w;
+    }
+}
+
 // Node.select: two children per lane and step, the argmax over the 8 lanes; the stone; the cursor at the child
 // NOISE: at the ROOT of the search (the path's first node) with two or more children a forced child -- mcts_dev.hpp's
 // forced_child of its visits, its stored prior and the root's visits, under S.forced_k_256 -- scores +inf
-template <bool WAVE, bool NOISE>
+// ROOT_GUMBEL: at the same node the Gumbel rule of iago_hip_serving.h replaces the score: the children whose visit count is
+// the schedule's for this playout score g + logit + sigma (mcts_dev.hpp, gumbel_score), every other child -inf
+template <bool WAVE, int NOISE>
 __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I, Cursor &C, bool descending)
 {
     const int kk = descending ? C.k : 0;
     const double sq = sqrt((double)(WAVE ? C.nv + C.nvv : C.nv));
-    const double force_k = (NOISE && C.path_n == 1 && kk >= 2) ? (double)S.forced_k_256 : 0.0, force_n = (double)C.nv;
+    const double force_k = (NOISE == ROOT_NOISE && C.path_n == 1 && kk >= 2) ? (double)S.forced_k_256 : 0.0, force_n = (double)C.nv;
     double best_v = -INFINITY;
     int best_i = 0x7fffffff;
     uint32_t pl[4] = {0u, 0u, 0u, 0u};
+    // the Gumbel rule's root: t = the children's visits, max_n their largest, `want` the visit count that is served now --
+    // the schedule's, or max_n where no child has the schedule's (a root that was not fresh).  Every lane of the group
+    // takes part in the three reductions; a game that is not at its root reduces zeros
+    [[maybe_unused]] bool groot = false;
+    [[maybe_unused]] int want = 0, max_n = 0;
+    if constexpr (NOISE == ROOT_GUMBEL) {
+        groot = C.path_n == 1 && kk >= 2;
+        const int kg = groot ? kk : 0;
+        uint32_t t = 0u, mx = 0u;
+        for (int j = (int)I.r; j < kg; j += 8) {
+            const uint32_t n = (uint32_t)S.T.nodes[I.base + C.fc + j].n_visits;
+            t += n;
+            mx = max(mx, n);
+        }
+        t = group8_add(t);
+        mx = max(mx, dpp_u32<DPP_XOR1>(mx));
+        mx = max(mx, dpp_u32<DPP_XOR2>(mx));
+        mx = max(mx, dpp_u32<DPP_HALF_MIRROR>(mx));
+        max_n = (int)mx;
+        const int row = kk < S.gumbel_m ? kk : S.gumbel_m, col = (int)t < S.n_sims - 1 ? (int)t : S.n_sims - 1;
+        want = groot ? (int)S.gumbel_sched[(int64_t)row * S.n_sims + col] : 0;
+        uint32_t hit = 0u;
+        for (int j = (int)I.r; j < kg; j += 8)
+            hit |= S.T.nodes[I.base + C.fc + j].n_visits == want ? 1u : 0u;
+        want = group8_add(hit) != 0u ? want : max_n;
+    }
     for (int j0 = (int)I.r; j0 < kk; j0 += 16) {
         const int j1 = j0 + 8;
         const bool two = j1 < kk;
@@ -959,9 +1015,19 @@ __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I
         uint4 s0, l0, s1, l1;
         node_record(S.T, c0, s0, l0);
         node_record(S.T, c1, s1, l1);
-        score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s0, l0, j0, sq, best_v, best_i, pl, force_k, force_n);
+        if constexpr (NOISE == ROOT_GUMBEL) {
+            if (groot) {
+                gumbel_child(S, I, s0, l0, j0, want, max_n, best_v, best_i, pl);
+                if (two)
+                    gumbel_child(S, I, s1, l1, j1, want, max_n, best_v, best_i, pl);
+                continue;
+            }
+        }
+        score_child<WAVE, NOISE == ROOT_NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s0, l0, j0, sq, best_v, best_i, pl, force_k,
+                                               force_n);
         if (two)
-            score_child<WAVE, NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s1, l1, j1, sq, best_v, best_i, pl, force_k, force_n);
+            score_child<WAVE, NOISE == ROOT_NOISE>(S.c_puct, (double)S.vloss, S.visit_off, s1, l1, j1, sq, best_v, best_i, pl,
+                                                   force_k, force_n);
     }
     argmax_step_payload<DPP_XOR1>(best_v, best_i, pl);
     argmax_step_payload<DPP_XOR2>(best_v, best_i, pl);
@@ -980,7 +1046,7 @@ __device__ __forceinline__ int select_child(const SearchParams &S, const Slot &I
 // ---- 4. descent (MCTS.py:105-133; the games' lanes): from the root, or on from the leaf whose priors arrived, to a node
 // that waits for its priors or to the playout's leaf.  A wave search: one step of its trees' slot order (the slot whose
 // turn it is), seeing the in-flight visits and the expansions of the slots before it.  Returns whether the game descended
-template <bool WAVE, bool NOISE>
+template <bool WAVE, int NOISE>
 __device__ __forceinline__ bool descend(const SearchParams &S, const Slot &I, GameShared<WAVE> &sh, Game &G, Cursor &C,
                                         int pace_limit, int &st_levels, int &st_children)
 {
@@ -1357,7 +1423,7 @@ __device__ __forceinline__ void epilogue(const SearchParams &S, const Slot &I, G
     }
 }
 
-template <bool WAVE, bool PARK = false, bool NOISE = false>
+template <bool WAVE, bool PARK = false, int NOISE = ROOT_PLAIN>
 __device__ __forceinline__ void game_workgroup(const SearchParams &S, const iago_row::HwParams &R, const long long t0, const int wg)
 {
     __shared__ GameShared<WAVE> sh;
@@ -1704,7 +1770,7 @@ __device__ __forceinline__ void net_workgroup(const SearchParams &S, const iago_
 // ONE grid: the game workgroups first (they are dispatched first, so all of them are resident whatever else
 // holds CUs; a net workgroup never waits for another net workgroup, so one that finds no CU free simply starts
 // late), then the net workgroups.  A game workgroup whose games are done serves the queue like the others.
-template <bool WAVE, bool PARK = false, bool NOISE = false>
+template <bool WAVE, bool PARK = false, int NOISE = ROOT_PLAIN>
 __device__ __forceinline__ void search_body(const SearchParams &S, const iago_row::HwParams &R, const iago_trunk::TrunkRParams &VP,
                                             const iago_policy::PolicyParams &PP)
 {
@@ -1764,13 +1830,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_noise_kernel(
     SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
 {
-    search_body<false, false, true>(S, R, VP, PP);
+    search_body<false, false, ROOT_NOISE>(S, R, VP, PP);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_noise_kernel(SearchParams S,
                                                                                                          iago_row::HwParams R)
 {
-    game_workgroup<false, false, true>(S, R, wall_clock64(), (int)blockIdx.x);
+    game_workgroup<false, false, ROOT_NOISE>(S, R, wall_clock64(), (int)blockIdx.x);
+}
+
+// The search under the Gumbel root rule (iago_mcts_search_gumbel: one search per launch): instantiations of their own once
+// more, for the single launch and the role split's game launch.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_gumbel_kernel(
+    SearchParams S, iago_row::HwParams R, iago_trunk::TrunkRParams VP, iago_policy::PolicyParams PP)
+{
+    search_body<false, false, ROOT_GUMBEL>(S, R, VP, PP);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void search_game_gumbel_kernel(SearchParams S,
+                                                                                                          iago_row::HwParams R)
+{
+    game_workgroup<false, false, ROOT_GUMBEL>(S, R, wall_clock64(), (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void search_net_kernel(
@@ -1844,7 +1924,7 @@ __global__ void search_scratch_warm_kernel(uint32_t *out, int n)
 
 // The kernels a search can be launched as, and what the runtime has said of each.  It is asked once per device (a
 // process may drive several): every launch comes through here.
-enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, F_NOISE, F_GAME_NOISE, N_FORMS };
+enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, F_NOISE, F_GAME_NOISE, F_GUMBEL, F_GAME_GUMBEL, N_FORMS };
 
 struct FormCache {
     const void *kernel;
@@ -1857,7 +1937,8 @@ struct FormCache {
                          {(const void *)search_park_kernel}, {(const void *)search_game_kernel},
                          {(const void *)search_game_park_kernel}, {(const void *)search_net_kernel},
                          {(const void *)search_arena_kernel},     {(const void *)search_noise_kernel},
-                         {(const void *)search_game_noise_kernel}};
+                         {(const void *)search_game_noise_kernel}, {(const void *)search_gumbel_kernel},
+                         {(const void *)search_game_gumbel_kernel}};
 std::mutex form_cache_mutex; // (static_lds and on[]; `reserved` is iago_reserve_lds's own)
 
 // reserves `bytes` of dynamic LDS for the form on the current device; `who`: the message of a failure
@@ -1935,6 +2016,7 @@ struct LaunchRequest {
     int cap_fast = 0, cap_full_256 = 256;         // the playout cap: playouts of a fast turn, full turns in 256
     const iago_root_noise *noise = nullptr;       // root noise: the counts rows applied where a root expands
     int forced_k_256 = 0;                         // forced playouts at the root (with noise): k_256, 0 = none
+    const iago_gumbel_root *gumbel = nullptr;     // the Gumbel root rule: tables, schedule, draws and constants
 };
 
 // games_per_workgroup without its flags (IAGO_SEARCH_CHAIN_SKIP, IAGO_SEARCH_NEGAMAX, IAGO_SEARCH_PUCT_AZ)
@@ -2050,8 +2132,8 @@ int size_grid(const iago_mcts_search_args *a, const LaunchRequest &q, SearchGrid
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: the streams belong to another device");
         if (a->max_cus != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
-        // (park, noise: the game launch's other instantiations, with books of their own)
-        const Form game = q.noise ? F_GAME_NOISE : q.park ? F_GAME_PARK : F_GAME;
+        // (park, noise, gumbel: the game launch's other instantiations, with books of their own)
+        const Form game = q.gumbel ? F_GAME_GUMBEL : q.noise ? F_GAME_NOISE : q.park ? F_GAME_PARK : F_GAME;
         const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
         int fixed = 0, per_game = 0;
         if (!static_lds_of(game, fixed))
@@ -2182,6 +2264,12 @@ SearchParams search_params(const iago_mcts_search_args *a, const SearchGrid &G, 
     S.noise_eps = q.noise ? q.noise->eps_256 : 0;
     S.noise_lg = q.noise ? __builtin_ctz((unsigned)q.noise->draws) : 0;
     S.forced_k_256 = q.noise ? q.forced_k_256 : 0;
+    S.gumbel_g = q.gumbel ? q.gumbel->g : nullptr;
+    S.gumbel_ln = q.gumbel ? q.gumbel->ln_q16 : nullptr;
+    S.gumbel_sched = q.gumbel ? q.gumbel->sched : nullptr;
+    S.gumbel_m = q.gumbel ? q.gumbel->m : 0;
+    S.gumbel_c_visit = q.gumbel ? q.gumbel->c_visit : 0;
+    S.gumbel_c_scale = q.gumbel ? q.gumbel->c_scale_256 : 0;
     return S;
 }
 
@@ -2227,17 +2315,20 @@ int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequ
     const dim3 grid((unsigned)G.grid), block(256);
     iago_search_streams *const sp = q.streams;
     if (!sp) {
-        const Form f = q.wave ? F_WAVE : q.noise ? F_NOISE : q.park ? F_PARK : F_SINGLE;
-        const char *const who = q.wave    ? "iago_mcts_search_wave"
-                                : q.noise ? "iago_mcts_search_noise"
-                                : q.park  ? "iago_mcts_search_park"
-                                          : "iago_mcts_search_persistent";
+        const Form f = q.wave ? F_WAVE : q.gumbel ? F_GUMBEL : q.noise ? F_NOISE : q.park ? F_PARK : F_SINGLE;
+        const char *const who = q.wave     ? "iago_mcts_search_wave"
+                                : q.gumbel ? "iago_mcts_search_gumbel"
+                                : q.noise  ? "iago_mcts_search_noise"
+                                : q.park   ? "iago_mcts_search_park"
+                                           : "iago_mcts_search_persistent";
         // (the search kernel's LDS: reserved by iago_mcts_search_capacity)
-        if (f != F_SINGLE && reserve_lds(f, lds, q.wave    ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
-                                                 : q.noise ? "iago_mcts_search_noise: cannot reserve the nets' LDS image"
-                                                           : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
+        if (f != F_SINGLE && reserve_lds(f, lds, q.wave     ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
+                                                 : q.gumbel ? "iago_mcts_search_gumbel: cannot reserve the nets' LDS image"
+                                                 : q.noise  ? "iago_mcts_search_noise: cannot reserve the nets' LDS image"
+                                                            : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
             return IAGO_ERR_HIP;
         switch (f) {
+        case F_GUMBEL: hipLaunchKernelGGL(search_gumbel_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         case F_NOISE: hipLaunchKernelGGL(search_noise_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         case F_WAVE: hipLaunchKernelGGL(search_wave_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
         case F_PARK: hipLaunchKernelGGL(search_park_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
@@ -2252,7 +2343,9 @@ int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequ
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    if (q.noise)
+    if (q.gumbel)
+        hipLaunchKernelGGL(search_game_gumbel_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
+    else if (q.noise)
         hipLaunchKernelGGL(search_game_noise_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
     else if (q.park)
         hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
@@ -2497,6 +2590,33 @@ extern "C" int iago_mcts_search_forced(const iago_mcts_search_args *a, const iag
     q.streams = fz->streams;
     q.noise = &fz->noise;
     q.forced_k_256 = fz->k_256;
+    return search_launch(a, stream, q);
+}
+
+extern "C" int iago_mcts_search_gumbel(const iago_mcts_search_args *a, const iago_search_gumbel_args *gz, void *stream)
+{
+    if (!a || !gz)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: null args");
+    if (const int rc = check_reserved(gz->reserved, 0, "iago_mcts_search_gumbel"))
+        return rc;
+    if (const int rc = iago_check_gumbel_root(&gz->gumbel, "iago_mcts_search_gumbel"))
+        return rc;
+    if (!gz->gumbel.sched)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: null schedule");
+    if (a->max_turns != 0 || a->games_total != 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: one search per launch (max_turns 0, games_total 0): whole "
+                                           "games under the Gumbel rule run turn by turn");
+    if (a->n_sims < 1 || a->n_sims > 32767)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: n_sims must be in [1, 32767] (the schedule's columns)");
+    if (a->games_per_workgroup <= 0 || !(a->games_per_workgroup & IAGO_SEARCH_NEGAMAX))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: the negamax backup is required (IAGO_SEARCH_NEGAMAX: a root "
+                                           "child's Q must be the root mover's value)");
+    if (!(a->games_per_workgroup & IAGO_SEARCH_PUCT_AZ))
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_gumbel: the AlphaZero selection is required (IAGO_SEARCH_PUCT_AZ: a "
+                                           "child's stored prior must be the policy's p)");
+    LaunchRequest q;
+    q.streams = gz->streams;
+    q.gumbel = &gz->gumbel;
     return search_launch(a, stream, q);
 }
 

@@ -42,9 +42,10 @@ _stream = ops._stream   # the current HIP stream as a void*
 # solve_empties (None: off, else an int in [0, 20]), explore_turns (an int, 0: off), playout_cap (None: off, else
 # (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)), forced_playouts (None: off, else k_256,
 # with root_noise), solved_targets (False: off; True, with solve_empties: the solved turns record the set of their
-# optimal moves) -- as SelfPlayEngine.play documents them.
+# optimal moves), gumbel (None: off, else (m, c_scale_256, c_visit): the Gumbel root search, without root_noise,
+# forced_playouts or explore_turns) -- as SelfPlayEngine.play documents them.
 PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise forced_playouts "
-                                   "solved_targets", defaults=(None, None, False))
+                                   "solved_targets gumbel", defaults=(None, None, False, None))
 NO_RULES = PlayRules(None, 0, None)
 
 
@@ -1282,12 +1283,19 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0, forced=None):
+    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0, forced=None, gumbel=None):
         """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent).  root_noise = (alpha_256, eps_256,
         draws): the urn of turn `turn` first (ops.root_noise: the counts rows, the mix on the children the roots have),
         then the launch that applies the rows where a root expands (iago_mcts_search_noise; forced = k_256: with forced
-        playouts at the root, iago_mcts_search_forced)."""
-        if root_noise is None:
+        playouts at the root, iago_mcts_search_forced).  gumbel = (m, c_scale_256, c_visit): the draw of turn `turn` first
+        (ops.gumbel_draw), then the launch with the Gumbel rule at the roots (iago_mcts_search_gumbel)."""
+        if gumbel is not None:
+            ids, turns = self._turn_ids(turn)
+            st = self._gumbel_state()
+            ops.gumbel_draw(self.tree.ref(), active, self.seed, ids, turns, gumbel, st["tables"], st["g"])
+            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, gumbel=gumbel))
+            st["last"] = gumbel
+        elif root_noise is None:
             self._launch_persistent(own, opp, active, n_sims)
         else:
             ids, turns = self._turn_ids(turn)
@@ -1323,6 +1331,12 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
+        elif rules.gumbel is not None:
+            if game is not None:
+                raise ValueError("whole games in one launch are not available with the Gumbel root search (the turn loop is)")
+            st = self._gumbel_state()
+            ops.search_gumbel(a, rules.gumbel, st["tables"], self._gumbel_sched(rules.gumbel[0], n_sims), st["g"],
+                              streams=self._split)
         elif rules.root_noise is not None:
             if game is not None:
                 raise ValueError("whole games in one launch are not available with root noise (the turn loop is)")
@@ -1428,6 +1442,46 @@ class BatchedMCTS(object):
             rows = self._noise_counts = torch.zeros((self.n_games, 64), dtype=torch.int16, device=self.cur_own.device)
         return rows
 
+    def _gumbel_state(self):
+        """What the Gumbel root search keeps on the device: the two tables (ops.gumbel_tables, uploaded once), the draws
+        g and the rows n / q / logit of gumbel_rows(), (n_games, 64) each, one row per slot, and the schedules by (m,
+        n_sims).  `last`: the rule of the last such search, which gumbel_move() finishes."""
+        st = getattr(self, "_gumbel", None)
+        if st is None:
+            dev, B = self.cur_own.device, self.n_games
+            st = self._gumbel = dict(
+                tables=tuple(torch.from_numpy(np.array(t)).to(dev) for t in ops.gumbel_tables()), sched={}, last=None,
+                g=torch.zeros((B, 64), dtype=torch.int32, device=dev), n=torch.zeros((B, 64), dtype=torch.int32, device=dev),
+                q=torch.zeros((B, 64), dtype=torch.float32, device=dev),
+                logit=torch.zeros((B, 64), dtype=torch.int32, device=dev))
+        return st
+
+    def _gumbel_sched(self, m, n_sims):
+        """ops.gumbel_schedule(m, n_sims) on the device, built once per (m, n_sims)."""
+        sched = self._gumbel_state()["sched"]
+        if (m, n_sims) not in sched:
+            sched[m, n_sims] = torch.from_numpy(ops.gumbel_schedule(m, n_sims)).to(self.cur_own.device)
+        return sched[m, n_sims]
+
+    def _gumbel_arg(self, gumbel, root_noise=None, forced_playouts=None):
+        """search()'s gumbel, validated: offered for the persistent engine under backup="negamax" and
+        selection="alphazero", and not together with root noise or forced playouts (the rule explores by its own draw)."""
+        gz = ops.gumbel_arg(gumbel)
+        if gz is None:
+            return None
+        if root_noise is not None or forced_playouts is not None:
+            raise ValueError("gumbel is not available together with root_noise or forced_playouts (the Gumbel root search "
+                             "explores by its own draw)")
+        if self.backup != "negamax":
+            raise ValueError("gumbel needs backup=\"negamax\" (a root child's Q must be the root mover's value)")
+        if self.selection != "alphazero":
+            raise ValueError("gumbel needs selection=\"alphazero\" (a child's stored prior must be the policy's p)")
+        if (not self.persistent or self.wave_entry or self.rollout_hook is not None or self.use_graph or self.async_steps
+                or self.lookahead):
+            raise ValueError("gumbel is offered for the persistent search only (not use_graph, async steps, the look-ahead, "
+                             "rollout_hook or the wave search)")
+        return gz
+
     def _backup_check(self):
         """backup="negamax" and selection="alphazero" are the persistent search's alone: a rollout hook (set after
         construction) would send search() and SelfPlayEngine's turns through the per-playout launches, whose rules are the
@@ -1453,7 +1507,8 @@ class BatchedMCTS(object):
         reads back before it starts (a caller that batches its readbacks passes them in)."""
         return torch.stack([active.sum().to(torch.int64), self.tree.n_nodes.max().to(torch.int64)])
 
-    def search(self, own, opp, active, n_sims, counts=None, check=True, root_noise=None, turn=0, forced_playouts=None):
+    def search(self, own, opp, active, n_sims, counts=None, check=True, root_noise=None, turn=0, forced_playouts=None,
+               gumbel=None):
         """n_sims playouts from the current roots; (own, opp) = root positions
         with own = side to move; active: uint8 mask of participating games.
         counts: (games in `active`, nodes of the fullest pool) when the caller has read
@@ -1466,8 +1521,17 @@ class BatchedMCTS(object):
         forced_playouts = k_256 (None, the default: off; an int in [1, 4096], with root_noise only, else ValueError):
         forced playouts at the root of this search (include/iago_hip_serving.h, iago_mcts_search_forced) -- a root child
         with n >= 1 visits and stored prior p scores +inf in Node.select while 256 n^2 < k_256 p N, N the root's visits.
-        pruned_visits() afterwards takes the forced visits out of the visit rows."""
+        pruned_visits() afterwards takes the forced visits out of the visit rows.
+        gumbel = (m, c_scale_256[, c_visit]) (None, the default: off; the persistent engine under backup="negamax" and
+        selection="alphazero" only, never with root_noise or forced_playouts, else ValueError): the Gumbel root search
+        (include/iago_hip_serving.h, iago_mcts_search_gumbel) -- the trees of the games in `active` are RESET first (the
+        rule needs fresh roots: no subtree reuse), then the draw of turn `turn` of game game_id_base + g, then the search
+        in which the root serves the sequential-halving schedule of (m, n_sims).  gumbel_move() afterwards gives the
+        halving's survivor and gumbel_rows() the rows the improved-policy target is made from (gumbel_targets)."""
         self._backup_check()
+        gz = self._gumbel_arg(gumbel, root_noise, forced_playouts)
+        if gz is not None and not 1 <= n_sims <= 32767:
+            raise ValueError("gumbel: n_sims must be in [1, 32767], not %r" % (n_sims,))
         noise = self._root_noise_arg(root_noise)
         forced = ops.forced_playouts_arg(forced_playouts, noise)
         n_active, used = (int(v) for v in (self.search_counts(active).tolist() if counts is None else counts))
@@ -1492,6 +1556,12 @@ class BatchedMCTS(object):
                 self._policy_key = key
             if self._la_stale_any:
                 self._refresh_priors(own, opp, active)
+        if gz is not None:
+            self.tree.reset(active)   # (fresh roots: nothing left to compact in the searched games)
+            self._search_persistent(own, opp, active, n_sims, n_active, turn=turn, gumbel=gz)
+            if check:
+                self.raise_errors(self.error_flags().tolist())
+            return
         self._compact_if_half_full(used)
         if noise is not None:
             self._search_persistent(own, opp, active, n_sims, n_active, noise, turn, forced)
@@ -1619,6 +1689,27 @@ class BatchedMCTS(object):
                                              _p(self.move), _p(self.visits) if want_visits else None,
                                              _stream()), "iago_mcts_best_move")
         return self.move, self.visits
+
+    def gumbel_move(self, active=None, gumbel=None):
+        """The move of the last search(gumbel=) on the trees as they stand (ops.gumbel_finish): of the root's most
+        visited children the first maximum of g + logit + sigma(q); one child or none: best_move's answer.  Also fills the
+        rows gumbel_rows() hands out.  gumbel: the rule, None = the last such search's.  Returns the engine's move buffer:
+        the next best_move / draw_move overwrites it."""
+        st = self._gumbel_state()
+        rule = st["last"] if gumbel is None else ops.gumbel_arg(gumbel)
+        if rule is None:
+            raise ValueError("gumbel_move: no search(gumbel=) has run on this engine")
+        ops.gumbel_finish(self.tree.ref(), active, rule, st["tables"], st["g"], self.move, st["n"], st["q"], st["logit"])
+        return self.move
+
+    def gumbel_rows(self, active=None, gumbel=None):
+        """(n, q, logit) of the last search(gumbel=), (n_games, 64) each, by cell: the root children's visits (int32),
+        their values (float32, 0 where unvisited) and logit_q16 of their stored priors (int32, INT32_MIN off the root's
+        children) -- what gumbel_targets takes.  The engine's own buffers (the next call overwrites them; the rows of games
+        outside `active` are stale)."""
+        self.gumbel_move(active, gumbel)
+        st = self._gumbel_state()
+        return st["n"], st["q"], st["logit"]
 
     def pruned_visits(self, active=None, forced_playouts=512):
         """The policy-target pruning of forced playouts (ops.prune_visits) on the trees as they stand: the (n_games, 64)
@@ -1793,18 +1884,25 @@ def _solve_empties_arg(k):
 
 
 def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None, forced_playouts=None,
-                solved_targets=False):
+                solved_targets=False, gumbel=None):
     """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
     where its own validator refuses it (forced_playouts: an int in [1, 4096], and only with root_noise).  Off is (None, 0,
-    None, None, None): explore_turns is an int in the record.  solved_targets: a bool, True only with solve_empties."""
+    None, None, None): explore_turns is an int in the record.  solved_targets: a bool, True only with solve_empties.
+    gumbel: (m, c_scale_256[, c_visit]), refused together with explore_turns, root_noise or forced_playouts."""
     noise = ops.root_noise_arg(root_noise)
+    gz = ops.gumbel_arg(gumbel)
+    if gz is not None and (noise is not None or forced_playouts is not None or ops.explore_turns_arg(explore_turns)):
+        raise ValueError("gumbel is not available together with explore_turns, root_noise or forced_playouts (the Gumbel "
+                         "root search explores by its own draw)")
+    if gz is not None and not 1 <= n_sims <= 32767:
+        raise ValueError("gumbel: n_sims must be in [1, 32767], not %r" % (n_sims,))
     if not isinstance(solved_targets, bool):
         raise ValueError("solved_targets must be a bool, not %r" % (solved_targets,))
     if solved_targets and solve_empties is None:
         raise ValueError("solved_targets records the solver's optimal moves: it needs solve_empties")
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
                      ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise),
-                     solved_targets)
+                     solved_targets, gz)
 
 
 def _no_forced_playouts(forced_playouts, who):
@@ -1866,6 +1964,39 @@ def _empties(own, opp):
     """(n,) int32: 64 - popcount(own | opp), the true count of empty squares (stone_num ignores handicap stones)."""
     cells = torch.arange(64, device=own.device)
     return 64 - (((own | opp).reshape(-1, 1) >> cells) & 1).sum(dim=1).to(torch.int32)
+
+
+def gumbel_targets(rows, c_visit=_lib.GUMBEL_C_VISIT, c_scale_256=256, scale=65536):
+    """The improved-policy target of the Gumbel root search from the rows of BatchedMCTS.gumbel_rows() -- (n, q, logit),
+    (B, 64) each, or with leading dimensions of any shape -- in torch float64 on the rows' device: over the legal moves
+    (logit != INT32_MIN), pi' = softmax(logit_q16 / 65536 + sigma(completed q^)) with sigma(x) = (c_visit + max n)
+    (c_scale_256 / 256) x and q^ = (q + 1) / 2.  The completed q of a visited move is its q; of an unvisited legal move
+    v_mix = (v0 + N wq) / (1 + N), N the sum of the visits, wq the mean q of the visited moves weighted by their priors p =
+    exp(logit_q16 / 65536), and v0 = wq (the root's own value is not kept).  A root without a visited child keeps its prior,
+    softmax(logit); a row without a legal move is 0.  Returns int32 rows round(scale pi'), the column ReplayWindow.add and
+    ReinforceTrainer.step_from_tuples(target="visits") take."""
+    n, q, logit = rows
+    f64 = torch.float64
+    legal = logit != -(1 << 31)
+    zero = torch.zeros((), dtype=f64, device=n.device)
+    lg = torch.where(legal, logit.to(f64) / 65536.0, zero)
+    nn, qq = n.to(f64), q.to(f64)
+    visited = legal & (n > 0)
+    p = torch.where(visited, torch.exp(lg), zero)
+    big_n = nn.sum(dim=-1, keepdim=True)
+    psum = p.sum(dim=-1, keepdim=True)
+    some = psum > 0
+    wq = (p * qq).sum(dim=-1, keepdim=True) / torch.where(some, psum, torch.ones_like(psum))
+    v_mix = (wq + big_n * wq) / (1.0 + big_n)
+    q_hat = (torch.where(visited, qq, v_mix) + 1.0) / 2.0
+    sigma = (float(c_visit) + nn.max(dim=-1, keepdim=True).values) * (float(c_scale_256) / 256.0) * q_hat
+    x = lg + torch.where(some, sigma, zero)
+    x = torch.where(legal, x, torch.full_like(x, -float("inf")))
+    top = x.max(dim=-1, keepdim=True).values
+    e = torch.where(legal, torch.exp(x - torch.where(top > -float("inf"), top, zero)), zero)
+    tot = e.sum(dim=-1, keepdim=True)
+    pi = e / torch.where(tot > 0, tot, torch.ones_like(tot))
+    return torch.round(float(scale) * pi).to(torch.int32)
 
 
 class SelfPlayEngine(object):
@@ -2010,7 +2141,8 @@ class SelfPlayEngine(object):
         m = self.mcts
         m.tree.reset()
         # (root noise: the urn is drawn per turn by a launch of its own, ops.root_noise -- the turn loop)
-        if not (applies and rules.root_noise is None and self._whole_games_in_one_launch(n_sims)):
+        # (the Gumbel root search: a draw and a finish per turn, launches of their own -- the turn loop)
+        if not (applies and rules.root_noise is None and rules.gumbel is None and self._whole_games_in_one_launch(n_sims)):
             return None
         res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, rules, **kw)
         if res is None:
@@ -2029,6 +2161,8 @@ class SelfPlayEngine(object):
             kw = {} if rules.root_noise is None else dict(root_noise=rules.root_noise, turn=s.turn)   # (off: today's calls)
             if rules.forced_playouts is not None:
                 kw["forced_playouts"] = rules.forced_playouts
+            if rules.gumbel is not None:   # (of a cap's two searches the full games' alone: a fast turn is the plain search's)
+                kw = dict(gumbel=rules.gumbel, turn=s.turn)
             if rules.playout_cap is None:
                 m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False, **kw)   # (sim_counter: + n_sims whoever searched)
                 continue
@@ -2073,7 +2207,7 @@ class SelfPlayEngine(object):
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         rec = self._new_records(B) if record else None
-        if record and rules.forced_playouts is not None:
+        if record and (rules.forced_playouts is not None or rules.gumbel is not None):
             rec["pi_raw"] = torch.zeros_like(rec["pi"])
         if record and rules.solved_targets:
             rec["best"] = torch.zeros((T, B), dtype=torch.int64, device=dev)
@@ -2139,6 +2273,15 @@ class SelfPlayEngine(object):
             launched += search(sides, own, opp, rules)
             for s in sides:
                 s.move, s.visits = s.mcts.draw_move(t, s.act) if t < rules.explore_turns else s.mcts.best_move(s.act)
+                if rules.gumbel is not None:
+                    # the games the Gumbel rule searched (under a cap the full ones): gumbel_move writes the halving's
+                    # survivor over best_move's most visited child in s.move (the engine's move buffer) and fills the
+                    # rows, from which a recorded game makes its improved-policy target
+                    f = s.act if cap is None else s.full
+                    s.mcts.gumbel_move(f, rules.gumbel)
+                    if record:
+                        st = s.mcts._gumbel_state()
+                        s.gumbel_pi = gumbel_targets((st["n"], st["q"], st["logit"]), rules.gumbel[2], rules.gumbel[1])
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
                 if rules.solved_targets:   # (the same score and move, and the set of the optimal moves)
@@ -2193,6 +2336,11 @@ class SelfPlayEngine(object):
                     for s in sides:   # (the forced games: the noised search's)
                         f = s.act if cap is None else s.full
                         pi = torch.where(f.reshape(B, 1) != 0, s.mcts.pruned_visits(f, rules.forced_playouts), pi)
+                if rules.gumbel is not None:
+                    rec["pi_raw"][t] = pi
+                    for s in sides:   # (the games under the Gumbel rule: the improved policy for the visit row)
+                        f = s.act if cap is None else s.full
+                        pi = torch.where(f.reshape(B, 1) != 0, s.gumbel_pi, pi)
                 if policy_moves:
                     valid = valid + _lib.REC_DRAWN * (drawn | forced).to(torch.uint8)
                 if opening is not None:
@@ -2252,7 +2400,7 @@ class SelfPlayEngine(object):
         return res
 
     def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None,
-             root_noise=None, forced_playouts=None, solved_targets=False):
+             root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -2303,15 +2451,26 @@ class SelfPlayEngine(object):
         score; 0 on every row that is not solved) -- the turn loop through ops.solve_endgame_moves(moves="best"), the
         play-out launch through iago_play_endgame_moves: the same records, and every other record as without it.
         solved_tuples() then carries best and a 0 / 1 `pi`, a noise-free policy target for the plies the search never
-        sees.  Without it the result's best is None."""
+        sees.  Without it the result's best is None.
+        gumbel = (m, c_scale_256[, c_visit]) (None, the default: off -- the engine of before, argument for argument; m in 2
+        .. 64, c_scale_256 in 1 .. 4096, c_visit in 0 .. 4096, default 50): the Gumbel root search of Danihelka et al. 2022
+        (include/iago_hip_serving.h, iago_mcts_search_gumbel), for engines with backup="negamax" and selection="alphazero".
+        Every searched turn starts from a FRESH root (no subtree reuse), draws one Gumbel per cell from (seed ^
+        GUMBEL_SEED_XOR; game_id_base + g, t, cell), spends the n_sims playouts on the top min(m, K) moves by g + logit
+        in sequential halving, and plays the survivor: the best of the most visited moves by g + logit + sigma(q).  `pi`
+        records the improved policy round(65536 softmax(logit + sigma(completed q))) (gumbel_targets) and `pi_raw` the
+        visit row; `move` is the survivor.  Such games ALWAYS run through the turn loop.  solve_empties and playout_cap
+        compose (under a cap only the FULL turns run the rule: a fast turn is the plain search's, pi = pi_raw);
+        explore_turns, root_noise and forced_playouts are refused beside it -- the rule explores by its own draw."""
         return self._play(n_sims, handicap, record,
                           _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts,
-                                      solved_targets))
+                                      solved_targets, gumbel))
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
         self.mcts._backup_check()
         self.mcts._root_noise_arg(rules.root_noise)   # (the persistent engine only: refused before anything is reset)
+        self.mcts._gumbel_arg(rules.gumbel)           # (likewise, and the backup and selection rules it needs)
         res = self._one_launch(n_sims, self.B, handicap, record, rules)
         if res is None:
             res = self._play_turns([_Side(self.mcts, n_sims)], *self._start_boards(self.B, handicap), record,
@@ -2319,7 +2478,7 @@ class SelfPlayEngine(object):
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
-                    playout_cap=None, root_noise=None, forced_playouts=None, solved_targets=False):
+                    playout_cap=None, root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -2332,11 +2491,14 @@ class SelfPlayEngine(object):
         the stream's games hand over at k empties and one launch plays all n_games out (launches = 2).  explore_turns:
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
         turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id.
-        forced_playouts: as in play(), with the record pi_raw.  solved_targets: as in play(), with the record best."""
-        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts, solved_targets)
+        forced_playouts: as in play(), with the record pi_raw.  solved_targets: as in play(), with the record best.
+        gumbel: as in play() -- the batch loop, game G's draws keyed by its own id, with the record pi_raw."""
+        rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts, solved_targets,
+                            gumbel)
         m, T = self.mcts, self.max_turns
         m._backup_check()
         m._root_noise_arg(rules.root_noise)
+        m._gumbel_arg(rules.gumbel)
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError("play_stream: n_games >= 1 expected")
@@ -2352,7 +2514,7 @@ class SelfPlayEngine(object):
         return res
 
     def play_match(self, n_sims, mcts_colour=None, record=True, solve_empties=None, forced_playouts=None, opponent=None,
-                   opening_turns=0, paired=False):
+                   opening_turns=0, paired=False, gumbel=None):
         """B games of PV-MCTS (n_sims playouts per move) against the SL policy it is built on -- the reference's
         `game.py --auto` (game.py:96-145,246-262) -- with the engine's nets: in game g PV-MCTS plays colour
         mcts_colour[g] (1 moves first; an int: every game; 2, the default, is the reference's setting) and the policy
@@ -2383,9 +2545,12 @@ class SelfPlayEngine(object):
         paired = True (needs an even B, and no mcts_colour: it sets it): games g and g + B / 2 draw the same opening
         (id_mod = B / 2, else B) and PV-MCTS plays colour 1 in the first half and colour 2 in the second.  With an
         opponent or opening_turns > 0 the match ALWAYS runs through the turn loop (launches = its turns); with all three at
-        their defaults it is the match above, argument for argument.  mcts_colour: None is 2, or with paired the halves."""
+        their defaults it is the match above, argument for argument.  mcts_colour: None is 2, or with paired the halves.
+        gumbel = (m, c_scale_256[, c_visit]) (None, the default: off): PV-MCTS's searched turns run the Gumbel root search
+        as in play() -- fresh roots, the survivor for a move, pi the improved policy and pi_raw the visit row.  Such a
+        match ALWAYS runs through the turn loop."""
         _no_forced_playouts(forced_playouts, "play_match")
-        rules = _play_rules(n_sims, solve_empties)
+        rules = _play_rules(n_sims, solve_empties, gumbel=gumbel)
         match = _match_rules(opponent, opening_turns, paired, mcts_colour, self.B)
         dev = self.mcts.cur_own.device
         if paired:
@@ -2393,6 +2558,7 @@ class SelfPlayEngine(object):
         else:
             col = _colour_arg(2 if mcts_colour is None else mcts_colour, self.B, dev, "play_match: mcts_colour")
         self.mcts._backup_check()   # (a hooked negamax engine: refused before anything is reset)
+        self.mcts._gumbel_arg(rules.gumbel)
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
         plain = match.opponent is None and match.opening_turns == 0
         res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None and plain,
@@ -2437,7 +2603,7 @@ class SelfPlayEngine(object):
         res.final_p2 = torch.cat([r.final_p2[:w] for r, w in parts])
         if record:
             cols = {k: [] for k in ("own", "opp", "valid", "move", "pi", "score")}
-            if rules.forced_playouts is not None:
+            if rules.forced_playouts is not None or rules.gumbel is not None:
                 cols["pi_raw"] = []
             if rules.solved_targets:
                 cols["best"] = []
@@ -2600,14 +2766,19 @@ class ArenaEngine(object):
         b.search(own, opp, s_b, n_b, counts=c_b, check=False)
         return (1 if c_a[0] else 0) + (1 if c_b[0] else 0)
 
-    def play(self, n_sims, a_colour=None, record=True, explore_turns=None, one_launch=None, forced_playouts=None):
+    def play(self, n_sims, a_colour=None, record=True, explore_turns=None, one_launch=None, forced_playouts=None,
+             gumbel=None):
         """B games from the opening, both trees fresh.  n_sims: playouts per move, an int or a pair (n_a, n_b); a_colour:
         the colour A plays, 1, 2 or a (B,) integer tensor of 1 / 2 (None: 1 in the first half of the games, 2 in the
         rest); explore_turns: as SelfPlayEngine.play's, each mover drawing with its own engine's seed and id; one_launch:
         True = one iago_mcts_search_arena launch per turn (the sequential form where the library answers
         IAGO_ERR_CAPACITY), False = the sequential form, None = ONE_LAUNCH_DEFAULT.  forced_playouts: None; anything else
-        is a ValueError (the arena has no root noise and does not force).  Returns an ArenaResult."""
+        is a ValueError (the arena has no root noise and does not force).  gumbel: None; anything else is a ValueError
+        (two searches in one launch do not take the Gumbel root search).  Returns an ArenaResult."""
         _no_forced_playouts(forced_playouts, "ArenaEngine.play")
+        if gumbel is not None:
+            raise ValueError("ArenaEngine.play: gumbel is not available (the Gumbel root search lives in the turn loop of "
+                             "play / play_stream / play_match)")
         n_a, n_b = self._n_sims(n_sims)
         col = self._colours(a_colour)
         rules = _play_rules(n_a, explore_turns=explore_turns)

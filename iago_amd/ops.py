@@ -1645,6 +1645,120 @@ def prune_visits(tree, active, c_puct, k_256, pruned, flags=0):
     return pruned
 
 
+def gumbel_arg(gumbel):
+    """gumbel of SelfPlayEngine.play / play_stream / play_match / BatchedMCTS.search / MCTS: None (off), or (m,
+    c_scale_256[, c_visit]) -- ints, 2 <= m <= 64 (the moves considered), 1 <= c_scale_256 <= 4096 (c_scale =
+    c_scale_256 / 256), 0 <= c_visit <= 4096 (default _lib.GUMBEL_C_VISIT) -- returned as a tuple of three ints."""
+    if gumbel is None:
+        return None
+    what = "gumbel must be None or (m, c_scale_256[, c_visit]), ints, not %r" % (gumbel,)
+    try:
+        vals = tuple(gumbel)
+    except TypeError:
+        raise ValueError(what)
+    if len(vals) not in (2, 3) or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals):
+        raise ValueError(what)
+    m, c_scale, c_visit = (vals + (_lib.GUMBEL_C_VISIT,))[:3]
+    if not 2 <= m <= 64:
+        raise ValueError("gumbel: m must be in [2, 64], not %r" % (m,))
+    if not 1 <= c_scale <= 4096:
+        raise ValueError("gumbel: c_scale_256 must be in [1, 4096], not %r" % (c_scale,))
+    if not 0 <= c_visit <= 4096:
+        raise ValueError("gumbel: c_visit must be in [0, 4096], not %r" % (c_visit,))
+    return int(m), int(c_scale), int(c_visit)
+
+
+_GUMBEL_TABLES = []
+
+
+def gumbel_tables():
+    """The two tables of the Gumbel root search (include/iago_hip_serving.h), computed once in numpy float64 and read as
+    they are by the device and by tests/gumbel_ref.py: (gumbel_q16, ln_q16), int32 arrays of 65536 and 4096 entries --
+    round(65536 * -ln(-ln((u + 0.5) / 65536))) and round(65536 * ln(1 + (i + 0.5) / 4096)).  Read-only."""
+    if not _GUMBEL_TABLES:
+        u = (np.arange(65536, dtype=np.float64) + 0.5) / 65536.0
+        g = np.rint(65536.0 * -np.log(-np.log(u))).astype(np.int32)
+        ln = np.rint(65536.0 * np.log1p((np.arange(4096, dtype=np.float64) + 0.5) / 4096.0)).astype(np.int32)
+        g.setflags(write=False)
+        ln.setflags(write=False)
+        _GUMBEL_TABLES.extend((g, ln))
+    return _GUMBEL_TABLES[0], _GUMBEL_TABLES[1]
+
+
+def gumbel_schedule(m, n_sims):
+    """The sequential-halving schedule of the Gumbel root search (include/iago_hip_serving.h): int16 [m + 1][n_sims], row k
+    the visit count the next considered move must have, playout by playout, when k moves are considered.  Rows 0 and 1
+    count 0, 1, 2, ...; row k >= 2: k counters at 0, L = ceil(log2 k), cur = k, and until the row is full extra = max(1,
+    n_sims // (L cur)) times the first cur counters are written and each of them grows by one, then cur = max(2, cur //
+    2).  m in [1, 64], n_sims in [1, 32767]."""
+    m, n_sims = int(m), int(n_sims)
+    if not 1 <= m <= 64 or not 1 <= n_sims <= 32767:
+        raise ValueError("gumbel_schedule: m in [1, 64] and n_sims in [1, 32767] expected, not %r, %r" % (m, n_sims))
+    out = np.zeros((m + 1, n_sims), np.int16)
+    out[0] = out[1] = np.arange(n_sims)
+    for k in range(2, m + 1):
+        row, counters = [], [0] * k
+        levels, cur = (k - 1).bit_length(), k
+        while len(row) < n_sims:
+            for _ in range(max(1, n_sims // (levels * cur))):
+                row.extend(counters[:cur])
+                counters[:cur] = [c + 1 for c in counters[:cur]]
+                if len(row) >= n_sims:
+                    break
+            cur = max(2, cur // 2)
+        out[k] = row[:n_sims]
+    return out
+
+
+def _gumbel_struct(gumbel, tables, sched, g, into=None):
+    """gumbel = (m, c_scale_256, c_visit); tables = (gumbel_q16, ln_q16) on the device; sched (m + 1, n_sims) int16 on the
+    device or None (the draw and the finish do not read it); g (n_games, 64) int32."""
+    z = _lib.GumbelRoot() if into is None else into
+    z.m, z.c_scale_256, z.c_visit = (int(v) for v in gumbel)
+    z.gumbel_q16, z.ln_q16 = _dev(tables[0], torch.int32, "gumbel_q16"), _dev(tables[1], torch.int32, "ln_q16")
+    z.sched = _dev(sched, torch.int16, "sched") if sched is not None else None
+    z.g = _dev(g, torch.int32, "g") if g is not None else None
+    return z
+
+
+def gumbel_draw(tree, active, seed, game_id, turn, gumbel, tables, g):
+    """iago_mcts_gumbel_draw (include/iago_hip_serving.h): the Gumbel root search's draw for the turn loop.  For every
+    game with active[g] != 0 (active None: every game) and every cell a: g[game][a] = gumbel_q16[c0 >> 16], c0 word 0 of
+    Philox4x32-10 on (game_id, turn, a, 0) under seed ^ GUMBEL_SEED_XOR.  Inactive games' rows are not touched.  tree:
+    TreePool.ref(); game_id / turn (n_games,) int32; tables: gumbel_tables() on the device; g (n_games, 64) int32.
+    Returns g."""
+    z = _gumbel_struct(gumbel, tables, None, g)
+    check(_lib.lib().iago_mcts_gumbel_draw(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                           C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _dev(game_id, torch.int32, "game_id"),
+                                           _dev(turn, torch.int32, "turn"), C.byref(z), _stream()), "iago_mcts_gumbel_draw")
+    return g
+
+
+def search_gumbel(args, gumbel, tables, sched, g, streams=None):
+    """iago_mcts_search_gumbel (include/iago_hip_serving.h): the ONE search of `args` (a _lib.MctsSearchArgs, max_turns 0,
+    negamax backup and AlphaZero selection, fresh roots) with the Gumbel rule at every active game's root -- a child
+    whose visits are sched[min(m, K)][min(t, n_sims - 1)] scores g + logit_q16(p) + sigma, every other child -inf.
+    sched: gumbel_schedule(m, args.n_sims) on the device; g: the rows gumbel_draw() left for this turn; streams: the
+    role split's handle or None.  The caller keeps everything alive until the launch has run."""
+    z = _lib.SearchGumbelArgs()
+    _gumbel_struct(gumbel, tables, sched, g, z.gumbel)
+    z.streams = streams
+    check(_lib.lib().iago_mcts_search_gumbel(C.byref(args), C.byref(z), _stream()), "iago_mcts_search_gumbel")
+
+
+def gumbel_finish(tree, active, gumbel, tables, g, move, n, q, logit):
+    """iago_mcts_gumbel_finish (include/iago_hip_serving.h): the move of the Gumbel root search -- of the root's children
+    with the most visits the first maximum of g + logit_q16(p) + sigma; one child or none: best_move's answer -- into
+    move (n_games,) int8, and the rows n (int32), q (float32, 0 where unvisited) and logit (int32, INT32_MIN off the root's
+    children), (n_games, 64) each.  Inactive games are not touched; the trees are only read."""
+    z = _gumbel_struct(gumbel, tables, None, g)
+    check(_lib.lib().iago_mcts_gumbel_finish(tree, _dev(active, torch.uint8, "active") if active is not None else None,
+                                             C.byref(z), _dev(move, torch.int8, "move"), _dev(n, torch.int32, "n"),
+                                             _dev(q, torch.float32, "q"), _dev(logit, torch.int32, "logit"), _stream()),
+          "iago_mcts_gumbel_finish")
+    return move
+
+
 def search_arena(args_a, args_b, check_result=True):
     """iago_mcts_search_arena (include/iago_hip_serving.h): the searches of `args_a` and `args_b` (two
     _lib.MctsSearchArgs, each a complete search of iago_mcts_search_persistent with its own nets, trees and rings) in

@@ -524,6 +524,93 @@ IAGO_API int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *a
 IAGO_API int iago_mcts_prune_visits_rule(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
                                          int32_t flags, int32_t *pruned /* [n_games][64] */, void *stream);
 
+/* ------------------------------------------------------------------ Gumbel root search */
+
+#define IAGO_GUMBEL_KEY 0x47554D42u /* ("GUMB") the draw's Philox key: the rollout seed with its high word XOR this */
+
+/*
+ * THE GUMBEL ROOT SEARCH (Danihelka et al. 2022, "Policy improvement by planning with Gumbel"): at the root of a searched
+ * turn m moves are sampled without replacement by Gumbel-top-k, the budget is spent on them by sequential halving, the
+ * survivor is played, and the policy target is softmax(logit + sigma(completed Q)) instead of the visit counts.  Everything
+ * that decides a move is in integers (Q16: units of 2^-16).
+ *   - preconditions: the negamax backup (IAGO_SEARCH_NEGAMAX: a root child's Q is the root mover's value), the AlphaZero
+ *     selection (IAGO_SEARCH_PUCT_AZ: a child's stored prior is the policy's p), ONE search per launch (max_turns 0,
+ *     games_total 0), n_sims in 1 .. 32767, and a FRESH root (n_nodes == 1) in every searched game -- the caller resets the
+ *     trees (BatchedMCTS.search does), so there is no subtree reuse under this rule.
+ *   - two tables, computed by the caller in float64 and read by the device as they are (it calls neither log nor exp):
+ *       gumbel_q16[u] = round(65536 * -ln(-ln((u + 0.5) / 65536))),  u = 0 .. 65535   (int32)
+ *       ln_q16[i]     = round(65536 * ln(1 + (i + 0.5) / 4096)),      i = 0 .. 4095    (int32)
+ *   - the draw (iago_mcts_gumbel_draw), before the search since it does not read the priors: for every active game g and
+ *     every cell a, g[g][a] = gumbel_q16[c0 >> 16] with c0 word 0 of Philox4x32-10 on the counter (game_id[g], turn[g], a, 0)
+ *     under the key `seed` with its high word XOR IAGO_GUMBEL_KEY (a key of its own).
+ *   - the logit of a stored float32 prior p > 0 with biased exponent e and 23-bit mantissa f:
+ *       logit_q16(p) = (e - 127) * 45426 + ln_q16[f >> 11]          (45426 = round(65536 ln 2); p == 1.0 likewise)
+ *   - the schedule sched[k][i], int16 [m + 1][n_sims], built by the caller: row k lists, playout by playout, the visit count
+ *     the next considered move must have when k moves are considered.  Rows 0 and 1 count 0, 1, 2, ...  For k >= 2 keep k
+ *     counters at 0, L = ceil(log2 k), cur = k, and until the row is full: extra = max(1, n_sims / (L cur)) (integer
+ *     division); extra times write the first cur counters and then add one to each of them; cur = max(2, cur / 2).  The row
+ *     is cut at n_sims entries.  (k = 4, n_sims = 16: 0 0 0 0 1 1 1 1 2 2 3 3 4 4 5 5.)
+ *   - selection, at the path's first node when it has K >= 2 children; every other node scores as ever.  t = the sum of the
+ *     children's visits, maxN their largest, want = sched[min(m, K)][min(t, n_sims - 1)].  A child with n != want scores
+ *     -inf; a child with n == want scores
+ *       g[action] + logit_q16(p) + sigma,   sigma = ((c_visit + maxN) * c_scale_256 * q16) >> 8   (int64)
+ *       q16 = (int)rintf(Q * 32768.0f) + 32768 for n > 0, 0 for n == 0 (the candidates are then all unvisited: it cancels)
+ *     a sum below 2^53, carried as a float64; the first maximum wins (the lowest child index).  Stated on the visit counts
+ *     alone, the rule keeps no state: the unvisited phase takes the top min(m, K) moves by g + logit, each later phase the
+ *     better half of the phase before.  If NO child has n == want the children of the largest visit count are scored
+ *     instead: this happens only where the preconditions were bypassed (a root that was not fresh).
+ *   - the move and the rows (iago_mcts_gumbel_finish): of the children with the largest visit count the argmax of the same
+ *     score, the lowest index on a tie; a root with one child (an only move, a pass: -1) or none (-2) answers as
+ *     iago_mcts_best_move does.  Per game three rows [64] by cell: n (int32 visits), q (float32, 0 where unvisited) and
+ *     logit (int32 logit_q16 of the stored prior; INT32_MIN off the root's children) -- what the improved-policy target is
+ *     made from on the host (engine.gumbel_targets).
+ */
+typedef struct iago_gumbel_root {
+    const int32_t *gumbel_q16; /* [65536] (the draw reads it) */
+    const int32_t *ln_q16;     /* [4096] (the search and the finish read it) */
+    const int16_t *sched;      /* [m + 1][n_sims] (the search reads it) */
+    int32_t *g;                /* [n_games][64] the draws by cell, one row per SLOT (tree) */
+    int32_t m;                 /* 2 .. 64: the moves considered */
+    int32_t c_scale_256;       /* 1 .. 4096 (256: the paper's c_scale = 1) */
+    int32_t c_visit;           /* 0 .. 4096 (50: the paper's) */
+    int32_t reserved0;         /* 0 */
+} iago_gumbel_root;
+
+/*
+ * The draw for the turn loop, a sibling of iago_mcts_root_noise: rows gumbel->g[g][0 .. 63] of every game with active[g] != 0
+ * (active NULL: every game) at turn[g] of the game with GLOBAL id game_id[g]; inactive games' rows are not touched.  Reads
+ * gumbel->gumbel_q16 and writes gumbel->g, nothing else.  Refused (IAGO_ERR_INVALID, nothing launched): a bad tree, a null
+ * array, a null table or g, m / c_scale_256 / c_visit out of range, reserved0 not 0.
+ */
+IAGO_API int iago_mcts_gumbel_draw(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,
+                                   const int32_t *turn, const iago_gumbel_root *gumbel, void *stream);
+
+typedef struct iago_search_gumbel_args {
+    iago_gumbel_root gumbel;      /* the tables, the schedule of (m, args->n_sims), the rows iago_mcts_gumbel_draw filled */
+    iago_search_streams *streams; /* optional: the role split of iago_mcts_search_split; NULL = the single launch */
+    int64_t reserved[4];          /* 0 */
+} iago_search_gumbel_args;
+
+/*
+ * ONE search of iago_mcts_search_persistent (max_turns == 0; with `streams` iago_mcts_search_split's) with the selection
+ * rule above at every active game's root.  Everything else -- the playouts below the root, the rollouts' Philox streams,
+ * z_log, the totals -- is iago_mcts_search_persistent's.  Whole games, streams of games, the wave search and the arena do
+ * not take the rule: such games run turn by turn (draw, search, finish).
+ * Refused (IAGO_ERR_INVALID, nothing launched, before the device is touched): null args, a null table / sched / g, m outside
+ * 2 .. 64, c_scale_256 outside 1 .. 4096, c_visit outside 0 .. 4096, reserved fields not 0, max_turns > 0 or games_total >
+ * 0, n_sims outside 1 .. 32767, games_per_workgroup without IAGO_SEARCH_NEGAMAX or without IAGO_SEARCH_PUCT_AZ.
+ */
+IAGO_API int iago_mcts_search_gumbel(const iago_mcts_search_args *args, const iago_search_gumbel_args *gumbel, void *stream);
+
+/*
+ * The move and the three rows of the rule above from the trees as they stand, a sibling of iago_mcts_best_move: for every
+ * game with active[g] != 0 (active NULL: every game) move[g] and the rows n[g], q[g], logit[g] ([n_games][64] each).  Reads
+ * gumbel->ln_q16, gumbel->g, c_scale_256 and c_visit; the trees are only read; inactive games are not touched.
+ * Refused (IAGO_ERR_INVALID, nothing launched): a bad tree, a null array, what iago_mcts_gumbel_draw refuses of `gumbel`.
+ */
+IAGO_API int iago_mcts_gumbel_finish(const iago_mcts_tree *tree, const uint8_t *active, const iago_gumbel_root *gumbel,
+                                     int8_t *move, int32_t *n, float *q, int32_t *logit, void *stream);
+
 /* ------------------------------------------------------------------ arena */
 
 /*

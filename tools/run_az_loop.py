@@ -29,10 +29,15 @@ merge = 1 or 2: the minibatches are drawn out of the window merged by position u
 distinct positions, "rows" keeps every position's weight in the window and changes the targets only.  0, the default:
 every row a position of its own (the JSON line's merge is null).  window_unique, the distinct positions of the window
 at the end, is logged beside window_count either way.
+gumbel = m > 0 (with backup = 1 and selection = 1, without noise_eps and forced_k: the engine refuses anything else): the
+Gumbel root search in self-play, SelfPlayEngine.play(gumbel=(m, 256)) -- fresh roots, sequential halving over the top m
+moves, the survivor played, the window receives the improved-policy rows.  The self-play engine then expands at the first
+visit (n_thr = 1: at n_thr 15 a budget of 20 would leave the rule five playouts) and no opening moves are drawn from the
+visit counts (the rule explores by its own draw); 0, the default: off.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
                                  [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]
-                                 [solve_empties=0] [solved_targets=0] [merge=0]"""
+                                 [solve_empties=0] [solved_targets=0] [merge=0] [gumbel=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,12 +60,14 @@ selection = engine.selection_arg("alphazero" if arg(16, 0) else "reference")
 solve_empties = arg(17, 0) if arg(17, 0) > 0 else None
 solved_targets = bool(arg(18, 0))
 merge = (None, "unique", "rows")[arg(19, 0)]
+gumbel = (arg(20, 0), 256) if arg(20, 0) > 0 else None
+sp_n_thr = 1 if gumbel is not None else 15
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
 tr = ReinforceTrainer(network.SLPolicy(), pool_dir=None, N=32, seed=0)
 vt = SupervisedTrainer(network.Value(), "value", seed=0, native=True)
-m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=15,
-                       capacity=engine.suggest_capacity(sims, 15), seed=1, backup=backup,
+m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_thr=sp_n_thr,
+                       capacity=engine.suggest_capacity(sims, sp_n_thr), seed=1, backup=backup,
                        selection=selection)   # default engine: the persistent search
 sp = engine.SelfPlayEngine(m)
 window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
@@ -111,8 +118,10 @@ def one():
     tr.model1.eval()
     vt.model.eval()
     extra = {} if solve_empties is None else dict(solve_empties=solve_empties, solved_targets=solved_targets)
-    res = sp.play(sims, explore_turns=8, playout_cap=playout_cap, root_noise=root_noise, forced_playouts=forced_playouts,
-                  **extra)
+    if gumbel is not None:
+        extra["gumbel"] = gumbel
+    res = sp.play(sims, explore_turns=None if gumbel is not None else 8, playout_cap=playout_cap, root_noise=root_noise,
+                  forced_playouts=forced_playouts, **extra)
     added = tr.add_to_window(window, res.tuples())
     if solved_targets:
         n = tr.add_to_window(window, res.solved_tuples())
@@ -143,10 +152,11 @@ for i in range(iters):
         print("round %d, %.1f s" % (i + 1, time.perf_counter() - t0), file=sys.stderr, flush=True)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
-print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d playouts per move, explore_turns 8) -> "
+print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d playouts per move, %s) -> "
                             "replay window of %d rows -> %d x (sample %d rows in random symmetries -> SLPolicy on the "
-                            "visit counts + Value on the results, native), 1 x MI355X"
-                            % (games, sims, window.capacity, updates, rows),
+                            "%s + Value on the results, native), 1 x MI355X"
+                            % (games, sims, "explore_turns 8" if gumbel is None else "the Gumbel root search, m %d" % gumbel[0],
+                               window.capacity, updates, rows, "visit counts" if gumbel is None else "improved policy"),
                   "rounds": iters, "seconds": dt, "rounds_per_sec": iters / dt,
                   "rows_added": added, "rows_added_per_sec": added / dt,
                   "rows_trained": iters * updates * rows, "rows_trained_per_sec": iters * updates * rows / dt,
@@ -155,7 +165,7 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "kl_first": kls[first], "kl_last": kls[-1],
                   "value_loss_first": vlosses[first], "value_loss_last": vlosses[-1],
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
-                  "root_noise": root_noise, "forced_playouts": forced_playouts, "backup": backup, "selection": selection,
+                  "root_noise": root_noise, "forced_playouts": forced_playouts, "gumbel": gumbel, "self_play_n_thr": sp_n_thr, "backup": backup, "selection": selection,
                   "solve_empties": solve_empties, "solved_targets": solved_targets,
                   **({"solved_rows_added": solved_rows[0]} if solved_targets else {}),
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {}),
