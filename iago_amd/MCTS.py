@@ -66,8 +66,9 @@ class MCTS(object):
                                                                                         solve_empties))
         self.solve_empties = solve_empties
         self.n_solved = 0
-        self.gumbel = self._m._gumbel_arg(gumbel)
-        if self.gumbel is not None and n_sims is None:
+        self._root = engine.root_rule(None, gumbel=gumbel, engine=self._m)   # (the turn loop's rule; n_sims: search() checks it)
+        self.gumbel = self._root and self._root.gumbel
+        if self._root is not None and n_sims is None:
             raise ValueError("gumbel needs n_sims: the halving's schedule is built for the budget")
         self._turn = 0   # (gumbel: searched get_move calls so far, the draw's turn)
 
@@ -81,23 +82,21 @@ class MCTS(object):
                 if move >= 0:   # (a pass or a finished game: the search answers as it always has)
                     self.n_solved += 1
                     return move
-        if self.gumbel is not None:
-            self._m.search(own, opp, self._one, self.n_sims, gumbel=self.gumbel, turn=self._turn)
+        if self._root is not None:   # (the rule's search of turn k, then its move in the engine's move buffer)
+            self._m.search(own, opp, self._one, self.n_sims, **self._root._asdict(), turn=self._turn)
             self._turn += 1
-            move = int(self._m.gumbel_move(self._one)[0].item())
-            if move == -2:
-                raise ValueError("max() arg is an empty sequence: the root has no children (fewer than n_thr playouts)")
-            return move
-        if self.n_sims is not None:
-            self._m.search(own, opp, self._one, self.n_sims)
+            self._root.move(self._m, self._one)
+            move = int(self._m.move[0].item())
         else:
-            start = time.time()
-            while time.time() - start < self.time_limit:
-                self._m.search(own, opp, self._one, self.chunk)
-        move = int(self._m.best_move(self._one)[0].item())
-        if move == -2:
-            raise ValueError("max() arg is an empty sequence: the root has no children "
-                             "(fewer than n_thr playouts)")  # what MCTS.py:147 raises
+            if self.n_sims is not None:
+                self._m.search(own, opp, self._one, self.n_sims)
+            else:
+                start = time.time()
+                while time.time() - start < self.time_limit:
+                    self._m.search(own, opp, self._one, self.chunk)
+            move = int(self._m.best_move(self._one)[0].item())
+        if move == -2:   # (what MCTS.py:147 raises)
+            raise ValueError("max() arg is an empty sequence: the root has no children (fewer than n_thr playouts)")
         return move
 
     def update_with_move(self, last_move):

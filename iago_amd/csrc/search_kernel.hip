@@ -1922,10 +1922,8 @@ __global__ void search_scratch_warm_kernel(uint32_t *out, int n)
         out[0] = sum;
 }
 
-// The kernels a search can be launched as, and what the runtime has said of each.  It is asked once per device (a
-// process may drive several): every launch comes through here.
-enum Form { F_SINGLE, F_WAVE, F_PARK, F_GAME, F_GAME_PARK, F_NET, F_ARENA, F_NOISE, F_GAME_NOISE, F_GUMBEL, F_GAME_GUMBEL, N_FORMS };
-
+// What the runtime has said of a kernel a search can be launched as.  It is asked once per device (a process may drive
+// several): every launch comes through here.
 struct FormCache {
     const void *kernel;
     std::atomic<uint64_t> reserved{0}; // devices on which its dynamic LDS is reserved (iago_reserve_lds's bits)
@@ -1933,41 +1931,58 @@ struct FormCache {
     struct {
         int lds = -1, per_cu = 0, cus = 0; // workgroups per CU at `lds` bytes of dynamic LDS (-1 = not asked yet); the
     } on[64];                              // device's CUs, where a caller counts them too (0 = not asked yet)
-} form_cache[N_FORMS] = {{(const void *)search_kernel},      {(const void *)search_wave_kernel},
-                         {(const void *)search_park_kernel}, {(const void *)search_game_kernel},
-                         {(const void *)search_game_park_kernel}, {(const void *)search_net_kernel},
-                         {(const void *)search_arena_kernel},     {(const void *)search_noise_kernel},
-                         {(const void *)search_game_noise_kernel}, {(const void *)search_gumbel_kernel},
-                         {(const void *)search_game_gumbel_kernel}};
+};
+
+// The variants of a launch, one row each: the entry point's name, its refusal when the single launch's LDS cannot be
+// reserved (none: iago_mcts_search_capacity reserves the plain kernel's), the single launch's kernel and the role split's
+// game launch's (none: the wave search is not split), each with its books beside it.  The two kernel columns are typed by
+// their argument lists: a kernel named in the other column does not compile.
+using SearchKernel = void (*)(SearchParams, iago_row::HwParams, iago_trunk::TrunkRParams, iago_policy::PolicyParams);
+using GameKernel = void (*)(SearchParams, iago_row::HwParams);
+struct Variant {
+    const char *who, *no_lds;
+    SearchKernel single;
+    GameKernel game;
+    FormCache single_form{(const void *)single}, game_form{(const void *)game};
+};
+struct {
+    Variant plain, wave, park, noise, gumbel; // (forced playouts: the noise variant)
+} variants = {
+    {"iago_mcts_search_persistent", nullptr, search_kernel, search_game_kernel},
+    {"iago_mcts_search_wave", "iago_mcts_search_wave: cannot reserve the nets' LDS image", search_wave_kernel, nullptr},
+    {"iago_mcts_search_park", "iago_mcts_search_park: cannot reserve the nets' LDS image", search_park_kernel, search_game_park_kernel},
+    {"iago_mcts_search_noise", "iago_mcts_search_noise: cannot reserve the nets' LDS image", search_noise_kernel, search_game_noise_kernel},
+    {"iago_mcts_search_gumbel", "iago_mcts_search_gumbel: cannot reserve the nets' LDS image", search_gumbel_kernel, search_game_gumbel_kernel}};
+FormCache net_form{(const void *)search_net_kernel}, arena_form{(const void *)search_arena_kernel};
 std::mutex form_cache_mutex; // (static_lds and on[]; `reserved` is iago_reserve_lds's own)
 
 // reserves `bytes` of dynamic LDS for the form on the current device; `who`: the message of a failure
-int reserve_lds(Form f, int bytes, const char *who) { return iago_reserve_lds(form_cache[f].kernel, bytes, form_cache[f].reserved, who); }
+int reserve_lds(FormCache &f, int bytes, const char *who) { return iago_reserve_lds(f.kernel, bytes, f.reserved, who); }
 
 // the form's static LDS; false: the runtime does not answer
-bool static_lds_of(Form f, int &bytes)
+bool static_lds_of(FormCache &f, int &bytes)
 {
     std::lock_guard<std::mutex> lock(form_cache_mutex);
     hipFuncAttributes fa;
-    if (form_cache[f].static_lds < 0 && hipFuncGetAttributes(&fa, form_cache[f].kernel) == hipSuccess)
-        form_cache[f].static_lds = (int)fa.sharedSizeBytes;
-    bytes = form_cache[f].static_lds;
+    if (f.static_lds < 0 && hipFuncGetAttributes(&fa, f.kernel) == hipSuccess)
+        f.static_lds = (int)fa.sharedSizeBytes;
+    bytes = f.static_lds;
     return bytes >= 0;
 }
 
 // the form's workgroups per CU of device `dev` at `lds` bytes of dynamic LDS, and the device's CUs where `cus` is given;
 // false: the device does not answer.  One answer is kept per device: that for the LDS size asked about last
-bool residency_of(Form f, int dev, int lds, int &per_cu, int *cus)
+bool residency_of(FormCache &f, int dev, int lds, int &per_cu, int *cus)
 {
     std::lock_guard<std::mutex> lock(form_cache_mutex);
-    auto &r = form_cache[f].on[dev & 63];
+    auto &r = f.on[dev & 63];
     if (cus && r.cus < 1 && hipDeviceGetAttribute(&r.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
         r.cus = 0;
         return false;
     }
     if (r.lds != lds) {
         r.lds = -1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.per_cu, form_cache[f].kernel, 256, (size_t)lds) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r.per_cu, f.kernel, 256, (size_t)lds) != hipSuccess)
             return false;
         r.lds = lds;
     }
@@ -1983,12 +1998,12 @@ extern "C" int iago_mcts_search_capacity(int32_t *cus, int32_t *workgroups_per_c
 {
     if (!cus || !workgroups_per_cu)
         return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_capacity: null pointer");
-    if (reserve_lds(F_SINGLE, search_lds(), "iago_mcts_search_capacity: cannot reserve the nets' LDS image"))
+    if (reserve_lds(variants.plain.single_form, search_lds(), "iago_mcts_search_capacity: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
     int dev = 0, n_cu = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_capacity: hipGetDevice failed");
-    if (!residency_of(F_SINGLE, dev, search_lds(), per, &n_cu))
+    if (!residency_of(variants.plain.single_form, dev, search_lds(), per, &n_cu))
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_capacity: the device does not answer");
     if (n_cu < 1 || per < 1 || per > 255)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_capacity: the search kernel does not fit a CU of this device");
@@ -2017,6 +2032,11 @@ struct LaunchRequest {
     const iago_root_noise *noise = nullptr;       // root noise: the counts rows applied where a root expands
     int forced_k_256 = 0;                         // forced playouts at the root (with noise): k_256, 0 = none
     const iago_gumbel_root *gumbel = nullptr;     // the Gumbel root rule: tables, schedule, draws and constants
+    // the row of `variants` this request is launched as
+    Variant &variant() const
+    {
+        return wave ? variants.wave : gumbel ? variants.gumbel : noise ? variants.noise : park ? variants.park : variants.plain;
+    }
 };
 
 // games_per_workgroup without its flags (IAGO_SEARCH_CHAIN_SKIP, IAGO_SEARCH_NEGAMAX, IAGO_SEARCH_PUCT_AZ)
@@ -2132,8 +2152,9 @@ int size_grid(const iago_mcts_search_args *a, const LaunchRequest &q, SearchGrid
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: the streams belong to another device");
         if (a->max_cus != 0)
             return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: max_cus must be 0 (the split owns the device's CUs)");
-        // (park, noise, gumbel: the game launch's other instantiations, with books of their own)
-        const Form game = q.gumbel ? F_GAME_GUMBEL : q.noise ? F_GAME_NOISE : q.park ? F_GAME_PARK : F_GAME;
+        if (!q.variant().game)
+            return iago_fail(IAGO_ERR_INVALID, "iago_mcts_search_split: this search has no game launch (the wave search is not split)");
+        FormCache &game = q.variant().game_form; // (every variant's game launch is an instantiation with books of its own)
         const size_t want = (size_t)G.gpw * (size_t)a->path_stride * 4u;
         int fixed = 0, per_game = 0;
         if (!static_lds_of(game, fixed))
@@ -2314,43 +2335,21 @@ int launch_search(const iago_mcts_search_args *a, void *stream, const LaunchRequ
         return rc;
     const dim3 grid((unsigned)G.grid), block(256);
     iago_search_streams *const sp = q.streams;
+    Variant &v = q.variant();
     if (!sp) {
-        const Form f = q.wave ? F_WAVE : q.gumbel ? F_GUMBEL : q.noise ? F_NOISE : q.park ? F_PARK : F_SINGLE;
-        const char *const who = q.wave     ? "iago_mcts_search_wave"
-                                : q.gumbel ? "iago_mcts_search_gumbel"
-                                : q.noise  ? "iago_mcts_search_noise"
-                                : q.park   ? "iago_mcts_search_park"
-                                           : "iago_mcts_search_persistent";
-        // (the search kernel's LDS: reserved by iago_mcts_search_capacity)
-        if (f != F_SINGLE && reserve_lds(f, lds, q.wave     ? "iago_mcts_search_wave: cannot reserve the nets' LDS image"
-                                                 : q.gumbel ? "iago_mcts_search_gumbel: cannot reserve the nets' LDS image"
-                                                 : q.noise  ? "iago_mcts_search_noise: cannot reserve the nets' LDS image"
-                                                            : "iago_mcts_search_park: cannot reserve the nets' LDS image"))
+        if (v.no_lds && reserve_lds(v.single_form, lds, v.no_lds))
             return IAGO_ERR_HIP;
-        switch (f) {
-        case F_GUMBEL: hipLaunchKernelGGL(search_gumbel_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
-        case F_NOISE: hipLaunchKernelGGL(search_noise_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
-        case F_WAVE: hipLaunchKernelGGL(search_wave_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
-        case F_PARK: hipLaunchKernelGGL(search_park_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
-        default: hipLaunchKernelGGL(search_kernel, grid, block, lds, (hipStream_t)stream, S, R, VP, PP); break;
-        }
-        return iago_check_launch(who);
+        hipLaunchKernelGGL(v.single, grid, block, lds, (hipStream_t)stream, S, R, VP, PP);
+        return iago_check_launch(v.who);
     }
     // both launches after everything queued on the caller's stream so far (the zeroing above included), the caller's
     // stream after both.  The game launch first: the net workgroups leave when the game workgroups have finished
-    if (reserve_lds(F_NET, lds, "iago_mcts_search_split: cannot reserve the nets' LDS image"))
+    if (reserve_lds(net_form, lds, "iago_mcts_search_split: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
     if (hipEventRecord(sp->ready, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sp->game, sp->ready, 0) != hipSuccess ||
         hipStreamWaitEvent(sp->net, sp->ready, 0) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_split: cannot order the launches after the stream");
-    if (q.gumbel)
-        hipLaunchKernelGGL(search_game_gumbel_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
-    else if (q.noise)
-        hipLaunchKernelGGL(search_game_noise_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
-    else if (q.park)
-        hipLaunchKernelGGL(search_game_park_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
-    else
-        hipLaunchKernelGGL(search_game_kernel, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
+    hipLaunchKernelGGL(v.game, dim3((unsigned)G.n_game_wgs), block, G.game_lds, sp->game, S, R);
     int rc = iago_check_launch("iago_mcts_search_split (game launch)");
     if (rc == IAGO_OK) {
         hipLaunchKernelGGL(search_net_kernel, dim3((unsigned)G.net_wgs), block, lds, sp->net, S, VP, PP);
@@ -2650,12 +2649,12 @@ extern "C" int iago_mcts_search_arena(const iago_mcts_search_args *a, const iago
     if (const int rc = iago_mcts_search_capacity(&cus, &per_cu))
         return rc;
     constexpr int lds = search_lds();
-    if (reserve_lds(F_ARENA, lds, "iago_mcts_search_arena: cannot reserve the nets' LDS image"))
+    if (reserve_lds(arena_form, lds, "iago_mcts_search_arena: cannot reserve the nets' LDS image"))
         return IAGO_ERR_HIP;
     int dev = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess)
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: hipGetDevice failed");
-    if (!residency_of(F_ARENA, dev, lds, per, nullptr))
+    if (!residency_of(arena_form, dev, lds, per, nullptr))
         return iago_fail(IAGO_ERR_HIP, "iago_mcts_search_arena: the device does not answer");
     if (per < 1)
         return iago_fail(IAGO_ERR_CAPACITY, "iago_mcts_search_arena: the arena kernel does not fit a CU of this device");

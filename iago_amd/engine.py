@@ -49,6 +49,88 @@ PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns pla
 NO_RULES = PlayRules(None, 0, None)
 
 
+# ---- The root rules -------------------------------------------------------------------------------------------------------
+# What a search does at its roots: nothing of its own (None: the plain root), root noise with or without forced playouts, or
+# the Gumbel root search.  All that differs between them is here ("The root rules").
+class RootRule(collections.namedtuple("RootRule", "root_noise forced_playouts gumbel")):
+    """A rule as search() takes it, validated (root_rule).  It answers: the engines it is offered for, the step before the
+    launch, the launch, the move, the recorded policy target."""
+    __slots__ = ()
+    fresh = property(lambda self: self.gumbel is not None)   # FRESH roots: search() resets the searched trees, no compaction
+    targets = property(lambda self: self.gumbel is not None or self.forced_playouts is not None)   # a target of its own
+
+    def require(self, m):
+        """The persistent search only; Gumbel under the negamax backup and the AlphaZero selection.  m None: not asked."""
+        if m is not None and self.gumbel is not None and getattr(m, "backup", "reference") != "negamax":
+            raise ValueError("gumbel needs backup=\"negamax\" (a root child's Q must be the root mover's value)")
+        if m is not None and self.gumbel is not None and getattr(m, "selection", "reference") != "alphazero":
+            raise ValueError("gumbel needs selection=\"alphazero\" (a child's stored prior must be the policy's p)")
+        if m is not None and (not getattr(m, "persistent", False) or getattr(m, "wave_entry", False)
+                              or getattr(m, "rollout_hook", None) is not None or getattr(m, "use_graph", False)
+                              or getattr(m, "async_steps", False) or getattr(m, "lookahead", 0)):
+            raise ValueError("%s is offered for the persistent search only (not use_graph, async steps, the look-ahead, "
+                             "rollout_hook or the wave search)" % ("root_noise" if self.gumbel is None else "gumbel"))
+        return self
+
+    def draw(self, m, own, opp, active, turn):
+        """Before the launch: the urn of turn `turn` (the counts rows, the mix on the children the roots have), or the draw."""
+        if self.gumbel is None:
+            ops.root_noise(m.tree.ref(), active, own, opp, m.seed, *m._turn_ids(turn), self.root_noise, m._noise_rows())
+        else:
+            st = m._gumbel_state()
+            ops.gumbel_draw(m.tree.ref(), active, m.seed, *m._turn_ids(turn), self.gumbel, st["tables"], st["g"])
+
+    def launch(self, m, args, n_sims, game=None):
+        """The rule's entry point on the engine's split handle; never whole games."""
+        if game is not None:
+            raise ValueError("whole games in one launch are not available with %s (the turn loop is)"
+                             % ("root noise" if self.gumbel is None else "the Gumbel root search"))
+        if self.gumbel is not None:
+            st = m._gumbel_state()
+            ops.search_gumbel(args, self.gumbel, st["tables"], m._gumbel_sched(self.gumbel[0], n_sims), st["g"], streams=m._split)
+            st["last"] = self.gumbel
+        elif self.forced_playouts is None:
+            ops.search_noise(args, self.root_noise, m._noise_rows(), streams=m._split)
+        else:
+            ops.search_forced(args, self.root_noise, m._noise_rows(), self.forced_playouts, streams=m._split)
+
+    def move(self, m, active, record=False):
+        """After the search: the Gumbel root writes the halving's survivor over best_move's in the engine's move buffer and,
+        for a recorded game, returns the improved policy of the rows it fills (made now, before the turn's other launches)."""
+        if self.gumbel is not None:
+            rows = m.gumbel_rows(active, self.gumbel)
+            return gumbel_targets(rows, self.gumbel[2], self.gumbel[1]) if record else None
+
+    def target(self, m, active, made):
+        """With `targets`, the recorded policy target of the searched games: what move() made, or the pruned visit row."""
+        return made if self.gumbel is not None else m.pruned_visits(active, self.forced_playouts)
+
+    @classmethod
+    def of(cls, rules):
+        """The RootRule of a PlayRules (validated: _play_rules), None: the plain root."""
+        root = cls(rules.root_noise, rules.forced_playouts, rules.gumbel)
+        return None if root == (None, None, None) else root
+
+
+def root_rule(n_sims, root_noise=None, forced_playouts=None, gumbel=None, explore_turns=None, beside="", engine=None):
+    """The RootRule of search()'s or play()'s arguments (None: the plain root), each refused where its validator refuses
+    it, in search()'s order.  The one place that knows what excludes what: gumbel stands alone (explore_turns, `beside`:
+    play()'s) and needs n_sims in [1, 32767] (None: no budget yet); forced_playouts needs root_noise.  engine: require()."""
+    gz, root = ops.gumbel_arg(gumbel), None
+    if gz is not None:
+        if root_noise is not None or forced_playouts is not None or ops.explore_turns_arg(explore_turns):
+            raise ValueError("gumbel is not available together with %sroot_noise or forced_playouts (the Gumbel root search "
+                             "explores by its own draw)" % beside)
+        root = RootRule(None, None, gz).require(engine)
+        if n_sims is not None and not 1 <= n_sims <= 32767:
+            raise ValueError("gumbel: n_sims must be in [1, 32767], not %r" % (n_sims,))
+    noise = ops.root_noise_arg(root_noise)
+    if noise is not None:
+        root = RootRule(noise, None, None).require(engine)
+    k_256 = ops.forced_playouts_arg(forced_playouts, noise)
+    return root if k_256 is None else root._replace(forced_playouts=k_256)
+
+
 class AlphaBeta(collections.namedtuple("AlphaBeta", "depth split", defaults=(0,))):
     """The fixed-depth alpha-beta opponent of SelfPlayEngine.play_match(opponent=): ops.alphabeta_moves at `depth` (an
     int in [1, 10]), the outside yardstick that owes nothing to the nets.  split (0, the default: none; 1 or 2, below
@@ -1283,38 +1365,27 @@ class BatchedMCTS(object):
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _search_persistent(self, own, opp, active, n_sims, n_active, root_noise=None, turn=0, forced=None, gumbel=None):
-        """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent).  root_noise = (alpha_256, eps_256,
-        draws): the urn of turn `turn` first (ops.root_noise: the counts rows, the mix on the children the roots have),
-        then the launch that applies the rows where a root expands (iago_mcts_search_noise; forced = k_256: with forced
-        playouts at the root, iago_mcts_search_forced).  gumbel = (m, c_scale_256, c_visit): the draw of turn `turn` first
-        (ops.gumbel_draw), then the launch with the Gumbel rule at the roots (iago_mcts_search_gumbel)."""
-        if gumbel is not None:
-            ids, turns = self._turn_ids(turn)
-            st = self._gumbel_state()
-            ops.gumbel_draw(self.tree.ref(), active, self.seed, ids, turns, gumbel, st["tables"], st["g"])
-            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, gumbel=gumbel))
-            st["last"] = gumbel
-        elif root_noise is None:
+    def _search_persistent(self, own, opp, active, n_sims, n_active, root=None, turn=0):
+        """n_sims playouts per active game as ONE launch (iago_mcts_search_persistent).  root (a RootRule): its draw of
+        turn `turn` first, then the launch under it."""
+        if root is None:
             self._launch_persistent(own, opp, active, n_sims)
         else:
-            ids, turns = self._turn_ids(turn)
-            ops.root_noise(self.tree.ref(), active, own, opp, self.seed, ids, turns, root_noise, self._noise_rows())
-            self._launch_persistent(own, opp, active, n_sims, PlayRules(None, 0, None, root_noise, forced))
+            root.draw(self, own, opp, active, turn)
+            self._launch_persistent(own, opp, active, n_sims, root=root)
         self.sim_counter = (self.sim_counter + n_sims) & 0xFFFFFFFF
         self.n_leaf_evals += n_active * n_sims
 
-    def _launch_persistent(self, own, opp, active, n_sims, rules=NO_RULES, game=None, park=None):
+    def _launch_persistent(self, own, opp, active, n_sims, rules=NO_RULES, game=None, park=None, root=None):
         """iago_mcts_search_persistent: one search from the roots (own, opp), or -- game = dict(max_turns, own,
         opp, n_turns, rec_own, rec_opp, rec_valid, rec_move, rec_pi) -- whole self-play games under `rules` (a
         PlayRules).  park = dict(parked, stones, pass_flg), given with rules.solve_empties: those games handed over at
         that many empties (iago_mcts_search_park); rules.explore_turns: their moves of the turns below it drawn from the
         visit counts (iago_mcts_search_explore, which carries the hand-over); rules.playout_cap: their searched turns
-        full or fast (iago_mcts_search_cap, which carries the other two).  rules.root_noise (one search only, no `game`):
-        a root that expands takes the counts row ops.root_noise left (iago_mcts_search_noise), and with
-        rules.forced_playouts the root's select forces (iago_mcts_search_forced).  The role split where it is set up,
-        else the single launch, whichever entry point takes the games."""
+        full or fast (iago_mcts_search_cap, which carries the other two).  root (a search's RootRule, else `rules`' own;
+        never with `game`): RootRule.launch.  The role split where it is set up, else the single launch."""
         a, keep = self._search_args(own, opp, active, n_sims, game)
+        root = root or RootRule.of(rules)
         ev = getattr(self, "launch_events", None)   # (bench.py: HIP event pairs around the launches, on their stream)
         if ev is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -1331,19 +1402,8 @@ class BatchedMCTS(object):
             w.width, w.vloss, w.timing = self.wave, self.virtual_loss, self.wave_timing.data_ptr()
             self._wave_active = active
             check(_lib.lib().iago_mcts_search_wave(C.byref(a), C.byref(w), _stream()), "iago_mcts_search_wave")
-        elif rules.gumbel is not None:
-            if game is not None:
-                raise ValueError("whole games in one launch are not available with the Gumbel root search (the turn loop is)")
-            st = self._gumbel_state()
-            ops.search_gumbel(a, rules.gumbel, st["tables"], self._gumbel_sched(rules.gumbel[0], n_sims), st["g"],
-                              streams=self._split)
-        elif rules.root_noise is not None:
-            if game is not None:
-                raise ValueError("whole games in one launch are not available with root noise (the turn loop is)")
-            if rules.forced_playouts is None:
-                ops.search_noise(a, rules.root_noise, self._noise_rows(), streams=self._split)
-            else:
-                ops.search_forced(a, rules.root_noise, self._noise_rows(), rules.forced_playouts, streams=self._split)
+        elif root is not None:
+            root.launch(self, a, n_sims, game)
         elif rules.playout_cap is not None:
             ops.search_cap(a, *rules.playout_cap, explore_turns=rules.explore_turns, streams=self._split, park=k)
         elif rules.explore_turns:
@@ -1463,26 +1523,7 @@ class BatchedMCTS(object):
             sched[m, n_sims] = torch.from_numpy(ops.gumbel_schedule(m, n_sims)).to(self.cur_own.device)
         return sched[m, n_sims]
 
-    def _gumbel_arg(self, gumbel, root_noise=None, forced_playouts=None):
-        """search()'s gumbel, validated: offered for the persistent engine under backup="negamax" and
-        selection="alphazero", and not together with root noise or forced playouts (the rule explores by its own draw)."""
-        gz = ops.gumbel_arg(gumbel)
-        if gz is None:
-            return None
-        if root_noise is not None or forced_playouts is not None:
-            raise ValueError("gumbel is not available together with root_noise or forced_playouts (the Gumbel root search "
-                             "explores by its own draw)")
-        if self.backup != "negamax":
-            raise ValueError("gumbel needs backup=\"negamax\" (a root child's Q must be the root mover's value)")
-        if self.selection != "alphazero":
-            raise ValueError("gumbel needs selection=\"alphazero\" (a child's stored prior must be the policy's p)")
-        if (not self.persistent or self.wave_entry or self.rollout_hook is not None or self.use_graph or self.async_steps
-                or self.lookahead):
-            raise ValueError("gumbel is offered for the persistent search only (not use_graph, async steps, the look-ahead, "
-                             "rollout_hook or the wave search)")
-        return gz
-
-    def _backup_check(self):
+    def _backup_check(self, rules=NO_RULES):
         """backup="negamax" and selection="alphazero" are the persistent search's alone: a rollout hook (set after
         construction) would send search() and SelfPlayEngine's turns through the per-playout launches, whose rules are the
         reference's.  Refused where a search or a round of games begins, before anything is reset."""
@@ -1491,16 +1532,8 @@ class BatchedMCTS(object):
             raise ValueError(_NEGAMAX_NEEDS)
         if getattr(self, "selection", "reference") == "alphazero" and per_playout:
             raise ValueError(_ALPHAZERO_NEEDS)
-
-    def _root_noise_arg(self, root_noise):
-        """search()'s root_noise, validated: offered for the persistent engine only."""
-        noise = ops.root_noise_arg(root_noise)
-        if noise is not None and (not getattr(self, "persistent", False) or getattr(self, "wave_entry", False)
-                                  or self.rollout_hook is not None or getattr(self, "use_graph", False)
-                                  or getattr(self, "async_steps", False) or getattr(self, "lookahead", 0)):
-            raise ValueError("root_noise is offered for the persistent search only (not use_graph, async steps, the "
-                             "look-ahead, rollout_hook or the wave search)")
-        return noise
+        if RootRule.of(rules) is not None:   # (likewise the root rule of a round of games)
+            RootRule.of(rules).require(self)
 
     def search_counts(self, active):
         """Device tensor int64[2]: games in `active`, nodes of the fullest pool -- what search()
@@ -1529,11 +1562,7 @@ class BatchedMCTS(object):
         in which the root serves the sequential-halving schedule of (m, n_sims).  gumbel_move() afterwards gives the
         halving's survivor and gumbel_rows() the rows the improved-policy target is made from (gumbel_targets)."""
         self._backup_check()
-        gz = self._gumbel_arg(gumbel, root_noise, forced_playouts)
-        if gz is not None and not 1 <= n_sims <= 32767:
-            raise ValueError("gumbel: n_sims must be in [1, 32767], not %r" % (n_sims,))
-        noise = self._root_noise_arg(root_noise)
-        forced = ops.forced_playouts_arg(forced_playouts, noise)
+        root = root_rule(n_sims, root_noise, forced_playouts, gumbel, engine=self)
         n_active, used = (int(v) for v in (self.search_counts(active).tolist() if counts is None else counts))
         if n_active == 0:
             # (the playout counter advances all the same: a game's Philox streams are keyed by ITS turn and
@@ -1556,17 +1585,12 @@ class BatchedMCTS(object):
                 self._policy_key = key
             if self._la_stale_any:
                 self._refresh_priors(own, opp, active)
-        if gz is not None:
-            self.tree.reset(active)   # (fresh roots: nothing left to compact in the searched games)
-            self._search_persistent(own, opp, active, n_sims, n_active, turn=turn, gumbel=gz)
-            if check:
-                self.raise_errors(self.error_flags().tolist())
-            return
-        self._compact_if_half_full(used)
-        if noise is not None:
-            self._search_persistent(own, opp, active, n_sims, n_active, noise, turn, forced)
-        elif self.persistent and self.rollout_hook is None:
-            self._search_persistent(own, opp, active, n_sims, n_active)
+        if root is not None and root.fresh:
+            self.tree.reset(active)   # (nothing left to compact in the searched games)
+        else:
+            self._compact_if_half_full(used)
+        if root is not None or (self.persistent and self.rollout_hook is None):
+            self._search_persistent(own, opp, active, n_sims, n_active, root, turn)
         elif self.async_steps and self.rollout_hook is None:
             self._search_async(own, opp, active, n_sims, n_active)
         elif self.use_graph:
@@ -1890,19 +1914,15 @@ def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None
     None, None, None): explore_turns is an int in the record.  solved_targets: a bool, True only with solve_empties.
     gumbel: (m, c_scale_256[, c_visit]), refused together with explore_turns, root_noise or forced_playouts."""
     noise = ops.root_noise_arg(root_noise)
-    gz = ops.gumbel_arg(gumbel)
-    if gz is not None and (noise is not None or forced_playouts is not None or ops.explore_turns_arg(explore_turns)):
-        raise ValueError("gumbel is not available together with explore_turns, root_noise or forced_playouts (the Gumbel "
-                         "root search explores by its own draw)")
-    if gz is not None and not 1 <= n_sims <= 32767:
-        raise ValueError("gumbel: n_sims must be in [1, 32767], not %r" % (n_sims,))
+    # (the Gumbel checks now; forced_playouts, where no gumbel excludes it, after the others below)
+    root = root_rule(n_sims, noise, forced_playouts if gumbel is not None else None, gumbel, explore_turns, "explore_turns, ")
     if not isinstance(solved_targets, bool):
         raise ValueError("solved_targets must be a bool, not %r" % (solved_targets,))
     if solved_targets and solve_empties is None:
         raise ValueError("solved_targets records the solver's optimal moves: it needs solve_empties")
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
                      ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise),
-                     solved_targets, gz)
+                     solved_targets, root and root.gumbel)
 
 
 def _no_forced_playouts(forced_playouts, who):
@@ -2140,9 +2160,8 @@ class SelfPlayEngine(object):
         fallback, whose searches (one launch per turn) compact a pool that is half full.  Same games either way."""
         m = self.mcts
         m.tree.reset()
-        # (root noise: the urn is drawn per turn by a launch of its own, ops.root_noise -- the turn loop)
-        # (the Gumbel root search: a draw and a finish per turn, launches of their own -- the turn loop)
-        if not (applies and rules.root_noise is None and rules.gumbel is None and self._whole_games_in_one_launch(n_sims)):
+        # (a root rule draws per turn by a launch of its own, ops.root_noise or ops.gumbel_draw -- the turn loop)
+        if not (applies and RootRule.of(rules) is None and self._whole_games_in_one_launch(n_sims)):
             return None
         res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, rules, **kw)
         if res is None:
@@ -2153,16 +2172,12 @@ class SelfPlayEngine(object):
     def _search_sides(self, sides, own, opp, rules):
         """The turn's searches, one side after the other (check=False: the loop reads every side's flags back).  Under a
         playout cap TWO searches per side from the same sim_counter -- a fast turn is the first n_fast playouts of the
-        full turn's search: the same Philox streams -- and the counter n_sims on, once.  Under root noise the search (of
-        a cap's two the full games' alone: a fast turn searches the clean priors) takes rules.root_noise and the side's
-        turn, and with it rules.forced_playouts.  Returns 1: a SelfPlayResult's `launches` counts the turns."""
+        full turn's search: the same Philox streams -- and the counter n_sims on, once.  A root rule goes with the search
+        (of a cap's two with the full games' alone) beside the side's turn.  Returns 1: `launches` counts the turns."""
+        root = RootRule.of(rules)
         for s in sides:
             m = s.mcts
-            kw = {} if rules.root_noise is None else dict(root_noise=rules.root_noise, turn=s.turn)   # (off: today's calls)
-            if rules.forced_playouts is not None:
-                kw["forced_playouts"] = rules.forced_playouts
-            if rules.gumbel is not None:   # (of a cap's two searches the full games' alone: a fast turn is the plain search's)
-                kw = dict(gumbel=rules.gumbel, turn=s.turn)
+            kw = {} if root is None else dict({k: v for k, v in root._asdict().items() if v is not None}, turn=s.turn)
             if rules.playout_cap is None:
                 m.search(own, opp, s.act, s.n_sims, counts=s.counts, check=False, **kw)   # (sim_counter: + n_sims whoever searched)
                 continue
@@ -2207,7 +2222,9 @@ class SelfPlayEngine(object):
         pass_flg = torch.zeros(B, dtype=torch.uint8, device=dev)
         done = torch.zeros(B, dtype=torch.uint8, device=dev)
         rec = self._new_records(B) if record else None
-        if record and (rules.forced_playouts is not None or rules.gumbel is not None):
+        root = RootRule.of(rules)
+        targets = record and root is not None and root.targets   # (the rule's own policy target in pi, the raw row in pi_raw)
+        if targets:
             rec["pi_raw"] = torch.zeros_like(rec["pi"])
         if record and rules.solved_targets:
             rec["best"] = torch.zeros((T, B), dtype=torch.int64, device=dev)
@@ -2251,12 +2268,12 @@ class SelfPlayEngine(object):
                     sol = mine & at_end if sol is None else sol | (mine & at_end)
                     mine = mine & ~at_end
                 s.mine, s.act, s.turn = mine, active if mine is everyone else mine.to(torch.uint8), t
-                if cap is None:
-                    counts["counts", i] = s.mcts.search_counts(s.act)
-                else:
+                s.ruled = s.act   # (the games a root rule searches: every searched one, under a cap the full ones)
+                if cap is not None:
                     s.fast = s.mcts.cap_mask(t, cap[1]) & s.act
-                    s.full = s.act ^ s.fast
-                    counts["counts", i] = s.mcts.search_counts(s.full)
+                    s.full = s.ruled = s.act ^ s.fast
+                counts["counts", i] = s.mcts.search_counts(s.ruled)
+                if cap is not None:
                     counts["counts_fast", i] = s.mcts.search_counts(s.fast)
             return drawn, forced, sol, opening, counts
 
@@ -2273,15 +2290,8 @@ class SelfPlayEngine(object):
             launched += search(sides, own, opp, rules)
             for s in sides:
                 s.move, s.visits = s.mcts.draw_move(t, s.act) if t < rules.explore_turns else s.mcts.best_move(s.act)
-                if rules.gumbel is not None:
-                    # the games the Gumbel rule searched (under a cap the full ones): gumbel_move writes the halving's
-                    # survivor over best_move's most visited child in s.move (the engine's move buffer) and fills the
-                    # rows, from which a recorded game makes its improved-policy target
-                    f = s.act if cap is None else s.full
-                    s.mcts.gumbel_move(f, rules.gumbel)
-                    if record:
-                        st = s.mcts._gumbel_state()
-                        s.gumbel_pi = gumbel_targets((st["n"], st["q"], st["logit"]), rules.gumbel[2], rules.gumbel[1])
+                if root is not None:   # (the rule's own move, written over best_move's in s.move: the engine's move buffer)
+                    s.made = root.move(s.mcts, s.ruled, record)
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
                 if rules.solved_targets:   # (the same score and move, and the set of the optimal moves)
@@ -2331,16 +2341,10 @@ class SelfPlayEngine(object):
                     v = s.act if cap is None else s.act + (_lib.REC_FAST - 1) * s.fast
                     p = s.visits * s.act.reshape(B, 1).to(torch.int32)
                     valid, pi = (v, p) if valid is None else (valid | v, pi + p)
-                if rules.forced_playouts is not None:
+                if targets:
                     rec["pi_raw"][t] = pi
-                    for s in sides:   # (the forced games: the noised search's)
-                        f = s.act if cap is None else s.full
-                        pi = torch.where(f.reshape(B, 1) != 0, s.mcts.pruned_visits(f, rules.forced_playouts), pi)
-                if rules.gumbel is not None:
-                    rec["pi_raw"][t] = pi
-                    for s in sides:   # (the games under the Gumbel rule: the improved policy for the visit row)
-                        f = s.act if cap is None else s.full
-                        pi = torch.where(f.reshape(B, 1) != 0, s.gumbel_pi, pi)
+                    for s in sides:   # (the games the rule searched: its target for the visit row)
+                        pi = torch.where(s.ruled.reshape(B, 1) != 0, root.target(s.mcts, s.ruled, s.made), pi)
                 if policy_moves:
                     valid = valid + _lib.REC_DRAWN * (drawn | forced).to(torch.uint8)
                 if opening is not None:
@@ -2468,9 +2472,7 @@ class SelfPlayEngine(object):
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
-        self.mcts._backup_check()
-        self.mcts._root_noise_arg(rules.root_noise)   # (the persistent engine only: refused before anything is reset)
-        self.mcts._gumbel_arg(rules.gumbel)           # (likewise, and the backup and selection rules it needs)
+        self.mcts._backup_check(rules)   # (an engine the rules are not offered for: refused before anything is reset)
         res = self._one_launch(n_sims, self.B, handicap, record, rules)
         if res is None:
             res = self._play_turns([_Side(self.mcts, n_sims)], *self._start_boards(self.B, handicap), record,
@@ -2496,9 +2498,7 @@ class SelfPlayEngine(object):
         rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts, solved_targets,
                             gumbel)
         m, T = self.mcts, self.max_turns
-        m._backup_check()
-        m._root_noise_arg(rules.root_noise)
-        m._gumbel_arg(rules.gumbel)
+        m._backup_check(rules)
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError("play_stream: n_games >= 1 expected")
@@ -2557,8 +2557,7 @@ class SelfPlayEngine(object):
             col = torch.cat([torch.full((self.B // 2,), c, dtype=torch.int8, device=dev) for c in (1, 2)])
         else:
             col = _colour_arg(2 if mcts_colour is None else mcts_colour, self.B, dev, "play_match: mcts_colour")
-        self.mcts._backup_check()   # (a hooked negamax engine: refused before anything is reset)
-        self.mcts._gumbel_arg(rules.gumbel)
+        self.mcts._backup_check(rules)   # (a hooked negamax engine, say: refused before anything is reset)
         codes = torch.where(col == 1, _lib.MATCH_MCTS_COLOUR_1, _lib.MATCH_MCTS_COLOUR_2).to(torch.uint8)
         plain = match.opponent is None and match.opening_turns == 0
         res = self._one_launch(n_sims, self.B, None, record, rules, applies=rules.solve_empties is None and plain,
@@ -2603,7 +2602,7 @@ class SelfPlayEngine(object):
         res.final_p2 = torch.cat([r.final_p2[:w] for r, w in parts])
         if record:
             cols = {k: [] for k in ("own", "opp", "valid", "move", "pi", "score")}
-            if rules.forced_playouts is not None or rules.gumbel is not None:
+            if RootRule.of(rules) is not None and RootRule.of(rules).targets:
                 cols["pi_raw"] = []
             if rules.solved_targets:
                 cols["best"] = []

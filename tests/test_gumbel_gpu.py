@@ -197,7 +197,7 @@ def test_one_move_a_pass_and_the_fallback(shipped, probe, tables, golden_rules):
     m.search(o, p, active, 9)
     z1 = m.z_log.cpu().numpy().copy()
     m.z_log_n.zero_()
-    m._search_persistent(o, p, active, 16, SLOTS, turn=1, gumbel=GUMBEL + (gr.C_VISIT,))
+    m._search_persistent(o, p, active, 16, SLOTS, engine.RootRule(None, None, GUMBEL + (gr.C_VISIT,)), 1)
     z2 = m.z_log.cpu().numpy().copy()
     move = m.gumbel_move(active).cpu().numpy().copy()
     fallbacks = 0

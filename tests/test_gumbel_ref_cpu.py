@@ -390,7 +390,9 @@ def test_gumbel_arg_and_play_rules():
 
 def test_the_engine_refuses_the_wrong_rules_without_a_device():
     from iago_amd import engine
-    check = engine.BatchedMCTS._gumbel_arg
+    def check(m, gumbel, **kw):   # (the rule of search()'s arguments, on engine m)
+        rule = engine.root_rule(16, gumbel=gumbel, engine=m, **kw)
+        return rule and rule.gumbel
     ok = dict(backup="negamax", selection="alphazero", persistent=True, wave_entry=False, rollout_hook=None, use_graph=False,
               async_steps=False, lookahead=0)
     assert check(types.SimpleNamespace(**ok), (16, 256)) == (16, 256, 50)
