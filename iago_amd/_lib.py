@@ -55,7 +55,8 @@ EXPERIMENTAL_SYMBOLS = [
 # random openings (ops.alphabeta_moves, ops.random_moves; SelfPlayEngine.play_match(opponent=AlphaBeta(d))), that
 # search with every root spread over the lanes (ops.alphabeta_moves(split=), AlphaBeta(d, split)), and the exact solver
 # spread the same way (ops.solve_endgame(split=), ops.solve_endgame_moves(split=)), and the Gumbel root search
-# (SelfPlayEngine.play(gumbel=), BatchedMCTS.search(gumbel=))
+# (SelfPlayEngine.play(gumbel=), BatchedMCTS.search(gumbel=)), and the root's value read back after a search
+# (ops.mcts_root_value, BatchedMCTS.root_value, SelfPlayEngine.play(root_values=True))
 SERVING_SYMBOLS = [
     "iago_mcts_search_wave", "iago_solve_endgame", "iago_play_endgame", "iago_mcts_search_park",
     "iago_solve_endgame_moves", "iago_play_endgame_moves",
@@ -65,16 +66,20 @@ SERVING_SYMBOLS = [
     "iago_mcts_search_forced", "iago_mcts_prune_visits", "iago_mcts_prune_visits_rule",
     "iago_alphabeta_moves", "iago_random_moves", "iago_alphabeta_moves_split", "iago_solve_endgame_split",
     "iago_mcts_gumbel_draw", "iago_mcts_search_gumbel", "iago_mcts_gumbel_finish",
+    "iago_mcts_root_value",
 ]
 # include/iago_hip_training.h: training the nets on the library's kernels -- the Value net's supervised update
 # (network.Value.value_grads, train_supervised.SupervisedTrainer(native=True)), SLPolicy on the search's visit counts
 # (network.SLPolicy.visits_grads, train_rl.ReinforceTrainer.step_from_tuples(target="visits")), minibatches out of a
 # replay window of self-play rows in random board symmetries (ops.replay_sample, replay.ReplayWindow), the rows'
 # canonical forms, the window merged by position up to symmetry and minibatches out of the merged rows
-# (ops.canonical_rows, ops.replay_merge, ops.replay_sample_merged, ReplayWindow.merge / sample(merged=))
+# (ops.canonical_rows, ops.replay_merge, ops.replay_sample_merged, ReplayWindow.merge / sample(merged=)), the Value
+# net's targets from the search's root values -- z mixed with q, TD(lambda) along the game -- and their sums per merged
+# position (ops.value_targets, SelfPlayResult.value_targets, ops.replay_merge_values, ReplayWindow(value_targets=True))
 TRAINING_SYMBOLS = [
     "iago_value_grad_workspace_bytes", "iago_value_mse_grad", "iago_policy_visits_grad", "iago_replay_sample",
     "iago_canonical_rows", "iago_replay_merge", "iago_replay_sample_merged",
+    "iago_value_targets", "iago_replay_merge_values",
 ]
 
 
@@ -194,6 +199,28 @@ class ReplaySampleMergedArgs(C.Structure):
         ("own_out", C.c_void_p), ("opp_out", C.c_void_p), ("pi_out", C.c_void_p), ("result_out", C.c_void_p),
         ("z_sum_out", C.c_void_p), ("mult_out", C.c_void_p), ("group_out", C.c_void_p), ("sym_out", C.c_void_p),
     ]
+
+
+class ValueTargetsArgs(C.Structure):
+    """Mirror of iago_value_targets_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("valid", C.c_void_p), ("q", C.c_void_p), ("score", C.c_void_p), ("z", C.c_void_p), ("mover", C.c_void_p),
+        ("n_turns", C.c_int64), ("n_games", C.c_int64), ("lam_256", C.c_int32), ("mix_256", C.c_int32),
+        ("out", C.c_void_p),
+    ]
+
+
+class ReplayMergeValuesArgs(C.Structure):
+    """Mirror of iago_replay_merge_values_args (include/iago_hip_training.h)."""
+    _fields_ = [
+        ("order", C.c_void_p), ("group", C.c_void_p), ("first", C.c_void_p), ("mult", C.c_void_p), ("v", C.c_void_p),
+        ("count", C.c_int64), ("n_unique", C.c_int64), ("v_sum", C.c_void_p), ("flags", C.c_void_p),
+    ]
+
+
+VALUE_Q16 = 65536             # a value target, a root value: Q16 (iago_value_targets, iago_mcts_root_value)
+ROOT_VALUE_SATURATED = 1      # IAGO_ROOT_VALUE_SATURATED: bits of iago_mcts_root_value's flags
+ROOT_VALUE_NAN = 2            # IAGO_ROOT_VALUE_NAN
 
 
 class ConvSplitLayer(C.Structure):
@@ -560,6 +587,8 @@ def lib():
     L.iago_canonical_rows.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.iago_replay_merge.argtypes = [C.POINTER(ReplayMergeArgs), vp]
     L.iago_replay_sample_merged.argtypes = [C.POINTER(ReplaySampleMergedArgs), vp]
+    L.iago_value_targets.argtypes = [C.POINTER(ValueTargetsArgs), vp]
+    L.iago_replay_merge_values.argtypes = [C.POINTER(ReplayMergeValuesArgs), vp]
     L.iago_split_nchw.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     L.iago_merge_nchw.argtypes = [vp, vp, vp, i64, i32, vp]
     L.iago_value_stem.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
@@ -581,6 +610,7 @@ def lib():
     L.iago_mcts_mix_backup.argtypes = [tp, vp, vp, vp, vp, C.c_float, vp, vp, vp]
     L.iago_mcts_pending.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
     L.iago_mcts_best_move.argtypes = [tp, vp, vp, vp, vp]
+    L.iago_mcts_root_value.argtypes = [tp, vp, vp, vp, vp, vp]
     L.iago_mcts_advance_root.argtypes = [tp, vp, vp, vp]
     L.iago_mcts_compact.argtypes = [tp, tp, vp, vp, vp]
     lp = C.POINTER(MctsLookahead)

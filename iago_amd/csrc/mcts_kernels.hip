@@ -215,6 +215,44 @@ __global__ __launch_bounds__(BLOCK) void best_move_kernel(Tree T, const uint8_t 
     move[g] = (int8_t)best;
 }
 
+// best_move_kernel's sibling for the value target (iago_mcts_root_value), one thread per game: the root's (n_visits, Q) by
+// visit()'s one 8-byte load, Q turned to the root MOVER's view (under the negamax rule a node's Q is the value for the
+// player who moved into it: -q, exact) and to Q16 -- one float32 multiply by 2^16 (exact), rint (to nearest even),
+// saturated to +-2^30 (bit 0 of flags), NaN 0 (bit 1).  Inactive games 0 and 0.  A root index outside the pool reads
+// nothing and gives 0 and 0.
+constexpr float ROOT_Q16_MAX = 1073741824.0f; // 2^30
+__global__ __launch_bounds__(BLOCK) void root_value_kernel(Tree T, const uint8_t *__restrict__ active,
+                                                           int32_t *__restrict__ q16, int32_t *__restrict__ n,
+                                                           uint32_t *__restrict__ flags)
+{
+#pragma clang fp contract(off)
+    const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= T.n_games)
+        return;
+    int32_t visits = 0, value = 0;
+    uint32_t raised = 0u;
+    const int root = active[g] ? T.root[g] : -1;
+    if ((uint32_t)root < (uint32_t)T.capacity) {
+        const uint2 nq = *(const uint2 *)&T.nodes[g * (int64_t)T.capacity + root];
+        visits = (int32_t)nq.x;
+        const float q = __uint_as_float(nq.y);
+        if (q != q) {
+            raised = IAGO_ROOT_VALUE_NAN;
+        } else {
+            float r = __builtin_rintf(-q * 65536.0f);
+            if (r > ROOT_Q16_MAX || r < -ROOT_Q16_MAX) {
+                raised = IAGO_ROOT_VALUE_SATURATED;
+                r = r > 0.0f ? ROOT_Q16_MAX : -ROOT_Q16_MAX;
+            }
+            value = (int32_t)r;
+        }
+    }
+    q16[g] = value;
+    n[g] = visits;
+    if (raised && flags)
+        atomicOr(flags, raised);
+}
+
 // best_move_kernel's sibling for exploring self-play (iago_mcts_draw_move): the move of game g is drawn in proportion
 // to the visit counts of its root's children -- mcts_dev.hpp's rule, the children in ascending cell order -- with the
 // Philox word of (game_id[g], turn[g]); no child visited: the first maximum, as above; no children: -2
@@ -1211,6 +1249,20 @@ int iago_mcts_best_move(const iago_mcts_tree *tree, const uint8_t *active, int8_
     hipLaunchKernelGGL(best_move_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0,
                        (hipStream_t)stream, *tree, active, move, visits);
     return iago_check_launch("iago_mcts_best_move");
+}
+
+int iago_mcts_root_value(const iago_mcts_tree *tree, const uint8_t *active, int32_t *q16, int32_t *n, uint32_t *flags,
+                         void *stream)
+{
+    if (check_tree(tree, "iago_mcts_root_value: bad tree"))
+        return IAGO_ERR_INVALID;
+    if (!active || !q16 || !n)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_root_value: null pointer (active, q16 and n expected)");
+    if (tree->n_games <= 0)
+        return iago_fail(IAGO_ERR_INVALID, "iago_mcts_root_value: n_games must be positive");
+    hipLaunchKernelGGL(root_value_kernel, dim3(grid_for(tree->n_games)), dim3(BLOCK), 0, (hipStream_t)stream, *tree, active,
+                       q16, n, flags);
+    return iago_check_launch("iago_mcts_root_value");
 }
 
 int iago_mcts_draw_move(const iago_mcts_tree *tree, const uint8_t *active, uint64_t seed, const int32_t *game_id,

@@ -316,6 +316,74 @@ __global__ __launch_bounds__(BLOCK) void replay_sample_merged_kernel(const iago_
     }
 }
 
+// iago_replay_merge_values: one wave per group, the lanes striding over the group's sorted rows, each summing the
+// column's entries of its rows' slots in 64 bits; one 64-bit wave reduction; lane 0 stores.  Integer sums and plain
+// stores: the bits do not depend on the schedule.  The span is clamped into the sorted order; a row whose slot lies
+// outside [0, count) or whose group number is not g is left out (bit 0).
+__global__ __launch_bounds__(BLOCK) void merge_values_kernel(const iago_replay_merge_values_args P)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t count = P.count, stride = (int64_t)gridDim.x * ROWS;
+    for (int64_t g = (int64_t)blockIdx.x * ROWS + (threadIdx.x >> 6); g < P.n_unique; g += stride) {
+        int64_t start = P.first[g], len = P.mult[g];
+        bool bad = start < 0 || start >= count || len < 1 || len > count - start;
+        start = start < 0 ? 0 : start > count ? count : start;
+        len = len < 0 ? 0 : len > count - start ? count - start : len;
+        int64_t acc = 0;
+        for (int64_t i = start + lane; i < start + len; i += 64) {
+            const int slot = P.order[i];
+            if ((uint32_t)slot < (uint32_t)count && (int64_t)P.group[i] == g) // (count < 2^31)
+                acc += P.v[slot];
+            else
+                bad = true;
+        }
+        acc = wave_sum(acc);
+        if (bad && P.flags)
+            atomicOr(P.flags, (uint32_t)IAGO_REPLAY_MERGE_BAD_INPUT);
+        if (lane == 0)
+            P.v_sum[g] = acc;
+    }
+}
+
+// iago_value_targets: one lane per game, walking its T turns backward; row t of every [t][b] record is contiguous over
+// the games, so a wave's loads are.  The chain (Gnext, Vnext) lives in two 64-bit registers per lane: no LDS, no scratch.
+// mover[t] is the same for every lane.  The rule: include/iago_hip_training.h.
+__device__ __forceinline__ void value_targets_game(const iago_value_targets_args &P, int64_t b, int64_t lam, int64_t mix,
+                                                   int64_t one)
+{
+    int64_t g_next = one * (int64_t)P.z[b], v_next = g_next;
+    for (int64_t t = P.n_turns - 1; t >= 0; t--) {
+        const int64_t at = t * P.n_games + b;
+        const int kind = P.valid[at];
+        const int64_t s = P.mover[t] == 1 ? 1 : -1;
+        int32_t out = 0;
+        if (kind == 1 || kind == 4 || kind == 3) {
+            int64_t v;
+            if (kind == 3) {
+                const int sc = P.score[at];
+                v = one * (int64_t)((sc > 0) - (sc < 0));
+            } else {
+                const int64_t q = P.q[at];
+                v = q > one ? one : q < -one ? -one : q;
+            }
+            v *= s;
+            const int64_t g = ((256 - lam) * v_next + lam * g_next + 128) >> 8; // (arithmetic: floors)
+            const int64_t r = ((256 - mix) * g + mix * v + 128) >> 8;
+            out = (int32_t)(s * r);
+            g_next = g;
+            v_next = v;
+        }
+        P.out[at] = out;
+    }
+}
+__global__ __launch_bounds__(BLOCK) void value_targets_kernel(const iago_value_targets_args P)
+{
+    const int64_t lam = P.lam_256, mix = P.mix_256, one = 65536;
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t b = (int64_t)blockIdx.x * BLOCK + threadIdx.x; b < P.n_games; b += stride)
+        value_targets_game(P, b, lam, mix, one);
+}
+
 unsigned grid_for(int64_t items, int per_block)
 {
     const int64_t blocks = (items + per_block - 1) / per_block;
@@ -393,6 +461,34 @@ int iago_replay_sample_merged(const iago_replay_sample_merged_args *args, void *
         return iago_fail(IAGO_ERR_INVALID, "iago_replay_sample_merged: mode must be 0 (unique) or 1 (rows)");
     hipLaunchKernelGGL(replay_sample_merged_kernel, dim3(grid_for(A.n, ROWS)), dim3(BLOCK), 0, (hipStream_t)stream, A);
     return iago_check_launch("iago_replay_sample_merged");
+}
+
+int iago_replay_merge_values(const iago_replay_merge_values_args *args, void *stream)
+{
+    if (!args)
+        return iago_fail(IAGO_ERR_INVALID, "iago_replay_merge_values: null args");
+    const iago_replay_merge_values_args &A = *args;
+    if (!A.order || !A.group || !A.first || !A.mult || !A.v || !A.v_sum)
+        return iago_fail(IAGO_ERR_INVALID, "iago_replay_merge_values: null pointer");
+    if (A.count <= 0 || A.count >= ((int64_t)1 << 31) || A.n_unique <= 0 || A.n_unique > A.count)
+        return iago_fail(IAGO_ERR_INVALID, "iago_replay_merge_values: need 1 <= n_unique <= count < 2^31");
+    hipLaunchKernelGGL(merge_values_kernel, dim3(grid_for(A.n_unique, ROWS)), dim3(BLOCK), 0, (hipStream_t)stream, A);
+    return iago_check_launch("iago_replay_merge_values");
+}
+
+int iago_value_targets(const iago_value_targets_args *args, void *stream)
+{
+    if (!args)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_targets: null args");
+    const iago_value_targets_args &A = *args;
+    if (!A.valid || !A.q || !A.score || !A.z || !A.mover || !A.out)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_targets: null pointer");
+    if (A.n_turns <= 0 || A.n_games <= 0 || A.n_turns > ((int64_t)1 << 31) / A.n_games)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_targets: need n_turns >= 1, n_games >= 1, n_turns * n_games <= 2^31");
+    if (A.lam_256 < 0 || A.lam_256 > 256 || A.mix_256 < 0 || A.mix_256 > 256)
+        return iago_fail(IAGO_ERR_INVALID, "iago_value_targets: lam_256 and mix_256 must be in [0, 256]");
+    hipLaunchKernelGGL(value_targets_kernel, dim3(grid_for(A.n_games, BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, A);
+    return iago_check_launch("iago_value_targets");
 }
 
 } // extern "C"

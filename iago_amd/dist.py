@@ -50,7 +50,8 @@ def all_gather_into(recv, send, group=None):
 def gather_tuples(fields, group=None):
     """All-gather per-rank tuple arrays (dict name -> tensor, same length along
     dim 0 on a rank, lengths may differ between ranks).  Returns a dict of
-    tensors holding rank 0's rows first, then rank 1's, ...
+    tensors holding rank 0's rows first, then rank 1's, ...  Every field travels, whatever
+    its name: a round's value targets (the int32 column `v`) go with its other columns.
 
     Two collectives regardless of the number of fields: one all-gather of the
     row counts, one all-gather of a byte buffer padded to the longest shard

@@ -43,9 +43,10 @@ _stream = ops._stream   # the current HIP stream as a void*
 # (n_fast, full_per_256)), root_noise (None: off, else (alpha_256, eps_256, draws)), forced_playouts (None: off, else k_256,
 # with root_noise), solved_targets (False: off; True, with solve_empties: the solved turns record the set of their
 # optimal moves), gumbel (None: off, else (m, c_scale_256, c_visit): the Gumbel root search, without root_noise,
-# forced_playouts or explore_turns) -- as SelfPlayEngine.play documents them.
+# forced_playouts or explore_turns), root_values (False: off; True: every searched turn records its root's value and
+# visits, the turn loop) -- as SelfPlayEngine.play documents them.
 PlayRules = collections.namedtuple("PlayRules", "solve_empties explore_turns playout_cap root_noise forced_playouts "
-                                   "solved_targets gumbel", defaults=(None, None, False, None))
+                                   "solved_targets gumbel root_values", defaults=(None, None, False, None, False))
 NO_RULES = PlayRules(None, 0, None)
 
 
@@ -228,6 +229,10 @@ def selection_arg(x):
     if isinstance(x, str) and x in SELECTION_RULES:
         return x
     raise ValueError("selection: \"reference\" or \"alphazero\" expected, not %r" % (x,))
+
+
+_ROOT_VALUE_NEEDS = ("root values need backup=\"negamax\" (under the reference's rule a root's Q mixes both players' views and "
+                     "is no value)")
 
 
 _ALPHAZERO_NEEDS = ("selection=\"alphazero\" is offered for the persistent search only (the per-playout launches -- "
@@ -1534,6 +1539,8 @@ class BatchedMCTS(object):
             raise ValueError(_ALPHAZERO_NEEDS)
         if RootRule.of(rules) is not None:   # (likewise the root rule of a round of games)
             RootRule.of(rules).require(self)
+        if rules.root_values and getattr(self, "backup", "reference") != "negamax":
+            raise ValueError(_ROOT_VALUE_NEEDS)
 
     def search_counts(self, active):
         """Device tensor int64[2]: games in `active`, nodes of the fullest pool -- what search()
@@ -1714,6 +1721,25 @@ class BatchedMCTS(object):
                                              _stream()), "iago_mcts_best_move")
         return self.move, self.visits
 
+    def root_value(self, active=None):
+        """(q16, n) of the roots as they stand after a search (ops.mcts_root_value): per game in `active` (None: every
+        game) the root's value for the root's MOVER in Q16 -- rint(-root.q * 65536), saturated to +-2^30 -- and the root's
+        visits, both (n_games,) int32; 0 and 0 for the other games.  For engines with backup="negamax" only (ValueError):
+        there a node's Q is the value for the player who moved into it, so -root.q is the mover's; under the reference's
+        rule the root's Q mixes both players' views and is no value.  The engine's own buffers: the next call overwrites
+        them.  Nothing is read back; a NaN or saturated value raises a bit of the engine's root_value_flags word."""
+        if getattr(self, "backup", "reference") != "negamax":
+            raise ValueError(_ROOT_VALUE_NEEDS)
+        st = getattr(self, "_root_value", None)
+        if st is None:
+            dev = self.move.device
+            st = self._root_value = (torch.zeros(self.n_games, dtype=torch.int32, device=dev),
+                                     torch.zeros(self.n_games, dtype=torch.int32, device=dev),
+                                     torch.ones(self.n_games, dtype=torch.uint8, device=dev))
+            self.root_value_flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        return ops.mcts_root_value(self.tree.ref(), st[2] if active is None else active, st[0], st[1],
+                                   self.root_value_flags)
+
     def gumbel_move(self, active=None, gumbel=None):
         """The move of the last search(gumbel=) on the trees as they stand (ops.gumbel_finish): of the root's most
         visited children the first maximum of g + logit + sigma(q); one child or none: best_move's answer.  Also fills the
@@ -1797,30 +1823,48 @@ class SelfPlayResult(object):
     # solved_targets: (T, B) int64 the set of the optimal moves of every solved row (bit a: move a reaches `score`), 0 on
     # every other row; None without solved targets
     best = None
+    # root_values: (T, B) int32 the root's value from the MOVER's view in Q16 on the searched rows (valid 1 or 4), 0 on
+    # every other row, and (T, B) int32 the root's visits there; None without root values
+    q = None
+    q_visits = None
 
-    def tuples(self):
-        """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view."""
-        return self._rows(1, True)
+    def value_targets(self, lam_256=256, mix_256=0):
+        """The Value net's targets of the games, (T, B) int32 in Q16 from the mover's view (ops.value_targets,
+        iago_value_targets): the result z mixed with the recorded root values -- TD(lambda) returns along the game,
+        lambda = lam_256 / 256, and mix_256 / 256 of the row's own value; a solved row's value is the sign of its exact
+        score.  (256, 0) is 65536 z from the mover's view, (256, 128) the z-q average, (0, 0) one-step bootstrapping.
+        0 where there is no searched or solved row.  Needs play(root_values=True): ValueError without the record."""
+        if self.q is None:
+            raise ValueError("value_targets: the games recorded no root values (play(root_values=True) records them)")
+        return ops.value_targets(self.valid, self.q, getattr(self, self.SCORE_RECORD, None), self.z, self.mover,
+                                 lam_256, mix_256)
 
-    def fast_tuples(self):
+    def tuples(self, value_target=None):
+        """Flat (s, pi, z) rows of all searched moves (valid == 1); z from the mover's view.  With root values recorded
+        (play(root_values=True)) also q, the root's value from the mover's view in Q16.  value_target = (lam_256,
+        mix_256): also v, the rows' value_targets(lam_256, mix_256) (int32, Q16)."""
+        return self._rows(1, True, value_target)
+
+    def fast_tuples(self, value_target=None):
         """tuples() of the FAST turns of the playout cap (valid == 4): searched with n_fast playouts, so not policy
-        targets -- the game's result still labels them."""
-        return self._rows(_lib.REC_FAST, True)
+        targets -- the game's result still labels them (and so do their roots' values: q and v as in tuples())."""
+        return self._rows(_lib.REC_FAST, True, value_target)
 
-    def solved_tuples(self):
+    def solved_tuples(self, value_target=None):
         """Flat rows of the moves the endgame solver played (valid == 3): own, opp, move, score (the exact final disc
         difference from the mover's view), z (from the mover's view), colour, game, turn.  Where the games recorded
         solved targets (play(solved_targets=True)) also best, the set of the row's optimal moves (int64, bit a: move a
         reaches the score; `move` is its lowest bit), and pi (rows, 64) int32 with 1 on every optimal move: the rows then
-        have every column ReplayWindow.add and ReinforceTrainer.step_from_tuples(..., target="visits") take."""
-        rows = self._rows(3, False)
+        have every column ReplayWindow.add and ReinforceTrainer.step_from_tuples(..., target="visits") take.
+        value_target = (lam_256, mix_256): also v, the rows' value_targets(lam_256, mix_256)."""
+        rows = self._rows(3, False, value_target)
         if self.best is not None:
             rows["best"] = self.best.reshape(-1)[self.valid.reshape(-1) == 3]
             cells = torch.arange(64, device=rows["best"].device)
             rows["pi"] = ((rows["best"].reshape(-1, 1) >> cells) & 1).to(torch.int32)
         return rows
 
-    def _rows(self, kind, searched):
+    def _rows(self, kind, searched, value_target=None):
         m = self.valid.reshape(-1) == kind
         T, B = self.valid.shape
         sign = torch.tensor([1 if c == 1 else -1 for c in self.mover], dtype=torch.int8,
@@ -1837,8 +1881,12 @@ class SelfPlayResult(object):
                     turn=turn.expand(T, B).reshape(-1)[m])
         if searched:
             rows["pi"] = self.pi.reshape(-1, 64)[m]
+            if self.q is not None:
+                rows["q"] = self.q.reshape(-1)[m]
         else:
             rows["score"] = getattr(self, self.SCORE_RECORD).reshape(-1)[m]
+        if value_target is not None:
+            rows["v"] = self.value_targets(*value_target).reshape(-1)[m]
         return rows
 
 
@@ -1908,11 +1956,12 @@ def _solve_empties_arg(k):
 
 
 def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None, root_noise=None, forced_playouts=None,
-                solved_targets=False, gumbel=None):
+                solved_targets=False, gumbel=None, root_values=False):
     """The PlayRules of play / play_stream / play_match / ArenaEngine.play from their caller's arguments, each refused
     where its own validator refuses it (forced_playouts: an int in [1, 4096], and only with root_noise).  Off is (None, 0,
     None, None, None): explore_turns is an int in the record.  solved_targets: a bool, True only with solve_empties.
-    gumbel: (m, c_scale_256[, c_visit]), refused together with explore_turns, root_noise or forced_playouts."""
+    gumbel: (m, c_scale_256[, c_visit]), refused together with explore_turns, root_noise or forced_playouts.
+    root_values: a bool."""
     noise = ops.root_noise_arg(root_noise)
     # (the Gumbel checks now; forced_playouts, where no gumbel excludes it, after the others below)
     root = root_rule(n_sims, noise, forced_playouts if gumbel is not None else None, gumbel, explore_turns, "explore_turns, ")
@@ -1920,9 +1969,11 @@ def _play_rules(n_sims, solve_empties=None, explore_turns=None, playout_cap=None
         raise ValueError("solved_targets must be a bool, not %r" % (solved_targets,))
     if solved_targets and solve_empties is None:
         raise ValueError("solved_targets records the solver's optimal moves: it needs solve_empties")
+    if not isinstance(root_values, bool):
+        raise ValueError("root_values must be a bool, not %r" % (root_values,))
     return PlayRules(_solve_empties_arg(solve_empties), ops.explore_turns_arg(explore_turns) or 0,
                      ops.playout_cap_arg(playout_cap, n_sims), noise, ops.forced_playouts_arg(forced_playouts, noise),
-                     solved_targets, root and root.gumbel)
+                     solved_targets, root and root.gumbel, root_values)
 
 
 def _no_forced_playouts(forced_playouts, who):
@@ -2160,8 +2211,9 @@ class SelfPlayEngine(object):
         fallback, whose searches (one launch per turn) compact a pool that is half full.  Same games either way."""
         m = self.mcts
         m.tree.reset()
-        # (a root rule draws per turn by a launch of its own, ops.root_noise or ops.gumbel_draw -- the turn loop)
-        if not (applies and RootRule.of(rules) is None and self._whole_games_in_one_launch(n_sims)):
+        # (a root rule draws per turn by a launch of its own, ops.root_noise or ops.gumbel_draw -- the turn loop; so do
+        # root values, read per turn by ops.mcts_root_value: the whole-game launch does not record them)
+        if not (applies and RootRule.of(rules) is None and not rules.root_values and self._whole_games_in_one_launch(n_sims)):
             return None
         res = self._play_persistent(n_sims, *self._start_boards(n, handicap), record, rules, **kw)
         if res is None:
@@ -2228,6 +2280,10 @@ class SelfPlayEngine(object):
             rec["pi_raw"] = torch.zeros_like(rec["pi"])
         if record and rules.solved_targets:
             rec["best"] = torch.zeros((T, B), dtype=torch.int64, device=dev)
+        values = record and rules.root_values   # (the roots' values and visits of the searched rows: q, q_visits)
+        if values:
+            rec["q"] = torch.zeros((T, B), dtype=torch.int32, device=dev)
+            rec["q_visits"] = torch.zeros((T, B), dtype=torch.int32, device=dev)
         legal = ops.legal_moves(own, opp)
         active = (legal != 0).to(torch.uint8)
         legal_next, active_next = torch.empty_like(legal), torch.empty_like(active)
@@ -2292,6 +2348,10 @@ class SelfPlayEngine(object):
                 s.move, s.visits = s.mcts.draw_move(t, s.act) if t < rules.explore_turns else s.mcts.best_move(s.act)
                 if root is not None:   # (the rule's own move, written over best_move's in s.move: the engine's move buffer)
                     s.made = root.move(s.mcts, s.ruled, record)
+                if values:   # (the engine's own buffers, 0 outside s.act: into the record at once; a game has one mover)
+                    q, n = s.mcts.root_value(s.act)
+                    rec["q"][t] += q
+                    rec["q_visits"][t] += n
             if sol is not None:
                 # (a game that is not solved here sends a full board: no search, no refusal)
                 if rules.solved_targets:   # (the same score and move, and the set of the optimal moves)
@@ -2370,7 +2430,8 @@ class SelfPlayEngine(object):
             checks = dict(no_children=(mv == -2).any(), all_done=done.all(),
                           bad_draw=(drawn & (draw == 64)).any() if policy_moves and opening is None else None,
                           unsolved=(ex["solved"] == 0).any() if sol is not None else None,
-                          unfinished=(ab["done"] == 0).any() if ab is not None else None, split_overflow=ab_over)
+                          unfinished=(ab["done"] == 0).any() if ab is not None else None, split_overflow=ab_over,
+                          bad_value=sum(s.mcts.root_value_flags[0] & _lib.ROOT_VALUE_NAN for s in sides) if values else None)
             drawn, forced, sol, opening, counts = movers(t)
             back = _read_back({**{("flags", i): s.mcts.error_flags(s.gave_up) for i, s in enumerate(sides)},
                                **checks, **counts})
@@ -2384,6 +2445,10 @@ class SelfPlayEngine(object):
             if back.get("unsolved"):
                 raise _lib.IagoError("solve_empties = %d: the endgame solver refused or did not finish a position at "
                                      "turn %d" % (k, t - 1))
+            if back.get("bad_value"):
+                for s in sides:
+                    s.mcts.root_value_flags.zero_()
+                raise _lib.IagoError("root_values: a searched root's value is NaN at turn %d" % (t - 1))
             if back.get("unfinished"):
                 raise _lib.IagoError("play_match: the alpha-beta opponent (depth %d) did not finish a position at turn %d"
                                      % (opponent.depth, t - 1))
@@ -2404,7 +2469,7 @@ class SelfPlayEngine(object):
         return res
 
     def play(self, n_sims, handicap=None, record=True, solve_empties=None, explore_turns=None, playout_cap=None,
-             root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None):
+             root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None, root_values=False):
         """B self-play games; handicap: (B,) int64 bit masks of extra colour-2 stones.  Returns a SelfPlayResult.
         solve_empties = k (an int in [0, 20]; None, the default: off): a turn that would be searched at a position of
         at most k empties (64 - popcount(own | opp)) runs no search -- the move is the exact endgame solver's
@@ -2465,10 +2530,18 @@ class SelfPlayEngine(object):
         records the improved policy round(65536 softmax(logit + sigma(completed q))) (gumbel_targets) and `pi_raw` the
         visit row; `move` is the survivor.  Such games ALWAYS run through the turn loop.  solve_empties and playout_cap
         compose (under a cap only the FULL turns run the rule: a fast turn is the plain search's, pi = pi_raw);
-        explore_turns, root_noise and forced_playouts are refused beside it -- the rule explores by its own draw."""
+        explore_turns, root_noise and forced_playouts are refused beside it -- the rule explores by its own draw.
+        root_values = True (False, the default: off; for engines with backup="negamax", else ValueError): every searched
+        turn also records its root's value from the MOVER's view in Q16 in `q` ((T, B) int32: rint(-root.q * 65536) read
+        after the search and before the tree moves on, BatchedMCTS.root_value; 0 on every row whose valid is not 1 or 4)
+        and the root's visits in `q_visits` -- what SelfPlayResult.value_targets and tuples(value_target=) turn into the
+        Value net's targets.  Such games ALWAYS run through the turn loop (the whole-game launch does not record root
+        values), with one more small launch per side and turn and still ONE readback per turn; the record changes no game:
+        every other record and every move are those of root_values=False.  Every other rule composes.  Without it the
+        result's q and q_visits are None."""
         return self._play(n_sims, handicap, record,
                           _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts,
-                                      solved_targets, gumbel))
+                                      solved_targets, gumbel, root_values))
 
     def _play(self, n_sims, handicap, record, rules):
         """play() under validated rules (a PlayRules)."""
@@ -2480,7 +2553,8 @@ class SelfPlayEngine(object):
         return res
 
     def play_stream(self, n_sims, n_games, handicap=None, record=True, solve_empties=None, explore_turns=None,
-                    playout_cap=None, root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None):
+                    playout_cap=None, root_noise=None, forced_playouts=None, solved_targets=False, gumbel=None,
+                    root_values=False):
         """n_games self-play games, at most B (the engine's slots) of them in play at a time, as ONE persistent launch
         where play() applies: a slot whose game ends takes the next game id on the device and plays that game from its
         first turn (iago_mcts_search_args.games_total), so the launch ends once, with the last game, instead of every B
@@ -2494,9 +2568,10 @@ class SelfPlayEngine(object):
         as in play() -- game G draws with its own id, whichever slot plays it.  playout_cap: as in play() -- game G's
         turns are full or fast by its own id.  root_noise: as in play() -- game G's urns are keyed by its own id.
         forced_playouts: as in play(), with the record pi_raw.  solved_targets: as in play(), with the record best.
-        gumbel: as in play() -- the batch loop, game G's draws keyed by its own id, with the record pi_raw."""
+        gumbel: as in play() -- the batch loop, game G's draws keyed by its own id, with the record pi_raw.
+        root_values: as in play() -- the batch loop, with the records q and q_visits."""
         rules = _play_rules(n_sims, solve_empties, explore_turns, playout_cap, root_noise, forced_playouts, solved_targets,
-                            gumbel)
+                            gumbel, root_values)
         m, T = self.mcts, self.max_turns
         m._backup_check(rules)
         n_games = int(n_games)
@@ -2606,6 +2681,8 @@ class SelfPlayEngine(object):
                 cols["pi_raw"] = []
             if rules.solved_targets:
                 cols["best"] = []
+            if rules.root_values:
+                cols["q"], cols["q_visits"] = [], []
             for r, w in parts:
                 dev, rows = r.z.device, min(r.n_turns, t)
                 pad = t - rows
@@ -2622,6 +2699,8 @@ class SelfPlayEngine(object):
                     cols["pi_raw"].append(torch.cat([r.pi_raw[:rows, :w], r.pi_raw.new_zeros((pad, w, 64))]))
                 if "best" in cols:
                     cols["best"].append(torch.cat([r.best[:rows, :w], r.best.new_zeros((pad, w))]))
+                for name in ("q", "q_visits") if "q" in cols else ():
+                    cols[name].append(torch.cat([getattr(r, name)[:rows, :w], r.q.new_zeros((pad, w))]))
                 cols["score"].append(torch.cat([r.score[:rows, :w], r.score.new_zeros((pad, w))]))
             for k, v in cols.items():
                 setattr(res, k, torch.cat(v, dim=1))

@@ -214,7 +214,9 @@ def replay_merge(own, opp, pi, z, count, meta=None):
     by (c_own, c_opp) as unsigned -- two stable sorts, torch's -- and summed per distinct position on the device.
     meta: optional int32 (2,) tensor, cleared here: [0] receives n_unique, [1] the flags (_lib.REPLAY_MERGE_*).
     Returns a dict own, opp (count,), pi (count, 64) int32, z_sum, mult int32, first int64 -- count-sized buffers
-    whose first n_unique entries are the groups, in ascending (own, opp) -- and meta.  Nothing is read back."""
+    whose first n_unique entries are the groups, in ascending (own, opp) -- meta, and the order / group (count,) int32
+    the merge took (the slots in ascending canonical position and their group numbers: what replay_merge_values sums
+    another column by).  Nothing is read back."""
     capacity, count = own.numel(), int(count)
     for name, t in (("opp", opp), ("z", z)):
         if t.numel() != capacity:
@@ -238,7 +240,7 @@ def replay_merge(own, opp, pi, z, count, meta=None):
     out = dict(own=torch.empty(count, dtype=torch.int64, device=dev), opp=torch.empty(count, dtype=torch.int64, device=dev),
                pi=torch.empty((count, 64), dtype=torch.int32, device=dev),
                z_sum=torch.empty(count, dtype=torch.int32, device=dev), mult=torch.empty(count, dtype=torch.int32, device=dev),
-               first=torch.empty(count, dtype=torch.int64, device=dev), meta=meta)
+               first=torch.empty(count, dtype=torch.int64, device=dev), meta=meta, order=order, group=group)
     a = _lib.ReplayMergeArgs()
     a.c_own, a.c_opp, a.sym = c_own.data_ptr(), c_opp.data_ptr(), sym.data_ptr()
     a.pi, a.z, a.count = _dev(pi, torch.int32, "pi"), _dev(z, torch.int8, "z"), count
@@ -284,6 +286,82 @@ def replay_sample_merged(own, opp, pi, z_sum, mult, first, count, n, seed=0, ste
     a.group_out, a.sym_out = out["group"].data_ptr(), out["sym"].data_ptr()
     check(_lib.lib().iago_replay_sample_merged(C.byref(a), _stream()), "iago_replay_sample_merged")
     return out
+
+
+def replay_merge_values(order, group, first, mult, v, flags=None):
+    """iago_replay_merge_values (include/iago_hip_training.h): the int32 column v (by slot; at least count entries) summed
+    per group of a merge -- order / group (count,) int32 and first int64 / mult int32 (n_unique,) as replay_merge
+    returns them (first / mult cut to the groups).  Returns v_sum (n_unique,) int64: 64-bit integer sums, the same bits
+    whatever the schedule.  flags: optional int32 word, or-ed into -- bit 0 (_lib.REPLAY_MERGE_BAD_INPUT): a span, slot or
+    group number the device refused."""
+    count, groups = order.numel(), first.numel()
+    if group.numel() != count or mult.numel() != groups:
+        raise ValueError("replay_merge_values: order / group have %d / %d entries, first / mult %d / %d"
+                         % (count, group.numel(), groups, mult.numel()))
+    if v.dim() != 1 or v.numel() < count:
+        raise ValueError("replay_merge_values: v must be a column of at least %d entries, got %s" % (count, tuple(v.shape)))
+    v_sum = torch.empty(groups, dtype=torch.int64, device=order.device)
+    a = _lib.ReplayMergeValuesArgs()
+    a.order, a.group = _dev(order, torch.int32, "order"), _dev(group, torch.int32, "group")
+    a.first, a.mult, a.v = _dev(first, torch.int64, "first"), _dev(mult, torch.int32, "mult"), _dev(v, torch.int32, "v")
+    a.count, a.n_unique, a.v_sum = count, groups, v_sum.data_ptr()
+    a.flags = _dev(flags, torch.int32, "flags") if flags is not None else None
+    check(_lib.lib().iago_replay_merge_values(C.byref(a), _stream()), "iago_replay_merge_values")
+    return v_sum
+
+
+def value_rate_arg(x, name):
+    """lam_256 / mix_256 of the value targets: an int in [0, 256] (256ths), or ValueError."""
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not 0 <= x <= 256:
+        raise ValueError("%s must be an int in [0, 256] (256ths), not %r" % (name, x))
+    return int(x)
+
+
+def value_targets(valid, q, score, z, mover, lam_256=256, mix_256=0):
+    """iago_value_targets (include/iago_hip_training.h): the Value net's targets of recorded games, (T, B) int32 in Q16
+    from the MOVER's view, 0 where there is no row.  valid (T, B) uint8, q (T, B) int32 (the roots' values from the
+    mover's view, Q16: SelfPlayResult.q), score (T, B) int8 (None: no solved rows' scores, zeros), z (B,) int8 (colour
+    1's view), mover (T,) int8 tensor or a sequence of colours 1 / 2.  lam_256 / mix_256 in [0, 256]: TD(lambda)'s lambda
+    and the weight of the row's own value, in 256ths -- (256, 0) is 65536 z from the mover's view."""
+    lam_256, mix_256 = value_rate_arg(lam_256, "lam_256"), value_rate_arg(mix_256, "mix_256")
+    if valid.dim() != 2:
+        raise ValueError("value_targets: valid must be (T, B), got %s" % (tuple(valid.shape),))
+    T, B = valid.shape
+    dev = valid.device
+    if score is None:
+        score = torch.zeros((T, B), dtype=torch.int8, device=dev)
+    if not isinstance(mover, torch.Tensor):
+        mover = torch.tensor(list(mover), dtype=torch.int8, device=dev)
+    for name, t, shape in (("q", q, (T, B)), ("score", score, (T, B)), ("z", z, (B,)), ("mover", mover, (T,))):
+        if tuple(t.shape) != shape:
+            raise ValueError("value_targets: %s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    out = torch.empty((T, B), dtype=torch.int32, device=dev)
+    a = _lib.ValueTargetsArgs()
+    a.valid, a.q, a.score = _dev(valid, torch.uint8, "valid"), _dev(q, torch.int32, "q"), _dev(score, torch.int8, "score")
+    a.z, a.mover = _dev(z, torch.int8, "z"), _dev(mover, torch.int8, "mover")
+    a.n_turns, a.n_games, a.lam_256, a.mix_256, a.out = T, B, lam_256, mix_256, out.data_ptr()
+    check(_lib.lib().iago_value_targets(C.byref(a), _stream()), "iago_value_targets")
+    return out
+
+
+def mcts_root_value(tree, active, q16=None, n=None, flags=None):
+    """iago_mcts_root_value (include/iago_hip_serving.h): after a search under the negamax backup, per game with
+    active[g] != 0 the root's value for the root's mover in Q16 -- rint(-root.q * 65536), saturated to +-2^30 -- and the
+    root's visits; 0 and 0 for the others.  tree: a pointer to the iago_mcts_tree (TreePool.ref()); active (n_games,)
+    uint8.  q16 / n: (n_games,) int32 buffers to fill (None: fresh ones).  flags: optional int32 word, or-ed into (_lib.ROOT_VALUE_SATURATED, _NAN).
+    Returns (q16, n)."""
+    games, dev = active.numel(), active.device
+    if games != tree._obj.n_games:   # (the kernel walks the tree's games)
+        raise ValueError("mcts_root_value: active has %d entries for %d games" % (games, tree._obj.n_games))
+    q16 = torch.empty(games, dtype=torch.int32, device=dev) if q16 is None else q16
+    n = torch.empty(games, dtype=torch.int32, device=dev) if n is None else n
+    if q16.numel() != games or n.numel() != games:
+        raise ValueError("mcts_root_value: q16 / n have %d / %d entries for %d games" % (q16.numel(), n.numel(), games))
+    check(_lib.lib().iago_mcts_root_value(tree, _dev(active, torch.uint8, "active"), _dev(q16, torch.int32, "q16"),
+                                          _dev(n, torch.int32, "n"),
+                                          _dev(flags, torch.int32, "flags") if flags is not None else None, _stream()),
+          "iago_mcts_root_value")
+    return q16, n
 
 
 def augment8_visits(own, opp, action, pi):

@@ -347,7 +347,8 @@ class ReinforceTrainer(object):
     def _gather_rows(self, tup, colour, with_pi, who):
         """The front half of an update from a round's tuples: the colour filter, the check that the ranks' game ids do
         not overlap, the all-gather and the canonical (turn, game) order.  Returns the gathered columns own, opp,
-        action, z (and pi with with_pi): the same rows in the same order on every rank."""
+        action, z (and pi with with_pi; and v, the rows' value targets, where the tuples carry them --
+        SelfPlayResult.tuples(value_target=...)): the same rows in the same order on every rank."""
         keep = slice(None)
         if colour is not None:
             keep = tup["colour"] == colour
@@ -368,6 +369,8 @@ class ReinforceTrainer(object):
                       key=key[keep])
         if with_pi:
             fields["pi"] = tup["pi"][keep]
+        if "v" in tup:
+            fields["v"] = tup["v"][keep]
         g = _canonical(idist.gather_tuples(fields))
         if g["z"].numel() == 0:
             raise ValueError("%s: no tuples" % who)
@@ -417,9 +420,13 @@ class ReinforceTrainer(object):
     def add_to_window(self, window, tup, colour=None):
         """The rows of a round's tuples into a replay.ReplayWindow: tup, colour, the all-gather and the canonical order
         as step_from_tuples(target="visits") takes them, the gathered rows appended -- every rank's window then holds
-        the same rows in the same slots.  Returns the number of rows added."""
+        the same rows in the same slots.  The rows' value targets v go with them where the tuples carry them (a window
+        with value targets refuses rows without).  Returns the number of rows added."""
         g = self._gather_rows(tup, colour, with_pi=True, who="add_to_window")
-        return window.add(dict(own=g["own"], opp=g["opp"], pi=g["pi"], move=g["action"], z=g["z"]))
+        rows = dict(own=g["own"], opp=g["opp"], pi=g["pi"], move=g["action"], z=g["z"])
+        if "v" in g:
+            rows["v"] = g["v"]
+        return window.add(rows)
 
     def step_from_window(self, window, n_rows, target="visits", step=None, merged=None):
         """One update from n_rows rows drawn out of the window (ReplayWindow.sample: with replacement, each row in a

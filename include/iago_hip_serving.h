@@ -524,6 +524,26 @@ IAGO_API int iago_mcts_prune_visits(const iago_mcts_tree *tree, const uint8_t *a
 IAGO_API int iago_mcts_prune_visits_rule(const iago_mcts_tree *tree, const uint8_t *active, float c_puct, int32_t k_256,
                                          int32_t flags, int32_t *pruned /* [n_games][64] */, void *stream);
 
+/*
+ * The root's value, read back after a search -- a sibling of iago_mcts_best_move for the Value net's targets
+ * (iago_value_targets, iago_hip_training.h).  For every game with active[g] != 0:
+ *   n[g]   = the root's n_visits,
+ *   q16[g] = the root's value for the root's MOVER in Q16.  Under IAGO_SEARCH_NEGAMAX a node's Q is the value for the
+ *            player who moved INTO it, so the mover's value is -root.q (exact), and
+ *              q16 = rint(-q * 65536):  one float32 multiply (by 2^16: exact), the conversion to nearest, ties to even,
+ *            saturated to +-2^30 (a result beyond them is stored as the nearer one and raises bit 0 of *flags); a NaN q
+ *            gives 0 and raises bit 1.  The Value net has no tanh, so |q| may exceed 1: nothing else is clipped here.
+ * Games with active[g] == 0 get 0 and 0 (so does a root index outside the pool, which is not read).  One thread per game;
+ * (n_visits, q) is the one 8-byte load Node.update takes.  The trees are only read.  Under the reference's backup rule a
+ * root's Q mixes both players' views and is no value: the entry point cannot tell, its callers must (BatchedMCTS.root_value
+ * refuses such an engine).  flags: optional, one word, or-ed into; the caller clears it.
+ * Refused (IAGO_ERR_INVALID, before any device is touched): a NULL or bad tree, NULL active, q16 or n, n_games <= 0.
+ */
+#define IAGO_ROOT_VALUE_SATURATED 1
+#define IAGO_ROOT_VALUE_NAN 2
+IAGO_API int iago_mcts_root_value(const iago_mcts_tree *tree, const uint8_t *active, int32_t *q16 /* [n_games] */,
+                                  int32_t *n /* [n_games] */, uint32_t *flags, void *stream);
+
 /* ------------------------------------------------------------------ Gumbel root search */
 
 #define IAGO_GUMBEL_KEY 0x47554D42u /* ("GUMB") the draw's Philox key: the rollout seed with its high word XOR this */

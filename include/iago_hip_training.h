@@ -223,6 +223,62 @@ typedef struct iago_replay_sample_merged_args {
 } iago_replay_sample_merged_args;
 IAGO_API int iago_replay_sample_merged(const iago_replay_sample_merged_args *args, void *stream);
 
+/*
+ * iago_value_targets: the Value net's targets of a round of recorded games from the search's own values -- the game's
+ *   result z mixed with the roots' values (iago_mcts_root_value, iago_hip_serving.h) and TD(lambda) returns along the
+ *   game, in 64-bit integers, Q16.  The records are SelfPlayResult's, [n_turns][n_games], turn-major:
+ *     valid (uint8)  1 / 4: the turn was searched (a full / a fast turn), 3: the endgame solver played it; 0, 2 and 5 (a
+ *                    pass or no turn, a move without a search, a random opening move) are NO rows,
+ *     q (int32)      the root's value from the MOVER's view in Q16 on the searched rows,
+ *     score (int8)   the exact final disc difference from the mover's view on the solved rows,
+ *     z (int8) [n_games] the game's result from colour 1's view,   mover (int8) [n_turns] the colour to move (1 or 2).
+ *   The rule, in colour 1's frame.  s_t = +1 where mover[t] == 1, else -1;  Z = 65536 z[b];
+ *     V_t = s_t clip(q[t][b], -65536, 65536) on a searched row,  V_t = s_t 65536 sign(score[t][b]) on a solved row.
+ *   Start with Gnext = Vnext = Z.  For t = n_turns - 1 .. 0, on a row:
+ *     G_t = ((256 - lam_256) Vnext + lam_256 Gnext + 128) >> 8     (an arithmetic shift: it floors),
+ *     R_t = ((256 - mix_256) G_t + mix_256 V_t + 128) >> 8,
+ *     out[t][b] = s_t R_t (int32: the target from the MOVER's view, |out| <= 65536),  then Gnext = G_t, Vnext = V_t.
+ *   Where there is no row out[t][b] = 0 and the chain stays as it is.  G is the TD(lambda) return of the position AFTER
+ *   which it stands, lambda = lam_256 / 256, without the row's own value; mix_256 / 256 of the row's own value joins it.
+ *   (256, 0): exactly 65536 z from the mover's view, the label of before.  (256, 128): the z-q average.  (0, 0): one-step
+ *   bootstrapping -- every row takes the next row's V, the last one Z.
+ *   One lane per game walking backward over the turns (a wave's loads of a record row are contiguous), no LDS, no
+ *   scratch memory, plain stores.
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or pointer, n_turns <= 0, n_games <= 0,
+ *   n_turns * n_games > 2^31, lam_256 or mix_256 outside [0, 256].
+ */
+typedef struct iago_value_targets_args {
+    const uint8_t *valid;
+    const int32_t *q;
+    const int8_t *score, *z, *mover;
+    int64_t n_turns, n_games;
+    int32_t lam_256, mix_256;
+    int32_t *out;
+} iago_value_targets_args;
+IAGO_API int iago_value_targets(const iago_value_targets_args *args, void *stream);
+
+/*
+ * iago_replay_merge_values: an int32 column of the window (v, by slot: the value targets) summed per group of a merge --
+ *   order / group [count] as iago_replay_merge took them, first (int64) / mult (int32) [n_unique] as it wrote them:
+ *     v_sum[g] (int64) = the sum of v[order[i]] over first[g] <= i < first[g] + mult[g].
+ *   A value is invariant under the board's symmetries: no variant enters.  One wave per group, the lanes striding over
+ *   the group's sorted rows, a 64-bit wave reduction, plain stores and no atomics on the sums: the bits do not depend on
+ *   the schedule.  The device checks what it indexes by: a span outside the sorted order is clamped into it, a row whose
+ *   slot lies outside [0, count) or whose group[i] is not g is left out; each raises IAGO_REPLAY_MERGE_BAD_INPUT in
+ *   *flags (optional, one word, or-ed into; the caller clears it).
+ *   Returns IAGO_ERR_INVALID, before touching a device, on a NULL struct or pointer (flags aside), count <= 0,
+ *   count >= 2^31, n_unique <= 0 or n_unique > count.
+ */
+typedef struct iago_replay_merge_values_args {
+    const int32_t *order, *group;
+    const int64_t *first;
+    const int32_t *mult, *v;
+    int64_t count, n_unique;
+    int64_t *v_sum;
+    uint32_t *flags;
+} iago_replay_merge_values_args;
+IAGO_API int iago_replay_merge_values(const iago_replay_merge_values_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

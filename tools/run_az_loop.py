@@ -34,10 +34,16 @@ Gumbel root search in self-play, SelfPlayEngine.play(gumbel=(m, 256)) -- fresh r
 moves, the survivor played, the window receives the improved-policy rows.  The self-play engine then expands at the first
 visit (n_thr = 1: at n_thr 15 a budget of 20 would leave the rule five playouts) and no opening moves are drawn from the
 visit counts (the rule explores by its own draw); 0, the default: off.
+td_lambda = l, q_mix = m, both in 256ths (with backup = 1: a root's Q is a value only under the negamax rule, anything else
+is refused): the Value net's labels are the search's own values instead of the game's result alone -- self-play records every
+searched root's value (SelfPlayEngine.play(root_values=True)), the rows enter a window with value targets
+(ReplayWindow(value_targets=True)) as tuples(value_target=(l, m)) -- TD(lambda) returns along the game with lambda = l / 256,
+mixed with m / 256 of the row's own root value (include/iago_hip_training.h, iago_value_targets) -- and step_rows takes the
+window's `result`, the target as a float.  256 / 0, the default: the result z, today's loop, which records nothing more.
     python3 tools/run_az_loop.py [iters=100] [games=64] [sims=20] [window_rounds=8] [updates_per_round=4] [rows=1024]
                                  [arena_every=0] [cap_fast=0] [cap_full=64] [noise_eps=0] [noise_alpha=77]
                                  [forced_k=0] [backup=0] [yardstick_every=0] [yardstick_depth=2] [selection=0]
-                                 [solve_empties=0] [solved_targets=0] [merge=0] [gumbel=0]"""
+                                 [solve_empties=0] [solved_targets=0] [merge=0] [gumbel=0] [td_lambda=256] [q_mix=0]"""
 import copy, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,6 +67,11 @@ solve_empties = arg(17, 0) if arg(17, 0) > 0 else None
 solved_targets = bool(arg(18, 0))
 merge = (None, "unique", "rows")[arg(19, 0)]
 gumbel = (arg(20, 0), 256) if arg(20, 0) > 0 else None
+td_lambda, q_mix = ops.value_rate_arg(arg(21, 256), "td_lambda"), ops.value_rate_arg(arg(22, 0), "q_mix")
+value_target = (td_lambda, q_mix) if (td_lambda, q_mix) != (256, 0) else None
+if value_target is not None and backup != "negamax":
+    raise ValueError("td_lambda / q_mix need backup = 1 (under the reference's backup rule a root's Q mixes both players' "
+                     "views and is no value)")
 sp_n_thr = 1 if gumbel is not None else 15
 w, b = bench.shipped_rollout_weights()
 torch.manual_seed(0)
@@ -70,7 +81,8 @@ m = engine.BatchedMCTS(games, tr.model1, vt.model, ops.RolloutWeights(w, b), n_t
                        capacity=engine.suggest_capacity(sims, sp_n_thr), seed=1, backup=backup,
                        selection=selection)   # default engine: the persistent search
 sp = engine.SelfPlayEngine(m)
-window = ReplayWindow(window_rounds * games * 60, seed=2)   # (a game has at most 60 searched turns)
+window = ReplayWindow(window_rounds * games * 60, seed=2,   # (a game has at most 60 searched turns)
+                      value_targets=value_target is not None)
 kls, vlosses = [], []
 solved_rows = [0]
 arena_scores = []
@@ -120,11 +132,13 @@ def one():
     extra = {} if solve_empties is None else dict(solve_empties=solve_empties, solved_targets=solved_targets)
     if gumbel is not None:
         extra["gumbel"] = gumbel
+    if value_target is not None:
+        extra["root_values"] = True
     res = sp.play(sims, explore_turns=None if gumbel is not None else 8, playout_cap=playout_cap, root_noise=root_noise,
                   forced_playouts=forced_playouts, **extra)
-    added = tr.add_to_window(window, res.tuples())
+    added = tr.add_to_window(window, res.tuples(value_target=value_target))
     if solved_targets:
-        n = tr.add_to_window(window, res.solved_tuples())
+        n = tr.add_to_window(window, res.solved_tuples(value_target=value_target))
         solved_rows[0] += n
         added += n
     for _ in range(updates):
@@ -167,6 +181,7 @@ print(json.dumps({"config": "exploring PV-MCTS self-play (%d games per round, %d
                   "adam_t_policy": int(tr.opt.t), "adam_t_value": int(vt.opt.t), "playout_cap": playout_cap,
                   "root_noise": root_noise, "forced_playouts": forced_playouts, "gumbel": gumbel, "self_play_n_thr": sp_n_thr, "backup": backup, "selection": selection,
                   "solve_empties": solve_empties, "solved_targets": solved_targets,
+                  "td_lambda": td_lambda, "q_mix": q_mix,
                   **({"solved_rows_added": solved_rows[0]} if solved_targets else {}),
                   **({"arena_every": arena_every, "arena": arena_scores} if arena_every > 0 else {}),
                   **({"yardstick_every": yardstick_every, "yardstick_depth": yardstick_depth,
